@@ -14,18 +14,31 @@ N > 1: the SAME image is sharded by image-row slabs over the ranks (strong scali
 exchange steps are the small fp64 all-reduces of the Sinkhorn column sums, the Gram partials and
 V^T x (torch.distributed "nccl" == RCCL over xGMI).
 
-`value` is the HBM-resident figure (the bench contract: inputs already in HBM when the timed region starts).
-SURVEY.md section 8d's own metric -- wall time from the fp32 plane in HOST memory to the L per-layer planes back in
-HOST memory: H2D + train + apply + D2H, median of >= 5 runs after 2 warm-ups -- is measured in the same run and
-reported beside it as `host_to_host` (nle_train_host + nle_apply_layers_host on page-locked buffers; one upload, the
-download of a finished layer overlapped with the next one's kernels).
+`value` is the HBM-resident figure (the bench contract: inputs already in HBM when the timed region starts);
+`ms_per_step` the milliseconds of one timed step.  A plain run does only that: set up, `--warmup` steps, `--steps` timed
+steps, the outputs if `--dump-outputs DIR` is given, and the JSON line.
 
-The JSON line also carries
-  roofline      the dominant kernel of the timed region: algorithmic bytes (or flops) per launch
-                divided by its average launch duration, measured with HIP events recorded on the
-                stream the kernels run on (nle_ctx_profile), against the MI355X peak;
-  cpu_baseline  the fp64 numpy oracle (a port of the reference's algorithm) timed on this box's
-                host cores on a bounded sample (rank 0, N = 1 only).
+--dump-outputs DIR  after the timed steps, what the last timed step computed, as .npy files:
+                layers.npy   float32 (L, n) the L per-layer planes (this rank's pixels, row-major); a plane larger than
+                             the 64 MB budget is replaced by a fixed sample of its pixels (numpy default_rng(0), sorted,
+                             the same pixels on every layer), so that the file stays comparable between builds;
+                eigvals.npy  float64 (K,) the eigenvalues the trained filter kept.
+                N > 1: every rank writes its own `layers_rank<r>.npy`; rank 0 writes `eigvals.npy`.
+                The input plane is the seeded synthetic plane of the config: the same arguments give the same inputs.
+
+--full adds, in the same run, everything else the benchmark measures and checks (the options that tune these legs
+act only with --full):
+  kernels, roofline  per-kernel HIP-event times of the timed region (nle_ctx_profile, recorded on the stream the
+                kernels run on; the events cost the timed steps some stream gaps) and the dominant kernel's
+                algorithmic bytes (or flops) per launch divided by its average launch duration, against the MI355X peak;
+  host_to_host  SURVEY.md section 8d's own metric -- wall time from the fp32 plane in HOST memory to the L per-layer
+                planes back in HOST memory: H2D + train + apply + D2H, median of >= 5 runs after 2 warm-ups
+                (nle_train_host + nle_apply_layers_host on page-locked buffers; one upload, the download of a finished
+                layer overlapped with the next one's kernels), and its 8-bit forms;
+  soak, pipelined, affinity_pass  steps after the timed region, images in flight, the stand-alone affinity passes;
+  cpu_baseline  oracle/nle_cpu_baseline.cpp (a port of the reference's algorithm) timed on this box's host cores
+                (rank 0, N = 1 only);
+  N > 1: shard_check (the sharded output against a single-GPU run, before anything is timed) and replicas.
 """
 from __future__ import annotations
 
@@ -146,12 +159,36 @@ def kernel_symbols(form, lazy):
     return sym
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: payload of all files together, under 64 MB with the .npy headers
+
+
+def dump_outputs(path, out, eigvals, rank, world):
+    """--dump-outputs: this rank's L layer planes of the last timed step (float32; a fixed seeded sample of its pixels when
+    the planes exceed the budget) and the filter's eigenvalues (float64), as DIR/<name>.npy"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    L, n = out.shape
+    ev = np.ascontiguousarray(eigvals, dtype=np.float64)
+    keep = min(n, (DUMP_BYTES - ev.nbytes) // world // (4 * L))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        out = out.index_select(1, torch.as_tensor(idx, device=out.device))
+    np.save(os.path.join(path, "layers.npy" if world == 1 else f"layers_rank{rank}.npy"), out.float().cpu().numpy())
+    if rank == 0:
+        np.save(os.path.join(path, "eigvals.npy"), ev)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg4")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (per-kernel times and roofline, "
+                         "host-to-host, soak, images in flight, affinity passes, CPU baseline; N > 1: shard check, replicas)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (layers.npy, eigvals.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL; gloo for rehearsals)")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "torch"],
@@ -179,6 +216,8 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=768, help="side of the CPU-baseline sample image")
     ap.add_argument("--cpu-threads", type=int, default=16, help="BLAS threads for the CPU baseline (<= visible cores)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
 
@@ -309,7 +348,7 @@ def main():
     # N > 1: before anything is timed, this rank's rows of the sharded result against the same rows of an unsharded run on
     # this GPU (only the order of the fp64 sums differs between the two; the test suite's bar for that is 1e-6)
     shard_check = None
-    if world > 1:
+    if world > 1 and args.full:
         c1 = nle.Context(local_rank)
         c1.set_mode(args.mode)
         f1 = nle.NLEFilter(c1)
@@ -328,23 +367,28 @@ def main():
             print(f"[bench] rank {rank}: sharded output differs from the single-GPU result ({shard_check})", file=sys.stderr, flush=True)
             dist.destroy_process_group()
             sys.exit(4)
-    for c_, _, _ in lanes:
-        c_.profile(1)   # HIP events around the N-sized kernels of the timed region
+    if args.full:
+        for c_, _, _ in lanes:
+            c_.profile(1)   # HIP events around the N-sized kernels of the timed region
     fence()
     t0 = time.perf_counter()
     run_steps(args.steps)
     fence()
     elapsed = time.perf_counter() - t0
     stats = {}
-    for c_, _, _ in lanes:
-        for k_, (n_, ms_) in c_.kernel_stats().items():
-            a_ = stats.get(k_, (0, 0.0))
-            stats[k_] = (a_[0] + n_, a_[1] + ms_)
-        c_.profile(False)
+    if args.full:
+        for c_, _, _ in lanes:
+            for k_, (n_, ms_) in c_.kernel_stats().items():
+                a_ = stats.get(k_, (0, 0.0))
+                stats[k_] = (a_[0] + n_, a_[1] + ms_)
+            c_.profile(False)
     info = flt.info()
     stage_ms = flt.timings()
+    if args.dump_outputs:
+        _, f_last, out_last = lanes[(args.steps - 1) % len(lanes)]   # the lane that ran the last timed step
+        dump_outputs(args.dump_outputs, out_last, f_last.eigvals, rank, world)
     soak = None
-    if world == 1 and args.soak_seconds > 0 and args.simulate_world <= 1 and len(lanes) == 1:
+    if world == 1 and args.full and args.soak_seconds > 0 and args.simulate_world <= 1 and len(lanes) == 1:
         ts_, t_end = [], time.perf_counter() + args.soak_seconds
         while time.perf_counter() < t_end:
             t1_ = time.perf_counter()
@@ -365,7 +409,7 @@ def main():
 
     # ---- N > 1, second leg: replicas -- every rank filters its OWN image, no collective in the data path (weak scaling)
     replicas = None
-    if world > 1 and not args.no_replicas and args.simulate_world <= 1:
+    if world > 1 and args.full and not args.no_replicas and args.simulate_world <= 1:
         c_r = nle.Context(local_rank)
         c_r.set_mode(args.mode)
         f_r = nle.NLEFilter(c_r)
@@ -392,7 +436,7 @@ def main():
     # image's p-sized host algebra (W_A root, eig(Q): ~2.7 ms of the 7.5) runs under another image's kernels.  Reported
     # beside `value`, which stays the one-image-at-a-time figure.
     pipelined = None
-    if world == 1 and args.simulate_world <= 1 and args.inflight == 1 and not args.no_pipelined:
+    if world == 1 and args.full and args.simulate_world <= 1 and args.inflight == 1 and not args.no_pipelined:
         import threading
         pipelined = []
         for M in (2, 3):
@@ -432,7 +476,7 @@ def main():
     # ---- SURVEY.md section 8d's metric: host plane -> host layers, median of >= 5 runs after 2 warm-ups.  N > 1 (slab
     # input): every rank uploads its own rows and downloads its own rows of the layers, max over ranks per run
     h2h = None
-    if (world == 1 or slab_input) and args.simulate_world <= 1 and args.h2h_runs > 0:
+    if (world == 1 or slab_input) and args.full and args.simulate_world <= 1 and args.h2h_runs > 0:
         rows0, rows1 = nle.slab_rows(H, rank, world) if world > 1 else (0, H)
         h_lum = ctx.host_alloc((rows1 - rows0, W))
         h_lum[...] = synth.synthetic_luminance(H, W).astype(np.float32)[rows0:rows1]
@@ -510,67 +554,70 @@ def main():
                                "equals_the_fp32_input_path": bool(np.array_equal(h_u8b, h_u8))}
         f2.close()
 
-    # ---- roofline of the dominant kernel (this rank's launches)
+    # ---- roofline of the dominant kernel (this rank's launches; --full only: it needs the HIP events of the timed region)
     ran = {k for k, v in stats.items() if v[0] > 0}
     form = "materialised" if "nystrom_extend" in ran else ("phi_free_tables" if "gram_gemm" in ran else "phi_free_exp")
+    formulation = flt.diag()["formulation"]
     form_label = {1: "materialised_f32", 2: "phi_free_tables", 3: "phi_free_exp_f32", 4: "materialised_f64",
-                  5: "streamed_f64 (no N x r matrix: fp64 affinity rows regenerated chunk by chunk)"}.get(flt.diag()["formulation"], form)
-    lazy = form == "phi_free_tables" and "project" not in ran
-    gsum = form == "phi_free_tables" and gram_on_index_sums(g, W, cfg["hx"])
-    lev_t0, lev_nt = flt.level_tiles()
-    models = roofline_models(info, L, form, g, lazy, gsum, lev_nt)
-    # (the committed PMC summary was collected at N = 1 on the default config: per-launch bytes of a row slab or of
-    # another config differ, so `traffic` is only attached to that case)
-    traffic, traffic_file = load_traffic() if (world == 1 and args.config == "cfg4" and args.simulate_world <= 1) else ({}, None)
-    per_kernel = {}
-    for name, (launches, total_ms) in stats.items():
-        if launches == 0:
-            continue
-        avg_ms = total_ms / launches
-        rec = {"launches_per_step": launches / args.steps, "avg_ms": avg_ms, "total_ms_per_step": total_ms / args.steps}
-        if name in models:
-            bound, units, peak = models[name]
-            if bound == "hbm":
-                ach, unit = units / (avg_ms * 1e-3) / 1e9, "GB/s"
-            else:
-                ach, unit = units / (avg_ms * 1e-3) / 1e12, "TFLOP/s"
-            rec.update({"bound": bound, "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak})
-            if name == "sinkhorn_pass" and form != "materialised":
-                rec["hbm_equivalent_GBs"] = info["n_local"] * info["r"] * 4.0 / (avg_ms * 1e-3) / 1e9
-            if form == "phi_free_tables" and name in ("sinkhorn_pass", "apply_reduce", "gram_rows"):
-                # what bounds the level-sorted pixel kernels: fp64 multiply-adds on the vector pipe (2 nC per pixel
-                # for a pass + the reciprocal; for the Gram nC(nC+1)/2 + nC in the pair form, a recurrence step + an add per
-                # index-sum table otherwise) and nC LDS table reads per pixel
-                nc_ = g["n_sel_cols"]
-                fma = (2 * nc_ + 8) if name != "gram_rows" else ((2 * (2 * nc_ - 1) + 2) if gsum else (nc_ * (nc_ + 1) // 2 + nc_))
-                rec["valu_f64"] = {"achieved": 2.0 * fma * info["n_local"] / (avg_ms * 1e-3) / 1e12, "peak": FP64_MFMA_PEAK_TF,
-                                   "unit": "TFLOP/s (fp64 vector == matrix peak)",
-                                   "frac": 2.0 * fma * info["n_local"] / (avg_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF}
-            rec["traffic"] = None
-            for sym in kernel_symbols(form, lazy).get(name, ()):
-                hit = [v for k, v in traffic.items() if sym in k]
-                if hit:
-                    rec["traffic"] = hit[0]
-                    break
-        per_kernel[name] = rec
-    dom = max((k for k in per_kernel if "bound" in per_kernel[k]), key=lambda k: per_kernel[k]["total_ms_per_step"])
-    d = per_kernel[dom]
-    roofline = {"kernel": dom, "bound": d["bound"], "achieved": d["achieved"], "peak": d["peak"], "unit": d["unit"],
-                "frac": d["frac"], "traffic": d.get("traffic"), "avg_launch_ms": d["avg_ms"],
-                "launches_per_step": d["launches_per_step"],
-                "algorithmic_bytes_per_launch" if d["bound"] == "hbm" else "algorithmic_flops_per_launch": models[dom][1],
-                "traffic_source": (f"{traffic_file}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on an earlier "
-                                   "box, committed; NOT measured inside this run") if d.get("traffic") else None,
-                "level_tiles": {"first": lev_t0, "count": lev_nt, "of": 16}}
-    if "valu_f64" in d:
-        roofline["valu_f64"] = d["valu_f64"]
+                  5: "streamed_f64 (no N x r matrix: fp64 affinity rows regenerated chunk by chunk)"}.get(formulation, form)
+    lazy = form == "phi_free_tables" and "project" not in ran      # whether V stayed implicit: known from the events only
+    per_kernel, roofline = None, None
+    if args.full:
+        gsum = form == "phi_free_tables" and gram_on_index_sums(g, W, cfg["hx"])
+        lev_t0, lev_nt = flt.level_tiles()
+        models = roofline_models(info, L, form, g, lazy, gsum, lev_nt)
+        # (the committed PMC summary was collected at N = 1 on the default config: per-launch bytes of a row slab or of
+        # another config differ, so `traffic` is only attached to that case)
+        traffic, traffic_file = load_traffic() if (world == 1 and args.config == "cfg4" and args.simulate_world <= 1) else ({}, None)
+        per_kernel = {}
+        for name, (launches, total_ms) in stats.items():
+            if launches == 0:
+                continue
+            avg_ms = total_ms / launches
+            rec = {"launches_per_step": launches / args.steps, "avg_ms": avg_ms, "total_ms_per_step": total_ms / args.steps}
+            if name in models:
+                bound, units, peak = models[name]
+                if bound == "hbm":
+                    ach, unit = units / (avg_ms * 1e-3) / 1e9, "GB/s"
+                else:
+                    ach, unit = units / (avg_ms * 1e-3) / 1e12, "TFLOP/s"
+                rec.update({"bound": bound, "achieved": ach, "peak": peak, "unit": unit, "frac": ach / peak})
+                if name == "sinkhorn_pass" and form != "materialised":
+                    rec["hbm_equivalent_GBs"] = info["n_local"] * info["r"] * 4.0 / (avg_ms * 1e-3) / 1e9
+                if form == "phi_free_tables" and name in ("sinkhorn_pass", "apply_reduce", "gram_rows"):
+                    # what bounds the level-sorted pixel kernels: fp64 multiply-adds on the vector pipe (2 nC per pixel
+                    # for a pass + the reciprocal; for the Gram nC(nC+1)/2 + nC in the pair form, a recurrence step + an add per
+                    # index-sum table otherwise) and nC LDS table reads per pixel
+                    nc_ = g["n_sel_cols"]
+                    fma = (2 * nc_ + 8) if name != "gram_rows" else ((2 * (2 * nc_ - 1) + 2) if gsum else (nc_ * (nc_ + 1) // 2 + nc_))
+                    rec["valu_f64"] = {"achieved": 2.0 * fma * info["n_local"] / (avg_ms * 1e-3) / 1e12, "peak": FP64_MFMA_PEAK_TF,
+                                       "unit": "TFLOP/s (fp64 vector == matrix peak)",
+                                       "frac": 2.0 * fma * info["n_local"] / (avg_ms * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF}
+                rec["traffic"] = None
+                for sym in kernel_symbols(form, lazy).get(name, ()):
+                    hit = [v for k, v in traffic.items() if sym in k]
+                    if hit:
+                        rec["traffic"] = hit[0]
+                        break
+            per_kernel[name] = rec
+        dom = max((k for k in per_kernel if "bound" in per_kernel[k]), key=lambda k: per_kernel[k]["total_ms_per_step"])
+        d = per_kernel[dom]
+        roofline = {"kernel": dom, "bound": d["bound"], "achieved": d["achieved"], "peak": d["peak"], "unit": d["unit"],
+                    "frac": d["frac"], "traffic": d.get("traffic"), "avg_launch_ms": d["avg_ms"],
+                    "launches_per_step": d["launches_per_step"],
+                    "algorithmic_bytes_per_launch" if d["bound"] == "hbm" else "algorithmic_flops_per_launch": models[dom][1],
+                    "traffic_source": (f"{traffic_file}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on an earlier "
+                                       "box, committed; NOT measured inside this run") if d.get("traffic") else None,
+                    "level_tiles": {"first": lev_t0, "count": lev_nt, "of": 16}}
+        if "valu_f64" in d:
+            roofline["valu_f64"] = d["valu_f64"]
 
     # ---- the materialising affinity pass (north_star: ">= 40 % HBM-bandwidth roofline on the affinity pass"): the default
     # path never writes K_AB, so the kernels of the stage-level API / the literal formulations are timed here by
     # themselves, HIP events on the ctx's stream, in the same run.  k_affinity: fp32 rows, B_A = N s (1 + p) (SURVEY.md
     # section 8d); k_affinity64: the fp64 rows of NLE_MODE_STREAMED_F64 (libm exp), one 2 GB chunk as that mode makes them
     affinity_pass = None
-    if world == 1 and args.simulate_world <= 1 and not args.no_affinity:
+    if world == 1 and args.full and args.simulate_world <= 1 and not args.no_affinity:
         affinity_pass = {}
         ldp = nle.ld(p)
         free_b, _ = torch.cuda.mem_get_info()
@@ -598,7 +645,7 @@ def main():
     # the run is estimated to fit the budget, else on a bounded sample of the same workload; and on ONE thread (the
     # reference is single threaded: Eigen without OpenMP, CMakeLists.txt:40-46) on a bounded sample
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import subprocess
         exe = entry.cpu_baseline_binary()
         try:
@@ -660,8 +707,11 @@ def main():
                        "formulation": form_label + (" (V implicit, apply in sample space)" if lazy else ""),
                        "storage": ("fp64 tables, histograms, reductions and MFMA; fp32 output planes; V implicit" if lazy else
                                    "fp64 affinities, Phi / chunks, V, reductions and MFMA; fp32 output planes"
-                                   if flt.diag()["formulation"] in (4, 5) else
+                                   if formulation in (4, 5) else
+                                   "fp64 tables, histograms, reductions and MFMA; fp32 output planes"
+                                   if formulation == 2 and not args.full else
                                    "fp64 reductions and Gram/projection MFMA; fp32 affinities, V and outputs")},
+            "full": bool(args.full),
             "host_to_host": h2h,
             "slab_input": bool(slab_input),
             "pipelined": pipelined,

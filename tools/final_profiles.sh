@@ -1,20 +1,22 @@
 #!/bin/bash
 # usage (on the GPU box, one part per gpurun call: each takes 5-15 min):
 #   bash tools/final_profiles.sh <round tag, e.g. r4> bench|prof4|prof35|extra
-# bench : the default driver line (cfg4) and the cfg3 / cfg5 lines            -> gpurun_out/<tag>_{final,cfg3,cfg5}_bench.json
+# bench : the full bench line (bench.py --full) of cfg4, cfg3, cfg5 and cfg2 -> $DEST/<tag>_{final,cfg3,cfg5,cfg2}_bench.json
+#         (DEST defaults to bench_out/ in the repository, which git ignores)
 # prof4 : rocprofv3 kernel stats + FETCH_SIZE / WRITE_SIZE passes of cfg4 (incl. the stand-alone affinity legs) -> gpurun_out/prof_<tag>_final
 # prof35: the same for cfg3 and cfg5                                           -> gpurun_out/prof_<tag>_cfg3, _cfg5
 # extra : materialised-mode profiles, timelines, dense-solver timing, determinism, soak
 set -o pipefail
-TAG=${1:-r4}; PART=${2:-bench}
+TAG=${1:-r4}; PART=${2:-bench}; DEST=${DEST:-bench_out}
 cd $GRAFT_REPO_ROOT
 case $PART in
 bench)
-  python3 bench.py > gpurun_out/${TAG}_final_bench.json 2> gpurun_out/${TAG}_final_bench.err || { tail -5 gpurun_out/${TAG}_final_bench.err; exit 1; }
+  mkdir -p $DEST
+  python3 bench.py --full > $DEST/${TAG}_final_bench.json 2> $DEST/${TAG}_final_bench.err || { tail -5 $DEST/${TAG}_final_bench.err; exit 1; }
   echo "bench cfg4 done"
-  python3 bench.py --config cfg3 --no-cpu-baseline > gpurun_out/${TAG}_cfg3_bench.json 2>/dev/null && echo "bench cfg3 done"
-  python3 bench.py --config cfg5 --no-cpu-baseline > gpurun_out/${TAG}_cfg5_bench.json 2>/dev/null && echo "bench cfg5 done"
-  python3 bench.py --config cfg2 --no-cpu-baseline > gpurun_out/${TAG}_cfg2_bench.json 2>/dev/null && echo "bench cfg2 done"
+  python3 bench.py --full --config cfg3 --no-cpu-baseline > $DEST/${TAG}_cfg3_bench.json 2>/dev/null && echo "bench cfg3 done"
+  python3 bench.py --full --config cfg5 --no-cpu-baseline > $DEST/${TAG}_cfg5_bench.json 2>/dev/null && echo "bench cfg5 done"
+  python3 bench.py --full --config cfg2 --no-cpu-baseline > $DEST/${TAG}_cfg2_bench.json 2>/dev/null && echo "bench cfg2 done"
   ;;
 prof4)
   bash tools/prof.sh ${TAG}_final > gpurun_out/prof_${TAG}_final.log 2>&1 && echo "prof final done"
