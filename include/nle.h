@@ -96,6 +96,19 @@ int nle_dev_download(nle_ctx* ctx, void* h_dst, const void* d_src, size_t bytes)
  *                          grid with <= 2048 samples, any K: what auto mode takes when Phi would not fit the device. */
 #define NLE_MODE_STREAMED_F64 5
 int nle_ctx_set_mode(nle_ctx* ctx, int mode);
+/* Patch (non-local-means) affinities, opt-in (new in this build: the reference compares single pixel values,
+ * src/filter.cpp:94-112).  With radius R > 0 the intensity term of every affinity, K_A and K_AB alike, compares the
+ * (2R + 1)^2 neighbourhoods of the two pixels (reflect-101 borders, OpenCV BORDER_DEFAULT):
+ *   S_ij = sum_{dy,dx in [-R, R]} (y[rho(r+dy), rho(c+dx)] - y[rho(rs+dy), rho(cs+dx)])^2    (an exact integer)
+ *   K_ij = exp(-(1/hx^2) (double)((r-rs)^2 + (c-cs)^2) - ((1/hy^2) / (2R+1)^2) (double)S_ij)
+ * so hy keeps its meaning (an intensity difference per pixel); R = 0 (default) is the reference's kernel bit for bit and
+ * leaves every code path unchanged.  Every later stage is the reference's.  R > 0 applies to nle_train* and
+ * nle_compute_kernel64 and needs an integer-valued plane in [0, 255] (the L channel of 8-bit Lab), R <= min(H, W) - 1,
+ * NLE_MODE_AUTO (which then takes NLE_MODE_MATERIALISED_F64, or NLE_MODE_STREAMED_F64 by the memory rule),
+ * NLE_MODE_MATERIALISED_F64 or NLE_MODE_STREAMED_F64, and full-plane input at world > 1 (no slab input); anything else,
+ * nle_compute_kernel and nle_nystrom included, returns NLE_ERR_INVALID.  0 <= radius <= NLE_PATCH_RADIUS_MAX. */
+#define NLE_PATCH_RADIUS_MAX 7
+int nle_ctx_set_patch_radius(nle_ctx* ctx, int radius);
 /* The Nystrom-extension GEMM Phi = K_AB^T (V_A Lambda^-1) (src/filter.cpp:275) of NLE_MODE_MATERIALISED and of nle_nystrom on
  * the bf16 matrix cores with SPLIT operands (each fp32 value as three bf16, six products, fp32 accumulate: fp32 accuracy at
  * ~2.7x the exact-fp32 MFMA's rate; plain bf16 operands miss the parity bar).  Off by default. */

@@ -202,6 +202,9 @@ public:
     // nle_filter_diag: {formulation, p, rank Ka, rank Wa, rank Q, K', chol(Ka), chol(Wa)}
     void diag(int info[8]) const;
     bool verbose = true;                 // the reference's stdout stage banners (:483-498,506)
+    // patch (non-local-means) affinities over (2 patchRadius + 1)^2 neighbourhoods for trainForEnhancement /
+    // trainForDenoise / trainFilter (nle_ctx_set_patch_radius; new here, 0 = the reference's single-value affinity)
+    int patchRadius = 0;
 
 private:
     nle_ctx* ctx_ = nullptr;

@@ -292,6 +292,11 @@ class Context:
         """0 auto, 1 materialised Phi, 2 Phi-free (NLE_MODE_* in include/nle.h)."""
         _check(lib().nle_ctx_set_mode(self._h, int(mode)), self._h)
 
+    def set_patch_radius(self, radius: int):
+        """patch (non-local-means) affinities over (2R + 1)^2 neighbourhoods, 0 <= R <= NLE_PATCH_RADIUS_MAX; 0 (default) is
+        the reference's single-value affinity (nle_ctx_set_patch_radius)"""
+        _check(lib().nle_ctx_set_patch_radius(self._h, int(radius)), self._h)
+
     def set_nystrom_bf16x3(self, on: bool = True):
         """the fused Nystrom GEMM on the bf16 matrix cores with split operands (nle_ctx_set_nystrom_bf16x3)"""
         _check(lib().nle_ctx_set_nystrom_bf16x3(self._h, 1 if on else 0), self._h)

@@ -313,6 +313,16 @@ int nle_ctx_set_nystrom_bf16x3(nle_ctx* ctx, int on) {
     return NLE_OK;
 }
 
+int nle_ctx_set_patch_radius(nle_ctx* ctx, int radius) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (radius < 0 || radius > NLE_PATCH_RADIUS_MAX)
+            throw Fail{NLE_ERR_INVALID, "patch radius must be in [0, " + std::to_string(NLE_PATCH_RADIUS_MAX) + "], got " +
+                                            std::to_string(radius)};
+        ctx->patch_radius = radius;
+    });
+}
+
 int nle_ctx_set_mode(nle_ctx* ctx, int mode) {
     if (!ctx || mode < 0 || mode > NLE_MODE_STREAMED_F64) return NLE_ERR_INVALID;
     ctx->mode = mode;

@@ -143,6 +143,17 @@ hipError_t sink_hist(hipStream_t s, int mode, const float* d_lum, GridSpec gs, i
 // ---- the literal decomposition in fp64 (generic64.hip): auto mode's fallback and the stage-level API
 hipError_t affinity64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, int ld, double sw,
                       double pw, long long pix0, long long M, double* d_kab, bool skip_samples = false);
+// patch (non-local-means) affinity rows, patch.hip: the rows affinity64 fills, with the intensity term pwd * S_ij, S_ij the
+// integer sum of squared differences of the (2R + 1)^2 patches (reflect-101 borders), 1 <= R <= 7, plane integer in [0, 255].
+// d_spatch: patch_spatch_bytes(p, R) bytes, sample j's patch values - 128 as int8 in row j (patch_kpad(R) bytes, zero
+// padded; rows p .. roundup16(p) zero); d_snorm[j] = sum of the squares of those int8 values.
+int patch_kpad(int R);
+size_t patch_spatch_bytes(int p, int R);
+// d_out (n x (2R + 1)^2 ints): the patch values around pixels d_pix[0 .. n) of the full plane
+hipError_t patch_gather(hipStream_t s, const float* d_lum, int H, int W, int R, const long long* d_pix, int n, int* d_out);
+hipError_t patch_affinity64(hipStream_t s, const float* d_lum, GridSpec gs, int R, const Sample4* d_samples,
+                            const signed char* d_spatch, const int* d_snorm, int p, int ld, double sw, double pwd,
+                            long long pix0, long long M, double* d_kab, bool skip_samples = false);
 hipError_t add64(hipStream_t s, double* d_y, const double* d_x, size_t n);  // y += x
 hipError_t row_scalings64(hipStream_t s, const double* d_X, long long M, int ld, int r, const double* d_u, double eps,
                           double* d_out);

@@ -17,12 +17,15 @@ struct SampleSet {
     std::vector<float4> packed;     // {row, col, lum, 0}
     bool quantised = false;         // whole plane integer valued in [0, 255] (checked on request)
     unsigned level_tiles = 0xffffu; // then: which 16-level tiles occur in this rank's part of the plane (bit t)
+    int R = 0;                      // patch radius (nle_ctx_set_patch_radius)
+    std::vector<int> patch;         // R > 0: p x (2R + 1)^2 patch values around each sample (reflect-101), row per sample
 };
 
 // d_lum: base of the FULL plane -- real, or virtual when the ctx takes slab input (only rows [row0, row1) of this rank
-// exist; the p sample values and the "integer valued" verdict are then completed by an all-reduce)
+// exist; the p sample values and the "integer valued" verdict are then completed by an all-reduce).  R > 0: also the
+// samples' patches (full plane only: the caller refuses slab input)
 SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool check_quantised = false,
-                        bool slab_plane = false) {
+                        bool slab_plane = false, int R = 0) {
     SampleSet s;
     s.gs = gs;
     s.p = gs.p();
@@ -71,11 +74,90 @@ SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool
         s.pix[k] = (long long)r * gs.W + cc;
         s.packed[k] = make_float4((float)r, (float)cc, s.val[k], 0.f);
     }
+    if (R > 0) {
+        const int d = (2 * R + 1) * (2 * R + 1);
+        s.R = R;
+        s.patch.resize((size_t)s.p * d);
+        DevBuf<long long> d_pix(s.p);
+        DevBuf<int> d_patch(s.patch.size());
+        HIP_OK(hipMemcpyAsync(d_pix.p, s.pix.data(), s.p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+        PROFILED(c, NLE_K_SMALL, nlek::patch_gather(c->stream, d_lum, gs.H, gs.W, R, d_pix.p, s.p, d_patch.p));
+        HIP_OK(hipMemcpyAsync(s.patch.data(), d_patch.p, s.patch.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
     return s;
+}
+
+// The checks of a patch radius R > 0 that need no device (nle_ctx_set_patch_radius has checked 0 <= R <= 7)
+void check_patch_radius(const nle_ctx* c, int R, int H, int W) {
+    if (R <= 0) return;
+    if (R > std::min(H, W) - 1)
+        throw Fail{NLE_ERR_INVALID, "patch radius " + std::to_string(R) + " needs an image of at least " + std::to_string(R + 1) +
+                                        " x " + std::to_string(R + 1) + " pixels (R <= min(H, W) - 1)"};
+    if (c->slab_input && c->world > 1)
+        throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need the full plane on every rank: slab input is not "
+                                    "supported with them"};
+}
+
+// Ka with patch affinities: S in exact integer arithmetic, the exponent in k_patch_affinity64's order (patch.hip)
+std::vector<double> build_Ka_patch(const SampleSet& s, double hx, double hy) {
+    const int p = s.p, d = (2 * s.R + 1) * (2 * s.R + 1);
+    const double sw = 1.0 / (hx * hx), pwd = (1.0 / (hy * hy)) / d;
+    std::vector<double> Ka((size_t)p * p);
+    for (int j = 0; j < p; ++j) {
+        const int rj = (int)(s.pix[j] / s.gs.W), cj = (int)(s.pix[j] % s.gs.W);
+        const int* yj = s.patch.data() + (size_t)j * d;
+        for (int i = j; i < p; ++i) {
+            const int ri = (int)(s.pix[i] / s.gs.W), ci = (int)(s.pix[i] % s.gs.W);
+            const int* yi = s.patch.data() + (size_t)i * d;
+            long long S = 0;
+            for (int k = 0; k < d; ++k) S += (long long)(yi[k] - yj[k]) * (yi[k] - yj[k]);
+            const long long dr = ri - rj, dc = ci - cj;
+            const double v = std::exp(-sw * (double)(dr * dr + dc * dc) - pwd * (double)S);
+            Ka[(size_t)j * p + i] = v;
+            Ka[(size_t)i * p + j] = v;
+        }
+    }
+    return Ka;
+}
+
+// The B operand of k_patch_affinity64: the sample patches shifted by -128 as int8 (zero padded), and their norms
+struct PatchOperands {
+    DevBuf<signed char> spatch;
+    DevBuf<int> snorm;
+};
+void upload_patch_operands(nle_ctx* c, const SampleSet& s, PatchOperands* po) {
+    if (s.R <= 0) return;
+    const int d = (2 * s.R + 1) * (2 * s.R + 1), kp = nlek::patch_kpad(s.R);
+    std::vector<signed char> bytes(nlek::patch_spatch_bytes(s.p, s.R), 0);
+    std::vector<int> norm(s.p, 0);
+    for (int j = 0; j < s.p; ++j)
+        for (int k = 0; k < d; ++k) {
+            const int v = s.patch[(size_t)j * d + k] - 128;
+            bytes[(size_t)j * kp + k] = (signed char)v;
+            norm[j] += v * v;
+        }
+    po->spatch.alloc(bytes.size());
+    po->snorm.alloc(s.p);
+    HIP_OK(hipMemcpyAsync(po->spatch.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(po->snorm.p, norm.data(), norm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));  // host staging vectors go out of scope
+}
+
+// fp64 affinity rows [pix0, pix0 + M) (natural order, ld columns): k_affinity64, or the patch kernel when R > 0
+hipError_t affinity_rows64(hipStream_t st, const float* d_lum, const SampleSet& ss, const float4* d_samples,
+                           const PatchOperands& po, int ld, double hx, double hy, long long pix0, long long M, double* d_kab,
+                           bool skip_samples = false) {
+    const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
+    if (ss.R <= 0) return nlek::affinity64(st, d_lum, ss.gs, d_samples, ss.p, ld, sw, pw, pix0, M, d_kab, skip_samples);
+    const double pwd = pw / ((2 * ss.R + 1) * (2 * ss.R + 1));
+    return nlek::patch_affinity64(st, d_lum, ss.gs, ss.R, d_samples, po.spatch.p, po.snorm.p, ss.p, ld, sw, pwd, pix0, M, d_kab,
+                                  skip_samples);
 }
 
 // Ka(i,j), reference src/filter.cpp:128-137,144 (fp64, integer spatial term)
 std::vector<double> build_Ka(const SampleSet& s, double hx, double hy) {
+    if (s.R > 0) return build_Ka_patch(s, hx, hy);
     const int p = s.p;
     const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
     std::vector<double> Ka((size_t)p * p);
@@ -422,13 +504,14 @@ void build_phi64(nle_ctx* c, const float* d_lum, const SampleSet& ss, const Nyst
     HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     DevBuf<double> d_B(ny.B.size());  // p x r column-major = what ts_gemm64 takes
     HIP_OK(hipMemcpyAsync(d_B.p, ny.B.data(), ny.B.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    PatchOperands po;
+    upload_patch_operands(c, ss, &po);
     HIP_OK(hipMemsetAsync(d_phi, 0, (size_t)std::max<long long>(M, 1) * ldr * sizeof(double), c->stream));
     const long long chunk = 1ll << 20;  // affinity rows of 1 Mi pixels at a time (K_AB is never held whole)
     DevBuf<double> d_kab((size_t)std::min<long long>(std::max<long long>(M, 1), chunk) * ldp);
     for (long long i0 = 0; i0 < M; i0 += chunk) {
         const long long m = std::min(chunk, M - i0);
-        PROFILED(c, NLE_K_AFFINITY, nlek::affinity64(c->stream, d_lum, ss.gs, d_samples.p, p, ldp, 1.0 / (hx * hx),
-                                                     1.0 / (hy * hy), pix0 + i0, m, d_kab.p));
+        PROFILED(c, NLE_K_AFFINITY, affinity_rows64(c->stream, d_lum, ss, d_samples.p, po, ldp, hx, hy, pix0 + i0, m, d_kab.p));
         PROFILED(c, NLE_K_NYSTROM, nlek::ts_gemm64(c->stream, d_kab.p, m, ldp, p, d_B.p, r, nullptr, d_phi + (size_t)i0 * ldr, ldr));
     }
     std::vector<double> rows;
@@ -859,7 +942,6 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
 void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss, const std::function<Nystrom()>& solve,
                     double hx, double hy, int T, int n_eig, long long pix0, long long M, StageMs* ms) {
     const int p = ss.p, ld = ld4(p);
-    const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
     hipStream_t st = c->stream;
     Trace tr;
     Timer tm_s(st), tm_g(st), tm_p(st);
@@ -870,6 +952,8 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
     const long long CH = std::max<long long>(256, std::min<long long>(std::max<long long>(M, 1), rows_fit));
     DevBuf<float4> d_samples(p);
     HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, st));
+    PatchOperands po;
+    upload_patch_operands(c, ss, &po);
     DevBuf<double> d_K((size_t)CH * ld), d_partial((size_t)nlek::kRowpassMaxBlocks * ld), d_zc(ld), d_z(ld), d_w(ld), d_ones(ld),
         d_sAh((size_t)2 * T * p), d_X1, d_X2, d_lam, d_uv((size_t)3 * p), d_cbuf((size_t)std::max<long long>(M, 1));
     HIP_OK(hipMemsetAsync(d_w.p, 0, ld * sizeof(double), st));
@@ -877,7 +961,7 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
     tr.mark("s64: alloc+upload");
     auto chunk_rows = [&](long long i0) { return std::min<long long>(CH, M - i0); };
     auto gen = [&](long long i0, long long mc) {
-        PROFILED(c, NLE_K_AFFINITY, nlek::affinity64(st, d_lum, ss.gs, d_samples.p, p, ld, sw, pw, pix0 + i0, mc, d_K.p, true));
+        PROFILED(c, NLE_K_AFFINITY, affinity_rows64(st, d_lum, ss, d_samples.p, po, ld, hx, hy, pix0 + i0, mc, d_K.p, true));
     };
     auto pass_pixels = [&](int mode, double* cbuf) {
         HIP_OK(hipMemsetAsync(d_z.p, 0, ld * sizeof(double), st));
@@ -1093,10 +1177,17 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         throw Fail{NLE_ERR_INVALID, "Phi-free path without tables supports at most 256 samples and 128 eigenvectors"};
     if (c->mode == 2 && !generic_ok && !tables_ok)
         throw Fail{NLE_ERR_INVALID, "Phi-free path supports at most 128 eigenvectors and a 32 x 36 sample grid"};
+    // patch affinities (R > 0): the fp64 formulations with explicit affinity rows only (the table, Phi-free and fp32 forms
+    // cannot express them); every check here is decided the same way on every rank
+    const int R = c->patch_radius;
+    if (R > 0 && c->mode != NLE_MODE_AUTO && c->mode != NLE_MODE_MATERIALISED_F64 && c->mode != NLE_MODE_STREAMED_F64)
+        throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) run in NLE_MODE_AUTO, NLE_MODE_MATERIALISED_F64 or "
+                                    "NLE_MODE_STREAMED_F64 only"};
+    check_patch_radius(c, R, H, W);
     // auto: the table form (all fp64) whenever it applies, else the literal decomposition in fp64 (generic64.hip).  The
     // fp32 formulations (materialised Phi, Phi-free with fp32 affinities) run only when asked for by mode: they miss
     // the 1e-4 bar on some well-posed inputs (DESIGN.md "Numerics").
-    const bool want_fuse = c->mode == 2 || c->mode == 3 || (c->mode == 0 && tables_ok);
+    const bool want_fuse = R == 0 && (c->mode == 2 || c->mode == 3 || (c->mode == 0 && tables_ok));
     HIP_OK(hipSetDevice(c->device));
 
     auto f = new nle_filter();
@@ -1115,8 +1206,11 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         // --- sample set, Ka and its eigenpairs (:486-491, host fp64)
         Timer tm_a(c->stream);
         tm_a.start();
-        SampleSet ss = fetch_samples(c, d_lum, gs, want_fuse && tables_ok, c->slab_input && c->world > 1);
-        const bool fuse = c->mode == 0 ? (tables_ok && ss.quantised)
+        SampleSet ss = fetch_samples(c, d_lum, gs, (want_fuse && tables_ok) || R > 0, c->slab_input && c->world > 1, R);
+        if (R > 0 && ranks_where(c, !ss.quantised) > 0)  // refused on every rank if the plane is not integer valued on one
+            throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
+                                        "(the L channel of 8-bit Lab)"};
+        const bool fuse = c->mode == 0 ? (want_fuse && tables_ok && ss.quantised)
                                        : (want_fuse && (generic_ok || (tables_ok && ss.quantised)));
         if (c->mode == 2 && !fuse)
             throw Fail{NLE_ERR_INVALID, "Phi-free path: more than 256 samples needs an integer-valued luminance plane"};
@@ -1247,6 +1341,8 @@ int nle_compute_kernel(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
             throw Fail{NLE_ERR_INVALID, "Number of samples per row and col must be <= that of image."};
         GridSpec gs;
         if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
+        if (ctx->patch_radius > 0)
+            throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) does not take patch affinities: use nle_compute_kernel64"};
         HIP_OK(hipSetDevice(ctx->device));
         SampleSet ss = fetch_samples(ctx, d_lum, gs);
         if (h_Ka) {
@@ -1276,6 +1372,8 @@ int nle_nystrom(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_sample
             throw Fail{NLE_ERR_INVALID, "Number of samples per row and col must be <= that of image."};
         GridSpec gs;
         if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
+        if (ctx->patch_radius > 0)
+            throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) does not take patch affinities: use the fp64 formulations"};
         HIP_OK(hipSetDevice(ctx->device));
         SampleSet ss = fetch_samples(ctx, d_lum, gs);
         std::vector<double> Ka = build_Ka(ss, hx, hy);
@@ -1356,8 +1454,13 @@ int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
             throw Fail{NLE_ERR_INVALID, "Number of samples per row and col must be <= that of image."};
         GridSpec gs;
         if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
+        const int R = ctx->patch_radius;
+        check_patch_radius(ctx, R, H, W);
         HIP_OK(hipSetDevice(ctx->device));
-        SampleSet ss = fetch_samples(ctx, d_lum, gs);
+        SampleSet ss = fetch_samples(ctx, d_lum, gs, R > 0, false, R);
+        if (R > 0 && !ss.quantised)
+            throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
+                                        "(the L channel of 8-bit Lab)"};
         if (h_Ka) {
             std::vector<double> Ka = build_Ka(ss, hx, hy);
             std::copy(Ka.begin(), Ka.end(), h_Ka);
@@ -1367,9 +1470,11 @@ int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
             slab(H, ctx->rank, ctx->world, &row0, &row1);
             DevBuf<float4> d_samples(ss.p);
             HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), ss.p * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+            PatchOperands po;
+            upload_patch_operands(ctx, ss, &po);
             PROFILED(ctx, NLE_K_AFFINITY,
-                     nlek::affinity64(ctx->stream, d_lum, gs, d_samples.p, ss.p, ld4(ss.p), 1.0 / (hx * hx), 1.0 / (hy * hy),
-                                      (long long)row0 * W, (long long)(row1 - row0) * W, d_kab));
+                     affinity_rows64(ctx->stream, d_lum, ss, d_samples.p, po, ld4(ss.p), hx, hy, (long long)row0 * W,
+                                     (long long)(row1 - row0) * W, d_kab));
             HIP_OK(hipStreamSynchronize(ctx->stream));
             prof_flush(ctx);
         }

@@ -14,6 +14,7 @@ int main(int argc, char* argv[]) {
     const nle::Image image = nlecli::load(a);
     if (image.empty()) return 0;                        // src/denoise.cpp:33-36
     nle::NLEFilter filter;
+    filter.patchRadius = a.patchRadius;
     filter.trainForDenoise(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors, sigmaColor,
                            sigmaSpace);
     const nle::Image result = filter.denoise(image, shrinkFactor, sigmaColor, sigmaSpace);
