@@ -703,7 +703,7 @@ hipError_t project64(hipStream_t s, const float* d_lum, GridSpec gs, const Sampl
         }
         const int p4 = (p + 3) & ~3;
         const size_t shm = (size_t)p4 * project64_res_ldb(nt_r, rem) * sizeof(double) + (size_t)p4 * sizeof(Sample4);
-        if (nt_r <= 4 && shm <= 150 * 1024 && std::getenv("NLE_PROJECT_CHUNKED") == nullptr) {
+        if (nt_r <= 4 && shm <= 150 * 1024) {
 #define NLE_PR(NTV, REMV) \
     if (nt_r == NTV && rem == REMV) \
         return launch_project64_res<NTV, 16, REMV>(s, M, d_lum, gs, d_samples, p, nsw, npw, pix0, d_D, ldd, d_c, d_V, ldv);
@@ -753,8 +753,6 @@ hipError_t project64(hipStream_t s, const float* d_lum, GridSpec gs, const Sampl
 namespace {
 constexpr int kLevels = 256;
 }
-
-int sink_hist_max_cols() { return 36; }  // 2 * 256 * nC doubles of LDS
 
 // ---- wave-level pre-reduction for the LDS histograms
 // Flat image regions put many lanes of a wave on ONE histogram level, and same-address LDS atomics
@@ -887,97 +885,9 @@ hipError_t hist_tables(hipStream_t s, GridSpec gs, const Sample4* d_samples, int
     return hipGetLastError();
 }
 
-// one workgroup per local image row; partial: [nrows_local][ldp] doubles
-__global__ __launch_bounds__(256) void k_sink_hist(int mode, const float* __restrict__ lum, GridSpec gs, int p,
-                                                   int ldp, int row0, const double* __restrict__ er,
-                                                   const double* __restrict__ ecT, const double* __restrict__ Ep,
-                                                   const double* __restrict__ w, double eps,
-                                                   double* __restrict__ ybuf, double* __restrict__ partial) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int nC = gs.nSelCols, nR = gs.nSelRows, W = gs.W;
-    double* g = reinterpret_cast<double*>(smem_raw);  // [256][nC]
-    double* h = g + kLevels * nC;                      // [256][nC]
-    double* ew = h + kLevels * nC;                     // [p]   er[r][a] * w[a,b]
-    const int tid = threadIdx.x;
-    const int lrow = blockIdx.x, r = row0 + lrow;
-    const double* er_r = er + (size_t)lrow * nR;
-    for (int i = tid; i < kLevels * nC; i += 256) h[i] = 0.0;
-    if (mode != ROWPASS_COLSUM) {
-        for (int sidx = tid; sidx < p; sidx += 256) ew[sidx] = er_r[sidx / nC] * w[sidx];
-        __syncthreads();
-        for (int i = tid; i < kLevels * nC; i += 256) {
-            const int x = i / nC, b = i - x * nC;
-            const double* ep = Ep + (size_t)x * p + b;
-            double s0 = 0.0, s1 = 0.0;
-            int a = 0;
-            for (; a + 1 < nR; a += 2) {
-                s0 += ew[a * nC + b] * ep[a * nC];
-                s1 += ew[(a + 1) * nC + b] * ep[(a + 1) * nC];
-            }
-            if (a < nR) s0 += ew[a * nC + b] * ep[a * nC];
-            g[i] = s0 + s1;
-        }
-    }
-    __syncthreads();
-    // is this image row a sample row?
-    const int dr = r - gs.rowOff;
-    const bool sample_row = dr >= 0 && (dr % gs.rowStep) == 0 && (dr / gs.rowStep) < nR;
-    for (int c = tid; c < W; c += 256) {
-        const size_t gi = (size_t)r * W + c;
-        const int x = (int)lum[gi];
-        bool smp = false;
-        if (sample_row) {
-            const int dc = c - gs.colOff;
-            smp = dc >= 0 && (dc % gs.colStep) == 0 && (dc / gs.colStep) < nC;
-        }
-        double y = 1.0;
-        if (mode != ROWPASS_COLSUM) {
-            double s0 = 0.0, s1 = 0.0;
-            int b = 0;
-            for (; b + 1 < nC; b += 2) {
-                s0 += ecT[(size_t)b * W + c] * g[x * nC + b];
-                s1 += ecT[(size_t)(b + 1) * W + c] * g[x * nC + b + 1];
-            }
-            if (b < nC) s0 += ecT[(size_t)b * W + c] * g[x * nC + b];
-            y = recip_or_zero_d(s0 + s1, eps);
-        }
-        if (smp) y = 0.0;
-        if (ybuf != nullptr) ybuf[(size_t)lrow * W + c] = y;
-        if (y != 0.0)
-            for (int b = 0; b < nC; ++b) atomicAdd(&h[x * nC + b], ecT[(size_t)b * W + c] * y);
-    }
-    __syncthreads();
-    for (int sidx = tid; sidx < ldp; sidx += 256) {
-        double out = 0.0;
-        if (sidx < p) {
-            const int a = sidx / nC, b = sidx - a * nC;
-            double s0 = 0.0, s1 = 0.0;
-            for (int x = 0; x < kLevels; x += 2) {
-                s0 += Ep[(size_t)x * p + sidx] * h[x * nC + b];
-                s1 += Ep[(size_t)(x + 1) * p + sidx] * h[(x + 1) * nC + b];
-            }
-            out = er_r[a] * (s0 + s1);
-        }
-        partial[(size_t)lrow * ldp + sidx] = out;
-    }
-}
-
-hipError_t sink_hist(hipStream_t s, int mode, const float* d_lum, GridSpec gs, int p, int ldp, int row0,
-                     int nrows_local, const double* d_er, const double* d_ecT, const double* d_Ep,
-                     const double* d_w, double eps, double* d_ybuf, double* d_partial) {
-    if (nrows_local <= 0) return hipSuccess;
-    const size_t shm = ((size_t)2 * kLevels * gs.nSelCols + p) * sizeof(double);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sink_hist),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sink_hist, dim3((unsigned)nrows_local), dim3(256), shm, s, mode, d_lum, gs, p, ldp, row0, d_er,
-                       d_ecT, d_Ep, d_w, eps, d_ybuf, d_partial);
-    return hipGetLastError();
-}
-
 // -------------------------------------------------------------------- tiled form of the table pass
-// k_sink_hist re-reads the whole Ep table (256 x p doubles) twice per image row from L2, which is
-// what bounds it.  The tiled form splits the pass into three kernels so that Ep is read ~once:
+// As one kernel with a workgroup per image row, the pass re-reads the whole Ep table (256 x p doubles) twice per row
+// from L2, which is what bounds it.  The tiled form splits the pass into three kernels so that Ep is read ~once:
 //   k_hist_g   : g[r][b,x] = sum_a er[r][a] w[a,b] Ep[x][a,b]   (fp64 MFMA; table columns are b-major)
 //   k_hist_pix : per image row: d_i, y_i, h[r][x,b] += ec y      (g row and h row in LDS)
 //   k_hist_hh  : HH[slab][x,b][a] = sum_{r in slab} er[r][a] h[r][x,b]
@@ -1423,7 +1333,12 @@ int apply_layers_per_launch(GridSpec gs) {
     return (int)std::max<size_t>(1, std::min<size_t>(kDotLayers, (size_t)(144 * 1024) / table));
 }
 
-// expand half of the sample-space apply for `nl` <= apply_layers_per_launch layers: the g tables from the w' vectors
+// whether apply_hist_layers expands on the level-sorted rows (sorted_expand) rather than with k_hist_dot
+bool use_sorted_expand(GridSpec gs, const SortedRows* sorted) {
+    return sorted != nullptr && gs.nSelCols <= sorted_expand_max_cols() && gs.W <= sorted_expand_max_width();
+}
+
+// expand half of the sample-space apply for `nl` <= apply_layers_per_launch layers (sorted_expand_layers on the sorted rows): the g tables from the w' vectors
 // (d_wl: nl vectors, stride ldw), then one dot kernel; d_ws: nl * nrows_local * 256 nC doubles;
 // d_out: layer l at d_out + l * ostride
 hipError_t apply_hist_layers(hipStream_t s, const float* d_lum, GridSpec gs, int p, int row0, int nrows_local,
@@ -1432,8 +1347,7 @@ hipError_t apply_hist_layers(hipStream_t s, const float* d_lum, GridSpec gs, int
                              LaunchObserver* obs, const SortedRows* sorted, bool round8) {
     const int nC = gs.nSelCols, nR = gs.nSelRows;
     if (nC > 36 || nR > 32 || nrows_local <= 0) return nrows_local <= 0 ? hipSuccess : hipErrorInvalidValue;
-    const bool use_sorted = sorted != nullptr && nC <= sorted_expand_max_cols() && gs.W <= sorted_expand_max_width() &&
-                            std::getenv("NLE_NO_SORTED_EXPAND") == nullptr;
+    const bool use_sorted = use_sorted_expand(gs, sorted);
     if (nl < 1 || nl > (use_sorted ? sorted_expand_layers(gs) : apply_layers_per_launch(gs))) return hipErrorInvalidValue;
     const size_t n = (size_t)kLevels * nC, gstride = (size_t)nrows_local * n;
     if (obs) obs->begin(SUB_HIST_G);
@@ -1887,185 +1801,6 @@ hipError_t gram_hist(hipStream_t s, const float* d_lum, GridSpec gs, int p, int 
     hipLaunchKernelGGL(k_ghist_final, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0, s, d_C, N, nsplit,
                        (size_t)ldm * N, d_Ep, p, nR, nC, d_Gk);
     if (obs) obs->end();
-    return hipGetLastError();
-}
-
-// -------------------------------------------------------------------- projection via the tables
-// V_i[k] = c_i sum_b ec[c_i][b] T_r[x_i][b][k],  T_r[x][b][k] = sum_a er[r][a] Ep[x][a,b] D[a,b][k]
-// (reference :327 in sample space).  One workgroup per image row: D lives in LDS, the row's pixels
-// are counting-sorted by level, then levels are processed 8 at a time: build T_r for the batch
-// (8 x nC x K' doubles in LDS), then one thread per pixel does its nC*K' multiply-adds and stores
-// its K' outputs.  p*(nC+... ) work per pixel becomes nC*K' instead of p*K'.
-constexpr int kPhXB = 4;     // levels per batch
-constexpr int kPhPB = 128;   // pixels per output sub-chunk (staged through LDS for 16-byte stores)
-constexpr int kPhKmax = 64;  // eigenvectors handled by this kernel
-
-template <int KT>  // Kp = 16 KT >= K: sT rows are zero padded to Kp so that the pixel loop has no per-k branch
-__global__ __launch_bounds__(256) void k_project_hist(const float* __restrict__ lum, GridSpec gs, int p, int row0,
-                                                      const double* __restrict__ er, const double* __restrict__ ecT,
-                                                      const double* __restrict__ Ep, const double* __restrict__ Dm,
-                                                      int ldd, int K, const double* __restrict__ cvec,
-                                                      float* __restrict__ V, int ldv) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int nC = gs.nSelCols, nR = gs.nSelRows, W = gs.W;
-    constexpr int Kp = 16 * KT;
-    double* sD = reinterpret_cast<double*>(smem_raw);        // [p][K]
-    double* sT = sD + (size_t)p * K;                         // [XB][nC][Kp]
-    double* sE = sT + (size_t)kPhXB * nC * Kp;              // [XB][p]  er[r][a] * Ep[x][a,b]
-    int* cnt = reinterpret_cast<int*>(sE + (size_t)kPhXB * p);  // [257] level offsets
-    int* fill = cnt + kLevels + 4;                           // [256]  (256 + 4 + 256 ints keep sOut 16-byte aligned)
-    float* sOut = reinterpret_cast<float*>(fill + kLevels);  // [PB][ldv]
-    unsigned short* idx = reinterpret_cast<unsigned short*>(sOut + (size_t)kPhPB * ldv);  // [W]
-    const int tid = threadIdx.x, lrow = blockIdx.x, r = row0 + lrow;
-    const double* er_r = er + (size_t)lrow * nR;
-    for (int i = tid; i < p * K; i += 256) sD[i] = Dm[(size_t)(i / K) * ldd + (i % K)];
-    for (int i = tid; i < kLevels; i += 256) {
-        cnt[i] = 0;
-        fill[i] = 0;
-    }
-    if (tid == 0) cnt[kLevels] = 0;
-    __syncthreads();
-    const float* lrowp = lum + (size_t)r * W;
-    for (int c = tid; c < W; c += 256) atomicAdd(&cnt[(int)lrowp[c]], 1);
-    __syncthreads();
-    if (tid < 64) {  // exclusive scan of 256 counters by one wave: 4 per lane + wave scan
-        int v[4], s = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[j] = cnt[4 * tid + j];
-            s += v[j];
-        }
-        int incl = s;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (tid >= off) incl += t;
-        }
-        int base = incl - s;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            cnt[4 * tid + j] = base;
-            base += v[j];
-        }
-        if (tid == 63) cnt[kLevels] = base;
-    }
-    __syncthreads();
-    for (int c = tid; c < W; c += 256) {
-        const int x = (int)lrowp[c];
-        idx[cnt[x] + atomicAdd(&fill[x], 1)] = (unsigned short)c;
-    }
-    __syncthreads();
-    for (int x0 = 0; x0 < kLevels; x0 += kPhXB) {
-        const int j0 = cnt[x0], j1 = cnt[x0 + kPhXB];
-        if (j1 == j0) continue;  // uniform: no pixel of this row has one of these levels
-        // stage er[r][a] * Ep[x][a,b] for the batch (coalesced), then T[xl][b][k] = sum_a sE[xl][a,b] D[a,b][k]
-        for (int i = tid; i < kPhXB * p; i += 256) {
-            const int sidx = i % p;
-            sE[i] = er_r[sidx / nC] * Ep[(size_t)x0 * p + i];
-        }
-        __syncthreads();
-        {
-            constexpr int kc = Kp / 4;  // chunks of 4 consecutive k (zero beyond K)
-            for (int o = tid; o < kPhXB * nC * kc; o += 256) {
-                const int xl = o / (nC * kc), rem = o - xl * nC * kc, b = rem / kc, k0 = (rem - b * kc) * 4;
-                const double* se = sE + (size_t)xl * p + b;
-                double t[4] = {0.0, 0.0, 0.0, 0.0};
-                if (k0 + 3 < K) {
-                    for (int a = 0; a < nR; ++a) {
-                        const double ev = se[a * nC];
-                        const double* dp = sD + (size_t)(a * nC + b) * K + k0;
-                        t[0] += ev * dp[0];
-                        t[1] += ev * dp[1];
-                        t[2] += ev * dp[2];
-                        t[3] += ev * dp[3];
-                    }
-                } else if (k0 < K) {
-                    for (int a = 0; a < nR; ++a) {
-                        const double ev = se[a * nC];
-                        const double* dp = sD + (size_t)(a * nC + b) * K + k0;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            if (k0 + q < K) t[q] += ev * dp[q];
-                    }
-                }
-                double* tp = sT + ((size_t)xl * nC + b) * Kp + k0;
-                tp[0] = t[0];
-                tp[1] = t[1];
-                tp[2] = t[2];
-                tp[3] = t[3];
-            }
-        }
-        __syncthreads();
-        for (int jb = j0; jb < j1; jb += kPhPB) {
-            const int npix = min(kPhPB, j1 - jb);
-            if (tid < npix) {
-                const int c = idx[jb + tid];
-                const int xl = (int)lrowp[c] - x0;
-                const double cf = cvec[(size_t)lrow * W + c];
-                double acc[Kp];
-#pragma unroll
-                for (int k = 0; k < Kp; ++k) acc[k] = 0.0;
-                const double* Tx = sT + (size_t)xl * nC * Kp;
-                for (int b = 0; b < nC; ++b) {
-                    const double e = ecT[(size_t)b * W + c];
-                    const double* Tb = Tx + (size_t)b * Kp;
-#pragma unroll
-                    for (int k = 0; k < Kp; ++k) acc[k] += e * Tb[k];
-                }
-                float* so = sOut + (size_t)tid * ldv;
-#pragma unroll
-                for (int k = 0; k < Kp; ++k)
-                    if (k < ldv) so[k] = (float)(cf * acc[k]);  // columns K..ldv-1 are exact zeros (T is zero padded)
-            }
-            __syncthreads();
-            // whole rows of V, 16 bytes per lane
-            const int nq = ldv >> 2;
-            for (int it = tid; it < npix * nq; it += 256) {
-                const int pj = it / nq, q = it - pj * nq;
-                const int c = idx[jb + pj];
-                *reinterpret_cast<float4*>(V + ((size_t)lrow * W + c) * ldv + 4 * q) =
-                    *reinterpret_cast<const float4*>(sOut + (size_t)pj * ldv + 4 * q);
-            }
-            __syncthreads();
-        }
-    }
-}
-
-bool project_hist_ok(GridSpec gs, int p, int K) {
-    if (K > kPhKmax || gs.W > 65535) return false;
-    const size_t Kp = ((size_t)K + 15) & ~(size_t)15;
-    const size_t shm = ((size_t)p * K + (size_t)kPhXB * gs.nSelCols * Kp + (size_t)kPhXB * p) * sizeof(double) +
-                       (size_t)(2 * kLevels + 4) * sizeof(int) + (size_t)kPhPB * (((size_t)K + 3) & ~(size_t)3) * sizeof(float) +
-                       (size_t)gs.W * sizeof(unsigned short) + 16;
-    return K <= kPhKmax && shm <= 150 * 1024;
-}
-
-hipError_t project_hist(hipStream_t s, const float* d_lum, GridSpec gs, int p, int row0, int nrows_local,
-                        const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_D, int ldd, int K,
-                        const double* d_c, float* d_V, int ldv) {
-    if (nrows_local <= 0) return hipSuccess;
-    const int KT = (K + 15) / 16;
-    const size_t shm = ((size_t)p * K + (size_t)kPhXB * gs.nSelCols * 16 * KT + (size_t)kPhXB * p) * sizeof(double) +
-                       (size_t)(2 * kLevels + 4) * sizeof(int) + (size_t)kPhPB * ldv * sizeof(float) +
-                       (size_t)gs.W * sizeof(unsigned short) + 16;
-    hipError_t e = hipSuccess;
-#define NLE_PH_CASE(T)                                                                                              \
-    case T:                                                                                                         \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_project_hist<T>),                                   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                             \
-        if (e != hipSuccess) return e;                                                                              \
-        hipLaunchKernelGGL((k_project_hist<T>), dim3((unsigned)nrows_local), dim3(256), shm, s, d_lum, gs, p, row0, \
-                           d_er, d_ecT, d_Ep, d_D, ldd, K, d_c, d_V, ldv);                                          \
-        break;
-    switch (KT) {
-        NLE_PH_CASE(1)
-        NLE_PH_CASE(2)
-        NLE_PH_CASE(3)
-        NLE_PH_CASE(4)
-        default:
-            return hipErrorInvalidValue;
-    }
-#undef NLE_PH_CASE
     return hipGetLastError();
 }
 

@@ -131,14 +131,9 @@ hipError_t project64(hipStream_t s, const float* d_lum, GridSpec gs, const Sampl
                      int ldv);
 
 // ---- quantised-luminance (integer 0..255) Sinkhorn pass: table look-ups instead of exponentials ----
-int sink_hist_max_cols();
 hipError_t check_levels(hipStream_t s, const float* d_lum, long long n, int* d_flag);  // 2 ints: [0] != 0: not quantised, [1]: 16-level tiles that occur (bit t)
 hipError_t hist_tables(hipStream_t s, GridSpec gs, const Sample4* d_samples, int p, double hx, double hy, int row0,
                        int nrows_local, double* d_er, double* d_ecT, double* d_Ep);
-// partial: [nrows_local][ldp] doubles (one row per image row); d_ybuf as in sink_pass
-hipError_t sink_hist(hipStream_t s, int mode, const float* d_lum, GridSpec gs, int p, int ldp, int row0,
-                     int nrows_local, const double* d_er, const double* d_ecT, const double* d_Ep,
-                     const double* d_w, double eps, double* d_ybuf, double* d_partial);
 
 // ---- the literal decomposition in fp64 (generic64.hip): auto mode's fallback and the stage-level API
 hipError_t affinity64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, int ld, double sw,
@@ -251,7 +246,7 @@ hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows_local, const u
                             const unsigned short* d_first, const double* d_E, const double* d_cvec, double* d_Aout, bool rec,
                             double kappa);
 
-// tiled form of sink_hist (three kernels, Ep read once per pass); writes the full column sums to d_z
+// the table pass (three kernels, Ep read once per pass; nSelCols <= 36, nSelRows <= 32); writes the full column sums to d_z
 size_t hist_tiled_workspace_elems(GridSpec gs, int nrows_local);
 hipError_t sink_hist_tiled(hipStream_t s, int mode, const float* d_lum, GridSpec gs, int p, int ldp, int row0,
                            int nrows_local, const double* d_er, const double* d_ecT, const double* d_Ep,
@@ -261,7 +256,8 @@ hipError_t sink_hist_tiled(hipStream_t s, int mode, const float* d_lum, GridSpec
                            const SortedRows* sorted = nullptr);  // given: the pixel kernel runs on the level-sorted rows
 // sample-space apply (tables): expand half for one layer, the p/K-sized middle, and the sample-pixel outputs
 int apply_layers_per_launch(GridSpec gs);
-// (sorted given, nC <= 12, W <= 4096: the pixel kernel runs on the level-sorted rows, sorted_expand)
+// use_sorted_expand: the pixel kernel runs on the level-sorted rows (sorted_expand, sorted_expand_layers per launch)
+bool use_sorted_expand(GridSpec gs, const SortedRows* sorted);
 hipError_t apply_hist_layers(hipStream_t s, const float* d_lum, GridSpec gs, int p, int row0, int nrows_local,
                              const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_wl, int ldw,
                              int nl, const double* d_c, double* d_ws, float* d_out, long long ostride,
@@ -278,12 +274,6 @@ size_t ghist_workspace_elems(GridSpec gs, int nrows_local);
 hipError_t gram_hist(hipStream_t s, const float* d_lum, GridSpec gs, int p, int row0, int nrows_local,
                      const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_c, double* d_ws,
                      double* d_Gk, LaunchObserver* obs = nullptr, const SortedRows* sorted = nullptr);
-
-// projection through the tables (quantised luminance): V = diag(c) K D, one workgroup per image row
-bool project_hist_ok(GridSpec gs, int p, int K);
-hipError_t project_hist(hipStream_t s, const float* d_lum, GridSpec gs, int p, int row0, int nrows_local,
-                        const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_D, int ldd, int K,
-                        const double* d_c, float* d_V, int ldv);
 
 // 8-bit BGR <-> Lab (colour.hip): d_lut = the fixed-point tables of nle_lab8_tables as one blob; d_lab / d_L optional outputs
 hipError_t bgr2lab8(hipStream_t s, const unsigned char* d_bgr, long long n, const double* d_lut, unsigned char* d_lab,

@@ -26,6 +26,7 @@ struct Nystrom {
 
 struct Ortho {
     int q = 0, K = 0, r_wa = 0, r_q = 0;
+    bool chol_wa = false;  // (W_A is always diagonalised here: the field mirrors OrthoSS's)
     std::vector<double> Sq, Cproj, VArows, Wa;
 };
 

@@ -88,6 +88,16 @@ SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool
     return s;
 }
 
+// The image and sample-grid checks of every entry point that takes a plane and sample counts
+GridSpec checked_grid(int H, int W, int nRow, int nCol) {
+    check_image_size(H, W);
+    if (nRow > H || nCol > W)  // reference src/filter.cpp:117-119
+        throw Fail{NLE_ERR_INVALID, "Number of samples per row and col must be <= that of image."};
+    GridSpec gs;
+    if (!make_grid(H, W, nRow, nCol, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
+    return gs;
+}
+
 // The checks of a patch radius R > 0 that need no device (nle_ctx_set_patch_radius has checked 0 <= R <= 7)
 void check_patch_radius(const nle_ctx* c, int R, int H, int W) {
     if (R <= 0) return;
@@ -264,6 +274,41 @@ std::vector<float> build_B(const Nystrom& n, int p) {
     return B;
 }
 
+inline hipError_t scatter_rows_any(hipStream_t s, const float* rows, const long long* idx, int n, int ld, float* d_X,
+                                   long long M) {
+    return nlek::scatter_rows(s, rows, idx, n, ld, d_X, M);
+}
+inline hipError_t scatter_rows_any(hipStream_t s, const double* rows, const long long* idx, int n, int ld, double* d_X,
+                                   long long M) {
+    return nlek::scatter_rows64(s, rows, idx, n, ld, d_X, M);
+}
+
+// Exact sample rows: row a of the column-major host matrix src (nrows x K) is written, zero padded to ld, over the row of
+// sample a's pixel in the device matrix d_X (this rank's slab [pix0, pix0 + M), ld columns); samples of other slabs are
+// skipped.  Returns with the stream drained (the host staging vectors go out of scope).
+template <typename T>
+void scatter_sample_rows(nle_ctx* c, const std::vector<long long>& pix, int nrows, const std::vector<double>& src, int K,
+                         int ld, long long pix0, long long M, T* d_X) {
+    std::vector<T> rows;
+    std::vector<long long> idx;
+    for (int a = 0; a < nrows; ++a) {
+        const long long loc = pix[a] - pix0;
+        if (loc < 0 || loc >= M) continue;
+        idx.push_back(loc);
+        const size_t off = rows.size();
+        rows.resize(off + ld, T(0));
+        for (int k = 0; k < K; ++k) rows[off + k] = (T)src[(size_t)k * nrows + a];
+    }
+    DevBuf<T> d_rows(rows.size());
+    DevBuf<long long> d_idx(idx.size());
+    if (!idx.empty()) {
+        HIP_OK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(d_idx.p, idx.data(), idx.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+        PROFILED(c, NLE_K_SMALL, scatter_rows_any(c->stream, d_rows.p, d_idx.p, (int)idx.size(), ld, d_X, M));
+    }
+    HIP_OK(hipStreamSynchronize(c->stream));
+}
+
 // Phi for the local slab: fused affinity + Nystrom extension, then exact V_A sample rows
 void build_phi(nle_ctx* c, const float* d_lum, const SampleSet& ss, const Nystrom& ny, double hx,
                double hy, long long pix0, long long M, float* d_phi) {
@@ -284,25 +329,8 @@ void build_phi(nle_ctx* c, const float* d_lum, const SampleSet& ss, const Nystro
         PROFILED(c, NLE_K_NYSTROM, nlek::ts_gemm(c->stream, true, nullptr, 0, d_lum, ss.gs, d_samples.p, sw, pw, pix0,
                                                  d_B.p, ny.ldr, p, d_phi, ny.ldr, M, nullptr, NLE_EPS));
     }
-    // sample pixels carry their exact V_A row (top block of phi, reference :275)
-    std::vector<float> rows;
-    std::vector<long long> idx;
-    for (int k = 0; k < p; ++k) {
-        const long long loc = ss.pix[k] - pix0;
-        if (loc < 0 || loc >= M) continue;
-        idx.push_back(loc);
-        const size_t off = rows.size();
-        rows.resize(off + ny.ldr, 0.f);
-        for (int j = 0; j < ny.r; ++j) rows[off + j] = (float)ny.VA[(size_t)j * p + k];
-    }
-    DevBuf<float> d_rows(rows.size());
-    DevBuf<long long> d_idx(idx.size());
-    if (!idx.empty()) {
-        HIP_OK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(d_idx.p, idx.data(), idx.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-        PROFILED(c, NLE_K_SMALL, nlek::scatter_rows(c->stream, d_rows.p, d_idx.p, (int)idx.size(), ny.ldr, d_phi, M));
-    }
-    HIP_OK(hipStreamSynchronize(c->stream));  // host staging vectors go out of scope
+    // sample pixels carry their exact V_A row (top block of phi, reference :275); drains the stream before B goes
+    scatter_sample_rows(c, ss.pix, p, ny.VA, ny.r, ny.ldr, pix0, M, d_phi);
 }
 
 // Sinkhorn (reference :238-245) as 2T passes: t0 = Phi^T 1, then alternately
@@ -370,43 +398,7 @@ void sinkhorn_passes(nle_ctx* c, const T_* d_phi, long long M, int ld, int r,
     }
 }
 
-// G (r x r col-major) = sum_i c_i^2 phi_i phi_i^T over ALL rows of every rank
-std::vector<double> gram_all(nle_ctx* c, const float* d_phi, long long M, int ld, int r, const double* d_u) {
-    const int ntiles = nlek::gram_num_tiles(ld);
-    DevBuf<double> d_partial(std::max<size_t>(nlek::gram_partial_elems(std::max<long long>(M, 1), ld), 1));
-    DevBuf<double> d_tiles((size_t)ntiles * 1024);
-    if (M > 0) {
-        PROFILED(c, NLE_K_GRAM, nlek::gram(c->stream, d_phi, M, ld, d_u, NLE_EPS, d_partial.p, d_tiles.p));
-    } else {
-        HIP_OK(hipMemsetAsync(d_tiles.p, 0, (size_t)ntiles * 1024 * sizeof(double), c->stream));
-    }
-    all_reduce(c, d_tiles.p, (size_t)ntiles * 1024);
-    std::vector<double> tiles((size_t)ntiles * 1024);
-    HIP_OK(hipMemcpyAsync(tiles.data(), d_tiles.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
-    std::vector<double> G((size_t)r * r, 0.0);
-    const int nt = (ld + 31) / 32;
-    int t = 0;
-    for (int ti = 0; ti < nt; ++ti)
-        for (int tj = ti; tj < nt; ++tj, ++t) {
-            const double* tl = tiles.data() + (size_t)t * 1024;
-            for (int a = 0; a < 32; ++a)
-                for (int b = 0; b < 32; ++b) {
-                    const int i = ti * 32 + a, j = tj * 32 + b;
-                    if (i >= r || j >= r) continue;
-                    if (ti == tj && j < i) continue;  // diagonal tiles: take the upper half
-                    const double v = tl[a * 32 + b];
-                    G[(size_t)j * r + i] = v;
-                    G[(size_t)i * r + j] = v;
-                }
-        }
-    return G;
-}
-
-}  // namespace
-
-namespace {
-// unpack the upper-triangular 32x32 tile list of gram()/gram_fused() into a symmetric n x n matrix
+// unpack the upper-triangular ts x ts tile list of gram() / gram64() into a symmetric n x n matrix
 std::vector<double> unpack_tiles(const std::vector<double>& tiles, int ld, int n, int ts) {
     std::vector<double> G((size_t)n * n, 0.0);
     const int nt = (ld + ts - 1) / ts;
@@ -427,31 +419,43 @@ std::vector<double> unpack_tiles(const std::vector<double>& tiles, int ld, int n
     return G;
 }
 
-void scatter_sample_rows(nle_ctx* c, const std::vector<long long>& pix, int nrows, const std::vector<double>& rows_cm,
-                         int ldrows, int K, int ldv, long long pix0, long long M, float* d_V) {
-    std::vector<float> rows;
-    std::vector<long long> idx;
-    for (int a = 0; a < nrows; ++a) {
-        const long long loc = pix[a] - pix0;
-        if (loc < 0 || loc >= M) continue;
-        idx.push_back(loc);
-        const size_t off = rows.size();
-        rows.resize(off + ldv, 0.f);
-        for (int k = 0; k < K; ++k) rows[off + k] = (float)rows_cm[(size_t)k * ldrows + a];
+// G (r x r col-major) = sum_i c_i^2 phi_i phi_i^T over ALL rows of every rank
+std::vector<double> gram_all(nle_ctx* c, const float* d_phi, long long M, int ld, int r, const double* d_u) {
+    const int ntiles = nlek::gram_num_tiles(ld);
+    DevBuf<double> d_partial(std::max<size_t>(nlek::gram_partial_elems(std::max<long long>(M, 1), ld), 1));
+    DevBuf<double> d_tiles((size_t)ntiles * 1024);
+    if (M > 0) {
+        PROFILED(c, NLE_K_GRAM, nlek::gram(c->stream, d_phi, M, ld, d_u, NLE_EPS, d_partial.p, d_tiles.p));
+    } else {
+        HIP_OK(hipMemsetAsync(d_tiles.p, 0, (size_t)ntiles * 1024 * sizeof(double), c->stream));
     }
-    if (idx.empty()) return;
-    DevBuf<float> d_rows(rows.size());
-    DevBuf<long long> d_idx(idx.size());
-    HIP_OK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(d_idx.p, idx.data(), idx.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-    PROFILED(c, NLE_K_SMALL, nlek::scatter_rows(c->stream, d_rows.p, d_idx.p, (int)idx.size(), ldv, d_V, M));
-    HIP_OK(hipStreamSynchronize(c->stream));  // staging vectors go out of scope
+    all_reduce(c, d_tiles.p, (size_t)ntiles * 1024);
+    std::vector<double> tiles((size_t)ntiles * 1024);
+    HIP_OK(hipMemcpyAsync(tiles.data(), d_tiles.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return unpack_tiles(tiles, ld, r, 32);
 }
 
-// ---- the two train paths; both fill f->K, ldv, eigvals, d_V ----
+// ---- the train paths; each fills f->K, ldv, eigvals and d_V or d_V64 (or the lazy form) ----
 struct StageMs {
     double sinkhorn = 0, gram = 0, project = 0, host = 0, host_overlapped = 0;
+    void take(Timer& s, Timer& g, Timer& p) {
+        sinkhorn = s.ms();
+        gram = g.ms();
+        project = p.ms();
+    }
 };
+
+// what the filter keeps of the orthogonalisation (Ortho or OrthoSS)
+template <typename O>
+void adopt_ortho(nle_filter* f, const O& o) {
+    f->K = o.K;
+    f->ldv = ld4(o.K);
+    f->eigvals = o.Sq;
+    f->r_wa = o.r_wa;
+    f->r_q = o.r_q;
+    f->chol_wa = o.chol_wa ? 1 : 0;
+}
 
 // (1) materialised Phi: Phi = K_AB^T B written once (N x r fp32), streamed by every later pass
 void train_materialised(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss, const Nystrom& ny,
@@ -470,12 +474,8 @@ void train_materialised(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
     double h0 = now_ms();
     Ortho o = orthogonalize_host(ny, ss.p, u_c, u_r, std::move(G), n_eig, true, c->topk_solver);
     ms->host += now_ms() - h0;
-    f->K = o.K;
-    f->ldv = ld4(o.K);
-    f->eigvals = o.Sq;
+    adopt_ortho(f, o);
     f->formulation = NLE_MODE_MATERIALISED;
-    f->r_wa = o.r_wa;
-    f->r_q = o.r_q;
     tm_p.start();
     std::vector<float> Cp((size_t)ny.r * f->ldv, 0.f);
     for (int k = 0; k < o.K; ++k)
@@ -485,14 +485,12 @@ void train_materialised(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
     DevBuf<float> d_V((size_t)std::max<long long>(M, 1) * f->ldv);
     PROFILED(c, NLE_K_PROJECT, nlek::ts_gemm(c->stream, false, d_phi.p, ny.ldr, nullptr, ss.gs, nullptr, 0.f, 0.f, 0,
                                              d_Cp.p, f->ldv, ny.r, d_V.p, f->ldv, M, d_u_c.p, NLE_EPS));
-    scatter_sample_rows(c, ss.pix, o.q, o.VArows, o.q, o.K, f->ldv, pix0, M, d_V.p);
+    scatter_sample_rows(c, ss.pix, o.q, o.VArows, o.K, f->ldv, pix0, M, d_V.p);
     tm_p.stop();
     HIP_OK(hipStreamSynchronize(c->stream));
     f->v_bytes = d_V.n * sizeof(float);
     f->d_V = d_V.take();
-    ms->sinkhorn = tm_s.ms();
-    ms->gram = tm_g.ms();
-    ms->project = tm_p.ms();
+    ms->take(tm_s, tm_g, tm_p);
 }
 
 // (1b) the same literal decomposition with Phi and V in fp64 (generic64.hip): what auto mode falls back to when the
@@ -514,24 +512,7 @@ void build_phi64(nle_ctx* c, const float* d_lum, const SampleSet& ss, const Nyst
         PROFILED(c, NLE_K_AFFINITY, affinity_rows64(c->stream, d_lum, ss, d_samples.p, po, ldp, hx, hy, pix0 + i0, m, d_kab.p));
         PROFILED(c, NLE_K_NYSTROM, nlek::ts_gemm64(c->stream, d_kab.p, m, ldp, p, d_B.p, r, nullptr, d_phi + (size_t)i0 * ldr, ldr));
     }
-    std::vector<double> rows;
-    std::vector<long long> idx;
-    for (int k = 0; k < p; ++k) {  // sample pixels carry their exact V_A row (top block of phi, reference :275)
-        const long long loc = ss.pix[k] - pix0;
-        if (loc < 0 || loc >= M) continue;
-        idx.push_back(loc);
-        const size_t off = rows.size();
-        rows.resize(off + ldr, 0.0);
-        for (int j = 0; j < r; ++j) rows[off + j] = ny.VA[(size_t)j * p + k];
-    }
-    DevBuf<double> d_rows(rows.size());
-    DevBuf<long long> d_idx(idx.size());
-    if (!idx.empty()) {
-        HIP_OK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(d_idx.p, idx.data(), idx.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-        PROFILED(c, NLE_K_SMALL, nlek::scatter_rows64(c->stream, d_rows.p, d_idx.p, (int)idx.size(), ldr, d_phi, M));
-    }
-    HIP_OK(hipStreamSynchronize(c->stream));  // host staging vectors go out of scope
+    scatter_sample_rows(c, ss.pix, p, ny.VA, r, ldr, pix0, M, d_phi);  // exact V_A rows (top block of phi, reference :275)
 }
 
 // G (r x r col-major) = sum over ALL rows of every rank of c_i^2 phi_i phi_i^T, c_i = recip(phi_i . u) (d_u null: 1)
@@ -571,12 +552,8 @@ void train_generic64(nle_ctx* c, nle_filter* f, const float* d_lum, const Sample
     double h0 = now_ms();
     Ortho o = orthogonalize_host(ny, ss.p, u_c, u_r, std::move(G), n_eig, /*device_f32=*/false, c->topk_solver);
     ms->host += now_ms() - h0;
-    f->K = o.K;
-    f->ldv = ld4(o.K);
-    f->eigvals = o.Sq;
+    adopt_ortho(f, o);
     f->formulation = NLE_MODE_MATERIALISED_F64;
-    f->r_wa = o.r_wa;
-    f->r_q = o.r_q;
     tm_p.start();
     DevBuf<double> d_Cp(o.Cproj.size()), d_cs((size_t)std::max<long long>(M, 1));  // Cproj: r x K column-major
     HIP_OK(hipMemcpyAsync(d_Cp.p, o.Cproj.data(), o.Cproj.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -584,33 +561,12 @@ void train_generic64(nle_ctx* c, nle_filter* f, const float* d_lum, const Sample
     DevBuf<double> d_V((size_t)std::max<long long>(M, 1) * f->ldv);
     HIP_OK(hipMemsetAsync(d_V.p, 0, d_V.n * sizeof(double), c->stream));
     PROFILED(c, NLE_K_PROJECT, nlek::ts_gemm64(c->stream, d_phi.p, M, ny.ldr, ny.r, d_Cp.p, o.K, d_cs.p, d_V.p, f->ldv));
-    {   // exact rows of the A block (top block of :327)
-        std::vector<double> rows;
-        std::vector<long long> idx;
-        for (int a = 0; a < o.q; ++a) {
-            const long long loc = ss.pix[a] - pix0;
-            if (loc < 0 || loc >= M) continue;
-            idx.push_back(loc);
-            const size_t off = rows.size();
-            rows.resize(off + f->ldv, 0.0);
-            for (int k = 0; k < o.K; ++k) rows[off + k] = o.VArows[(size_t)k * o.q + a];
-        }
-        if (!idx.empty()) {
-            DevBuf<double> d_rows(rows.size());
-            DevBuf<long long> d_idx(idx.size());
-            HIP_OK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            HIP_OK(hipMemcpyAsync(d_idx.p, idx.data(), idx.size() * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-            PROFILED(c, NLE_K_SMALL, nlek::scatter_rows64(c->stream, d_rows.p, d_idx.p, (int)idx.size(), f->ldv, d_V.p, M));
-            HIP_OK(hipStreamSynchronize(c->stream));
-        }
-    }
+    scatter_sample_rows(c, ss.pix, o.q, o.VArows, o.K, f->ldv, pix0, M, d_V.p);  // exact rows of the A block (top of :327)
     tm_p.stop();
     HIP_OK(hipStreamSynchronize(c->stream));
     f->v64_bytes = d_V.n * sizeof(double);
     f->d_V64 = d_V.take();
-    ms->sinkhorn = tm_s.ms();
-    ms->gram = tm_g.ms();
-    ms->project = tm_p.ms();
+    ms->take(tm_s, tm_g, tm_p);
 }
 
 // Operands of the factored Sinkhorn update (fused.hip: k_sink_update_a/b) from what solve_Ka left: X1 (2p x r column-major)
@@ -654,9 +610,58 @@ void build_update_operands(nle_ctx* c, const Nystrom& ny, int p, DevBuf<double>&
     }
 }
 
+// The Sinkhorn iterations in sample space (reference :238-245 as 2T passes), shared by the table / Phi-free and the
+// streamed fp64 formulations.  Each pass has an N-sized half, the caller's pass_pixels(mode, last) -- z = the column sums
+// over this rank's pixels under the scaling whose sample-side vector is d_w; the last pass also stores its row scalings c
+// -- and a p-sized half here: the all-reduce of z (zrows slices of stride zld), then the factored update (fused.hip).
+// Pass n uses the scaling whose sample row sums are sAh[n-1] (and w) and produces sAh[n]; pass 0 is the column sum
+// Phi^T 1 (:234,239).  The constructor makes d_w (zero: the pass kernels read its padding up to zld), so it goes where
+// the caller's launch order wants that memset.
+struct SampleSinkhorn {
+    nle_ctx* c;
+    int p, T, zld;
+    DevBuf<double> d_w, d_sAh, d_X1, d_X2, d_lam, d_uv;
+    // sample row sums V_A u of the scaling that defines the final c (input of the last pass) and of the output of the
+    // last pass (the r scaling): complete once the stream is drained after run()
+    std::vector<double> sA_c, sA_r;
+
+    SampleSinkhorn(nle_ctx* c_, int p_, int zld_, int T_)
+        : c(c_), p(p_), T(T_), zld(zld_), d_w(zld_), d_sAh((size_t)2 * T_ * p_), d_uv((size_t)3 * p_) {
+        HIP_OK(hipMemsetAsync(d_w.p, 0, zld * sizeof(double), c->stream));
+    }
+
+    // `solve` factors Ka on the host (solve_Ka); it is called only after the first pass -- the column sum, which needs
+    // nothing of it -- is on the stream, so the factorisation runs under that pass.
+    Nystrom run(const std::function<Nystrom()>& solve, const std::function<void(int, bool)>& pass_pixels, double* d_z,
+                int zrows) {
+        pass_pixels(nlek::ROWPASS_COLSUM, false);
+        Nystrom ny = solve();
+        build_update_operands(c, ny, p, d_X1, d_X2, d_lam);
+        auto update = [&](int n, int mode) {
+            all_reduce(c, d_z, (size_t)zrows * zld);
+            PROFILED(c, NLE_K_SMALL,
+                     nlek::sink_update(c->stream, mode, p, ny.r, ny.chol, d_X1.p, d_X2.p, d_lam.p, d_z, zrows, zld,
+                                       n > 0 ? d_sAh.p + (size_t)(n - 1) * p : nullptr, NLE_EPS, d_uv.p, d_uv.p + 2 * p,
+                                       d_sAh.p + (size_t)n * p, d_w.p));
+        };
+        update(0, nlek::ROWPASS_COLSUM);
+        for (int n = 1; n < 2 * T; ++n) {
+            pass_pixels(nlek::ROWPASS_RECIP, n == 2 * T - 1);
+            update(n, nlek::ROWPASS_RECIP);
+        }
+        // (Fetching these on a second stream, so that the Gram kernels could be queued first, saved ~50 us but made two
+        // processes sharing one GPU stall for tens of milliseconds per all-reduce: one stream per ctx it stays.)
+        sA_c.resize(p);
+        sA_r.resize(p);
+        HIP_OK(hipMemcpyAsync(sA_c.data(), d_sAh.p + (size_t)(2 * T - 2) * p, p * sizeof(double), hipMemcpyDeviceToHost,
+                              c->stream));
+        HIP_OK(hipMemcpyAsync(sA_r.data(), d_sAh.p + (size_t)(2 * T - 1) * p, p * sizeof(double), hipMemcpyDeviceToHost,
+                              c->stream));
+        return ny;
+    }
+};
+
 // (2) Phi-free: every N-sized pass regenerates its affinity rows (fused.hip)
-// `solve` factors Ka on the host (solve_Ka); it is called only after the first pass -- the column sum, which
-// needs nothing of it -- is on the stream, so the factorisation runs under that pass.
 void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss,
                         const std::function<Nystrom()>& solve, double hx, double hy, int T, int n_eig, long long pix0,
                         long long M, StageMs* ms) {
@@ -672,29 +677,27 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
     HIP_OK(hipMemsetAsync(d_samples.p, 0, P64 * sizeof(float4), c->stream));
     HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     constexpr int kZS = 8;  // slices of the block partials, summed by k_sink_update
-    DevBuf<double> d_z((size_t)kZS * P64), d_w(P64), d_sAh((size_t)2 * T * p), d_X1, d_X2, d_lam, d_uv((size_t)3 * p),
-        d_partial((size_t)nlek::sink_pass_rows(std::max<long long>(M, 1)) * P64);
-    DevBuf<double> d_cbuf((size_t)std::max<long long>(M, 1));
+    const int npart = nlek::sink_pass_rows(std::max<long long>(M, 1));
+    DevBuf<double> d_z((size_t)kZS * P64), d_partial, d_cbuf((size_t)std::max<long long>(M, 1));
     // quantised luminance + Cartesian sample grid: table look-ups replace the exponentials (fused.hip)
-    const bool hist = ss.quantised && c->mode != 3 && ss.gs.nSelCols <= nlek::sink_hist_max_cols() &&
+    const bool hist = ss.quantised && c->mode != NLE_MODE_PHI_FREE_EXP && ss.gs.nSelCols <= nlek::ghist_max_cols() &&
                       ss.gs.nSelRows <= 32 && M > 0;
     if (!hist && p > nlek::sink_pass_max_p()) throw Fail{NLE_ERR_INVALID, "Phi-free path: too many samples for the generic kernels"};
     const int nrows_local = (int)(M / ss.gs.W), row0 = (int)(pix0 / ss.gs.W);
-    DevBuf<double> d_er, d_ecT, d_Ep;
+    DevBuf<double> d_er, d_ecT, d_Ep, d_hws;
     if (hist) {
         d_er.alloc((size_t)nrows_local * ss.gs.nSelRows);
         d_ecT.alloc((size_t)ss.gs.nSelCols * ss.gs.W);
         d_Ep.alloc((size_t)256 * p);
-        d_partial.alloc((size_t)nrows_local * P64);
+        d_hws.alloc(nlek::hist_tiled_workspace_elems(ss.gs, nrows_local));
         PROFILED(c, NLE_K_SMALL, nlek::hist_tables(c->stream, ss.gs, d_samples.p, p, hx, hy, row0, nrows_local, d_er.p,
                                                    d_ecT.p, d_Ep.p));
+    } else {
+        d_partial.alloc((size_t)npart * P64);
     }
-    HIP_OK(hipMemsetAsync(d_w.p, 0, P64 * sizeof(double), c->stream));
-    const bool hist_tiled = hist && ss.gs.nSelCols <= 36 && ss.gs.nSelRows <= 32 && std::getenv("NLE_HIST_UNTILED") == nullptr;
-    DevBuf<double> d_hws;
-    if (hist_tiled) d_hws.alloc(nlek::hist_tiled_workspace_elems(ss.gs, nrows_local));
+    SampleSinkhorn sk(c, p, P64, T);
     // level-sorted rows: the pixel halves of every table pass run without LDS atomics (sorted.hip); sorted once here
-    const bool sorted = hist_tiled && ss.gs.W <= nlek::sorted_max_width() && std::getenv("NLE_NO_SORTED_ROWS") == nullptr;
+    const bool sorted = hist && ss.gs.W <= nlek::sorted_max_width() && std::getenv("NLE_NO_SORTED_ROWS") == nullptr;
     DevBuf<unsigned short> d_scol, d_first;
     DevBuf<uint2> d_desc;
     DevBuf<double> d_E, d_E2;
@@ -725,63 +728,27 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
         }
     }
     const nlek::SortedRows* srp = sorted ? &sr : nullptr;
-    const int nrows = hist ? nrows_local : nlek::sink_pass_rows(std::max<long long>(M, 1));
     tr.mark("ss: alloc+upload");
-    // pass n uses the scaling whose sample row sums are sAh[n-1] (and w) and produces sAh[n]; pass 0 is the
-    // column sum Phi^T 1 (:234,239)
-    auto pass_pixels = [&](int mode, double* ybuf) {  // the N-sized half: z = sum over this rank's pixels
-        if (M > 0 && hist_tiled) {
+    auto pass_pixels = [&](int mode, bool last) {  // the N-sized half: z = sum over this rank's pixels
+        double* ybuf = last ? d_cbuf.p : nullptr;
+        if (hist) {
             // tiled table pass: writes the local column sums straight into slice 0 of d_z
             static const int kmap[4] = {NLE_K_SINK_TABLES, NLE_K_SINKHORN_PASS, NLE_K_REDUCE, NLE_K_REDUCE};
             ProfObserver obs(c, kmap);
             HIP_OK(nlek::sink_hist_tiled(c->stream, mode, d_lum, ss.gs, p, P64, row0, nrows_local, d_er.p, d_ecT.p,
-                                         d_Ep.p, d_w.p, NLE_EPS, ybuf, d_hws.p, d_z.p, &obs, nullptr, nullptr, srp));
+                                         d_Ep.p, sk.d_w.p, NLE_EPS, ybuf, d_hws.p, d_z.p, &obs, nullptr, nullptr, srp));
         } else if (M > 0) {
-            if (hist)
-                PROFILED(c, NLE_K_SINKHORN_PASS, nlek::sink_hist(c->stream, mode, d_lum, ss.gs, p, P64, row0, nrows_local,
-                                                                 d_er.p, d_ecT.p, d_Ep.p, d_w.p, NLE_EPS, ybuf,
-                                                                 d_partial.p));
-            else
-                PROFILED(c, NLE_K_SINKHORN_PASS, nlek::sink_pass(c->stream, mode, d_lum, ss.gs, d_samples.p, p, d_w.p, nsw,
-                                                                 npw, pix0, M, NLE_EPS, ybuf, d_partial.p));
-            PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(c->stream, d_partial.p, nrows, P64, d_z.p, kZS));
+            PROFILED(c, NLE_K_SINKHORN_PASS, nlek::sink_pass(c->stream, mode, d_lum, ss.gs, d_samples.p, p, sk.d_w.p, nsw,
+                                                             npw, pix0, M, NLE_EPS, ybuf, d_partial.p));
+            PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(c->stream, d_partial.p, npart, P64, d_z.p, kZS));
         } else {
             HIP_OK(hipMemsetAsync(d_z.p, 0, (size_t)kZS * P64 * sizeof(double), c->stream));
         }
     };
-    const int zrows = hist_tiled ? 1 : kZS;
-    int r = 0;
-    bool chol = false;
-    auto pass_update = [&](int n, int mode) {  // the p-sized half: all-reduce, then the factored update (fused.hip)
-        all_reduce(c, d_z.p, (size_t)zrows * P64);
-        PROFILED(c, NLE_K_SMALL,
-                 nlek::sink_update(c->stream, mode, p, r, chol, d_X1.p, d_X2.p, d_lam.p, d_z.p, zrows, P64,
-                                   n > 0 ? d_sAh.p + (size_t)(n - 1) * p : nullptr, NLE_EPS, d_uv.p, d_uv.p + 2 * p,
-                                   d_sAh.p + (size_t)n * p, d_w.p));
-    };
-    pass_pixels(nlek::ROWPASS_COLSUM, nullptr);
-    // factor Ka on the host while the column-sum pass runs, then upload the factors of the update
-    const Nystrom ny = solve();
-    r = ny.r;
-    chol = ny.chol;
-    f->r = r;
+    const Nystrom ny = sk.run(solve, pass_pixels, d_z.p, hist ? 1 : kZS);
+    f->r = ny.r;
     f->chol_ka = ny.chol ? 1 : 0;
     f->formulation = hist ? NLE_MODE_PHI_FREE : NLE_MODE_PHI_FREE_EXP;
-    build_update_operands(c, ny, p, d_X1, d_X2, d_lam);
-    pass_update(0, nlek::ROWPASS_COLSUM);
-    for (int n = 1; n < 2 * T; ++n) {
-        pass_pixels(nlek::ROWPASS_RECIP, n == 2 * T - 1 ? d_cbuf.p : nullptr);
-        pass_update(n, nlek::ROWPASS_RECIP);
-    }
-    // sample row sums V_A u of the scaling that defines the final c (input of the last pass) and of the
-    // output of the last pass (the r scaling).  (Fetching them on a second stream, so that the Gram kernels
-    // could be queued first, saved ~50 us but made two processes sharing one GPU stall for tens of
-    // milliseconds per all-reduce: one stream per ctx it stays.)
-    std::vector<double> sA_c(p), sA_r(p);
-    HIP_OK(hipMemcpyAsync(sA_c.data(), d_sAh.p + (size_t)(2 * T - 2) * p, p * sizeof(double), hipMemcpyDeviceToHost,
-                          c->stream));
-    HIP_OK(hipMemcpyAsync(sA_r.data(), d_sAh.p + (size_t)(2 * T - 1) * p, p * sizeof(double), hipMemcpyDeviceToHost,
-                          c->stream));
     tm_s.stop();
     tr.mark("ss: passes enqueued");
     HIP_OK(hipStreamSynchronize(c->stream));
@@ -791,75 +758,65 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
     // Quantised luminance: histogram + fp64 GEMM over the look-up tables (k_ghist_*); otherwise
     // regenerated affinity rows on the fp64 MFMA (k_gram64).
     tm_g.start();
-    const bool ghist = hist && ss.gs.nSelCols <= nlek::ghist_max_cols();
     const int ntiles = nlek::gram64_num_tiles(p);
-    const size_t g_elems = ghist ? (size_t)p * p : (size_t)ntiles * 256;
+    const size_t g_elems = hist ? (size_t)p * p : (size_t)ntiles * 256;
     DevBuf<double> d_gpart, d_tiles(g_elems);
     auto enqueue_gram = [&] {
-    if (M <= 0) {
-        HIP_OK(hipMemsetAsync(d_tiles.p, 0, g_elems * sizeof(double), c->stream));
-    } else if (ghist) {
-        d_gpart.alloc(nlek::ghist_workspace_elems(ss.gs, nrows_local));
-        static const int gmap[4] = {NLE_K_GRAM_ROWS, NLE_K_SMALL, NLE_K_GRAM_GEMM, NLE_K_SMALL};
-        ProfObserver obs(c, gmap);
-        HIP_OK(nlek::gram_hist(c->stream, d_lum, ss.gs, p, row0, nrows_local, d_er.p, d_ecT.p, d_Ep.p, d_cbuf.p,
-                               d_gpart.p, d_tiles.p, &obs, srp));
-    } else {
-        d_gpart.alloc(std::max<size_t>(nlek::gram64_partial_elems(M, p), 1));
-        PROFILED(c, NLE_K_GRAM, nlek::gram64(c->stream, d_lum, ss.gs, d_samples.p, p, nsw, npw, pix0, M, d_cbuf.p,
-                                             d_gpart.p, d_tiles.p));
-    }
+        if (M <= 0) {
+            HIP_OK(hipMemsetAsync(d_tiles.p, 0, g_elems * sizeof(double), c->stream));
+        } else if (hist) {
+            d_gpart.alloc(nlek::ghist_workspace_elems(ss.gs, nrows_local));
+            static const int gmap[4] = {NLE_K_GRAM_ROWS, NLE_K_SMALL, NLE_K_GRAM_GEMM, NLE_K_SMALL};
+            ProfObserver obs(c, gmap);
+            HIP_OK(nlek::gram_hist(c->stream, d_lum, ss.gs, p, row0, nrows_local, d_er.p, d_ecT.p, d_Ep.p, d_cbuf.p,
+                                   d_gpart.p, d_tiles.p, &obs, srp));
+        } else {
+            d_gpart.alloc(std::max<size_t>(nlek::gram64_partial_elems(M, p), 1));
+            PROFILED(c, NLE_K_GRAM, nlek::gram64(c->stream, d_lum, ss.gs, d_samples.p, p, nsw, npw, pix0, M, d_cbuf.p,
+                                                 d_gpart.p, d_tiles.p));
+        }
     };
     OrthoSS o;
     // (the opt-in Lanczos solver works on the LITERAL q x q matrix Q = Wa + S (Wab Wab^T) S with Wa as computed, not mirrored
     // from its lower triangle -- what Spectra's DenseGenMatProd multiplies by in a USE_SPECTRA build, src/filter.cpp:174, 311
     // -- so it takes the host route, which forms exactly that; the device route diagonalises a symmetric similar matrix)
-    if (ghist && std::getenv("NLE_HOST_ORTHO") == nullptr && c->topk_solver == 0) {
+    if (hist && c->topk_solver == 0) {
         // the Gram kernels were enqueued above; the q-sized products run on the device, the eigensolves on the host
-        ortho_ss_device(c, o, ny, p, sA_c, sA_r, d_tiles.p, n_eig, enqueue_gram, [&] { all_reduce(c, d_tiles.p, g_elems); },
-                        &ms->host, &ms->host_overlapped, tr);
+        ortho_ss_device(c, o, ny, p, sk.sA_c, sk.sA_r, d_tiles.p, n_eig, enqueue_gram,
+                        [&] { all_reduce(c, d_tiles.p, g_elems); }, &ms->host, &ms->host_overlapped, tr);
         tm_g.stop();
     } else {
-    enqueue_gram();
-    double h0 = now_ms();
-    ortho_ss_prepare(o, ny, p, sA_c, sA_r, /*literal_q=*/c->topk_solver != 0);  // host, while the Gram kernel runs
-    const double h_overlapped = now_ms() - h0;
-    tr.mark("ss: ortho prepare (host)");
-    // (a device-to-host copy into pageable memory blocks the host until the stream reaches it, so it
-    // is issued only now)
-    all_reduce(c, d_tiles.p, g_elems);
-    std::vector<double> tiles(g_elems);
-    HIP_OK(hipMemcpyAsync(tiles.data(), d_tiles.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    tm_g.stop();
-    HIP_OK(hipStreamSynchronize(c->stream));
-    tr.mark("ss: gram sync");
-    h0 = now_ms();
-    ortho_ss_finish(o, ghist ? std::move(tiles) : unpack_tiles(tiles, nlek::gram64_ld(p), p, 16), n_eig, c->topk_solver);
-    ms->host += now_ms() - h0;
-    tr.mark("ss: ortho finish (host)");
-    ms->host_overlapped += h_overlapped;
+        enqueue_gram();
+        double h0 = now_ms();
+        ortho_ss_prepare(o, ny, p, sk.sA_c, sk.sA_r, /*literal_q=*/c->topk_solver != 0);  // host, while the Gram kernel runs
+        const double h_overlapped = now_ms() - h0;
+        tr.mark("ss: ortho prepare (host)");
+        // (a device-to-host copy into pageable memory blocks the host until the stream reaches it, so it
+        // is issued only now)
+        all_reduce(c, d_tiles.p, g_elems);
+        std::vector<double> tiles(g_elems);
+        HIP_OK(hipMemcpyAsync(tiles.data(), d_tiles.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        tm_g.stop();
+        HIP_OK(hipStreamSynchronize(c->stream));
+        tr.mark("ss: gram sync");
+        h0 = now_ms();
+        ortho_ss_finish(o, hist ? std::move(tiles) : unpack_tiles(tiles, nlek::gram64_ld(p), p, 16), n_eig, c->topk_solver);
+        ms->host += now_ms() - h0;
+        tr.mark("ss: ortho finish (host)");
+        ms->host_overlapped += h_overlapped;
     }
-    f->K = o.K;
-    f->ldv = ld4(o.K);
-    f->eigvals = o.Sq;
-    f->r_wa = o.r_wa;
-    f->r_q = o.r_q;
-    f->chol_wa = o.chol_wa ? 1 : 0;
+    adopt_ortho(f, o);
 
     // V = diag(c) K_AB^T D: the Nystrom extension of the K' retained eigenvectors, affinity fused
     tm_p.start();
     if (o.K > 128) throw Fail{NLE_ERR_INVALID, "Phi-free path supports at most 128 eigenvectors"};
     const int ldd = nlek::project64_ld(o.K);
-    std::vector<double> Dp((size_t)p * ldd, 0.0), Vr((size_t)p * ldd, 0.0);
+    std::vector<double> Dp((size_t)p * ldd, 0.0);
     for (int k = 0; k < o.K; ++k)
-        for (int a = 0; a < p; ++a) {
-            Dp[(size_t)a * ldd + k] = o.D[(size_t)k * p + a];
-            Vr[(size_t)a * ldd + k] = o.Vrows[(size_t)k * p + a];
-        }
+        for (int a = 0; a < p; ++a) Dp[(size_t)a * ldd + k] = o.D[(size_t)k * p + a];
     DevBuf<double> d_D(Dp.size());
     HIP_OK(hipMemcpyAsync(d_D.p, Dp.data(), Dp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const bool lazy = hist_tiled && std::getenv("NLE_EAGER_V") == nullptr;
-    if (lazy) {
+    if (hist) {
         // keep what defines V implicitly; the projection runs only if somebody asks for the matrix
         auto own = [&](auto& buf) {
             using T = std::remove_pointer_t<decltype(buf.p)>;
@@ -868,6 +825,9 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
             f->owned.emplace_back(ptr, bytes);
             return ptr;
         };
+        std::vector<double> Vr((size_t)p * ldd, 0.0);
+        for (int k = 0; k < o.K; ++k)
+            for (int a = 0; a < p; ++a) Vr[(size_t)a * ldd + k] = o.Vrows[(size_t)k * p + a];
         DevBuf<double> d_Vr(Vr.size());
         DevBuf<long long> d_spix(p), d_sloc(p);
         DevBuf<float> d_slab((size_t)M);
@@ -907,28 +867,20 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
         f->h_Vrows = o.Vrows;
         f->h_sample_pix = ss.pix;
         tm_p.stop();
-        ms->sinkhorn = tm_s.ms();
-        ms->gram = tm_g.ms();
-        ms->project = tm_p.ms();
+        ms->take(tm_s, tm_g, tm_p);
         return;
     }
     DevBuf<float> d_V((size_t)std::max<long long>(M, 1) * f->ldv);
-    if (hist && nlek::project_hist_ok(ss.gs, p, o.K) && std::getenv("NLE_PROJECT_HIST") != nullptr)
-        PROFILED(c, NLE_K_PROJECT, nlek::project_hist(c->stream, d_lum, ss.gs, p, row0, nrows_local, d_er.p, d_ecT.p,
-                                                      d_Ep.p, d_D.p, ldd, o.K, d_cbuf.p, d_V.p, f->ldv));
-    else
-        PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, d_lum, ss.gs, d_samples.p, p, nsw, npw, pix0, M, d_D.p, o.K,
-                                                   d_cbuf.p, d_V.p, f->ldv));
+    PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, d_lum, ss.gs, d_samples.p, p, nsw, npw, pix0, M, d_D.p, o.K,
+                                               d_cbuf.p, d_V.p, f->ldv));
     tr.mark("ss: project enqueued");
-    scatter_sample_rows(c, ss.pix, p, o.Vrows, p, o.K, f->ldv, pix0, M, d_V.p);
+    scatter_sample_rows(c, ss.pix, p, o.Vrows, o.K, f->ldv, pix0, M, d_V.p);
     tm_p.stop();
     HIP_OK(hipStreamSynchronize(c->stream));
     tr.mark("ss: project sync");
     f->v_bytes = d_V.n * sizeof(float);
     f->d_V = d_V.take();
-    ms->sinkhorn = tm_s.ms();
-    ms->gram = tm_g.ms();
-    ms->project = tm_p.ms();
+    ms->take(tm_s, tm_g, tm_p);
 }
 
 // (3) The same sample-space algebra on fp64 affinity rows (k_affinity64: libm exp of the reference's own argument, :104-112),
@@ -937,7 +889,7 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
 //   Sinkhorn half-iteration   y_i = recip(k_i . w), z += k_i y_i                 k_rowpass64 (u := w)
 //   Gram                      Gk += sum c_i^2 k_i k_i^T                          k_gram64d
 //   eigenvectors              V_i = c_i k_i^T D                                  k_tsgemm64      (V: N x K' fp64, as mode 4)
-// and the p-sized side is train_sample_space's (factored update, ortho_ss_device).  Costs a pass 2 x N p 8 bytes of HBM
+// and the p-sized side is train_sample_space's (SampleSinkhorn, ortho_ss_device).  Costs a pass 2 x N p 8 bytes of HBM
 // traffic (write + read of the chunk) where the materialised form reads N r 8 once -- the price of not holding it.
 void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss, const std::function<Nystrom()>& solve,
                     double hx, double hy, int T, int n_eig, long long pix0, long long M, StageMs* ms) {
@@ -954,51 +906,31 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
     HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, st));
     PatchOperands po;
     upload_patch_operands(c, ss, &po);
-    DevBuf<double> d_K((size_t)CH * ld), d_partial((size_t)nlek::kRowpassMaxBlocks * ld), d_zc(ld), d_z(ld), d_w(ld), d_ones(ld),
-        d_sAh((size_t)2 * T * p), d_X1, d_X2, d_lam, d_uv((size_t)3 * p), d_cbuf((size_t)std::max<long long>(M, 1));
-    HIP_OK(hipMemsetAsync(d_w.p, 0, ld * sizeof(double), st));
+    DevBuf<double> d_K((size_t)CH * ld), d_partial((size_t)nlek::kRowpassMaxBlocks * ld), d_zc(ld), d_z(ld), d_ones(ld),
+        d_cbuf((size_t)std::max<long long>(M, 1));
+    SampleSinkhorn sk(c, p, ld, T);
     HIP_OK(nlek::fill64(st, d_ones.p, ld, 1.0));
     tr.mark("s64: alloc+upload");
     auto chunk_rows = [&](long long i0) { return std::min<long long>(CH, M - i0); };
     auto gen = [&](long long i0, long long mc) {
         PROFILED(c, NLE_K_AFFINITY, affinity_rows64(st, d_lum, ss, d_samples.p, po, ld, hx, hy, pix0 + i0, mc, d_K.p, true));
     };
-    auto pass_pixels = [&](int mode, double* cbuf) {
+    auto pass_pixels = [&](int mode, bool last) {
         HIP_OK(hipMemsetAsync(d_z.p, 0, ld * sizeof(double), st));
         for (long long i0 = 0; i0 < M; i0 += CH) {
             const long long mc = chunk_rows(i0);
             gen(i0, mc);
             int nb = 0;
-            PROFILED(c, NLE_K_SINKHORN_PASS, nlek::rowpass64(st, mode, d_K.p, mc, ld, d_w.p, d_ones.p, nullptr, NLE_EPS, d_partial.p, &nb));
+            PROFILED(c, NLE_K_SINKHORN_PASS, nlek::rowpass64(st, mode, d_K.p, mc, ld, sk.d_w.p, d_ones.p, nullptr, NLE_EPS, d_partial.p, &nb));
             PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(st, d_partial.p, nb, ld, d_zc.p));
             HIP_OK(nlek::add64(st, d_z.p, d_zc.p, ld));
-            if (cbuf) PROFILED(c, NLE_K_SMALL, nlek::row_scalings64(st, d_K.p, mc, ld, p, d_w.p, NLE_EPS, cbuf + i0));
+            if (last) PROFILED(c, NLE_K_SMALL, nlek::row_scalings64(st, d_K.p, mc, ld, p, sk.d_w.p, NLE_EPS, d_cbuf.p + i0));
         }
     };
-    int r = 0;
-    bool chol = false;
-    auto pass_update = [&](int n, int mode) {
-        all_reduce(c, d_z.p, (size_t)ld);
-        PROFILED(c, NLE_K_SMALL, nlek::sink_update(st, mode, p, r, chol, d_X1.p, d_X2.p, d_lam.p, d_z.p, 1, ld,
-                                                   n > 0 ? d_sAh.p + (size_t)(n - 1) * p : nullptr, NLE_EPS, d_uv.p, d_uv.p + 2 * p,
-                                                   d_sAh.p + (size_t)n * p, d_w.p));
-    };
-    pass_pixels(nlek::ROWPASS_COLSUM, nullptr);
-    const Nystrom ny = solve();
-    r = ny.r;
-    chol = ny.chol;
-    f->r = r;
+    const Nystrom ny = sk.run(solve, pass_pixels, d_z.p, 1);
+    f->r = ny.r;
     f->chol_ka = ny.chol ? 1 : 0;
     f->formulation = NLE_MODE_STREAMED_F64;
-    build_update_operands(c, ny, p, d_X1, d_X2, d_lam);
-    pass_update(0, nlek::ROWPASS_COLSUM);
-    for (int n = 1; n < 2 * T; ++n) {
-        pass_pixels(nlek::ROWPASS_RECIP, n == 2 * T - 1 ? d_cbuf.p : nullptr);
-        pass_update(n, nlek::ROWPASS_RECIP);
-    }
-    std::vector<double> sA_c(p), sA_r(p);
-    HIP_OK(hipMemcpyAsync(sA_c.data(), d_sAh.p + (size_t)(2 * T - 2) * p, p * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(sA_r.data(), d_sAh.p + (size_t)(2 * T - 1) * p, p * sizeof(double), hipMemcpyDeviceToHost, st));
     tm_s.stop();
     HIP_OK(hipStreamSynchronize(st));
     tr.mark("s64: sinkhorn");
@@ -1016,15 +948,10 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
         }
     };
     OrthoSS o;
-    ortho_ss_device(c, o, ny, p, sA_c, sA_r, d_G.p, n_eig, enqueue_gram, [&] { all_reduce(c, d_G.p, pp); }, &ms->host,
+    ortho_ss_device(c, o, ny, p, sk.sA_c, sk.sA_r, d_G.p, n_eig, enqueue_gram, [&] { all_reduce(c, d_G.p, pp); }, &ms->host,
                     &ms->host_overlapped, tr);
     tm_g.stop();
-    f->K = o.K;
-    f->ldv = ld4(o.K);
-    f->eigvals = o.Sq;
-    f->r_wa = o.r_wa;
-    f->r_q = o.r_q;
-    f->chol_wa = o.chol_wa ? 1 : 0;
+    adopt_ortho(f, o);
     // V = diag(c) K D (the Nystrom extension of the K' kept eigenvectors, :324-327) + the exact sample rows
     tm_p.start();
     DevBuf<double> d_D((size_t)p * o.K), d_V((size_t)std::max<long long>(M, 1) * f->ldv);
@@ -1035,34 +962,13 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
         gen(i0, mc);
         PROFILED(c, NLE_K_PROJECT, nlek::ts_gemm64(st, d_K.p, mc, ld, p, d_D.p, o.K, d_cbuf.p + i0, d_V.p + (size_t)i0 * f->ldv, f->ldv));
     }
-    {
-        std::vector<double> rows;
-        std::vector<long long> idx;
-        for (int a = 0; a < p; ++a) {
-            const long long loc = ss.pix[a] - pix0;
-            if (loc < 0 || loc >= M) continue;
-            idx.push_back(loc);
-            const size_t off = rows.size();
-            rows.resize(off + f->ldv, 0.0);
-            for (int k = 0; k < o.K; ++k) rows[off + k] = o.Vrows[(size_t)k * p + a];
-        }
-        if (!idx.empty()) {
-            DevBuf<double> d_rows(rows.size());
-            DevBuf<long long> d_idx(idx.size());
-            HIP_OK(hipMemcpyAsync(d_rows.p, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice, st));
-            HIP_OK(hipMemcpyAsync(d_idx.p, idx.data(), idx.size() * sizeof(long long), hipMemcpyHostToDevice, st));
-            PROFILED(c, NLE_K_SMALL, nlek::scatter_rows64(st, d_rows.p, d_idx.p, (int)idx.size(), f->ldv, d_V.p, M));
-            HIP_OK(hipStreamSynchronize(st));
-        }
-    }
+    scatter_sample_rows(c, ss.pix, p, o.Vrows, o.K, f->ldv, pix0, M, d_V.p);
     tm_p.stop();
     HIP_OK(hipStreamSynchronize(st));
     tr.mark("s64: project");
     f->v64_bytes = d_V.n * sizeof(double);
     f->d_V64 = d_V.take();
-    ms->sinkhorn = tm_s.ms();
-    ms->gram = tm_g.ms();
-    ms->project = tm_p.ms();
+    ms->take(tm_s, tm_g, tm_p);
 }
 
 // materialise V = diag(c) K D of a lazy filter (projection kernel + exact sample rows)
@@ -1082,7 +988,7 @@ void ensure_V(nle_filter* f) {
     DevBuf<float> d_V((size_t)std::max<long long>(M, 1) * f->ldv);
     PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, f->d_lum - pix0, f->gs, f->d_samples, f->p, f->nsw, f->npw, pix0,
                                                M, f->d_D, f->K, f->d_c, d_V.p, f->ldv));
-    scatter_sample_rows(c, f->h_sample_pix, f->p, f->h_Vrows, f->p, f->K, f->ldv, pix0, M, d_V.p);
+    scatter_sample_rows(c, f->h_sample_pix, f->p, f->h_Vrows, f->K, f->ldv, pix0, M, d_V.p);
     HIP_OK(hipStreamSynchronize(c->stream));
     f->v_bytes = d_V.n * sizeof(float);
     f->d_V = d_V.take();
@@ -1123,10 +1029,10 @@ void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L 
                                                d_resp.p, d_t.p, d_Wp.p, d_YA.p));
     if (M > 0) {
         static const int emap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_EXPAND, NLE_K_REDUCE, NLE_K_REDUCE};
-        int lb = std::min(L, nlek::apply_layers_per_launch(f->gs));
-        if (f->has_sorted && f->gs.nSelCols <= nlek::sorted_expand_max_cols() && f->gs.W <= nlek::sorted_expand_max_width() &&
-            std::getenv("NLE_NO_SORTED_EXPAND") == nullptr)
-            lb = std::min(L, nlek::sorted_expand_layers(f->gs));  // what one launch of the sorted expand kernel takes
+        const nlek::SortedRows* srt = f->has_sorted ? &f->sorted : nullptr;
+        // layers per launch of the expand kernel apply_hist_layers will pick
+        int lb = std::min(L, nlek::use_sorted_expand(f->gs, srt) ? nlek::sorted_expand_layers(f->gs)
+                                                                   : nlek::apply_layers_per_launch(f->gs));
         if (group > 0) lb = std::min(lb, group);
         DevBuf<double> d_gws((size_t)lb * nrows_local * 256 * f->gs.nSelCols);
         for (int l = 0; l < L; l += lb) {
@@ -1135,7 +1041,7 @@ void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L 
                 ProfObserver obs(c, emap);
                 HIP_OK(nlek::apply_hist_layers(c->stream, lum, f->gs, p, f->row0, nrows_local, f->d_er, f->d_ecT, f->d_Ep,
                                                d_Wp.p + (size_t)l * P64, P64, nl, f->d_c, d_gws.p, d_y + (size_t)l * M, M,
-                                               &obs, f->has_sorted ? &f->sorted : nullptr, round8));
+                                               &obs, srt, round8));
             }
             PROFILED(c, NLE_K_SMALL, nlek::scatter_samples(c->stream, p, nl, f->d_sample_loc, d_YA.p + (size_t)l * p,
                                                            d_y + (size_t)l * M, M, round8));
@@ -1151,17 +1057,13 @@ void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L 
 // d_lum_in: the full H x W plane, or -- ctx in slab-input mode -- this rank's rows [row0, row1) only
 nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow, int nCol, double hx,
                        double hy, int T, int n_eig) {
-    check_image_size(H, W);
+    const GridSpec gs = checked_grid(H, W, nRow, nCol);
     const float* d_lum = d_lum_in;
     if (c->slab_input && c->world > 1) {  // virtual base of the full image: only this rank's rows are ever dereferenced
         int r0, r1;
         slab(H, c->rank, c->world, &r0, &r1);
         d_lum = d_lum_in - (size_t)r0 * W;
     }
-    if (nRow > H || nCol > W)  // reference src/filter.cpp:117-119
-        throw Fail{NLE_ERR_INVALID, "Number of samples per row and col must be <= that of image."};
-    GridSpec gs;
-    if (!make_grid(H, W, nRow, nCol, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
     if (T < 1) throw Fail{NLE_ERR_INVALID, "nSinkhornIter must be >= 1"};
     if (n_eig < 1) throw Fail{NLE_ERR_INVALID, "nEigenVectors must be >= 1"};
     if (!(hx > 0) || !(hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
@@ -1172,10 +1074,11 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
     // Phi-free needs <= 128 eigenvectors; its generic kernels need <= 256 samples, its table kernels
     // (quantised luminance, checked on the device below) a sample grid of at most 32 x 36.
     const bool generic_ok = gs.p() <= nlek::sink_pass_max_p() && n_eig <= 128;
-    const bool tables_ok = n_eig <= 128 && gs.nSelCols <= nlek::ghist_max_cols() && gs.nSelRows <= 32 && c->mode != 3;
-    if (c->mode == 3 && !generic_ok)
+    const bool tables_ok =
+        n_eig <= 128 && gs.nSelCols <= nlek::ghist_max_cols() && gs.nSelRows <= 32 && c->mode != NLE_MODE_PHI_FREE_EXP;
+    if (c->mode == NLE_MODE_PHI_FREE_EXP && !generic_ok)
         throw Fail{NLE_ERR_INVALID, "Phi-free path without tables supports at most 256 samples and 128 eigenvectors"};
-    if (c->mode == 2 && !generic_ok && !tables_ok)
+    if (c->mode == NLE_MODE_PHI_FREE && !generic_ok && !tables_ok)
         throw Fail{NLE_ERR_INVALID, "Phi-free path supports at most 128 eigenvectors and a 32 x 36 sample grid"};
     // patch affinities (R > 0): the fp64 formulations with explicit affinity rows only (the table, Phi-free and fp32 forms
     // cannot express them); every check here is decided the same way on every rank
@@ -1187,7 +1090,8 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
     // auto: the table form (all fp64) whenever it applies, else the literal decomposition in fp64 (generic64.hip).  The
     // fp32 formulations (materialised Phi, Phi-free with fp32 affinities) run only when asked for by mode: they miss
     // the 1e-4 bar on some well-posed inputs (DESIGN.md "Numerics").
-    const bool want_fuse = R == 0 && (c->mode == 2 || c->mode == 3 || (c->mode == 0 && tables_ok));
+    const bool want_fuse = R == 0 && (c->mode == NLE_MODE_PHI_FREE || c->mode == NLE_MODE_PHI_FREE_EXP ||
+                                      (c->mode == NLE_MODE_AUTO && tables_ok));
     HIP_OK(hipSetDevice(c->device));
 
     auto f = new nle_filter();
@@ -1210,9 +1114,9 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         if (R > 0 && ranks_where(c, !ss.quantised) > 0)  // refused on every rank if the plane is not integer valued on one
             throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
                                         "(the L channel of 8-bit Lab)"};
-        const bool fuse = c->mode == 0 ? (want_fuse && tables_ok && ss.quantised)
-                                       : (want_fuse && (generic_ok || (tables_ok && ss.quantised)));
-        if (c->mode == 2 && !fuse)
+        const bool fuse = c->mode == NLE_MODE_AUTO ? (want_fuse && tables_ok && ss.quantised)
+                                                   : (want_fuse && (generic_ok || (tables_ok && ss.quantised)));
+        if (c->mode == NLE_MODE_PHI_FREE && !fuse)
             throw Fail{NLE_ERR_INVALID, "Phi-free path: more than 256 samples needs an integer-valued luminance plane"};
         tr.mark("fetch_samples");
         f->p = ss.p;
@@ -1278,7 +1182,7 @@ void apply_impl(nle_filter* f, const float* d_x_in, int H, int W, const double* 
         throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
     if (L < 1 || L > 64) throw Fail{NLE_ERR_INVALID, "number of layers must be in [1, 64]"};
     HIP_OK(hipSetDevice(c->device));
-    if (f->lazy && std::getenv("NLE_APPLY_WITH_V") == nullptr) {
+    if (f->lazy) {
         apply_sample_space(f, d_x, h_g, L, d_y, done, group, round8);
         return;
     }
@@ -1336,11 +1240,7 @@ int nle_compute_kernel(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
                        double hx, double hy, double* h_Ka, float* d_kab) {
     if (!ctx || !d_lum) return NLE_ERR_INVALID;
     return guard(ctx, [&] {
-        check_image_size(H, W);
-        if (n_row_samples > H || n_col_samples > W)
-            throw Fail{NLE_ERR_INVALID, "Number of samples per row and col must be <= that of image."};
-        GridSpec gs;
-        if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
+        const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         if (ctx->patch_radius > 0)
             throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) does not take patch affinities: use nle_compute_kernel64"};
         HIP_OK(hipSetDevice(ctx->device));
@@ -1367,11 +1267,7 @@ int nle_nystrom(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_sample
                 double hy, double* h_eigvals, int* r, float* d_phi) {
     if (!ctx || !d_lum || !d_phi || !r) return NLE_ERR_INVALID;
     return guard(ctx, [&] {
-        check_image_size(H, W);
-        if (n_row_samples > H || n_col_samples > W)
-            throw Fail{NLE_ERR_INVALID, "Number of samples per row and col must be <= that of image."};
-        GridSpec gs;
-        if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
+        const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         if (ctx->patch_radius > 0)
             throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) does not take patch affinities: use the fp64 formulations"};
         HIP_OK(hipSetDevice(ctx->device));
@@ -1449,11 +1345,7 @@ int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
                          double hy, double* h_Ka, double* d_kab) {
     if (!ctx || !d_lum) return NLE_ERR_INVALID;
     return guard(ctx, [&] {
-        check_image_size(H, W);
-        if (n_row_samples > H || n_col_samples > W)
-            throw Fail{NLE_ERR_INVALID, "Number of samples per row and col must be <= that of image."};
-        GridSpec gs;
-        if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
+        const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         const int R = ctx->patch_radius;
         check_patch_radius(ctx, R, H, W);
         HIP_OK(hipSetDevice(ctx->device));
@@ -1644,7 +1536,7 @@ int nle_filter_eigvec_range(const nle_filter* f, int ncols, double* h_min, doubl
             d_tmp.alloc((size_t)std::max<long long>(M, 1) * ldc);
             PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, f->d_lum - pix0, f->gs, f->d_samples, f->p, f->nsw, f->npw,
                                                        pix0, M, d_Dk.p, ncols, f->d_c, d_tmp.p, ldc));
-            scatter_sample_rows(c, f->h_sample_pix, f->p, f->h_Vrows, f->p, ncols, ldc, pix0, M, d_tmp.p);
+            scatter_sample_rows(c, f->h_sample_pix, f->p, f->h_Vrows, ncols, ldc, pix0, M, d_tmp.p);
             HIP_OK(hipStreamSynchronize(c->stream));  // Dk (host) is consumed
             d_cols = d_tmp.p;
         } else {
@@ -1775,7 +1667,7 @@ int nle_apply_rounded8(nle_filter* f, const float* d_x, int H, int W, const doub
     if (!f || !f->ctx || !d_x || !h_fS || !d_y) return NLE_ERR_INVALID;
     return guard(f->ctx, [&] {
         apply_impl(f, d_x, H, W, h_fS, 1, d_y, nullptr, 0, /*round8=*/true);
-        if (!(f->lazy && std::getenv("NLE_APPLY_WITH_V") == nullptr)) {  // formulations with fp32 planes: round those
+        if (!f->lazy) {  // formulations with fp32 planes: round those
             DevBuf<unsigned char> d_o((size_t)std::max<long long>(f->n_local, 1));
             HIP_OK(nlek::plane_to_u8(f->ctx->stream, d_y, f->n_local, d_o.p));
             HIP_OK(nlek::channel8_plane(f->ctx->stream, d_o.p, f->n_local, d_y));

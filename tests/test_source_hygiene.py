@@ -11,3 +11,15 @@ def test_product_sources_have_no_ablation_hooks():
     for f in glob.glob(os.path.join(PKG_DIR, "csrc", "*")) + glob.glob(os.path.join(PKG_DIR, "host", "*")):
         text = open(f, errors="replace").read()
         assert "NLE_ABL_" not in text and "NLE_STAMP" not in text, f
+
+
+# Environment switches whose variants were taken out (nothing but the switch reached them): no source may read them again
+REMOVED_SWITCHES = ("NLE_HIST_UNTILED", "NLE_PROJECT_HIST", "NLE_EAGER_V", "NLE_APPLY_WITH_V", "NLE_HOST_ORTHO",
+                    "NLE_PROJECT_CHUNKED", "NLE_NO_SORTED_EXPAND")
+
+
+def test_product_sources_read_no_removed_switches():
+    for f in glob.glob(os.path.join(PKG_DIR, "csrc", "*")) + glob.glob(os.path.join(PKG_DIR, "host", "*")):
+        text = open(f, errors="replace").read()
+        for name in REMOVED_SWITCHES:
+            assert name not in text, (f, name)
