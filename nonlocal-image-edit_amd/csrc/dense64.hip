@@ -178,9 +178,6 @@ __global__ __launch_bounds__(kSyT) void k_sytrd_wave(int n, int G, int cw, int l
             for (int m = 0; m < RPL; ++m) st_pub(cbase + (size_t)1 * ldc + lane + 64 * m, col[lane + 64 * m]);
         }
     }
-#ifdef NLE_SYTRD_PROBE
-    unsigned long long tp0 = 0, tp1 = 0, tp2 = 0, tp3 = 0, nspin = 0, t_a, t_b;
-#endif
     // The step loop in RPL segments of (up to) 64 steps: in segment M0 the blocks of 64 rows below 64 M0 are done with, and
     // every row loop of the body starts at M0 AT COMPILE TIME -- half the instructions on average, and no branch (a run-time
     // skip of those blocks costs more than it saves, see above).  The row-(m < M0) entries of v, w, vn are never read.
@@ -189,9 +186,6 @@ __global__ __launch_bounds__(kSyT) void k_sytrd_wave(int n, int G, int cw, int l
         constexpr int M0 = decltype(M0c)::value;
         const int k_lo = max(0, 64 * M0 - 1), k_hi = dead ? -1 : min(n - 3, 64 * M0 + 62);
         for (int k = k_lo; k <= k_hi; ++k) {
-#ifdef NLE_SYTRD_PROBE
-            t_a = wall_clock64();
-#endif
             // (1) the published y_k (j = k+1 ..) and column k+1 (rows k+1 ..) into LDS.  All of a thread's words are requested
             // together and re-requested until none is unset: a poll is a round trip to the coherent level of the memory system.
             double* ly = land + (size_t)(k & 1) * 2 * ldc;
@@ -199,9 +193,6 @@ __global__ __launch_bounds__(kSyT) void k_sytrd_wave(int n, int G, int cw, int l
             const double* yrec = pub + (size_t)k * S + n + 2;
             const double* crec = cbase + (size_t)(k + 1) * ldc;
             bool fail = false;
-#ifdef NLE_SYTRD_PROBE
-            unsigned spins_probe = 0;
-#endif
             {
                 // (straight-line rounds: a thread's words beyond n - 1 poll word n - 1 again instead of being guarded)
                 constexpr int NP = (RPL + 3) / 4;
@@ -256,26 +247,17 @@ __global__ __launch_bounds__(kSyT) void k_sytrd_wave(int n, int G, int cw, int l
                         vc[q] = oc == kUnset ? fc : oc;
                     }
                 }
-#ifdef NLE_SYTRD_PROBE
-                spins_probe = spins;
-#endif
 #pragma unroll
                 for (int q = 0; q < NP; ++q) {
                     ly[idx[q]] = __longlong_as_double((long long)vy[q]);
                     lc[idx[q]] = __longlong_as_double((long long)vc[q]);
                 }
             }
-#ifdef NLE_SYTRD_PROBE
-            t_b = wall_clock64(); tp3 += t_b - t_a; t_a = t_b; nspin += spins_probe;
-#endif
             if (__syncthreads_or(fail)) {
                 if (tid == 0) __hip_atomic_store(status, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 dead = true;
                 return;
             }
-#ifdef NLE_SYTRD_PROBE
-            t_b = wall_clock64(); tp0 += t_b - t_a; t_a = t_b;
-#endif
             // (2) s = y . v, w = tau (y - (tau s / 2) v) on the active rows (i > k), zero elsewhere.  (Skipping the blocks of 64
             // rows that are done with costs more than it saves: 15 wave-uniform branches per loop, +1.3 us per step measured --
             // with one wave per SIMD nothing hides a branch's refetch.  The step loop is kept as straight as it can be.)
@@ -336,9 +318,6 @@ __global__ __launch_bounds__(kSyT) void k_sytrd_wave(int n, int G, int cw, int l
                 const int i = lane + 64 * m;
                 vn[m] = i == k + 2 ? 1.0 : (i > k + 2 ? vn[m] * scale1 : 0.0);
             }
-#ifdef NLE_SYTRD_PROBE
-            t_b = wall_clock64(); tp1 += t_b - t_a; t_a = t_b;
-#endif
             // (4) own columns j >= k+2: A -= v w^T + w v^T (products rounded separately: the two stored copies of an entry stay
             // bitwise equal), their products with v_{k+1} published as y_{k+1}; column k+2 published as it now stands
             double* yrec1 = pub + (size_t)(k + 1) * S + n + 2;
@@ -372,9 +351,6 @@ __global__ __launch_bounds__(kSyT) void k_sytrd_wave(int n, int G, int cw, int l
                     if (lane == 0) d_out[n - 1] = dl;
                 }
             }
-#ifdef NLE_SYTRD_PROBE
-            t_b = wall_clock64(); tp2 += t_b - t_a;
-#endif
             if (writer) {  // the record the back-transformation and the host read (after this wave's part of the hand-off)
                 double* rec = pub + (size_t)k * S;
 #pragma unroll
@@ -399,19 +375,15 @@ __global__ __launch_bounds__(kSyT) void k_sytrd_wave(int n, int G, int cw, int l
     segments<RPL>(segment);
     if (dead) return;
     if (writer && lane == 0) e_out[0] = 0.0;
-#ifdef NLE_SYTRD_PROBE
-    if (lane == 0 && (gw == 0 || gw == NW - 1)) printf("[sytrd probe] n=%d gw=%d: poll %.1f us (%llu extra rounds), barrier %.1f us, (2)(3) %.1f us, (4) %.1f us (wall clock, 100 MHz)\n", n, gw, tp3 * 0.01, nspin, tp0 * 0.01, tp1 * 0.01, tp2 * 0.01);
-#endif
 }
 
 int sytrd_max_n() { return 1152; }
 
 // Distribution of the one-hand-off form: four waves a workgroup, `cw` whole columns a wave.  Few workgroups mean few pollers
-// of every published word, many mean a short sweep over the own columns on the critical path: measured (NLE_SYTRD_CW), four
+// of every published word, many mean a short sweep over the own columns on the critical path: measured, four
 // columns a wave up to n = 640 (n = 400: 25 workgroups), two above (n = 900: 113 workgroups, 5.9 against 6.6 ms with the
 // upload; one column a wave is slower again).
 static int sytrd_cols_per_wave(int n) {
-    if (const char* e = std::getenv("NLE_SYTRD_CW")) return std::max(1, std::min(4, std::atoi(e)));
     return n > 640 ? 2 : 4;
 }
 // rows per lane the kernel is instantiated for, and with it the padded column length in LDS and in the published records

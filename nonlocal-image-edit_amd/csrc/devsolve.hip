@@ -120,8 +120,6 @@ bool DevSymEig::reduce(nle_ctx* c, int n_, const double* d_M, const double* d_di
 void DevSymEig::vectors(nle_ctx* c, int first, int count, double* d_Z) {
     if (count <= 0) return;
     if (first < 0 || first + count > n) throw Fail{NLE_ERR_INVALID, "device eigensolver: eigenvector range"};
-    static const bool trace = std::getenv("NLE_EIG_TRACE") != nullptr;
-    const double t0 = trace ? now_ms() : 0.0;
     double* hz = static_cast<double*>(pinned_take(c, (size_t)n * count * sizeof(double)));
     if (!hz) {
         hZ.resize((size_t)n * count);
@@ -129,7 +127,6 @@ void DevSymEig::vectors(nle_ctx* c, int first, int count, double* d_Z) {
     }
     if (!nleh::tridiag_eigenvectors(n, d.data(), e.data(), D.data(), first, count, hz))
         throw Fail{NLE_ERR_NUMERIC, "eigensolver did not converge (tridiagonal eigenvectors)"};
-    if (trace) std::fprintf(stderr, "[nle eig] device path n = %d: %d vectors by inverse iteration %.3f ms\n", n, count, now_ms() - t0);
     HIP_OK(hipMemcpyAsync(d_Z, hz, (size_t)n * count * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_OK(nlek::sytrd_back(st, n, pub.p, count, d_Z, n));
 }

@@ -15,16 +15,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <numeric>
-#include <chrono>
-#include <cstdio>
 #include <thread>
 #include <vector>
 #if defined(__x86_64__)
 #include <immintrin.h>
-#endif
-#if defined(__linux__)
-#include <pthread.h>
-#include <sched.h>
 #endif
 
 namespace nleh {
@@ -128,9 +122,17 @@ NLE_SIMD_CLONES void tridiagonalize(int n, double* V, double* d, double* e) {
     e[0] = 0.0;
 }
 
-// implicit QL on (d, e) accumulating rotations into V's columns; returns false if an
-// eigenvalue needs more than 60 sweeps.
-NLE_SIMD_CLONES bool ql_implicit(int n, double* V, double* d, double* e) {
+struct Sweep {
+    int l, m;      // rotations act on columns (i, i+1) for i = m-1 .. l
+    size_t first;  // index of the i = m-1 rotation in the (c, s) lists
+};
+
+// Implicit-shift QL on (d, e) (tql2), written once for its two uses: ACCUMULATE applies every plane rotation to V's
+// columns at once (ql_implicit), otherwise the rotations of each sweep are recorded for later (ql_record).  The
+// iteration itself, and so d, is the same either way.  false: an eigenvalue needs more than 60 sweeps.
+template <bool ACCUMULATE>
+static inline __attribute__((always_inline)) bool tql2(int n, double* V, double* d, double* e, std::vector<Sweep>* sweeps,
+                                                       std::vector<double>* cs, std::vector<double>* sn) {
     for (int i = 1; i < n; ++i) e[i - 1] = e[i];
     e[n - 1] = 0.0;
     double f = 0.0, tst1 = 0.0;
@@ -160,6 +162,7 @@ NLE_SIMD_CLONES bool ql_implicit(int n, double* V, double* d, double* e) {
                 double c = 1.0, c2 = c, c3 = c;
                 const double el1 = e[l + 1];
                 double s = 0.0, s2 = 0.0;
+                if (!ACCUMULATE) sweeps->push_back(Sweep{l, m, cs->size()});
                 for (int i = m - 1; i >= l; --i) {
                     c3 = c2;
                     c2 = c;
@@ -172,13 +175,18 @@ NLE_SIMD_CLONES bool ql_implicit(int n, double* V, double* d, double* e) {
                     c = p / r;
                     p = c * d[i] - s * g;
                     d[i + 1] = h + s * (c * g + s * d[i]);
-                    double* vi = &at(V, n, 0, i);
-                    double* vi1 = &at(V, n, 0, i + 1);
+                    if (ACCUMULATE) {
+                        double* vi = &at(V, n, 0, i);
+                        double* vi1 = &at(V, n, 0, i + 1);
 #pragma omp simd
-                    for (int k = 0; k < n; ++k) {
-                        const double hk = vi1[k];
-                        vi1[k] = s * vi[k] + c * hk;
-                        vi[k] = c * vi[k] - s * hk;
+                        for (int k = 0; k < n; ++k) {
+                            const double hk = vi1[k];
+                            vi1[k] = s * vi[k] + c * hk;
+                            vi[k] = c * vi[k] - s * hk;
+                        }
+                    } else {
+                        cs->push_back(c);
+                        sn->push_back(s);
                     }
                 }
                 p = -s * s2 * c3 * el1 * e[l] / dl1;
@@ -190,6 +198,14 @@ NLE_SIMD_CLONES bool ql_implicit(int n, double* V, double* d, double* e) {
         e[l] = 0.0;
     }
     return true;
+}
+
+// implicit QL on (d, e) accumulating rotations into V's columns
+NLE_SIMD_CLONES bool ql_implicit(int n, double* V, double* d, double* e) { return tql2<true>(n, V, d, e, nullptr, nullptr, nullptr); }
+
+// the same iteration recording the rotations of every sweep (phase 2 below)
+bool ql_record(int n, double* d, double* e, std::vector<Sweep>& sweeps, std::vector<double>& cs, std::vector<double>& sn) {
+    return tql2<false>(n, nullptr, d, e, &sweeps, &cs, &sn);
 }
 
 // ---- the same solver in three barrier-free phases (what sym_eigen_top runs)
@@ -342,87 +358,29 @@ void tridiag_reduce(int n, double* V, double* d, double* e, double* hs) {
     tridiag_reduce_impl(n, V, d, e, hs, kLe, kLt);
 }
 
-struct Sweep {
-    int l, m;      // rotations act on columns (i, i+1) for i = m-1 .. l
-    size_t first;  // index of the i = m-1 rotation in the (c, s) lists
+// M's lower triangle mirrored into V (n x n; SelfAdjointEigenSolver reads only the lower one)
+void mirror_lower(const double* M, int n, double* V) {
+    for (int c = 0; c < n; ++c)
+        for (int r = 0; r < n; ++r) V[(size_t)c * n + r] = (r >= c) ? M[(size_t)c * n + r] : M[(size_t)r * n + c];
+}
+
+// the mirrored M after tridiag_reduce: Householder vectors in V, their scales in hs, T in (d, e)
+struct Reduced {
+    std::vector<double> V, d, e, hs;
 };
-
-// RECORD == false: the same iteration (bit-identical eigenvalues) without keeping the rotations -- for callers that take
-// their eigenvectors from inverse iteration
-template <bool RECORD>
-bool ql_iterate(int n, double* d, double* e, std::vector<Sweep>& sweeps, std::vector<double>& cs, std::vector<double>& sn) {
-    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
-    e[n - 1] = 0.0;
-    double f = 0.0, tst1 = 0.0;
-    const double eps = std::ldexp(1.0, -52);
-    for (int l = 0; l < n; ++l) {
-        tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
-        int m = l;
-        while (m < n) {
-            if (std::fabs(e[m]) <= eps * tst1) break;
-            ++m;
-        }
-        if (m > l) {
-            int iter = 0;
-            do {
-                if (++iter > 60) return false;
-                double g = d[l];
-                double p = (d[l + 1] - g) / (2.0 * e[l]);
-                double r = hyp(p, 1.0);
-                if (p < 0) r = -r;
-                d[l] = e[l] / (p + r);
-                d[l + 1] = e[l] * (p + r);
-                const double dl1 = d[l + 1];
-                double h = g - d[l];
-                for (int i = l + 2; i < n; ++i) d[i] -= h;
-                f += h;
-                p = d[m];
-                double c = 1.0, c2 = c, c3 = c;
-                const double el1 = e[l + 1];
-                double s = 0.0, s2 = 0.0;
-                if (RECORD) sweeps.push_back(Sweep{l, m, cs.size()});
-                for (int i = m - 1; i >= l; --i) {
-                    c3 = c2;
-                    c2 = c;
-                    s2 = s;
-                    g = c * e[i];
-                    h = c * p;
-                    r = hyp(p, e[i]);
-                    e[i + 1] = s * r;
-                    s = e[i] / r;
-                    c = p / r;
-                    p = c * d[i] - s * g;
-                    d[i + 1] = h + s * (c * g + s * d[i]);
-                    if (RECORD) {
-                        cs.push_back(c);
-                        sn.push_back(s);
-                    }
-                }
-                p = -s * s2 * c3 * el1 * e[l] / dl1;
-                e[l] = s * p;
-                d[l] = c * p;
-            } while (std::fabs(e[l]) > eps * tst1);
-        }
-        d[l] += f;
-        e[l] = 0.0;
-    }
-    return true;
+Reduced reduce_lower(const double* M, int n) {
+    Reduced t{std::vector<double>((size_t)n * n), std::vector<double>(n), std::vector<double>(n), std::vector<double>(n)};
+    mirror_lower(M, n, t.V.data());
+    tridiag_reduce(n, t.V.data(), t.d.data(), t.e.data(), t.hs.data());
+    return t;
 }
 
-bool ql_record(int n, double* d, double* e, std::vector<Sweep>& sweeps, std::vector<double>& cs, std::vector<double>& sn) {
-    return ql_iterate<true>(n, d, e, sweeps, cs, sn);
-}
 // Eigenvalues only, by the square-root-free QL variant of Pal, Walker and Kahan as LAPACK's dsterf organises it (implicit
 // Wilkinson shift; deflation where e_m^2 <= eps^2 |d_m d_{m+1}|; 2 x 2 blocks in closed form, dlae2): one reciprocal
 // and a handful of multiplications per rotation instead of tql2's two hypot calls -- 0.22 -> ~0.1 ms at n = 196.
 // d: diagonal, e[1..n): sub-diagonal (e[i] couples i-1 and i) on entry; d holds the eigenvalues (unsorted) on return.
 bool ql_values(int n, double* d, double* e2) {
     if (n <= 1) return true;
-    if (std::getenv("NLE_EIG_TQL") != nullptr) {  // the rotation-based iteration (what ql_record runs)
-        std::vector<Sweep> sweeps;
-        std::vector<double> cs, sn;
-        return ql_iterate<false>(n, d, e2, sweeps, cs, sn);
-    }
     const double eps = std::ldexp(1.0, -53), eps2 = eps * eps, safmin = 2.2250738585072014e-308;
     double anorm = 0.0;
     for (int i = 0; i < n; ++i) anorm = std::max(anorm, std::fabs(d[i]) + (i + 1 < n ? std::fabs(e2[i + 1]) : 0.0) + std::fabs(e2[i]));
@@ -599,53 +557,6 @@ NLE_SIMD_CLONES void back_transform_cols(int n, const double* V, const double* h
     for (int jb = j0; jb < j1; jb += CB) back_transform_block<CB>(n, V, hs, Y + (size_t)jb * n, std::min(CB, j1 - jb));
 }
 
-// CPUs that share the calling thread's last-level cache (Linux sysfs), empty if unknown: where helper threads are
-// pinned when NLE_PIN_THREADS is set (left to the scheduler on a 256-CPU host they start on other core complexes,
-// with cold caches and a remote copy of the matrix).
-std::vector<int> llc_siblings() {
-    std::vector<int> cpus;
-#if defined(__linux__)
-    const int cpu = sched_getcpu();
-    if (cpu < 0) return cpus;
-    char path[128];
-    std::snprintf(path, sizeof path, "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", cpu);
-    FILE* fh = std::fopen(path, "r");
-    if (!fh) return cpus;
-    char buf[512] = {0};
-    if (std::fgets(buf, sizeof buf, fh)) {
-        const char* q = buf;
-        while (*q) {  // "a-b,c,d-e"
-            char* end = nullptr;
-            long a = std::strtol(q, &end, 10);
-            if (end == q) break;
-            long b = a;
-            if (*end == '-') {
-                q = end + 1;
-                b = std::strtol(q, &end, 10);
-            }
-            for (long c = a; c <= b && cpus.size() < 256; ++c) cpus.push_back((int)c);
-            q = (*end == ',') ? end + 1 : end;
-            if (*end != ',') break;
-        }
-    }
-    std::fclose(fh);
-#endif
-    return cpus;
-}
-
-void pin_to(std::thread& t, const std::vector<int>& cpus) {
-#if defined(__linux__)
-    if (cpus.empty()) return;
-    cpu_set_t set;
-    CPU_ZERO(&set);
-    for (int c : cpus) CPU_SET(c, &set);
-    (void)pthread_setaffinity_np(t.native_handle(), sizeof set, &set);
-#else
-    (void)t;
-    (void)cpus;
-#endif
-}
-
 template <typename F>
 void run_split(int nparts, int nthreads, F&& body) {  // body(part) for part in [0, nparts), split over threads
     nthreads = std::max(1, std::min(nthreads, nparts));
@@ -653,16 +564,11 @@ void run_split(int nparts, int nthreads, F&& body) {  // body(part) for part in 
         for (int q = 0; q < nparts; ++q) body(q);
         return;
     }
-    static const bool pin = std::getenv("NLE_PIN_THREADS") != nullptr;  // opt-in, see default_threads
-    const std::vector<int> near = pin ? llc_siblings() : std::vector<int>();
     std::vector<std::thread> th;
     auto work = [&](int t) {
         for (int q = t; q < nparts; q += nthreads) body(q);
     };
-    for (int t = 1; t < nthreads; ++t) {
-        th.emplace_back(work, t);
-        pin_to(th.back(), near);
-    }
+    for (int t = 1; t < nthreads; ++t) th.emplace_back(work, t);
     work(0);
     for (auto& x : th) x.join();
 }
@@ -939,12 +845,7 @@ bool cholesky_with_inverse(const double* M, int n, double* L, double* Linv, doub
 
 bool sym_eigen(const double* M, int n, double* U, double* D) {
     if (n <= 0) return true;
-    // mirror the lower triangle (SelfAdjointEigenSolver reads only the lower one)
-    for (int c = 0; c < n; ++c)
-        for (int r = 0; r < n; ++r) {
-            const double v = (r >= c) ? M[(size_t)c * n + r] : M[(size_t)r * n + c];
-            U[(size_t)c * n + r] = v;
-        }
+    mirror_lower(M, n, U);
     std::vector<double> e(n);
     if (n == 1) {
         D[0] = U[0];
@@ -969,16 +870,13 @@ bool sym_eigen(const double* M, int n, double* U, double* D) {
 
 // Threads for the two parallel phases.  Measured on the GPU box's host (EPYC 9575F, a 16-CPU quota over 256 logical
 // CPUs shared with other tenants), n = 200: helpers left to the scheduler start on other core complexes and make the
-// solve slower (1.3 -> 1.8-2.8 ms); pinned to the caller's L3 domain (NLE_PIN_THREADS=1) they gain a little (all
-// eigenvectors 1.90 -> 1.35 ms on four threads, top 50 1.27 -> 1.14 ms on two) but stall for milliseconds whenever
-// that domain is busy with somebody else's work, which a shared host cannot rule out.  So: one thread below
-// n = 512; from there eight unpinned helpers pay (n = 900, all eigenvectors: 124 -> ~70 ms).  NLE_EIG_THREADS overrides.
+// solve slower (1.3 -> 1.8-2.8 ms); pinned to the caller's L3 domain they gained a little (all eigenvectors 1.90 -> 1.35
+// ms on four threads, top 50 1.27 -> 1.14 ms on two) but stalled for milliseconds whenever that domain was busy with
+// somebody else's work, which a shared host cannot rule out.  So: one thread below n = 512; from there eight unpinned
+// helpers pay (n = 900, all eigenvectors: 124 -> ~70 ms).
 void run_parts(int nparts, int nthreads, const std::function<void(int)>& body) { run_split(nparts, nthreads, body); }
 
-int default_threads(int n, int) {
-    if (const char* e = std::getenv("NLE_EIG_THREADS")) return std::max(1, std::atoi(e));
-    return n >= 512 ? 8 : 1;
-}
+int default_threads(int n, int) { return n >= 512 ? 8 : 1; }
 
 // x <- x minus its components along the m orthonormal vectors z_0 .. z_{m-1} (stride n), two passes.  Four vectors at a
 // time: their four dot products in ONE sweep over x (independent accumulators), their combined update in one more -- half the
@@ -1385,18 +1283,12 @@ bool tridiag_inverse_iteration(int n, const double* d, const double* e, const do
         }
         return true;
     };
-    static const bool no_block = std::getenv("NLE_EIG_NO_BLOCK") != nullptr;
     std::vector<char> done_group(ngroups, 0);
-    if (!no_block)
-        for (int g = 0; g < ngroups; ++g)
-            if (starts[g + 1] - starts[g] >= kBlockMin) {
-                const bool blk = do_group_block(starts[g], starts[g + 1]);
-                if (std::getenv("NLE_EIG_TRACE"))
-                    std::fprintf(stderr, "[nle eig] cluster of %d vectors: %s\n", starts[g + 1] - starts[g],
-                                 blk ? "block inverse iteration + Cholesky-QR" : "block form gave up, vector by vector");
-                if (!blk && !do_group(starts[g], starts[g + 1])) return false;
-                done_group[g] = 1;
-            }
+    for (int g = 0; g < ngroups; ++g)
+        if (starts[g + 1] - starts[g] >= kBlockMin) {
+            if (!do_group_block(starts[g], starts[g + 1]) && !do_group(starts[g], starts[g + 1])) return false;
+            done_group[g] = 1;
+        }
 #if defined(__x86_64__)
     {   // isolated eigenvalues (clusters of one: nothing to orthogonalise against), eight per sweep
         static const bool x8 = __builtin_cpu_supports("avx512f") && std::getenv("NLE_EIG_NO_X8") == nullptr;
@@ -1428,8 +1320,7 @@ bool tridiag_inverse_iteration(int n, const double* d, const double* e, const do
         const double m = done_group[g] ? 0.0 : starts[g + 1] - starts[g];
         work += m * n * (8.0 + m);
     }
-    int nthreads = (ngroups >= 2 && work > 3e5) ? std::min(4, ngroups) : 1;
-    if (const char* ev = std::getenv("NLE_EIG_THREADS")) nthreads = std::max(1, std::min(std::atoi(ev), ngroups));
+    const int nthreads = (ngroups >= 2 && work > 3e5) ? std::min(4, ngroups) : 1;
     if (nthreads <= 1) {
         for (int g = 0; g < ngroups; ++g)
             if (!done_group[g] && !do_group(starts[g], starts[g + 1])) return false;
@@ -1481,16 +1372,13 @@ bool tridiag_eigenvectors(int n, const double* d, const double* e, const double*
 bool sym_eigen_top_reduced(int n, const double* V, const double* d_in, const double* e_in, const double* hs, int ncols,
                            int nthreads, double* U, double* D) {
     if (nthreads <= 0) nthreads = default_threads(n, ncols);
-    static const bool trace = std::getenv("NLE_EIG_TRACE") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = trace ? now() : 0.0;
     std::vector<double> d(d_in, d_in + n), e(e_in, e_in + n);
     const std::vector<double> d0(d), e0(e);  // T itself (the QL iteration overwrites d and e)
     std::vector<Sweep> sweeps;
     std::vector<double> cs, sn;
     // a leading part of the spectrum: the eigenvectors come from inverse iteration, the rotations are not needed (should
     // the inverse iteration give up, the iteration is repeated with recording below)
-    const bool invit = ncols > 0 && 2 * ncols <= n && std::getenv("NLE_EIG_NO_INVIT") == nullptr;
+    const bool invit = ncols > 0 && 2 * ncols <= n;
     if (invit || ncols == 0) {
         if (!ql_values(n, d.data(), e.data())) return false;
     } else {
@@ -1498,7 +1386,6 @@ bool sym_eigen_top_reduced(int n, const double* V, const double* d_in, const dou
         sn.reserve((size_t)n * n);
         if (!ql_record(n, d.data(), e.data(), sweeps, cs, sn)) return false;
     }
-    const double t1 = trace ? now() : 0.0;
     // descending order (stable on the ascending sort the classic path uses, reversed)
     std::vector<int> idx(n);
     std::iota(idx.begin(), idx.end(), 0);
@@ -1509,15 +1396,11 @@ bool sym_eigen_top_reduced(int n, const double* V, const double* d_in, const dou
     if (invit) {
         // a leading part of the spectrum only: inverse iteration on T for those eigenvalues, then the back-transformation
         if (tridiag_inverse_iteration(n, d0.data(), e0.data(), D, ncols, U)) {
-            const double t2 = trace ? now() : 0.0;
             const int cparts0 = std::max(1, std::min(nthreads, (ncols + 3) / 4));
             run_split(cparts0, nthreads, [&](int q) {
                 const int j0 = (int)((long long)ncols * q / cparts0), j1 = (int)((long long)ncols * (q + 1) / cparts0);
                 back_transform_cols(n, V, hs, U, j0, j1);
             });
-            if (trace)
-                std::fprintf(stderr, "[nle eig] n = %d, %d vectors: QL %.3f ms, inverse iteration %.3f ms, back-transformation %.3f ms\n",
-                             n, ncols, t1 - t0, t2 - t1, now() - t2);
             return true;
         }
         // inverse iteration gave up: the rotations after all (same iteration, same eigenvalues)
@@ -1554,10 +1437,7 @@ bool sym_eigen_top(const double* M, int n, int ncols, int nthreads, double* U, d
         if (ncols) U[0] = 1.0;
         return true;
     }
-    std::vector<double> V((size_t)n * n), d(n), e(n), hs(n);
-    for (int c = 0; c < n; ++c)  // mirror the lower triangle (SelfAdjointEigenSolver reads only the lower one)
-        for (int r = 0; r < n; ++r) V[(size_t)c * n + r] = (r >= c) ? M[(size_t)c * n + r] : M[(size_t)r * n + c];
-    tridiag_reduce(n, V.data(), d.data(), e.data(), hs.data());
+    auto [V, d, e, hs] = reduce_lower(M, n);
     return sym_eigen_top_reduced(n, V.data(), d.data(), e.data(), hs.data(), ncols, nthreads, U, D);
 }
 
@@ -1723,10 +1603,7 @@ bool sym_eigen_select(const double* M, int n, double* D, int first, int count, d
         if (count > 0) U[0] = 1.0;
         return true;
     }
-    std::vector<double> V((size_t)n * n), d(n), e(n), hs(n);
-    for (int c = 0; c < n; ++c)  // mirror the lower triangle (SelfAdjointEigenSolver reads only the lower one)
-        for (int r = 0; r < n; ++r) V[(size_t)c * n + r] = (r >= c) ? M[(size_t)c * n + r] : M[(size_t)r * n + c];
-    tridiag_reduce(n, V.data(), d.data(), e.data(), hs.data());
+    auto [V, d, e, hs] = reduce_lower(M, n);
     const std::vector<double> d0(d), e0(e);
     if (!ql_values(n, d.data(), e.data())) return false;
     std::sort(d.begin(), d.end(), [](double a, double b) { return a > b; });
@@ -1760,10 +1637,7 @@ bool sym_eigen_below(const double* M, int n, double eps, int max_below, int* kep
         if (n - kept <= max_below) std::copy(D.begin() + kept, D.end(), Dbelow);
         return true;
     }
-    std::vector<double> V((size_t)n * n), d(n), e(n), hs(n);
-    for (int c = 0; c < n; ++c)
-        for (int r = 0; r < n; ++r) V[(size_t)c * n + r] = (r >= c) ? M[(size_t)c * n + r] : M[(size_t)r * n + c];
-    tridiag_reduce(n, V.data(), d.data(), e.data(), hs.data());
+    auto [V, d, e, hs] = reduce_lower(M, n);
     const SturmT t = sturm_setup(n, d.data(), e.data());
     const int kept = n - sturm_count1(t, eps);
     *kept_out = kept;
@@ -1792,8 +1666,7 @@ bool sym_eigen_below(const double* M, int n, double eps, int max_below, int* kep
 bool sym_eigen_blocked(const double* M, int n, double* U, double* D) {
     if (n <= 2) return sym_eigen(M, n, U, D);
     std::vector<double> V((size_t)n * n), d(n), e(n);
-    for (int c = 0; c < n; ++c)
-        for (int r = 0; r < n; ++r) V[(size_t)c * n + r] = (r >= c) ? M[(size_t)c * n + r] : M[(size_t)r * n + c];
+    mirror_lower(M, n, V.data());
     tridiagonalize(n, V.data(), d.data(), e.data());
     std::vector<Sweep> sweeps;
     std::vector<double> cs, sn;
@@ -1830,18 +1703,10 @@ bool eigen_decomposition_topk(const double* M, int n, double eps, int kmax, doub
         std::copy(D.begin(), D.begin() + kmax, Dk);
         return true;
     }
-    static const bool trace = std::getenv("NLE_EIG_TRACE") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = trace ? now() : 0.0;
-    std::vector<double> V((size_t)n * n), d(n), e(n), hs(n);
-    for (int c = 0; c < n; ++c)  // mirror the lower triangle (SelfAdjointEigenSolver reads only the lower one)
-        for (int r = 0; r < n; ++r) V[(size_t)c * n + r] = (r >= c) ? M[(size_t)c * n + r] : M[(size_t)r * n + c];
-    tridiag_reduce(n, V.data(), d.data(), e.data(), hs.data());
-    const double t1 = trace ? now() : 0.0;
+    auto [V, d, e, hs] = reduce_lower(M, n);
     const SturmT t = sturm_setup(n, d.data(), e.data());
     *r_out = n - sturm_count1(t, eps);  // descending order: the leading run >= eps IS the count of eigenvalues >= eps
     sturm_eigenvalues_desc(t, 0, kmax, Dk);
-    const double t2 = trace ? now() : 0.0;
     if (kmax == 0) return true;
     if (!tridiag_inverse_iteration(n, d.data(), e.data(), Dk, kmax, U)) {
         std::vector<double> D(n);
@@ -1849,11 +1714,7 @@ bool eigen_decomposition_topk(const double* M, int n, double eps, int kmax, doub
         std::copy(D.begin(), D.begin() + kmax, Dk);
         return true;
     }
-    const double t3 = trace ? now() : 0.0;
     back_transform_cols(n, V.data(), hs.data(), U, 0, kmax);
-    if (trace)
-        std::fprintf(stderr, "[nle eig] n = %d, %d pairs: reduction %.3f ms, bisection %.3f ms, inverse iteration %.3f ms, back-transformation %.3f ms\n",
-                     n, kmax, t1 - t0, t2 - t1, t3 - t2, now() - t3);
     return true;
 }
 

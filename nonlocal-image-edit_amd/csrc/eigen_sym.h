@@ -23,7 +23,7 @@ bool eigen_decomposition(const double* M, int n, double eps, double* U, double* 
 bool eigen_decomposition_top(const double* M, int n, double eps, int kmax, double* U, double* D, int* r);
 
 // All eigenvalues DESCENDING in D and the first `ncols` eigenvectors in U (n x ncols); nthreads <= 0 picks the
-// default (1; NLE_EIG_THREADS overrides).  The rotation and back-transformation phases need no barriers and
+// default (1 below n = 512, else 8).  The rotation and back-transformation phases need no barriers and
 // can run on short-lived threads.
 bool sym_eigen_top(const double* M, int n, int ncols, int nthreads, double* U, double* D);
 // the same for a matrix already reduced to tridiagonal form (V, hs: the Householder vectors and scales; d, e: T), e.g.
@@ -76,8 +76,8 @@ void gemm_nn_cols(const double* A, const double* B, double* C, int m, int k, int
 void gemm_nt_cols(const double* A, const double* B, double* C, int m, int k, int n, int j0, int j1);
 void gemm_tn_cols(const double* A, const double* B, double* C, int m, int k, int n, int j0, int j1);
 
-// body(part) for part in [0, nparts) on up to nthreads threads (the caller's plus short-lived helpers pinned to its
-// L3 domain); parts are dealt round-robin
+// body(part) for part in [0, nparts) on up to nthreads threads (the caller's plus short-lived helpers); parts are dealt
+// round-robin
 void run_parts(int nparts, int nthreads, const std::function<void(int)>& body);
 
 }  // namespace nleh

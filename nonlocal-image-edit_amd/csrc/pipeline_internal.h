@@ -390,7 +390,8 @@ inline void all_reduce(nle_ctx* c, double* d, size_t n) {
 // A rank-local verdict that the collectives after it depend on (does Phi fit HERE?  which formulation?) is agreed over the
 // ranks before anything acts on it: the number of ranks on which `flag` holds.  Without this a rank that refuses (or picks
 // another formulation) leaves its peers blocked in their next all-reduce.  One 8-byte all-reduce; nothing when world == 1.
-// (The tests inject a dissenting rank through the all-reduce callback: this is the only one-double all-reduce.)
+// (The tests inject a dissenting rank through the all-reduce callback, which sees every call of this one as a one-double
+// all-reduce: the refusals and the streaming choice of pipeline.hip, and the solver fallbacks of ortho.hip.)
 inline int ranks_where(nle_ctx* c, bool flag) {
     if (c->world <= 1 && !c->comm) return flag ? 1 : 0;
     DevBuf<double> d(1);

@@ -6,8 +6,8 @@
 // the host solve is 1.09 ms = reduction 0.44 + QL 0.22 + inverse iteration 0.20 + back-transformation 0.20; this kernel
 // does the reduction in 0.66 ms (3.3 us per step: five workgroup barriers, two single-wave sections and ~300 dependent
 // fp64 operations per step on ONE compute unit), so with it the solve takes 1.39 ms.  A 4.3 GHz host core wins a
-// 200-step latency chain.  The kernel stays as an opt-in (NLE_DEVICE_TRIDIAG=1, nle_eigen_decomposition_top_device) with
-// its test; the O(n^2) rest -- QL, inverse iteration for the K kept eigenvectors, their back-transformation -- is the
+// 200-step latency chain.  The kernel stays behind nle_eigen_decomposition_top_device, with its test; the train path does
+// not use it.  The O(n^2) rest -- QL, inverse iteration for the K kept eigenvectors, their back-transformation -- is the
 // host's either way (eigen_sym.cpp: eigen_decomposition_top_reduced).
 //
 // Same algorithm, storage and scaling as tridiag_reduce in eigen_sym.cpp (the EISPACK tred2 recurrence: rows n-1 .. 1,

@@ -15,7 +15,11 @@ def test_product_sources_have_no_ablation_hooks():
 
 # Environment switches whose variants were taken out (nothing but the switch reached them): no source may read them again
 REMOVED_SWITCHES = ("NLE_HIST_UNTILED", "NLE_PROJECT_HIST", "NLE_EAGER_V", "NLE_APPLY_WITH_V", "NLE_HOST_ORTHO",
-                    "NLE_PROJECT_CHUNKED", "NLE_NO_SORTED_EXPAND")
+                    "NLE_PROJECT_CHUNKED", "NLE_NO_SORTED_EXPAND",
+                    # the solver layer's tuning and measurement switches
+                    "NLE_DEVICE_TRIDIAG", "NLE_WA_SERIAL", "NLE_NO_DEFLATE", "NLE_HOST_THREADS", "NLE_EIG_TQL",
+                    "NLE_EIG_NO_BLOCK", "NLE_EIG_NO_INVIT", "NLE_EIG_THREADS", "NLE_PIN_THREADS", "NLE_EIG_TRACE",
+                    "NLE_SYTRD_CW", "NLE_SYTRD_PROBE")
 
 
 def test_product_sources_read_no_removed_switches():
