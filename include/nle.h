@@ -109,6 +109,25 @@ int nle_ctx_set_mode(nle_ctx* ctx, int mode);
  * nle_compute_kernel and nle_nystrom included, returns NLE_ERR_INVALID.  0 <= radius <= NLE_PATCH_RADIUS_MAX. */
 #define NLE_PATCH_RADIUS_MAX 7
 int nle_ctx_set_patch_radius(nle_ctx* ctx, int radius);
+/* Sample selection, opt-in (new in this build: the reference always takes its Cartesian grid, src/filter.cpp:56-80).
+ *   NLE_SAMPLER_GRID      the reference's grid (default; bit for bit what this build always computed)
+ *   NLE_SAMPLER_FARTHEST  farthest-point selection in the affinity's own metric, same count p as the grid would take:
+ *     D(i, j) = (1/hx^2) (double)(dr^2 + dc^2) + (1/hy^2) dy^2   (dr dc integer, dy = (double)y_i - (double)y_j, no fma)
+ *     s_0 = pixel (H/2, W/2); then p - 1 times the pixel whose smallest D to the samples chosen so far is largest (ties
+ *     to the smallest row-major index).  The set is used in ascending row-major order (the reference's [selected; rest]).
+ * It always uses the single-value distance above, also with a patch radius R > 0 (which then applies to the affinities
+ * only).  Farthest applies to nle_train* and nle_compute_kernel64, in NLE_MODE_AUTO (which takes NLE_MODE_MATERIALISED_F64,
+ * or NLE_MODE_STREAMED_F64 by the memory rule), NLE_MODE_MATERIALISED_F64 and NLE_MODE_STREAMED_F64; the other modes, slab
+ * input at world > 1, nle_compute_kernel and nle_nystrom return NLE_ERR_INVALID.  At world > 1 (full-plane input) rank 0
+ * selects and the set reaches the other ranks through the fp64 all-reduce. */
+#define NLE_SAMPLER_GRID 0
+#define NLE_SAMPLER_FARTHEST 1
+int nle_ctx_set_sampler(nle_ctx* ctx, int sampler);
+/* The sample set the ctx's sampler takes on the FULL H x W plane d_lum (fp32; may be NULL for the grid): *p samples, their
+ * row-major indices ascending in h_idx (room for nle_sample_grid's n_sel_rows * n_sel_cols; may be NULL to learn *p).  A
+ * collective at world > 1 under NLE_SAMPLER_FARTHEST. */
+int nle_sample_pixels(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
+                      double hy, long long* h_idx, int* p);
 /* The Nystrom-extension GEMM Phi = K_AB^T (V_A Lambda^-1) (src/filter.cpp:275) of NLE_MODE_MATERIALISED and of nle_nystrom on
  * the bf16 matrix cores with SPLIT operands (each fp32 value as three bf16, six products, fp32 accumulate: fp32 accuracy at
  * ~2.7x the exact-fp32 MFMA's rate; plain bf16 operands miss the parity bar).  Off by default. */
@@ -283,6 +302,8 @@ int nle_filter_info(const nle_filter* f, long long* n_local, int* K, int* r, int
  *   [7] the same for Wa's inverse root. */
 int nle_filter_diag(const nle_filter* f, int* h_info);
 int nle_filter_eigvals(const nle_filter* f, double* h_eigvals /* K */);
+/* the filter's sample set: *p row-major pixel indices, ascending, in h_idx (may be NULL to learn *p) */
+int nle_filter_sample_pixels(const nle_filter* f, long long* h_idx, int* p);
 /* min / max coefficient of the first `ncols` eigenvectors over this rank's slab (what the reference
  * prints at src/filter.cpp:506): h_min[ncols], h_max[ncols].  A filter whose V is implicit projects just
  * these columns into a temporary; it does not materialise the N x K matrix. */

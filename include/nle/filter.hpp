@@ -205,6 +205,9 @@ public:
     // patch (non-local-means) affinities over (2 patchRadius + 1)^2 neighbourhoods for trainForEnhancement /
     // trainForDenoise / trainFilter (nle_ctx_set_patch_radius; new here, 0 = the reference's single-value affinity)
     int patchRadius = 0;
+    // sample selection for trainForEnhancement / trainForDenoise / trainFilter (nle_ctx_set_sampler; new here,
+    // NLE_SAMPLER_GRID = the reference's grid, NLE_SAMPLER_FARTHEST = farthest-point selection)
+    int sampler = 0;
 
 private:
     nle_ctx* ctx_ = nullptr;

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 MODE_AUTO, MODE_MATERIALISED, MODE_PHI_FREE, MODE_PHI_FREE_EXP, MODE_MATERIALISED_F64, MODE_STREAMED_F64 = (
     _abi.NLE_MODE_AUTO, _abi.NLE_MODE_MATERIALISED, _abi.NLE_MODE_PHI_FREE, _abi.NLE_MODE_PHI_FREE_EXP,
     _abi.NLE_MODE_MATERIALISED_F64, _abi.NLE_MODE_STREAMED_F64)
+SAMPLER_GRID, SAMPLER_FARTHEST = _abi.NLE_SAMPLER_GRID, _abi.NLE_SAMPLER_FARTHEST
 
 _lib = None
 
@@ -296,6 +297,22 @@ class Context:
         """patch (non-local-means) affinities over (2R + 1)^2 neighbourhoods, 0 <= R <= NLE_PATCH_RADIUS_MAX; 0 (default) is
         the reference's single-value affinity (nle_ctx_set_patch_radius)"""
         _check(lib().nle_ctx_set_patch_radius(self._h, int(radius)), self._h)
+
+    def set_sampler(self, sampler: int):
+        """sample selection: SAMPLER_GRID (0, default, the reference's grid) or SAMPLER_FARTHEST (1, farthest-point
+        selection in the affinity's metric; nle_ctx_set_sampler)"""
+        _check(lib().nle_ctx_set_sampler(self._h, int(sampler)), self._h)
+
+    def sample_pixels(self, lum, n_row_samples, n_col_samples, hx, hy):
+        """the ctx's sample set on the full plane `lum` (nle_sample_pixels): row-major pixel indices, ascending, int64"""
+        x = self._lum(lum)
+        H, W = x.shape
+        g = sample_grid(H, W, n_row_samples, n_col_samples)
+        out = np.zeros(g["n_sel_rows"] * g["n_sel_cols"], dtype=np.int64)
+        p = C.c_int()
+        _check(lib().nle_sample_pixels(self._h, C.c_void_p(x.data_ptr()), H, W, int(n_row_samples), int(n_col_samples),
+                                       float(hx), float(hy), _np_ptr(out), C.byref(p)), self._h)
+        return out[:p.value]
 
     def set_nystrom_bf16x3(self, on: bool = True):
         """the fused Nystrom GEMM on the bf16 matrix cores with split operands (nle_ctx_set_nystrom_bf16x3)"""
@@ -734,6 +751,14 @@ class NLEFilter:
         K = self.info()["K"]
         out = np.zeros(K, dtype=np.float64)
         _check(lib().nle_filter_eigvals(self._f, _np_ptr(out)))
+        return out
+
+    def sample_pixels(self):
+        """the sample set the filter was trained on (nle_filter_sample_pixels): row-major pixel indices, ascending"""
+        p = C.c_int()
+        _check(lib().nle_filter_sample_pixels(self._f, None, C.byref(p)))
+        out = np.zeros(p.value, dtype=np.int64)
+        _check(lib().nle_filter_sample_pixels(self._f, _np_ptr(out), C.byref(p)))
         return out
 
     def eigvecs(self):

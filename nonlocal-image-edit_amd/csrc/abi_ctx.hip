@@ -323,6 +323,16 @@ int nle_ctx_set_patch_radius(nle_ctx* ctx, int radius) {
     });
 }
 
+int nle_ctx_set_sampler(nle_ctx* ctx, int sampler) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (sampler != NLE_SAMPLER_GRID && sampler != NLE_SAMPLER_FARTHEST)
+            throw Fail{NLE_ERR_INVALID, "sampler must be NLE_SAMPLER_GRID (0) or NLE_SAMPLER_FARTHEST (1), got " +
+                                            std::to_string(sampler)};
+        ctx->sampler = sampler;
+    });
+}
+
 int nle_ctx_set_mode(nle_ctx* ctx, int mode) {
     if (!ctx || mode < 0 || mode > NLE_MODE_STREAMED_F64) return NLE_ERR_INVALID;
     ctx->mode = mode;

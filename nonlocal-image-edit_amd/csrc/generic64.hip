@@ -38,7 +38,7 @@ constexpr int kAff64Pix = 64;
 __global__ __launch_bounds__(256) void k_affinity64(const float* __restrict__ lum, GridSpec gs,
                                                     const Sample4* __restrict__ samples, int p, int ld, double sw,
                                                     double pw, long long pix0, long long M, double* __restrict__ kab,
-                                                    int skip_samples) {
+                                                    int skip_samples, const unsigned* __restrict__ smask) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw64[];
     int2* srow_col = reinterpret_cast<int2*>(smem_raw64);                       // [ld]
     double* sval = reinterpret_cast<double*>(smem_raw64 + (size_t)ld * sizeof(int2));  // [ld]
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_affinity64(const float* __restrict__ lu
             const long long gi = pix0 + i0 + il;
             const int row = (int)(gi / gs.W), col = (int)(gi - (long long)row * gs.W);
             const double x = (double)lum[gi];
-            const bool zero_row = skip_samples && is_sample_pixel(gs, row, col);
+            const bool zero_row = skip_samples && is_sample(gs, smask, gi, row, col);
             double2 o = make_double2(0.0, 0.0);
             const unsigned s0 = 2 * q;
             if (!zero_row) {
@@ -84,13 +84,13 @@ __global__ __launch_bounds__(256) void k_affinity64(const float* __restrict__ lu
 }
 
 hipError_t affinity64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, int ld, double sw,
-                      double pw, long long pix0, long long M, double* d_kab, bool skip_samples) {
+                      double pw, long long pix0, long long M, double* d_kab, bool skip_samples, const unsigned* d_smask) {
     if (M <= 0) return hipSuccess;
     if (ld & 1) return hipErrorInvalidValue;   // rows are written two doubles at a time (ld = nle_ld(p) is a multiple of 4)
     const long long ngroups = (M + kAff64Pix - 1) / kAff64Pix;
     const int grid = (int)std::min<long long>(ngroups, 16384);
     hipLaunchKernelGGL(k_affinity64, dim3((unsigned)grid), dim3(256), (size_t)ld * (sizeof(int2) + sizeof(double)), s, d_lum, gs,
-                       d_samples, p, ld, sw, pw, pix0, M, d_kab, skip_samples ? 1 : 0);
+                       d_samples, p, ld, sw, pw, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask);
     return hipGetLastError();
 }
 

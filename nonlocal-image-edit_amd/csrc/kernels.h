@@ -30,6 +30,11 @@ __device__ __forceinline__ bool is_sample_pixel(const GridSpec& gs, int row, int
     const int qr = dr / gs.rowStep, qc = dc / gs.colStep;
     return (qr * gs.rowStep == dr) && (qc * gs.colStep == dc) && qr < gs.nSelRows && qc < gs.nSelCols;
 }
+// the sample predicate of pixel gi = (row, col): bit gi of a listed set's mask (NLE_SAMPLER_FARTHEST), or the grid's
+// closed form when there is no mask
+__device__ __forceinline__ bool is_sample(const GridSpec& gs, const unsigned* smask, long long gi, int row, int col) {
+    return smask ? ((smask[gi >> 5] >> (unsigned)(gi & 31)) & 1u) != 0 : is_sample_pixel(gs, row, col);
+}
 #endif
 
 // composite launchers report each kernel they enqueue so that the caller can time them separately
@@ -136,8 +141,11 @@ hipError_t hist_tables(hipStream_t s, GridSpec gs, const Sample4* d_samples, int
                        int nrows_local, double* d_er, double* d_ecT, double* d_Ep);
 
 // ---- the literal decomposition in fp64 (generic64.hip): auto mode's fallback and the stage-level API
+// d_smask (optional): with skip_samples, the rows zeroed are those of the pixels whose bit is set (ceil(N / 32) words, bit
+// i % 32 of word i / 32 = pixel i) instead of the grid's
 hipError_t affinity64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, int ld, double sw,
-                      double pw, long long pix0, long long M, double* d_kab, bool skip_samples = false);
+                      double pw, long long pix0, long long M, double* d_kab, bool skip_samples = false,
+                      const unsigned* d_smask = nullptr);
 // patch (non-local-means) affinity rows, patch.hip: the rows affinity64 fills, with the intensity term pwd * S_ij, S_ij the
 // integer sum of squared differences of the (2R + 1)^2 patches (reflect-101 borders), 1 <= R <= 7, plane integer in [0, 255].
 // d_spatch: patch_spatch_bytes(p, R) bytes, sample j's patch values - 128 as int8 in row j (patch_kpad(R) bytes, zero
@@ -148,7 +156,17 @@ size_t patch_spatch_bytes(int p, int R);
 hipError_t patch_gather(hipStream_t s, const float* d_lum, int H, int W, int R, const long long* d_pix, int n, int* d_out);
 hipError_t patch_affinity64(hipStream_t s, const float* d_lum, GridSpec gs, int R, const Sample4* d_samples,
                             const signed char* d_spatch, const int* d_snorm, int p, int ld, double sw, double pwd,
-                            long long pix0, long long M, double* d_kab, bool skip_samples = false);
+                            long long pix0, long long M, double* d_kab, bool skip_samples = false,
+                            const unsigned* d_smask = nullptr);
+// farthest-point sample selection (sampler.hip): the p pixels of NLE_SAMPLER_FARTHEST in the order chosen, into d_list (p
+// ints), for the full H x W plane d_lum.  Workspace: d_m (H W doubles), d_pv / d_pi (2 farthest_max_blocks() each).
+int farthest_max_blocks();
+hipError_t farthest_samples(hipStream_t s, const float* d_lum, int H, int W, int p, double sw, double pw, double* d_m,
+                            double* d_pv, int* d_pi, int* d_list);
+// d_out[k] = d_lum[d_pix[k]]
+hipError_t gather_pix(hipStream_t s, const float* d_lum, const long long* d_pix, int n, float* d_out);
+// d_mask (ceil(N / 32) words) = the bitmask of the pixels d_pix[0 .. n)
+hipError_t sample_mask(hipStream_t s, const long long* d_pix, int n, long long N, unsigned* d_mask);
 hipError_t add64(hipStream_t s, double* d_y, const double* d_x, size_t n);  // y += x
 hipError_t row_scalings64(hipStream_t s, const double* d_X, long long M, int ld, int r, const double* d_u, double eps,
                           double* d_out);

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_patch_affinity64(const float* __restric
                                                           const signed char* __restrict__ spatch,
                                                           const int* __restrict__ snorm, int p, int ld, double sw, double pwd,
                                                           long long pix0, long long M, double* __restrict__ kab,
-                                                          int skip_samples) {
+                                                          int skip_samples, const unsigned* __restrict__ smask) {
     // the exponent is rounded operation by operation, as the definition (and build_Ka on the host) evaluates it: a
     // contracted fma would round -sw d2 - pwd S once instead of twice, ~1 ulp of a large exponent
 #pragma clang fp contract(off)
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void k_patch_affinity64(const float* __restric
                 const unsigned il = f / nq, q = f - il * nq;
                 const long long gi = pix0 + i0 + il;
                 const int row = (int)(gi / gs.W), col = (int)(gi - (long long)row * gs.W);
-                const bool zero_row = skip_samples && is_sample_pixel(gs, row, col);
+                const bool zero_row = skip_samples && is_sample(gs, smask, gi, row, col);
                 double v[2] = {0.0, 0.0};
                 if (!zero_row) {
                     const int xn = pn[il];
@@ -182,7 +182,7 @@ size_t patch_spatch_bytes(int p, int R) { return (size_t)((p + 15) & ~15) * patc
 
 hipError_t patch_affinity64(hipStream_t s, const float* d_lum, GridSpec gs, int R, const Sample4* d_samples,
                             const signed char* d_spatch, const int* d_snorm, int p, int ld, double sw, double pwd,
-                            long long pix0, long long M, double* d_kab, bool skip_samples) {
+                            long long pix0, long long M, double* d_kab, bool skip_samples, const unsigned* d_smask) {
     if (M <= 0) return hipSuccess;
     if ((ld & 1) || R < 1 || R > 7 || ld < p) return hipErrorInvalidValue;
     const long long ngroups = (M + kPatchPix - 1) / kPatchPix;
@@ -192,7 +192,7 @@ hipError_t patch_affinity64(hipStream_t s, const float* d_lum, GridSpec gs, int 
     const int ks = patch_kpad(R) / 64;
 #define NLE_PATCH_LAUNCH(KS_)                                                                                            \
     hipLaunchKernelGGL(k_patch_affinity64<KS_>, dim3((unsigned)grid), dim3(256), lds, s, d_lum, gs, R, d_samples, d_spatch, \
-                       d_snorm, p, ld, sw, pwd, pix0, M, d_kab, skip_samples ? 1 : 0)
+                       d_snorm, p, ld, sw, pwd, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask)
     switch (ks) {
         case 1: NLE_PATCH_LAUNCH(1); break;
         case 2: NLE_PATCH_LAUNCH(2); break;

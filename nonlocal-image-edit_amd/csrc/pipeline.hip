@@ -18,17 +18,20 @@ struct SampleSet {
     bool quantised = false;         // whole plane integer valued in [0, 255] (checked on request)
     unsigned level_tiles = 0xffffu; // then: which 16-level tiles occur in this rank's part of the plane (bit t)
     int R = 0;                      // patch radius (nle_ctx_set_patch_radius)
+    bool listed = false;            // pix is a sampler's list (NLE_SAMPLER_FARTHEST), not the grid's closed form
     std::vector<int> patch;         // R > 0: p x (2R + 1)^2 patch values around each sample (reflect-101), row per sample
 };
 
 // d_lum: base of the FULL plane -- real, or virtual when the ctx takes slab input (only rows [row0, row1) of this rank
 // exist; the p sample values and the "integer valued" verdict are then completed by an all-reduce).  R > 0: also the
-// samples' patches (full plane only: the caller refuses slab input)
+// samples' patches (full plane only: the caller refuses slab input).  list: the sample pixels of NLE_SAMPLER_FARTHEST
+// (ascending, gs.p() of them; full plane only) instead of the grid's
 SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool check_quantised = false,
-                        bool slab_plane = false, int R = 0) {
+                        bool slab_plane = false, int R = 0, const std::vector<long long>* list = nullptr) {
     SampleSet s;
     s.gs = gs;
     s.p = gs.p();
+    if (list && ((int)list->size() != s.p || slab_plane)) throw Fail{NLE_ERR_INVALID, "fetch_samples: bad sample list"};
     s.val.resize(s.p);
     int flag = 1;
     int fl2[2] = {1, 0xffff};  // check_levels: [0] verdict, [1] level tiles
@@ -55,7 +58,14 @@ SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool
     } else {
         DevBuf<float> d_val(s.p);
         DevBuf<int> d_flag(2);
-        PROFILED(c, NLE_K_SMALL, nlek::gather_samples(c->stream, d_lum, gs, d_val.p));
+        DevBuf<long long> d_pix;
+        if (list) {
+            d_pix.alloc(s.p);
+            HIP_OK(hipMemcpyAsync(d_pix.p, list->data(), s.p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+            PROFILED(c, NLE_K_SMALL, nlek::gather_pix(c->stream, d_lum, d_pix.p, s.p, d_val.p));
+        } else {
+            PROFILED(c, NLE_K_SMALL, nlek::gather_samples(c->stream, d_lum, gs, d_val.p));
+        }
         if (check_quantised) {
             PROFILED(c, NLE_K_SMALL, nlek::check_levels(c->stream, d_lum, (long long)gs.H * gs.W, d_flag.p));
             HIP_OK(hipMemcpyAsync(fl2, d_flag.p, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -68,9 +78,10 @@ SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool
     if (s.quantised && (fl2[1] & 0xffff) != 0) s.level_tiles = (unsigned)fl2[1] & 0xffffu;
     s.pix.resize(s.p);
     s.packed.resize(s.p);
+    s.listed = list != nullptr;
     for (int k = 0; k < s.p; ++k) {
-        const int r = gs.rowOff + (k / gs.nSelCols) * gs.rowStep;
-        const int cc = gs.colOff + (k % gs.nSelCols) * gs.colStep;
+        const int r = list ? (int)((*list)[k] / gs.W) : gs.rowOff + (k / gs.nSelCols) * gs.rowStep;
+        const int cc = list ? (int)((*list)[k] - (long long)r * gs.W) : gs.colOff + (k % gs.nSelCols) * gs.colStep;
         s.pix[k] = (long long)r * gs.W + cc;
         s.packed[k] = make_float4((float)r, (float)cc, s.val[k], 0.f);
     }
@@ -107,6 +118,52 @@ void check_patch_radius(const nle_ctx* c, int R, int H, int W) {
     if (c->slab_input && c->world > 1)
         throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need the full plane on every rank: slab input is not "
                                     "supported with them"};
+}
+
+// The checks of the farthest sampler that need no device; the ctx's mode is checked where it applies (nle_train*)
+void check_sampler(const nle_ctx* c, double hx, double hy) {
+    if (c->sampler != NLE_SAMPLER_FARTHEST) return;
+    if (!(hx > 0) || !(hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
+    if (c->slab_input && c->world > 1)
+        throw Fail{NLE_ERR_INVALID, "the farthest sampler needs the full plane on every rank: slab input is not supported "
+                                    "with it"};
+}
+
+// The sample pixels of NLE_SAMPLER_FARTHEST on the full plane d_lum (sampler.hip), ascending.  At world > 1 rank 0 selects
+// and the others receive the set through the fp64 all-reduce (they add zeros; indices < 2^31 are exact in fp64); the last
+// slot carries rank 0's failure, so that every rank returns the same verdict.
+std::vector<long long> farthest_list(nle_ctx* c, const float* d_lum, const GridSpec& gs, double hx, double hy) {
+    const int p = gs.p();
+    const long long N = (long long)gs.H * gs.W;
+    std::vector<long long> list(p);
+    std::vector<double> v((size_t)p + 1, 0.0);
+    if (c->rank == 0 || c->world <= 1) {
+        try {
+            const int nb = nlek::farthest_max_blocks();
+            DevBuf<double> d_m((size_t)N), d_pv((size_t)2 * nb);
+            DevBuf<int> d_pi((size_t)2 * nb), d_list(p);
+            std::vector<int> idx(p);
+            PROFILED(c, NLE_K_SMALL, nlek::farthest_samples(c->stream, d_lum, gs.H, gs.W, p, 1.0 / (hx * hx), 1.0 / (hy * hy),
+                                                            d_m.p, d_pv.p, d_pi.p, d_list.p));
+            HIP_OK(hipMemcpyAsync(idx.data(), d_list.p, p * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipStreamSynchronize(c->stream));
+            for (int k = 0; k < p; ++k) v[k] = (double)idx[k];
+        } catch (const Fail&) {
+            if (c->world <= 1) throw;
+            v[p] = 1.0;
+        }
+    }
+    if (c->world > 1) {
+        DevBuf<double> d_v((size_t)p + 1);
+        HIP_OK(hipMemcpyAsync(d_v.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        all_reduce(c, d_v.p, (size_t)p + 1);
+        HIP_OK(hipMemcpyAsync(v.data(), d_v.p, v.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        if (v[p] != 0.0) throw Fail{NLE_ERR_HIP, "the farthest sampler failed on rank 0"};
+    }
+    for (int k = 0; k < p; ++k) list[k] = (long long)v[k];
+    std::sort(list.begin(), list.end());
+    return list;
 }
 
 // Ka with patch affinities: S in exact integer arithmetic, the exponent in k_patch_affinity64's order (patch.hip)
@@ -157,12 +214,13 @@ void upload_patch_operands(nle_ctx* c, const SampleSet& s, PatchOperands* po) {
 // fp64 affinity rows [pix0, pix0 + M) (natural order, ld columns): k_affinity64, or the patch kernel when R > 0
 hipError_t affinity_rows64(hipStream_t st, const float* d_lum, const SampleSet& ss, const float4* d_samples,
                            const PatchOperands& po, int ld, double hx, double hy, long long pix0, long long M, double* d_kab,
-                           bool skip_samples = false) {
+                           bool skip_samples = false, const unsigned* d_smask = nullptr) {
     const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
-    if (ss.R <= 0) return nlek::affinity64(st, d_lum, ss.gs, d_samples, ss.p, ld, sw, pw, pix0, M, d_kab, skip_samples);
+    if (ss.R <= 0)
+        return nlek::affinity64(st, d_lum, ss.gs, d_samples, ss.p, ld, sw, pw, pix0, M, d_kab, skip_samples, d_smask);
     const double pwd = pw / ((2 * ss.R + 1) * (2 * ss.R + 1));
     return nlek::patch_affinity64(st, d_lum, ss.gs, ss.R, d_samples, po.spatch.p, po.snorm.p, ss.p, ld, sw, pwd, pix0, M, d_kab,
-                                  skip_samples);
+                                  skip_samples, d_smask);
 }
 
 // Ka(i,j), reference src/filter.cpp:128-137,144 (fp64, integer spatial term)
@@ -906,6 +964,15 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
     HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, st));
     PatchOperands po;
     upload_patch_operands(c, ss, &po);
+    DevBuf<unsigned> d_smask;  // a listed sample set: its rows are zeroed by bitmask instead of the grid's closed form
+    if (ss.listed) {
+        const long long N = (long long)ss.gs.H * ss.gs.W;
+        DevBuf<long long> d_spix(p);
+        d_smask.alloc((size_t)((N + 31) / 32));
+        HIP_OK(hipMemcpyAsync(d_spix.p, ss.pix.data(), p * sizeof(long long), hipMemcpyHostToDevice, st));
+        PROFILED(c, NLE_K_SMALL, nlek::sample_mask(st, d_spix.p, p, N, d_smask.p));
+        HIP_OK(hipStreamSynchronize(st));  // d_spix goes out of scope
+    }
     DevBuf<double> d_K((size_t)CH * ld), d_partial((size_t)nlek::kRowpassMaxBlocks * ld), d_zc(ld), d_z(ld), d_ones(ld),
         d_cbuf((size_t)std::max<long long>(M, 1));
     SampleSinkhorn sk(c, p, ld, T);
@@ -913,7 +980,8 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
     tr.mark("s64: alloc+upload");
     auto chunk_rows = [&](long long i0) { return std::min<long long>(CH, M - i0); };
     auto gen = [&](long long i0, long long mc) {
-        PROFILED(c, NLE_K_AFFINITY, affinity_rows64(st, d_lum, ss, d_samples.p, po, ld, hx, hy, pix0 + i0, mc, d_K.p, true));
+        PROFILED(c, NLE_K_AFFINITY, affinity_rows64(st, d_lum, ss, d_samples.p, po, ld, hx, hy, pix0 + i0, mc, d_K.p, true,
+                                                    d_smask.p));
     };
     auto pass_pixels = [&](int mode, bool last) {
         HIP_OK(hipMemsetAsync(d_z.p, 0, ld * sizeof(double), st));
@@ -1087,10 +1155,17 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) run in NLE_MODE_AUTO, NLE_MODE_MATERIALISED_F64 or "
                                     "NLE_MODE_STREAMED_F64 only"};
     check_patch_radius(c, R, H, W);
+    // the farthest sampler (a listed sample set): the fp64 formulations with explicit affinity rows only (the tables need a
+    // Cartesian set, the other forms are fp32); decided the same way on every rank
+    const bool farthest = c->sampler == NLE_SAMPLER_FARTHEST;
+    if (farthest && c->mode != NLE_MODE_AUTO && c->mode != NLE_MODE_MATERIALISED_F64 && c->mode != NLE_MODE_STREAMED_F64)
+        throw Fail{NLE_ERR_INVALID, "the farthest sampler runs in NLE_MODE_AUTO, NLE_MODE_MATERIALISED_F64 or "
+                                    "NLE_MODE_STREAMED_F64 only"};
+    check_sampler(c, hx, hy);
     // auto: the table form (all fp64) whenever it applies, else the literal decomposition in fp64 (generic64.hip).  The
     // fp32 formulations (materialised Phi, Phi-free with fp32 affinities) run only when asked for by mode: they miss
     // the 1e-4 bar on some well-posed inputs (DESIGN.md "Numerics").
-    const bool want_fuse = R == 0 && (c->mode == NLE_MODE_PHI_FREE || c->mode == NLE_MODE_PHI_FREE_EXP ||
+    const bool want_fuse = R == 0 && !farthest && (c->mode == NLE_MODE_PHI_FREE || c->mode == NLE_MODE_PHI_FREE_EXP ||
                                       (c->mode == NLE_MODE_AUTO && tables_ok));
     HIP_OK(hipSetDevice(c->device));
 
@@ -1110,7 +1185,10 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         // --- sample set, Ka and its eigenpairs (:486-491, host fp64)
         Timer tm_a(c->stream);
         tm_a.start();
-        SampleSet ss = fetch_samples(c, d_lum, gs, (want_fuse && tables_ok) || R > 0, c->slab_input && c->world > 1, R);
+        std::vector<long long> list;
+        if (farthest) list = farthest_list(c, d_lum, gs, hx, hy);
+        SampleSet ss = fetch_samples(c, d_lum, gs, (want_fuse && tables_ok) || R > 0, c->slab_input && c->world > 1, R,
+                                     farthest ? &list : nullptr);
         if (R > 0 && ranks_where(c, !ss.quantised) > 0)  // refused on every rank if the plane is not integer valued on one
             throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
                                         "(the L channel of 8-bit Lab)"};
@@ -1120,6 +1198,7 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
             throw Fail{NLE_ERR_INVALID, "Phi-free path: more than 256 samples needs an integer-valued luminance plane"};
         tr.mark("fetch_samples");
         f->p = ss.p;
+        f->h_sample_pix = ss.pix;
         double h0 = now_ms();
         std::vector<double> Ka = build_Ka(ss, hx, hy);
         tr.mark("build_Ka");
@@ -1243,6 +1322,8 @@ int nle_compute_kernel(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         if (ctx->patch_radius > 0)
             throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) does not take patch affinities: use nle_compute_kernel64"};
+        if (ctx->sampler != NLE_SAMPLER_GRID)
+            throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) takes the grid sampler only: use nle_compute_kernel64"};
         HIP_OK(hipSetDevice(ctx->device));
         SampleSet ss = fetch_samples(ctx, d_lum, gs);
         if (h_Ka) {
@@ -1270,6 +1351,8 @@ int nle_nystrom(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_sample
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         if (ctx->patch_radius > 0)
             throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) does not take patch affinities: use the fp64 formulations"};
+        if (ctx->sampler != NLE_SAMPLER_GRID)
+            throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) takes the grid sampler only: use the fp64 formulations"};
         HIP_OK(hipSetDevice(ctx->device));
         SampleSet ss = fetch_samples(ctx, d_lum, gs);
         std::vector<double> Ka = build_Ka(ss, hx, hy);
@@ -1348,8 +1431,11 @@ int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         const int R = ctx->patch_radius;
         check_patch_radius(ctx, R, H, W);
+        check_sampler(ctx, hx, hy);
         HIP_OK(hipSetDevice(ctx->device));
-        SampleSet ss = fetch_samples(ctx, d_lum, gs, R > 0, false, R);
+        std::vector<long long> list;
+        if (ctx->sampler == NLE_SAMPLER_FARTHEST) list = farthest_list(ctx, d_lum, gs, hx, hy);
+        SampleSet ss = fetch_samples(ctx, d_lum, gs, R > 0, false, R, list.empty() ? nullptr : &list);
         if (R > 0 && !ss.quantised)
             throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
                                         "(the L channel of 8-bit Lab)"};
@@ -1510,6 +1596,35 @@ int nle_filter_eigvals(const nle_filter* f, double* h_eigvals) {
     if (!f || !h_eigvals) return NLE_ERR_INVALID;
     std::copy(f->eigvals.begin(), f->eigvals.end(), h_eigvals);
     return NLE_OK;
+}
+
+int nle_filter_sample_pixels(const nle_filter* f, long long* h_idx, int* p) {
+    if (!f || !p) return NLE_ERR_INVALID;
+    *p = (int)f->h_sample_pix.size();
+    if (h_idx) std::copy(f->h_sample_pix.begin(), f->h_sample_pix.end(), h_idx);
+    return NLE_OK;
+}
+
+int nle_sample_pixels(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
+                      double hy, long long* h_idx, int* p) {
+    if (!ctx || !p) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
+        if (gs.p() > 2048) throw Fail{NLE_ERR_INVALID, "more than 2048 samples is not supported"};
+        std::vector<long long> list((size_t)gs.p());
+        if (ctx->sampler == NLE_SAMPLER_FARTHEST) {
+            if (!d_lum) throw Fail{NLE_ERR_INVALID, "the farthest sampler needs the luminance plane"};
+            check_sampler(ctx, hx, hy);
+            HIP_OK(hipSetDevice(ctx->device));
+            list = farthest_list(ctx, d_lum, gs, hx, hy);
+            prof_flush(ctx);
+        } else {
+            for (int k = 0; k < gs.p(); ++k)
+                list[k] = (long long)(gs.rowOff + (k / gs.nSelCols) * gs.rowStep) * W + gs.colOff + (k % gs.nSelCols) * gs.colStep;
+        }
+        *p = gs.p();
+        if (h_idx) std::copy(list.begin(), list.end(), h_idx);
+    });
 }
 
 int nle_filter_eigvec_range(const nle_filter* f, int ncols, double* h_min, double* h_max) {

@@ -64,6 +64,7 @@ struct nle_ctx {
     bool slab_input = false;  // nle_ctx_set_slab_input: planes handed in hold this rank's rows only
     bool nystrom_bf16x3 = false;  // nle_ctx_set_nystrom_bf16x3: the fused Nystrom GEMM on the bf16 MFMA with split operands
     int patch_radius = 0;  // nle_ctx_set_patch_radius: patch (non-local-means) affinities of (2R + 1)^2 pixels (patch.hip)
+    int sampler = 0;  // nle_ctx_set_sampler: NLE_SAMPLER_GRID or NLE_SAMPLER_FARTHEST (sampler.hip)
     int topk_solver = 0;  // nle_ctx_set_topk_solver: 0 full eigensolve of Q (:313-316), 1 Lanczos top-K (:170-199)
     bool profiling = false;
     bool profile_all = false;  // level 2: also the small / second-stage kernels (each timed launch costs ~10 us of gaps)
@@ -107,7 +108,7 @@ struct nle_filter {
     nlek::SortedRows sorted{};
     std::vector<std::pair<void*, size_t>> owned;  // workspace-cache buffers that live as long as the filter
     std::vector<double> h_Vrows;                  // p x K col-major: exact rows of V at the sample pixels
-    std::vector<long long> h_sample_pix;
+    std::vector<long long> h_sample_pix;          // the sample pixels, in the order of the sample set (ascending)
 };
 
 

@@ -2,9 +2,10 @@
 //   <image> <output> <# row samples> <# col samples> <hx> <hy> <# sinkhorn iterations> <# eigen vectors> ...
 // print the same usage line when too few arguments are given, parse numbers with std::stoi / std::stod (garbage
 // throws, like the reference: src/enhance.cpp:20-31, src/denoise.cpp:19-31) and return 0 on the two soft failures
-// (usage, unreadable image) for drop-in compatibility.  New here: an optional LEADING `--patch-radius R` (patch affinities,
-// NLEFilter::patchRadius); reference command lines never start with `--`, so they parse exactly as before.  An invalid R
-// prints a message to stderr and exits with status 2 before anything touches the GPU.
+// (usage, unreadable image) for drop-in compatibility.  New here: optional LEADING `--patch-radius R` (patch affinities,
+// NLEFilter::patchRadius) and `--sampler grid|farthest` (NLEFilter::sampler), in either order; reference command lines
+// never start with `--`, so they parse exactly as before.  An invalid value prints a message to stderr and exits with
+// status 2 before anything touches the GPU.
 #pragma once
 
 #include <cstdlib>
@@ -25,25 +26,40 @@ struct FilterArgs {
     double hx = 0, hy = 0;
     std::vector<double> extra;  // everything after the eighth argument, as doubles
     int patchRadius = 0;        // --patch-radius R
+    int sampler = NLE_SAMPLER_GRID;  // --sampler grid|farthest
 };
 
 // false (after printing the usage line to stderr) when fewer than `min_argc` arguments were given
 inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a) {
     std::vector<char*> shifted;
-    if (argc >= 2 && std::string(argv[1]) == "--patch-radius") {
-        const std::string v = argc >= 3 ? argv[2] : "";
-        char* end = nullptr;
-        const long r = v.empty() ? -1 : std::strtol(v.c_str(), &end, 10);
-        if (v.empty() || *end != '\0' || r < 0 || r > NLE_PATCH_RADIUS_MAX) {
-            std::cerr << argv[0] << ": --patch-radius takes an integer in [0, " << NLE_PATCH_RADIUS_MAX << "], got '" << v
-                      << "'" << std::endl;
-            std::exit(2);
+    int first = 1;  // the first argument after the leading options
+    while (first < argc) {
+        const std::string opt = argv[first];
+        if (opt != "--patch-radius" && opt != "--sampler") break;
+        const std::string v = first + 1 < argc ? argv[first + 1] : "";
+        if (opt == "--patch-radius") {
+            char* end = nullptr;
+            const long r = v.empty() ? -1 : std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || r < 0 || r > NLE_PATCH_RADIUS_MAX) {
+                std::cerr << argv[0] << ": --patch-radius takes an integer in [0, " << NLE_PATCH_RADIUS_MAX << "], got '" << v
+                          << "'" << std::endl;
+                std::exit(2);
+            }
+            a->patchRadius = (int)r;
+        } else {
+            if (v != "grid" && v != "farthest") {
+                std::cerr << argv[0] << ": --sampler takes 'grid' or 'farthest', got '" << v << "'" << std::endl;
+                std::exit(2);
+            }
+            a->sampler = v == "grid" ? NLE_SAMPLER_GRID : NLE_SAMPLER_FARTHEST;
         }
-        a->patchRadius = (int)r;
+        first += 2;
+    }
+    if (first > 1) {
         shifted.push_back(argv[0]);  // the rest parses as a reference command line
-        for (int i = 3; i < argc; ++i) shifted.push_back(argv[i]);
+        for (int i = first; i < argc; ++i) shifted.push_back(argv[i]);
         shifted.push_back(nullptr);
-        argc -= 2;
+        argc -= first - 1;
         argv = shifted.data();
     }
     if (argc < min_argc) {

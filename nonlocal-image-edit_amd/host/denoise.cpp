@@ -15,6 +15,7 @@ int main(int argc, char* argv[]) {
     if (image.empty()) return 0;                        // src/denoise.cpp:33-36
     nle::NLEFilter filter;
     filter.patchRadius = a.patchRadius;
+    filter.sampler = a.sampler;
     filter.trainForDenoise(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors, sigmaColor,
                            sigmaSpace);
     const nle::Image result = filter.denoise(image, shrinkFactor, sigmaColor, sigmaSpace);

@@ -13,6 +13,7 @@ int main(int argc, char* argv[]) {
     if (image.empty()) return 0;                        // src/enhance.cpp:34-37
     nle::NLEFilter filter;
     filter.patchRadius = a.patchRadius;
+    filter.sampler = a.sampler;
     filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
     const nle::Image result = filter.enhance(image, a.extra);  // the weights are argv[9..]
     nlecli::report(filter);

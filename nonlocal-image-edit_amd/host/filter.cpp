@@ -573,8 +573,10 @@ void NLEFilter::trainOnDevice(const float* d_lum, int rows, int cols, int nRowSa
         std::cout << "Orthogonalize" << std::endl;
     }
     check(nle_ctx_set_patch_radius(ctx_, patchRadius), ctx_);
+    check(nle_ctx_set_sampler(ctx_, sampler), ctx_);
     const int st = nle_train(ctx_, d_lum, rows, cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, &f_);
     nle_ctx_set_patch_radius(ctx_, 0);  // the shared ctx's other users (the free functions) keep the reference's affinity
+    nle_ctx_set_sampler(ctx_, NLE_SAMPLER_GRID);  // and its grid
     check(st, ctx_);
     fh_.reset(f_, [](nle_filter* f) { nle_filter_destroy(f); });
     rows_ = rows;
@@ -780,6 +782,7 @@ void NLEFilter::trainForEnhancementGroup(const Image& image, int nRowSamples, in
         check(nle_dev_upload(c, d_bgr.p, image.ptr<unsigned char>() + (size_t)r0 * W * 3, nl * 3), c);
         check(nle_bgr2lab8(c, static_cast<unsigned char*>(d_bgr.p), (long long)nl, nullptr, d_L.f()), c);
         check(nle_ctx_set_patch_radius(c, patchRadius), c);  // refused by the train at world > 1 (slab input) when > 0
+        check(nle_ctx_set_sampler(c, sampler), c);           // likewise when farthest
         check(nle_train(c, d_L.f(), H, W, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, &fs[r]), c);
     });
     for (int r = 0; r < G; ++r) group_[r].reset(fs[r], [](nle_filter* f) { nle_filter_destroy(f); });
