@@ -95,6 +95,26 @@ int nle_dev_download(nle_ctx* ctx, void* h_dst, const void* d_src, size_t bytes)
  *                          workspace is bounded (NLE_STREAM64_CHUNK_MB, default 2048), V (N x K') is fp64.  Any plane, any
  *                          grid with <= 2048 samples, any K: what auto mode takes when Phi would not fit the device. */
 #define NLE_MODE_STREAMED_F64 5
+/*   NLE_MODE_EXACT_F64     the exact filter, opt-in (new in this build; auto mode never takes it): the reference algorithm
+ *                          with the full pixel affinity in place of the Nystrom extension -- no samples (nRow, nCol are
+ *                          checked as the reference checks them, :117-119, and not used).  For the plane y (H x W, N = HW,
+ *                          pixel i at (r_i, c_i), row-major), sw = 1/hx^2, pw = 1/hy^2:
+ *                            K_ij = exp(-sw (double)((r_i - r_j)^2 + (c_i - c_j)^2) - pw (y_i - y_j)^2), all N x N entries
+ *                            r = 1;  T times: c = recip(K r);  r = recip(K c)   (recip: inplaceReciprocal, :42-54, EPS 1e-10)
+ *                            W = diag(r) K diag(c);  Ws = (W + W^T) / 2
+ *                            (lambda_k, v_k) = the min(K, N) largest eigenpairs of Ws by algebraic value, descending; the
+ *                            leading ones with lambda >= 1e-10 are kept (K', :213-215)
+ *                          each v_k unit norm, its entry of largest magnitude positive (ties: the lowest index); every
+ *                          kept pair has ||Ws v - lambda v||_2 <= 1e-10 by an explicit operator application, else the train
+ *                          returns NLE_ERR_NUMERIC.  K is regenerated on the fp64 matrix cores, never stored (O(N^2) work
+ *                          per product); bitwise reproducible on one device.  Needs an integer-valued plane in [0, 255],
+ *                          N <= NLE_EXACT_MAX_PIXELS, 1 <= nEigenVectors <= 256, patch radius 0, NLE_SAMPLER_GRID and
+ *                          world == 1; anything else returns NLE_ERR_INVALID before any collective.  V (N x K') is fp64;
+ *                          nle_filter_diag gives {6, 0, 0, 0, K', K', 0, 0}; nle_filter_timings [0] 0, [1] Sinkhorn, [2] the
+ *                          eigensolver's operator products, [3] orthogonalisation, Ritz and V assembly, [4] host algebra,
+ *                          [5] wall total. */
+#define NLE_MODE_EXACT_F64 6
+#define NLE_EXACT_MAX_PIXELS 1048576 /* 1 << 20 */
 int nle_ctx_set_mode(nle_ctx* ctx, int mode);
 /* Patch (non-local-means) affinities, opt-in (new in this build: the reference compares single pixel values,
  * src/filter.cpp:94-112).  With radius R > 0 the intensity term of every affinity, K_A and K_AB alike, compares the
@@ -267,6 +287,12 @@ int nle_sinkhorn_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int 
                             int max_iter, double* h_u_c, double* h_u_r);
 int nle_gram64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, const double* h_u, double* h_G);
 int nle_row_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, const double* h_u, double* d_out);
+/* The hot path of NLE_MODE_EXACT_F64: d_Y = K d_X with K the exact N x N affinity of the plane d_lum (definition above;
+ * integer valued in [0, 255], N = H W <= NLE_EXACT_MAX_PIXELS), regenerated on the fly.  d_X, d_Y: N x ld fp64, row per
+ * pixel, ld a multiple of 4, ncols <= ld logical columns; d_Y must not alias d_X; its columns >= ncols come out zero.
+ * Deterministic (fixed summation order). */
+int nle_affinity_product64(nle_ctx* ctx, const float* d_lum, int H, int W, double hx, double hy, const double* d_X, int ld,
+                           int ncols, double* d_Y);
 
 /* ---- the fused path ---------------------------------------------------------------- */
 /* NLEFilter::trainFilter, src/filter.cpp:480-502.  d_lum: FULL H x W fp32 luminance on the

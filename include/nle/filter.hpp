@@ -208,6 +208,9 @@ public:
     // sample selection for trainForEnhancement / trainForDenoise / trainFilter (nle_ctx_set_sampler; new here,
     // NLE_SAMPLER_GRID = the reference's grid, NLE_SAMPLER_FARTHEST = farthest-point selection)
     int sampler = 0;
+    // the exact (Nystrom-free) filter for trainForEnhancement / trainForDenoise / trainFilter (NLE_MODE_EXACT_F64 around
+    // the train; new here): one device, at most NLE_EXACT_MAX_PIXELS pixels, patchRadius 0 and the grid sampler
+    bool exact = false;
 
 private:
     nle_ctx* ctx_ = nullptr;

@@ -33,6 +33,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 MODE_AUTO, MODE_MATERIALISED, MODE_PHI_FREE, MODE_PHI_FREE_EXP, MODE_MATERIALISED_F64, MODE_STREAMED_F64 = (
     _abi.NLE_MODE_AUTO, _abi.NLE_MODE_MATERIALISED, _abi.NLE_MODE_PHI_FREE, _abi.NLE_MODE_PHI_FREE_EXP,
     _abi.NLE_MODE_MATERIALISED_F64, _abi.NLE_MODE_STREAMED_F64)
+MODE_EXACT_F64 = _abi.NLE_MODE_EXACT_F64  # the exact (Nystrom-free) filter, opt-in
+EXACT_MAX_PIXELS = _abi.NLE_EXACT_MAX_PIXELS
 SAMPLER_GRID, SAMPLER_FARTHEST = _abi.NLE_SAMPLER_GRID, _abi.NLE_SAMPLER_FARTHEST
 
 _lib = None
@@ -290,7 +292,7 @@ class Context:
         _check(lib().nle_ctx_synchronize(self._h), self._h)
 
     def set_mode(self, mode: int):
-        """0 auto, 1 materialised Phi, 2 Phi-free (NLE_MODE_* in include/nle.h)."""
+        """0 auto, 1 materialised Phi, 2 Phi-free, ..., 6 the exact filter (NLE_MODE_* in include/nle.h)."""
         _check(lib().nle_ctx_set_mode(self._h, int(mode)), self._h)
 
     def set_patch_radius(self, radius: int):
@@ -313,6 +315,28 @@ class Context:
         _check(lib().nle_sample_pixels(self._h, C.c_void_p(x.data_ptr()), H, W, int(n_row_samples), int(n_col_samples),
                                        float(hx), float(hy), _np_ptr(out), C.byref(p)), self._h)
         return out[:p.value]
+
+    def affinity_product64(self, lum, X, hx, hy):
+        """Y = K X with K the exact N x N affinity of the H x W plane `lum` (integer valued in [0, 255]; the kernel of
+        MODE_EXACT_F64, nle_affinity_product64).  X: N x ncols (or N) float64, numpy or CUDA; returns an N x ncols float64
+        CUDA tensor."""
+        torch = _torch()
+        lum = self._lum(lum)
+        H, W = lum.shape
+        X = torch.as_tensor(X, dtype=torch.float64, device=lum.device)
+        if X.ndim == 1:
+            X = X[:, None]
+        N, ncols = X.shape
+        if N != H * W:
+            raise NLEError(NLE_ERR_INVALID, f"X must have H * W = {H * W} rows, got {N}")
+        ldx = ld(ncols)
+        Xp = torch.zeros((N, ldx), dtype=torch.float64, device=lum.device)
+        Xp[:, :ncols] = X
+        Y = torch.empty_like(Xp)
+        self._sync_in()
+        _check(lib().nle_affinity_product64(self._h, C.c_void_p(lum.data_ptr()), H, W, float(hx), float(hy),
+                                            C.c_void_p(Xp.data_ptr()), ldx, ncols, C.c_void_p(Y.data_ptr())), self._h)
+        return Y[:, :ncols]
 
     def set_nystrom_bf16x3(self, on: bool = True):
         """the fused Nystrom GEMM on the bf16 matrix cores with split operands (nle_ctx_set_nystrom_bf16x3)"""

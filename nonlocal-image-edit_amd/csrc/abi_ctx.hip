@@ -334,7 +334,7 @@ int nle_ctx_set_sampler(nle_ctx* ctx, int sampler) {
 }
 
 int nle_ctx_set_mode(nle_ctx* ctx, int mode) {
-    if (!ctx || mode < 0 || mode > NLE_MODE_STREAMED_F64) return NLE_ERR_INVALID;
+    if (!ctx || mode < 0 || mode > NLE_MODE_EXACT_F64) return NLE_ERR_INVALID;
     ctx->mode = mode;
     return NLE_OK;
 }

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 namespace nlek {
 
 // Closed form of samplePixels (reference src/filter.cpp:56-80).
@@ -318,5 +320,35 @@ hipError_t apply_expand(hipStream_t s, const float* d_V, long long M, int ld, co
 // X[idx[k]] = src[k] (ld floats each) for idx[k] in [0, M)
 hipError_t scatter_rows(hipStream_t s, const float* d_src, const long long* d_idx, int n, int ld,
                         float* d_X, long long M);
+
+// ---- the exact filter (exact.hip, NLE_MODE_EXACT_F64): Y = K X with the N x N affinity regenerated on the fly
+// lum: the H x W plane (integer valued in [0, 255]); d_es / d_el: exact_tables' spatial (es_len >= max(H, W)) and
+// level (256) tables on the device; d_part: exact_part_elems(H W) doubles of workspace for the one- and two-column form
+struct ExactPlane {
+    const float* lum;
+    int H, W;
+    const double* d_es;
+    int es_len;
+    const double* d_el;
+    double* d_part;
+};
+void exact_tables(int H, int W, double hx, double hy, std::vector<double>* es, std::vector<double>* el);
+size_t exact_part_elems(long long N);
+// Y (N x ldy, columns < ncols) = K X (N x ldx, columns < ncols); deterministic, segmented over the source pixels
+hipError_t affinity_product64(hipStream_t s, const ExactPlane& pl, const double* d_X, int ldx, int ncols, double* d_Y, int ldy);
+// the eigensolver's element-wise steps (pipeline.hip: train_exact64)
+hipError_t exact_start(hipStream_t s, double* d_X, long long N, int ld, int col0, int ncols, unsigned seed);
+hipError_t exact_scale2(hipStream_t s, const double* d_X, int ldx, long long N, int b, const double* d_c, const double* d_r,
+                        double* d_Z);
+hipError_t exact_combine(hipStream_t s, const double* d_Y, long long N, int b, const double* d_c, const double* d_r, double* d_A,
+                         int lda);
+hipError_t exact_recip(hipStream_t s, double* d_v, long long N, double eps);
+hipError_t exact_axpby(hipStream_t s, const double* d_S, int lds, double alpha, const double* d_B, int ldb, double beta,
+                       double* d_D, int ldd, long long N, int n, int pad);
+int exact_col_blocks(long long N);
+hipError_t exact_colnorm2(hipStream_t s, const double* d_A, int lda, const double* d_B, int ldb, const double* d_theta,
+                          long long N, int n, double* d_part);
+hipError_t exact_colmaxabs(hipStream_t s, const double* d_A, int lda, long long N, int n, double* d_pv);
+hipError_t exact_scale_cols(hipStream_t s, double* d_A, int lda, long long N, int n, const double* d_s);
 
 }  // namespace nlek

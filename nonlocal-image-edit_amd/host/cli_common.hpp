@@ -3,9 +3,10 @@
 // print the same usage line when too few arguments are given, parse numbers with std::stoi / std::stod (garbage
 // throws, like the reference: src/enhance.cpp:20-31, src/denoise.cpp:19-31) and return 0 on the two soft failures
 // (usage, unreadable image) for drop-in compatibility.  New here: optional LEADING `--patch-radius R` (patch affinities,
-// NLEFilter::patchRadius) and `--sampler grid|farthest` (NLEFilter::sampler), in either order; reference command lines
-// never start with `--`, so they parse exactly as before.  An invalid value prints a message to stderr and exits with
-// status 2 before anything touches the GPU.
+// NLEFilter::patchRadius), `--sampler grid|farthest` (NLEFilter::sampler) and the flag `--exact` (NLEFilter::exact, no
+// value; not with a non-zero radius or the farthest sampler), in any order; reference command lines never start with
+// `--`, so they parse exactly as before.  An invalid value prints a message to stderr and exits with status 2 before
+// anything touches the GPU.
 #pragma once
 
 #include <cstdlib>
@@ -27,6 +28,7 @@ struct FilterArgs {
     std::vector<double> extra;  // everything after the eighth argument, as doubles
     int patchRadius = 0;        // --patch-radius R
     int sampler = NLE_SAMPLER_GRID;  // --sampler grid|farthest
+    bool exact = false;              // --exact
 };
 
 // false (after printing the usage line to stderr) when fewer than `min_argc` arguments were given
@@ -35,6 +37,15 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a) {
     int first = 1;  // the first argument after the leading options
     while (first < argc) {
         const std::string opt = argv[first];
+        if (opt == "--exact") {
+            a->exact = true;
+            first += 1;
+            continue;
+        }
+        if (opt.rfind("--exact=", 0) == 0) {
+            std::cerr << argv[0] << ": --exact takes no value, got '" << opt << "'" << std::endl;
+            std::exit(2);
+        }
         if (opt != "--patch-radius" && opt != "--sampler") break;
         const std::string v = first + 1 < argc ? argv[first + 1] : "";
         if (opt == "--patch-radius") {
@@ -54,6 +65,11 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a) {
             a->sampler = v == "grid" ? NLE_SAMPLER_GRID : NLE_SAMPLER_FARTHEST;
         }
         first += 2;
+    }
+    if (a->exact && (a->patchRadius != 0 || a->sampler != NLE_SAMPLER_GRID)) {
+        std::cerr << argv[0] << ": --exact uses no samples and single-pixel affinities: it does not combine with "
+                  << "--patch-radius R > 0 or --sampler farthest" << std::endl;
+        std::exit(2);
     }
     if (first > 1) {
         shifted.push_back(argv[0]);  // the rest parses as a reference command line

@@ -16,6 +16,7 @@ int main(int argc, char* argv[]) {
     nle::NLEFilter filter;
     filter.patchRadius = a.patchRadius;
     filter.sampler = a.sampler;
+    filter.exact = a.exact;
     filter.trainForDenoise(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors, sigmaColor,
                            sigmaSpace);
     const nle::Image result = filter.denoise(image, shrinkFactor, sigmaColor, sigmaSpace);

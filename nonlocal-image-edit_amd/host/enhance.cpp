@@ -14,6 +14,7 @@ int main(int argc, char* argv[]) {
     nle::NLEFilter filter;
     filter.patchRadius = a.patchRadius;
     filter.sampler = a.sampler;
+    filter.exact = a.exact;
     filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
     const nle::Image result = filter.enhance(image, a.extra);  // the weights are argv[9..]
     nlecli::report(filter);

@@ -34,6 +34,12 @@ nle_ctx* shared_ctx() {
     return ctx;
 }
 
+// the mode a ctx of this process is created with (NLE_MODE, default auto): what a train with NLEFilter::exact restores
+int default_mode() {
+    const char* m = std::getenv("NLE_MODE");
+    return m ? std::atoi(m) : NLE_MODE_AUTO;
+}
+
 void check(int status, nle_ctx* ctx) {
     if (status != NLE_OK) throw std::runtime_error(nle_last_error(ctx));
 }
@@ -574,9 +580,11 @@ void NLEFilter::trainOnDevice(const float* d_lum, int rows, int cols, int nRowSa
     }
     check(nle_ctx_set_patch_radius(ctx_, patchRadius), ctx_);
     check(nle_ctx_set_sampler(ctx_, sampler), ctx_);
+    if (exact) check(nle_ctx_set_mode(ctx_, NLE_MODE_EXACT_F64), ctx_);
     const int st = nle_train(ctx_, d_lum, rows, cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, &f_);
     nle_ctx_set_patch_radius(ctx_, 0);  // the shared ctx's other users (the free functions) keep the reference's affinity
     nle_ctx_set_sampler(ctx_, NLE_SAMPLER_GRID);  // and its grid
+    if (exact) nle_ctx_set_mode(ctx_, default_mode());  // and its mode
     check(st, ctx_);
     fh_.reset(f_, [](nle_filter* f) { nle_filter_destroy(f); });
     rows_ = rows;
@@ -783,7 +791,10 @@ void NLEFilter::trainForEnhancementGroup(const Image& image, int nRowSamples, in
         check(nle_bgr2lab8(c, static_cast<unsigned char*>(d_bgr.p), (long long)nl, nullptr, d_L.f()), c);
         check(nle_ctx_set_patch_radius(c, patchRadius), c);  // refused by the train at world > 1 (slab input) when > 0
         check(nle_ctx_set_sampler(c, sampler), c);           // likewise when farthest
-        check(nle_train(c, d_L.f(), H, W, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, &fs[r]), c);
+        if (exact) check(nle_ctx_set_mode(c, NLE_MODE_EXACT_F64), c);  // refused by the train at world > 1
+        const int st = nle_train(c, d_L.f(), H, W, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, &fs[r]);
+        if (exact) nle_ctx_set_mode(c, default_mode());
+        check(st, c);
     });
     for (int r = 0; r < G; ++r) group_[r].reset(fs[r], [](nle_filter* f) { nle_filter_destroy(f); });
     ctx_ = g->ctx[0];
