@@ -279,7 +279,9 @@ int nle_row_scalings(nle_ctx* ctx, const float* d_phi, long long M, int ld, int 
 
 /* The same stages on fp64 device matrices (row-per-pixel, leading dimension any value >= the logical width; outputs use
  * nle_ld(width)), all products and sums in fp64: what include/nle/filter.hpp's free functions run on, so that the
- * reference's unit tests (test/test_filter.cpp, tolerance 1e-10) hold at their own tolerance. */
+ * reference's unit tests (test/test_filter.cpp, tolerance 1e-10) hold at their own tolerance.  The leading dimension is a
+ * row stride only: columns >= the logical width are never read, whatever they hold (a sub-block of a wider matrix, an
+ * uninitialised buffer, NaN); nle_sinkhorn_scalings64 takes r <= 2048 (any ld), more returns NLE_ERR_INVALID. */
 int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
                          double hy, double* h_Ka, double* d_kab);
 int nle_ts_gemm64(nle_ctx* ctx, const double* d_A, long long M, int lda, int kd, const double* h_B, int nc, double* d_C);
@@ -349,7 +351,8 @@ int nle_filter_timings(const nle_filter* f, double* h_ms);
  * training image -> NLE_ERR_INVALID (:447-449). */
 int nle_apply(nle_filter* f, const float* d_x, int H, int W, const double* h_fS, float* d_y);
 /* the L per-layer outputs y_l = V ((lambda^l - lambda^(l+1)) o V^T x), base layer
- * lambda^(L-1) (src/filter.cpp:334-347); d_y: L x n_local fp32 (layer-major). */
+ * lambda^(L-1) (src/filter.cpp:334-347); d_y: L x n_local fp32 (layer-major).  1 <= L <= 64 whatever K' is: L x K' is
+ * not bounded (the layers go out a group per launch when their tables do not fit on chip together). */
 int nle_apply_layers(nle_filter* f, const float* d_x, int H, int W, int L, float* d_y);
 /* host-buffer forms.  h_x == NULL: filter the plane the filter was trained on (kept on the device by
  * nle_train_host), which is what `enhance` does (src/enhance.cpp:43-44) -- one upload for train + apply.  Finished

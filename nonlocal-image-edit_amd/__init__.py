@@ -533,6 +533,67 @@ class Context:
                                       C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    # the same stages on fp64 device matrices (nle_*64): X is a float64 CUDA tensor (M, ld), rows contiguous (a row
+    # sub-block X[q:] included), ANY ld >= the logical width; columns >= the logical width are never read
+    def _mat64(self, X, width, what):
+        torch = _torch()
+        if X.dtype != torch.float64 or X.ndim != 2 or not X.is_cuda:
+            raise NLEError(NLE_ERR_INVALID, f"{what}: need a float64 device tensor (M, ld)")
+        M, ldx = X.shape
+        if X.stride(1) != 1 or (M > 1 and X.stride(0) != ldx):
+            raise NLEError(NLE_ERR_INVALID, f"{what}: rows must be contiguous with stride ld")
+        if not 1 <= width <= ldx:
+            raise NLEError(NLE_ERR_INVALID, f"{what}: need 1 <= logical width <= ld")
+        self._sync_in()
+        return M, ldx
+
+    def ts_gemm64(self, A, kd, B):
+        """C = A[:, :kd] @ B  (A fp64 CUDA M x lda, B fp64 numpy kd x nc) -> fp64 CUDA M x ld(nc)."""
+        torch = _torch()
+        M, lda = self._mat64(A, kd, "ts_gemm64")
+        B = np.asfortranarray(np.asarray(B, dtype=np.float64))
+        if B.ndim != 2 or B.shape[0] != kd:
+            raise NLEError(NLE_ERR_INVALID, "ts_gemm64: B must be kd x nc")
+        nc = B.shape[1]
+        Cc = torch.empty((M, ld(nc)), dtype=torch.float64, device=A.device)
+        _check(lib().nle_ts_gemm64(self._h, C.c_void_p(A.data_ptr()), M, lda, kd, _np_ptr(B), nc,
+                                   C.c_void_p(Cc.data_ptr())), self._h)
+        return Cc
+
+    def sinkhorn_scalings64(self, phi, r, eigvals, max_iter=10):
+        """Sinkhorn iterations (src/filter.cpp:238-245) on fp64 device phi -> (u_c, u_r); r <= 2048."""
+        M, ldp = self._mat64(phi, r, "sinkhorn_scalings64")
+        ev = np.ascontiguousarray(eigvals, dtype=np.float64)
+        if ev.size < r:
+            raise NLEError(NLE_ERR_INVALID, "sinkhorn_scalings64: need r eigenvalues")
+        uc, ur = np.zeros(r), np.zeros(r)
+        _check(lib().nle_sinkhorn_scalings64(self._h, C.c_void_p(phi.data_ptr()), M, ldp, r, _np_ptr(ev), max_iter,
+                                             _np_ptr(uc), _np_ptr(ur)), self._h)
+        return uc, ur
+
+    def gram64(self, phi, r, u=None):
+        """sum_i c_i^2 phi_i phi_i^T (r x r), c_i = recip(phi_i . u); u None: c_i = 1"""
+        M, ldp = self._mat64(phi, r, "gram64")
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.size < r:
+                raise NLEError(NLE_ERR_INVALID, "gram64: need r entries of u")
+        G = np.zeros((r, r), dtype=np.float64, order="F")
+        _check(lib().nle_gram64(self._h, C.c_void_p(phi.data_ptr()), M, ldp, r, _np_ptr(u) if u is not None else None,
+                                _np_ptr(G)), self._h)
+        return np.ascontiguousarray(G)
+
+    def row_scalings64(self, phi, r, u):
+        torch = _torch()
+        M, ldp = self._mat64(phi, r, "row_scalings64")
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.size < r:
+            raise NLEError(NLE_ERR_INVALID, "row_scalings64: need r entries of u")
+        out = torch.empty(M, dtype=torch.float64, device=phi.device)
+        _check(lib().nle_row_scalings64(self._h, C.c_void_p(phi.data_ptr()), M, ldp, r, _np_ptr(u),
+                                        C.c_void_p(out.data_ptr())), self._h)
+        return out
+
     # ---- colour / denoise wrapper pieces (device tensors) ----
     def bgr2lab8(self, bgr):
         """`cvtColor(COLOR_BGR2Lab)` on an H x W x 3 uint8 image: (lab uint8 H x W x 3, L float32 H x W)"""

@@ -10,7 +10,7 @@
 //   k_tsgemm64        :275, :327, :250                  tall-skinny products on v_mfma_f64_16x16x4_f64
 //   k_rowpass64       :239,243 + :42-54, :456           phi (D (phi^T r)) with inplaceReciprocal, one pass; V^T x
 //   k_gram64d         :296                              Wab Wab^T (its N-sized part) on the fp64 MFMA
-//   k_apply_expand64  :456                              V (diag f) (V^T x), all layers in one pass
+//   k_apply_expand64  :456                              V (diag f) (V^T x), as many layers per pass as fit in LDS
 // It is a fallback, sized for correctness first: operands come straight from global memory (L2), one wave per 16 x 16
 // output tile; N x r fp64 is 26.8 GB at cfg4, which 288 GB of HBM holds comfortably.
 #include "kernels.h"
@@ -228,20 +228,22 @@ hipError_t gemm64s(hipStream_t s, int m, int n, int kk, const double* A, long lo
 // ------------------------------------------------------------------ one pass over X (M x ld fp64)
 // partial[b][j] = sum over the rows of block b of X[i][j] y_i;  COLSUM: y = 1;  RECIP: y_i = recip(X_i . (lam o t_in));
 // XVEC: y_i = xvec[i].  One wave per row at a time; lane l owns columns l, l + 64, ... (<= kRp64Cols per lane).
-constexpr int kRp64Cols = 32;  // ld <= 2048
+// ld is the row stride of X only: columns >= w (the logical width) are never loaded, so whatever they hold -- NaN
+// included -- stays out of the sums.  t_in, lam and the rows of partial have lw = (w + 3) & ~3 entries, those >= w zero.
+constexpr int kRp64Cols = 32;  // w <= 2048
 
-template <int NCL>  // columns per lane: ld <= 64 NCL
-__global__ __launch_bounds__(256) void k_rowpass64(int mode, const double* __restrict__ X, long long M, int ld,
+template <int NCL>  // columns per lane: w <= 64 NCL
+__global__ __launch_bounds__(256) void k_rowpass64(int mode, const double* __restrict__ X, long long M, int ld, int w, int lw,
                                                    const double* __restrict__ t_in, const double* __restrict__ lam,
                                                    const float* __restrict__ xvec, double eps, double* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    double* sred = reinterpret_cast<double*>(smem_raw);  // [4][ld]
+    double* sred = reinterpret_cast<double*>(smem_raw);  // [4][lw]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double u[NCL], acc[NCL];
 #pragma unroll
     for (int k = 0; k < NCL; ++k) {
         const int j = lane + 64 * k;
-        u[k] = (mode == ROWPASS_RECIP && j < ld) ? lam[j] * t_in[j] : 0.0;
+        u[k] = (mode == ROWPASS_RECIP && j < w) ? lam[j] * t_in[j] : 0.0;
         acc[k] = 0.0;
     }
     const long long wv = (long long)blockIdx.x * 4 + wave, nw = (long long)gridDim.x * 4;
@@ -251,7 +253,7 @@ __global__ __launch_bounds__(256) void k_rowpass64(int mode, const double* __res
 #pragma unroll
         for (int k = 0; k < NCL; ++k) {
             const int j = lane + 64 * k;
-            v[k] = (j < ld) ? X[(size_t)i * ld + j] : 0.0;
+            v[k] = (j < w) ? X[(size_t)i * ld + j] : 0.0;
             s += v[k] * u[k];
         }
         double y = 1.0;
@@ -268,20 +270,21 @@ __global__ __launch_bounds__(256) void k_rowpass64(int mode, const double* __res
 #pragma unroll
     for (int k = 0; k < NCL; ++k) {
         const int j = lane + 64 * k;
-        if (j < ld) sred[wave * ld + j] = acc[k];
+        if (j < lw) sred[wave * lw + j] = acc[k];
     }
     __syncthreads();
-    for (int j = threadIdx.x; j < ld; j += 256)
-        partial[(size_t)blockIdx.x * ld + j] = (sred[j] + sred[ld + j]) + (sred[2 * ld + j] + sred[3 * ld + j]);
+    for (int j = threadIdx.x; j < lw; j += 256)
+        partial[(size_t)blockIdx.x * lw + j] = (sred[j] + sred[lw + j]) + (sred[2 * lw + j] + sred[3 * lw + j]);
 }
 
-hipError_t rowpass64(hipStream_t s, int mode, const double* d_X, long long M, int ld, const double* d_t_in,
+hipError_t rowpass64(hipStream_t s, int mode, const double* d_X, long long M, int ld, int w, const double* d_t_in,
                      const double* d_lam, const float* d_xvec, double eps, double* d_partial, int* nblocks) {
-    if (ld > 64 * kRp64Cols) return hipErrorInvalidValue;
+    if (w < 1 || w > ld || w > 64 * kRp64Cols) return hipErrorInvalidValue;
+    const int lw = (w + 3) & ~3;
     long long nb = (M + 3) / 4;
     nb = std::max<long long>(1, std::min<long long>(nb, kRowpassMaxBlocks));
     *nblocks = (int)nb;
-    const size_t shm = (size_t)4 * ld * sizeof(double);
+    const size_t shm = (size_t)4 * lw * sizeof(double);
 #define NLE_RP64(NCLV)                                                                                                  \
     {                                                                                                                   \
         if (shm > 48 * 1024) {                                                                                          \
@@ -289,14 +292,14 @@ hipError_t rowpass64(hipStream_t s, int mode, const double* d_X, long long M, in
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                  \
             if (ea != hipSuccess) return ea;                                                                            \
         }                                                                                                               \
-        hipLaunchKernelGGL((k_rowpass64<NCLV>), dim3((unsigned)nb), dim3(256), shm, s, mode, d_X, M, ld, d_t_in, d_lam,  \
-                           d_xvec, eps, d_partial);                                                                     \
+        hipLaunchKernelGGL((k_rowpass64<NCLV>), dim3((unsigned)nb), dim3(256), shm, s, mode, d_X, M, ld, w, lw, d_t_in, \
+                           d_lam, d_xvec, eps, d_partial);                                                              \
     }
-    if (ld <= 64) NLE_RP64(1)
-    else if (ld <= 128) NLE_RP64(2)
-    else if (ld <= 256) NLE_RP64(4)
-    else if (ld <= 512) NLE_RP64(8)
-    else if (ld <= 1024) NLE_RP64(16)
+    if (lw <= 64) NLE_RP64(1)
+    else if (lw <= 128) NLE_RP64(2)
+    else if (lw <= 256) NLE_RP64(4)
+    else if (lw <= 512) NLE_RP64(8)
+    else if (lw <= 1024) NLE_RP64(16)
     else NLE_RP64(32)
 #undef NLE_RP64
     return hipGetLastError();
@@ -401,18 +404,28 @@ __global__ __launch_bounds__(256) void k_apply_expand64(const double* __restrict
     }
 }
 
+// The [L][K] table of a launch lives in LDS: the layers go out in equal groups whose table fits kApplyLdsBytes (64 KiB,
+// two workgroups per CU; one layer at K = 2048 is 16 KiB, so a group always exists).  Every layer is summed in the same
+// order whatever group it lands in.
 hipError_t apply_expand64(hipStream_t s, const double* d_V, long long M, int ld, int K, const double* d_g, int L, float* d_Y,
                           long long ystride) {
-    if (M <= 0) return hipSuccess;
-    const size_t shm = (size_t)L * K * sizeof(double);
-    if (shm > 64 * 1024) return hipErrorInvalidValue;
-    if (shm > 48 * 1024) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_apply_expand64),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (ea != hipSuccess) return ea;
-    }
+    if (M <= 0 || L <= 0) return hipSuccess;
+    const size_t per_layer = (size_t)K * sizeof(double);
+    if (per_layer > kApplyLdsBytes) return hipErrorInvalidValue;
+    const int lmax = per_layer ? (int)std::min<size_t>(kApplyLdsBytes / per_layer, (size_t)L) : L;
+    const int ngroups = (L + lmax - 1) / lmax, lg = (L + ngroups - 1) / ngroups;
     const long long nb = std::min<long long>((M + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_apply_expand64, dim3((unsigned)nb), dim3(256), shm, s, d_V, M, ld, K, d_g, L, d_Y, ystride);
+    for (int l0 = 0; l0 < L; l0 += lg) {
+        const int ln = std::min(lg, L - l0);
+        const size_t shm = (size_t)ln * per_layer;
+        if (shm > 48 * 1024) {
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_apply_expand64),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+            if (ea != hipSuccess) return ea;
+        }
+        hipLaunchKernelGGL(k_apply_expand64, dim3((unsigned)nb), dim3(256), shm, s, d_V, M, ld, K, d_g + (size_t)l0 * ld, ln,
+                           d_Y + (size_t)l0 * ystride, ystride);
+    }
     return hipGetLastError();
 }
 

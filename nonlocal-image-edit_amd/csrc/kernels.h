@@ -49,6 +49,8 @@ enum { SUB_HIST_G = 0, SUB_HIST_PIX = 1, SUB_HIST_HH = 2, SUB_HIST_Z = 3 };
 enum { SUB_GHIST_ROWS = 0, SUB_GHIST_EE = 1, SUB_GHIST_GEMM = 2, SUB_GHIST_FINAL = 3 };
 
 constexpr int kRowpassMaxBlocks = 1024;
+// LDS one launch of the apply-expand kernels may take for its [layers][K] fp64 table: more layers go out in several launches
+constexpr size_t kApplyLdsBytes = 64 * 1024;
 constexpr int kGramTilesPerWave = 7;
 constexpr int kGramRowsPerStage = 32;
 
@@ -180,7 +182,9 @@ hipError_t gemm64s(hipStream_t s, int m, int n, int kk, const double* A, long lo
                    long long rsB, long long csB, double* C, long long rsC, long long csC, const double* dl = nullptr,
                    const double* dk = nullptr, const double* dr = nullptr, const double* add = nullptr, long long rsD = 0,
                    long long csD = 0);
-hipError_t rowpass64(hipStream_t s, int mode, const double* d_X, long long M, int ld, const double* d_t_in,
+// one pass over X (M x ld, logical width w <= 2048: columns >= w are never read); d_t_in, d_lam and the rows of
+// d_partial have (w + 3) & ~3 entries
+hipError_t rowpass64(hipStream_t s, int mode, const double* d_X, long long M, int ld, int w, const double* d_t_in,
                      const double* d_lam, const float* d_xvec, double eps, double* d_partial, int* nblocks);
 // G (r x r, full symmetric) = sum_i cs_i^2 x_i x_i^T (cs null: 1); d_partial: gram64d_partial_elems doubles
 size_t gram64d_partial_elems(long long M, int r);

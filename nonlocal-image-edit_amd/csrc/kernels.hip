@@ -737,18 +737,32 @@ __global__ __launch_bounds__(256) void k_apply_expand(const float* __restrict__ 
     }
 }
 
+// layers in equal groups whose [layers][ld] table fits kApplyLdsBytes (see apply_expand64); same sums per layer in any group
 hipError_t apply_expand(hipStream_t s, const float* d_V, long long M, int ld, const double* d_g, int L,
                         float* d_Y, long long ystride) {
-    if (M <= 0) return hipSuccess;
+    if (M <= 0 || L <= 0) return hipSuccess;
     int G, Q;
     if (!pick_gq(ld, &G, &Q)) return hipErrorInvalidValue;
     const int rows_per_block = 4 * (64 / G);
     long long nb = (M + rows_per_block - 1) / rows_per_block;
     if (nb > 4096) nb = 4096;
-    const size_t shm = (size_t)L * ld * sizeof(double);
-    NLE_DISPATCH_GQ(G, Q,
-                    hipLaunchKernelGGL((k_apply_expand<G_, Q_>), dim3((unsigned)nb), dim3(256), shm, s, d_V,
-                                       M, ld, d_g, L, d_Y, ystride))
+    const size_t per_layer = (size_t)ld * sizeof(double);
+    if (per_layer > kApplyLdsBytes) return hipErrorInvalidValue;
+    const int lmax = (int)std::min<size_t>(kApplyLdsBytes / per_layer, (size_t)L);
+    const int ngroups = (L + lmax - 1) / lmax, lg = (L + ngroups - 1) / ngroups;
+    for (int l0 = 0; l0 < L; l0 += lg) {
+        const int ln = std::min(lg, L - l0);
+        const size_t shm = (size_t)ln * per_layer;
+        NLE_DISPATCH_GQ(G, Q, {
+            if (shm > 48 * 1024) {
+                hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_apply_expand<G_, Q_>),
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+                if (ea != hipSuccess) return ea;
+            }
+            hipLaunchKernelGGL((k_apply_expand<G_, Q_>), dim3((unsigned)nb), dim3(256), shm, s, d_V, M, ld,
+                               d_g + (size_t)l0 * ld, ln, d_Y + (size_t)l0 * ystride, ystride);
+        })
+    }
     return hipGetLastError();
 }
 

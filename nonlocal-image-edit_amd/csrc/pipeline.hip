@@ -393,20 +393,27 @@ void build_phi(nle_ctx* c, const float* d_lum, const SampleSet& ss, const Nystro
 
 // Sinkhorn (reference :238-245) as 2T passes: t0 = Phi^T 1, then alternately
 // t <- Phi^T recip(Phi (lam o t)).  Returns u_c, u_r (host) and leaves lam o t_c_in on d_u_c.
-inline hipError_t rowpass_any(hipStream_t s, int mode, const float* X, long long M, int ld, const double* t, const double* lam,
-                              const float* xv, double eps, double* partial, int* nb) {
+// The fp64 pass takes the logical width: it never loads a column >= r (nle.h: "leading dimension any value >= the logical
+// width"), and its vectors have ld4(r) entries.  The fp32 pass reads whole rows of ld (a multiple of 4, padding zero).
+inline hipError_t rowpass_any(hipStream_t s, int mode, const float* X, long long M, int ld, int /*r*/, const double* t,
+                              const double* lam, const float* xv, double eps, double* partial, int* nb) {
     return nlek::rowpass(s, mode, X, M, ld, t, lam, xv, eps, partial, nb);
 }
-inline hipError_t rowpass_any(hipStream_t s, int mode, const double* X, long long M, int ld, const double* t, const double* lam,
-                              const float* xv, double eps, double* partial, int* nb) {
-    return nlek::rowpass64(s, mode, X, M, ld, t, lam, xv, eps, partial, nb);
+inline hipError_t rowpass_any(hipStream_t s, int mode, const double* X, long long M, int ld, int r, const double* t,
+                              const double* lam, const float* xv, double eps, double* partial, int* nb) {
+    return nlek::rowpass64(s, mode, X, M, ld, r, t, lam, xv, eps, partial, nb);
 }
+inline int pass_width(const float*, int ld, int /*r*/) { return ld; }
+inline int pass_width(const double*, int /*ld*/, int r) { return ld4(r); }
 
 template <typename T_>
-void sinkhorn_passes(nle_ctx* c, const T_* d_phi, long long M, int ld, int r,
+void sinkhorn_passes(nle_ctx* c, const T_* d_phi, long long M, int ld_phi, int r,
                      const std::vector<double>& lam, int T, std::vector<double>* u_c,
-                     std::vector<double>* u_r, double* d_u_c_out /* ld doubles or null */) {
+                     std::vector<double>* u_r, double* d_u_c_out /* pass_width doubles or null */) {
     if (T < 1) throw Fail{NLE_ERR_INVALID, "nSinkhornIter must be >= 1"};
+    if (std::is_same<T_, double>::value && r > 2048)
+        throw Fail{NLE_ERR_INVALID, "the fp64 Sinkhorn pass takes a logical width of at most 2048"};
+    const int ld = pass_width(d_phi, ld_phi, r);  // length of lam, t and of a row of partials (== ld_phi on the train paths)
     std::vector<double> lam_pad(ld, 0.0);
     std::copy(lam.begin(), lam.begin() + r, lam_pad.begin());
     DevBuf<double> d_lam(ld), d_t[3], d_partial((size_t)nlek::kRowpassMaxBlocks * ld);
@@ -414,7 +421,7 @@ void sinkhorn_passes(nle_ctx* c, const T_* d_phi, long long M, int ld, int r,
     HIP_OK(hipMemcpyAsync(d_lam.p, lam_pad.data(), ld * sizeof(double), hipMemcpyHostToDevice, c->stream));
     int nb = 0;
     // t_r(0) = Phi^T 1
-    PROFILED(c, NLE_K_SINKHORN_PASS, rowpass_any(c->stream, nlek::ROWPASS_COLSUM, d_phi, M, ld, nullptr, nullptr,
+    PROFILED(c, NLE_K_SINKHORN_PASS, rowpass_any(c->stream, nlek::ROWPASS_COLSUM, d_phi, M, ld_phi, r, nullptr, nullptr,
                                                    nullptr, NLE_EPS, d_partial.p, &nb));
     PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(c->stream, d_partial.p, nb, ld, d_t[0].p));
     all_reduce(c, d_t[0].p, ld);
@@ -425,7 +432,7 @@ void sinkhorn_passes(nle_ctx* c, const T_* d_phi, long long M, int ld, int r,
         // c = recip(Phi (lam o t_r));  t_c = Phi^T c
         idx_c_in = cur;
         int nxt = (cur + 1) % 3;
-        PROFILED(c, NLE_K_SINKHORN_PASS, rowpass_any(c->stream, nlek::ROWPASS_RECIP, d_phi, M, ld, d_t[cur].p,
+        PROFILED(c, NLE_K_SINKHORN_PASS, rowpass_any(c->stream, nlek::ROWPASS_RECIP, d_phi, M, ld_phi, r, d_t[cur].p,
                                                        d_lam.p, nullptr, NLE_EPS, d_partial.p, &nb));
         PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(c->stream, d_partial.p, nb, ld, d_t[nxt].p));
         all_reduce(c, d_t[nxt].p, ld);
@@ -436,7 +443,7 @@ void sinkhorn_passes(nle_ctx* c, const T_* d_phi, long long M, int ld, int r,
             // only u_r = lam o t_c enters the W blocks)
             nxt = (cur + 1) % 3;
             if (nxt == idx_c_in) nxt = (nxt + 1) % 3;
-            PROFILED(c, NLE_K_SINKHORN_PASS, rowpass_any(c->stream, nlek::ROWPASS_RECIP, d_phi, M, ld, d_t[cur].p,
+            PROFILED(c, NLE_K_SINKHORN_PASS, rowpass_any(c->stream, nlek::ROWPASS_RECIP, d_phi, M, ld_phi, r, d_t[cur].p,
                                                            d_lam.p, nullptr, NLE_EPS, d_partial.p, &nb));
             PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(c->stream, d_partial.p, nb, ld, d_t[nxt].p));
             all_reduce(c, d_t[nxt].p, ld);
@@ -989,7 +996,7 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
             const long long mc = chunk_rows(i0);
             gen(i0, mc);
             int nb = 0;
-            PROFILED(c, NLE_K_SINKHORN_PASS, nlek::rowpass64(st, mode, d_K.p, mc, ld, sk.d_w.p, d_ones.p, nullptr, NLE_EPS, d_partial.p, &nb));
+            PROFILED(c, NLE_K_SINKHORN_PASS, nlek::rowpass64(st, mode, d_K.p, mc, ld, ld, sk.d_w.p, d_ones.p, nullptr, NLE_EPS, d_partial.p, &nb));
             PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(st, d_partial.p, nb, ld, d_zc.p));
             HIP_OK(nlek::add64(st, d_z.p, d_zc.p, ld));
             if (last) PROFILED(c, NLE_K_SMALL, nlek::row_scalings64(st, d_K.p, mc, ld, p, sk.d_w.p, NLE_EPS, d_cbuf.p + i0));
@@ -1642,7 +1649,7 @@ void apply_impl(nle_filter* f, const float* d_x_in, int H, int W, const double* 
     HIP_OK(hipMemcpyAsync(d_resp.p, resp.data(), resp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     int nb = 0;
     if (f->d_V64)
-        PROFILED(c, NLE_K_APPLY_REDUCE, nlek::rowpass64(c->stream, nlek::ROWPASS_XVEC, f->d_V64, M, ld, nullptr, nullptr,
+        PROFILED(c, NLE_K_APPLY_REDUCE, nlek::rowpass64(c->stream, nlek::ROWPASS_XVEC, f->d_V64, M, ld, ld, nullptr, nullptr,
                                                         d_x + pix0, NLE_EPS, d_partial.p, &nb));
     else
     PROFILED(c, NLE_K_APPLY_REDUCE, nlek::rowpass(c->stream, nlek::ROWPASS_XVEC, f->d_V, M, ld, nullptr, nullptr,

@@ -714,3 +714,112 @@ def test_device_tridiagonalisation_gives_the_host_solver_s_eigenpairs(nle, ctx, 
     U2, D2, _ = ctx.eigen_decomposition_top_device(M2, k)
     assert np.abs(D2 - np.linalg.eigvalsh(M2)[::-1]).max() < 1e-13
     assert np.abs(M2 @ U2 - U2 * D2[:k]).max() < 1e-12
+
+
+# (H, W, nRow, nCol, hx, hy, T, K, L): K' x L = 8960, 8250, 16384 -- beyond the 8192 table entries (64 KiB of fp64) that
+# one launch of the apply-expand kernels holds in LDS, so the layers go out in groups
+MANY_LAYER_CASES = [
+    (64, 64, 12, 12, 12.0, 30.0, 5, 140, 64),
+    (64, 64, 16, 16, 8.0, 30.0, 5, 250, 33),
+    (48, 64, 16, 16, 6.0, 25.0, 5, 256, 64),
+]
+
+
+def _gamma(k):
+    u = 2.0 ** -53
+    return k * u / (1.0 - k * u)
+
+
+def _check_layers_against_single_applies(nle, f, x32, Y32, L, where):
+    """metamorphic, independent of the oracle: layer l of apply_layers(L) against apply(x, fS = response l), the L = 1
+    route.  Both are the fp32 rounding of an fp64 sum of the same K' terms V_ik g_k t_k, so
+    |a - b| <= 2^-23 max(|a|, |b|) + g(K' + 2) sum_k |V_ik g_k t_k|"""
+    ev = f.eigvals
+    Kp = ev.size
+    resp = nle.layer_responses(ev, L)
+    V = f.eigvecs().cpu().numpy()[:, :Kp].astype(np.float64)
+    t = V.T @ x32.astype(np.float64).ravel()
+    for l in sorted({0, 1, L - 2, L - 1}):
+        a = Y32[l].astype(np.float64)
+        b = f.apply(x32, resp[l]).cpu().numpy().astype(np.float64)
+        mag = np.abs(V) @ np.abs(resp[l] * t)
+        bound = 2.0 ** -23 * np.maximum(np.abs(a), np.abs(b)) + _gamma(Kp + 2) * mag
+        worst = float((np.abs(a - b) / np.maximum(bound, 1e-300)).max())
+        assert (np.abs(a - b) <= bound).all(), f"{where}: layer {l} of apply_layers({L}) != apply(response {l}): {worst:.3g} x bound"
+
+
+@pytest.mark.parametrize("m", [4, 5, 1], ids=["materialised_f64", "streamed_f64", "materialised_f32"])
+@pytest.mark.parametrize("case", MANY_LAYER_CASES, ids=["140x64", "250x33", "256x64"])
+def test_apply_layers_up_to_64_layers_on_many_eigenvectors(nle, oracle, ctx, m, case):
+    """nle_apply_layers takes 1 <= L <= 64 on any K': every one of the L layers against the oracle (per-layer norms are
+    8 .. 380 for the detail layers, ~8e3 for the base layer: relative L2 is well posed for all of them, none is left
+    out), at the 1e-4 bar on the two fp64 formulations.  The opt-in fp32 formulation is here for its apply kernel, not
+    its training accuracy (12 .. 28 pixels per sample, below the 64 at which test_train_apply_layers_match_oracle
+    relaxes it): the call must succeed, K' must match and the metamorphic check must hold; its error against the
+    oracle is printed."""
+    H, W, nr, nc, hx, hy, T, K, L = case
+    x = oracle.synthetic_luminance(H, W)
+    x32 = x.astype(np.float32)
+    V_o, S_o = oracle.train_filter(x, nr, nc, hx, hy, T, K)
+    assert S_o.size == K, "the case must keep every requested eigenvector"
+    Y_o = oracle.apply_layers(V_o, S_o, x, L).reshape(L, -1)
+    norms = np.linalg.norm(Y_o, axis=1)
+    assert norms.min() > 1.0, "every layer must be well posed for a relative error"
+    ctx.set_mode(m)
+    try:
+        f = nle.NLEFilter(ctx).train_filter(x32, nr, nc, hx, hy, T, K)
+        Y32 = f.apply_layers(x32, L).cpu().numpy()
+    finally:
+        ctx.set_mode(0)
+    d = f.diag()
+    assert d["formulation"] == m and d["K"] == S_o.size and Y32.shape == (L, H * W)
+    assert np.isfinite(Y32).all()
+    errs = np.array([rel_l2(Y32[j], Y_o[j]) for j in range(L)])
+    print(f"many layers, mode {m}, K' x L = {S_o.size} x {L}: per-layer rel L2 vs oracle max {errs.max():.2e} "
+          f"(layer {int(errs.argmax())}), median {np.median(errs):.2e}; bar {PER_LAYER_TOL:.0e}"
+          + ("" if m in FP64_MODES else " (not asserted for the fp32 formulation)"))
+    if m in FP64_MODES:
+        for j in range(L):
+            assert errs[j] <= PER_LAYER_TOL, f"layer {j}: {errs[j]:.3e}"
+    _check_layers_against_single_applies(nle, f, x32, Y32, L, f"mode {m}")
+    f.close()
+
+
+def test_apply_layers_64_layers_on_the_table_formulation(nle, oracle, ctx):
+    """the table formulation at its own limits (K = 128, L = 64, integer plane, 12 x 12 grid): it applies the layers a few
+    per launch (as many tables as fit in LDS) -- all 64 against the oracle, and against the single-layer route"""
+    H, W, nr, nc, hx, hy, T, K, L = 64, 64, 12, 12, 12.0, 30.0, 5, 128, 64
+    x = oracle.synthetic_luminance(H, W)
+    assert np.array_equal(x, np.rint(x)) and x.min() >= 0 and x.max() <= 255
+    x32 = x.astype(np.float32)
+    V_o, S_o = oracle.train_filter(x, nr, nc, hx, hy, T, K)
+    assert S_o.size == K
+    Y_o = oracle.apply_layers(V_o, S_o, x, L).reshape(L, -1)
+    assert np.linalg.norm(Y_o, axis=1).min() > 1.0
+    ctx.set_mode(2)
+    ctx.profile(True)
+    try:
+        f = nle.NLEFilter(ctx).train_filter(x32, nr, nc, hx, hy, T, K)
+        Y32 = f.apply_layers(x32, L).cpu().numpy()
+        stats = ctx.kernel_stats()
+    finally:
+        ctx.profile(False)
+        ctx.set_mode(0)
+    d = f.diag()
+    assert d["formulation"] == nle.MODE_PHI_FREE and d["K"] == K
+    # one table build per Sinkhorn pass after the column sum, then one per launch of the apply, each launch taking at
+    # most 4 layers (kDotLayers / kExpLayers): 64 layers cannot go out in one
+    launches = stats["sink_tables"][0] - (2 * T - 1)
+    print(f"table formulation: {L} layers in {launches} launches of the expand half")
+    assert -(-L // 4) <= launches <= L
+    errs = np.array([rel_l2(Y32[j], Y_o[j]) for j in range(L)])
+    print(f"many layers, table formulation, K' x L = {K} x {L}: per-layer rel L2 vs oracle max {errs.max():.2e} "
+          f"(layer {int(errs.argmax())}); bar {PER_LAYER_TOL:.0e}")
+    for j in range(L):
+        assert errs[j] <= PER_LAYER_TOL, f"layer {j}: {errs[j]:.3e}"
+    # layer l alone through apply(): the same tables and sums, one layer per launch -- equal up to the fp32 rounding
+    resp = nle.layer_responses(f.eigvals, L)
+    for l in (0, 1, L - 2, L - 1):
+        b = f.apply(x32, resp[l]).cpu().numpy()
+        assert rel_l2(Y32[l], b) < 1e-6, (l, rel_l2(Y32[l], b))
+    f.close()
