@@ -129,14 +129,41 @@ int nle_ctx_set_mode(nle_ctx* ctx, int mode);
  * nle_compute_kernel and nle_nystrom included, returns NLE_ERR_INVALID.  0 <= radius <= NLE_PATCH_RADIUS_MAX. */
 #define NLE_PATCH_RADIUS_MAX 7
 int nle_ctx_set_patch_radius(nle_ctx* ctx, int radius);
+/* Chroma-aware (Lab) affinities, opt-in (new in this build: the reference compares two pixels by position and luminance
+ * only, src/filter.cpp:94-112, so two regions of equal lightness and different colour are one tone to the filter).  With
+ * the a and b planes of 8-bit Lab set (d_a, d_b: device pointers to the full H x W planes, fp32, integer valued in
+ * [0, 255] -- what nle_lab8_channel gives; BORROWED until they are replaced or cleared) every affinity, K_A and K_AB
+ * alike, gets one more term.  With R the patch radius (0: single values), rho reflect-101 and e0 the exponent this build
+ * computes without chroma (R = 0: -(1/hx^2) (double)d2 - (1/hy^2) dL^2; R > 0: -(1/hx^2) (double)d2 - pwd (double)S_L):
+ *   S_ab = sum_{dy,dx in [-R, R]} (a[rho(r+dy), rho(c+dx)] - a[rho(rs+dy), rho(cs+dx)])^2 + (b[..] - b[..])^2   (exact integer)
+ *   K_ij = exp(e0 - cwd (double)S_ab),   cwd = (1/hc^2) / (2R+1)^2
+ * the chroma term subtracted last, every operation rounded on its own (no fma).  hc > 0 is the chroma bandwidth: a chroma
+ * difference per pixel, the same unit as hy.  Every later stage is the reference's.  NULL, NULL and any hc: off (the
+ * default), and then none of this runs: every code path and every number is what it was.  One pointer NULL and the other
+ * not, or hc not finite or <= 0, is NLE_ERR_INVALID.  The planes describe the trains (nle_train, nle_train_host,
+ * nle_train_host_u8) and nle_compute_kernel64 calls that follow, exactly where patch affinities run: NLE_MODE_AUTO (which
+ * then takes NLE_MODE_MATERIALISED_F64, or NLE_MODE_STREAMED_F64 by the memory rule) and those two modes; the grid and the
+ * farthest sampler; full-plane input at world > 1.  A train checks that L, a and b are integer valued in [0, 255] (agreed
+ * by every rank).  Anything else returns NLE_ERR_INVALID before any collective and leaves the ctx usable: the other modes
+ * (a 256-level table cannot index a colour triple), nle_compute_kernel, nle_nystrom, slab input at world > 1, a
+ * non-integer plane, and a patch radius above NLE_CHROMA_PATCH_RADIUS_MAX (S_ab is a second int8 MFMA accumulation over
+ * 2 (2R+1)^2 values; radius 4-7 would add three or more K steps where the plane gather already dominates).  The farthest
+ * sampler keeps its luminance-only distance D below: chroma applies to the affinities only, as a patch radius does.
+ * The affinity kernels keep the samples' tables in LDS: with chroma nle_compute_kernel64 takes at most 2728 samples at patch
+ * radius 0 and 5984 above (NLE_ERR_INVALID beyond; a train takes at most 2048 anyway).
+ * Applying a filter needs nothing: V is explicit in both fp64 forms.  nle_filter_chroma: the hc a filter was trained with,
+ * 0.0 when it was trained without. */
+#define NLE_CHROMA_PATCH_RADIUS_MAX 3
+int nle_ctx_set_chroma(nle_ctx* ctx, const float* d_a, const float* d_b, double hc);
+int nle_filter_chroma(const nle_filter* f, double* hc);
 /* Sample selection, opt-in (new in this build: the reference always takes its Cartesian grid, src/filter.cpp:56-80).
  *   NLE_SAMPLER_GRID      the reference's grid (default; bit for bit what this build always computed)
  *   NLE_SAMPLER_FARTHEST  farthest-point selection in the affinity's own metric, same count p as the grid would take:
  *     D(i, j) = (1/hx^2) (double)(dr^2 + dc^2) + (1/hy^2) dy^2   (dr dc integer, dy = (double)y_i - (double)y_j, no fma)
  *     s_0 = pixel (H/2, W/2); then p - 1 times the pixel whose smallest D to the samples chosen so far is largest (ties
  *     to the smallest row-major index).  The set is used in ascending row-major order (the reference's [selected; rest]).
- * It always uses the single-value distance above, also with a patch radius R > 0 (which then applies to the affinities
- * only).  Farthest applies to nle_train* and nle_compute_kernel64, in NLE_MODE_AUTO (which takes NLE_MODE_MATERIALISED_F64,
+ * It always uses the single-value, luminance-only distance above, also with a patch radius R > 0 or with chroma planes
+ * set (which then apply to the affinities only).  Farthest applies to nle_train* and nle_compute_kernel64, in NLE_MODE_AUTO (which takes NLE_MODE_MATERIALISED_F64,
  * or NLE_MODE_STREAMED_F64 by the memory rule), NLE_MODE_MATERIALISED_F64 and NLE_MODE_STREAMED_F64; the other modes, slab
  * input at world > 1, nle_compute_kernel and nle_nystrom return NLE_ERR_INVALID.  At world > 1 (full-plane input) rank 0
  * selects and the set reaches the other ranks through the fp64 all-reduce. */

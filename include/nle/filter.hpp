@@ -191,8 +191,9 @@ public:
     void trainFilter(const Image& channel, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,
                      int nEigenVectors);
     // train on an fp32 luminance plane that is already on the device
+    // (d_a, d_b: the a and b planes for chromaBandwidth > 0, as nle_ctx_set_chroma takes them; both null: no chroma)
     void trainOnDevice(const float* d_lum, int rows, int cols, int nRowSamples, int nColSamples, DType hx, DType hy,
-                       int nSinkhornIter, int nEigenVectors);
+                       int nSinkhornIter, int nEigenVectors, const float* d_a = nullptr, const float* d_b = nullptr);
     // per-layer outputs (L planes, CV_64F) -- what the 1e-4 per-detail-layer bar compares
     std::vector<Image> applyLayers(const Image& channel, int nLayers) const;
 
@@ -211,6 +212,11 @@ public:
     // the exact (Nystrom-free) filter for trainForEnhancement / trainForDenoise / trainFilter (NLE_MODE_EXACT_F64 around
     // the train; new here): one device, at most NLE_EXACT_MAX_PIXELS pixels, patchRadius 0 and the grid sampler
     bool exact = false;
+    // chroma-aware (Lab) affinities for trainForEnhancement (nle_ctx_set_chroma; new here, 0 = the reference's
+    // luminance-only affinity): the chroma bandwidth hc > 0, a chroma difference per pixel in the unit of hy.  Needs
+    // patchRadius <= NLE_CHROMA_PATCH_RADIUS_MAX and not `exact`.  trainFilter takes a bare luminance plane, has no
+    // chroma and ignores it; trainForDenoise throws if it is set (a and b are what that path estimates)
+    double chromaBandwidth = 0;
 
 private:
     nle_ctx* ctx_ = nullptr;

@@ -242,6 +242,7 @@ class Context:
         self._cb = None
         self._comm = None
         self._allreduce = allreduce
+        self._chroma = None  # set_chroma: the a and b planes the ctx borrows
 
     def set_shard(self, rank: int, world: int, n_samples: int, allreduce):
         """`allreduce(tensor)` sums a float64 CUDA tensor in place over all ranks (e.g.
@@ -299,6 +300,21 @@ class Context:
         """patch (non-local-means) affinities over (2R + 1)^2 neighbourhoods, 0 <= R <= NLE_PATCH_RADIUS_MAX; 0 (default) is
         the reference's single-value affinity (nle_ctx_set_patch_radius)"""
         _check(lib().nle_ctx_set_patch_radius(self._h, int(radius)), self._h)
+
+    def set_chroma(self, a=None, b=None, hc: float = 0.0):
+        """chroma-aware (Lab) affinities: the a and b planes of 8-bit Lab (H x W, integer valued in [0, 255]) and the chroma
+        bandwidth hc > 0; a = b = None turns them off (nle_ctx_set_chroma).  The ctx borrows the planes: the device
+        tensors made here are kept alive until they are replaced or cleared."""
+        if a is None and b is None:
+            _check(lib().nle_ctx_set_chroma(self._h, None, None, float(hc)), self._h)
+            self._chroma = None
+            return
+        ta = None if a is None else self._lum(a)
+        tb = None if b is None else self._lum(b)
+        _torch().cuda.synchronize(self.device)  # the planes are complete before any later train reads them
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        _check(lib().nle_ctx_set_chroma(self._h, ptr(ta), ptr(tb), float(hc)), self._h)
+        self._chroma = (ta, tb)
 
     def set_sampler(self, sampler: int):
         """sample selection: SAMPLER_GRID (0, default, the reference's grid) or SAMPLER_FARTHEST (1, farthest-point
@@ -830,6 +846,12 @@ class NLEFilter:
         _check(lib().nle_filter_diag(self._f, _np_ptr(v)))
         keys = ("formulation", "p", "r_Ka", "r_Wa", "r_Q", "K", "chol_Ka", "chol_Wa")
         return {k: int(x) for k, x in zip(keys, v)}
+
+    def chroma(self):
+        """the chroma bandwidth hc the filter was trained with, 0.0 without (nle_filter_chroma)"""
+        hc = C.c_double()
+        _check(lib().nle_filter_chroma(self._f, C.byref(hc)))
+        return hc.value
 
     @property
     def eigvals(self):

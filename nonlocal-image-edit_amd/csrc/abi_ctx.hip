@@ -323,6 +323,29 @@ int nle_ctx_set_patch_radius(nle_ctx* ctx, int radius) {
     });
 }
 
+int nle_ctx_set_chroma(nle_ctx* ctx, const float* d_a, const float* d_b, double hc) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_a && !d_b) {  // off, whatever hc is
+            ctx->chroma_a = ctx->chroma_b = nullptr;
+            ctx->chroma_hc = 0.0;
+            return;
+        }
+        if (!d_a || !d_b) throw Fail{NLE_ERR_INVALID, "nle_ctx_set_chroma takes both the a and the b plane, or neither"};
+        if (!std::isfinite(hc) || !(hc > 0))
+            throw Fail{NLE_ERR_INVALID, "the chroma bandwidth hc must be finite and > 0, got " + std::to_string(hc)};
+        ctx->chroma_a = d_a;
+        ctx->chroma_b = d_b;
+        ctx->chroma_hc = hc;
+    });
+}
+
+int nle_filter_chroma(const nle_filter* f, double* hc) {
+    if (!f || !hc) return NLE_ERR_INVALID;
+    *hc = f->chroma_hc;
+    return NLE_OK;
+}
+
 int nle_ctx_set_sampler(nle_ctx* ctx, int sampler) {
     if (!ctx) return NLE_ERR_INVALID;
     return guard(ctx, [&] {

@@ -35,18 +35,26 @@ __device__ __forceinline__ double recip0_g(double s, double eps) {
 // pixel's row: 16-byte coalesced stores, 32-bit index arithmetic, the samples (row, col, value as doubles) in LDS.
 constexpr int kAff64Pix = 64;
 
+// CHROMA (nle_ctx_set_chroma, radius 0): the samples' (a, b) sit beside their (row, col, L) in LDS, the pixel's a and b are
+// loaded once, and the exponent is (-sw d2 - pw dL^2) - cw (da^2 + db^2), every operation rounded on its own (the order of
+// the definition in include/nle.h and of build_Ka on the host).  The CHROMA = false instantiation is the kernel as it was.
+template <bool CHROMA>
 __global__ __launch_bounds__(256) void k_affinity64(const float* __restrict__ lum, GridSpec gs,
                                                     const Sample4* __restrict__ samples, int p, int ld, double sw,
                                                     double pw, long long pix0, long long M, double* __restrict__ kab,
-                                                    int skip_samples, const unsigned* __restrict__ smask) {
+                                                    int skip_samples, const unsigned* __restrict__ smask,
+                                                    const float* __restrict__ pa, const float* __restrict__ pb,
+                                                    const float2* __restrict__ sab, double cw) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw64[];
     int2* srow_col = reinterpret_cast<int2*>(smem_raw64);                       // [ld]
     double* sval = reinterpret_cast<double*>(smem_raw64 + (size_t)ld * sizeof(int2));  // [ld]
+    float2* schroma = reinterpret_cast<float2*>(sval + ld);                     // [ld], CHROMA only
     for (int k = threadIdx.x; k < ld; k += 256) {
         Sample4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (k < p) v = samples[k];
         srow_col[k] = make_int2((int)v.x, (int)v.y);
         sval[k] = (double)v.z;
+        if constexpr (CHROMA) schroma[k] = k < p ? sab[k] : make_float2(0.f, 0.f);
     }
     __syncthreads();
     const unsigned nq = (unsigned)ld >> 1, per_group = kAff64Pix * nq;
@@ -64,18 +72,40 @@ __global__ __launch_bounds__(256) void k_affinity64(const float* __restrict__ lu
             const bool zero_row = skip_samples && is_sample(gs, smask, gi, row, col);
             double2 o = make_double2(0.0, 0.0);
             const unsigned s0 = 2 * q;
-            if (!zero_row) {
-                if (s0 < (unsigned)p) {
-                    const int2 rc = srow_col[s0];
-                    const long long dr = row - rc.x, dc = col - rc.y;  // integer spatial term (:109)
-                    const double dv = x - sval[s0];
-                    o.x = exp(-sw * (double)(dr * dr + dc * dc) - pw * (dv * dv));
+            if constexpr (CHROMA) {
+#pragma clang fp contract(off)
+                if (!zero_row) {
+                    const float xa = pa[gi], xb = pb[gi];
+                    double v[2] = {0.0, 0.0};
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const unsigned s = s0 + e;
+                        if (s < (unsigned)p) {
+                            const int2 rc = srow_col[s];
+                            const float2 ab = schroma[s];
+                            const long long dr = row - rc.x, dc = col - rc.y;
+                            const double dv = x - sval[s];
+                            const double da = (double)(xa - ab.x), db = (double)(xb - ab.y);  // integers: exact
+                            const double e0 = -sw * (double)(dr * dr + dc * dc) - pw * (dv * dv);
+                            v[e] = exp(e0 - cw * (da * da + db * db));
+                        }
+                    }
+                    o = make_double2(v[0], v[1]);
                 }
-                if (s0 + 1 < (unsigned)p) {
-                    const int2 rc = srow_col[s0 + 1];
-                    const long long dr = row - rc.x, dc = col - rc.y;
-                    const double dv = x - sval[s0 + 1];
-                    o.y = exp(-sw * (double)(dr * dr + dc * dc) - pw * (dv * dv));
+            } else {
+                if (!zero_row) {
+                    if (s0 < (unsigned)p) {
+                        const int2 rc = srow_col[s0];
+                        const long long dr = row - rc.x, dc = col - rc.y;  // integer spatial term (:109)
+                        const double dv = x - sval[s0];
+                        o.x = exp(-sw * (double)(dr * dr + dc * dc) - pw * (dv * dv));
+                    }
+                    if (s0 + 1 < (unsigned)p) {
+                        const int2 rc = srow_col[s0 + 1];
+                        const long long dr = row - rc.x, dc = col - rc.y;
+                        const double dv = x - sval[s0 + 1];
+                        o.y = exp(-sw * (double)(dr * dr + dc * dc) - pw * (dv * dv));
+                    }
                 }
             }
             *reinterpret_cast<double2*>(out + (size_t)f * 2) = o;
@@ -89,8 +119,25 @@ hipError_t affinity64(hipStream_t s, const float* d_lum, GridSpec gs, const Samp
     if (ld & 1) return hipErrorInvalidValue;   // rows are written two doubles at a time (ld = nle_ld(p) is a multiple of 4)
     const long long ngroups = (M + kAff64Pix - 1) / kAff64Pix;
     const int grid = (int)std::min<long long>(ngroups, 16384);
-    hipLaunchKernelGGL(k_affinity64, dim3((unsigned)grid), dim3(256), (size_t)ld * (sizeof(int2) + sizeof(double)), s, d_lum, gs,
-                       d_samples, p, ld, sw, pw, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask);
+    hipLaunchKernelGGL(k_affinity64<false>, dim3((unsigned)grid), dim3(256), (size_t)ld * (sizeof(int2) + sizeof(double)), s,
+                       d_lum, gs, d_samples, p, ld, sw, pw, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask, nullptr, nullptr,
+                       nullptr, 0.0);
+    return hipGetLastError();
+}
+
+size_t affinity64_chroma_lds_bytes(int ld) { return (size_t)ld * (sizeof(int2) + sizeof(double) + sizeof(float2)); }
+
+hipError_t affinity64_chroma(hipStream_t s, const float* d_lum, const float* d_a, const float* d_b, GridSpec gs,
+                             const Sample4* d_samples, const float2* d_sab, int p, int ld, double sw, double pw, double cw,
+                             long long pix0, long long M, double* d_kab, bool skip_samples, const unsigned* d_smask) {
+    if (M <= 0) return hipSuccess;
+    // the launch takes the default dynamic-LDS allowance (the caller refuses a larger sample set with a message)
+    if ((ld & 1) || ld < p || !d_a || !d_b || !d_sab || affinity64_chroma_lds_bytes(ld) > kDynLdsDefault)
+        return hipErrorInvalidValue;
+    const long long ngroups = (M + kAff64Pix - 1) / kAff64Pix;
+    const int grid = (int)std::min<long long>(ngroups, 16384);
+    hipLaunchKernelGGL(k_affinity64<true>, dim3((unsigned)grid), dim3(256), affinity64_chroma_lds_bytes(ld), s, d_lum, gs,
+                       d_samples, p, ld, sw, pw, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask, d_a, d_b, d_sab, cw);
     return hipGetLastError();
 }
 

@@ -150,6 +150,16 @@ hipError_t hist_tables(hipStream_t s, GridSpec gs, const Sample4* d_samples, int
 hipError_t affinity64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, int ld, double sw,
                       double pw, long long pix0, long long M, double* d_kab, bool skip_samples = false,
                       const unsigned* d_smask = nullptr);
+// chroma-aware rows at patch radius 0 (nle_ctx_set_chroma): exp((-sw d2 - pw dL^2) - cw (da^2 + db^2)), every operation rounded
+// on its own.  d_a, d_b: the full a and b planes (integer valued in [0, 255]); d_sab[j] = sample j's (a, b).  The samples'
+// tables take affinity64_chroma_lds_bytes(ld) of dynamic LDS, at most kDynLdsDefault (what a launch gets without opting in
+// to more): a larger ld is hipErrorInvalidValue, and the caller refuses it with a message first.
+constexpr size_t kDynLdsDefault = 64 * 1024;
+size_t affinity64_chroma_lds_bytes(int ld);
+hipError_t affinity64_chroma(hipStream_t s, const float* d_lum, const float* d_a, const float* d_b, GridSpec gs,
+                             const Sample4* d_samples, const float2* d_sab, int p, int ld, double sw, double pw, double cw,
+                             long long pix0, long long M, double* d_kab, bool skip_samples = false,
+                             const unsigned* d_smask = nullptr);
 // patch (non-local-means) affinity rows, patch.hip: the rows affinity64 fills, with the intensity term pwd * S_ij, S_ij the
 // integer sum of squared differences of the (2R + 1)^2 patches (reflect-101 borders), 1 <= R <= 7, plane integer in [0, 255].
 // d_spatch: patch_spatch_bytes(p, R) bytes, sample j's patch values - 128 as int8 in row j (patch_kpad(R) bytes, zero
@@ -162,6 +172,19 @@ hipError_t patch_affinity64(hipStream_t s, const float* d_lum, GridSpec gs, int 
                             const signed char* d_spatch, const int* d_snorm, int p, int ld, double sw, double pwd,
                             long long pix0, long long M, double* d_kab, bool skip_samples = false,
                             const unsigned* d_smask = nullptr);
+// the same rows with the chroma term (nle_ctx_set_chroma), 1 <= R <= 3: exp((-sw d2 - pwd S_L) - cwd S_ab), S_ab the integer
+// sum of squared differences of the a and of the b patches, a second i32 accumulation on the same MFMA.  d_cpatch:
+// patch_cpatch_bytes(p, R) bytes, row j = sample j's a patch then its b patch, each value - 128 as int8, zero padded to
+// patch_ckpad(R) bytes (rows p .. roundup16(p) zero); d_cnorm[j] = sum of the squares of those int8 values.
+int patch_ckpad(int R);
+size_t patch_cpatch_bytes(int p, int R);
+constexpr size_t kPatchChromaLdsMax = 128 * 1024;  // dynamic LDS the chroma patch kernel may ask for (160 KiB per CU)
+size_t patch_affinity64_chroma_lds_bytes(int ld);
+hipError_t patch_affinity64_chroma(hipStream_t s, const float* d_lum, const float* d_a, const float* d_b, GridSpec gs, int R,
+                                   const Sample4* d_samples, const signed char* d_spatch, const int* d_snorm,
+                                   const signed char* d_cpatch, const int* d_cnorm, int p, int ld, double sw, double pwd,
+                                   double cwd, long long pix0, long long M, double* d_kab, bool skip_samples = false,
+                                   const unsigned* d_smask = nullptr);
 // farthest-point sample selection (sampler.hip): the p pixels of NLE_SAMPLER_FARTHEST in the order chosen, into d_list (p
 // ints), for the full H x W plane d_lum.  Workspace: d_m (H W doubles), d_pv / d_pi (2 farthest_max_blocks() each).
 int farthest_max_blocks();

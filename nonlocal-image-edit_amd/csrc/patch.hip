@@ -16,6 +16,9 @@
 // block by column block (kPatchCols samples), the int32 dot products go to LDS; the epilogue is k_affinity64's: one
 // thread per double2 of the group's contiguous output span, fp64 exponent in the same order (not contracted), libm exp,
 // 16-byte stores.
+//
+// With chroma planes (nle_ctx_set_chroma, R <= 3) the KC > 0 instantiations add the term cwd S_ab of the a and b patches:
+// see the comment at the kernel.
 #include "kernels.h"
 
 #include <algorithm>
@@ -28,6 +31,7 @@ namespace {
 constexpr int kPatchPix = 64;         // pixels per group (4 waves x 16-row MFMA tiles)
 constexpr int kPatchCols = 128;       // samples per column block of the LDS dot-product tile
 constexpr int kPatchDotLd = kPatchCols + 4;  // row stride of that tile (ints): the 4-row lane groups fall on other banks
+constexpr int kPatchChromaCols = kPatchCols / 2;  // chroma form: two tiles (L and ab dot products), each half as wide
 
 // reflect-101 for |overhang| <= n - 1 (the caller checks R <= min(H, W) - 1); the clamp only keeps a bad argument in bounds
 __device__ __forceinline__ int reflect101(int t, int n) {
@@ -61,26 +65,42 @@ hipError_t patch_gather(hipStream_t s, const float* d_lum, int H, int W, int R, 
     return hipGetLastError();
 }
 
-template <int KS>
-__global__ __launch_bounds__(256) void k_patch_affinity64(const float* __restrict__ lum, GridSpec gs, int R,
+// KC > 0: the chroma form (nle_ctx_set_chroma, R <= 3).  S_L and S_ab carry different weights, so S_ab is a second i32
+// accumulation of KC K steps over the a patch followed by the b patch (2 d values, zero padded to KC x 64), gathered from
+// the a and b planes as the L fragment is from L.  Both dot-product tiles live in LDS side by side, each half as wide
+// (64 samples per column block instead of 128), so the kernel's LDS and occupancy are those of the chroma-off form; the
+// epilogue subtracts cwd S_ab last.  KC = 0 is the kernel as it was (its launch bounds ask for nothing: same code).
+template <int KS, int KC>
+__global__ __launch_bounds__(256, KC > 0 ? 4 : 1) void k_patch_affinity64(const float* __restrict__ lum, GridSpec gs, int R,
                                                           const Sample4* __restrict__ samples,
                                                           const signed char* __restrict__ spatch,
                                                           const int* __restrict__ snorm, int p, int ld, double sw, double pwd,
                                                           long long pix0, long long M, double* __restrict__ kab,
-                                                          int skip_samples, const unsigned* __restrict__ smask) {
+                                                          int skip_samples, const unsigned* __restrict__ smask,
+                                                          const float* __restrict__ pa, const float* __restrict__ pb,
+                                                          const signed char* __restrict__ cpatch,
+                                                          const int* __restrict__ cnorm, double cwd) {
     // the exponent is rounded operation by operation, as the definition (and build_Ka on the host) evaluates it: a
     // contracted fma would round -sw d2 - pwd S once instead of twice, ~1 ulp of a large exponent
 #pragma clang fp contract(off)
+    constexpr bool CHROMA = KC > 0;
+    constexpr int COLS = CHROMA ? kPatchChromaCols : kPatchCols;  // samples per column block of a dot-product tile
+    constexpr int DLD = COLS + 4;                               // its row stride (ints), as kPatchDotLd
+    constexpr int KCN = CHROMA ? KC : 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_patch[];
     int2* srow_col = reinterpret_cast<int2*>(smem_patch);                                  // [ld]
     int* sn = reinterpret_cast<int*>(smem_patch + (size_t)ld * sizeof(int2));               // [ld]
     int* pn = sn + ld;                                                                      // [kPatchPix]
-    int* dot = pn + kPatchPix;                                                              // [kPatchPix][kPatchDotLd]
+    int* dot = pn + kPatchPix;                                                              // [kPatchPix][DLD]
+    int* dotc = dot + kPatchPix * DLD;                                                      // CHROMA: [kPatchPix][DLD]
+    int* pcn = dotc + kPatchPix * DLD;                                                      // CHROMA: [kPatchPix]
+    int* scn = pcn + kPatchPix;                                                             // CHROMA: [ld]
     for (int k = threadIdx.x; k < ld; k += 256) {
         Sample4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (k < p) v = samples[k];
         srow_col[k] = make_int2((int)v.x, (int)v.y);
         sn[k] = k < p ? snorm[k] : 0;
+        if constexpr (CHROMA) scn[k] = k < p ? cnorm[k] : 0;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int P = 2 * R + 1, d = P * P, KP = KS * 64;
@@ -91,7 +111,8 @@ __global__ __launch_bounds__(256) void k_patch_affinity64(const float* __restric
         // ---- A fragments of this wave's 16 pixels: lane holds pixel 16 wv + (lane & 15), patch entries
         //      k = 64 ks + 16 (lane >> 4) + e, e < 16 (v - 128, 0 beyond d or beyond M), and their partial norm
         i32x4 a[KS];
-        int nrm = 0;
+        i32x4 ac[KCN];
+        int nrm = 0, nrmc = 0;
         {
             const long long il = i0 + 16 * wv + (lane & 15);
             const bool live = il < M;
@@ -124,14 +145,59 @@ __global__ __launch_bounds__(256) void k_patch_affinity64(const float* __restric
                 }
                 a[ks] = i32x4{words[0], words[1], words[2], words[3]};
             }
+            if constexpr (CHROMA) {
+                // entries k < d: the a patch at offset k; d <= k < 2 d: the b patch at offset k - d; beyond: 0.  One
+                // word (four loads) at a time: with the K steps' 16 loads each unrolled and hoisted like the L fragment's,
+                // the kernel held 180 (KC = 1) and 256 (KC = 2) registers, 2 and 1 waves per SIMD where the chroma-off
+                // kernel of the same radius runs 4; this way, and asked for 4 by its launch bounds, it keeps 4 without scratch
+#pragma unroll
+                for (int ks = 0; ks < KC; ++ks) {
+                    i32x4 frag = {0, 0, 0, 0};
+                    const int kb = 64 * ks + 16 * (lane >> 4);
+                    const float* __restrict__ pl = kb < d ? pa : pb;
+                    const int ko = kb < d ? kb : kb - d;
+                    int dy = ko / P, dx = ko - dy * P;
+#pragma unroll 1
+                    for (int w = 0; w < 4; ++w) {
+                        unsigned wd = 0;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int k = kb + 4 * w + e;
+                            int v = 0;
+                            if (live && k < 2 * d) {
+                                const int rr = reflect101(row + dy - R, gs.H), cc = reflect101(col + dx - R, gs.W);
+                                v = (int)pl[(size_t)rr * gs.W + cc] - 128;
+                            }
+                            nrmc += v * v;
+                            wd |= ((unsigned)v & 0xffu) << (8 * e);
+                            if (++dx == P) {
+                                dx = 0;
+                                if (++dy == P) {  // the a patch is done: on to the b patch
+                                    dy = 0;
+                                    pl = pb;
+                                }
+                            }
+                        }
+                        frag[w] = (int)wd;
+                    }
+                    ac[ks] = frag;
+                }
+            }
         }
         nrm += __shfl_xor(nrm, 16);
         nrm += __shfl_xor(nrm, 32);
+        if constexpr (CHROMA) {
+            nrmc += __shfl_xor(nrmc, 16);
+            nrmc += __shfl_xor(nrmc, 32);
+        }
         __syncthreads();  // the previous group's epilogue is done with pn / dot (and the sample tables are in on the first)
-        if (lane < 16) pn[16 * wv + lane] = nrm;
-        for (int cb0 = 0; cb0 < ld; cb0 += kPatchCols) {
+        if (lane < 16) {
+            pn[16 * wv + lane] = nrm;
+            if constexpr (CHROMA) pcn[16 * wv + lane] = nrmc;
+        }
+        for (int cb0 = 0; cb0 < ld; cb0 += COLS) {
             // ---- dot products of the column block: dot[row][s - cb0] = x'_row . s'_s
-            const int t1 = min(ntiles, (cb0 + kPatchCols) >> 4);
+            const int t1 = min(ntiles, (cb0 + COLS) >> 4);
             for (int t = cb0 >> 4; t < t1; ++t) {
                 const signed char* bp = spatch + (size_t)(16 * t + (lane & 15)) * KP + 16 * (lane >> 4);
                 i32x4 acc = {0, 0, 0, 0};
@@ -141,13 +207,24 @@ __global__ __launch_bounds__(256) void k_patch_affinity64(const float* __restric
                     acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[ks], b, acc, 0, 0, 0);
                 }
                 // C/D: column = lane & 15, row = 4 (lane >> 4) + reg
-                int* dp = dot + (16 * wv + 4 * (lane >> 4)) * kPatchDotLd + 16 * t - cb0 + (lane & 15);
+                int* dp = dot + (16 * wv + 4 * (lane >> 4)) * DLD + 16 * t - cb0 + (lane & 15);
 #pragma unroll
-                for (int g = 0; g < 4; ++g) dp[g * kPatchDotLd] = acc[g];
+                for (int g = 0; g < 4; ++g) dp[g * DLD] = acc[g];
+                if constexpr (CHROMA) {
+                    const signed char* cp = cpatch + (size_t)(16 * t + (lane & 15)) * (KC * 64) + 16 * (lane >> 4);
+                    i32x4 accc = {0, 0, 0, 0};
+#pragma unroll
+                    for (int ks = 0; ks < KC; ++ks) {
+                        const i32x4 b = *reinterpret_cast<const i32x4*>(cp + 64 * ks);
+                        accc = __builtin_amdgcn_mfma_i32_16x16x64_i8(ac[ks], b, accc, 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) dp[(kPatchPix + g) * DLD] = accc[g];  // the same place in dotc
+                }
             }
             __syncthreads();
             // ---- epilogue over the group's rows x this block's columns: one double2 per thread per step
-            const int ncols = min(kPatchCols, ld - cb0), nq = ncols >> 1;
+            const int ncols = min(COLS, ld - cb0), nq = ncols >> 1;
             const unsigned per_group = (unsigned)(kPatchPix * nq);
             const unsigned nvalid = (unsigned)min((long long)kPatchPix, M - i0) * nq;
             for (unsigned f = threadIdx.x; f < per_group; f += 256) {
@@ -159,7 +236,13 @@ __global__ __launch_bounds__(256) void k_patch_affinity64(const float* __restric
                 double v[2] = {0.0, 0.0};
                 if (!zero_row) {
                     const int xn = pn[il];
-                    const int2 dd = *reinterpret_cast<const int2*>(dot + il * kPatchDotLd + 2 * q);
+                    const int2 dd = *reinterpret_cast<const int2*>(dot + il * DLD + 2 * q);
+                    int xcn = 0;
+                    int2 ddc = make_int2(0, 0);
+                    if constexpr (CHROMA) {
+                        xcn = pcn[il];
+                        ddc = *reinterpret_cast<const int2*>(dotc + il * DLD + 2 * q);
+                    }
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
                         const int s = cb0 + 2 * (int)q + e;
@@ -167,7 +250,13 @@ __global__ __launch_bounds__(256) void k_patch_affinity64(const float* __restric
                             const int2 rc = srow_col[s];
                             const long long dr = row - rc.x, dc = col - rc.y;
                             const int S = xn + sn[s] - 2 * (e ? dd.y : dd.x);
-                            v[e] = exp(-sw * (double)(dr * dr + dc * dc) - pwd * (double)S);
+                            if constexpr (CHROMA) {
+                                const int Sc = xcn + scn[s] - 2 * (e ? ddc.y : ddc.x);
+                                const double e0 = -sw * (double)(dr * dr + dc * dc) - pwd * (double)S;
+                                v[e] = exp(e0 - cwd * (double)Sc);
+                            } else {
+                                v[e] = exp(-sw * (double)(dr * dr + dc * dc) - pwd * (double)S);
+                            }
                         }
                     }
                 }
@@ -190,15 +279,60 @@ hipError_t patch_affinity64(hipStream_t s, const float* d_lum, GridSpec gs, int 
     const size_t lds = (size_t)ld * (sizeof(int2) + sizeof(int)) + kPatchPix * sizeof(int) +
                        (size_t)kPatchPix * kPatchDotLd * sizeof(int);
     const int ks = patch_kpad(R) / 64;
-#define NLE_PATCH_LAUNCH(KS_)                                                                                            \
-    hipLaunchKernelGGL(k_patch_affinity64<KS_>, dim3((unsigned)grid), dim3(256), lds, s, d_lum, gs, R, d_samples, d_spatch, \
-                       d_snorm, p, ld, sw, pwd, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask)
+#define NLE_PATCH_LAUNCH(KS_)                                                                                               \
+    hipLaunchKernelGGL((k_patch_affinity64<KS_, 0>), dim3((unsigned)grid), dim3(256), lds, s, d_lum, gs, R, d_samples,       \
+                       d_spatch, d_snorm, p, ld, sw, pwd, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask, nullptr, nullptr,  \
+                       nullptr, nullptr, 0.0)
     switch (ks) {
         case 1: NLE_PATCH_LAUNCH(1); break;
         case 2: NLE_PATCH_LAUNCH(2); break;
         case 3: NLE_PATCH_LAUNCH(3); break;
         default: NLE_PATCH_LAUNCH(4); break;
     }
+#undef NLE_PATCH_LAUNCH
+    return hipGetLastError();
+}
+
+int patch_ckpad(int R) {
+    const int d2 = 2 * (2 * R + 1) * (2 * R + 1);
+    return (d2 + 63) & ~63;
+}
+
+size_t patch_cpatch_bytes(int p, int R) { return (size_t)((p + 15) & ~15) * patch_ckpad(R); }
+
+size_t patch_affinity64_chroma_lds_bytes(int ld) {
+    return (size_t)ld * (sizeof(int2) + 2 * sizeof(int)) + 2 * kPatchPix * sizeof(int) +
+           2 * (size_t)kPatchPix * (kPatchChromaCols + 4) * sizeof(int);
+}
+
+hipError_t patch_affinity64_chroma(hipStream_t s, const float* d_lum, const float* d_a, const float* d_b, GridSpec gs, int R,
+                                   const Sample4* d_samples, const signed char* d_spatch, const int* d_snorm,
+                                   const signed char* d_cpatch, const int* d_cnorm, int p, int ld, double sw, double pwd,
+                                   double cwd, long long pix0, long long M, double* d_kab, bool skip_samples,
+                                   const unsigned* d_smask) {
+    if (M <= 0) return hipSuccess;
+    // R <= 3: one K step for L; one (R = 1) or two (R = 2, 3) for the concatenated a and b patches
+    if ((ld & 1) || R < 1 || R > 3 || ld < p || !d_a || !d_b || !d_cpatch || !d_cnorm) return hipErrorInvalidValue;
+    // 34.5 KiB of tiles + 16 bytes per sample: past 1888 samples the launch asks for more than the default allowance
+    const size_t lds = patch_affinity64_chroma_lds_bytes(ld);
+    if (lds > kPatchChromaLdsMax) return hipErrorInvalidValue;  // (the caller refuses such a sample set with a message)
+    const long long ngroups = (M + kPatchPix - 1) / kPatchPix;
+    const int grid = (int)std::min<long long>(ngroups, 8192);
+    hipError_t e = hipSuccess;
+#define NLE_PATCH_LAUNCH(KC_)                                                                                               \
+    do {                                                                                                                    \
+        if (lds > kDynLdsDefault)                                                                                           \
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_patch_affinity64<1, KC_>),                              \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
+        if (e != hipSuccess) return e;                                                                                      \
+        hipLaunchKernelGGL((k_patch_affinity64<1, KC_>), dim3((unsigned)grid), dim3(256), lds, s, d_lum, gs, R, d_samples,  \
+                           d_spatch, d_snorm, p, ld, sw, pwd, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask, d_a, d_b,      \
+                           d_cpatch, d_cnorm, cwd);                                                                         \
+    } while (0)
+    if (patch_ckpad(R) == 64)
+        NLE_PATCH_LAUNCH(1);
+    else
+        NLE_PATCH_LAUNCH(2);
 #undef NLE_PATCH_LAUNCH
     return hipGetLastError();
 }

@@ -20,14 +20,24 @@ struct SampleSet {
     int R = 0;                      // patch radius (nle_ctx_set_patch_radius)
     bool listed = false;            // pix is a sampler's list (NLE_SAMPLER_FARTHEST), not the grid's closed form
     std::vector<int> patch;         // R > 0: p x (2R + 1)^2 patch values around each sample (reflect-101), row per sample
+    // chroma (nle_ctx_set_chroma): the full a and b planes on the device, hc, and the samples' a and b values (R = 0:
+    // p each) or patches (R > 0: p x (2R + 1)^2 each, as `patch`)
+    const float* d_a = nullptr;
+    const float* d_b = nullptr;
+    double hc = 0.0;
+    bool chroma_quantised = false;  // both planes integer valued in [0, 255]
+    std::vector<int> aval, bval;
+    bool chroma() const { return d_a != nullptr; }
 };
 
 // d_lum: base of the FULL plane -- real, or virtual when the ctx takes slab input (only rows [row0, row1) of this rank
 // exist; the p sample values and the "integer valued" verdict are then completed by an all-reduce).  R > 0: also the
 // samples' patches (full plane only: the caller refuses slab input).  list: the sample pixels of NLE_SAMPLER_FARTHEST
-// (ascending, gs.p() of them; full plane only) instead of the grid's
+// (ascending, gs.p() of them; full plane only) instead of the grid's.  chroma: also the level check of the ctx's a and b
+// planes and the samples' a and b values or patches (full plane only: the caller refuses slab input)
 SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool check_quantised = false,
-                        bool slab_plane = false, int R = 0, const std::vector<long long>* list = nullptr) {
+                        bool slab_plane = false, int R = 0, const std::vector<long long>* list = nullptr,
+                        bool chroma = false) {
     SampleSet s;
     s.gs = gs;
     s.p = gs.p();
@@ -96,6 +106,30 @@ SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool
         HIP_OK(hipMemcpyAsync(s.patch.data(), d_patch.p, s.patch.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
     }
+    if (chroma) {
+        if (slab_plane || !c->chroma_a || !c->chroma_b) throw Fail{NLE_ERR_INVALID, "fetch_samples: no chroma planes"};
+        s.R = R;
+        s.d_a = c->chroma_a;
+        s.d_b = c->chroma_b;
+        s.hc = c->chroma_hc;
+        const int d = (2 * R + 1) * (2 * R + 1);  // R = 0: the one-value patch is the pixel itself
+        const size_t n = (size_t)s.p * d;
+        s.aval.resize(n);
+        s.bval.resize(n);
+        DevBuf<long long> d_pix(s.p);
+        DevBuf<int> d_ab(2 * n), d_flag(4);
+        int fl4[4] = {1, 0, 1, 0};
+        HIP_OK(hipMemcpyAsync(d_pix.p, s.pix.data(), s.p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+        PROFILED(c, NLE_K_SMALL, nlek::patch_gather(c->stream, s.d_a, gs.H, gs.W, R, d_pix.p, s.p, d_ab.p));
+        PROFILED(c, NLE_K_SMALL, nlek::patch_gather(c->stream, s.d_b, gs.H, gs.W, R, d_pix.p, s.p, d_ab.p + n));
+        PROFILED(c, NLE_K_SMALL, nlek::check_levels(c->stream, s.d_a, (long long)gs.H * gs.W, d_flag.p));
+        PROFILED(c, NLE_K_SMALL, nlek::check_levels(c->stream, s.d_b, (long long)gs.H * gs.W, d_flag.p + 2));
+        HIP_OK(hipMemcpyAsync(s.aval.data(), d_ab.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(s.bval.data(), d_ab.p + n, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipMemcpyAsync(fl4, d_flag.p, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        s.chroma_quantised = fl4[0] == 0 && fl4[2] == 0;
+    }
     return s;
 }
 
@@ -118,6 +152,24 @@ void check_patch_radius(const nle_ctx* c, int R, int H, int W) {
     if (c->slab_input && c->world > 1)
         throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need the full plane on every rank: slab input is not "
                                     "supported with them"};
+}
+
+// The checks of chroma affinities (nle_ctx_set_chroma) that need no device; the ctx's mode is checked where it applies
+void check_chroma(const nle_ctx* c, int R, int p) {
+    if (!c->chroma_a) return;
+    if (R > NLE_CHROMA_PATCH_RADIUS_MAX)
+        throw Fail{NLE_ERR_INVALID, "chroma affinities take a patch radius of at most " +
+                                        std::to_string(NLE_CHROMA_PATCH_RADIUS_MAX) + ", got " + std::to_string(R)};
+    if (c->slab_input && c->world > 1)
+        throw Fail{NLE_ERR_INVALID, "chroma affinities need the full plane on every rank: slab input is not supported with "
+                                    "them"};
+    // the samples' tables of the affinity kernels live in LDS
+    const int ld = ld4(p);
+    const bool fits = R > 0 ? nlek::patch_affinity64_chroma_lds_bytes(ld) <= nlek::kPatchChromaLdsMax
+                            : nlek::affinity64_chroma_lds_bytes(ld) <= nlek::kDynLdsDefault;
+    if (!fits)
+        throw Fail{NLE_ERR_INVALID, "chroma affinities: " + std::to_string(p) + " samples do not fit the affinity kernel's "
+                                    "LDS tables (at most 2728 at patch radius 0, 5984 above)"};
 }
 
 // The checks of the farthest sampler that need no device; the ctx's mode is checked where it applies (nle_train*)
@@ -166,10 +218,27 @@ std::vector<long long> farthest_list(nle_ctx* c, const float* d_lum, const GridS
     return list;
 }
 
-// Ka with patch affinities: S in exact integer arithmetic, the exponent in k_patch_affinity64's order (patch.hip)
+// S_ab of samples i and j: the integer sum of squared differences of their a and of their b values (R = 0) or patches
+long long chroma_ssd(const SampleSet& s, int i, int j) {
+    const int d = (2 * s.R + 1) * (2 * s.R + 1);
+    const int *ai = s.aval.data() + (size_t)i * d, *aj = s.aval.data() + (size_t)j * d;
+    const int *bi = s.bval.data() + (size_t)i * d, *bj = s.bval.data() + (size_t)j * d;
+    long long S = 0;
+    for (int k = 0; k < d; ++k)
+        S += (long long)(ai[k] - aj[k]) * (ai[k] - aj[k]) + (long long)(bi[k] - bj[k]) * (bi[k] - bj[k]);
+    return S;
+}
+
+// the chroma weight of S_ab: (1/hc^2) / (2R + 1)^2
+double chroma_cwd(const SampleSet& s) { return (1.0 / (s.hc * s.hc)) / ((2 * s.R + 1) * (2 * s.R + 1)); }
+
+// Ka with patch affinities: S in exact integer arithmetic, the exponent in k_patch_affinity64's order (patch.hip); with
+// chroma the term cwd S_ab is subtracted last
 std::vector<double> build_Ka_patch(const SampleSet& s, double hx, double hy) {
     const int p = s.p, d = (2 * s.R + 1) * (2 * s.R + 1);
     const double sw = 1.0 / (hx * hx), pwd = (1.0 / (hy * hy)) / d;
+    const bool chroma = s.chroma();
+    const double cwd = chroma ? chroma_cwd(s) : 0.0;
     std::vector<double> Ka((size_t)p * p);
     for (int j = 0; j < p; ++j) {
         const int rj = (int)(s.pix[j] / s.gs.W), cj = (int)(s.pix[j] % s.gs.W);
@@ -180,7 +249,9 @@ std::vector<double> build_Ka_patch(const SampleSet& s, double hx, double hy) {
             long long S = 0;
             for (int k = 0; k < d; ++k) S += (long long)(yi[k] - yj[k]) * (yi[k] - yj[k]);
             const long long dr = ri - rj, dc = ci - cj;
-            const double v = std::exp(-sw * (double)(dr * dr + dc * dc) - pwd * (double)S);
+            double e = -sw * (double)(dr * dr + dc * dc) - pwd * (double)S;
+            if (chroma) e = e - cwd * (double)chroma_ssd(s, i, j);
+            const double v = std::exp(e);
             Ka[(size_t)j * p + i] = v;
             Ka[(size_t)i * p + j] = v;
         }
@@ -189,11 +260,41 @@ std::vector<double> build_Ka_patch(const SampleSet& s, double hx, double hy) {
 }
 
 // The B operand of k_patch_affinity64: the sample patches shifted by -128 as int8 (zero padded), and their norms
+// With chroma: the samples' (a, b) pairs of k_affinity64<true> (R = 0), or the second B operand of the chroma patch
+// kernel -- a patch then b patch of each sample, shifted by -128 as int8, zero padded -- and its norms (R > 0)
 struct PatchOperands {
     DevBuf<signed char> spatch;
     DevBuf<int> snorm;
+    DevBuf<float2> sab;
+    DevBuf<signed char> cpatch;
+    DevBuf<int> cnorm;
 };
+void upload_chroma_operands(nle_ctx* c, const SampleSet& s, PatchOperands* po) {
+    if (s.R <= 0) {
+        std::vector<float2> ab(s.p);
+        for (int j = 0; j < s.p; ++j) ab[j] = make_float2((float)s.aval[j], (float)s.bval[j]);
+        po->sab.alloc(s.p);
+        HIP_OK(hipMemcpyAsync(po->sab.p, ab.data(), ab.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));  // host staging vector goes out of scope
+        return;
+    }
+    const int d = (2 * s.R + 1) * (2 * s.R + 1), kp = nlek::patch_ckpad(s.R);
+    std::vector<signed char> bytes(nlek::patch_cpatch_bytes(s.p, s.R), 0);
+    std::vector<int> norm(s.p, 0);
+    for (int j = 0; j < s.p; ++j)
+        for (int k = 0; k < 2 * d; ++k) {
+            const int v = (k < d ? s.aval[(size_t)j * d + k] : s.bval[(size_t)j * d + k - d]) - 128;
+            bytes[(size_t)j * kp + k] = (signed char)v;
+            norm[j] += v * v;
+        }
+    po->cpatch.alloc(bytes.size());
+    po->cnorm.alloc(s.p);
+    HIP_OK(hipMemcpyAsync(po->cpatch.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(po->cnorm.p, norm.data(), norm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));  // host staging vectors go out of scope
+}
 void upload_patch_operands(nle_ctx* c, const SampleSet& s, PatchOperands* po) {
+    if (s.chroma()) upload_chroma_operands(c, s, po);
     if (s.R <= 0) return;
     const int d = (2 * s.R + 1) * (2 * s.R + 1), kp = nlek::patch_kpad(s.R);
     std::vector<signed char> bytes(nlek::patch_spatch_bytes(s.p, s.R), 0);
@@ -216,6 +317,15 @@ hipError_t affinity_rows64(hipStream_t st, const float* d_lum, const SampleSet& 
                            const PatchOperands& po, int ld, double hx, double hy, long long pix0, long long M, double* d_kab,
                            bool skip_samples = false, const unsigned* d_smask = nullptr) {
     const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
+    if (ss.chroma()) {
+        const double cwd = chroma_cwd(ss);
+        if (ss.R <= 0)
+            return nlek::affinity64_chroma(st, d_lum, ss.d_a, ss.d_b, ss.gs, d_samples, po.sab.p, ss.p, ld, sw, pw, cwd, pix0, M,
+                                           d_kab, skip_samples, d_smask);
+        return nlek::patch_affinity64_chroma(st, d_lum, ss.d_a, ss.d_b, ss.gs, ss.R, d_samples, po.spatch.p, po.snorm.p,
+                                             po.cpatch.p, po.cnorm.p, ss.p, ld, sw, pw / ((2 * ss.R + 1) * (2 * ss.R + 1)), cwd,
+                                             pix0, M, d_kab, skip_samples, d_smask);
+    }
     if (ss.R <= 0)
         return nlek::affinity64(st, d_lum, ss.gs, d_samples, ss.p, ld, sw, pw, pix0, M, d_kab, skip_samples, d_smask);
     const double pwd = pw / ((2 * ss.R + 1) * (2 * ss.R + 1));
@@ -228,6 +338,8 @@ std::vector<double> build_Ka(const SampleSet& s, double hx, double hy) {
     if (s.R > 0) return build_Ka_patch(s, hx, hy);
     const int p = s.p;
     const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
+    const bool chroma = s.chroma();
+    const double cw = chroma ? chroma_cwd(s) : 0.0;
     std::vector<double> Ka((size_t)p * p);
     auto column = [&](int j) {
         const int rj = (int)(s.pix[j] / s.gs.W), cj = (int)(s.pix[j] % s.gs.W);
@@ -236,7 +348,9 @@ std::vector<double> build_Ka(const SampleSet& s, double hx, double hy) {
             const long long dr = ri - rj, dc = ci - cj;
             const double sq = (double)(dr * dr + dc * dc);
             const double dv = (double)s.val[i] - (double)s.val[j];
-            const double v = std::exp(-sw * sq - pw * (dv * dv));
+            double e = -sw * sq - pw * (dv * dv);
+            if (chroma) e = e - cw * (double)chroma_ssd(s, i, j);  // subtracted last (include/nle.h)
+            const double v = std::exp(e);
             Ka[(size_t)j * p + i] = v;
             Ka[(size_t)i * p + j] = v;
         }
@@ -1143,6 +1257,7 @@ void check_exact(const nle_ctx* c, int H, int W, int n_eig) {
         throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 takes at most NLE_EXACT_MAX_PIXELS (2^20) pixels"};
     if (n_eig > 256) throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 takes at most 256 eigenvectors"};
     if (c->patch_radius > 0) throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 does not take patch affinities (radius must be 0)"};
+    if (c->chroma_a) throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 does not take chroma affinities (nle_ctx_set_chroma)"};
     if (c->sampler != NLE_SAMPLER_GRID)
         throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 takes no samples: the sampler must be NLE_SAMPLER_GRID"};
 }
@@ -1527,6 +1642,12 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) run in NLE_MODE_AUTO, NLE_MODE_MATERIALISED_F64 or "
                                     "NLE_MODE_STREAMED_F64 only"};
     check_patch_radius(c, R, H, W);
+    // chroma affinities: the same two formulations, for the same reason (a 256-level table cannot index a colour triple)
+    const bool chroma = c->chroma_a != nullptr;
+    if (chroma && c->mode != NLE_MODE_AUTO && c->mode != NLE_MODE_MATERIALISED_F64 && c->mode != NLE_MODE_STREAMED_F64)
+        throw Fail{NLE_ERR_INVALID, "chroma affinities (nle_ctx_set_chroma) run in NLE_MODE_AUTO, NLE_MODE_MATERIALISED_F64 or "
+                                    "NLE_MODE_STREAMED_F64 only"};
+    check_chroma(c, R, gs.p());
     // the farthest sampler (a listed sample set): the fp64 formulations with explicit affinity rows only (the tables need a
     // Cartesian set, the other forms are fp32); decided the same way on every rank
     const bool farthest = c->sampler == NLE_SAMPLER_FARTHEST;
@@ -1537,7 +1658,7 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
     // auto: the table form (all fp64) whenever it applies, else the literal decomposition in fp64 (generic64.hip).  The
     // fp32 formulations (materialised Phi, Phi-free with fp32 affinities) run only when asked for by mode: they miss
     // the 1e-4 bar on some well-posed inputs (DESIGN.md "Numerics").
-    const bool want_fuse = R == 0 && !farthest && (c->mode == NLE_MODE_PHI_FREE || c->mode == NLE_MODE_PHI_FREE_EXP ||
+    const bool want_fuse = R == 0 && !farthest && !chroma && (c->mode == NLE_MODE_PHI_FREE || c->mode == NLE_MODE_PHI_FREE_EXP ||
                                       (c->mode == NLE_MODE_AUTO && tables_ok));
     HIP_OK(hipSetDevice(c->device));
 
@@ -1559,11 +1680,15 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         tm_a.start();
         std::vector<long long> list;
         if (farthest) list = farthest_list(c, d_lum, gs, hx, hy);
-        SampleSet ss = fetch_samples(c, d_lum, gs, (want_fuse && tables_ok) || R > 0, c->slab_input && c->world > 1, R,
-                                     farthest ? &list : nullptr);
+        SampleSet ss = fetch_samples(c, d_lum, gs, (want_fuse && tables_ok) || R > 0 || chroma, c->slab_input && c->world > 1,
+                                     R, farthest ? &list : nullptr, chroma);
         if (R > 0 && ranks_where(c, !ss.quantised) > 0)  // refused on every rank if the plane is not integer valued on one
             throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
                                         "(the L channel of 8-bit Lab)"};
+        if (chroma && ranks_where(c, !ss.quantised || !ss.chroma_quantised) > 0)  // likewise agreed by every rank
+            throw Fail{NLE_ERR_INVALID, "chroma affinities need integer-valued L, a and b planes in [0, 255] (the channels of "
+                                        "8-bit Lab)"};
+        f->chroma_hc = chroma ? ss.hc : 0.0;
         const bool fuse = c->mode == NLE_MODE_AUTO ? (want_fuse && tables_ok && ss.quantised)
                                                    : (want_fuse && (generic_ok || (tables_ok && ss.quantised)));
         if (c->mode == NLE_MODE_PHI_FREE && !fuse)
@@ -1694,6 +1819,8 @@ int nle_compute_kernel(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         if (ctx->patch_radius > 0)
             throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) does not take patch affinities: use nle_compute_kernel64"};
+        if (ctx->chroma_a)
+            throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) does not take chroma affinities: use nle_compute_kernel64"};
         if (ctx->sampler != NLE_SAMPLER_GRID)
             throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) takes the grid sampler only: use nle_compute_kernel64"};
         HIP_OK(hipSetDevice(ctx->device));
@@ -1723,6 +1850,8 @@ int nle_nystrom(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_sample
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         if (ctx->patch_radius > 0)
             throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) does not take patch affinities: use the fp64 formulations"};
+        if (ctx->chroma_a)
+            throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) does not take chroma affinities: use the fp64 formulations"};
         if (ctx->sampler != NLE_SAMPLER_GRID)
             throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) takes the grid sampler only: use the fp64 formulations"};
         HIP_OK(hipSetDevice(ctx->device));
@@ -1803,14 +1932,20 @@ int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         const int R = ctx->patch_radius;
         check_patch_radius(ctx, R, H, W);
+        const bool chroma = ctx->chroma_a != nullptr;
+        if (chroma && !(hx > 0 && hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
+        check_chroma(ctx, R, gs.p());
         check_sampler(ctx, hx, hy);
         HIP_OK(hipSetDevice(ctx->device));
         std::vector<long long> list;
         if (ctx->sampler == NLE_SAMPLER_FARTHEST) list = farthest_list(ctx, d_lum, gs, hx, hy);
-        SampleSet ss = fetch_samples(ctx, d_lum, gs, R > 0, false, R, list.empty() ? nullptr : &list);
+        SampleSet ss = fetch_samples(ctx, d_lum, gs, R > 0 || chroma, false, R, list.empty() ? nullptr : &list, chroma);
         if (R > 0 && !ss.quantised)
             throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
                                         "(the L channel of 8-bit Lab)"};
+        if (chroma && (!ss.quantised || !ss.chroma_quantised))
+            throw Fail{NLE_ERR_INVALID, "chroma affinities need integer-valued L, a and b planes in [0, 255] (the channels of "
+                                        "8-bit Lab)"};
         if (h_Ka) {
             std::vector<double> Ka = build_Ka(ss, hx, hy);
             std::copy(Ka.begin(), Ka.end(), h_Ka);

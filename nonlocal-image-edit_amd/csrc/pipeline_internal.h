@@ -64,6 +64,11 @@ struct nle_ctx {
     bool slab_input = false;  // nle_ctx_set_slab_input: planes handed in hold this rank's rows only
     bool nystrom_bf16x3 = false;  // nle_ctx_set_nystrom_bf16x3: the fused Nystrom GEMM on the bf16 MFMA with split operands
     int patch_radius = 0;  // nle_ctx_set_patch_radius: patch (non-local-means) affinities of (2R + 1)^2 pixels (patch.hip)
+    // nle_ctx_set_chroma: the a and b planes of 8-bit Lab (borrowed device pointers, full H x W plane) and the chroma
+    // bandwidth hc; both null = off
+    const float* chroma_a = nullptr;
+    const float* chroma_b = nullptr;
+    double chroma_hc = 0.0;
     int sampler = 0;  // nle_ctx_set_sampler: NLE_SAMPLER_GRID or NLE_SAMPLER_FARTHEST (sampler.hip)
     int topk_solver = 0;  // nle_ctx_set_topk_solver: 0 full eigensolve of Q (:313-316), 1 Lanczos top-K (:170-199)
     bool profiling = false;
@@ -88,6 +93,7 @@ struct nle_filter {
     double* d_V64 = nullptr;  // fp64 formulation (generic64.hip): m_eigvecs in fp64, same leading dimension
     size_t v64_bytes = 0;
     std::vector<double> eigvals;
+    double chroma_hc = 0.0;  // the chroma bandwidth the filter was trained with (nle_ctx_set_chroma), 0 = without
     double ms[6] = {0, 0, 0, 0, 0, 0};
     // nle_filter_diag: formulation taken, eigenvalues kept by the three cuts (:214 on Ka, Wa, Q), Cholesky shortcuts
     int formulation = 0, r_wa = 0, r_q = 0, chol_ka = 0, chol_wa = 0;

@@ -4,11 +4,13 @@
 // throws, like the reference: src/enhance.cpp:20-31, src/denoise.cpp:19-31) and return 0 on the two soft failures
 // (usage, unreadable image) for drop-in compatibility.  New here: optional LEADING `--patch-radius R` (patch affinities,
 // NLEFilter::patchRadius), `--sampler grid|farthest` (NLEFilter::sampler) and the flag `--exact` (NLEFilter::exact, no
-// value; not with a non-zero radius or the farthest sampler), in any order; reference command lines never start with
+// value; not with a non-zero radius or the farthest sampler) and, for enhance only, `--chroma HC` (chroma-aware affinities,
+// NLEFilter::chromaBandwidth: a finite number > 0; not with --exact or a radius above NLE_CHROMA_PATCH_RADIUS_MAX), in any order; reference command lines never start with
 // `--`, so they parse exactly as before.  An invalid value prints a message to stderr and exits with status 2 before
 // anything touches the GPU.
 #pragma once
 
+#include <cmath>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -29,10 +31,12 @@ struct FilterArgs {
     int patchRadius = 0;        // --patch-radius R
     int sampler = NLE_SAMPLER_GRID;  // --sampler grid|farthest
     bool exact = false;              // --exact
+    double chroma = 0;               // --chroma HC (enhance only)
 };
 
 // false (after printing the usage line to stderr) when fewer than `min_argc` arguments were given
-inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a) {
+// allow_chroma: the tool takes `--chroma HC` (enhance); otherwise the option is refused (denoise estimates a and b)
+inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false) {
     std::vector<char*> shifted;
     int first = 1;  // the first argument after the leading options
     while (first < argc) {
@@ -46,9 +50,23 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a) {
             std::cerr << argv[0] << ": --exact takes no value, got '" << opt << "'" << std::endl;
             std::exit(2);
         }
-        if (opt != "--patch-radius" && opt != "--sampler") break;
+        if (opt != "--patch-radius" && opt != "--sampler" && opt != "--chroma") break;
         const std::string v = first + 1 < argc ? argv[first + 1] : "";
-        if (opt == "--patch-radius") {
+        if (opt == "--chroma") {
+            if (!allow_chroma) {
+                std::cerr << argv[0] << ": --chroma is not supported here: the a and b planes are what this tool estimates"
+                          << std::endl;
+                std::exit(2);
+            }
+            char* end = nullptr;
+            const double hc = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            if (v.empty() || *end != '\0' || !std::isfinite(hc) || !(hc > 0)) {
+                std::cerr << argv[0] << ": --chroma takes a finite number > 0 (the chroma bandwidth), got '" << v << "'"
+                          << std::endl;
+                std::exit(2);
+            }
+            a->chroma = hc;
+        } else if (opt == "--patch-radius") {
             char* end = nullptr;
             const long r = v.empty() ? -1 : std::strtol(v.c_str(), &end, 10);
             if (v.empty() || *end != '\0' || r < 0 || r > NLE_PATCH_RADIUS_MAX) {
@@ -69,6 +87,11 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a) {
     if (a->exact && (a->patchRadius != 0 || a->sampler != NLE_SAMPLER_GRID)) {
         std::cerr << argv[0] << ": --exact uses no samples and single-pixel affinities: it does not combine with "
                   << "--patch-radius R > 0 or --sampler farthest" << std::endl;
+        std::exit(2);
+    }
+    if (a->chroma != 0 && (a->exact || a->patchRadius > NLE_CHROMA_PATCH_RADIUS_MAX)) {
+        std::cerr << argv[0] << ": --chroma does not combine with --exact or with --patch-radius R > "
+                  << NLE_CHROMA_PATCH_RADIUS_MAX << std::endl;
         std::exit(2);
     }
     if (first > 1) {

@@ -8,13 +8,14 @@
 
 int main(int argc, char* argv[]) {
     nlecli::FilterArgs a;
-    if (!nlecli::parse(argc, argv, 10, &a)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
+    if (!nlecli::parse(argc, argv, 10, &a, /*allow_chroma=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
     const nle::Image image = nlecli::load(a);
     if (image.empty()) return 0;                        // src/enhance.cpp:34-37
     nle::NLEFilter filter;
     filter.patchRadius = a.patchRadius;
     filter.sampler = a.sampler;
     filter.exact = a.exact;
+    filter.chromaBandwidth = a.chroma;
     filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
     const nle::Image result = filter.enhance(image, a.extra);  // the weights are argv[9..]
     nlecli::report(filter);

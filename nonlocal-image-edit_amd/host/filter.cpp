@@ -566,7 +566,7 @@ void NLEFilter::trainFilter(const Image& channel, int nRowSamples, int nColSampl
 }
 
 void NLEFilter::trainOnDevice(const float* d_lum, int rows, int cols, int nRowSamples, int nColSamples, DType hx,
-                              DType hy, int nSinkhornIter, int nEigenVectors) {
+                              DType hy, int nSinkhornIter, int nEigenVectors, const float* d_a, const float* d_b) {
     ctx_ = shared_ctx();
     fh_.reset();
     f_ = nullptr;
@@ -581,7 +581,17 @@ void NLEFilter::trainOnDevice(const float* d_lum, int rows, int cols, int nRowSa
     check(nle_ctx_set_patch_radius(ctx_, patchRadius), ctx_);
     check(nle_ctx_set_sampler(ctx_, sampler), ctx_);
     if (exact) check(nle_ctx_set_mode(ctx_, NLE_MODE_EXACT_F64), ctx_);
+    if (d_a || d_b) {
+        const int sc = nle_ctx_set_chroma(ctx_, d_a, d_b, chromaBandwidth);
+        if (sc != NLE_OK) {  // leave the shared ctx as it was found
+            nle_ctx_set_patch_radius(ctx_, 0);
+            nle_ctx_set_sampler(ctx_, NLE_SAMPLER_GRID);
+            if (exact) nle_ctx_set_mode(ctx_, default_mode());
+            check(sc, ctx_);
+        }
+    }
     const int st = nle_train(ctx_, d_lum, rows, cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, &f_);
+    nle_ctx_set_chroma(ctx_, nullptr, nullptr, 0.0);  // the planes were borrowed for this train only
     nle_ctx_set_patch_radius(ctx_, 0);  // the shared ctx's other users (the free functions) keep the reference's affinity
     nle_ctx_set_sampler(ctx_, NLE_SAMPLER_GRID);  // and its grid
     if (exact) nle_ctx_set_mode(ctx_, default_mode());  // and its mode
@@ -618,6 +628,16 @@ void NLEFilter::trainForEnhancement(const Image& image, int nRowSamples, int nCo
     const size_t n = image.total();
     Dev d_bgr(ctx_, n * 3), d_L(ctx_, n * 4);
     check(nle_dev_upload(ctx_, d_bgr.p, image.ptr<unsigned char>(), n * 3), ctx_);
+    if (chromaBandwidth != 0) {  // the a and b planes of the same Lab image, alive for the train
+        Dev d_lab(ctx_, n * 3), d_a(ctx_, n * 4), d_b(ctx_, n * 4);
+        unsigned char* lab = static_cast<unsigned char*>(d_lab.p);
+        check(nle_bgr2lab8(ctx_, static_cast<unsigned char*>(d_bgr.p), (long long)n, lab, d_L.f()), ctx_);
+        check(nle_lab8_channel(ctx_, lab, (long long)n, 1, d_a.f()), ctx_);
+        check(nle_lab8_channel(ctx_, lab, (long long)n, 2, d_b.f()), ctx_);
+        trainOnDevice(d_L.f(), image.rows, image.cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, d_a.f(),
+                      d_b.f());
+        return;
+    }
     check(nle_bgr2lab8(ctx_, static_cast<unsigned char*>(d_bgr.p), (long long)n, nullptr, d_L.f()), ctx_);
     trainOnDevice(d_L.f(), image.rows, image.cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors);
 }
@@ -685,6 +705,9 @@ void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSam
     if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enchance RGB image.");
     if (nRowSamples > image.rows || nColSamples > image.cols)
         throw std::runtime_error("Number of samples per row and col must be <= that of image.");
+    if (chromaBandwidth != 0)
+        throw std::runtime_error("trainForDenoise does not take chroma affinities (chromaBandwidth must be 0): the a and b "
+                                 "planes are what it estimates");
     // BGR -> Lab, L, bilateral filter (8 bit), convertTo(double), trainFilter -- all on the device
     ctx_ = shared_ctx();
     const size_t n = image.total();
@@ -786,13 +809,29 @@ void NLEFilter::trainForEnhancementGroup(const Image& image, int nRowSamples, in
         int r0 = 0, r1 = 0;
         check(nle_slab_rows(H, r, G, &r0, &r1), c);
         const size_t nl = (size_t)(r1 - r0) * W;
+        const bool chroma = chromaBandwidth != 0;
         Dev d_bgr(c, nl * 3), d_L(c, nl * 4);
+        std::unique_ptr<Dev> d_lab, d_a, d_b;
+        if (chroma) {
+            d_lab.reset(new Dev(c, nl * 3));
+            d_a.reset(new Dev(c, nl * 4));
+            d_b.reset(new Dev(c, nl * 4));
+        }
+        unsigned char* lab = chroma ? static_cast<unsigned char*>(d_lab->p) : nullptr;
         check(nle_dev_upload(c, d_bgr.p, image.ptr<unsigned char>() + (size_t)r0 * W * 3, nl * 3), c);
-        check(nle_bgr2lab8(c, static_cast<unsigned char*>(d_bgr.p), (long long)nl, nullptr, d_L.f()), c);
+        check(nle_bgr2lab8(c, static_cast<unsigned char*>(d_bgr.p), (long long)nl, lab, d_L.f()), c);
         check(nle_ctx_set_patch_radius(c, patchRadius), c);  // refused by the train at world > 1 (slab input) when > 0
         check(nle_ctx_set_sampler(c, sampler), c);           // likewise when farthest
         if (exact) check(nle_ctx_set_mode(c, NLE_MODE_EXACT_F64), c);  // refused by the train at world > 1
-        const int st = nle_train(c, d_L.f(), H, W, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, &fs[r]);
+        int st = NLE_OK;
+        if (chroma) {  // this rank's slab of a and b: refused by the train at world > 1 (slab input), like a patch radius
+            check(nle_lab8_channel(c, lab, (long long)nl, 1, d_a->f()), c);
+            check(nle_lab8_channel(c, lab, (long long)nl, 2, d_b->f()), c);
+            st = nle_ctx_set_chroma(c, d_a->f(), d_b->f(), chromaBandwidth);
+        }
+        if (st == NLE_OK)
+            st = nle_train(c, d_L.f(), H, W, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, &fs[r]);
+        if (chroma) nle_ctx_set_chroma(c, nullptr, nullptr, 0.0);
         if (exact) nle_ctx_set_mode(c, default_mode());
         check(st, c);
     });
