@@ -113,32 +113,44 @@ __global__ __launch_bounds__(256) void k_affinity64(const float* __restrict__ lu
     }
 }
 
-hipError_t affinity64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, int ld, double sw,
-                      double pw, long long pix0, long long M, double* d_kab, bool skip_samples, const unsigned* d_smask) {
-    if (M <= 0) return hipSuccess;
-    if (ld & 1) return hipErrorInvalidValue;   // rows are written two doubles at a time (ld = nle_ld(p) is a multiple of 4)
+size_t affinity64_chroma_lds_bytes(int ld) { return (size_t)ld * (sizeof(int2) + sizeof(double) + sizeof(float2)); }
+
+namespace {
+hipError_t launch_affinity64(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
+                             bool skip_samples) {
+    if (a.ld & 1) return hipErrorInvalidValue;   // rows are written two doubles at a time (ld = nle_ld(p) is a multiple of 4)
     const long long ngroups = (M + kAff64Pix - 1) / kAff64Pix;
     const int grid = (int)std::min<long long>(ngroups, 16384);
-    hipLaunchKernelGGL(k_affinity64<false>, dim3((unsigned)grid), dim3(256), (size_t)ld * (sizeof(int2) + sizeof(double)), s,
-                       d_lum, gs, d_samples, p, ld, sw, pw, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask, nullptr, nullptr,
-                       nullptr, 0.0);
+    hipLaunchKernelGGL(k_affinity64<false>, dim3((unsigned)grid), dim3(256), (size_t)a.ld * (sizeof(int2) + sizeof(double)), s,
+                       a.lum, a.gs, a.samples, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, nullptr,
+                       nullptr, nullptr, 0.0);
     return hipGetLastError();
 }
 
-size_t affinity64_chroma_lds_bytes(int ld) { return (size_t)ld * (sizeof(int2) + sizeof(double) + sizeof(float2)); }
-
-hipError_t affinity64_chroma(hipStream_t s, const float* d_lum, const float* d_a, const float* d_b, GridSpec gs,
-                             const Sample4* d_samples, const float2* d_sab, int p, int ld, double sw, double pw, double cw,
-                             long long pix0, long long M, double* d_kab, bool skip_samples, const unsigned* d_smask) {
-    if (M <= 0) return hipSuccess;
+hipError_t launch_affinity64_chroma(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
+                                    bool skip_samples) {
     // the launch takes the default dynamic-LDS allowance (the caller refuses a larger sample set with a message)
-    if ((ld & 1) || ld < p || !d_a || !d_b || !d_sab || affinity64_chroma_lds_bytes(ld) > kDynLdsDefault)
+    if ((a.ld & 1) || a.ld < a.p || !a.a || !a.b || !a.sab || affinity64_chroma_lds_bytes(a.ld) > kDynLdsDefault)
         return hipErrorInvalidValue;
     const long long ngroups = (M + kAff64Pix - 1) / kAff64Pix;
     const int grid = (int)std::min<long long>(ngroups, 16384);
-    hipLaunchKernelGGL(k_affinity64<true>, dim3((unsigned)grid), dim3(256), affinity64_chroma_lds_bytes(ld), s, d_lum, gs,
-                       d_samples, p, ld, sw, pw, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask, d_a, d_b, d_sab, cw);
+    hipLaunchKernelGGL(k_affinity64<true>, dim3((unsigned)grid), dim3(256), affinity64_chroma_lds_bytes(a.ld), s, a.lum, a.gs,
+                       a.samples, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, a.a, a.b, a.sab, a.cw);
     return hipGetLastError();
+}
+}  // namespace
+
+// the R > 0 half of the launcher below, next to its kernels in patch.hip; declared here and not in kernels.h: nothing else
+// calls it
+hipError_t patch_affinity_rows64(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
+                                 bool skip_samples);
+// the one launcher of the fp64 affinity rows: R > 0 goes to patch.hip, chroma (both planes given) to the CHROMA forms
+hipError_t affinity_rows64(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
+                           bool skip_samples) {
+    if (M <= 0) return hipSuccess;
+    if (a.R > 0) return patch_affinity_rows64(s, a, pix0, M, d_kab, skip_samples);
+    return a.a ? launch_affinity64_chroma(s, a, pix0, M, d_kab, skip_samples)
+               : launch_affinity64(s, a, pix0, M, d_kab, skip_samples);
 }
 
 // y[i] += x[i]

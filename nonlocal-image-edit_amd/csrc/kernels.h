@@ -1,4 +1,4 @@
-// Launch wrappers of the gfx950 kernels (kernels.hip).  Internal to libnle_hip.so.
+// Launch wrappers of the gfx950 kernels (kernels.hip and, by section, the other device files).  Internal to libnle_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -145,46 +145,46 @@ hipError_t hist_tables(hipStream_t s, GridSpec gs, const Sample4* d_samples, int
                        int nrows_local, double* d_er, double* d_ecT, double* d_Ep);
 
 // ---- the literal decomposition in fp64 (generic64.hip): auto mode's fallback and the stage-level API
-// d_smask (optional): with skip_samples, the rows zeroed are those of the pixels whose bit is set (ceil(N / 32) words, bit
-// i % 32 of word i / 32 = pixel i) instead of the grid's
-hipError_t affinity64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, int ld, double sw,
-                      double pw, long long pix0, long long M, double* d_kab, bool skip_samples = false,
-                      const unsigned* d_smask = nullptr);
-// chroma-aware rows at patch radius 0 (nle_ctx_set_chroma): exp((-sw d2 - pw dL^2) - cw (da^2 + db^2)), every operation rounded
-// on its own.  d_a, d_b: the full a and b planes (integer valued in [0, 255]); d_sab[j] = sample j's (a, b).  The samples'
-// tables take affinity64_chroma_lds_bytes(ld) of dynamic LDS, at most kDynLdsDefault (what a launch gets without opting in
-// to more): a larger ld is hipErrorInvalidValue, and the caller refuses it with a message first.
+// What a launch of the fp64 affinity-row kernels takes (filled once per sample set: samples.hip, AffinityRows64).  Rows of
+// ld columns, kab[i][j] = exp((-sw d2 - pw I_ij) - cw S_ab), every operation rounded on its own, with
+//   R = 0 (k_affinity64, generic64.hip): I = dL^2, pw = 1/hy^2; chroma: S_ab = da^2 + db^2, sab[j] = sample j's (a, b), the
+//     tables in affinity64_chroma_lds_bytes(ld) of LDS, at most kDynLdsDefault (what a launch gets without opting in to more);
+//   1 <= R <= 7 (k_patch_affinity64, patch.hip): I = S_ij, the integer sum of squared differences of the (2R + 1)^2 patches
+//     (reflect-101 borders, plane integer valued in [0, 255]), pw = (1/hy^2) / (2R + 1)^2.  spatch: patch_spatch_bytes(p, R)
+//     bytes, sample j's patch values - 128 as int8 in row j (patch_kpad(R) bytes, zero padded; rows p .. roundup16(p) zero);
+//     snorm[j] = the sum of the squares of those int8 values.  Chroma (R <= 3): S_ab likewise of the a and of the b patches,
+//     cw = (1/hc^2) / (2R + 1)^2, a second i32 accumulation on the same MFMA; cpatch: patch_cpatch_bytes(p, R) bytes, row j
+//     = sample j's a patch then its b patch, padded to patch_ckpad(R) bytes, cnorm as snorm; the tables take
+//     patch_affinity64_chroma_lds_bytes(ld) of LDS, at most kPatchChromaLdsMax.
+// A sample set that does not fit the LDS bound is hipErrorInvalidValue: the caller refuses it with a message first.
+struct Affinity64Args {
+    const float* lum = nullptr;  // the full H x W plane
+    GridSpec gs{};
+    const Sample4* samples = nullptr;
+    int p = 0, ld = 0;
+    double sw = 0.0, pw = 0.0;
+    int R = 0;
+    const signed char *spatch = nullptr, *cpatch = nullptr;  // R > 0; cpatch: with chroma
+    const int *snorm = nullptr, *cnorm = nullptr;
+    const float *a = nullptr, *b = nullptr;  // chroma (both set): the full a and b planes, integer valued in [0, 255]
+    double cw = 0.0;
+    const float2* sab = nullptr;  // chroma, R = 0
+    // optional, with skip_samples: the rows zeroed are the pixels whose bit is set (bit i % 32 of word i / 32), not the grid's
+    const unsigned* smask = nullptr;
+};
 constexpr size_t kDynLdsDefault = 64 * 1024;
+constexpr size_t kPatchChromaLdsMax = 128 * 1024;  // dynamic LDS the chroma patch kernel may ask for (160 KiB per CU)
 size_t affinity64_chroma_lds_bytes(int ld);
-hipError_t affinity64_chroma(hipStream_t s, const float* d_lum, const float* d_a, const float* d_b, GridSpec gs,
-                             const Sample4* d_samples, const float2* d_sab, int p, int ld, double sw, double pw, double cw,
-                             long long pix0, long long M, double* d_kab, bool skip_samples = false,
-                             const unsigned* d_smask = nullptr);
-// patch (non-local-means) affinity rows, patch.hip: the rows affinity64 fills, with the intensity term pwd * S_ij, S_ij the
-// integer sum of squared differences of the (2R + 1)^2 patches (reflect-101 borders), 1 <= R <= 7, plane integer in [0, 255].
-// d_spatch: patch_spatch_bytes(p, R) bytes, sample j's patch values - 128 as int8 in row j (patch_kpad(R) bytes, zero
-// padded; rows p .. roundup16(p) zero); d_snorm[j] = sum of the squares of those int8 values.
+size_t patch_affinity64_chroma_lds_bytes(int ld);
 int patch_kpad(int R);
+int patch_ckpad(int R);
 size_t patch_spatch_bytes(int p, int R);
+size_t patch_cpatch_bytes(int p, int R);
+// rows [pix0, pix0 + M) into d_kab; skip_samples: the rows of the sample pixels themselves come out as zeros
+hipError_t affinity_rows64(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
+                           bool skip_samples);
 // d_out (n x (2R + 1)^2 ints): the patch values around pixels d_pix[0 .. n) of the full plane
 hipError_t patch_gather(hipStream_t s, const float* d_lum, int H, int W, int R, const long long* d_pix, int n, int* d_out);
-hipError_t patch_affinity64(hipStream_t s, const float* d_lum, GridSpec gs, int R, const Sample4* d_samples,
-                            const signed char* d_spatch, const int* d_snorm, int p, int ld, double sw, double pwd,
-                            long long pix0, long long M, double* d_kab, bool skip_samples = false,
-                            const unsigned* d_smask = nullptr);
-// the same rows with the chroma term (nle_ctx_set_chroma), 1 <= R <= 3: exp((-sw d2 - pwd S_L) - cwd S_ab), S_ab the integer
-// sum of squared differences of the a and of the b patches, a second i32 accumulation on the same MFMA.  d_cpatch:
-// patch_cpatch_bytes(p, R) bytes, row j = sample j's a patch then its b patch, each value - 128 as int8, zero padded to
-// patch_ckpad(R) bytes (rows p .. roundup16(p) zero); d_cnorm[j] = sum of the squares of those int8 values.
-int patch_ckpad(int R);
-size_t patch_cpatch_bytes(int p, int R);
-constexpr size_t kPatchChromaLdsMax = 128 * 1024;  // dynamic LDS the chroma patch kernel may ask for (160 KiB per CU)
-size_t patch_affinity64_chroma_lds_bytes(int ld);
-hipError_t patch_affinity64_chroma(hipStream_t s, const float* d_lum, const float* d_a, const float* d_b, GridSpec gs, int R,
-                                   const Sample4* d_samples, const signed char* d_spatch, const int* d_snorm,
-                                   const signed char* d_cpatch, const int* d_cnorm, int p, int ld, double sw, double pwd,
-                                   double cwd, long long pix0, long long M, double* d_kab, bool skip_samples = false,
-                                   const unsigned* d_smask = nullptr);
 // farthest-point sample selection (sampler.hip): the p pixels of NLE_SAMPLER_FARTHEST in the order chosen, into d_list (p
 // ints), for the full H x W plane d_lum.  Workspace: d_m (H W doubles), d_pv / d_pi (2 farthest_max_blocks() each).
 int farthest_max_blocks();

@@ -269,30 +269,6 @@ __global__ __launch_bounds__(256, KC > 0 ? 4 : 1) void k_patch_affinity64(const 
 
 size_t patch_spatch_bytes(int p, int R) { return (size_t)((p + 15) & ~15) * patch_kpad(R); }
 
-hipError_t patch_affinity64(hipStream_t s, const float* d_lum, GridSpec gs, int R, const Sample4* d_samples,
-                            const signed char* d_spatch, const int* d_snorm, int p, int ld, double sw, double pwd,
-                            long long pix0, long long M, double* d_kab, bool skip_samples, const unsigned* d_smask) {
-    if (M <= 0) return hipSuccess;
-    if ((ld & 1) || R < 1 || R > 7 || ld < p) return hipErrorInvalidValue;
-    const long long ngroups = (M + kPatchPix - 1) / kPatchPix;
-    const int grid = (int)std::min<long long>(ngroups, 8192);
-    const size_t lds = (size_t)ld * (sizeof(int2) + sizeof(int)) + kPatchPix * sizeof(int) +
-                       (size_t)kPatchPix * kPatchDotLd * sizeof(int);
-    const int ks = patch_kpad(R) / 64;
-#define NLE_PATCH_LAUNCH(KS_)                                                                                               \
-    hipLaunchKernelGGL((k_patch_affinity64<KS_, 0>), dim3((unsigned)grid), dim3(256), lds, s, d_lum, gs, R, d_samples,       \
-                       d_spatch, d_snorm, p, ld, sw, pwd, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask, nullptr, nullptr,  \
-                       nullptr, nullptr, 0.0)
-    switch (ks) {
-        case 1: NLE_PATCH_LAUNCH(1); break;
-        case 2: NLE_PATCH_LAUNCH(2); break;
-        case 3: NLE_PATCH_LAUNCH(3); break;
-        default: NLE_PATCH_LAUNCH(4); break;
-    }
-#undef NLE_PATCH_LAUNCH
-    return hipGetLastError();
-}
-
 int patch_ckpad(int R) {
     const int d2 = 2 * (2 * R + 1) * (2 * R + 1);
     return (d2 + 63) & ~63;
@@ -305,16 +281,35 @@ size_t patch_affinity64_chroma_lds_bytes(int ld) {
            2 * (size_t)kPatchPix * (kPatchChromaCols + 4) * sizeof(int);
 }
 
-hipError_t patch_affinity64_chroma(hipStream_t s, const float* d_lum, const float* d_a, const float* d_b, GridSpec gs, int R,
-                                   const Sample4* d_samples, const signed char* d_spatch, const int* d_snorm,
-                                   const signed char* d_cpatch, const int* d_cnorm, int p, int ld, double sw, double pwd,
-                                   double cwd, long long pix0, long long M, double* d_kab, bool skip_samples,
-                                   const unsigned* d_smask) {
-    if (M <= 0) return hipSuccess;
+namespace {
+hipError_t launch_patch_affinity64(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
+                                   bool skip_samples) {
+    if ((a.ld & 1) || a.R < 1 || a.R > 7 || a.ld < a.p) return hipErrorInvalidValue;
+    const long long ngroups = (M + kPatchPix - 1) / kPatchPix;
+    const int grid = (int)std::min<long long>(ngroups, 8192);
+    const size_t lds = (size_t)a.ld * (sizeof(int2) + sizeof(int)) + kPatchPix * sizeof(int) +
+                       (size_t)kPatchPix * kPatchDotLd * sizeof(int);
+    const int ks = patch_kpad(a.R) / 64;
+#define NLE_PATCH_LAUNCH(KS_)                                                                                               \
+    hipLaunchKernelGGL((k_patch_affinity64<KS_, 0>), dim3((unsigned)grid), dim3(256), lds, s, a.lum, a.gs, a.R, a.samples,   \
+                       a.spatch, a.snorm, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, nullptr,    \
+                       nullptr, nullptr, nullptr, 0.0)
+    switch (ks) {
+        case 1: NLE_PATCH_LAUNCH(1); break;
+        case 2: NLE_PATCH_LAUNCH(2); break;
+        case 3: NLE_PATCH_LAUNCH(3); break;
+        default: NLE_PATCH_LAUNCH(4); break;
+    }
+#undef NLE_PATCH_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_patch_affinity64_chroma(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
+                                          bool skip_samples) {
     // R <= 3: one K step for L; one (R = 1) or two (R = 2, 3) for the concatenated a and b patches
-    if ((ld & 1) || R < 1 || R > 3 || ld < p || !d_a || !d_b || !d_cpatch || !d_cnorm) return hipErrorInvalidValue;
+    if ((a.ld & 1) || a.R < 1 || a.R > 3 || a.ld < a.p || !a.a || !a.b || !a.cpatch || !a.cnorm) return hipErrorInvalidValue;
     // 34.5 KiB of tiles + 16 bytes per sample: past 1888 samples the launch asks for more than the default allowance
-    const size_t lds = patch_affinity64_chroma_lds_bytes(ld);
+    const size_t lds = patch_affinity64_chroma_lds_bytes(a.ld);
     if (lds > kPatchChromaLdsMax) return hipErrorInvalidValue;  // (the caller refuses such a sample set with a message)
     const long long ngroups = (M + kPatchPix - 1) / kPatchPix;
     const int grid = (int)std::min<long long>(ngroups, 8192);
@@ -325,16 +320,23 @@ hipError_t patch_affinity64_chroma(hipStream_t s, const float* d_lum, const floa
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_patch_affinity64<1, KC_>),                              \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
         if (e != hipSuccess) return e;                                                                                      \
-        hipLaunchKernelGGL((k_patch_affinity64<1, KC_>), dim3((unsigned)grid), dim3(256), lds, s, d_lum, gs, R, d_samples,  \
-                           d_spatch, d_snorm, p, ld, sw, pwd, pix0, M, d_kab, skip_samples ? 1 : 0, d_smask, d_a, d_b,      \
-                           d_cpatch, d_cnorm, cwd);                                                                         \
+        hipLaunchKernelGGL((k_patch_affinity64<1, KC_>), dim3((unsigned)grid), dim3(256), lds, s, a.lum, a.gs, a.R, a.samples, \
+                           a.spatch, a.snorm, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, a.a, a.b, \
+                           a.cpatch, a.cnorm, a.cw);                                                                        \
     } while (0)
-    if (patch_ckpad(R) == 64)
+    if (patch_ckpad(a.R) == 64)
         NLE_PATCH_LAUNCH(1);
     else
         NLE_PATCH_LAUNCH(2);
 #undef NLE_PATCH_LAUNCH
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t patch_affinity_rows64(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
+                                 bool skip_samples) {
+    return a.a ? launch_patch_affinity64_chroma(s, a, pix0, M, d_kab, skip_samples)
+               : launch_patch_affinity64(s, a, pix0, M, d_kab, skip_samples);
 }
 
 }  // namespace nlek

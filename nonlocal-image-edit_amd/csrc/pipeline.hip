@@ -1,138 +1,14 @@
-// Host orchestration of the hot path behind the C ABI (include/nle.h): context, the
-// fused train pipeline (NLEFilter::trainFilter, reference src/filter.cpp:480-502) and
-// apply (:445-458).  Small (p x p, r x r) algebra and the three symmetric eigensolves run
-// on the host in fp64; everything N-sized is a HIP kernel (kernels.hip).
+// Host orchestration of the hot path behind the C ABI (include/nle.h): the Nystrom solve, the train paths
+// (NLEFilter::trainFilter, reference src/filter.cpp:480-502), apply (:445-458) and the bodies of the stage entry points.
+// Small (p x p, r x r) algebra and the three symmetric eigensolves run on the host in fp64; everything N-sized is a HIP
+// kernel.  The sample set, Ka and the fp64 affinity rows -- the patch, chroma and sampler options -- are samples.hip's.
 #include "ortho.h"
+#include "samples.h"
 
 using nlek::GridSpec;
 using namespace nlep;
 
 namespace {
-// ---- sample set + Ka (host) ----
-struct SampleSet {
-    GridSpec gs;
-    int p = 0;
-    std::vector<long long> pix;     // row-major pixel index of each sample (permuted order)
-    std::vector<float> val;         // luminance
-    std::vector<float4> packed;     // {row, col, lum, 0}
-    bool quantised = false;         // whole plane integer valued in [0, 255] (checked on request)
-    unsigned level_tiles = 0xffffu; // then: which 16-level tiles occur in this rank's part of the plane (bit t)
-    int R = 0;                      // patch radius (nle_ctx_set_patch_radius)
-    bool listed = false;            // pix is a sampler's list (NLE_SAMPLER_FARTHEST), not the grid's closed form
-    std::vector<int> patch;         // R > 0: p x (2R + 1)^2 patch values around each sample (reflect-101), row per sample
-    // chroma (nle_ctx_set_chroma): the full a and b planes on the device, hc, and the samples' a and b values (R = 0:
-    // p each) or patches (R > 0: p x (2R + 1)^2 each, as `patch`)
-    const float* d_a = nullptr;
-    const float* d_b = nullptr;
-    double hc = 0.0;
-    bool chroma_quantised = false;  // both planes integer valued in [0, 255]
-    std::vector<int> aval, bval;
-    bool chroma() const { return d_a != nullptr; }
-};
-
-// d_lum: base of the FULL plane -- real, or virtual when the ctx takes slab input (only rows [row0, row1) of this rank
-// exist; the p sample values and the "integer valued" verdict are then completed by an all-reduce).  R > 0: also the
-// samples' patches (full plane only: the caller refuses slab input).  list: the sample pixels of NLE_SAMPLER_FARTHEST
-// (ascending, gs.p() of them; full plane only) instead of the grid's.  chroma: also the level check of the ctx's a and b
-// planes and the samples' a and b values or patches (full plane only: the caller refuses slab input)
-SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, bool check_quantised = false,
-                        bool slab_plane = false, int R = 0, const std::vector<long long>* list = nullptr,
-                        bool chroma = false) {
-    SampleSet s;
-    s.gs = gs;
-    s.p = gs.p();
-    if (list && ((int)list->size() != s.p || slab_plane)) throw Fail{NLE_ERR_INVALID, "fetch_samples: bad sample list"};
-    s.val.resize(s.p);
-    int flag = 1;
-    int fl2[2] = {1, 0xffff};  // check_levels: [0] verdict, [1] level tiles
-    if (slab_plane) {
-        int row0, row1;
-        slab(gs.H, c->rank, c->world, &row0, &row1);
-        DevBuf<double> d_v((size_t)s.p + 1);
-        PROFILED(c, NLE_K_SMALL, nlek::gather_samples_slab(c->stream, d_lum, gs, row0, row1, d_v.p));
-        if (check_quantised) {
-            DevBuf<int> d_flag(2);
-            PROFILED(c, NLE_K_SMALL, nlek::check_levels(c->stream, d_lum + (size_t)row0 * gs.W, (long long)(row1 - row0) * gs.W, d_flag.p));
-            HIP_OK(hipMemcpyAsync(fl2, d_flag.p, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipStreamSynchronize(c->stream));
-            flag = fl2[0];
-        }
-        const double fl = flag != 0 ? 1.0 : 0.0;
-        HIP_OK(hipMemcpyAsync(d_v.p + s.p, &fl, sizeof(double), hipMemcpyHostToDevice, c->stream));
-        all_reduce(c, d_v.p, (size_t)s.p + 1);
-        std::vector<double> v((size_t)s.p + 1);
-        HIP_OK(hipMemcpyAsync(v.data(), d_v.p, v.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        for (int k = 0; k < s.p; ++k) s.val[k] = (float)v[k];
-        flag = v[s.p] > 0.0 ? 1 : 0;
-    } else {
-        DevBuf<float> d_val(s.p);
-        DevBuf<int> d_flag(2);
-        DevBuf<long long> d_pix;
-        if (list) {
-            d_pix.alloc(s.p);
-            HIP_OK(hipMemcpyAsync(d_pix.p, list->data(), s.p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-            PROFILED(c, NLE_K_SMALL, nlek::gather_pix(c->stream, d_lum, d_pix.p, s.p, d_val.p));
-        } else {
-            PROFILED(c, NLE_K_SMALL, nlek::gather_samples(c->stream, d_lum, gs, d_val.p));
-        }
-        if (check_quantised) {
-            PROFILED(c, NLE_K_SMALL, nlek::check_levels(c->stream, d_lum, (long long)gs.H * gs.W, d_flag.p));
-            HIP_OK(hipMemcpyAsync(fl2, d_flag.p, 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        }
-        HIP_OK(hipMemcpyAsync(s.val.data(), d_val.p, s.p * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        if (check_quantised) flag = fl2[0];
-    }
-    s.quantised = check_quantised && flag == 0;
-    if (s.quantised && (fl2[1] & 0xffff) != 0) s.level_tiles = (unsigned)fl2[1] & 0xffffu;
-    s.pix.resize(s.p);
-    s.packed.resize(s.p);
-    s.listed = list != nullptr;
-    for (int k = 0; k < s.p; ++k) {
-        const int r = list ? (int)((*list)[k] / gs.W) : gs.rowOff + (k / gs.nSelCols) * gs.rowStep;
-        const int cc = list ? (int)((*list)[k] - (long long)r * gs.W) : gs.colOff + (k % gs.nSelCols) * gs.colStep;
-        s.pix[k] = (long long)r * gs.W + cc;
-        s.packed[k] = make_float4((float)r, (float)cc, s.val[k], 0.f);
-    }
-    if (R > 0) {
-        const int d = (2 * R + 1) * (2 * R + 1);
-        s.R = R;
-        s.patch.resize((size_t)s.p * d);
-        DevBuf<long long> d_pix(s.p);
-        DevBuf<int> d_patch(s.patch.size());
-        HIP_OK(hipMemcpyAsync(d_pix.p, s.pix.data(), s.p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-        PROFILED(c, NLE_K_SMALL, nlek::patch_gather(c->stream, d_lum, gs.H, gs.W, R, d_pix.p, s.p, d_patch.p));
-        HIP_OK(hipMemcpyAsync(s.patch.data(), d_patch.p, s.patch.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    if (chroma) {
-        if (slab_plane || !c->chroma_a || !c->chroma_b) throw Fail{NLE_ERR_INVALID, "fetch_samples: no chroma planes"};
-        s.R = R;
-        s.d_a = c->chroma_a;
-        s.d_b = c->chroma_b;
-        s.hc = c->chroma_hc;
-        const int d = (2 * R + 1) * (2 * R + 1);  // R = 0: the one-value patch is the pixel itself
-        const size_t n = (size_t)s.p * d;
-        s.aval.resize(n);
-        s.bval.resize(n);
-        DevBuf<long long> d_pix(s.p);
-        DevBuf<int> d_ab(2 * n), d_flag(4);
-        int fl4[4] = {1, 0, 1, 0};
-        HIP_OK(hipMemcpyAsync(d_pix.p, s.pix.data(), s.p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-        PROFILED(c, NLE_K_SMALL, nlek::patch_gather(c->stream, s.d_a, gs.H, gs.W, R, d_pix.p, s.p, d_ab.p));
-        PROFILED(c, NLE_K_SMALL, nlek::patch_gather(c->stream, s.d_b, gs.H, gs.W, R, d_pix.p, s.p, d_ab.p + n));
-        PROFILED(c, NLE_K_SMALL, nlek::check_levels(c->stream, s.d_a, (long long)gs.H * gs.W, d_flag.p));
-        PROFILED(c, NLE_K_SMALL, nlek::check_levels(c->stream, s.d_b, (long long)gs.H * gs.W, d_flag.p + 2));
-        HIP_OK(hipMemcpyAsync(s.aval.data(), d_ab.p, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(s.bval.data(), d_ab.p + n, n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipMemcpyAsync(fl4, d_flag.p, 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        s.chroma_quantised = fl4[0] == 0 && fl4[2] == 0;
-    }
-    return s;
-}
-
 // The image and sample-grid checks of every entry point that takes a plane and sample counts
 GridSpec checked_grid(int H, int W, int nRow, int nCol) {
     check_image_size(H, W);
@@ -141,230 +17,6 @@ GridSpec checked_grid(int H, int W, int nRow, int nCol) {
     GridSpec gs;
     if (!make_grid(H, W, nRow, nCol, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
     return gs;
-}
-
-// The checks of a patch radius R > 0 that need no device (nle_ctx_set_patch_radius has checked 0 <= R <= 7)
-void check_patch_radius(const nle_ctx* c, int R, int H, int W) {
-    if (R <= 0) return;
-    if (R > std::min(H, W) - 1)
-        throw Fail{NLE_ERR_INVALID, "patch radius " + std::to_string(R) + " needs an image of at least " + std::to_string(R + 1) +
-                                        " x " + std::to_string(R + 1) + " pixels (R <= min(H, W) - 1)"};
-    if (c->slab_input && c->world > 1)
-        throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need the full plane on every rank: slab input is not "
-                                    "supported with them"};
-}
-
-// The checks of chroma affinities (nle_ctx_set_chroma) that need no device; the ctx's mode is checked where it applies
-void check_chroma(const nle_ctx* c, int R, int p) {
-    if (!c->chroma_a) return;
-    if (R > NLE_CHROMA_PATCH_RADIUS_MAX)
-        throw Fail{NLE_ERR_INVALID, "chroma affinities take a patch radius of at most " +
-                                        std::to_string(NLE_CHROMA_PATCH_RADIUS_MAX) + ", got " + std::to_string(R)};
-    if (c->slab_input && c->world > 1)
-        throw Fail{NLE_ERR_INVALID, "chroma affinities need the full plane on every rank: slab input is not supported with "
-                                    "them"};
-    // the samples' tables of the affinity kernels live in LDS
-    const int ld = ld4(p);
-    const bool fits = R > 0 ? nlek::patch_affinity64_chroma_lds_bytes(ld) <= nlek::kPatchChromaLdsMax
-                            : nlek::affinity64_chroma_lds_bytes(ld) <= nlek::kDynLdsDefault;
-    if (!fits)
-        throw Fail{NLE_ERR_INVALID, "chroma affinities: " + std::to_string(p) + " samples do not fit the affinity kernel's "
-                                    "LDS tables (at most 2728 at patch radius 0, 5984 above)"};
-}
-
-// The checks of the farthest sampler that need no device; the ctx's mode is checked where it applies (nle_train*)
-void check_sampler(const nle_ctx* c, double hx, double hy) {
-    if (c->sampler != NLE_SAMPLER_FARTHEST) return;
-    if (!(hx > 0) || !(hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
-    if (c->slab_input && c->world > 1)
-        throw Fail{NLE_ERR_INVALID, "the farthest sampler needs the full plane on every rank: slab input is not supported "
-                                    "with it"};
-}
-
-// The sample pixels of NLE_SAMPLER_FARTHEST on the full plane d_lum (sampler.hip), ascending.  At world > 1 rank 0 selects
-// and the others receive the set through the fp64 all-reduce (they add zeros; indices < 2^31 are exact in fp64); the last
-// slot carries rank 0's failure, so that every rank returns the same verdict.
-std::vector<long long> farthest_list(nle_ctx* c, const float* d_lum, const GridSpec& gs, double hx, double hy) {
-    const int p = gs.p();
-    const long long N = (long long)gs.H * gs.W;
-    std::vector<long long> list(p);
-    std::vector<double> v((size_t)p + 1, 0.0);
-    if (c->rank == 0 || c->world <= 1) {
-        try {
-            const int nb = nlek::farthest_max_blocks();
-            DevBuf<double> d_m((size_t)N), d_pv((size_t)2 * nb);
-            DevBuf<int> d_pi((size_t)2 * nb), d_list(p);
-            std::vector<int> idx(p);
-            PROFILED(c, NLE_K_SMALL, nlek::farthest_samples(c->stream, d_lum, gs.H, gs.W, p, 1.0 / (hx * hx), 1.0 / (hy * hy),
-                                                            d_m.p, d_pv.p, d_pi.p, d_list.p));
-            HIP_OK(hipMemcpyAsync(idx.data(), d_list.p, p * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipStreamSynchronize(c->stream));
-            for (int k = 0; k < p; ++k) v[k] = (double)idx[k];
-        } catch (const Fail&) {
-            if (c->world <= 1) throw;
-            v[p] = 1.0;
-        }
-    }
-    if (c->world > 1) {
-        DevBuf<double> d_v((size_t)p + 1);
-        HIP_OK(hipMemcpyAsync(d_v.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        all_reduce(c, d_v.p, (size_t)p + 1);
-        HIP_OK(hipMemcpyAsync(v.data(), d_v.p, v.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));
-        if (v[p] != 0.0) throw Fail{NLE_ERR_HIP, "the farthest sampler failed on rank 0"};
-    }
-    for (int k = 0; k < p; ++k) list[k] = (long long)v[k];
-    std::sort(list.begin(), list.end());
-    return list;
-}
-
-// S_ab of samples i and j: the integer sum of squared differences of their a and of their b values (R = 0) or patches
-long long chroma_ssd(const SampleSet& s, int i, int j) {
-    const int d = (2 * s.R + 1) * (2 * s.R + 1);
-    const int *ai = s.aval.data() + (size_t)i * d, *aj = s.aval.data() + (size_t)j * d;
-    const int *bi = s.bval.data() + (size_t)i * d, *bj = s.bval.data() + (size_t)j * d;
-    long long S = 0;
-    for (int k = 0; k < d; ++k)
-        S += (long long)(ai[k] - aj[k]) * (ai[k] - aj[k]) + (long long)(bi[k] - bj[k]) * (bi[k] - bj[k]);
-    return S;
-}
-
-// the chroma weight of S_ab: (1/hc^2) / (2R + 1)^2
-double chroma_cwd(const SampleSet& s) { return (1.0 / (s.hc * s.hc)) / ((2 * s.R + 1) * (2 * s.R + 1)); }
-
-// Ka with patch affinities: S in exact integer arithmetic, the exponent in k_patch_affinity64's order (patch.hip); with
-// chroma the term cwd S_ab is subtracted last
-std::vector<double> build_Ka_patch(const SampleSet& s, double hx, double hy) {
-    const int p = s.p, d = (2 * s.R + 1) * (2 * s.R + 1);
-    const double sw = 1.0 / (hx * hx), pwd = (1.0 / (hy * hy)) / d;
-    const bool chroma = s.chroma();
-    const double cwd = chroma ? chroma_cwd(s) : 0.0;
-    std::vector<double> Ka((size_t)p * p);
-    for (int j = 0; j < p; ++j) {
-        const int rj = (int)(s.pix[j] / s.gs.W), cj = (int)(s.pix[j] % s.gs.W);
-        const int* yj = s.patch.data() + (size_t)j * d;
-        for (int i = j; i < p; ++i) {
-            const int ri = (int)(s.pix[i] / s.gs.W), ci = (int)(s.pix[i] % s.gs.W);
-            const int* yi = s.patch.data() + (size_t)i * d;
-            long long S = 0;
-            for (int k = 0; k < d; ++k) S += (long long)(yi[k] - yj[k]) * (yi[k] - yj[k]);
-            const long long dr = ri - rj, dc = ci - cj;
-            double e = -sw * (double)(dr * dr + dc * dc) - pwd * (double)S;
-            if (chroma) e = e - cwd * (double)chroma_ssd(s, i, j);
-            const double v = std::exp(e);
-            Ka[(size_t)j * p + i] = v;
-            Ka[(size_t)i * p + j] = v;
-        }
-    }
-    return Ka;
-}
-
-// The B operand of k_patch_affinity64: the sample patches shifted by -128 as int8 (zero padded), and their norms
-// With chroma: the samples' (a, b) pairs of k_affinity64<true> (R = 0), or the second B operand of the chroma patch
-// kernel -- a patch then b patch of each sample, shifted by -128 as int8, zero padded -- and its norms (R > 0)
-struct PatchOperands {
-    DevBuf<signed char> spatch;
-    DevBuf<int> snorm;
-    DevBuf<float2> sab;
-    DevBuf<signed char> cpatch;
-    DevBuf<int> cnorm;
-};
-void upload_chroma_operands(nle_ctx* c, const SampleSet& s, PatchOperands* po) {
-    if (s.R <= 0) {
-        std::vector<float2> ab(s.p);
-        for (int j = 0; j < s.p; ++j) ab[j] = make_float2((float)s.aval[j], (float)s.bval[j]);
-        po->sab.alloc(s.p);
-        HIP_OK(hipMemcpyAsync(po->sab.p, ab.data(), ab.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));  // host staging vector goes out of scope
-        return;
-    }
-    const int d = (2 * s.R + 1) * (2 * s.R + 1), kp = nlek::patch_ckpad(s.R);
-    std::vector<signed char> bytes(nlek::patch_cpatch_bytes(s.p, s.R), 0);
-    std::vector<int> norm(s.p, 0);
-    for (int j = 0; j < s.p; ++j)
-        for (int k = 0; k < 2 * d; ++k) {
-            const int v = (k < d ? s.aval[(size_t)j * d + k] : s.bval[(size_t)j * d + k - d]) - 128;
-            bytes[(size_t)j * kp + k] = (signed char)v;
-            norm[j] += v * v;
-        }
-    po->cpatch.alloc(bytes.size());
-    po->cnorm.alloc(s.p);
-    HIP_OK(hipMemcpyAsync(po->cpatch.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(po->cnorm.p, norm.data(), norm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));  // host staging vectors go out of scope
-}
-void upload_patch_operands(nle_ctx* c, const SampleSet& s, PatchOperands* po) {
-    if (s.chroma()) upload_chroma_operands(c, s, po);
-    if (s.R <= 0) return;
-    const int d = (2 * s.R + 1) * (2 * s.R + 1), kp = nlek::patch_kpad(s.R);
-    std::vector<signed char> bytes(nlek::patch_spatch_bytes(s.p, s.R), 0);
-    std::vector<int> norm(s.p, 0);
-    for (int j = 0; j < s.p; ++j)
-        for (int k = 0; k < d; ++k) {
-            const int v = s.patch[(size_t)j * d + k] - 128;
-            bytes[(size_t)j * kp + k] = (signed char)v;
-            norm[j] += v * v;
-        }
-    po->spatch.alloc(bytes.size());
-    po->snorm.alloc(s.p);
-    HIP_OK(hipMemcpyAsync(po->spatch.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(po->snorm.p, norm.data(), norm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));  // host staging vectors go out of scope
-}
-
-// fp64 affinity rows [pix0, pix0 + M) (natural order, ld columns): k_affinity64, or the patch kernel when R > 0
-hipError_t affinity_rows64(hipStream_t st, const float* d_lum, const SampleSet& ss, const float4* d_samples,
-                           const PatchOperands& po, int ld, double hx, double hy, long long pix0, long long M, double* d_kab,
-                           bool skip_samples = false, const unsigned* d_smask = nullptr) {
-    const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
-    if (ss.chroma()) {
-        const double cwd = chroma_cwd(ss);
-        if (ss.R <= 0)
-            return nlek::affinity64_chroma(st, d_lum, ss.d_a, ss.d_b, ss.gs, d_samples, po.sab.p, ss.p, ld, sw, pw, cwd, pix0, M,
-                                           d_kab, skip_samples, d_smask);
-        return nlek::patch_affinity64_chroma(st, d_lum, ss.d_a, ss.d_b, ss.gs, ss.R, d_samples, po.spatch.p, po.snorm.p,
-                                             po.cpatch.p, po.cnorm.p, ss.p, ld, sw, pw / ((2 * ss.R + 1) * (2 * ss.R + 1)), cwd,
-                                             pix0, M, d_kab, skip_samples, d_smask);
-    }
-    if (ss.R <= 0)
-        return nlek::affinity64(st, d_lum, ss.gs, d_samples, ss.p, ld, sw, pw, pix0, M, d_kab, skip_samples, d_smask);
-    const double pwd = pw / ((2 * ss.R + 1) * (2 * ss.R + 1));
-    return nlek::patch_affinity64(st, d_lum, ss.gs, ss.R, d_samples, po.spatch.p, po.snorm.p, ss.p, ld, sw, pwd, pix0, M, d_kab,
-                                  skip_samples, d_smask);
-}
-
-// Ka(i,j), reference src/filter.cpp:128-137,144 (fp64, integer spatial term)
-std::vector<double> build_Ka(const SampleSet& s, double hx, double hy) {
-    if (s.R > 0) return build_Ka_patch(s, hx, hy);
-    const int p = s.p;
-    const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
-    const bool chroma = s.chroma();
-    const double cw = chroma ? chroma_cwd(s) : 0.0;
-    std::vector<double> Ka((size_t)p * p);
-    auto column = [&](int j) {
-        const int rj = (int)(s.pix[j] / s.gs.W), cj = (int)(s.pix[j] % s.gs.W);
-        for (int i = j; i < p; ++i) {
-            const int ri = (int)(s.pix[i] / s.gs.W), ci = (int)(s.pix[i] % s.gs.W);
-            const long long dr = ri - rj, dc = ci - cj;
-            const double sq = (double)(dr * dr + dc * dc);
-            const double dv = (double)s.val[i] - (double)s.val[j];
-            double e = -sw * sq - pw * (dv * dv);
-            if (chroma) e = e - cw * (double)chroma_ssd(s, i, j);  // subtracted last (include/nle.h)
-            const double v = std::exp(e);
-            Ka[(size_t)j * p + i] = v;
-            Ka[(size_t)i * p + j] = v;
-        }
-    };
-    // p (p + 1) / 2 libm exponentials: 1.5 ms on one core at p = 900, before anything else of the train can start.  From
-    // 384 samples on, 8 short-lived threads take BLOCKS of columns of equal triangle area (same values: every entry has one
-    // writer; dealing the columns round-robin had the threads' mirrored writes share every cache line: 6.7 ms)
-    const int nt = p >= 384 ? 8 : 1;
-    std::vector<int> cut(nt + 1, p);
-    for (int t = 0; t < nt; ++t) cut[t] = (int)(p * (1.0 - std::sqrt(1.0 - (double)t / nt)));
-    nleh::run_parts(nt, nt, [&](int t) {
-        for (int j = cut[t]; j < cut[t + 1]; ++j) column(j);
-    });
-    return Ka;
 }
 
 // What the later stages need of Ka.  The literal form is the reference's: Ka's eigenpairs with the
@@ -485,8 +137,7 @@ void scatter_sample_rows(nle_ctx* c, const std::vector<long long>& pix, int nrow
 void build_phi(nle_ctx* c, const float* d_lum, const SampleSet& ss, const Nystrom& ny, double hx,
                double hy, long long pix0, long long M, float* d_phi) {
     const int p = ss.p;
-    DevBuf<float4> d_samples(p);
-    HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    DevBuf<float4> d_samples = upload_samples(c, ss);
     std::vector<float> B = build_B(ny, p);
     DevBuf<float> d_B(B.size());
     HIP_OK(hipMemcpyAsync(d_B.p, B.data(), B.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -677,18 +328,15 @@ void train_materialised(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
 void build_phi64(nle_ctx* c, const float* d_lum, const SampleSet& ss, const Nystrom& ny, double hx, double hy, long long pix0,
                  long long M, double* d_phi) {
     const int p = ss.p, ldp = ld4(p), r = ny.r, ldr = ny.ldr;
-    DevBuf<float4> d_samples(p);
-    HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    const AffinityRows64 kab(c, d_lum, ss, hx, hy, /*want_mask=*/false);
     DevBuf<double> d_B(ny.B.size());  // p x r column-major = what ts_gemm64 takes
     HIP_OK(hipMemcpyAsync(d_B.p, ny.B.data(), ny.B.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    PatchOperands po;
-    upload_patch_operands(c, ss, &po);
     HIP_OK(hipMemsetAsync(d_phi, 0, (size_t)std::max<long long>(M, 1) * ldr * sizeof(double), c->stream));
     const long long chunk = 1ll << 20;  // affinity rows of 1 Mi pixels at a time (K_AB is never held whole)
     DevBuf<double> d_kab((size_t)std::min<long long>(std::max<long long>(M, 1), chunk) * ldp);
     for (long long i0 = 0; i0 < M; i0 += chunk) {
         const long long m = std::min(chunk, M - i0);
-        PROFILED(c, NLE_K_AFFINITY, affinity_rows64(c->stream, d_lum, ss, d_samples.p, po, ldp, hx, hy, pix0 + i0, m, d_kab.p));
+        PROFILED(c, NLE_K_AFFINITY, kab.rows(pix0 + i0, m, d_kab.p));
         PROFILED(c, NLE_K_NYSTROM, nlek::ts_gemm64(c->stream, d_kab.p, m, ldp, p, d_B.p, r, nullptr, d_phi + (size_t)i0 * ldr, ldr));
     }
     scatter_sample_rows(c, ss.pix, p, ny.VA, r, ldr, pix0, M, d_phi);  // exact V_A rows (top block of phi, reference :275)
@@ -852,9 +500,7 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
     tm_s.start();
     // the pass kernel reads the sample table up to the next multiple of 16: pad with zeros (their
     // w entries are zero, so they only have to be finite)
-    DevBuf<float4> d_samples(P64);
-    HIP_OK(hipMemsetAsync(d_samples.p, 0, P64 * sizeof(float4), c->stream));
-    HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    DevBuf<float4> d_samples = upload_samples(c, ss, P64);
     constexpr int kZS = 8;  // slices of the block partials, summed by k_sink_update
     const int npart = nlek::sink_pass_rows(std::max<long long>(M, 1));
     DevBuf<double> d_z((size_t)kZS * P64), d_partial, d_cbuf((size_t)std::max<long long>(M, 1));
@@ -1081,29 +727,14 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
     if (const char* e = std::getenv("NLE_STREAM64_CHUNK_MB")) budget_mb = (size_t)std::max(1, std::atoi(e));
     const long long rows_fit = (long long)((budget_mb << 20) / ((size_t)ld * sizeof(double)));
     const long long CH = std::max<long long>(256, std::min<long long>(std::max<long long>(M, 1), rows_fit));
-    DevBuf<float4> d_samples(p);
-    HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), p * sizeof(float4), hipMemcpyHostToDevice, st));
-    PatchOperands po;
-    upload_patch_operands(c, ss, &po);
-    DevBuf<unsigned> d_smask;  // a listed sample set: its rows are zeroed by bitmask instead of the grid's closed form
-    if (ss.listed) {
-        const long long N = (long long)ss.gs.H * ss.gs.W;
-        DevBuf<long long> d_spix(p);
-        d_smask.alloc((size_t)((N + 31) / 32));
-        HIP_OK(hipMemcpyAsync(d_spix.p, ss.pix.data(), p * sizeof(long long), hipMemcpyHostToDevice, st));
-        PROFILED(c, NLE_K_SMALL, nlek::sample_mask(st, d_spix.p, p, N, d_smask.p));
-        HIP_OK(hipStreamSynchronize(st));  // d_spix goes out of scope
-    }
+    const AffinityRows64 kab(c, d_lum, ss, hx, hy, /*want_mask=*/true);
     DevBuf<double> d_K((size_t)CH * ld), d_partial((size_t)nlek::kRowpassMaxBlocks * ld), d_zc(ld), d_z(ld), d_ones(ld),
         d_cbuf((size_t)std::max<long long>(M, 1));
     SampleSinkhorn sk(c, p, ld, T);
     HIP_OK(nlek::fill64(st, d_ones.p, ld, 1.0));
     tr.mark("s64: alloc+upload");
     auto chunk_rows = [&](long long i0) { return std::min<long long>(CH, M - i0); };
-    auto gen = [&](long long i0, long long mc) {
-        PROFILED(c, NLE_K_AFFINITY, affinity_rows64(st, d_lum, ss, d_samples.p, po, ld, hx, hy, pix0 + i0, mc, d_K.p, true,
-                                                    d_smask.p));
-    };
+    auto gen = [&](long long i0, long long mc) { PROFILED(c, NLE_K_AFFINITY, kab.rows(pix0 + i0, mc, d_K.p, true)); };
     auto pass_pixels = [&](int mode, bool last) {
         HIP_OK(hipMemsetAsync(d_z.p, 0, ld * sizeof(double), st));
         for (long long i0 = 0; i0 < M; i0 += CH) {
@@ -1256,9 +887,10 @@ void check_exact(const nle_ctx* c, int H, int W, int n_eig) {
     if ((long long)H * W > NLE_EXACT_MAX_PIXELS)
         throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 takes at most NLE_EXACT_MAX_PIXELS (2^20) pixels"};
     if (n_eig > 256) throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 takes at most 256 eigenvectors"};
-    if (c->patch_radius > 0) throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 does not take patch affinities (radius must be 0)"};
-    if (c->chroma_a) throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 does not take chroma affinities (nle_ctx_set_chroma)"};
-    if (c->sampler != NLE_SAMPLER_GRID)
+    const AffinityOpts opts = affinity_opts(c);
+    if (opts.patch()) throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 does not take patch affinities (radius must be 0)"};
+    if (opts.chroma()) throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 does not take chroma affinities (nle_ctx_set_chroma)"};
+    if (opts.listed())
         throw Fail{NLE_ERR_INVALID, "NLE_MODE_EXACT_F64 takes no samples: the sampler must be NLE_SAMPLER_GRID"};
 }
 
@@ -1635,31 +1267,14 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         throw Fail{NLE_ERR_INVALID, "Phi-free path without tables supports at most 256 samples and 128 eigenvectors"};
     if (c->mode == NLE_MODE_PHI_FREE && !generic_ok && !tables_ok)
         throw Fail{NLE_ERR_INVALID, "Phi-free path supports at most 128 eigenvectors and a 32 x 36 sample grid"};
-    // patch affinities (R > 0): the fp64 formulations with explicit affinity rows only (the table, Phi-free and fp32 forms
-    // cannot express them); every check here is decided the same way on every rank
-    const int R = c->patch_radius;
-    if (R > 0 && c->mode != NLE_MODE_AUTO && c->mode != NLE_MODE_MATERIALISED_F64 && c->mode != NLE_MODE_STREAMED_F64)
-        throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) run in NLE_MODE_AUTO, NLE_MODE_MATERIALISED_F64 or "
-                                    "NLE_MODE_STREAMED_F64 only"};
-    check_patch_radius(c, R, H, W);
-    // chroma affinities: the same two formulations, for the same reason (a 256-level table cannot index a colour triple)
-    const bool chroma = c->chroma_a != nullptr;
-    if (chroma && c->mode != NLE_MODE_AUTO && c->mode != NLE_MODE_MATERIALISED_F64 && c->mode != NLE_MODE_STREAMED_F64)
-        throw Fail{NLE_ERR_INVALID, "chroma affinities (nle_ctx_set_chroma) run in NLE_MODE_AUTO, NLE_MODE_MATERIALISED_F64 or "
-                                    "NLE_MODE_STREAMED_F64 only"};
-    check_chroma(c, R, gs.p());
-    // the farthest sampler (a listed sample set): the fp64 formulations with explicit affinity rows only (the tables need a
-    // Cartesian set, the other forms are fp32); decided the same way on every rank
-    const bool farthest = c->sampler == NLE_SAMPLER_FARTHEST;
-    if (farthest && c->mode != NLE_MODE_AUTO && c->mode != NLE_MODE_MATERIALISED_F64 && c->mode != NLE_MODE_STREAMED_F64)
-        throw Fail{NLE_ERR_INVALID, "the farthest sampler runs in NLE_MODE_AUTO, NLE_MODE_MATERIALISED_F64 or "
-                                    "NLE_MODE_STREAMED_F64 only"};
-    check_sampler(c, hx, hy);
+    // patch affinities, chroma affinities, the farthest sampler: every check here is decided the same way on every rank
+    const AffinityOpts opts = affinity_opts(c);
+    check_affinity_opts(c, opts, gs, H, W, hx, hy, Caller::TRAIN);
     // auto: the table form (all fp64) whenever it applies, else the literal decomposition in fp64 (generic64.hip).  The
     // fp32 formulations (materialised Phi, Phi-free with fp32 affinities) run only when asked for by mode: they miss
     // the 1e-4 bar on some well-posed inputs (DESIGN.md "Numerics").
-    const bool want_fuse = R == 0 && !farthest && !chroma && (c->mode == NLE_MODE_PHI_FREE || c->mode == NLE_MODE_PHI_FREE_EXP ||
-                                      (c->mode == NLE_MODE_AUTO && tables_ok));
+    const bool want_fuse = !opts.any() && (c->mode == NLE_MODE_PHI_FREE || c->mode == NLE_MODE_PHI_FREE_EXP ||
+                                           (c->mode == NLE_MODE_AUTO && tables_ok));
     HIP_OK(hipSetDevice(c->device));
 
     auto f = new nle_filter();
@@ -1679,16 +1294,14 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         Timer tm_a(c->stream);
         tm_a.start();
         std::vector<long long> list;
-        if (farthest) list = farthest_list(c, d_lum, gs, hx, hy);
-        SampleSet ss = fetch_samples(c, d_lum, gs, (want_fuse && tables_ok) || R > 0 || chroma, c->slab_input && c->world > 1,
-                                     R, farthest ? &list : nullptr, chroma);
-        if (R > 0 && ranks_where(c, !ss.quantised) > 0)  // refused on every rank if the plane is not integer valued on one
-            throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
-                                        "(the L channel of 8-bit Lab)"};
-        if (chroma && ranks_where(c, !ss.quantised || !ss.chroma_quantised) > 0)  // likewise agreed by every rank
-            throw Fail{NLE_ERR_INVALID, "chroma affinities need integer-valued L, a and b planes in [0, 255] (the channels of "
-                                        "8-bit Lab)"};
-        f->chroma_hc = chroma ? ss.hc : 0.0;
+        if (opts.listed()) list = farthest_list(c, d_lum, gs, hx, hy);
+        FetchSpec spec;
+        spec.check_levels = want_fuse && tables_ok;
+        spec.slab_plane = c->slab_input && c->world > 1;
+        spec.list = opts.listed() ? &list : nullptr;
+        SampleSet ss = fetch_samples(c, d_lum, gs, opts, spec);
+        require_integer_planes(c, ss, /*agree_over_ranks=*/true);
+        f->chroma_hc = opts.chroma() ? opts.hc : 0.0;
         const bool fuse = c->mode == NLE_MODE_AUTO ? (want_fuse && tables_ok && ss.quantised)
                                                    : (want_fuse && (generic_ok || (tables_ok && ss.quantised)));
         if (c->mode == NLE_MODE_PHI_FREE && !fuse)
@@ -1817,14 +1430,9 @@ int nle_compute_kernel(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
     if (!ctx || !d_lum) return NLE_ERR_INVALID;
     return guard(ctx, [&] {
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
-        if (ctx->patch_radius > 0)
-            throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) does not take patch affinities: use nle_compute_kernel64"};
-        if (ctx->chroma_a)
-            throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) does not take chroma affinities: use nle_compute_kernel64"};
-        if (ctx->sampler != NLE_SAMPLER_GRID)
-            throw Fail{NLE_ERR_INVALID, "nle_compute_kernel (fp32) takes the grid sampler only: use nle_compute_kernel64"};
+        check_affinity_opts(ctx, affinity_opts(ctx), gs, H, W, hx, hy, Caller::KERNEL32);
         HIP_OK(hipSetDevice(ctx->device));
-        SampleSet ss = fetch_samples(ctx, d_lum, gs);
+        SampleSet ss = fetch_samples(ctx, d_lum, gs, AffinityOpts{});
         if (h_Ka) {
             std::vector<double> Ka = build_Ka(ss, hx, hy);
             std::copy(Ka.begin(), Ka.end(), h_Ka);
@@ -1832,8 +1440,7 @@ int nle_compute_kernel(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
         if (d_kab) {
             int row0, row1;
             slab(H, ctx->rank, ctx->world, &row0, &row1);
-            DevBuf<float4> d_samples(ss.p);
-            HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), ss.p * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+            DevBuf<float4> d_samples = upload_samples(ctx, ss);
             PROFILED(ctx, NLE_K_AFFINITY,
                      nlek::affinity(ctx->stream, d_lum, gs, d_samples.p, ss.p, ld4(ss.p), nsw_of(hx), nsw_of(hy),
                                     (long long)row0 * W, (long long)(row1 - row0) * W, d_kab));
@@ -1848,14 +1455,9 @@ int nle_nystrom(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_sample
     if (!ctx || !d_lum || !d_phi || !r) return NLE_ERR_INVALID;
     return guard(ctx, [&] {
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
-        if (ctx->patch_radius > 0)
-            throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) does not take patch affinities: use the fp64 formulations"};
-        if (ctx->chroma_a)
-            throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) does not take chroma affinities: use the fp64 formulations"};
-        if (ctx->sampler != NLE_SAMPLER_GRID)
-            throw Fail{NLE_ERR_INVALID, "nle_nystrom (fp32) takes the grid sampler only: use the fp64 formulations"};
+        check_affinity_opts(ctx, affinity_opts(ctx), gs, H, W, hx, hy, Caller::NYSTROM32);
         HIP_OK(hipSetDevice(ctx->device));
-        SampleSet ss = fetch_samples(ctx, d_lum, gs);
+        SampleSet ss = fetch_samples(ctx, d_lum, gs, AffinityOpts{});
         std::vector<double> Ka = build_Ka(ss, hx, hy);
         Nystrom ny = solve_Ka(nullptr, Ka, ss.p, false);
         int row0, row1;
@@ -1930,22 +1532,15 @@ int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
     if (!ctx || !d_lum) return NLE_ERR_INVALID;
     return guard(ctx, [&] {
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
-        const int R = ctx->patch_radius;
-        check_patch_radius(ctx, R, H, W);
-        const bool chroma = ctx->chroma_a != nullptr;
-        if (chroma && !(hx > 0 && hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
-        check_chroma(ctx, R, gs.p());
-        check_sampler(ctx, hx, hy);
+        const AffinityOpts opts = affinity_opts(ctx);
+        check_affinity_opts(ctx, opts, gs, H, W, hx, hy, Caller::KERNEL64);
         HIP_OK(hipSetDevice(ctx->device));
         std::vector<long long> list;
-        if (ctx->sampler == NLE_SAMPLER_FARTHEST) list = farthest_list(ctx, d_lum, gs, hx, hy);
-        SampleSet ss = fetch_samples(ctx, d_lum, gs, R > 0 || chroma, false, R, list.empty() ? nullptr : &list, chroma);
-        if (R > 0 && !ss.quantised)
-            throw Fail{NLE_ERR_INVALID, "patch affinities (patch radius > 0) need an integer-valued luminance plane in [0, 255] "
-                                        "(the L channel of 8-bit Lab)"};
-        if (chroma && (!ss.quantised || !ss.chroma_quantised))
-            throw Fail{NLE_ERR_INVALID, "chroma affinities need integer-valued L, a and b planes in [0, 255] (the channels of "
-                                        "8-bit Lab)"};
+        if (opts.listed()) list = farthest_list(ctx, d_lum, gs, hx, hy);
+        FetchSpec spec;
+        spec.list = opts.listed() ? &list : nullptr;
+        SampleSet ss = fetch_samples(ctx, d_lum, gs, opts, spec);
+        require_integer_planes(ctx, ss, /*agree_over_ranks=*/false);
         if (h_Ka) {
             std::vector<double> Ka = build_Ka(ss, hx, hy);
             std::copy(Ka.begin(), Ka.end(), h_Ka);
@@ -1953,13 +1548,8 @@ int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
         if (d_kab) {
             int row0, row1;
             slab(H, ctx->rank, ctx->world, &row0, &row1);
-            DevBuf<float4> d_samples(ss.p);
-            HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), ss.p * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
-            PatchOperands po;
-            upload_patch_operands(ctx, ss, &po);
-            PROFILED(ctx, NLE_K_AFFINITY,
-                     affinity_rows64(ctx->stream, d_lum, ss, d_samples.p, po, ld4(ss.p), hx, hy, (long long)row0 * W,
-                                     (long long)(row1 - row0) * W, d_kab));
+            const AffinityRows64 kab(ctx, d_lum, ss, hx, hy, /*want_mask=*/false);
+            PROFILED(ctx, NLE_K_AFFINITY, kab.rows((long long)row0 * W, (long long)(row1 - row0) * W, d_kab));
             HIP_OK(hipStreamSynchronize(ctx->stream));
             prof_flush(ctx);
         }
@@ -2138,9 +1728,10 @@ int nle_sample_pixels(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_
         const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
         if (gs.p() > 2048) throw Fail{NLE_ERR_INVALID, "more than 2048 samples is not supported"};
         std::vector<long long> list((size_t)gs.p());
-        if (ctx->sampler == NLE_SAMPLER_FARTHEST) {
+        const AffinityOpts opts = affinity_opts(ctx);
+        if (opts.listed()) {
             if (!d_lum) throw Fail{NLE_ERR_INVALID, "the farthest sampler needs the luminance plane"};
-            check_sampler(ctx, hx, hy);
+            check_affinity_opts(ctx, opts, gs, H, W, hx, hy, Caller::SAMPLE_PIXELS);
             HIP_OK(hipSetDevice(ctx->device));
             list = farthest_list(ctx, d_lum, gs, hx, hy);
             prof_flush(ctx);
@@ -2367,11 +1958,10 @@ int nle_bench_affinity(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
         GridSpec gs;
         if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
         HIP_OK(hipSetDevice(ctx->device));
-        SampleSet ss = fetch_samples(ctx, d_lum, gs);
+        SampleSet ss = fetch_samples(ctx, d_lum, gs, AffinityOpts{});
         int row0, row1;
         slab(H, ctx->rank, ctx->world, &row0, &row1);
-        DevBuf<float4> d_samples(ss.p);
-        HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), ss.p * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+        DevBuf<float4> d_samples = upload_samples(ctx, ss);
         const float sw = nsw_of(hx), pw = nsw_of(hy);
         const long long pix0 = (long long)row0 * W, M = (long long)(row1 - row0) * W;
         HIP_OK(nlek::affinity(ctx->stream, d_lum, gs, d_samples.p, ss.p, ld4(ss.p), sw, pw, pix0, M, d_kab));
@@ -2392,18 +1982,17 @@ int nle_bench_affinity64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
         GridSpec gs;
         if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) throw Fail{NLE_ERR_INVALID, "invalid sample counts"};
         HIP_OK(hipSetDevice(ctx->device));
-        SampleSet ss = fetch_samples(ctx, d_lum, gs);
+        // the plain k_affinity64<false>, whatever the ctx's options are
+        SampleSet ss = fetch_samples(ctx, d_lum, gs, AffinityOpts{});
         int row0, row1;
         slab(H, ctx->rank, ctx->world, &row0, &row1);
-        DevBuf<float4> d_samples(ss.p);
-        HIP_OK(hipMemcpyAsync(d_samples.p, ss.packed.data(), ss.p * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+        const AffinityRows64 kab(ctx, d_lum, ss, hx, hy, /*want_mask=*/false);
         const long long pix0 = (long long)row0 * W, M = std::min<long long>(rows, row1 - row0) * W;
-        const double sw = 1.0 / (hx * hx), pw = 1.0 / (hy * hy);
-        HIP_OK(nlek::affinity64(ctx->stream, d_lum, gs, d_samples.p, ss.p, ld4(ss.p), sw, pw, pix0, M, d_kab, true));
+        HIP_OK(kab.rows(pix0, M, d_kab, true));
         Timer tm(ctx->stream);
         tm.start();
         for (int i = 0; i < reps; ++i)
-            HIP_OK(nlek::affinity64(ctx->stream, d_lum, gs, d_samples.p, ss.p, ld4(ss.p), sw, pw, pix0, M, d_kab, true));
+            HIP_OK(kab.rows(pix0, M, d_kab, true));
         tm.stop();
         *h_avg_ms = tm.ms() / reps;
     });

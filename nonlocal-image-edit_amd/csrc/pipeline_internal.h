@@ -1,6 +1,7 @@
-// Internals shared by the host-side translation units of libnle_hip.so (pipeline.hip, devsolve.hip): the ctx / filter
-// structs behind the opaque handles of include/nle.h, error plumbing, the stream-ordered workspace arena, per-kernel event
-// timing, the sample-grid closed form and the RCCL loader.  Not installed, not part of the ABI.
+// Internals shared by the host-side translation units of libnle_hip.so (pipeline.hip, samples.hip, ortho.hip, devsolve.hip,
+// abi_ctx.hip): the ctx / filter structs behind the opaque handles of include/nle.h, error plumbing, the stream-ordered
+// workspace arena, per-kernel event timing, the sample-grid closed form and the RCCL loader.  Not installed, not part of
+// the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -181,6 +182,7 @@ struct DevBuf {
     explicit DevBuf(size_t count) { alloc(count); }
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n), owner(o.owner) { o.take(); }  // (a DevBuf returned from a function)
     void alloc(size_t count) {
         release();
         if (count) {
