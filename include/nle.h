@@ -397,6 +397,51 @@ int nle_apply_u8(nle_filter* f, const float* d_x, int H, int W, const double* h_
 int nle_apply_rounded8(nle_filter* f, const float* d_x, int H, int W, const double* h_fS, float* d_y);
 int nle_apply_u8_host(nle_filter* f, const float* h_x, int H, int W, const double* h_fS, unsigned char* h_out);
 
+/* ---- region edits (new in this build: the reference edits with one global weight vector, src/filter.cpp:412-443) ---- */
+/* Scribble on a few regions and give each its own layer weights.  A trained filter f has K' pairs (V, lambda) over N = H W
+ * pixels.  Inputs: L layers, 1 <= L <= NLE_REGION_LAYERS_MAX; M regions, 1 <= M <= NLE_REGION_MAX; stroke planes s_1 .. s_M
+ * (fp32, any finite values; the CLI gives 0 / 1); scales c_m (NULL: 1); the spread t > 0; the floor phi > 0; the weights
+ * Wt[(M + 1)][L], fp64, row-major, row 0 the background and row m region m.
+ *   Spread   q_m = nle_apply(f, s_m, fS) with fS[k] = c_m pow(lambda_k, t): label propagation V lambda^t V^T s_m on the
+ *            affinity the filter was trained on, exactly the apply path of whatever formulation f was trained in; an fp32
+ *            plane.  The scale rides in fS (no extra pass).
+ *   Layers   Y_0 .. Y_{L-1} = nle_apply_layers(f, x, L), fp32 planes.
+ *   Combine  pointwise, per pixel i, in fp64, every operation rounded on its own (no fma), sums in ascending m and l:
+ *              u_m     = Q_m[i] > 0 ? (double)Q_m[i] : 0                       (a NaN q counts as 0)
+ *              sigma   = u_1 + u_2 + .. + u_M ;   d = sigma > phi ? sigma : phi
+ *              alpha_m = u_m / d ;   alpha_0 = 1 - sigma / d
+ *              w_l     = alpha_0 Wt[0][l] + alpha_1 Wt[1][l] + .. + alpha_M Wt[M][l]
+ *              y       = w_0 (double)Y_0[i] + .. + w_{L-1} (double)Y_{L-1}[i]
+ *            The rule is continuous in q: where the strokes have little influence (sigma < phi) the pixel blends to the
+ *            background row, elsewhere the memberships sum to 1.
+ * Output kinds: NLE_REGION_OUT_F32 stores (float)y; NLE_REGION_OUT_ROUNDED8 stores rintf((float)y) saturated to [0, 255] as
+ * fp32 (the rule of nle_apply_u8's last step; what nle_lab2bgr8 takes from nle_apply_rounded8); NLE_REGION_OUT_U8 stores
+ * the same value as a byte.
+ * The C++ surface and the CLI set c_m = N / sum_i s_m(i) (summed on the host in fp64): a spread stroke then has mean ~ 1
+ * whatever its size and phi is dimensionless; their defaults are t = 4 and phi = 0.05. */
+#define NLE_REGION_MAX 8
+#define NLE_REGION_LAYERS_MAX 16
+#define NLE_REGION_OUT_F32 0
+#define NLE_REGION_OUT_ROUNDED8 1
+#define NLE_REGION_OUT_U8 2
+/* the stage call, the rule alone: d_layers L planes and d_q M planes of n fp32 values each, plane l at d_layers +
+ * l layer_stride and plane m at d_q + m q_stride (strides in floats, >= n); h_weights (M + 1) x L; d_out n floats, or n
+ * bytes for NLE_REGION_OUT_U8.  No alignment is required of pointers or strides. */
+int nle_region_combine(nle_ctx* ctx, const float* d_layers, int L, const float* d_q, int M, long long n,
+                       long long layer_stride, long long q_stride, const double* h_weights, double floor, int out_kind,
+                       void* d_out);
+/* the spreads: d_strokes M planes of H W fp32 values, plane-major; h_scale M doubles or NULL; d_q M planes likewise */
+int nle_region_spread(nle_filter* f, const float* d_strokes, int M, int H, int W, const double* h_scale, double spread,
+                      float* d_q);
+/* nle_apply_layers + nle_region_spread + nle_region_combine with the L + M work planes in the ctx's workspace: bitwise what
+ * the three calls give.  Works for every formulation nle_apply works for (it only composes them).  NLE_ERR_INVALID, with a
+ * message and the ctx left usable, for M or L out of range, a spread or floor that is not finite and > 0, a scale that is not
+ * finite, H W that is not the filter's, a NULL pointer (h_scale apart), an unknown out kind, and world > 1 (the combine is pixel-local, but slabs
+ * and device groups are not built: refused before any collective). */
+int nle_apply_regions(nle_filter* f, const float* d_x, int H, int W, int L, const float* d_strokes, int M,
+                      const double* h_scale, double spread, double floor, const double* h_weights, int out_kind,
+                      void* d_out);
+
 /* ---- colour wrapper on the device (the code either side of the path) ------------------------------- */
 /* cv::cvtColor(COLOR_BGR2Lab) on an 8-bit image as the reference uses it (src/filter.cpp:423,463) and
  * the split / convertTo(CV_64F) of the L channel (:424-426,465-467): d_bgr n x 3 bytes -> d_lab n x 3

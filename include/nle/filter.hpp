@@ -179,6 +179,17 @@ public:
     void trainForEnhancement(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
                              int nSinkhornIter = 10, int nEigenVectors = 5);
     Image enhance(const Image& I, const std::vector<DType>& weights) const;
+    // region edits (new here; nle_apply_regions in nle.h states the rule): enhance with layer weights of its own for every
+    // scribbled region.  strokes[m]: a one-channel 8-bit image of I's size, a pixel belongs to the stroke where its byte is
+    // >= 128; regionWeights[m]: the weights of region m, as many as `weights`, which is the background's row.  Each stroke
+    // is spread along the trained affinity (V lambda^spread V^T s, scaled to mean 1) and the spreads decide, pixel by
+    // pixel, how the rows blend; below `floor` of total influence a pixel blends to the background.  The defaults are the
+    // values of the two CPU experiments behind the definition, not tuned further.  Throws
+    // std::runtime_error for an all-zero stroke, a size mismatch, a weight count other than weights.size(), more than
+    // NLE_REGION_MAX strokes or NLE_REGION_LAYERS_MAX weights, and for a filter trained on a device group (NLE_DEVICES).
+    Image enhanceRegions(const Image& I, const std::vector<Image>& strokes,
+                         const std::vector<std::vector<DType>>& regionWeights, const std::vector<DType>& weights,
+                         DType spread = 4, DType floor = 0.05) const;
     // include/filter.hpp:40-45: the filter is trained on the bilateral-filtered L channel; denoise shrinks the
     // eigenvalues to min(lambda, 1)^k on the a and b channels (src/filter.cpp:349-410, 521-538)
     void trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,

@@ -36,6 +36,10 @@ MODE_AUTO, MODE_MATERIALISED, MODE_PHI_FREE, MODE_PHI_FREE_EXP, MODE_MATERIALISE
 MODE_EXACT_F64 = _abi.NLE_MODE_EXACT_F64  # the exact (Nystrom-free) filter, opt-in
 EXACT_MAX_PIXELS = _abi.NLE_EXACT_MAX_PIXELS
 SAMPLER_GRID, SAMPLER_FARTHEST = _abi.NLE_SAMPLER_GRID, _abi.NLE_SAMPLER_FARTHEST
+# region edits: the bounds and the output kinds of nle_region_combine / nle_apply_regions
+REGION_MAX, REGION_LAYERS_MAX = _abi.NLE_REGION_MAX, _abi.NLE_REGION_LAYERS_MAX
+REGION_OUT_F32, REGION_OUT_ROUNDED8, REGION_OUT_U8 = (_abi.NLE_REGION_OUT_F32, _abi.NLE_REGION_OUT_ROUNDED8,
+                                                      _abi.NLE_REGION_OUT_U8)
 
 _lib = None
 
@@ -653,6 +657,26 @@ class Context:
                                     C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    def region_combine(self, layers, q, weights, floor=0.05, out_kind=0, out=None):
+        """nle_region_combine, the rule alone: layers (L, n) and q (M, n) float32 device tensors whose rows are contiguous
+        and may lie any stride >= n apart (a view into a larger buffer, at any offset, is taken as it is); weights
+        (M + 1, L) float64, row 0 the background.  Returns n float32 values, or n bytes for REGION_OUT_U8."""
+        torch = _torch()
+        self._sync_in()
+        L, n = layers.shape
+        M = q.shape[0]
+        if q.shape[1] != n or layers.stride(1) != 1 or q.stride(1) != 1:
+            raise NLEError(NLE_ERR_INVALID, "region_combine: layers (L, n) and q (M, n) with contiguous rows")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (M + 1, L):
+            raise NLEError(NLE_ERR_INVALID, f"region_combine: weights must be {(M + 1, L)}, got {w.shape}")
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32, device=layers.device)
+        _check(lib().nle_region_combine(self._h, C.c_void_p(layers.data_ptr()), L, C.c_void_p(q.data_ptr()), M, n,
+                                        layers.stride(0) if L > 1 else n, q.stride(0) if M > 1 else n, _np_ptr(w),
+                                        float(floor), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
+        return out
+
     def bench_affinity(self, lum, n_row_samples, n_col_samples, hx, hy, reps=10):
         torch = _torch()
         lum = self._lum(lum)
@@ -904,6 +928,56 @@ class NLEFilter:
             out = torch.empty(n, dtype=torch.float32, device=x.device)
         _check(lib().nle_apply(self._f, C.c_void_p(x.data_ptr()), H, W, _np_ptr(fs), C.c_void_p(out.data_ptr())),
                self.ctx._h)
+        return out
+
+    def _strokes(self, strokes):
+        torch = _torch()
+        t = torch.as_tensor(strokes, dtype=torch.float32, device=f"cuda:{self.ctx.device}").contiguous()
+        if t.ndim != 3:
+            raise NLEError(NLE_ERR_INVALID, "strokes must be M x H x W")
+        self.ctx._sync_in()
+        return t
+
+    @staticmethod
+    def _scale(scale, M):
+        if scale is None:
+            return None, None
+        c = np.ascontiguousarray(scale, dtype=np.float64)
+        if c.shape != (M,):
+            raise NLEError(NLE_ERR_INVALID, f"scale must hold M = {M} values, got {c.shape}")
+        return c, _np_ptr(c)
+
+    def region_spread(self, strokes, scale=None, spread=4.0, out=None):
+        """nle_region_spread: q_m = apply(s_m, c_m lambda^spread) for the M stroke planes (M x H x W); scale: the M values
+        c_m or None (1).  Returns (M, n_local) float32."""
+        torch = _torch()
+        s = self._strokes(strokes)
+        M, H, W = s.shape
+        c, cp = self._scale(scale, M)
+        if out is None:
+            out = torch.empty((M, self.info()["n_local"]), dtype=torch.float32, device=s.device)
+        _check(lib().nle_region_spread(self._f, C.c_void_p(s.data_ptr()), M, H, W, cp, float(spread),
+                                       C.c_void_p(out.data_ptr())), self.ctx._h)
+        return out
+
+    def apply_regions(self, x, n_layers, strokes, weights, scale=None, spread=4.0, floor=0.05, out_kind=0, out=None):
+        """nle_apply_regions: the layers of x, the spreads of the stroke planes and the combine in one call.  weights:
+        (M + 1, n_layers) float64, row 0 the background.  Returns n_local float32 values, or bytes for REGION_OUT_U8."""
+        torch = _torch()
+        x = self.ctx._lum(x)
+        H, W = x.shape
+        s = self._strokes(strokes)
+        M = s.shape[0]
+        c, cp = self._scale(scale, M)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (M + 1, int(n_layers)):
+            raise NLEError(NLE_ERR_INVALID, f"weights must be {(M + 1, int(n_layers))}, got {w.shape}")
+        if out is None:
+            out = torch.empty(self.info()["n_local"], dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32,
+                              device=x.device)
+        _check(lib().nle_apply_regions(self._f, C.c_void_p(x.data_ptr()), H, W, int(n_layers), C.c_void_p(s.data_ptr()), M,
+                                       cp, float(spread), float(floor), _np_ptr(w), int(out_kind),
+                                       C.c_void_p(out.data_ptr())), self.ctx._h)
         return out
 
     def apply_layers(self, x, n_layers, out=None):

@@ -331,6 +331,17 @@ hipError_t channel8(hipStream_t s, const unsigned char* d_img, long long n, int 
 // cv::max(y, 0) / cv::min(y, 255) / convertTo(CV_8U) of a filtered plane (src/filter.cpp:434-436): round half to even
 hipError_t plane_to_u8(hipStream_t s, const float* d_y, long long n, unsigned char* d_out);
 hipError_t channel8_plane(hipStream_t s, const unsigned char* d_u8, long long n, float* d_out);  // bytes -> fp32 levels
+// region edits (region.hip; the rule is stated in include/nle.h at nle_region_combine): per pixel the memberships of the M
+// spread stroke planes d_q blend the rows of wt ((M + 1) x L, row 0 the background) into one weight per layer, and the L
+// layer planes d_layers are summed under those weights -- fp64, every operation rounded on its own.  Planes by base pointer
+// and plane stride (in floats); out_kind: NLE_REGION_OUT_*; d_out n floats, or n bytes for NLE_REGION_OUT_U8.
+constexpr int kRegionLayersMax = 16, kRegionMax = 8;  // NLE_REGION_LAYERS_MAX, NLE_REGION_MAX
+struct RegionWeights {
+    double wt[(kRegionMax + 1) * kRegionLayersMax];  // the first (M + 1) * L entries are read
+};
+hipError_t region_combine(hipStream_t s, const float* d_layers, long long layer_stride, int L, const float* d_q,
+                          long long q_stride, int M, long long n, const RegionWeights& wt, double floor, int out_kind,
+                          void* d_out);
 // single-channel 8-bit bilateral filter (fp32 planes holding integers); tables from the host: space_w (2r+1)^2 with 0
 // outside the circle, colour_w 256 entries
 int bilateral8_max_radius();

@@ -1950,6 +1950,105 @@ int nle_apply_u8_host(nle_filter* f, const float* h_x, int H, int W, const doubl
     });
 }
 
+// ---- region edits (include/nle.h "region edits"; the kernel is region.hip) ----
+}  // extern "C"
+
+namespace {
+
+// every refusal of the three entry points, before anything is enqueued (and so before any collective)
+void region_check_combine(int L, int M, double floor, int out_kind) {
+    if (L < 1 || L > NLE_REGION_LAYERS_MAX)
+        throw Fail{NLE_ERR_INVALID, "region edits take 1 to " + std::to_string(NLE_REGION_LAYERS_MAX) + " layers, got " +
+                                        std::to_string(L)};
+    if (M < 1 || M > NLE_REGION_MAX)
+        throw Fail{NLE_ERR_INVALID, "region edits take 1 to " + std::to_string(NLE_REGION_MAX) + " regions, got " +
+                                        std::to_string(M)};
+    if (!std::isfinite(floor) || !(floor > 0))
+        throw Fail{NLE_ERR_INVALID, "the region floor must be finite and > 0, got " + std::to_string(floor)};
+    if (out_kind != NLE_REGION_OUT_F32 && out_kind != NLE_REGION_OUT_ROUNDED8 && out_kind != NLE_REGION_OUT_U8)
+        throw Fail{NLE_ERR_INVALID, "unknown region output kind " + std::to_string(out_kind) + " (NLE_REGION_OUT_*)"};
+}
+
+void region_check_spread(const nle_filter* f, int M, int H, int W, const double* h_scale, double spread) {
+    if (M < 1 || M > NLE_REGION_MAX)
+        throw Fail{NLE_ERR_INVALID, "region edits take 1 to " + std::to_string(NLE_REGION_MAX) + " regions, got " +
+                                        std::to_string(M)};
+    if (!std::isfinite(spread) || !(spread > 0))
+        throw Fail{NLE_ERR_INVALID, "the region spread must be finite and > 0, got " + std::to_string(spread)};
+    for (int m = 0; h_scale && m < M; ++m)
+        if (!std::isfinite(h_scale[m]))
+            throw Fail{NLE_ERR_INVALID, "the scale of region " + std::to_string(m + 1) + " is not finite"};
+    if (f->ctx->world > 1)
+        throw Fail{NLE_ERR_INVALID, "region edits run on one device only (world == 1): slabs and device groups are not built"};
+    if (H <= 0 || W <= 0 || (long long)H * W != (long long)f->H * f->W)  // the text of nle_apply's refusal (:447-449)
+        throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+}
+
+void region_combine_impl(nle_ctx* c, const float* d_layers, int L, const float* d_q, int M, long long n, long long layer_stride,
+                         long long q_stride, const double* h_weights, double floor, int out_kind, void* d_out) {
+    nlek::RegionWeights wt{};
+    std::copy(h_weights, h_weights + (size_t)(M + 1) * L, wt.wt);
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(nlek::region_combine(c->stream, d_layers, layer_stride, L, d_q, q_stride, M, n, wt, floor, out_kind, d_out));
+    HIP_OK(hipStreamSynchronize(c->stream));
+}
+
+// q_m = apply(s_m, c_m lambda^t), one nle_apply per stroke plane
+void region_spread_impl(nle_filter* f, const float* d_strokes, int M, int H, int W, const double* h_scale, double spread,
+                        float* d_q) {
+    std::vector<double> fS((size_t)f->K);
+    for (int m = 0; m < M; ++m) {
+        const double cm = h_scale ? h_scale[m] : 1.0;
+        for (int k = 0; k < f->K; ++k) fS[k] = cm * std::pow(f->eigvals[k], spread);
+        apply_impl(f, d_strokes + (size_t)m * H * W, H, W, fS.data(), 1, d_q + (size_t)m * f->n_local);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int nle_region_combine(nle_ctx* ctx, const float* d_layers, int L, const float* d_q, int M, long long n, long long layer_stride,
+                       long long q_stride, const double* h_weights, double floor, int out_kind, void* d_out) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_layers || !d_q || !h_weights || !d_out) throw Fail{NLE_ERR_INVALID, "nle_region_combine: NULL pointer"};
+        region_check_combine(L, M, floor, out_kind);
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_region_combine: n must be >= 1"};
+        if ((L > 1 && layer_stride < n) || (M > 1 && q_stride < n) || layer_stride < 0 || q_stride < 0)
+            throw Fail{NLE_ERR_INVALID, "nle_region_combine: a plane stride is smaller than n"};
+        region_combine_impl(ctx, d_layers, L, d_q, M, n, layer_stride, q_stride, h_weights, floor, out_kind, d_out);
+    });
+}
+
+int nle_region_spread(nle_filter* f, const float* d_strokes, int M, int H, int W, const double* h_scale, double spread,
+                      float* d_q) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        if (!d_strokes || !d_q) throw Fail{NLE_ERR_INVALID, "nle_region_spread: NULL pointer"};
+        region_check_spread(f, M, H, W, h_scale, spread);
+        region_spread_impl(f, d_strokes, M, H, W, h_scale, spread, d_q);
+    });
+}
+
+int nle_apply_regions(nle_filter* f, const float* d_x, int H, int W, int L, const float* d_strokes, int M,
+                      const double* h_scale, double spread, double floor, const double* h_weights, int out_kind, void* d_out) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        nle_ctx* c = f->ctx;
+        if (!d_x || !d_strokes || !h_weights || !d_out) throw Fail{NLE_ERR_INVALID, "nle_apply_regions: NULL pointer"};
+        region_check_combine(L, M, floor, out_kind);
+        region_check_spread(f, M, H, W, h_scale, spread);
+        const long long n = f->n_local;  // == H W: world == 1
+        DevBuf<float> d_work((size_t)(L + M) * n);
+        std::vector<double> resp((size_t)L * f->K);
+        layer_resp(f->eigvals.data(), f->K, L, resp.data());
+        apply_impl(f, d_x, H, W, resp.data(), L, d_work.p);  // nle_apply_layers
+        region_spread_impl(f, d_strokes, M, H, W, h_scale, spread, d_work.p + (size_t)L * n);
+        region_combine_impl(c, d_work.p, L, d_work.p + (size_t)L * n, M, n, n, n, h_weights, floor, out_kind, d_out);
+    });
+}
+
 int nle_bench_affinity(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
                        double hy, float* d_kab, int reps, double* h_avg_ms) {
     if (!ctx || !d_lum || !d_kab || reps < 1 || !h_avg_ms) return NLE_ERR_INVALID;

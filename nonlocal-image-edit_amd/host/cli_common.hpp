@@ -7,7 +7,10 @@
 // value; not with a non-zero radius or the farthest sampler) and, for enhance only, `--chroma HC` (chroma-aware affinities,
 // NLEFilter::chromaBandwidth: a finite number > 0; not with --exact or a radius above NLE_CHROMA_PATCH_RADIUS_MAX), in any order; reference command lines never start with
 // `--`, so they parse exactly as before.  An invalid value prints a message to stderr and exits with status 2 before
-// anything touches the GPU.
+// anything touches the GPU.  For enhance only, region edits (NLEFilter::enhanceRegions): `--region MASK:w1,w2,...`, up to
+// NLE_REGION_MAX times (split at the last `:`; MASK any image the readers decode, its first channel is the stroke; as many
+// weights as positional ones, which are the background's), `--region-spread T` and `--region-floor F` (finite, > 0; only
+// with a region).
 #pragma once
 
 #include <cmath>
@@ -32,13 +35,34 @@ struct FilterArgs {
     int sampler = NLE_SAMPLER_GRID;  // --sampler grid|farthest
     bool exact = false;              // --exact
     double chroma = 0;               // --chroma HC (enhance only)
+    // --region MASK:w1,w2,... (enhance only, repeatable), --region-spread T, --region-floor F
+    struct Region {
+        std::string mask;
+        std::vector<double> weights;
+    };
+    std::vector<Region> regions;
+    double regionSpread = 4, regionFloor = 0.05;
 };
+
+// a finite number > 0, or exit 2
+inline double positive_option(const char* prog, const std::string& opt, const std::string& v) {
+    char* end = nullptr;
+    const double x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+    if (v.empty() || *end != '\0' || !std::isfinite(x) || !(x > 0)) {
+        std::cerr << prog << ": " << opt << " takes a finite number > 0, got '" << v << "'" << std::endl;
+        std::exit(2);
+    }
+    return x;
+}
 
 // false (after printing the usage line to stderr) when fewer than `min_argc` arguments were given
 // allow_chroma: the tool takes `--chroma HC` (enhance); otherwise the option is refused (denoise estimates a and b)
-inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false) {
+// allow_regions: the tool takes the region options (enhance); otherwise they are refused (denoise has no layer weights)
+inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false,
+                  bool allow_regions = false) {
     std::vector<char*> shifted;
     int first = 1;  // the first argument after the leading options
+    bool spreadGiven = false, floorGiven = false;
     while (first < argc) {
         const std::string opt = argv[first];
         if (opt == "--exact") {
@@ -50,8 +74,50 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
             std::cerr << argv[0] << ": --exact takes no value, got '" << opt << "'" << std::endl;
             std::exit(2);
         }
-        if (opt != "--patch-radius" && opt != "--sampler" && opt != "--chroma") break;
+        const bool regionOpt = opt == "--region" || opt == "--region-spread" || opt == "--region-floor";
+        if (opt != "--patch-radius" && opt != "--sampler" && opt != "--chroma" && !regionOpt) break;
         const std::string v = first + 1 < argc ? argv[first + 1] : "";
+        if (regionOpt) {
+            if (!allow_regions) {
+                std::cerr << argv[0] << ": " << opt << " is not supported here: region edits give layer weights, which this "
+                          << "tool does not take" << std::endl;
+                std::exit(2);
+            }
+            if (opt == "--region-spread") {
+                a->regionSpread = positive_option(argv[0], opt, v);
+                spreadGiven = true;
+            } else if (opt == "--region-floor") {
+                a->regionFloor = positive_option(argv[0], opt, v);
+                floorGiven = true;
+            } else {
+                const size_t colon = v.rfind(':');
+                FilterArgs::Region r;
+                bool ok = colon != std::string::npos && colon > 0 && colon + 1 < v.size();
+                if (ok) {
+                    r.mask = v.substr(0, colon);
+                    const std::string list = v.substr(colon + 1) + ",";
+                    for (size_t p = 0, q; ok && (q = list.find(',', p)) != std::string::npos; p = q + 1) {
+                        const std::string w = list.substr(p, q - p);
+                        char* end = nullptr;
+                        const double x = w.empty() ? 0.0 : std::strtod(w.c_str(), &end);
+                        ok = !w.empty() && *end == '\0' && std::isfinite(x);
+                        r.weights.push_back(x);
+                    }
+                }
+                if (!ok) {
+                    std::cerr << argv[0] << ": --region takes MASK:w1,w2,... (an image and finite weights), got '" << v << "'"
+                              << std::endl;
+                    std::exit(2);
+                }
+                if ((int)a->regions.size() == NLE_REGION_MAX) {
+                    std::cerr << argv[0] << ": --region can be given at most " << NLE_REGION_MAX << " times" << std::endl;
+                    std::exit(2);
+                }
+                a->regions.push_back(r);
+            }
+            first += 2;
+            continue;
+        }
         if (opt == "--chroma") {
             if (!allow_chroma) {
                 std::cerr << argv[0] << ": --chroma is not supported here: the a and b planes are what this tool estimates"
@@ -94,6 +160,10 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
                   << NLE_CHROMA_PATCH_RADIUS_MAX << std::endl;
         std::exit(2);
     }
+    if ((spreadGiven || floorGiven) && a->regions.empty()) {
+        std::cerr << argv[0] << ": --region-spread and --region-floor need at least one --region" << std::endl;
+        std::exit(2);
+    }
     if (first > 1) {
         shifted.push_back(argv[0]);  // the rest parses as a reference command line
         for (int i = first; i < argc; ++i) shifted.push_back(argv[i]);
@@ -117,6 +187,19 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
         else *reals[i] = std::stod(argv[3 + i]);
     }
     for (int i = 9; i < argc; ++i) a->extra.push_back(std::stod(argv[i]));
+    if (!a->regions.empty()) {  // every region has the background's weight count
+        if ((int)a->extra.size() > NLE_REGION_LAYERS_MAX) {
+            std::cerr << argv[0] << ": --region takes at most " << NLE_REGION_LAYERS_MAX << " weights, got "
+                      << a->extra.size() << std::endl;
+            std::exit(2);
+        }
+        for (const auto& r : a->regions)
+            if (r.weights.size() != a->extra.size()) {
+                std::cerr << argv[0] << ": --region " << r.mask << " has " << r.weights.size() << " weights, the command line "
+                          << "has " << a->extra.size() << std::endl;
+                std::exit(2);
+            }
+    }
     return true;
 }
 

@@ -3,21 +3,49 @@
 //           <# eigen vectors> <weight 1> [<weight 2> ...]
 // Differences: runs headless (no imshow / waitKey, src/enhance.cpp:48-49), reads BMP/PPM and writes
 // BMP/PPM/PNG through nle/image_io.hpp instead of OpenCV.  The hot path runs on the GPU through
-// libnle_hip.so.
+// libnle_hip.so.  New here: leading options (cli_common.hpp), among them the region edits `--region MASK:w1,w2,...`
+// (repeatable), `--region-spread T`, `--region-floor F`: the positional weights are then the background's.
 #include "cli_common.hpp"
 
 int main(int argc, char* argv[]) {
     nlecli::FilterArgs a;
-    if (!nlecli::parse(argc, argv, 10, &a, /*allow_chroma=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
+    if (!nlecli::parse(argc, argv, 10, &a, /*allow_chroma=*/true, /*allow_regions=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
     const nle::Image image = nlecli::load(a);
     if (image.empty()) return 0;                        // src/enhance.cpp:34-37
+    // the strokes: the first channel of every mask, read before anything touches the GPU
+    std::vector<nle::Image> strokes;
+    std::vector<std::vector<double>> regionWeights;
+    for (const auto& r : a.regions) {
+        const nle::Image mask = nle::imread(r.mask);
+        if (mask.empty() || mask.rows != image.rows || mask.cols != image.cols) {
+            std::cerr << argv[0] << ": --region mask " << r.mask
+                      << (mask.empty() ? " cannot be read" : " does not have the image's size") << std::endl;
+            return 2;
+        }
+        nle::Image s(mask.rows, mask.cols, nle::NLE_8U, 1);
+        const int ch = mask.channels();
+        bool any = false;
+        for (size_t i = 0; i < mask.total(); ++i) {
+            s.ptr<unsigned char>()[i] = mask.ptr<unsigned char>()[i * ch];
+            any = any || s.ptr<unsigned char>()[i] >= 128;
+        }
+        if (!any) {
+            std::cerr << argv[0] << ": --region mask " << r.mask << " marks no pixel (no byte >= 128 in its first channel)"
+                      << std::endl;
+            return 2;
+        }
+        strokes.push_back(s);
+        regionWeights.push_back(r.weights);
+    }
     nle::NLEFilter filter;
     filter.patchRadius = a.patchRadius;
     filter.sampler = a.sampler;
     filter.exact = a.exact;
     filter.chromaBandwidth = a.chroma;
     filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
-    const nle::Image result = filter.enhance(image, a.extra);  // the weights are argv[9..]
+    const nle::Image result = strokes.empty() ? filter.enhance(image, a.extra)  // the weights are argv[9..]
+                                              : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,
+                                                                      a.regionFloor);
     nlecli::report(filter);
     return nlecli::finish(a, result, "Done. Press any key in result window to exit.");  // src/enhance.cpp:45
 }

@@ -909,6 +909,60 @@ Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights) 
     return out;
 }
 
+Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& strokes,
+                                 const std::vector<std::vector<DType>>& regionWeights, const std::vector<DType>& weights,
+                                 DType spread, DType floor) const {
+    if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enhance RGB image.");
+    if (!group_.empty())
+        throw std::runtime_error("Region edits run on one device: this filter was trained on a device group (NLE_DEVICES).");
+    long long n = 0;
+    if (f_) nle_filter_info(f_, &n, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (!f_ || (long long)image.total() != n)
+        throw std::runtime_error(
+            "Cannot apply filter on image with different size from the image filter was trained on.");
+    const int M = (int)strokes.size(), L = (int)weights.size();
+    if (M < 1 || M > NLE_REGION_MAX)
+        throw std::runtime_error("Region edits take 1 to " + std::to_string(NLE_REGION_MAX) + " strokes.");
+    if (L < 1 || L > NLE_REGION_LAYERS_MAX)
+        throw std::runtime_error("Region edits take 1 to " + std::to_string(NLE_REGION_LAYERS_MAX) + " weights.");
+    if ((int)regionWeights.size() != M) throw std::runtime_error("Region edits need one weight vector per stroke.");
+    const size_t np = image.total();
+    // Wt: row 0 the background, row m region m; the stroke planes as 0 / 1 and their scales c_m = N / sum s_m
+    std::vector<double> Wt(weights), scale((size_t)M);
+    std::vector<float> planes((size_t)M * np);
+    for (int m = 0; m < M; ++m) {
+        if ((int)regionWeights[m].size() != L)
+            throw std::runtime_error("Region " + std::to_string(m + 1) + " has " + std::to_string(regionWeights[m].size()) +
+                                     " weights, the background has " + std::to_string(L) + ".");
+        Wt.insert(Wt.end(), regionWeights[m].begin(), regionWeights[m].end());
+        const Image& s = strokes[m];
+        if (s.channels() != 1 || s.depth() != NLE_8U || s.rows != image.rows || s.cols != image.cols)
+            throw std::runtime_error("Stroke " + std::to_string(m + 1) + " must be a one-channel 8-bit image of the image's size.");
+        const unsigned char* b = s.ptr<unsigned char>();
+        double sum = 0.0;
+        for (size_t i = 0; i < np; ++i) {
+            const float v = b[i] >= 128 ? 1.f : 0.f;
+            planes[(size_t)m * np + i] = v;
+            sum += v;
+        }
+        if (!(sum > 0)) throw std::runtime_error("Stroke " + std::to_string(m + 1) + " is empty (no byte >= 128).");
+        scale[m] = (double)np / sum;
+    }
+    // enhance's body (:422-440 on the device) with nle_apply_regions in place of nle_apply_rounded8
+    Dev d_bgr(ctx_, np * 3), d_lab(ctx_, np * 3), d_L(ctx_, np * 4), d_y(ctx_, np * 4), d_s(ctx_, planes.size() * 4);
+    check(nle_dev_upload(ctx_, d_bgr.p, image.ptr<unsigned char>(), np * 3), ctx_);
+    check(nle_dev_upload(ctx_, d_s.p, planes.data(), planes.size() * 4), ctx_);
+    check(nle_bgr2lab8(ctx_, static_cast<unsigned char*>(d_bgr.p), (long long)np, static_cast<unsigned char*>(d_lab.p),
+                       d_L.f()), ctx_);
+    check(nle_apply_regions(f_, d_L.f(), image.rows, image.cols, L, d_s.f(), M, scale.data(), spread, floor, Wt.data(),
+                            NLE_REGION_OUT_ROUNDED8, d_y.f()), ctx_);
+    check(nle_lab2bgr8(ctx_, static_cast<unsigned char*>(d_lab.p), d_y.f(), (long long)np,
+                       static_cast<unsigned char*>(d_bgr.p)), ctx_);
+    Image out(image.rows, image.cols, NLE_8U, 3);
+    check(nle_dev_download(ctx_, out.ptr<unsigned char>(), d_bgr.p, np * 3), ctx_);
+    return out;
+}
+
 Vec NLEFilter::eigvals() const {
     if (!f_) return Vec();
     int K = 0;
