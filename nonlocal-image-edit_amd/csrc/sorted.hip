@@ -698,6 +698,8 @@ static int sorted_grid(int nrows) {
 // Where the recurrence of column_factors stays inside the normal range of fp64 (with a wide margin): every e_b =
 // exp(-(u - b cs)^2 / hx^2) and every ratio rho_b = exp((2 cs u - (2 b + 1) cs^2) / hx^2), u = c - cb0, c = 0 .. W-1.
 // Narrow kernels (W / hx beyond ~20) keep the table form.  *kappa = exp(-2 cs^2 / hx^2).
+// m_rho never binds before m_e where there are two columns or more: (umax + nC cs)^2 >= 2 cs umax + (2 nC + 1) cs^2 for
+// nC >= 2.  The check stays: it is the condition on rho_b, stated where rho_b is used.
 bool sorted_recurrence(GridSpec gs, double hx, double* kappa) {
     const double cs = gs.colStep, umax = std::max<double>(gs.colOff, gs.W - 1 - gs.colOff), nC = gs.nSelCols;
     const double span = umax + nC * cs;  // |u - b cs| <= span
