@@ -56,7 +56,10 @@ void nle_ctx_destroy(nle_ctx* ctx) {
     for (auto e : ctx->prof_pool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->own_comm && !ctx->comm_aborted.load()) (void)rccl().CommDestroy(ctx->comm);
-    for (auto* f : ctx->filters) f->ctx = nullptr;  // their V is freed directly when they are destroyed
+    for (auto* f : ctx->filters) {  // orphaned: the table state goes to the cache freed below, V is freed on destroy
+        f->tables.reset();
+        f->ctx = nullptr;
+    }
     if (ctx->d_lut) (void)hipFree(ctx->d_lut);
     for (auto e : ctx->copy_ev)
         if (e) (void)hipEventDestroy(e);

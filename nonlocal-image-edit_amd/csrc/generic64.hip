@@ -1,6 +1,6 @@
 // The literal decomposition of the hot path with every N-sized matrix in fp64 (gfx950).
 //
-// Why it exists.  The table formulation (fused.hip / sorted.hip) is all-fp64 but needs an integer-valued luminance plane
+// Why it exists.  The table formulation (tables.hip / sorted.hip) is all-fp64 but needs an integer-valued luminance plane
 // and a sample grid of at most 32 x 36; the fp32 formulations (kernels.hip: Phi, V and the affinities in fp32) miss the
 // 1e-4 per-layer bar on some well-posed inputs (profiles/r1_parity_fuzz.txt: detail layers that are small differences
 // 1 - lambda at spatial bandwidths of a few pixels).  This file is what auto mode falls back to for any other input

@@ -25,6 +25,9 @@ __device__ __forceinline__ float affinity_value(float pr, float pc, float px, Sa
     const float dr = pr - s.x, dc = pc - s.y, dv = px - s.z;
     return __builtin_amdgcn_exp2f(nsw * (dr * dr + dc * dc) + npw * (dv * dv));
 }
+__device__ __forceinline__ double recip_or_zero_d(double s, double eps) {
+    return (fabs(s) >= eps) ? 1.0 / s : 0.0;  // inplaceReciprocal, src/filter.cpp:42-54
+}
 // closed form of the selection predicate of samplePixels (src/filter.cpp:68-70)
 __device__ __forceinline__ bool is_sample_pixel(const GridSpec& gs, int row, int col) {
     const int dr = row - gs.rowOff, dc = col - gs.colOff;
@@ -139,7 +142,12 @@ hipError_t project64(hipStream_t s, const float* d_lum, GridSpec gs, const Sampl
                      float npw, long long pix0, long long M, const double* d_D, int K, const double* d_c, float* d_V,
                      int ldv);
 
-// ---- quantised-luminance (integer 0..255) Sinkhorn pass: table look-ups instead of exponentials ----
+// ---- the table formulation (tables.hip, sorted.hip): quantised luminance (integer 0..255) on a Cartesian sample grid --
+// table look-ups instead of exponentials.  Its limits, stated once: a grid of at most 32 x 36 samples (LDS and registers of
+// the k_hist_* / k_ghist_* / k_sorted_* kernels) and at most 128 eigenvectors (project64, when V is asked for).
+inline bool tables_apply(GridSpec gs, int K = 1) {
+    return gs.nSelRows >= 1 && gs.nSelRows <= 32 && gs.nSelCols >= 1 && gs.nSelCols <= 36 && K <= 128;
+}
 hipError_t check_levels(hipStream_t s, const float* d_lum, long long n, int* d_flag);  // 2 ints: [0] != 0: not quantised, [1]: 16-level tiles that occur (bit t)
 hipError_t hist_tables(hipStream_t s, GridSpec gs, const Sample4* d_samples, int p, double hx, double hy, int row0,
                        int nrows_local, double* d_er, double* d_ecT, double* d_Ep);
@@ -265,62 +273,56 @@ struct SortedRows {
     int lev_t0 = 0, lev_nt = 16;  // the 16-level tiles [lev_t0, lev_t0 + lev_nt) that occur in the image (check_levels)
     bool mom = false;             // the pass kernel's pixel loop in its moment form (sorted_moments_ok)
 };
+// What the composite launchers below take: the table path's state on one rank, rows [row0, row0 + nrows) of the image;
+// non-owning (pipeline_internal.h: TableFilter owns it)
+struct TableView {
+    const float* lum;              // virtual base of the full image: only this rank's rows are ever dereferenced
+    GridSpec gs;
+    int p, ldp;                    // samples; ldp = sink_pass_ld(p), the stride of the p-sized vectors
+    int row0, nrows;
+    const double *er, *ecT, *Ep;   // hist_tables
+    const double* cvec;            // c_i per local pixel (0 at sample pixels): the last Sinkhorn pass writes it
+    const SortedRows* sorted;      // null: the pixel kernels are the LDS-atomic ones (k_hist_pix, k_hist_dot, k_ghist_rows*)
+};
+
 // Gram by index sums (sorted.hip: k_sorted_gsum): S_r[t][x] = sum c_i^2 G_t(col_i), t < 2 nC - 1; layout [row][t][level]
 bool sorted_gsum_ok(GridSpec gs, double hx);
-hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows_local, const unsigned short* d_scol, const uint2* d_desc,
-                            const unsigned short* d_first, const double* d_E2, const double* d_cvec, double* d_Aout, double hx);
+hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows, const SortedRows& sr, const double* d_cvec, double* d_Aout);
 bool sorted_recurrence(GridSpec gs, double hx, double* kappa);
 int sorted_max_width();
 size_t sorted_scol_elems(int W, int nrows_local);  // allocation size of SortedRows::scol
-int sorted_gram_max_cols();
 // expand half of the sample-space apply on the sorted rows (nl <= sorted_expand_layers() layers per launch)
-int sorted_expand_max_cols();
-int sorted_expand_max_width();
 int sorted_expand_layers(GridSpec gs);
-hipError_t sorted_expand(hipStream_t s, GridSpec gs, int nrows_local, const unsigned short* d_scol, const uint2* d_desc,
-                         const double* d_E, const double* d_g, size_t gstride, int nl, const double* d_cvec, float* d_out,
-                         long long ostride, bool rec = false, double kappa = 0.0, bool round8 = false);
+hipError_t sorted_expand(hipStream_t s, GridSpec gs, int nrows, const SortedRows& sr, const double* d_g, size_t gstride, int nl,
+                         const double* d_cvec, float* d_out, long long ostride, bool round8);
 hipError_t dist_table(hipStream_t s, int W, double hx, double* d_E);
 hipError_t sort_rows(hipStream_t s, const float* d_lum, GridSpec gs, int row0, int nrows_local, unsigned short* d_scol,
                      uint2* d_desc, unsigned short* d_first);
-hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows_local, const unsigned short* d_scol,
-                       const uint2* d_desc, const unsigned short* d_first, const double* d_E, const double* d_g, double eps,
-                       double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec, bool rec, double kappa,
-                       int lev_t0 = 0, int lev_nt = 16,   // table columns of the level tiles [lev_t0, +lev_nt) only
-                       bool mom = false);                 // the moment form of the pixel loop (sorted_moments_ok)
+// the table columns of sr's level tiles only; the pixel loop in the form sr.mom / sr.rec say
+hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows, const SortedRows& sr, const double* d_g,
+                       double eps, double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec);
 bool sorted_moments_ok(GridSpec gs, double hx);
-hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows_local, const unsigned short* d_scol, const uint2* d_desc,
-                            const unsigned short* d_first, const double* d_E, const double* d_cvec, double* d_Aout, bool rec,
-                            double kappa);
+hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows, const SortedRows& sr, const double* d_cvec, double* d_Aout);
 
-// the table pass (three kernels, Ep read once per pass; nSelCols <= 36, nSelRows <= 32); writes the full column sums to d_z
+// the table pass (three kernels, Ep read once per pass); writes the full column sums to d_z.  d_ybuf (optional): y_i per
+// local pixel; mode XVEC (apply, reduce half): y_i = cvec_i * xvec_i
 size_t hist_tiled_workspace_elems(GridSpec gs, int nrows_local);
-hipError_t sink_hist_tiled(hipStream_t s, int mode, const float* d_lum, GridSpec gs, int p, int ldp, int row0,
-                           int nrows_local, const double* d_er, const double* d_ecT, const double* d_Ep,
-                           const double* d_w, double eps, double* d_ybuf, double* d_ws, double* d_z,
-                           LaunchObserver* obs = nullptr, const double* d_cvec = nullptr,
-                           const float* d_xvec = nullptr,   // mode XVEC: y_i = cvec_i * xvec_i (apply, reduce half)
-                           const SortedRows* sorted = nullptr);  // given: the pixel kernel runs on the level-sorted rows
-// sample-space apply (tables): expand half for one layer, the p/K-sized middle, and the sample-pixel outputs
-int apply_layers_per_launch(GridSpec gs);
-// use_sorted_expand: the pixel kernel runs on the level-sorted rows (sorted_expand, sorted_expand_layers per launch)
-bool use_sorted_expand(GridSpec gs, const SortedRows* sorted);
-hipError_t apply_hist_layers(hipStream_t s, const float* d_lum, GridSpec gs, int p, int row0, int nrows_local,
-                             const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_wl, int ldw,
-                             int nl, const double* d_c, double* d_ws, float* d_out, long long ostride,
-                             LaunchObserver* obs, const SortedRows* sorted = nullptr, bool round8 = false);
+hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const double* d_w, double eps, double* d_ybuf,
+                           double* d_ws, double* d_z, LaunchObserver* obs = nullptr, const float* d_xvec = nullptr);
+// sample-space apply (tables): expand half for nl <= apply_layers_per_launch(v) layers (decided there and nowhere else), the
+// p/K-sized middle, and the sample-pixel outputs
+int apply_layers_per_launch(const TableView& v);
+hipError_t apply_hist_layers(hipStream_t s, const TableView& v, const double* d_wl, int ldw, int nl, double* d_ws, float* d_out,
+                             long long ostride, LaunchObserver* obs, bool round8 = false);
 hipError_t apply_small(hipStream_t s, int p, int K, int ldk, int L, int ldw, const double* d_m, const double* d_D,
                        const double* d_Vrows, const double* d_xA /* x at the p sample pixels */, const double* d_resp,
                        double* d_t, double* d_Wp, double* d_YA);
 hipError_t scatter_samples(hipStream_t s, int p, int L, const long long* d_loc, const double* d_YA, float* d_Y,
                            long long ystride, bool round8 = false);  // round8: clamp to [0, 255], round half to even, in fp64
 
-// Gram in sample space through the same tables (quantised luminance, nSelCols <= ghist_max_cols())
-int ghist_max_cols();
+// Gram in sample space through the same tables; d_Gk: p x p
 size_t ghist_workspace_elems(GridSpec gs, int nrows_local);
-hipError_t gram_hist(hipStream_t s, const float* d_lum, GridSpec gs, int p, int row0, int nrows_local,
-                     const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_c, double* d_ws,
-                     double* d_Gk, LaunchObserver* obs = nullptr, const SortedRows* sorted = nullptr);
+hipError_t gram_hist(hipStream_t s, const TableView& v, double* d_ws, double* d_Gk, LaunchObserver* obs = nullptr);
 
 // 8-bit BGR <-> Lab (colour.hip): d_lut = the fixed-point tables of nle_lab8_tables as one blob; d_lab / d_L optional outputs
 hipError_t bgr2lab8(hipStream_t s, const unsigned char* d_bgr, long long n, const double* d_lut, unsigned char* d_lab,

@@ -266,7 +266,7 @@ std::vector<double> gram_all(nle_ctx* c, const float* d_phi, long long M, int ld
     return unpack_tiles(tiles, ld, r, 32);
 }
 
-// ---- the train paths; each fills f->K, ldv, eigvals and d_V or d_V64 (or the lazy form) ----
+// ---- the train paths; each fills f->K, ldv, eigvals and d_V or d_V64 (or the table form, f->tables) ----
 struct StageMs {
     double sinkhorn = 0, gram = 0, project = 0, host = 0, host_overlapped = 0;
     void take(Timer& s, Timer& g, Timer& p) {
@@ -488,11 +488,162 @@ struct SampleSinkhorn {
     }
 };
 
-// (2) Phi-free: every N-sized pass regenerates its affinity rows (fused.hip)
-void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss,
+// The host route of the sample-space orthogonalisation, the part that does not need the Gram under the Gram kernels.  The
+// fp32 Phi-free form always takes it, the table form with the opt-in Lanczos solver: that one works on the LITERAL q x q
+// matrix Q = Wa + S (Wab Wab^T) S with Wa as computed, not mirrored from its lower triangle -- what Spectra's
+// DenseGenMatProd multiplies by in a USE_SPECTRA build, src/filter.cpp:174, 311 -- which the host forms exactly; the device
+// route diagonalises a symmetric similar matrix.  d_G: what enqueue_gram fills, 16 x 16 upper tiles (gram64) or p x p.
+OrthoSS ortho_ss_host(nle_ctx* c, const Nystrom& ny, int p, const SampleSinkhorn& sk, const std::function<void()>& enqueue_gram,
+                      double* d_G, size_t g_elems, bool tile16, int n_eig, Timer& tm_g, StageMs* ms, Trace& tr) {
+    OrthoSS o;
+    enqueue_gram();
+    double h0 = now_ms();
+    ortho_ss_prepare(o, ny, p, sk.sA_c, sk.sA_r, /*literal_q=*/c->topk_solver != 0);  // host, while the Gram kernel runs
+    const double h_overlapped = now_ms() - h0;
+    tr.mark("ss: ortho prepare (host)");
+    // (a device-to-host copy into pageable memory blocks the host until the stream reaches it, so it
+    // is issued only now)
+    all_reduce(c, d_G, g_elems);
+    std::vector<double> tiles(g_elems);
+    HIP_OK(hipMemcpyAsync(tiles.data(), d_G, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    tm_g.stop();
+    HIP_OK(hipStreamSynchronize(c->stream));
+    tr.mark("ss: gram sync");
+    h0 = now_ms();
+    ortho_ss_finish(o, tile16 ? unpack_tiles(tiles, nlek::gram64_ld(p), p, 16) : std::move(tiles), n_eig, c->topk_solver);
+    ms->host += now_ms() - h0;
+    tr.mark("ss: ortho finish (host)");
+    ms->host_overlapped += h_overlapped;
+    return o;
+}
+
+// X (p x K column-major on the host) as the p x ldd row-major, zero-padded operand of project64 / k_apply_small
+std::vector<double> padded_rows(const std::vector<double>& X, int p, int K, int ldd) {
+    std::vector<double> R((size_t)p * ldd, 0.0);
+    for (int k = 0; k < K; ++k)
+        for (int a = 0; a < p; ++a) R[(size_t)a * ldd + k] = X[(size_t)k * p + a];
+    return R;
+}
+
+}  // namespace
+
+// quantised luminance + Cartesian sample grid: table look-ups replace the exponentials (tables.hip), and the pixel halves of
+// every table pass run on level-sorted rows, without LDS atomics (sorted.hip; sorted once here).  d_lum: virtual full base.
+nlep::TableFilter::TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet& ss, double hx, double hy, int row0_, int nrows_)
+    : gs(ss.gs), p(ss.p), P64(nlek::sink_pass_ld(ss.p)), row0(row0_), nrows(nrows_), nsw(nsw_of(hx)), npw(nsw_of(hy)),
+      lum(d_lum), samples(upload_samples(ctx, ss, nlek::sink_pass_ld(ss.p))), c((size_t)nrows_ * ss.gs.W),
+      er((size_t)nrows_ * ss.gs.nSelRows), ecT((size_t)ss.gs.nSelCols * ss.gs.W), Ep((size_t)256 * ss.p) {
+    PROFILED(ctx, NLE_K_SMALL, nlek::hist_tables(ctx->stream, gs, samples.p, p, hx, hy, row0, nrows, er.p, ecT.p, Ep.p));
+    if (gs.W > nlek::sorted_max_width() || std::getenv("NLE_NO_SORTED_ROWS") != nullptr) return;
+    scol.alloc(nlek::sorted_scol_elems(gs.W, nrows));  // k_sort_rows writes every entry a pass reads
+    first.alloc((size_t)nrows * 258);
+    desc.alloc((size_t)nrows * nlek::kSortedThreads);
+    E.alloc((size_t)gs.W + 1);
+    PROFILED(ctx, NLE_K_SMALL, nlek::dist_table(ctx->stream, gs.W, hx, E.p));
+    PROFILED(ctx, NLE_K_SMALL, nlek::sort_rows(ctx->stream, d_lum, gs, row0, nrows, scol.p, desc.p, first.p));
+    HIP_OK(hipMemsetAsync(c.p, 0, c.n * sizeof(double), ctx->stream));  // sample pixels are never visited
+    sorted = nlek::SortedRows{scol.p, desc.p, first.p, E.p, false, 0.0};
+    sorted.rec = nlek::sorted_recurrence(gs, hx, &sorted.kappa);
+    sorted.mom = nlek::sorted_moments_ok(gs, hx);
+    if (std::getenv("NLE_ALL_LEVEL_TILES") == nullptr) {  // the tables' columns of level tiles that do not occur are skipped
+        int t0 = 0, t1 = 16;
+        while (t0 < 15 && !((ss.level_tiles >> t0) & 1u)) ++t0;
+        while (t1 > t0 + 1 && !((ss.level_tiles >> (t1 - 1)) & 1u)) --t1;
+        sorted.lev_t0 = t0;
+        sorted.lev_nt = t1 - t0;
+    }
+    if (nlek::sorted_gsum_ok(gs, hx)) {  // the Gram on index sums: one more distance table, exp(-2 d^2 / hx^2)
+        E2.alloc((size_t)gs.W + 1);
+        PROFILED(ctx, NLE_K_SMALL, nlek::dist_table(ctx->stream, gs.W, hx / std::sqrt(2.0), E2.p));
+        sorted.E2 = E2.p;
+        sorted.hx = hx;
+    }
+}
+
+namespace {
+
+// (2) the table formulation: every N-sized pass works on look-up tables of the quantised plane; V
+// stays implicit (TableFilter)
+void train_tables(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss, const std::function<Nystrom()>& solve,
+                  double hx, double hy, int T, int n_eig, long long pix0, long long M, StageMs* ms) {
+    const int p = ss.p;
+    Trace tr;
+    Timer tm_s(c->stream), tm_g(c->stream), tm_p(c->stream);
+    tm_s.start();
+    auto t = std::make_unique<TableFilter>(c, d_lum, ss, hx, hy, (int)(pix0 / ss.gs.W), (int)(M / ss.gs.W));
+    const nlek::TableView view = t->view();
+    DevBuf<double> d_z(t->P64), d_hws(nlek::hist_tiled_workspace_elems(ss.gs, t->nrows));
+    SampleSinkhorn sk(c, p, t->P64, T);
+    tr.mark("ss: alloc+upload");
+    auto pass_pixels = [&](int mode, bool last) {  // the N-sized half: the local column sums, straight into d_z
+        static const int kmap[4] = {NLE_K_SINK_TABLES, NLE_K_SINKHORN_PASS, NLE_K_REDUCE, NLE_K_REDUCE};
+        ProfObserver obs(c, kmap);
+        HIP_OK(nlek::sink_hist_tiled(c->stream, mode, view, sk.d_w.p, NLE_EPS, last ? t->c.p : nullptr, d_hws.p, d_z.p, &obs));
+    };
+    const Nystrom ny = sk.run(solve, pass_pixels, d_z.p, 1);
+    f->r = ny.r;
+    f->chol_ka = ny.chol ? 1 : 0;
+    f->formulation = NLE_MODE_PHI_FREE;
+    tm_s.stop();
+    tr.mark("ss: passes enqueued");
+    HIP_OK(hipStreamSynchronize(c->stream));
+    tr.mark("ss: sinkhorn sync");
+
+    // Gram in sample space: histogram + fp64 GEMM over the look-up tables (k_ghist_*), enqueued; the host half that does
+    // not need it runs meanwhile
+    tm_g.start();
+    const size_t g_elems = (size_t)p * p;
+    DevBuf<double> d_gpart, d_G(g_elems);
+    auto enqueue_gram = [&] {
+        d_gpart.alloc(nlek::ghist_workspace_elems(ss.gs, t->nrows));
+        static const int gmap[4] = {NLE_K_GRAM_ROWS, NLE_K_SMALL, NLE_K_GRAM_GEMM, NLE_K_SMALL};
+        ProfObserver obs(c, gmap);
+        HIP_OK(nlek::gram_hist(c->stream, view, d_gpart.p, d_G.p, &obs));
+    };
+    OrthoSS o;
+    if (c->topk_solver == 0) {
+        // the q-sized products run on the device, the eigensolves on the host
+        ortho_ss_device(c, o, ny, p, sk.sA_c, sk.sA_r, d_G.p, n_eig, enqueue_gram, [&] { all_reduce(c, d_G.p, g_elems); },
+                        &ms->host, &ms->host_overlapped, tr);
+        tm_g.stop();
+    } else {
+        o = ortho_ss_host(c, ny, p, sk, enqueue_gram, d_G.p, g_elems, /*tile16=*/false, n_eig, tm_g, ms, tr);
+    }
+    adopt_ortho(f, o);
+
+    // keep what defines V = diag(c) K_AB^T D implicitly (K' <= 128: tables_apply); the projection runs only if somebody asks
+    tm_p.start();
+    t->ldd = nlek::project64_ld(o.K);
+    const std::vector<double> Dp = padded_rows(o.D, p, o.K, t->ldd), Vr = padded_rows(o.Vrows, p, o.K, t->ldd);
+    std::vector<long long> sloc(p);
+    for (int a = 0; a < p; ++a) {
+        const long long loc = ss.pix[a] - pix0;
+        sloc[a] = (loc >= 0 && loc < M) ? loc : -1;
+    }
+    t->D.alloc(Dp.size());
+    HIP_OK(hipMemcpyAsync(t->D.p, Dp.data(), Dp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    t->Vrows.alloc(Vr.size());
+    t->sample_loc.alloc(p);
+    t->slab.alloc((size_t)M);
+    HIP_OK(hipMemcpyAsync(t->Vrows.p, Vr.data(), Vr.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(t->sample_loc.p, sloc.data(), p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(t->slab.p, d_lum + pix0, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));  // the host staging vectors go out of scope
+    t->lum = t->slab.p - pix0;  // the caller's plane is not ours to keep
+    t->drop_gram_only();
+    f->tables = std::move(t);
+    f->h_Vrows = o.Vrows;
+    tm_p.stop();
+    ms->take(tm_s, tm_g, tm_p);
+}
+
+// (2b) Phi-free with fp32 affinities (NLE_MODE_PHI_FREE on a plane that is not integer valued, NLE_MODE_PHI_FREE_EXP): every
+// N-sized pass regenerates its affinity rows (fused.hip)
+void train_phi_free_exp(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss,
                         const std::function<Nystrom()>& solve, double hx, double hy, int T, int n_eig, long long pix0,
                         long long M, StageMs* ms) {
     const int p = ss.p;
+    if (p > nlek::sink_pass_max_p()) throw Fail{NLE_ERR_INVALID, "Phi-free path: too many samples for the generic kernels"};
     const int P64 = nlek::sink_pass_ld(p);
     const float nsw = nsw_of(hx), npw = nsw_of(hy);
     Trace tr;
@@ -502,200 +653,44 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
     // w entries are zero, so they only have to be finite)
     DevBuf<float4> d_samples = upload_samples(c, ss, P64);
     constexpr int kZS = 8;  // slices of the block partials, summed by k_sink_update
-    const int npart = nlek::sink_pass_rows(std::max<long long>(M, 1));
-    DevBuf<double> d_z((size_t)kZS * P64), d_partial, d_cbuf((size_t)std::max<long long>(M, 1));
-    // quantised luminance + Cartesian sample grid: table look-ups replace the exponentials (fused.hip)
-    const bool hist = ss.quantised && c->mode != NLE_MODE_PHI_FREE_EXP && ss.gs.nSelCols <= nlek::ghist_max_cols() &&
-                      ss.gs.nSelRows <= 32 && M > 0;
-    if (!hist && p > nlek::sink_pass_max_p()) throw Fail{NLE_ERR_INVALID, "Phi-free path: too many samples for the generic kernels"};
-    const int nrows_local = (int)(M / ss.gs.W), row0 = (int)(pix0 / ss.gs.W);
-    DevBuf<double> d_er, d_ecT, d_Ep, d_hws;
-    if (hist) {
-        d_er.alloc((size_t)nrows_local * ss.gs.nSelRows);
-        d_ecT.alloc((size_t)ss.gs.nSelCols * ss.gs.W);
-        d_Ep.alloc((size_t)256 * p);
-        d_hws.alloc(nlek::hist_tiled_workspace_elems(ss.gs, nrows_local));
-        PROFILED(c, NLE_K_SMALL, nlek::hist_tables(c->stream, ss.gs, d_samples.p, p, hx, hy, row0, nrows_local, d_er.p,
-                                                   d_ecT.p, d_Ep.p));
-    } else {
-        d_partial.alloc((size_t)npart * P64);
-    }
+    const int npart = nlek::sink_pass_rows(M);  // M > 0: every rank owns an image row (train_impl)
+    DevBuf<double> d_z((size_t)kZS * P64), d_partial((size_t)npart * P64), d_cbuf((size_t)M);
     SampleSinkhorn sk(c, p, P64, T);
-    // level-sorted rows: the pixel halves of every table pass run without LDS atomics (sorted.hip); sorted once here
-    const bool sorted = hist && ss.gs.W <= nlek::sorted_max_width() && std::getenv("NLE_NO_SORTED_ROWS") == nullptr;
-    DevBuf<unsigned short> d_scol, d_first;
-    DevBuf<uint2> d_desc;
-    DevBuf<double> d_E, d_E2;
-    nlek::SortedRows sr{};
-    if (sorted) {
-        d_scol.alloc(nlek::sorted_scol_elems(ss.gs.W, nrows_local));  // k_sort_rows writes every entry a pass reads
-        d_first.alloc((size_t)nrows_local * 258);
-        d_desc.alloc((size_t)nrows_local * nlek::kSortedThreads);
-        d_E.alloc((size_t)ss.gs.W + 1);
-        PROFILED(c, NLE_K_SMALL, nlek::dist_table(c->stream, ss.gs.W, hx, d_E.p));
-        PROFILED(c, NLE_K_SMALL, nlek::sort_rows(c->stream, d_lum, ss.gs, row0, nrows_local, d_scol.p, d_desc.p, d_first.p));
-        HIP_OK(hipMemsetAsync(d_cbuf.p, 0, d_cbuf.n * sizeof(double), c->stream));  // sample pixels are never visited
-        sr = nlek::SortedRows{d_scol.p, d_desc.p, d_first.p, d_E.p, false, 0.0};
-        sr.rec = nlek::sorted_recurrence(ss.gs, hx, &sr.kappa);
-        sr.mom = nlek::sorted_moments_ok(ss.gs, hx);
-        if (std::getenv("NLE_ALL_LEVEL_TILES") == nullptr) {  // the tables' columns of level tiles that do not occur are skipped
-            int t0 = 0, t1 = 16;
-            while (t0 < 15 && !((ss.level_tiles >> t0) & 1u)) ++t0;
-            while (t1 > t0 + 1 && !((ss.level_tiles >> (t1 - 1)) & 1u)) --t1;
-            sr.lev_t0 = t0;
-            sr.lev_nt = t1 - t0;
-        }
-        if (nlek::sorted_gsum_ok(ss.gs, hx)) {  // the Gram on index sums: one more distance table, exp(-2 d^2 / hx^2)
-            d_E2.alloc((size_t)ss.gs.W + 1);
-            PROFILED(c, NLE_K_SMALL, nlek::dist_table(c->stream, ss.gs.W, hx / std::sqrt(2.0), d_E2.p));
-            sr.E2 = d_E2.p;
-            sr.hx = hx;
-        }
-    }
-    const nlek::SortedRows* srp = sorted ? &sr : nullptr;
     tr.mark("ss: alloc+upload");
     auto pass_pixels = [&](int mode, bool last) {  // the N-sized half: z = sum over this rank's pixels
-        double* ybuf = last ? d_cbuf.p : nullptr;
-        if (hist) {
-            // tiled table pass: writes the local column sums straight into slice 0 of d_z
-            static const int kmap[4] = {NLE_K_SINK_TABLES, NLE_K_SINKHORN_PASS, NLE_K_REDUCE, NLE_K_REDUCE};
-            ProfObserver obs(c, kmap);
-            HIP_OK(nlek::sink_hist_tiled(c->stream, mode, d_lum, ss.gs, p, P64, row0, nrows_local, d_er.p, d_ecT.p,
-                                         d_Ep.p, sk.d_w.p, NLE_EPS, ybuf, d_hws.p, d_z.p, &obs, nullptr, nullptr, srp));
-        } else if (M > 0) {
-            PROFILED(c, NLE_K_SINKHORN_PASS, nlek::sink_pass(c->stream, mode, d_lum, ss.gs, d_samples.p, p, sk.d_w.p, nsw,
-                                                             npw, pix0, M, NLE_EPS, ybuf, d_partial.p));
-            PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(c->stream, d_partial.p, npart, P64, d_z.p, kZS));
-        } else {
-            HIP_OK(hipMemsetAsync(d_z.p, 0, (size_t)kZS * P64 * sizeof(double), c->stream));
-        }
+        PROFILED(c, NLE_K_SINKHORN_PASS, nlek::sink_pass(c->stream, mode, d_lum, ss.gs, d_samples.p, p, sk.d_w.p, nsw, npw, pix0,
+                                                         M, NLE_EPS, last ? d_cbuf.p : nullptr, d_partial.p));
+        PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(c->stream, d_partial.p, npart, P64, d_z.p, kZS));
     };
-    const Nystrom ny = sk.run(solve, pass_pixels, d_z.p, hist ? 1 : kZS);
+    const Nystrom ny = sk.run(solve, pass_pixels, d_z.p, kZS);
     f->r = ny.r;
     f->chol_ka = ny.chol ? 1 : 0;
-    f->formulation = hist ? NLE_MODE_PHI_FREE : NLE_MODE_PHI_FREE_EXP;
+    f->formulation = NLE_MODE_PHI_FREE_EXP;
     tm_s.stop();
     tr.mark("ss: passes enqueued");
     HIP_OK(hipStreamSynchronize(c->stream));
     tr.mark("ss: sinkhorn sync");
 
-    // Gram in sample space, enqueued; the host half that does not need it runs meanwhile.
-    // Quantised luminance: histogram + fp64 GEMM over the look-up tables (k_ghist_*); otherwise
-    // regenerated affinity rows on the fp64 MFMA (k_gram64).
+    // Gram in sample space on regenerated affinity rows (k_gram64, fp64 MFMA), enqueued; the host half that does not need
+    // it runs meanwhile
     tm_g.start();
-    const int ntiles = nlek::gram64_num_tiles(p);
-    const size_t g_elems = hist ? (size_t)p * p : (size_t)ntiles * 256;
-    DevBuf<double> d_gpart, d_tiles(g_elems);
-    auto enqueue_gram = [&] {
-        if (M <= 0) {
-            HIP_OK(hipMemsetAsync(d_tiles.p, 0, g_elems * sizeof(double), c->stream));
-        } else if (hist) {
-            d_gpart.alloc(nlek::ghist_workspace_elems(ss.gs, nrows_local));
-            static const int gmap[4] = {NLE_K_GRAM_ROWS, NLE_K_SMALL, NLE_K_GRAM_GEMM, NLE_K_SMALL};
-            ProfObserver obs(c, gmap);
-            HIP_OK(nlek::gram_hist(c->stream, d_lum, ss.gs, p, row0, nrows_local, d_er.p, d_ecT.p, d_Ep.p, d_cbuf.p,
-                                   d_gpart.p, d_tiles.p, &obs, srp));
-        } else {
-            d_gpart.alloc(std::max<size_t>(nlek::gram64_partial_elems(M, p), 1));
-            PROFILED(c, NLE_K_GRAM, nlek::gram64(c->stream, d_lum, ss.gs, d_samples.p, p, nsw, npw, pix0, M, d_cbuf.p,
-                                                 d_gpart.p, d_tiles.p));
-        }
-    };
-    OrthoSS o;
-    // (the opt-in Lanczos solver works on the LITERAL q x q matrix Q = Wa + S (Wab Wab^T) S with Wa as computed, not mirrored
-    // from its lower triangle -- what Spectra's DenseGenMatProd multiplies by in a USE_SPECTRA build, src/filter.cpp:174, 311
-    // -- so it takes the host route, which forms exactly that; the device route diagonalises a symmetric similar matrix)
-    if (hist && c->topk_solver == 0) {
-        // the Gram kernels were enqueued above; the q-sized products run on the device, the eigensolves on the host
-        ortho_ss_device(c, o, ny, p, sk.sA_c, sk.sA_r, d_tiles.p, n_eig, enqueue_gram,
-                        [&] { all_reduce(c, d_tiles.p, g_elems); }, &ms->host, &ms->host_overlapped, tr);
-        tm_g.stop();
-    } else {
-        enqueue_gram();
-        double h0 = now_ms();
-        ortho_ss_prepare(o, ny, p, sk.sA_c, sk.sA_r, /*literal_q=*/c->topk_solver != 0);  // host, while the Gram kernel runs
-        const double h_overlapped = now_ms() - h0;
-        tr.mark("ss: ortho prepare (host)");
-        // (a device-to-host copy into pageable memory blocks the host until the stream reaches it, so it
-        // is issued only now)
-        all_reduce(c, d_tiles.p, g_elems);
-        std::vector<double> tiles(g_elems);
-        HIP_OK(hipMemcpyAsync(tiles.data(), d_tiles.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        tm_g.stop();
-        HIP_OK(hipStreamSynchronize(c->stream));
-        tr.mark("ss: gram sync");
-        h0 = now_ms();
-        ortho_ss_finish(o, hist ? std::move(tiles) : unpack_tiles(tiles, nlek::gram64_ld(p), p, 16), n_eig, c->topk_solver);
-        ms->host += now_ms() - h0;
-        tr.mark("ss: ortho finish (host)");
-        ms->host_overlapped += h_overlapped;
-    }
+    const size_t g_elems = (size_t)nlek::gram64_num_tiles(p) * 256;
+    DevBuf<double> d_gpart(nlek::gram64_partial_elems(M, p)), d_tiles(g_elems);
+    const OrthoSS o = ortho_ss_host(
+        c, ny, p, sk,
+        [&] {
+            PROFILED(c, NLE_K_GRAM, nlek::gram64(c->stream, d_lum, ss.gs, d_samples.p, p, nsw, npw, pix0, M, d_cbuf.p, d_gpart.p,
+                                                 d_tiles.p));
+        },
+        d_tiles.p, g_elems, /*tile16=*/true, n_eig, tm_g, ms, tr);
     adopt_ortho(f, o);
 
-    // V = diag(c) K_AB^T D: the Nystrom extension of the K' retained eigenvectors, affinity fused
+    // V = diag(c) K_AB^T D: the Nystrom extension of the K' <= 128 (train_impl) retained eigenvectors, affinity fused
     tm_p.start();
-    if (o.K > 128) throw Fail{NLE_ERR_INVALID, "Phi-free path supports at most 128 eigenvectors"};
-    const int ldd = nlek::project64_ld(o.K);
-    std::vector<double> Dp((size_t)p * ldd, 0.0);
-    for (int k = 0; k < o.K; ++k)
-        for (int a = 0; a < p; ++a) Dp[(size_t)a * ldd + k] = o.D[(size_t)k * p + a];
+    const std::vector<double> Dp = padded_rows(o.D, p, o.K, nlek::project64_ld(o.K));
     DevBuf<double> d_D(Dp.size());
     HIP_OK(hipMemcpyAsync(d_D.p, Dp.data(), Dp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (hist) {
-        // keep what defines V implicitly; the projection runs only if somebody asks for the matrix
-        auto own = [&](auto& buf) {
-            using T = std::remove_pointer_t<decltype(buf.p)>;
-            const size_t bytes = buf.n * sizeof(T);
-            T* ptr = buf.take();
-            f->owned.emplace_back(ptr, bytes);
-            return ptr;
-        };
-        std::vector<double> Vr((size_t)p * ldd, 0.0);
-        for (int k = 0; k < o.K; ++k)
-            for (int a = 0; a < p; ++a) Vr[(size_t)a * ldd + k] = o.Vrows[(size_t)k * p + a];
-        DevBuf<double> d_Vr(Vr.size());
-        DevBuf<long long> d_spix(p), d_sloc(p);
-        DevBuf<float> d_slab((size_t)M);
-        std::vector<long long> sloc(p);
-        for (int a = 0; a < p; ++a) {
-            const long long loc = ss.pix[a] - pix0;
-            sloc[a] = (loc >= 0 && loc < M) ? loc : -1;
-        }
-        HIP_OK(hipMemcpyAsync(d_Vr.p, Vr.data(), Vr.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(d_spix.p, ss.pix.data(), p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(d_sloc.p, sloc.data(), p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-        HIP_OK(hipMemcpyAsync(d_slab.p, d_lum + pix0, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-        HIP_OK(hipStreamSynchronize(c->stream));  // the host staging vectors go out of scope
-        f->lazy = true;
-        f->gs = ss.gs;
-        f->nsw = nsw;
-        f->npw = npw;
-        f->ldd = ldd;
-        f->P64 = P64;
-        f->d_lum = own(d_slab);
-        f->d_c = own(d_cbuf);
-        f->d_er = own(d_er);
-        f->d_ecT = own(d_ecT);
-        f->d_Ep = own(d_Ep);
-        f->d_D = own(d_D);
-        f->d_Vrows = own(d_Vr);
-        f->d_samples = own(d_samples);
-        f->d_sample_pix = own(d_spix);
-        f->d_sample_loc = own(d_sloc);
-        if (sorted) {
-            f->has_sorted = true;
-            f->sorted = nlek::SortedRows{own(d_scol), own(d_desc), own(d_first), own(d_E), sr.rec, sr.kappa};
-            f->sorted.lev_t0 = sr.lev_t0;
-            f->sorted.lev_nt = sr.lev_nt;
-            f->sorted.mom = sr.mom;
-        }
-        f->h_Vrows = o.Vrows;
-        f->h_sample_pix = ss.pix;
-        tm_p.stop();
-        ms->take(tm_s, tm_g, tm_p);
-        return;
-    }
-    DevBuf<float> d_V((size_t)std::max<long long>(M, 1) * f->ldv);
+    DevBuf<float> d_V((size_t)M * f->ldv);
     PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, d_lum, ss.gs, d_samples.p, p, nsw, npw, pix0, M, d_D.p, o.K,
                                                d_cbuf.p, d_V.p, f->ldv));
     tr.mark("ss: project enqueued");
@@ -714,7 +709,7 @@ void train_sample_space(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
 //   Sinkhorn half-iteration   y_i = recip(k_i . w), z += k_i y_i                 k_rowpass64 (u := w)
 //   Gram                      Gk += sum c_i^2 k_i k_i^T                          k_gram64d
 //   eigenvectors              V_i = c_i k_i^T D                                  k_tsgemm64      (V: N x K' fp64, as mode 4)
-// and the p-sized side is train_sample_space's (SampleSinkhorn, ortho_ss_device).  Costs a pass 2 x N p 8 bytes of HBM
+// and the p-sized side is train_tables' (SampleSinkhorn, ortho_ss_device).  Costs a pass 2 x N p 8 bytes of HBM
 // traffic (write + read of the chunk) where the materialised form reads N r 8 once -- the price of not holding it.
 void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss, const std::function<Nystrom()>& solve,
                     double hx, double hy, int T, int n_eig, long long pix0, long long M, StageMs* ms) {
@@ -791,7 +786,7 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
     ms->take(tm_s, tm_g, tm_p);
 }
 
-// materialise V = diag(c) K D of a lazy filter (projection kernel + exact sample rows)
+// materialise V = diag(c) K D of a table filter (projection kernel + exact sample rows)
 void ensure_V(nle_filter* f) {
     if (f->d_V) return;
     nle_ctx* c = f->ctx;
@@ -803,18 +798,19 @@ void ensure_V(nle_filter* f) {
         f->d_V = d_V.take();
         return;
     }
-    if (!f->lazy) return;
+    if (!f->tables) return;
+    const TableFilter& t = *f->tables;
     const long long M = f->n_local, pix0 = (long long)f->row0 * f->W;
     DevBuf<float> d_V((size_t)std::max<long long>(M, 1) * f->ldv);
-    PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, f->d_lum - pix0, f->gs, f->d_samples, f->p, f->nsw, f->npw, pix0,
-                                               M, f->d_D, f->K, f->d_c, d_V.p, f->ldv));
+    PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, t.lum, t.gs, t.samples.p, t.p, t.nsw, t.npw, pix0, M, t.D.p, f->K,
+                                               t.c.p, d_V.p, f->ldv));
     scatter_sample_rows(c, f->h_sample_pix, f->p, f->h_Vrows, f->K, f->ldv, pix0, M, d_V.p);
     HIP_OK(hipStreamSynchronize(c->stream));
     f->v_bytes = d_V.n * sizeof(float);
     f->d_V = d_V.take();
 }
 
-// apply on the p-sized side of a lazy filter: reduce half (column sums m = sum_i k_i c_i x_i through the
+// apply on the p-sized side of a table filter: reduce half (column sums m = sum_i k_i c_i x_i through the
 // tables), the p/K-sized middle (k_apply_small), and one table pass per output layer
 // `done(l0, nl)`, when given, is called after layers [l0, l0 + nl) are complete on the stream (the host-buffer entry
 // points start their download there); `group` caps the layers per launch (0: as many as fit)
@@ -822,53 +818,42 @@ using LayersDone = std::function<void(int, int)>;
 void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L x K */, int L, float* d_y,
                         const LayersDone& done = nullptr, int group = 0, bool round8 = false) {
     nle_ctx* c = f->ctx;
-    const long long M = f->n_local, pix0 = (long long)f->row0 * f->W;
-    const int p = f->p, K = f->K, P64 = f->P64, nrows_local = (int)(M / f->W);
-    const float* lum = f->d_lum - pix0;  // indexed by global pixel, only this rank's rows are touched
-    DevBuf<double> d_ws(std::max<size_t>(nlek::hist_tiled_workspace_elems(f->gs, std::max(nrows_local, 1)), 1)), d_m(P64),
-        d_resp((size_t)L * K), d_t(K), d_Wp((size_t)L * P64), d_YA((size_t)L * p);
+    const TableFilter& t = *f->tables;
+    const nlek::TableView view = t.view();
+    const long long M = f->n_local;
+    const int p = t.p, K = f->K, P64 = t.P64;
+    DevBuf<double> d_ws(nlek::hist_tiled_workspace_elems(t.gs, t.nrows)), d_m(P64), d_resp((size_t)L * K), d_t(K),
+        d_Wp((size_t)L * P64), d_YA((size_t)L * p);
     HIP_OK(hipMemcpyAsync(d_resp.p, h_g, (size_t)L * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (M > 0) {
+    {
         static const int rmap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_REDUCE, NLE_K_REDUCE, NLE_K_REDUCE};
         ProfObserver obs(c, rmap);
-        HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, lum, f->gs, p, P64, f->row0, nrows_local, f->d_er,
-                                     f->d_ecT, f->d_Ep, nullptr, NLE_EPS, nullptr, d_ws.p, d_m.p, &obs, f->d_c, d_x,
-                                     f->has_sorted ? &f->sorted : nullptr));
-    } else {
-        HIP_OK(hipMemsetAsync(d_m.p, 0, P64 * sizeof(double), c->stream));
+        HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_ws.p, d_m.p, &obs, d_x));
     }
     all_reduce(c, d_m.p, P64);
     // x at the p sample pixels: every rank's own rows, completed by the all-reduce when the planes are slabs
     DevBuf<double> d_xA(p);
     {
         const bool slabs = c->slab_input && c->world > 1;
-        PROFILED(c, NLE_K_SMALL, nlek::gather_samples_slab(c->stream, d_x, f->gs, slabs ? f->row0 : 0, slabs ? f->row1 : f->H, d_xA.p));
+        PROFILED(c, NLE_K_SMALL, nlek::gather_samples_slab(c->stream, d_x, t.gs, slabs ? f->row0 : 0, slabs ? f->row1 : f->H, d_xA.p));
         if (slabs) all_reduce(c, d_xA.p, p);
     }
-    PROFILED(c, NLE_K_SMALL, nlek::apply_small(c->stream, p, K, f->ldd, L, P64, d_m.p, f->d_D, f->d_Vrows, d_xA.p,
-                                               d_resp.p, d_t.p, d_Wp.p, d_YA.p));
-    if (M > 0) {
-        static const int emap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_EXPAND, NLE_K_REDUCE, NLE_K_REDUCE};
-        const nlek::SortedRows* srt = f->has_sorted ? &f->sorted : nullptr;
-        // layers per launch of the expand kernel apply_hist_layers will pick
-        int lb = std::min(L, nlek::use_sorted_expand(f->gs, srt) ? nlek::sorted_expand_layers(f->gs)
-                                                                   : nlek::apply_layers_per_launch(f->gs));
-        if (group > 0) lb = std::min(lb, group);
-        DevBuf<double> d_gws((size_t)lb * nrows_local * 256 * f->gs.nSelCols);
-        for (int l = 0; l < L; l += lb) {
-            const int nl = std::min(lb, L - l);
-            {
-                ProfObserver obs(c, emap);
-                HIP_OK(nlek::apply_hist_layers(c->stream, lum, f->gs, p, f->row0, nrows_local, f->d_er, f->d_ecT, f->d_Ep,
-                                               d_Wp.p + (size_t)l * P64, P64, nl, f->d_c, d_gws.p, d_y + (size_t)l * M, M,
-                                               &obs, srt, round8));
-            }
-            PROFILED(c, NLE_K_SMALL, nlek::scatter_samples(c->stream, p, nl, f->d_sample_loc, d_YA.p + (size_t)l * p,
-                                                           d_y + (size_t)l * M, M, round8));
-            if (done) done(l, nl);
+    PROFILED(c, NLE_K_SMALL, nlek::apply_small(c->stream, p, K, t.ldd, L, P64, d_m.p, t.D.p, t.Vrows.p, d_xA.p, d_resp.p,
+                                               d_t.p, d_Wp.p, d_YA.p));
+    static const int emap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_EXPAND, NLE_K_REDUCE, NLE_K_REDUCE};
+    int lb = std::min(L, nlek::apply_layers_per_launch(view));
+    if (group > 0) lb = std::min(lb, group);
+    DevBuf<double> d_gws((size_t)lb * t.nrows * 256 * t.gs.nSelCols);
+    for (int l = 0; l < L; l += lb) {
+        const int nl = std::min(lb, L - l);
+        {
+            ProfObserver obs(c, emap);
+            HIP_OK(nlek::apply_hist_layers(c->stream, view, d_Wp.p + (size_t)l * P64, P64, nl, d_gws.p, d_y + (size_t)l * M, M,
+                                           &obs, round8));
         }
-    } else if (done) {
-        done(0, L);
+        PROFILED(c, NLE_K_SMALL, nlek::scatter_samples(c->stream, p, nl, t.sample_loc.p, d_YA.p + (size_t)l * p,
+                                                       d_y + (size_t)l * M, M, round8));
+        if (done) done(l, nl);
     }
     HIP_OK(hipStreamSynchronize(c->stream));
     prof_flush(c);
@@ -1259,10 +1244,9 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
     // same on all ranks (an empty slab used to take a different path and mismatch the all-reduces)
     if (c->world > H) throw Fail{NLE_ERR_INVALID, "more ranks than image rows"};
     // Phi-free needs <= 128 eigenvectors; its generic kernels need <= 256 samples, its table kernels
-    // (quantised luminance, checked on the device below) a sample grid of at most 32 x 36.
+    // (quantised luminance, checked on the device below) a sample grid of at most 32 x 36: nlek::tables_apply
     const bool generic_ok = gs.p() <= nlek::sink_pass_max_p() && n_eig <= 128;
-    const bool tables_ok =
-        n_eig <= 128 && gs.nSelCols <= nlek::ghist_max_cols() && gs.nSelRows <= 32 && c->mode != NLE_MODE_PHI_FREE_EXP;
+    const bool tables_ok = nlek::tables_apply(gs, n_eig) && c->mode != NLE_MODE_PHI_FREE_EXP;
     if (c->mode == NLE_MODE_PHI_FREE_EXP && !generic_ok)
         throw Fail{NLE_ERR_INVALID, "Phi-free path without tables supports at most 256 samples and 128 eigenvectors"};
     if (c->mode == NLE_MODE_PHI_FREE && !generic_ok && !tables_ok)
@@ -1286,6 +1270,7 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         const long long pix0 = (long long)f->row0 * W;
         const long long M = (long long)(f->row1 - f->row0) * W;
         f->n_local = M;
+        if (M <= 0) throw Fail{NLE_ERR_INVALID, "a rank without image rows"};  // (world <= H: cannot happen; the train paths rely on it)
         const double t_begin = now_ms();
         pinned_reset(c);
         Trace tr;
@@ -1331,8 +1316,10 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
             if (std::getenv("NLE_AUTO_STREAM64")) stream64 = true;
             if (c->world > 1) stream64 = ranks_where(c, stream64) > 0;  // one rank short of memory: everybody streams
         }
-        if (fuse) {
-            train_sample_space(c, f, d_lum, ss, [&] { return solve(true); }, hx, hy, T, n_eig, pix0, M, &sm);
+        if (fuse && tables_ok && ss.quantised) {
+            train_tables(c, f, d_lum, ss, [&] { return solve(true); }, hx, hy, T, n_eig, pix0, M, &sm);
+        } else if (fuse) {
+            train_phi_free_exp(c, f, d_lum, ss, [&] { return solve(true); }, hx, hy, T, n_eig, pix0, M, &sm);
         } else if (stream64) {
             train_stream64(c, f, d_lum, ss, [&] { return solve(true); }, hx, hy, T, n_eig, pix0, M, &sm);
         } else {
@@ -1371,7 +1358,7 @@ void apply_impl(nle_filter* f, const float* d_x_in, int H, int W, const double* 
         throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
     if (L < 1 || L > 64) throw Fail{NLE_ERR_INVALID, "number of layers must be in [1, 64]"};
     HIP_OK(hipSetDevice(c->device));
-    if (f->lazy) {
+    if (f->tables) {
         apply_sample_space(f, d_x, h_g, L, d_y, done, group, round8);
         return;
     }
@@ -1686,7 +1673,6 @@ void nle_filter_destroy(nle_filter* f) {
     if (f->d_V) arena_release(f->ctx, f->d_V, f->v_bytes);  // back to the ctx's workspace cache (or hipFree)
     if (f->d_plane) arena_release(f->ctx, f->d_plane, f->plane_bytes);
     if (f->d_V64) arena_release(f->ctx, f->d_V64, f->v64_bytes);
-    for (auto& b : f->owned) arena_release(f->ctx, b.first, b.second);
     delete f;
 }
 
@@ -1754,11 +1740,12 @@ int nle_filter_eigvec_range(const nle_filter* f, int ncols, double* h_min, doubl
         const float* d_cols = f->d_V;
         int ldc = f->ldv;
         DevBuf<float> d_tmp;
-        if (!f->d_V && f->lazy) {
+        if (!f->d_V && f->tables) {
+            const TableFilter& t = *f->tables;
             const long long M = f->n_local, pix0 = (long long)f->row0 * f->W;
-            const int ldd_full = f->ldd, ldd = nlek::project64_ld(ncols);
+            const int ldd_full = t.ldd, ldd = nlek::project64_ld(ncols);
             std::vector<double> Dfull((size_t)f->p * ldd_full), Dk((size_t)f->p * ldd, 0.0);
-            HIP_OK(hipMemcpyAsync(Dfull.data(), f->d_D, Dfull.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIP_OK(hipMemcpyAsync(Dfull.data(), t.D.p, Dfull.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             HIP_OK(hipStreamSynchronize(c->stream));
             for (int a = 0; a < f->p; ++a)
                 for (int k = 0; k < ncols; ++k) Dk[(size_t)a * ldd + k] = Dfull[(size_t)a * ldd_full + k];
@@ -1766,8 +1753,8 @@ int nle_filter_eigvec_range(const nle_filter* f, int ncols, double* h_min, doubl
             HIP_OK(hipMemcpyAsync(d_Dk.p, Dk.data(), Dk.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
             ldc = ld4(ncols);
             d_tmp.alloc((size_t)std::max<long long>(M, 1) * ldc);
-            PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, f->d_lum - pix0, f->gs, f->d_samples, f->p, f->nsw, f->npw,
-                                                       pix0, M, d_Dk.p, ncols, f->d_c, d_tmp.p, ldc));
+            PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, t.lum, t.gs, t.samples.p, t.p, t.nsw, t.npw, pix0, M, d_Dk.p,
+                                                       ncols, t.c.p, d_tmp.p, ldc));
             scatter_sample_rows(c, f->h_sample_pix, f->p, f->h_Vrows, ncols, ldc, pix0, M, d_tmp.p);
             HIP_OK(hipStreamSynchronize(c->stream));  // Dk (host) is consumed
             d_cols = d_tmp.p;
@@ -1899,7 +1886,7 @@ int nle_apply_rounded8(nle_filter* f, const float* d_x, int H, int W, const doub
     if (!f || !f->ctx || !d_x || !h_fS || !d_y) return NLE_ERR_INVALID;
     return guard(f->ctx, [&] {
         apply_impl(f, d_x, H, W, h_fS, 1, d_y, nullptr, 0, /*round8=*/true);
-        if (!f->lazy) {  // formulations with fp32 planes: round those
+        if (!f->tables) {  // formulations with fp32 planes: round those
             DevBuf<unsigned char> d_o((size_t)std::max<long long>(f->n_local, 1));
             HIP_OK(nlek::plane_to_u8(f->ctx->stream, d_y, f->n_local, d_o.p));
             HIP_OK(nlek::channel8_plane(f->ctx->stream, d_o.p, f->n_local, d_y));
@@ -2099,8 +2086,9 @@ int nle_bench_affinity64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
 
 int nle_filter_level_tiles(const nle_filter* f, int* first_tile, int* n_tiles) {
     if (!f || !first_tile || !n_tiles) return NLE_ERR_INVALID;
-    *first_tile = f->has_sorted ? f->sorted.lev_t0 : 0;
-    *n_tiles = f->has_sorted ? f->sorted.lev_nt : 16;
+    const nlek::SortedRows* sr = f->tables ? f->tables->sorted_rows() : nullptr;
+    *first_tile = sr ? sr->lev_t0 : 0;
+    *n_tiles = sr ? sr->lev_nt : 16;
     return NLE_OK;
 }
 

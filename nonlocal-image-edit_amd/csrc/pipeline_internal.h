@@ -29,6 +29,7 @@
 #include "kernels.h"
 
 using nlek::GridSpec;
+namespace nlep { struct TableFilter; struct SampleSet; }
 
 // ------------------------------------------------------------------------------ types
 struct nle_ctx {
@@ -89,7 +90,7 @@ struct nle_filter {
     int H = 0, W = 0, row0 = 0, row1 = 0;
     long long n_local = 0;
     int K = 0, ldv = 0, r = 0, p = 0;
-    float* d_V = nullptr;  // m_eigvecs (n_local x ldv fp32); in the lazy form it is materialised on first request
+    float* d_V = nullptr;  // m_eigvecs (n_local x ldv fp32); in the table form it is materialised on first request
     size_t v_bytes = 0;
     double* d_V64 = nullptr;  // fp64 formulation (generic64.hip): m_eigvecs in fp64, same leading dimension
     size_t v64_bytes = 0;
@@ -98,22 +99,11 @@ struct nle_filter {
     double ms[6] = {0, 0, 0, 0, 0, 0};
     // nle_filter_diag: formulation taken, eigenvalues kept by the three cuts (:214 on Ka, Wa, Q), Cholesky shortcuts
     int formulation = 0, r_wa = 0, r_q = 0, chol_ka = 0, chol_wa = 0;
-    // Lazy / sample-space form (tables formulation): m_eigvecs is the implicit V = diag(c) K D.  apply()
-    // works on the p-sized side of it (t = D^T sum_i k_i c_i x_i, y = c_i k_i . D(f o t)) and never needs
-    // the N x K' matrix; nle_filter_eigvecs & co. build it on demand with the projection kernel.
-    bool lazy = false;
-    nlek::GridSpec gs{};
-    float nsw = 0.f, npw = 0.f;
-    int ldd = 0, P64 = 0;
+    // set: the table formulation (TableFilter below), m_eigvecs implicit.  It dies with the filter or with the ctx, whichever
+    // goes first (nle_ctx_destroy): its buffers are the ctx's workspace cache's
+    std::unique_ptr<nlep::TableFilter> tables;
     float* d_plane = nullptr;  // nle_train_host: the uploaded training plane (full image), kept for apply(h_x == NULL)
     size_t plane_bytes = 0;
-    float* d_lum = nullptr;  // this rank's slab of the training luminance
-    double *d_c = nullptr, *d_er = nullptr, *d_ecT = nullptr, *d_Ep = nullptr, *d_D = nullptr, *d_Vrows = nullptr;
-    float4* d_samples = nullptr;
-    long long *d_sample_pix = nullptr, *d_sample_loc = nullptr;
-    bool has_sorted = false;  // level-sorted rows (sorted.hip) of the training plane, for the apply's reduce half
-    nlek::SortedRows sorted{};
-    std::vector<std::pair<void*, size_t>> owned;  // workspace-cache buffers that live as long as the filter
     std::vector<double> h_Vrows;                  // p x K col-major: exact rows of V at the sample pixels
     std::vector<long long> h_sample_pix;          // the sample pixels, in the order of the sample set (ascending)
 };
@@ -203,6 +193,37 @@ struct DevBuf {
         return q;
     }
     ~DevBuf() { release(); }
+};
+
+// The table formulation's state on one rank, owned from train to apply.  m_eigvecs is the implicit
+// V = diag(c) K D: apply() works on the p-sized side of it (t = D^T sum_i k_i c_i x_i, y = c_i k_i . D(f o t)) and never
+// needs the N x K' matrix; nle_filter_eigvecs & co. build it on demand with the projection kernel.  Every buffer goes back
+// to the workspace cache of the ctx it was made on when the object dies.
+struct TableFilter {
+    nlek::GridSpec gs{};
+    int p = 0, P64 = 0, row0 = 0, nrows = 0, ldd = 0;  // P64 = sink_pass_ld(p): stride of the p-sized vectors, padding of `samples`
+    float nsw = 0.f, npw = 0.f;
+    const float* lum = nullptr;  // virtual base of the full image: the caller's plane while training, `slab` afterwards
+    DevBuf<float4> samples;
+    DevBuf<double> c, er, ecT, Ep;  // c_i per local pixel (0 at sample pixels; the last Sinkhorn pass writes it); hist_tables
+    // level-sorted rows of the training plane (sorted.hip) where they exist; `sorted` is filled by the constructor and nowhere
+    // else.  E2 and sorted.hx serve the Gram only (sorted_gsum_ok)
+    DevBuf<unsigned short> scol, first;
+    DevBuf<uint2> desc;
+    DevBuf<double> E, E2;
+    nlek::SortedRows sorted{};
+    // added when training ends (train_tables): the kept eigenvectors in sample space and the exact rows of V at the sample
+    // pixels (p x ldd row-major), the samples' local pixel index (-1 off this rank), this rank's slab of the training plane
+    DevBuf<double> D, Vrows;
+    DevBuf<long long> sample_loc;
+    DevBuf<float> slab;
+
+    TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet& ss, double hx, double hy, int row0, int nrows);
+    void drop_gram_only() { E2.release(), sorted.E2 = nullptr, sorted.hx = 0.0; }
+    const nlek::SortedRows* sorted_rows() const { return scol.p ? &sorted : nullptr; }  // null: no sorted rows were made
+    nlek::TableView view() const {
+        return nlek::TableView{lum, gs, p, P64, row0, nrows, er.p, ecT.p, Ep.p, c.p, sorted_rows()};
+    }
 };
 
 struct Timer {

@@ -1,4 +1,4 @@
-// Level-sorted image rows: the N-sized halves of the table formulation (fused.hip, "quantised-luminance fast path")
+// Level-sorted image rows: the N-sized halves of the table formulation (tables.hip)
 // without LDS atomics.
 //
 // The table kernels of round 1 (k_hist_pix, k_ghist_rows) keep a 256 x nC histogram per image row in LDS and add nC
@@ -24,7 +24,7 @@
 // row starting with three dependent global loads -- showed the kernel waiting on memory latency for most of its time.)
 //
 // Reference arithmetic restated: the Sinkhorn row products / column sums of src/filter.cpp:238-245, the Gram
-// Wab Wab^T of :296 and the reduce half of apply (:456), exactly as fused.hip derives them; only the order of the
+// Wab Wab^T of :296 and the reduce half of apply (:456), exactly as tables.hip derives them; only the order of the
 // fp64 sums differs.
 #include "kernels.h"
 
@@ -114,7 +114,7 @@ __device__ __forceinline__ int block_max256(int v, int* red) {
 
 int sorted_max_width() { return 8192; }  // 8 W fits 16 bits; chunks of <= 32 pixels (kMaxBlocks)
 
-// E[d] = exp(-d^2 / hx^2), d = 0 .. W: the same expression as ecT in k_hist_tables (fused.hip), so the two agree bit for bit
+// E[d] = exp(-d^2 / hx^2), d = 0 .. W: the same expression as ecT in k_hist_tables (tables.hip), so the two agree bit for bit
 __global__ void k_dist_table(int W, double inv_hx2, double* __restrict__ E) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d <= W) {
@@ -725,12 +725,10 @@ bool sorted_moments_ok(GridSpec gs, double hx) {
     return span * span / (hx * hx) < 500.0;
 }
 
-hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows_local, const unsigned short* d_scol,
-                       const uint2* d_desc, const unsigned short* d_first, const double* d_E, const double* d_g, double eps,
-                       double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec, bool rec, double kappa,
-                       int lev_t0, int lev_nt, bool mom) {
-    const int nC = gs.nSelCols;
-    if (nC < 1 || nC > 36 || gs.W > sorted_max_width() || lev_t0 < 0 || lev_nt < 1 || lev_t0 + lev_nt > kLevels / 16)
+hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows_local, const SortedRows& sr, const double* d_g,
+                       double eps, double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec) {
+    const int nC = gs.nSelCols, lev_t0 = sr.lev_t0, lev_nt = sr.lev_nt;
+    if (!tables_apply(gs) || gs.W > sorted_max_width() || lev_t0 < 0 || lev_nt < 1 || lev_t0 + lev_nt > kLevels / 16)
         return hipErrorInvalidValue;
     if (nrows_local <= 0) return hipSuccess;
     const size_t shm = sorted_lds_bytes(gs.W, (nC < 11 ? nC : 11) | 1);
@@ -742,22 +740,22 @@ hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                    \
             if (ea != hipSuccess) return ea;                                                                              \
         }                                                                                                                 \
-        hipLaunchKernelGGL((k_sorted_pass<NCV, CFV>), dim3((unsigned)grid), dim3(kT), shm, s, mode, d_scol, d_desc,        \
-                           d_first, gs, row0, nrows_local, d_E, d_g, eps, d_ybuf, d_h, d_cvec, d_xvec, kappa, lev_t0,     \
+        hipLaunchKernelGGL((k_sorted_pass<NCV, CFV>), dim3((unsigned)grid), dim3(kT), shm, s, mode, sr.scol, sr.desc,      \
+                           sr.first, gs, row0, nrows_local, sr.E, d_g, eps, d_ybuf, d_h, d_cvec, d_xvec, sr.kappa, lev_t0, \
                            lev_nt);                                                                                       \
     }
 #define NLE_SP(NCV)                                                                                                       \
     case NCV:                                                                                                             \
         if constexpr ((NCV) > 1) {                                                                                        \
-            if (mom) {                                                                                                    \
+            if (sr.mom) {                                                                                                 \
                 NLE_SP1(NCV, 2)                                                                                           \
                 break;                                                                                                    \
             }                                                                                                             \
         }                                                                                                                 \
         if constexpr ((NCV) > 12) {                                                                                       \
-            if (rec) NLE_SP1(NCV, 1) else NLE_SP1(NCV, 0)                                                                 \
+            if (sr.rec) NLE_SP1(NCV, 1) else NLE_SP1(NCV, 0)                                                              \
         } else {                                                                                                          \
-            if (rec) return hipErrorInvalidValue;                                                                         \
+            if (sr.rec) return hipErrorInvalidValue;                                                                      \
             NLE_SP1(NCV, 0)                                                                                               \
         }                                                                                                                 \
         break;
@@ -871,18 +869,14 @@ __global__ __launch_bounds__(kT) void k_sorted_expand(const unsigned short* __re
     }
 }
 
-int sorted_expand_max_cols() { return 36; }
-int sorted_expand_max_width() { return 8192; }
 // layers one launch takes: four up to 12 columns and 4096 pixels per row, two beyond (registers, LDS)
 int sorted_expand_layers(GridSpec gs) { return (gs.nSelCols <= 12 && gs.W <= 4096) ? kExpLayers : 2; }
 
-hipError_t sorted_expand(hipStream_t s, GridSpec gs, int nrows_local, const unsigned short* d_scol, const uint2* d_desc,
-                         const double* d_E, const double* d_g, size_t gstride, int nl, const double* d_cvec, float* d_out,
-                         long long ostride, bool rec, double kappa, bool round8) {
+hipError_t sorted_expand(hipStream_t s, GridSpec gs, int nrows_local, const SortedRows& sr, const double* d_g, size_t gstride,
+                         int nl, const double* d_cvec, float* d_out, long long ostride, bool round8) {
     const int nC = gs.nSelCols;
     const int lmax = sorted_expand_layers(gs);
-    if (nC < 1 || nC > sorted_expand_max_cols() || gs.W > sorted_expand_max_width() || nl < 1 || nl > lmax)
-        return hipErrorInvalidValue;
+    if (!tables_apply(gs) || gs.W > sorted_max_width() || nl < 1 || nl > lmax) return hipErrorInvalidValue;
     if (nrows_local <= 0) return hipSuccess;
     const size_t shm = (size_t)((gs.W + 2) & ~1) * sizeof(double) + (size_t)lmax * gs.W * sizeof(float);
     int ncu = 256, dev = 0;
@@ -895,15 +889,15 @@ hipError_t sorted_expand(hipStream_t s, GridSpec gs, int nrows_local, const unsi
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                 \
             if (ea != hipSuccess) return ea;                                                                           \
         }                                                                                                              \
-        hipLaunchKernelGGL((k_sorted_expand<NCV, LV, RECV>), dim3((unsigned)grid), dim3(kT), shm, s, d_scol, d_desc,   \
-                           gs, nrows_local, d_E, d_g, gstride, nl, d_cvec, d_out, ostride, kappa, round8 ? 1 : 0);     \
+        hipLaunchKernelGGL((k_sorted_expand<NCV, LV, RECV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc, \
+                           gs, nrows_local, sr.E, d_g, gstride, nl, d_cvec, d_out, ostride, sr.kappa, round8 ? 1 : 0); \
     }
 #define NLE_SX(NCV)                                                                                                    \
     case NCV:                                                                                                          \
         if constexpr ((NCV) <= 12) {                                                                                   \
             if (lmax == kExpLayers) NLE_SX1(NCV, kExpLayers, false) else NLE_SX1(NCV, 2, false)                        \
         } else {                                                                                                       \
-            if (rec) NLE_SX1(NCV, 2, true) else NLE_SX1(NCV, 2, false)                                                 \
+            if (sr.rec) NLE_SX1(NCV, 2, true) else NLE_SX1(NCV, 2, false)                                              \
         }                                                                                                              \
         break;
     switch (nC) {
@@ -995,7 +989,7 @@ __global__ __launch_bounds__(kT) void k_sorted_gram(const unsigned short* __rest
 // (complete the square).  So the nC (nC + 1) / 2 pair tables of k_sorted_gram(_wide) collapse to 2 nC - 1 tables
 //     S_r[t][x] = sum_{i in row r, x_i = x} c_i^2 G_t(col_i)
 // -- 59 instead of 465 at cfg5, in one launch instead of 15, an eighth of the table bytes -- and the same identity on the rows
-// shrinks the GEMM behind it from nR (nR + 1) / 2 to 2 nR - 1 rows (fused.hip: gram_hist).  Exact algebra; only the order and
+// shrinks the GEMM behind it from nR (nR + 1) / 2 to 2 nR - 1 rows (tables.hip: gram_hist).  Exact algebra; only the order and
 // grouping of roundings differ from the pair form.
 // G_t along t by the recurrence of a Gaussian on an equispaced grid (as column_factors<REC>), started from ONE table value:
 //     G_0 = E2[|c - cb0|],   G_{t+1} = G_t rho_t,   rho_0 = exp(theta (c - cb0)) kappa1,   rho_{t+1} = rho_t kappa1^2,
@@ -1085,13 +1079,12 @@ bool sorted_gsum_ok(GridSpec gs, double hx) {
     return gs.W <= sorted_max_width() && m_g < 600.0 && m_rho < 600.0;
 }
 
-hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows_local, const unsigned short* d_scol, const uint2* d_desc,
-                            const unsigned short* d_first, const double* d_E2, const double* d_cvec, double* d_Aout,
-                            double hx) {
+hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows_local, const SortedRows& sr, const double* d_cvec,
+                            double* d_Aout) {
     const int nC = gs.nSelCols, nt = 2 * nC - 1;
-    if (nC < 1 || nC > 36 || gs.W > sorted_max_width()) return hipErrorInvalidValue;
+    if (!tables_apply(gs) || gs.W > sorted_max_width() || sr.E2 == nullptr) return hipErrorInvalidValue;
     if (nrows_local <= 0) return hipSuccess;
-    const double cs = gs.colStep;
+    const double cs = gs.colStep, hx = sr.hx;
     const double theta = 2.0 * cs / (hx * hx), kappa1 = std::exp(-cs * cs / (2.0 * hx * hx));
     const size_t shm = sorted_lds_bytes(gs.W, 11) + (size_t)((((gs.W >> 6) + 2) & ~1) + 64) * sizeof(double);
     const int grid = sorted_grid(nrows_local);
@@ -1102,8 +1095,8 @@ hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows_local, const u
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                   \
             if (ea != hipSuccess) return ea;                                                                             \
         }                                                                                                                \
-        hipLaunchKernelGGL((k_sorted_gsum<NTV>), dim3((unsigned)grid), dim3(kT), shm, s, d_scol, d_desc, d_first, gs,     \
-                           nrows_local, d_E2, d_cvec, d_Aout, theta, kappa1);                                            \
+        hipLaunchKernelGGL((k_sorted_gsum<NTV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc, sr.first, gs,  \
+                           nrows_local, sr.E2, d_cvec, d_Aout, theta, kappa1);                                           \
     } break;
     switch (nt) {
         NLE_GS(1) NLE_GS(3) NLE_GS(5) NLE_GS(7) NLE_GS(9) NLE_GS(11) NLE_GS(13) NLE_GS(15) NLE_GS(17) NLE_GS(19) NLE_GS(21)
@@ -1204,14 +1197,10 @@ __global__ __launch_bounds__(kT) void k_sorted_gram_wide(const unsigned short* _
     }
 }
 
-int sorted_gram_max_cols() { return 36; }
-
-
-hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows_local, const unsigned short* d_scol, const uint2* d_desc,
-                            const unsigned short* d_first, const double* d_E, const double* d_cvec, double* d_Aout, bool rec,
-                            double kappa) {
+hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows_local, const SortedRows& sr, const double* d_cvec,
+                            double* d_Aout) {
     const int nC = gs.nSelCols;
-    if (nC < 1 || nC > sorted_gram_max_cols() || gs.W > sorted_max_width()) return hipErrorInvalidValue;
+    if (!tables_apply(gs) || gs.W > sorted_max_width()) return hipErrorInvalidValue;
     if (nrows_local <= 0) return hipSuccess;
     const size_t shm = sorted_lds_bytes(gs.W, 11);
     const int grid = sorted_grid(nrows_local);
@@ -1225,8 +1214,8 @@ hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows_local, const u
             if (ea != hipSuccess) return ea;                                                                            \
         }                                                                                                               \
         for (int b0 = 0; b0 < nC; b0 += bb)                                                                             \
-            hipLaunchKernelGGL((k_sorted_gram_wide<NCV>), dim3((unsigned)grid), dim3(kT), shm, s, d_scol, d_desc,       \
-                               d_first, gs, nrows_local, d_E, d_cvec, d_Aout, rec ? 1 : 0, kappa, b0,                    \
+            hipLaunchKernelGGL((k_sorted_gram_wide<NCV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc,     \
+                               sr.first, gs, nrows_local, sr.E, d_cvec, d_Aout, sr.rec ? 1 : 0, sr.kappa, b0,            \
                                std::min(bb, nC - b0));                                                                  \
     } break;
         switch (nC) {
@@ -1245,12 +1234,12 @@ hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows_local, const u
                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                  \
             if (ea != hipSuccess) return ea;                                                                            \
         }                                                                                                               \
-        hipLaunchKernelGGL((k_sorted_gram<NCV, RECV>), dim3((unsigned)grid), dim3(kT), shm, s, d_scol, d_desc, d_first,  \
-                           gs, nrows_local, d_E, d_cvec, d_Aout, kappa);                                                \
+        hipLaunchKernelGGL((k_sorted_gram<NCV, RECV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc,        \
+                           sr.first, gs, nrows_local, sr.E, d_cvec, d_Aout, sr.kappa);                                  \
     }
 #define NLE_SG(NCV)                                                                                                     \
     case NCV:                                                                                                           \
-        if (rec) return hipErrorInvalidValue; /* up to 11 columns: table form only */                                    \
+        if (sr.rec) return hipErrorInvalidValue; /* up to 11 columns: table form only */                                 \
         NLE_SG1(NCV, false)                                                                                             \
         break;
     switch (nC) {

@@ -823,3 +823,33 @@ def test_apply_layers_64_layers_on_the_table_formulation(nle, oracle, ctx):
         b = f.apply(x32, resp[l]).cpu().numpy()
         assert rel_l2(Y32[l], b) < 1e-6, (l, rel_l2(Y32[l], b))
     f.close()
+
+
+def test_table_filters_own_their_state_across_trains_and_destroys(nle, oracle, ctx):
+    """the table formulation's state belongs to its filter: filters of different shapes trained on one ctx do not disturb
+    each other, and a destroyed filter's buffers -- handed out again by the ctx's workspace cache to the next train of the
+    same shape -- are nobody else's.  Level-sorted rows (W <= 8192) are bitwise reproducible, so everything is compared
+    bit for bit; the eigenvector range as test_eigvec_range_without_materialising_V does (entries of magnitude <= 1, one
+    fp32 rounding each on either route)."""
+    T, K, L = 8, 10, 4
+    xa = oracle.synthetic_luminance(96, 128).astype(np.float32)
+    xb = oracle.synthetic_luminance(64, 200, seed=77).astype(np.float32)
+    xc = oracle.synthetic_luminance(96, 128, seed=4242).astype(np.float32)
+    fa = nle.NLEFilter(ctx).train_filter(xa, 6, 8, 32.0, 30.0, T, K)
+    ya = fa.apply_layers(xa, L).cpu().numpy()
+    fb = nle.NLEFilter(ctx).train_filter(xb, 5, 12, 32.0, 30.0, T, K)
+    yb = fb.apply_layers(xb, L).cpu().numpy()
+    assert fa.diag()["formulation"] == nle.MODE_PHI_FREE and fb.diag()["formulation"] == nle.MODE_PHI_FREE
+    assert np.isfinite(ya).all() and np.isfinite(yb).all() and np.abs(ya[-1]).max() > 1.0 and np.abs(yb[-1]).max() > 1.0
+    assert np.array_equal(fa.apply_layers(xa, L).cpu().numpy(), ya)
+    fa.close()
+    fc = nle.NLEFilter(ctx).train_filter(xc, 6, 8, 32.0, 30.0, T, K)   # the same sizes as A's: A's blocks come back out
+    yc = fc.apply_layers(xc, L).cpu().numpy()
+    assert np.array_equal(fb.apply_layers(xb, L).cpu().numpy(), yb)
+    mn, mx = fb.eigvec_range(4)
+    V = fb.eigvecs().cpu().numpy()[:, :4].astype(np.float64)
+    assert V.shape[0] == 64 * 200
+    assert np.allclose(mn, V.min(0), rtol=0, atol=1e-6) and np.allclose(mx, V.max(0), rtol=0, atol=1e-6)
+    assert np.array_equal(fc.apply_layers(xc, L).cpu().numpy(), yc)
+    fb.close()
+    fc.close()

@@ -1,4 +1,4 @@
-// Variants of the table Sinkhorn pixel kernel (k_hist_pix<10>, fused.hip) on a cfg4-shaped problem: which LDS
+// Variants of the table Sinkhorn pixel kernel (k_hist_pix<10>, tables.hip) on a cfg4-shaped problem: which LDS
 // accumulation is fastest?  Timing experiment only (round-2 VERDICT item 3: "measure, don't argue").
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -o /tmp/hpv tools/micro/hist_pix_variants.hip
 //   V0  the shipping kernel: ds_add_f64 + wave-level pre-reduction of levels shared by >= 12 lanes
@@ -6,7 +6,7 @@
 //   V2  V1 without the pre-reduction
 //   V3  ds_add_f64, two sub-histograms (even / odd lanes)
 //   V4  ds_add_u64, two sub-histograms
-#include "../../nonlocal-image-edit_amd/csrc/fused.hip"
+#include "../../nonlocal-image-edit_amd/csrc/tables.hip"
 
 #include <cmath>
 #include <cstdio>
