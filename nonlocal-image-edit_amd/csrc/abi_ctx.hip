@@ -32,7 +32,8 @@ int nle_ctx_create(int device, void* stream, nle_ctx** out) {
         HIP_OK(hipSetDevice(device));
         auto c = new nle_ctx();
         c->device = device;
-        if (const char* e = std::getenv("NLE_Q_SOLVER")) c->topk_solver = (std::string(e) == "lanczos") ? 1 : 0;
+        c->sw = nlesw::read_switches();
+        c->topk_solver = c->sw.q_solver;  // a default at creation only: nle_ctx_set_topk_solver overrides it
         if (stream) {
             c->stream = reinterpret_cast<hipStream_t>(stream);
         } else {
@@ -396,7 +397,8 @@ int nle_ctx_init_rccl(nle_ctx* ctx, int rank, int world, const void* h_id, size_
 
 int nle_ctx_abort_rccl(nle_ctx* ctx) {
     if (!ctx) return NLE_ERR_INVALID;
-    // no guard(): this may run on another thread than the one that uses the ctx (whose error string it must not touch)
+    // no guard(): this may run on another thread than the one that uses the ctx (whose error string and switch snapshot
+    // it must not touch)
     std::lock_guard<std::mutex> lk(ctx->comm_mu);  // not while the ctx's own thread is inside an enqueue on this communicator
     if (!ctx->comm || !ctx->own_comm) return NLE_OK;
     if (ctx->comm_aborted.exchange(1, std::memory_order_acq_rel) != 0) return NLE_OK;

@@ -4,11 +4,10 @@
 
 namespace nlep {
 
-// p x p problems go to the device from this order on (NLE_DEV_SOLVER_MIN overrides; NLE_HOST_SOLVER=1 keeps them on the
-// host).  Below it a host core wins: the reduction is a chain of n dependent steps and a step costs the device two
-// hand-offs between workgroups (measured: profiles/r3_dense_solver_timing.txt).
-int dev_solver_min_n();
-bool use_dev_solver(int n);
+// p x p problems go to the device from order sw.dev_solver_min on (288 unless NLE_DEV_SOLVER_MIN says otherwise;
+// sw.host_solver keeps them on the host).  Below it a host core wins: the reduction is a chain of n dependent steps and a
+// step costs the device two hand-offs between workgroups (measured: profiles/r3_dense_solver_timing.txt).
+bool use_dev_solver(const nlesw::Switches& sw, int n);
 
 // holds `n` compute units of the DEVICE's budget for persistent launches while alive
 int device_cu_count(int device);

@@ -49,15 +49,8 @@ CuLease::~CuLease() {
     g_cu_cv.notify_all();
 }
 
-int dev_solver_min_n() {
-    static const int v = [] {
-        const char* e = std::getenv("NLE_DEV_SOLVER_MIN");
-        return e ? std::max(3, std::atoi(e)) : 288;
-    }();
-    return v;
-}
-bool use_dev_solver(int n) {
-    return n >= dev_solver_min_n() && n <= nlek::sytrd_max_n() && std::getenv("NLE_HOST_SOLVER") == nullptr;
+bool use_dev_solver(const nlesw::Switches& sw, int n) {
+    return n >= sw.dev_solver_min && n <= nlek::sytrd_max_n() && !sw.host_solver;
 }
 
 hipStream_t aux_stream(nle_ctx* c) {
@@ -81,7 +74,7 @@ void DevSymEig::prepare(nle_ctx* c, int n_, hipStream_t stream) {
 bool DevSymEig::reduce(nle_ctx* c, int n_, const double* d_M, const double* d_diag_add) {
     if (!pub.p || n != n_) prepare(c, n_, st);
     int G = nlek::sytrd_groups(n);
-    if (const char* e = std::getenv("NLE_SYTRD_G")) G = std::atoi(e);
+    if (c->sw.sytrd_g_set) G = c->sw.sytrd_g;
     // every workgroup of the persistent launch needs a compute unit of its own for the whole launch: a device that exposes
     // fewer (a partitioned or smaller part) cannot run it -- the caller takes the host solver
     if (G <= 0 || G + 16 > device_cu_count(c->device)) return false;
@@ -109,7 +102,7 @@ bool DevSymEig::reduce(nle_ctx* c, int n_, const double* d_M, const double* d_di
     // a hand-off between workgroups timed out (the workgroups were not co-resident after all), or the matrix was not
     // finite: not an error of the train -- the host solver (nleh::eigen_decomposition*) takes over
     if (h_status != 0) {
-        if (std::getenv("NLE_TRACE")) std::fprintf(stderr, "[nle trace] device eigensolver (n = %d): hand-off timed out, host solver takes over\n", n);
+        if (c->sw.trace) std::fprintf(stderr, "[nle trace] device eigensolver (n = %d): hand-off timed out, host solver takes over\n", n);
         return false;
     }
     for (int i = 0; i < n; ++i)

@@ -8,6 +8,7 @@
 // orthonormal eigenvectors; `eigen_decomposition` adds the reference's post-processing
 // (:209-216): descending order, keep the leading run with D >= eps.
 #include "eigen_sym.h"
+#include "switches.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1051,8 +1052,9 @@ __attribute__((target("avx512f"))) static bool inverse_iteration_x8(int n, const
 // eigenvalues closer than 1e-3 ||T|| re-orthogonalised against each other (modified Gram-Schmidt, twice).  O(n k)
 // instead of the O(n^2 k)-ish rotation sweeps: what sym_eigen_top uses when only the leading part of the spectrum is
 // wanted (orthogonalize keeps K of q eigenvectors, src/filter.cpp:314).  Z: n x k column-major.  false: a vector did not
-// reach a residual of 1e3 eps ||T|| (the caller falls back to the rotation form).
-bool tridiag_inverse_iteration(int n, const double* d, const double* e, const double* lam, int k, double* Z) {
+// reach a residual of 1e3 eps ||T|| (the caller falls back to the rotation form).  no_x8: Switches::eig_no_x8 as the public
+// entry point read it.
+bool tridiag_inverse_iteration(int n, const double* d, const double* e, const double* lam, int k, double* Z, bool no_x8) {
     const double eps = std::ldexp(1.0, -52);
     double onenrm = 0.0;
     for (int i = 0; i < n; ++i)
@@ -1291,7 +1293,7 @@ bool tridiag_inverse_iteration(int n, const double* d, const double* e, const do
         }
 #if defined(__x86_64__)
     {   // isolated eigenvalues (clusters of one: nothing to orthogonalise against), eight per sweep
-        static const bool x8 = __builtin_cpu_supports("avx512f") && std::getenv("NLE_EIG_NO_X8") == nullptr;
+        const bool x8 = __builtin_cpu_supports("avx512f") && !no_x8;
         std::vector<int> single;
         if (x8 && n >= 16)
             for (int g = 0; g < ngroups; ++g)
@@ -1353,7 +1355,7 @@ bool tridiag_inverse_iteration(int n, const double* d, const double* e, const do
 
 bool tridiag_eigenvectors(int n, const double* d, const double* e, const double* lam_all, int first, int count, double* Z) {
     if (count <= 0) return true;
-    if (tridiag_inverse_iteration(n, d, e, lam_all + first, count, Z)) return true;
+    if (tridiag_inverse_iteration(n, d, e, lam_all + first, count, Z, nlesw::read_switches().eig_no_x8)) return true;
     // the classic iteration on T itself: rotations accumulated from the identity
     std::vector<double> V((size_t)n * n, 0.0), dd(d, d + n), ee(e, e + n);
     for (int i = 0; i < n; ++i) V[(size_t)i * n + i] = 1.0;
@@ -1369,8 +1371,9 @@ bool tridiag_eigenvectors(int n, const double* d, const double* e, const double*
 
 // The part of sym_eigen_top after the reduction: V (n x n, u_i in column i rows 0..i-1), hs, and the tridiagonal (d, e) as
 // tridiag_reduce -- or the device kernel k_tridiag (tridiag.hip), same conventions -- leaves them.
-bool sym_eigen_top_reduced(int n, const double* V, const double* d_in, const double* e_in, const double* hs, int ncols,
-                           int nthreads, double* U, double* D) {
+// (the public functions below read the switches once, at their entry, and hand no_x8 down through these overloads)
+static bool sym_eigen_top_reduced(int n, const double* V, const double* d_in, const double* e_in, const double* hs, int ncols,
+                                  int nthreads, double* U, double* D, bool no_x8) {
     if (nthreads <= 0) nthreads = default_threads(n, ncols);
     std::vector<double> d(d_in, d_in + n), e(e_in, e_in + n);
     const std::vector<double> d0(d), e0(e);  // T itself (the QL iteration overwrites d and e)
@@ -1395,7 +1398,7 @@ bool sym_eigen_top_reduced(int n, const double* V, const double* d_in, const dou
     if (ncols == 0) return true;
     if (invit) {
         // a leading part of the spectrum only: inverse iteration on T for those eigenvalues, then the back-transformation
-        if (tridiag_inverse_iteration(n, d0.data(), e0.data(), D, ncols, U)) {
+        if (tridiag_inverse_iteration(n, d0.data(), e0.data(), D, ncols, U, no_x8)) {
             const int cparts0 = std::max(1, std::min(nthreads, (ncols + 3) / 4));
             run_split(cparts0, nthreads, [&](int q) {
                 const int j0 = (int)((long long)ncols * q / cparts0), j1 = (int)((long long)ncols * (q + 1) / cparts0);
@@ -1429,7 +1432,12 @@ bool sym_eigen_top_reduced(int n, const double* V, const double* d_in, const dou
     return true;
 }
 
-bool sym_eigen_top(const double* M, int n, int ncols, int nthreads, double* U, double* D) {
+bool sym_eigen_top_reduced(int n, const double* V, const double* d_in, const double* e_in, const double* hs, int ncols,
+                           int nthreads, double* U, double* D) {
+    return sym_eigen_top_reduced(n, V, d_in, e_in, hs, ncols, nthreads, U, D, nlesw::read_switches().eig_no_x8);
+}
+
+static bool sym_eigen_top(const double* M, int n, int ncols, int nthreads, double* U, double* D, bool no_x8) {
     if (n <= 0) return true;
     ncols = std::max(0, std::min(ncols, n));
     if (n == 1) {
@@ -1438,7 +1446,10 @@ bool sym_eigen_top(const double* M, int n, int ncols, int nthreads, double* U, d
         return true;
     }
     auto [V, d, e, hs] = reduce_lower(M, n);
-    return sym_eigen_top_reduced(n, V.data(), d.data(), e.data(), hs.data(), ncols, nthreads, U, D);
+    return sym_eigen_top_reduced(n, V.data(), d.data(), e.data(), hs.data(), ncols, nthreads, U, D, no_x8);
+}
+bool sym_eigen_top(const double* M, int n, int ncols, int nthreads, double* U, double* D) {
+    return sym_eigen_top(M, n, ncols, nthreads, U, D, nlesw::read_switches().eig_no_x8);
 }
 
 // eigen_decomposition_top for a matrix already reduced (n >= 2, kmax <= n): all eigenvalues descending in D, the first kmax
@@ -1446,7 +1457,7 @@ bool sym_eigen_top(const double* M, int n, int ncols, int nthreads, double* U, d
 bool eigen_decomposition_top_reduced(int n, double eps, int kmax, const double* V, const double* d, const double* e,
                                      const double* hs, double* U, double* D, int* r_out) {
     kmax = std::max(0, std::min(kmax, n));
-    if (!sym_eigen_top_reduced(n, V, d, e, hs, kmax, 0, U, D)) return false;
+    if (!sym_eigen_top_reduced(n, V, d, e, hs, kmax, 0, U, D, nlesw::read_switches().eig_no_x8)) return false;
     int r = 0;
     while (r < n && D[r] >= eps) ++r;
     *r_out = r;
@@ -1595,8 +1606,8 @@ void sturm_eigenvalues_desc(const SturmT& t, int first, int count, double* out) 
 // All eigenvalues (DESCENDING, in D) and the eigenvectors of D[first .. first + count) only (U: n x count): the reduction
 // without the orthogonal factor, QL on (d, e) for the values, inverse iteration on T for the selected vectors, and their
 // back-transformation.  What the deflated root of Wa needs: the few eigenpairs the 1e-10 cut removes (pipeline.hip).
-bool sym_eigen_select(const double* M, int n, double* D, int first, int count, double* U, double below_eps, int max_below,
-                      int* kept_out) {
+static bool sym_eigen_select(const double* M, int n, double* D, int first, int count, double* U, double below_eps, int max_below,
+                             int* kept_out, bool no_x8) {
     if (n <= 0) return true;
     if (n == 1) {
         D[0] = M[0];
@@ -1618,9 +1629,13 @@ bool sym_eigen_select(const double* M, int n, double* D, int first, int count, d
     first = std::max(0, std::min(first, n));
     count = std::max(0, std::min(count, n - first));
     if (count == 0) return true;
-    if (!tridiag_inverse_iteration(n, d0.data(), e0.data(), D + first, count, U)) return false;
+    if (!tridiag_inverse_iteration(n, d0.data(), e0.data(), D + first, count, U, no_x8)) return false;
     back_transform_cols(n, V.data(), hs.data(), U, 0, count);
     return true;
+}
+bool sym_eigen_select(const double* M, int n, double* D, int first, int count, double* U, double below_eps, int max_below,
+                      int* kept_out) {
+    return sym_eigen_select(M, n, D, first, count, U, below_eps, max_below, kept_out, nlesw::read_switches().eig_no_x8);
 }
 
 // What the deflated root of Wa needs and no more (ortho.hip): *kept_out = the number of eigenvalues >= eps (one Sturm
@@ -1628,9 +1643,10 @@ bool sym_eigen_select(const double* M, int n, double* D, int first, int count, d
 // (n x max_below), the largest eigenvalue in *lam_max and the smallest kept one in *lam_min_kept, all by bisection.
 bool sym_eigen_below(const double* M, int n, double eps, int max_below, int* kept_out, double* lam_max, double* lam_min_kept,
                      double* Dbelow, double* U) {
-    if (n < 8 || std::getenv("NLE_EIG_NO_BISECT") != nullptr) {
+    const nlesw::Switches sw = nlesw::read_switches();
+    if (n < 8 || sw.eig_no_bisect) {
         std::vector<double> D(n);
-        if (!sym_eigen_select(M, n, D.data(), 0, 0, U, eps, max_below, kept_out)) return false;
+        if (!sym_eigen_select(M, n, D.data(), 0, 0, U, eps, max_below, kept_out, sw.eig_no_x8)) return false;
         const int kept = *kept_out;
         *lam_max = D[0];
         *lam_min_kept = kept > 0 ? D[kept - 1] : 0.0;
@@ -1655,7 +1671,7 @@ bool sym_eigen_below(const double* M, int n, double eps, int max_below, int* kep
         if (nb <= max_below) std::copy(out.begin() + 2, out.end(), Dbelow);
     }
     if (nb == 0 || nb > max_below) return true;
-    if (!tridiag_inverse_iteration(n, d.data(), e.data(), Dbelow, nb, U)) return false;
+    if (!tridiag_inverse_iteration(n, d.data(), e.data(), Dbelow, nb, U, sw.eig_no_x8)) return false;
     back_transform_cols(n, V.data(), hs.data(), U, 0, nb);
     return true;
 }
@@ -1695,11 +1711,13 @@ bool sym_eigen_blocked(const double* M, int n, double* U, double* D) {
 // (orthogonalize on Q, :313-316): Dk[0 .. kmax) = the kmax largest eigenvalues DESCENDING, U (n x kmax) their eigenvectors,
 // *r_out = number of eigenvalues >= eps.  Householder reduction, eigenvalues by bisection, eigenvectors by inverse iteration
 // and back-transformation.  For 2 kmax <= n (else, and should the inverse iteration give up: eigen_decomposition_top).
+static bool eigen_decomposition_top(const double* M, int n, double eps, int kmax, double* U, double* D, int* r_out, bool no_x8);
 bool eigen_decomposition_topk(const double* M, int n, double eps, int kmax, double* U, double* Dk, int* r_out) {
+    const nlesw::Switches sw = nlesw::read_switches();
     kmax = std::max(0, std::min(kmax, n));
-    if (n < 8 || 2 * kmax > n || std::getenv("NLE_EIG_NO_BISECT") != nullptr) {
+    if (n < 8 || 2 * kmax > n || sw.eig_no_bisect) {
         std::vector<double> D(n);
-        if (!eigen_decomposition_top(M, n, eps, kmax, U, D.data(), r_out)) return false;
+        if (!eigen_decomposition_top(M, n, eps, kmax, U, D.data(), r_out, sw.eig_no_x8)) return false;
         std::copy(D.begin(), D.begin() + kmax, Dk);
         return true;
     }
@@ -1708,9 +1726,9 @@ bool eigen_decomposition_topk(const double* M, int n, double eps, int kmax, doub
     *r_out = n - sturm_count1(t, eps);  // descending order: the leading run >= eps IS the count of eigenvalues >= eps
     sturm_eigenvalues_desc(t, 0, kmax, Dk);
     if (kmax == 0) return true;
-    if (!tridiag_inverse_iteration(n, d.data(), e.data(), Dk, kmax, U)) {
+    if (!tridiag_inverse_iteration(n, d.data(), e.data(), Dk, kmax, U, sw.eig_no_x8)) {
         std::vector<double> D(n);
-        if (!eigen_decomposition_top(M, n, eps, kmax, U, D.data(), r_out)) return false;
+        if (!eigen_decomposition_top(M, n, eps, kmax, U, D.data(), r_out, sw.eig_no_x8)) return false;
         std::copy(D.begin(), D.begin() + kmax, Dk);
         return true;
     }
@@ -1718,7 +1736,7 @@ bool eigen_decomposition_topk(const double* M, int n, double eps, int kmax, doub
     return true;
 }
 
-bool eigen_decomposition_top(const double* M, int n, double eps, int kmax, double* U, double* D, int* r_out) {
+static bool eigen_decomposition_top(const double* M, int n, double eps, int kmax, double* U, double* D, int* r_out, bool no_x8) {
     kmax = std::max(0, std::min(kmax, n));
     if (2 * kmax > n && default_threads(n, kmax) == 1) {
         // most eigenvectors wanted, one thread: accumulating the orthogonal factor (classic form) is cheaper
@@ -1731,7 +1749,7 @@ bool eigen_decomposition_top(const double* M, int n, double eps, int kmax, doubl
             D[j] = Da[src];
             if (j < kmax) std::copy(Ua.begin() + (size_t)src * n, Ua.begin() + (size_t)src * n + n, U + (size_t)j * n);
         }
-    } else if (!sym_eigen_top(M, n, kmax, 0, U, D)) {
+    } else if (!sym_eigen_top(M, n, kmax, 0, U, D, no_x8)) {
         return false;
     }
     // reference src/filter.cpp:209-216: descending, keep the leading run >= eps
@@ -1741,8 +1759,12 @@ bool eigen_decomposition_top(const double* M, int n, double eps, int kmax, doubl
     return true;
 }
 
+bool eigen_decomposition_top(const double* M, int n, double eps, int kmax, double* U, double* D, int* r_out) {
+    return eigen_decomposition_top(M, n, eps, kmax, U, D, r_out, nlesw::read_switches().eig_no_x8);
+}
+
 bool eigen_decomposition(const double* M, int n, double eps, double* U, double* D, int* r_out) {
-    return eigen_decomposition_top(M, n, eps, n, U, D, r_out);
+    return eigen_decomposition_top(M, n, eps, n, U, D, r_out, nlesw::read_switches().eig_no_x8);
 }
 
 // ---- opt-in top-K solver with the semantics of the reference's USE_SPECTRA build (src/filter.cpp:170-199) ----

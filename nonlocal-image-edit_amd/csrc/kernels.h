@@ -272,6 +272,7 @@ struct SortedRows {
     double hx = 0.0;
     int lev_t0 = 0, lev_nt = 16;  // the 16-level tiles [lev_t0, lev_t0 + lev_nt) that occur in the image (check_levels)
     bool mom = false;             // the pass kernel's pixel loop in its moment form (sorted_moments_ok)
+    int wgs_per_cu = 2;           // workgroups per compute unit of the sorted kernels' grids: two of 512 threads, each walks its rows
 };
 // What the composite launchers below take: the table path's state on one rank, rows [row0, row0 + nrows) of the image;
 // non-owning (pipeline_internal.h: TableFilter owns it)
@@ -285,6 +286,8 @@ struct TableView {
     const SortedRows* sorted;      // null: the pixel kernels are the LDS-atomic ones (k_hist_pix, k_hist_dot, k_ghist_rows*)
 };
 
+// sorted_gsum_ok, sorted_recurrence, sorted_moments_ok: pure functions of the grid and the bandwidth -- where the form
+// named stays inside fp64's normal range.  Whoever fills a SortedRows combines them with what else decides the form.
 // Gram by index sums (sorted.hip: k_sorted_gsum): S_r[t][x] = sum c_i^2 G_t(col_i), t < 2 nC - 1; layout [row][t][level]
 bool sorted_gsum_ok(GridSpec gs, double hx);
 hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows, const SortedRows& sr, const double* d_cvec, double* d_Aout);

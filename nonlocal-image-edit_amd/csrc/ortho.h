@@ -51,12 +51,14 @@ struct OrthoSS {
 
 // reference :282-331 on the host from the materialised quantities (G = sum over all pixels of c^2 phi phi^T)
 Ortho orthogonalize_host(const Nystrom& ny, int p, const std::vector<double>& u_c, const std::vector<double>& u_r,
-                         std::vector<double> G, int n_eig, bool device_f32 = true, int topk_solver = 0);
+                         std::vector<double> G, int n_eig, bool device_f32, int topk_solver, bool trace);
 // sample-space form, host: everything that does not need the Gram matrix, then the rest
+// literal_q: S = Wa^-1/2 itself (no Cholesky root): Q is then the reference's matrix; force_eig, trace: the caller's
+// switches (Switches::force_eig, ::trace)
 void ortho_ss_prepare(OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c, const std::vector<double>& sA_r,
-                      bool literal_q = false);  // literal_q: S = Wa^-1/2 itself (no Cholesky root): Q is then the reference's matrix
-void ortho_ss_finish(OrthoSS& o, std::vector<double> Gk, int n_eig, int topk_solver = 0);
-// sample-space form with the p x p products (and, from dev_solver_min_n() samples on, the solvers) on the device
+                      bool literal_q, bool force_eig, bool trace);
+void ortho_ss_finish(OrthoSS& o, std::vector<double> Gk, int n_eig, int topk_solver, bool trace);
+// sample-space form with the p x p products (and, where use_dev_solver says so, the solvers) on the device
 void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c,
                      const std::vector<double>& sA_r, double* d_Gk, int n_eig, const std::function<void()>& enqueue_gram,
                      const std::function<void()>& reduce_gram, double* host_ms, double* host_overlapped_ms, Trace& tr);

@@ -38,7 +38,7 @@ void mm_tn(const double* A, const double* B, double* C, int m, int k, int n) {
 // eigenvalues, the leading run >= eps counted in *rq, eigenvectors of the first min(n_eig, q) only.  solver 1: the
 // USE_SPECTRA build's topkEigenDecomposition (:170-199): nev = min(n_eig, q - 1) pairs of largest magnitude by Lanczos,
 // *rq = converged pairs in the leading run >= eps.  Vq: q x (columns formed), Sq: their eigenvalues, descending.
-void top_eigenpairs(const std::vector<double>& Qm, int q, int n_eig, int solver, std::vector<double>* Vq,
+void top_eigenpairs(const std::vector<double>& Qm, int q, int n_eig, int solver, bool trace, std::vector<double>* Vq,
                     std::vector<double>* Sq, int* rq) {
     if (solver == 1 && q > 1) {
         const int nev = std::min(std::max(n_eig, 1), q - 1);
@@ -52,7 +52,7 @@ void top_eigenpairs(const std::vector<double>& Qm, int q, int n_eig, int solver,
         int r = 0;
         while (r < nconv && (*Sq)[r] >= NLE_EPS) ++r;  // :186-196
         *rq = r;
-        if (std::getenv("NLE_TRACE")) std::fprintf(stderr, "[nle trace] Lanczos top-%d of %d: %d restarts, %d converged\n", nev, q, restarts, nconv);
+        if (trace) std::fprintf(stderr, "[nle trace] Lanczos top-%d of %d: %d restarts, %d converged\n", nev, q, restarts, nconv);
         return;
     }
     Vq->assign((size_t)q * std::min(q, std::max(n_eig, 1)), 0.0);  // only the kept eigenvectors (:314)
@@ -61,9 +61,9 @@ void top_eigenpairs(const std::vector<double>& Qm, int q, int n_eig, int solver,
         throw Fail{NLE_ERR_NUMERIC, "eigensolver did not converge on Q"};
 }
 
-// the NLE_TRACE line of a root of Wa (nd >= 0: a deflated root, `where` names its route)
-void trace_wa(int kept, int q, double largest, double smallest_kept, int nd = -1, const char* where = "") {
-    if (!std::getenv("NLE_TRACE")) return;
+// the trace line of a root of Wa (nd >= 0: a deflated root, `where` names its route)
+void trace_wa(bool trace, int kept, int q, double largest, double smallest_kept, int nd = -1, const char* where = "") {
+    if (!trace) return;
     char defl[64] = "";
     if (nd >= 0) std::snprintf(defl, sizeof defl, ", %d deflated%s", nd, where);
     std::fprintf(stderr, "[nle trace] Wa: %d of %d eigenvalues >= 1e-10 (largest %.3e, smallest kept %.3e)%s\n", kept, q, largest,
@@ -76,7 +76,7 @@ struct EigRoot {
     std::vector<double> U2, l2, Us;
     int r2 = 0;
 };
-EigRoot eigen_root(const std::vector<double>& Wa, int q) {
+EigRoot eigen_root(const std::vector<double>& Wa, int q, bool trace) {
     EigRoot e;
     e.U2.resize((size_t)q * q);
     e.l2.resize(q);
@@ -87,7 +87,7 @@ EigRoot eigen_root(const std::vector<double>& Wa, int q) {
         const double s = std::sqrt(recip0(e.l2[k]));
         for (int i = 0; i < q; ++i) e.Us[(size_t)k * q + i] = e.U2[(size_t)k * q + i] * s;
     }
-    trace_wa(e.r2, q, e.l2[0], e.r2 > 0 ? e.l2[e.r2 - 1] : 0.0);
+    trace_wa(trace, e.r2, q, e.l2[0], e.r2 > 0 ? e.l2[e.r2 - 1] : 0.0);
     return e;
 }
 
@@ -134,7 +134,7 @@ namespace nlep {
 
 Ortho orthogonalize_host(const Nystrom& ny, int p, const std::vector<double>& u_c,
                          const std::vector<double>& u_r, std::vector<double> G, int n_eig, bool device_f32,
-                         int topk_solver) {
+                         int topk_solver, bool trace) {
     const int r = ny.r, q = ny.r;  // :247 -- the A block is the first q = r permuted rows
     // phi_A = V_A[:q] (exact, fp64); what the device holds for those rows is float(V_A)
     std::vector<double> cA(q), rA(q), cA32(q);
@@ -176,7 +176,7 @@ Ortho orthogonalize_host(const Nystrom& ny, int p, const std::vector<double>& u_
     mm(left.data(), G.data(), LG.data(), q, r, r);
     mm_nt(LG.data(), left.data(), WW.data(), q, r, q);
     // S = Wa^{-1/2} (pseudo-inverse root), :287-292
-    const auto [U2, l2, Us, r2] = eigen_root(o.Wa, q);
+    const auto [U2, l2, Us, r2] = eigen_root(o.Wa, q, trace);
     std::vector<double> S((size_t)q * q);
     o.r_wa = r2;
     if (r2 <= 0) throw Fail{NLE_ERR_NUMERIC, "Wa has no eigenvalue >= 1e-10"};
@@ -193,7 +193,7 @@ Ortho orthogonalize_host(const Nystrom& ny, int p, const std::vector<double>& u_
         mm_tn(Us.data(), WF.data(), Qt.data(), q, r2, r2);
         for (int k = 0; k < r2; ++k) Qt[(size_t)k * r2 + k] += l2[k];
         std::vector<double> Vt;
-        top_eigenpairs(Qt, r2, n_eig, topk_solver, &Vt, &Sq, &rq);
+        top_eigenpairs(Qt, r2, n_eig, topk_solver, trace, &Vt, &Sq, &rq);
         K = std::min(n_eig, rq);  // :314
         if (K <= 0) throw Fail{NLE_ERR_NUMERIC, "Q has no eigenvalue >= 1e-10"};
         T2.resize((size_t)q * K);
@@ -205,7 +205,7 @@ Ortho orthogonalize_host(const Nystrom& ny, int p, const std::vector<double>& u_
         mm(S.data(), WW.data(), T1.data(), q, q, q);
         mm(T1.data(), S.data(), Qm.data(), q, q, q);
         for (size_t i = 0; i < Qm.size(); ++i) Qm[i] += o.Wa[i];
-        top_eigenpairs(Qm, q, n_eig, topk_solver, &Vq, &Sq, &rq);
+        top_eigenpairs(Qm, q, n_eig, topk_solver, trace, &Vq, &Sq, &rq);
         K = std::min(n_eig, rq);  // :314
         if (K <= 0) throw Fail{NLE_ERR_NUMERIC, "Q has no eigenvalue >= 1e-10"};
         T2.resize((size_t)q * K);
@@ -229,7 +229,7 @@ Ortho orthogonalize_host(const Nystrom& ny, int p, const std::vector<double>& u_
 // first half: everything that does not depend on the Gram matrix (runs on the host while the GPU
 // computes Gk): sample scalings, Kr, P, Wa and S = Wa^-1/2 (:287-292)
 void ortho_ss_prepare(OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c,
-                      const std::vector<double>& sA_r, bool literal_q) {
+                      const std::vector<double>& sA_r, bool literal_q, bool force_eig, bool trace) {
     const int r = ny.r, q = ny.r;
     sample_scalings(o, ny, p, sA_c, sA_r);
     if (ny.chol) {
@@ -252,7 +252,7 @@ void ortho_ss_prepare(OrthoSS& o, const Nystrom& ny, int p, const std::vector<do
     // eigenvectors V (:327).  When A is provably free of eigenvalues below the cut, F = L^-T (Cholesky).
     o.S.resize((size_t)q * q);
     // (literal_q: the caller wants Q itself, S = Wa^-1/2 the symmetric root -- the Lanczos option -- not a similar matrix)
-    if (!literal_q && std::getenv("NLE_FORCE_EIG") == nullptr) {
+    if (!literal_q && !force_eig) {
         std::vector<double> L, Li;
         if (certified_cholesky(o.Wa, q, L, Li)) {
             std::vector<double> Lt((size_t)q * q);
@@ -269,7 +269,7 @@ void ortho_ss_prepare(OrthoSS& o, const Nystrom& ny, int p, const std::vector<do
             return;
         }
     }
-    const auto [U2, l2, Us, r2] = eigen_root(o.Wa, q);
+    const auto [U2, l2, Us, r2] = eigen_root(o.Wa, q, trace);
     mm_nt(Us.data(), U2.data(), o.S.data(), q, r2, q);  // :287-292
     o.r_wa = r2;
     o.St = o.S;
@@ -277,7 +277,7 @@ void ortho_ss_prepare(OrthoSS& o, const Nystrom& ny, int p, const std::vector<do
 }
 
 // second half: needs Gk
-void ortho_ss_finish(OrthoSS& o, std::vector<double> Gk, int n_eig, int topk_solver) {
+void ortho_ss_finish(OrthoSS& o, std::vector<double> Gk, int n_eig, int topk_solver, bool trace) {
     const int p = o.p, r = o.r, q = o.q;
     const std::vector<double>&cA = o.cA, &rA = o.rA, &Kr = o.Kr, &Wa = o.Wa, &S = o.S;
     for (int a = q; a < p; ++a) {  // B-block samples
@@ -302,7 +302,7 @@ void ortho_ss_finish(OrthoSS& o, std::vector<double> Gk, int n_eig, int topk_sol
     for (size_t i = 0; i < Qm.size(); ++i) Qm[i] += o.A2[i];  // :296
     std::vector<double> Vq, Sq;
     int rq = 0;
-    top_eigenpairs(Qm, q, n_eig, topk_solver, &Vq, &Sq, &rq);
+    top_eigenpairs(Qm, q, n_eig, topk_solver, trace, &Vq, &Sq, &rq);
     const int K = std::min(n_eig, rq);  // :314
     if (K <= 0) throw Fail{NLE_ERR_NUMERIC, "Q has no eigenvalue >= 1e-10"};
     o.K = K;
@@ -453,7 +453,7 @@ void wa_root_device(nle_ctx* c, const OrthoSS& o, const Nystrom& ny, const SsDev
             }
             ws.ch.factor(c, q, ws.Ah.p);
             const bool fact_ok = ws.ch.finish(c);
-            if (!fact_ok && std::getenv("NLE_TRACE"))
+            if (!fact_ok && tr.on)
                 fprintf(stderr, "[nle trace] Wa: the deflated matrix did not factor (trace of the inverse %.3e, %d dropped, sigma %.3e)\n",
                         ws.ch.inv_trace, nd, sig);
             if (fact_ok) {
@@ -469,7 +469,7 @@ void wa_root_device(nle_ctx* c, const OrthoSS& o, const Nystrom& ny, const SsDev
                 w.on_device = true;
                 w.r_wa = kept;
                 w.nd = nd;
-                trace_wa(kept, q, D[0], D[kept - 1], nd, " (device)");
+                trace_wa(tr.on, kept, q, D[0], D[kept - 1], nd, " (device)");
             }
         }
     }
@@ -481,7 +481,7 @@ void wa_root_device(nle_ctx* c, const OrthoSS& o, const Nystrom& ny, const SsDev
     HIP_OK(hipStreamWaitEvent(st, c->aux_ev, 0));  // the first stream's later kernels see F, L, G, Wa
 }
 
-// W_A root, host route.  With `cholesky_forms` (q below dev_solver_min_n()) the Cholesky attempt and the deflated root come
+// W_A root, host route.  With `cholesky_forms` (q below the device solvers' order, use_dev_solver) the Cholesky attempt and the deflated root come
 // first; the eigenvector root is the fallback of both, and what the host does when the device route gave up.
 void wa_root_host(OrthoSS& o, bool cholesky_forms, bool force_eig, WaRoot& w, Trace& tr) {
     const int q = o.q, max_defl = q / 8;
@@ -533,7 +533,7 @@ void wa_root_host(OrthoSS& o, bool cholesky_forms, bool force_eig, WaRoot& w, Tr
                 factored = nleh::cholesky_with_inverse(Ah.data(), q, L.data(), Li.data(), &inv_trace);
                 if (factored) {
                     tr.mark("ss:   deflated matrix + its Cholesky factor and inverse");
-                    trace_wa(kept, q, lam_max, lam_min_kept, nd);
+                    trace_wa(tr.on, kept, q, lam_max, lam_min_kept, nd);
                 }
             }
         }
@@ -564,7 +564,7 @@ void wa_root_host(OrthoSS& o, bool cholesky_forms, bool force_eig, WaRoot& w, Tr
         w.nd = nd;
         return;
     }
-    EigRoot e = eigen_root(o.Wa, q);
+    EigRoot e = eigen_root(o.Wa, q, tr.on);
     w.form = WaRoot::kEigen;
     w.r_wa = e.r2;
     w.l2_kept.assign(e.l2.begin(), e.l2.begin() + e.r2);
@@ -632,7 +632,7 @@ struct QtEig {
     DevBuf<double> d_Vq, d_l2q;
 };
 
-// Top eigenpairs of Qt.  From dev_solver_min_n() on: reduction, eigenvalues and back-transformation on the device
+// Top eigenpairs of Qt.  Where use_dev_solver says so: reduction, eigenvalues and back-transformation on the device
 // (dense64.hip), only the inverse iteration for the K kept vectors on the host.  Below it: all on the host.
 // Sets o.K, o.r_q, o.Sq.
 void top_eigenpairs_Qt(nle_ctx* c, OrthoSS& o, const WaRoot& w, const double* d_Qm, int n_eig, QtEig& t, double* host_ms,
@@ -642,7 +642,7 @@ void top_eigenpairs_Qt(nle_ctx* c, OrthoSS& o, const WaRoot& w, const double* d_
     const size_t mm_ = (size_t)m * m;
     int rq = 0;
     double h0 = 0.0;
-    t.on_device = c->topk_solver == 0 && use_dev_solver(m) && !std::getenv("NLE_HOST_Q");
+    t.on_device = c->topk_solver == 0 && use_dev_solver(c->sw, m) && !c->sw.host_q;
     if (t.on_device) {
         const double* d_add = nullptr;
         if (!w.chol_form()) {
@@ -671,7 +671,7 @@ void top_eigenpairs_Qt(nle_ctx* c, OrthoSS& o, const WaRoot& w, const double* d_
         h0 = now_ms();
         if (!w.chol_form())
             for (int k = 0; k < m; ++k) Qm[(size_t)k * m + k] += w.l2_kept[k];
-        top_eigenpairs(Qm, m, n_eig, c->topk_solver, &t.Vq, &t.Sq, &rq);
+        top_eigenpairs(Qm, m, n_eig, c->topk_solver, tr.on, &t.Vq, &t.Sq, &rq);
     }
     const int K = std::min(n_eig, rq);  // :314
     if (K <= 0) throw Fail{NLE_ERR_NUMERIC, "Q has no eigenvalue >= 1e-10"};
@@ -726,11 +726,11 @@ void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std
     hipStream_t st = c->stream;
     SsDevice dv;
     scalings_Kr_P(st, o, ny, p, sA_c, sA_r, dv);
-    // ---- Wa and a root F of its pseudo-inverse, beside the Gram kernels: on the host below dev_solver_min_n(), else on the
+    // ---- Wa and a root F of its pseudo-inverse, beside the Gram kernels: on the host below the device solvers' order (use_dev_solver), else on the
     // device on the ctx's second stream (the Gram kernels are on the first)
     const double h0 = now_ms();
-    const bool dev_wa = use_dev_solver(q) && !std::getenv("NLE_HOST_WA");
-    const bool force_eig = std::getenv("NLE_FORCE_EIG") != nullptr;
+    const bool dev_wa = use_dev_solver(c->sw, q) && !c->sw.host_wa;
+    const bool force_eig = c->sw.force_eig;
     // On the device route with Ka resident there (solve_Ka's device Cholesky) Wa is formed on the device; the host copy is
     // built only if the host root has to take over.
     if (!(dev_wa && ny.dev)) build_Wa(o);

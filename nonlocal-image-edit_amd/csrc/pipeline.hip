@@ -28,10 +28,11 @@ GridSpec checked_grid(int H, int W, int nRow, int nCol) {
 // p^3/3 factorisation instead of a p x p eigensolve.  The materialised path keeps the eigenpairs.
 
 
-Nystrom solve_Ka(nle_ctx* c, const std::vector<double>& Ka, int p, bool allow_chol) {
+// (c null: everything on the host; the switches come as an argument either way)
+Nystrom solve_Ka(nle_ctx* c, const nlesw::Switches& sw, const std::vector<double>& Ka, int p, bool allow_chol) {
     Nystrom n;
-    if (allow_chol && std::getenv("NLE_FORCE_EIG") == nullptr) {
-        if (c && use_dev_solver(p) && !std::getenv("NLE_HOST_KA")) {  // blocked factorisation + inverse on the device (dense64.hip)
+    if (allow_chol && !sw.force_eig) {
+        if (c && use_dev_solver(sw, p) && !sw.host_ka) {  // blocked factorisation + inverse on the device (dense64.hip)
             const size_t pp = (size_t)p * p;
             auto kd = std::make_shared<KaDevice>();
             kd->Ka.alloc(pp);
@@ -142,8 +143,7 @@ void build_phi(nle_ctx* c, const float* d_lum, const SampleSet& ss, const Nystro
     DevBuf<float> d_B(B.size());
     HIP_OK(hipMemcpyAsync(d_B.p, B.data(), B.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     const float sw = nsw_of(hx), pw = nsw_of(hy);
-    static const bool env3 = std::getenv("NLE_NYSTROM_BF16X3") != nullptr;
-    if (c->nystrom_bf16x3 || env3) {  // split-bf16 operands on the bf16 matrix cores (tsgemm_bf16x3.hip)
+    if (c->nystrom_bf16x3 || c->sw.nystrom_bf16x3) {  // split-bf16 operands on the bf16 matrix cores (tsgemm_bf16x3.hip)
         DevBuf<unsigned short> d_Bs(nlek::ts_gemm_bf16x3_bsplit_elems(p, ny.ldr));
         HIP_OK(nlek::ts_gemm_bf16x3_split(c->stream, d_B.p, p, ny.ldr, d_Bs.p));
         PROFILED(c, NLE_K_NYSTROM, nlek::ts_gemm_bf16x3(c->stream, d_lum, ss.gs, d_samples.p, sw, pw, pix0, d_Bs.p, ny.ldr, p,
@@ -302,7 +302,7 @@ void train_materialised(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
     std::vector<double> G = gram_all(c, d_phi.p, M, ny.ldr, ny.r, d_u_c.p);
     tm_g.stop();
     double h0 = now_ms();
-    Ortho o = orthogonalize_host(ny, ss.p, u_c, u_r, std::move(G), n_eig, true, c->topk_solver);
+    Ortho o = orthogonalize_host(ny, ss.p, u_c, u_r, std::move(G), n_eig, /*device_f32=*/true, c->topk_solver, c->sw.trace);
     ms->host += now_ms() - h0;
     adopt_ortho(f, o);
     f->formulation = NLE_MODE_MATERIALISED;
@@ -377,7 +377,7 @@ void train_generic64(nle_ctx* c, nle_filter* f, const float* d_lum, const Sample
     std::vector<double> G = gram_all64(c, d_phi.p, M, ny.ldr, ny.r, d_u_c.p);
     tm_g.stop();
     double h0 = now_ms();
-    Ortho o = orthogonalize_host(ny, ss.p, u_c, u_r, std::move(G), n_eig, /*device_f32=*/false, c->topk_solver);
+    Ortho o = orthogonalize_host(ny, ss.p, u_c, u_r, std::move(G), n_eig, /*device_f32=*/false, c->topk_solver, c->sw.trace);
     ms->host += now_ms() - h0;
     adopt_ortho(f, o);
     f->formulation = NLE_MODE_MATERIALISED_F64;
@@ -498,7 +498,7 @@ OrthoSS ortho_ss_host(nle_ctx* c, const Nystrom& ny, int p, const SampleSinkhorn
     OrthoSS o;
     enqueue_gram();
     double h0 = now_ms();
-    ortho_ss_prepare(o, ny, p, sk.sA_c, sk.sA_r, /*literal_q=*/c->topk_solver != 0);  // host, while the Gram kernel runs
+    ortho_ss_prepare(o, ny, p, sk.sA_c, sk.sA_r, /*literal_q=*/c->topk_solver != 0, c->sw.force_eig, tr.on);  // host, while the Gram kernel runs
     const double h_overlapped = now_ms() - h0;
     tr.mark("ss: ortho prepare (host)");
     // (a device-to-host copy into pageable memory blocks the host until the stream reaches it, so it
@@ -510,7 +510,7 @@ OrthoSS ortho_ss_host(nle_ctx* c, const Nystrom& ny, int p, const SampleSinkhorn
     HIP_OK(hipStreamSynchronize(c->stream));
     tr.mark("ss: gram sync");
     h0 = now_ms();
-    ortho_ss_finish(o, tile16 ? unpack_tiles(tiles, nlek::gram64_ld(p), p, 16) : std::move(tiles), n_eig, c->topk_solver);
+    ortho_ss_finish(o, tile16 ? unpack_tiles(tiles, nlek::gram64_ld(p), p, 16) : std::move(tiles), n_eig, c->topk_solver, tr.on);
     ms->host += now_ms() - h0;
     tr.mark("ss: ortho finish (host)");
     ms->host_overlapped += h_overlapped;
@@ -529,12 +529,15 @@ std::vector<double> padded_rows(const std::vector<double>& X, int p, int K, int 
 
 // quantised luminance + Cartesian sample grid: table look-ups replace the exponentials (tables.hip), and the pixel halves of
 // every table pass run on level-sorted rows, without LDS atomics (sorted.hip; sorted once here).  d_lum: virtual full base.
+// Which form each sorted kernel takes is decided here and nowhere else: sorted.hip's bounds on the bandwidth, and the
+// switches of the call's snapshot that force a plain form.
 nlep::TableFilter::TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet& ss, double hx, double hy, int row0_, int nrows_)
     : gs(ss.gs), p(ss.p), P64(nlek::sink_pass_ld(ss.p)), row0(row0_), nrows(nrows_), nsw(nsw_of(hx)), npw(nsw_of(hy)),
       lum(d_lum), samples(upload_samples(ctx, ss, nlek::sink_pass_ld(ss.p))), c((size_t)nrows_ * ss.gs.W),
       er((size_t)nrows_ * ss.gs.nSelRows), ecT((size_t)ss.gs.nSelCols * ss.gs.W), Ep((size_t)256 * ss.p) {
     PROFILED(ctx, NLE_K_SMALL, nlek::hist_tables(ctx->stream, gs, samples.p, p, hx, hy, row0, nrows, er.p, ecT.p, Ep.p));
-    if (gs.W > nlek::sorted_max_width() || std::getenv("NLE_NO_SORTED_ROWS") != nullptr) return;
+    const nlesw::Switches& sw = ctx->sw;
+    if (gs.W > nlek::sorted_max_width() || sw.no_sorted_rows) return;
     scol.alloc(nlek::sorted_scol_elems(gs.W, nrows));  // k_sort_rows writes every entry a pass reads
     first.alloc((size_t)nrows * 258);
     desc.alloc((size_t)nrows * nlek::kSortedThreads);
@@ -543,16 +546,17 @@ nlep::TableFilter::TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet
     PROFILED(ctx, NLE_K_SMALL, nlek::sort_rows(ctx->stream, d_lum, gs, row0, nrows, scol.p, desc.p, first.p));
     HIP_OK(hipMemsetAsync(c.p, 0, c.n * sizeof(double), ctx->stream));  // sample pixels are never visited
     sorted = nlek::SortedRows{scol.p, desc.p, first.p, E.p, false, 0.0};
-    sorted.rec = nlek::sorted_recurrence(gs, hx, &sorted.kappa);
-    sorted.mom = nlek::sorted_moments_ok(gs, hx);
-    if (std::getenv("NLE_ALL_LEVEL_TILES") == nullptr) {  // the tables' columns of level tiles that do not occur are skipped
+    sorted.rec = nlek::sorted_recurrence(gs, hx, &sorted.kappa) && !sw.sorted_table;  // (kappa is set either way)
+    sorted.mom = nlek::sorted_moments_ok(gs, hx) && !sw.sorted_table && !sw.sorted_no_moments;
+    sorted.wgs_per_cu = sw.sorted_wgs_per_cu;
+    if (!sw.all_level_tiles) {  // the tables' columns of level tiles that do not occur are skipped
         int t0 = 0, t1 = 16;
         while (t0 < 15 && !((ss.level_tiles >> t0) & 1u)) ++t0;
         while (t1 > t0 + 1 && !((ss.level_tiles >> (t1 - 1)) & 1u)) --t1;
         sorted.lev_t0 = t0;
         sorted.lev_nt = t1 - t0;
     }
-    if (nlek::sorted_gsum_ok(gs, hx)) {  // the Gram on index sums: one more distance table, exp(-2 d^2 / hx^2)
+    if (nlek::sorted_gsum_ok(gs, hx) && !sw.gram_pairs) {  // the Gram on index sums: one more distance table, exp(-2 d^2 / hx^2)
         E2.alloc((size_t)gs.W + 1);
         PROFILED(ctx, NLE_K_SMALL, nlek::dist_table(ctx->stream, gs.W, hx / std::sqrt(2.0), E2.p));
         sorted.E2 = E2.p;
@@ -567,7 +571,7 @@ namespace {
 void train_tables(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet& ss, const std::function<Nystrom()>& solve,
                   double hx, double hy, int T, int n_eig, long long pix0, long long M, StageMs* ms) {
     const int p = ss.p;
-    Trace tr;
+    Trace tr(c->sw.trace);
     Timer tm_s(c->stream), tm_g(c->stream), tm_p(c->stream);
     tm_s.start();
     auto t = std::make_unique<TableFilter>(c, d_lum, ss, hx, hy, (int)(pix0 / ss.gs.W), (int)(M / ss.gs.W));
@@ -646,7 +650,7 @@ void train_phi_free_exp(nle_ctx* c, nle_filter* f, const float* d_lum, const Sam
     if (p > nlek::sink_pass_max_p()) throw Fail{NLE_ERR_INVALID, "Phi-free path: too many samples for the generic kernels"};
     const int P64 = nlek::sink_pass_ld(p);
     const float nsw = nsw_of(hx), npw = nsw_of(hy);
-    Trace tr;
+    Trace tr(c->sw.trace);
     Timer tm_s(c->stream), tm_g(c->stream), tm_p(c->stream);
     tm_s.start();
     // the pass kernel reads the sample table up to the next multiple of 16: pad with zeros (their
@@ -715,11 +719,10 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
                     double hx, double hy, int T, int n_eig, long long pix0, long long M, StageMs* ms) {
     const int p = ss.p, ld = ld4(p);
     hipStream_t st = c->stream;
-    Trace tr;
+    Trace tr(c->sw.trace);
     Timer tm_s(st), tm_g(st), tm_p(st);
     tm_s.start();
-    size_t budget_mb = 2048;
-    if (const char* e = std::getenv("NLE_STREAM64_CHUNK_MB")) budget_mb = (size_t)std::max(1, std::atoi(e));
+    const size_t budget_mb = (size_t)c->sw.stream64_chunk_mb;
     const long long rows_fit = (long long)((budget_mb << 20) / ((size_t)ld * sizeof(double)));
     const long long CH = std::max<long long>(256, std::min<long long>(std::max<long long>(M, 1), rows_fit));
     const AffinityRows64 kab(c, d_lum, ss, hx, hy, /*want_mask=*/true);
@@ -1211,7 +1214,7 @@ nle_filter* train_exact_impl(nle_ctx* c, const float* d_lum, int H, int W, doubl
         f->n_local = (long long)H * W;
         const double t_begin = now_ms();
         pinned_reset(c);
-        Trace tr;
+        Trace tr(c->sw.trace);
         train_exact64(c, f, d_lum, H, W, hx, hy, T, n_eig, tr);
         prof_flush(c);
         f->ms[5] = now_ms() - t_begin;
@@ -1273,7 +1276,7 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         if (M <= 0) throw Fail{NLE_ERR_INVALID, "a rank without image rows"};  // (world <= H: cannot happen; the train paths rely on it)
         const double t_begin = now_ms();
         pinned_reset(c);
-        Trace tr;
+        Trace tr(c->sw.trace);
         StageMs sm;
         // --- sample set, Ka and its eigenpairs (:486-491, host fp64)
         Timer tm_a(c->stream);
@@ -1300,7 +1303,7 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
         sm.host += now_ms() - h0;
         auto solve = [&](bool allow_chol) {
             const double t0 = now_ms();
-            Nystrom ny = solve_Ka(c, Ka, ss.p, allow_chol);
+            Nystrom ny = solve_Ka(c, c->sw, Ka, ss.p, allow_chol);
             tr.mark(ny.chol ? "chol(Ka)" : "eig(Ka)");
             sm.host += now_ms() - t0;
             return ny;
@@ -1313,7 +1316,7 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
             size_t free_b = 0, total_b = 0;
             const size_t need = (size_t)std::max<long long>(M, 1) * ld4(ss.p) * sizeof(double);
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > (free_b + c->arena_bytes) / 2) stream64 = true;
-            if (std::getenv("NLE_AUTO_STREAM64")) stream64 = true;
+            if (c->sw.auto_stream64) stream64 = true;
             if (c->world > 1) stream64 = ranks_where(c, stream64) > 0;  // one rank short of memory: everybody streams
         }
         if (fuse && tables_ok && ss.quantised) {
@@ -1446,7 +1449,7 @@ int nle_nystrom(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_sample
         HIP_OK(hipSetDevice(ctx->device));
         SampleSet ss = fetch_samples(ctx, d_lum, gs, AffinityOpts{});
         std::vector<double> Ka = build_Ka(ss, hx, hy);
-        Nystrom ny = solve_Ka(nullptr, Ka, ss.p, false);
+        Nystrom ny = solve_Ka(nullptr, ctx->sw, Ka, ss.p, false);
         int row0, row1;
         slab(H, ctx->rank, ctx->world, &row0, &row1);
         build_phi(ctx, d_lum, ss, ny, hx, hy, (long long)row0 * W, (long long)(row1 - row0) * W, d_phi);

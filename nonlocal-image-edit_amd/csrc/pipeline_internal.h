@@ -27,6 +27,7 @@
 #include "../../include/nle.h"
 #include "eigen_sym.h"
 #include "kernels.h"
+#include "switches.h"
 
 using nlek::GridSpec;
 namespace nlep { struct TableFilter; struct SampleSet; }
@@ -73,6 +74,9 @@ struct nle_ctx {
     double chroma_hc = 0.0;
     int sampler = 0;  // nle_ctx_set_sampler: NLE_SAMPLER_GRID or NLE_SAMPLER_FARTHEST (sampler.hip)
     int topk_solver = 0;  // nle_ctx_set_topk_solver: 0 full eigensolve of Q (:313-316), 1 Lanczos top-K (:170-199)
+    // the environment switches as they stood when the call in progress began (guard() takes the snapshot; nothing below
+    // an entry point asks the environment itself)
+    nlesw::Switches sw;
     bool profiling = false;
     bool profile_all = false;  // level 2: also the small / second-stage kernels (each timed launch costs ~10 us of gaps)
     struct ProfRec {
@@ -470,11 +474,11 @@ inline double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
-// NLE_TRACE=1: stage marks of a train call on stderr
+// stage marks of a train call on stderr (on: Switches::trace of the call's snapshot)
 struct Trace {
     bool on;
     double t0, last;
-    Trace() : on(std::getenv("NLE_TRACE") != nullptr) { t0 = last = now_ms(); }
+    explicit Trace(bool on_) : on(on_) { t0 = last = now_ms(); }
     void mark(const char* what) {
         if (!on) return;
         const double t = now_ms();
@@ -486,9 +490,12 @@ struct Trace {
 // error text of the last failed call without a ctx (nle_ctx_create)
 inline thread_local std::string g_create_err;
 
-// body of every C ABI entry point: exceptions become status codes, the ctx's workspace cache serves the DevBufs
+// body of every C ABI entry point: exceptions become status codes, the ctx's workspace cache serves the DevBufs, and the
+// ctx's snapshot of the environment switches is taken -- when the call begins, not when an entry point is entered from
+// inside another one on this thread: the nested one keeps its caller's snapshot
 template <typename Fn>
 int guard(nle_ctx* c, Fn&& fn) {
+    if (c && g_cur == nullptr) c->sw = nlesw::read_switches();
     CurCtx scope(c);
     try {
         fn();

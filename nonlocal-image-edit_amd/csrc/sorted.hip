@@ -436,95 +436,49 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
                 for (int b = 2; b < NC; ++b) gv[b] *= sCk[b];  // C_0 = C_1 = 1
             }
         }
-        // MOM: two (nC <= 12) or FOUR pixels of the chunk at a time.  A pixel's work is a few dependent chains of fp64
-        // operations -- the reciprocal's Newton steps, the Horner recurrences, the running powers -- and with 2-4 waves per
-        // SIMD their LATENCY, not their issue rate, is what the loop costs; four independent pixels give the scheduler
-        // 8-16 chains to interleave, and the state of a pixel is 8 doubles now that no e_b is kept.  Lanes past their own
-        // chunk (and the padding of the last block) work on column 0 and add exact zeros.
-        constexpr int PB = NC > 0 ? 1 : 2;  // pixels in flight per thread: interleaving 2 / 4 bought nothing (profiles/r4_pass_ablation.txt);
-                               // one leaves the registers for the next row's table row, requested BEFORE the loop (below)
-        auto pixels = [&](const unsigned (&c8)[PB], const int base) {
+        // MOM: one pixel in flight per thread; interleaving 2 / 4 bought nothing (profiles/r4_pass_ablation.txt).  Lanes
+        // past their own chunk (and the padding of the last block) work on column 0 and add exact zeros.
+        auto pixel_mom = [&](const unsigned c8, const int at) {  // at: the pixel's place in the chunk
             if constexpr (!MOM) return;
             else {
-            double e0[PB], rho[PB], rho2[PB], y[PB];
-            bool keep[PB];
-#pragma unroll
-            for (int k = 0; k < PB; ++k) {
-                e0[k] = e_at(sEa, c8[k], (unsigned)cb0 << 3);
-                rho[k] = e_at(sEa, c8[k], (unsigned)(cb0 + cs) << 3);
-                keep[k] = base + k < len;
-                y[k] = 1.0;
-            }
-            if (xmode) {
-#pragma unroll
-                for (int k = 0; k < PB; ++k) y[k] = cv_row[c8[k] >> 3] * (double)xv_row[c8[k] >> 3];  // apply: y_i = c_i x_i
-            }
-#pragma unroll
-            for (int k = 0; k < PB; ++k) {
-                double r0 = __builtin_amdgcn_rcp(e0[k]);  // e_0 is a normal number here (sorted_moments_ok)
-                r0 = fma(fma(-e0[k], r0, 1.0), r0, r0);
-                r0 = fma(fma(-e0[k], r0, 1.0), r0, r0);
-                rho[k] *= r0;
-                rho2[k] = rho[k] * rho[k];
-            }
+            const double e0 = e_at(sEa, c8, (unsigned)cb0 << 3);
+            double rho = e_at(sEa, c8, (unsigned)(cb0 + cs) << 3);
+            bool keep = at < len;
+            double y = 1.0;
+            if (xmode) y = cv_row[c8 >> 3] * (double)xv_row[c8 >> 3];  // apply: y_i = c_i x_i
+            double r0 = __builtin_amdgcn_rcp(e0);  // e_0 is a normal number here (sorted_moments_ok)
+            r0 = fma(fma(-e0, r0, 1.0), r0, r0);
+            r0 = fma(fma(-e0, r0, 1.0), r0, r0);
+            rho *= r0;
+            const double rho2 = rho * rho;
             if (recip) {
-                // even and odd coefficients: two Horner chains in rho^2 of half the length, per pixel
+                // even and odd coefficients: two Horner chains in rho^2 of half the length
                 constexpr int LE = (NC - 1) & ~1, LO = ((NC - 2) & ~1) + 1;   // highest even / odd index < NC
-                double se[PB], so[PB];
+                double se = q[LE], so = q[LO];
 #pragma unroll
-                for (int k = 0; k < PB; ++k) {
-                    se[k] = q[LE];
-                    so[k] = q[LO];
-                }
+                for (int b = LE - 2; b >= 0; b -= 2) se = fma(se, rho2, q[b]);
 #pragma unroll
-                for (int b = LE - 2; b >= 0; b -= 2) {
-#pragma unroll
-                    for (int k = 0; k < PB; ++k) se[k] = fma(se[k], rho2[k], q[b]);
-                }
-#pragma unroll
-                for (int b = LO - 2; b >= 1; b -= 2) {
-#pragma unroll
-                    for (int k = 0; k < PB; ++k) so[k] = fma(so[k], rho2[k], q[b]);
-                }
-#pragma unroll
-                for (int k = 0; k < PB; ++k) {
-                    const double sm = fma(so[k], rho[k], se[k]) * e0[k];
-                    double r = __builtin_amdgcn_rcp(sm);  // inplaceReciprocal (src/filter.cpp:42-54), recip0_d's arithmetic
-                    r = fma(fma(-sm, r, 1.0), r, r);
-                    r = fma(fma(-sm, r, 1.0), r, r);
-                    y[k] = r;
-                    keep[k] = keep[k] && fabs(sm) >= eps;
-                }
+                for (int b = LO - 2; b >= 1; b -= 2) so = fma(so, rho2, q[b]);
+                const double sm = fma(so, rho, se) * e0;
+                double r = __builtin_amdgcn_rcp(sm);  // inplaceReciprocal (src/filter.cpp:42-54), recip0_d's arithmetic
+                r = fma(fma(-sm, r, 1.0), r, r);
+                r = fma(fma(-sm, r, 1.0), r, r);
+                y = r;
+                keep = keep && fabs(sm) >= eps;
             }
-#pragma unroll
-            for (int k = 0; k < PB; ++k) {
-                const bool on = base + k < len;
-                y[k] = keep[k] ? y[k] : 0.0;  // the padding of the slot adds exact zeros
-                if (yb_row != nullptr && on) yb_row[c8[k] >> 3] = y[k];
-            }
-            // moments: acc_b += sum_k y_k e_0k rho_k^b, even and odd chains per pixel, the pixels summed pairwise
-            auto sum_pb = [](const double (&t)[PB]) {
-                if constexpr (PB == 4) return (t[0] + t[1]) + (t[2] + t[3]);
-                else if constexpr (PB == 2) return t[0] + t[1];
-                else return t[0];
-            };
-            double te[PB], to[PB];
-#pragma unroll
-            for (int k = 0; k < PB; ++k) {
-                te[k] = y[k] * e0[k];
-                to[k] = te[k] * rho[k];
-            }
-            acc[0] += sum_pb(te);
-            acc[1] += sum_pb(to);
+            y = keep ? y : 0.0;  // the padding of the slot adds exact zeros
+            if (yb_row != nullptr && at < len) yb_row[c8 >> 3] = y;
+            // moments: acc_b += y e_0 rho^b, an even and an odd chain
+            double te = y * e0, to = te * rho;
+            acc[0] += te;
+            acc[1] += to;
 #pragma unroll
             for (int b = 2; b < NC; b += 2) {
-#pragma unroll
-                for (int k = 0; k < PB; ++k) te[k] *= rho2[k];
-                acc[b] += sum_pb(te);
+                te *= rho2;
+                acc[b] += te;
                 if (b + 1 < NC) {
-#pragma unroll
-                    for (int k = 0; k < PB; ++k) to[k] *= rho2[k];
-                    acc[b + 1] += sum_pb(to);
+                    to *= rho2;
+                    acc[b + 1] += to;
                 }
             }
             }
@@ -568,27 +522,12 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
 #pragma unroll
             for (int b = 0; b < kMaxBlocks; ++b) {
                 if (4 * b >= wlen) break;
-                if constexpr (PB == 4) {
-                    const unsigned c8[PB] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
-                    pixels(c8, 4 * b);
-                    NLE_PIXEL_FENCE();
-                } else if constexpr (PB == 2) {
-                    const unsigned c8a[PB] = {idx[b].x & 0xffffu, idx[b].x >> 16}, c8b[PB] = {idx[b].y & 0xffffu, idx[b].y >> 16};
-                    pixels(c8a, 4 * b);
-                    NLE_PIXEL_FENCE();
-                    if (4 * b + 2 < wlen) {
-                        pixels(c8b, 4 * b + 2);
-                        NLE_PIXEL_FENCE();
-                    }
-                } else {
-                    const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
+                const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if (4 * b + k < wlen) {
-                            const unsigned c8one[PB] = {cs4[k]};
-                            pixels(c8one, 4 * b + k);
-                            NLE_PIXEL_FENCE();
-                        }
+                for (int k = 0; k < 4; ++k) {
+                    if (4 * b + k < wlen) {
+                        pixel_mom(cs4[k], 4 * b + k);
+                        NLE_PIXEL_FENCE();
                     }
                 }
             }
@@ -686,13 +625,11 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
     }
 }
 
-static int sorted_grid(int nrows) {
+static int sorted_grid(int nrows, const SortedRows& sr) {
     int ncu = 256;
     int dev = 0;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    int mult = 2;  // two 512-thread workgroups per CU, each walks its rows
-    if (const char* e = std::getenv("NLE_SORTED_WGS_PER_CU")) mult = std::max(1, std::atoi(e));  // measurement hook
-    return std::max(1, std::min(nrows, mult * ncu));
+    return std::max(1, std::min(nrows, sr.wgs_per_cu * ncu));
 }
 
 // Where the recurrence of column_factors stays inside the normal range of fp64 (with a wide margin): every e_b =
@@ -706,11 +643,10 @@ bool sorted_recurrence(GridSpec gs, double hx, double* kappa) {
     const double m_e = span * span / (hx * hx);
     const double m_rho = (2.0 * cs * umax + (2.0 * nC + 1.0) * cs * cs) / (hx * hx);
     *kappa = std::exp(-2.0 * cs * cs / (hx * hx));
-    const bool off = std::getenv("NLE_SORTED_TABLE") != nullptr;  // every column factor from the table
     // up to 12 columns the factors of a pixel stay in registers between its two uses (10 table reads per pixel at cfg4:
     // measured no slower than the recurrence, and bit-identical to the ecT table of the other kernels); beyond, the table
     // form reads every factor twice and the LDS pipe bounds it (cfg5, 30 columns: 1212 -> 861 us per pass)
-    return !off && gs.nSelCols > 12 && m_e < 500.0 && m_rho < 500.0;
+    return gs.nSelCols > 12 && m_e < 500.0 && m_rho < 500.0;
 }
 
 // Where the moment form of k_sorted_pass stays inside the normal range of fp64 with a wide margin: e_0 = exp(-u^2 / hx^2)
@@ -719,7 +655,6 @@ bool sorted_recurrence(GridSpec gs, double hx, double* kappa) {
 // Sinkhorn scalings (<= 1 / eps = 1e10 each).  The bound 500 (1e217) leaves 1e90 on either side; cfg5's 30 columns at
 // hx = W / 8 sit at 251.  Very narrow kernels (W / hx beyond ~20) keep the table / recurrence forms.
 bool sorted_moments_ok(GridSpec gs, double hx) {
-    if (std::getenv("NLE_SORTED_TABLE") != nullptr || std::getenv("NLE_SORTED_NO_MOMENTS") != nullptr) return false;
     const double cs = gs.colStep, umax = std::max<double>(gs.colOff, gs.W - 1 - gs.colOff), nC = gs.nSelCols;
     const double span = umax + nC * cs;
     return span * span / (hx * hx) < 500.0;
@@ -732,7 +667,7 @@ hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows
         return hipErrorInvalidValue;
     if (nrows_local <= 0) return hipSuccess;
     const size_t shm = sorted_lds_bytes(gs.W, (nC < 11 ? nC : 11) | 1);
-    const int grid = sorted_grid(nrows_local);
+    const int grid = sorted_grid(nrows_local, sr);
 #define NLE_SP1(NCV, CFV)                                                                                                 \
     {                                                                                                                     \
         if (shm > 48 * 1024) {                                                                                            \
@@ -1070,7 +1005,6 @@ __global__ __launch_bounds__(kT) void k_sorted_gsum(const unsigned short* __rest
 // where the recurrence above stays inside fp64's normal range (with a wide margin): every G_t and every rho_t, and the
 // exp(theta u) table; the same on the rows (the GEMM's F[r][s] is evaluated directly, no recurrence)
 bool sorted_gsum_ok(GridSpec gs, double hx) {
-    if (std::getenv("NLE_GRAM_PAIRS") != nullptr) return false;  // measurement: the pair-table form
     const double cs = gs.colStep, nC = gs.nSelCols, Wd = gs.W;
     // every centre m_t lies inside the image, so |c - m_t| < W: -log of the smallest G_t; and the |log| of the largest
     // rho_t = exp(theta (c - cb0) - (2 t + 1) cs^2 / (2 hx^2)) and of the exp(theta (64 k - cb0)) table
@@ -1087,7 +1021,7 @@ hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows_local, const S
     const double cs = gs.colStep, hx = sr.hx;
     const double theta = 2.0 * cs / (hx * hx), kappa1 = std::exp(-cs * cs / (2.0 * hx * hx));
     const size_t shm = sorted_lds_bytes(gs.W, 11) + (size_t)((((gs.W >> 6) + 2) & ~1) + 64) * sizeof(double);
-    const int grid = sorted_grid(nrows_local);
+    const int grid = sorted_grid(nrows_local, sr);
 #define NLE_GS(NTV)                                                                                                      \
     case NTV: {                                                                                                          \
         if (shm > 48 * 1024) {                                                                                           \
@@ -1203,7 +1137,7 @@ hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows_local, const S
     if (!tables_apply(gs) || gs.W > sorted_max_width()) return hipErrorInvalidValue;
     if (nrows_local <= 0) return hipSuccess;
     const size_t shm = sorted_lds_bytes(gs.W, 11);
-    const int grid = sorted_grid(nrows_local);
+    const int grid = sorted_grid(nrows_local, sr);
     if (nC > 11) {
         const int bb = gram_wide_bb(nC);
 #define NLE_SGW(NCV)                                                                                                    \

@@ -20,6 +20,15 @@ namespace nle {
 
 namespace {
 
+// the mode a ctx of this process is created with (NLE_MODE, default auto): what a train with NLEFilter::exact restores
+int default_mode() {
+    const char* m = std::getenv("NLE_MODE");
+    return m ? std::atoi(m) : NLE_MODE_AUTO;
+}
+
+// NLE_DEVICES as given (null: unset)
+const char* devices_env() { return std::getenv("NLE_DEVICES"); }
+
 // one context per process, created on first use (the reference keeps no global state; this one
 // only holds the HIP stream)
 nle_ctx* shared_ctx() {
@@ -29,15 +38,9 @@ nle_ctx* shared_ctx() {
         if (const char* e = std::getenv("NLE_DEVICE")) dev = std::atoi(e);
         if (nle_ctx_create(dev, nullptr, &ctx) != NLE_OK)
             throw std::runtime_error(std::string("nle: cannot create GPU context: ") + nle_last_error(nullptr));
-        if (const char* m = std::getenv("NLE_MODE")) nle_ctx_set_mode(ctx, std::atoi(m));
+        nle_ctx_set_mode(ctx, default_mode());
     }
     return ctx;
-}
-
-// the mode a ctx of this process is created with (NLE_MODE, default auto): what a train with NLEFilter::exact restores
-int default_mode() {
-    const char* m = std::getenv("NLE_MODE");
-    return m ? std::atoi(m) : NLE_MODE_AUTO;
 }
 
 void check(int status, nle_ctx* ctx) {
@@ -145,7 +148,7 @@ DeviceGroup* device_group(int p_samples) {
     static bool looked = false;
     if (!looked) {
         looked = true;
-        const char* e = std::getenv("NLE_DEVICES");
+        const char* e = devices_env();
         std::vector<int> devs;
         if (e) {
             std::string s(e);
@@ -172,7 +175,7 @@ DeviceGroup* device_group(int p_samples) {
             for (int r = 0; r < G; ++r) {
                 if (nle_ctx_create(devs[r], nullptr, &g->ctx[r]) != NLE_OK)
                     throw std::runtime_error(std::string("nle: cannot create GPU context: ") + nle_last_error(nullptr));
-                if (const char* m = std::getenv("NLE_MODE")) nle_ctx_set_mode(g->ctx[r], std::atoi(m));
+                nle_ctx_set_mode(g->ctx[r], default_mode());
                 g->ranks[r] = DeviceGroup::Rank{g, r};
             }
         }
@@ -615,7 +618,7 @@ void NLEFilter::trainForEnhancement(const Image& image, int nRowSamples, int nCo
     if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enhance RGB image.");
     if (nRowSamples > image.rows || nColSamples > image.cols)
         throw std::runtime_error("Number of samples per row and col must be <= that of image.");
-    if (std::getenv("NLE_DEVICES") != nullptr) {
+    if (devices_env() != nullptr) {
         int rs, ro, nr, cs, co, nc;
         if (nle_sample_grid(image.rows, image.cols, nRowSamples, nColSamples, &rs, &ro, &nr, &cs, &co, &nc) == NLE_OK &&
             device_group(nr * nc) != nullptr) {
