@@ -316,6 +316,17 @@ int nle_sinkhorn_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int 
                             int max_iter, double* h_u_c, double* h_u_r);
 int nle_gram64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, const double* h_u, double* h_G);
 int nle_row_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, const double* h_u, double* d_out);
+/* The small dense fp64 product of the p- and q-sized algebra (one launch, fp64 MFMA), all operands on the device:
+ * C(i,j) = dl[i] (sum_k A(i,k) dk[k] B(k,j)) dr[j] + add(i,j) for i < m, j < n, k < kk, every matrix given by its pointer
+ * and its (row stride, column stride) in doubles, so that transposes, sub-blocks and padded row- or column-major outputs
+ * need no copy; d_dl (m), d_dk (kk), d_dr (n) and d_add (strides rs_add, cs_add) may each be NULL.  Only the m x n entries
+ * of C are written.  d_add may be d_C with C's strides; C must not overlap A or B.  Sums run over k ascending in one
+ * chain per entry, A(i,k) dk[k] rounded first.  nle_gemm64s_window() is the number of k whose operands one wave loads
+ * in one go. */
+int nle_gemm64s(nle_ctx* ctx, int m, int n, int kk, const double* d_A, long long rs_a, long long cs_a, const double* d_B,
+                long long rs_b, long long cs_b, double* d_C, long long rs_c, long long cs_c, const double* d_dl,
+                const double* d_dk, const double* d_dr, const double* d_add, long long rs_add, long long cs_add);
+int nle_gemm64s_window(void);
 /* The hot path of NLE_MODE_EXACT_F64: d_Y = K d_X with K the exact N x N affinity of the plane d_lum (definition above;
  * integer valued in [0, 255], N = H W <= NLE_EXACT_MAX_PIXELS), regenerated on the fly.  d_X, d_Y: N x ld fp64, row per
  * pixel, ld a multiple of 4, ncols <= ld logical columns; d_Y must not alias d_X; its columns >= ncols come out zero.

@@ -614,6 +614,15 @@ class Context:
                                         C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    def gemm64s(self, m, n, kk, A, sA, B, sB, Cm, sC, dl=None, dk=None, dr=None, add=None, sadd=(0, 0)):
+        """nle_gemm64s on float64 CUDA tensors, in place in Cm: A, B, Cm (and add) are taken as flat buffers whose entry
+        (i, j) sits at i * s[0] + j * s[1] doubles from data_ptr(); dl, dk, dr: vectors or None"""
+        self._sync_in()
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        _check(lib().nle_gemm64s(self._h, m, n, kk, ptr(A), sA[0], sA[1], ptr(B), sB[0], sB[1], ptr(Cm), sC[0], sC[1],
+                                 ptr(dl), ptr(dk), ptr(dr), ptr(add), sadd[0], sadd[1]), self._h)
+        return Cm
+
     # ---- colour / denoise wrapper pieces (device tensors) ----
     def bgr2lab8(self, bgr):
         """`cvtColor(COLOR_BGR2Lab)` on an H x W x 3 uint8 image: (lab uint8 H x W x 3, L float32 H x W)"""

@@ -231,13 +231,132 @@ hipError_t ts_gemm64(hipStream_t s, const double* d_A, long long M, int lda, int
 // ------------------------------------------------------------------ small dense products (p-, q-sized), fp64 MFMA
 // C(i,j) = dl[i] (sum_k A(i,k) dk[k] B(k,j)) dr[j] + add(i,j), every matrix given by (pointer, row stride, column
 // stride) so that transposes, sub-blocks and row- or column-major outputs need no copies; dl, dk, dr, add optional.
-// One wave per 16 x 16 tile of C; the k loop is unrolled four MFMA steps deep so that 8 loads are in flight.
+// One wave per 16 x 16 tile of C.  These products are latency-bound (a 200^3 one is 16 MFLOP): what a tile costs is
+// the number of dependent memory round trips, so the k range is cut into windows of kGemm64sWin k, every a/b (and dk)
+// operand of a window is loaded into registers before its MFMA chain starts, and the next window's loads are issued
+// before the current window's MFMAs.  Two windows are therefore in flight together: kk <= 2 kGemm64sWin (cfg4:
+// kk <= 200) is ONE round trip, kk = 900 five instead of 57.  The epilogue's dl / dr / add are loaded up front too.
+// Register budget: a workgroup is 4 waves, one per SIMD, so a wave may use the SIMD's whole file (512 registers);
+// two windows hold 2 x 32 steps x (a, b, dk) x 2 registers = 384 (256 without dk).  No scratch.
+// It runs where a tile's latency is what the product costs: up to kGemm64sWindowedMaxTiles output tiles (one workgroup per
+// CU); larger outputs take k_gemm64s_stream below.  A launch with kk well under a window still issues the whole first
+// window's loads (the lanes past kk re-read k = 0): kk = 32 costs ~3 us more than in the streaming form.
+// Arithmetic is what the four-steps-at-a-time loop does: k ascending in one accumulator chain, a scaled by dk
+// before the MFMA, MFMA steps issued in groups of four up to the first group that starts at k >= kk, operands of
+// k >= kk (and of rows / columns outside the matrix) exactly 0.  Out-of-range lanes load from a clamped, valid
+// address and select 0 afterwards (a load under a per-element condition would be waited for one by one).
+constexpr int kGemm64sWinSteps = 32;                    // MFMA steps (of 4 k) per window
+constexpr int kGemm64sWin = 4 * kGemm64sWinSteps;       // k per window
+constexpr int kGemm64sWindowedMaxTiles = 4 * 256;       // output tiles up to which the windowed kernel runs: one workgroup per CU
+
+namespace {
+template <bool HAS_DK>
+struct Gemm64sWindow {
+    double a[kGemm64sWinSteps], b[kGemm64sWinSteps], d[HAS_DK ? kGemm64sWinSteps : 1];
+    // issues the loads of k in [k0, k0 + kGemm64sWin); kq = this lane's k within a step; kk >= 1.  The lane's pointers
+    // advance four k at a time (one add each: a product per load would cost more than the loads); a lane past the
+    // end reads k = 0 instead
+    __device__ __forceinline__ void load(const double* __restrict__ ap, long long csA, const double* __restrict__ bp,
+                                         long long rsB, const double* __restrict__ dk, int k0, int kq, int kk) {
+        const double* pa = ap + (long long)(k0 + kq) * csA;
+        const double* pb = bp + (long long)(k0 + kq) * rsB;
+        const double* pd = dk + (k0 + kq);
+#pragma unroll
+        for (int u = 0; u < kGemm64sWinSteps; ++u) {
+            const bool kok = k0 + 4 * u + kq < kk;
+            a[u] = *(kok ? pa : ap);
+            b[u] = *(kok ? pb : bp);
+            if constexpr (HAS_DK) d[u] = *(kok ? pd : dk);
+            pa += 4 * csA;
+            pb += 4 * rsB;
+            pd += 4;
+        }
+    }
+    // the window's MFMA chain, in groups of four steps like the loop it replaces (a group that starts at k >= kk is
+    // not issued: wave-uniform)
+    __device__ __forceinline__ void mfma(f64x4& acc, int k0, int kq, int kk, bool aok, bool bok) const {
+#pragma unroll
+        for (int g = 0; g < kGemm64sWinSteps / 4; ++g) {
+            if (k0 + 16 * g >= kk) break;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int u = 4 * g + v;
+                const bool kok = k0 + 4 * u + kq < kk;
+                double av = a[u];
+                if constexpr (HAS_DK) av *= d[u];
+                av = (aok && kok) ? av : 0.0;
+                const double bv = (bok && kok) ? b[u] : 0.0;
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+            }
+        }
+    }
+};
+}  // namespace
+
+template <bool HAS_DK>
 __global__ __launch_bounds__(256) void k_gemm64s(int m, int n, int kk, const double* __restrict__ A, long long rsA,
                                                  long long csA, const double* __restrict__ B, long long rsB, long long csB,
-                                                 double* __restrict__ C, long long rsC, long long csC,
-                                                 const double* __restrict__ dl, const double* __restrict__ dk,
-                                                 const double* __restrict__ dr, const double* __restrict__ add,
-                                                 long long rsD, long long csD) {
+                                                 double* C, long long rsC, long long csC, const double* __restrict__ dl,
+                                                 const double* __restrict__ dk, const double* __restrict__ dr,
+                                                 const double* add, long long rsD, long long csD) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, kq = lane >> 4;
+    const int ct = (n + 15) / 16, rt = (m + 15) / 16;
+    const int t = blockIdx.x * 4 + wave;
+    if (t >= rt * ct) return;  // wave-uniform
+    const int ti = t / ct, tj = t - ti * ct;
+    const int ai = ti * 16 + l15, bj = tj * 16 + l15;
+    const bool aok = ai < m, bok = bj < n;
+    const int bjc = min(bj, n - 1);
+    const double* ap = A + (long long)min(ai, m - 1) * rsA;
+    const double* bp = B + (long long)bjc * csB;
+    Gemm64sWindow<HAS_DK> w0, w1;
+    if (kk > 0) w0.load(ap, csA, bp, rsB, dk, 0, kq, kk);
+    if (kk > kGemm64sWin) w1.load(ap, csA, bp, rsB, dk, kGemm64sWin, kq, kk);
+    // the epilogue's operands, in flight with the first windows (add may be C itself: an entry is read and written by
+    // one lane only).  An absent operand is loaded from a valid address (C: m, n >= 1) and replaced afterwards: a branch round the
+    // load would put a full wait behind it
+    const double srv = *(dr ? dr + bjc : C);
+    const double sr = dr ? srv : 1.0;
+    double sl[4], ad[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int roc = min(ti * 16 + kq + 4 * e, m - 1);
+        const double slv = *(dl ? dl + roc : C);
+        const double adv = *(add ? add + ((long long)roc * rsD + (long long)bjc * csD) : C);
+        sl[e] = dl ? slv : 1.0;
+        ad[e] = adv;
+    }
+    f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < kk; k0 += 2 * kGemm64sWin) {
+        w0.mfma(acc, k0, kq, kk, aok, bok);
+        if (k0 + 2 * kGemm64sWin < kk) w0.load(ap, csA, bp, rsB, dk, k0 + 2 * kGemm64sWin, kq, kk);
+        if (k0 + kGemm64sWin < kk) {
+            w1.mfma(acc, k0 + kGemm64sWin, kq, kk, aok, bok);
+            if (k0 + 3 * kGemm64sWin < kk) w1.load(ap, csA, bp, rsB, dk, k0 + 3 * kGemm64sWin, kq, kk);
+        }
+    }
+    if (bok) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int ro = ti * 16 + kq + 4 * e;
+            if (ro < m) {
+                double v = sl[e] * acc[e] * sr;
+                if (add) v += ad[e];
+                C[(long long)ro * rsC + (long long)bj * csC] = v;
+            }
+        }
+    }
+}
+
+// The same product for outputs of many tiles: four MFMA steps' operands in flight per wave, few registers, up to eight
+// waves per SIMD.  Beyond about one workgroup per CU the product is bound by throughput, not by one tile's latency, and
+// the windowed kernel's one wave per SIMD loses (m = n = 800 .. 900: measured ~30 % slower).  Same arithmetic, same bits.
+__global__ __launch_bounds__(256) void k_gemm64s_stream(int m, int n, int kk, const double* __restrict__ A, long long rsA,
+                                                        long long csA, const double* __restrict__ B, long long rsB,
+                                                        long long csB, double* C, long long rsC, long long csC,
+                                                        const double* __restrict__ dl, const double* __restrict__ dk,
+                                                        const double* __restrict__ dr, const double* add, long long rsD,
+                                                        long long csD) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, kq = lane >> 4;
     const int ct = (n + 15) / 16, rt = (m + 15) / 16;
     const int t = blockIdx.x * 4 + wave;
@@ -274,13 +393,23 @@ __global__ __launch_bounds__(256) void k_gemm64s(int m, int n, int kk, const dou
     }
 }
 
+int gemm64s_window() { return kGemm64sWin; }
+
 hipError_t gemm64s(hipStream_t s, int m, int n, int kk, const double* A, long long rsA, long long csA, const double* B,
                    long long rsB, long long csB, double* C, long long rsC, long long csC, const double* dl, const double* dk,
                    const double* dr, const double* add, long long rsD, long long csD) {
     if (m <= 0 || n <= 0) return hipSuccess;
     const long long ntiles = (long long)((m + 15) / 16) * ((n + 15) / 16);
-    hipLaunchKernelGGL(k_gemm64s, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, s, m, n, kk, A, rsA, csA, B, rsB, csB, C, rsC,
-                       csC, dl, dk, dr, add, rsD, csD);
+    const dim3 grid((unsigned)((ntiles + 3) / 4));
+    if (ntiles > kGemm64sWindowedMaxTiles)
+        hipLaunchKernelGGL(k_gemm64s_stream, grid, dim3(256), 0, s, m, n, kk, A, rsA, csA, B, rsB, csB, C, rsC, csC, dl, dk, dr,
+                           add, rsD, csD);
+    else if (dk)
+        hipLaunchKernelGGL(k_gemm64s<true>, grid, dim3(256), 0, s, m, n, kk, A, rsA, csA, B, rsB, csB, C, rsC, csC, dl, dk, dr,
+                           add, rsD, csD);
+    else
+        hipLaunchKernelGGL(k_gemm64s<false>, grid, dim3(256), 0, s, m, n, kk, A, rsA, csA, B, rsB, csB, C, rsC, csC, dl, dk, dr,
+                           add, rsD, csD);
     return hipGetLastError();
 }
 
@@ -505,14 +634,19 @@ hipError_t scatter_rows64(hipStream_t s, const double* d_src, const long long* d
     return hipGetLastError();
 }
 
-// X (m x n column-major, leading dimension m) <- diag(dl) X
-__global__ void k_scale_rows64(double* __restrict__ X, int m, int n, const double* __restrict__ dl) {
+// Y(i, j) = X[j m + i] dl[i]: X m x n column-major (leading dimension m), Y in any layout (row stride, column stride)
+__global__ void k_scale_rows64_to(const double* __restrict__ X, int m, int n, const double* __restrict__ dl,
+                                  double* __restrict__ Y, long long rsY, long long csY) {
     const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < (long long)m * n) X[f] *= dl[f % m];
+    if (f >= (long long)m * n) return;
+    const int i = (int)(f % m), j = (int)(f / m);
+    Y[i * rsY + j * csY] = X[f] * dl[i];
 }
-hipError_t scale_rows64(hipStream_t s, double* d_X, int m, int n, const double* d_dl) {
+hipError_t scale_rows64_to(hipStream_t s, const double* d_X, int m, int n, const double* d_dl, double* d_Y, long long rsY,
+                           long long csY) {
     if (m <= 0 || n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_scale_rows64, dim3((unsigned)(((long long)m * n + 255) / 256)), dim3(256), 0, s, d_X, m, n, d_dl);
+    hipLaunchKernelGGL(k_scale_rows64_to, dim3((unsigned)(((long long)m * n + 255) / 256)), dim3(256), 0, s, d_X, m, n, d_dl, d_Y,
+                       rsY, csY);
     return hipGetLastError();
 }
 

@@ -213,6 +213,9 @@ hipError_t gemm64s(hipStream_t s, int m, int n, int kk, const double* A, long lo
                    long long rsB, long long csB, double* C, long long rsC, long long csC, const double* dl = nullptr,
                    const double* dk = nullptr, const double* dr = nullptr, const double* add = nullptr, long long rsD = 0,
                    long long csD = 0);
+// Two kernels, one arithmetic (bit-identical results): up to 1024 16 x 16 output tiles (one workgroup per CU) the windowed
+// form (all of a tile's operands in flight before its MFMA chain; one wave per SIMD), beyond it the streaming loop
+int gemm64s_window();  // k per operand window of k_gemm64s (two windows are in flight together)
 // one pass over X (M x ld, logical width w <= 2048: columns >= w are never read); d_t_in, d_lam and the rows of
 // d_partial have (w + 3) & ~3 entries
 hipError_t rowpass64(hipStream_t s, int mode, const double* d_X, long long M, int ld, int w, const double* d_t_in,
@@ -225,7 +228,9 @@ hipError_t apply_expand64(hipStream_t s, const double* d_V, long long M, int ld,
                           long long ystride);
 hipError_t scatter_rows64(hipStream_t s, const double* d_src, const long long* d_idx, int n, int ld, double* d_X, long long M);
 hipError_t to_f32(hipStream_t s, const double* d_X, long long n, float* d_out);
-hipError_t scale_rows64(hipStream_t s, double* d_X, int m, int n, const double* d_dl);  // X (m x n col-major) <- diag(dl) X
+// Y(i, j) = X(i, j) dl[i], X m x n col-major (leading dimension m), Y by (row stride, column stride)
+hipError_t scale_rows64_to(hipStream_t s, const double* d_X, int m, int n, const double* d_dl, double* d_Y, long long rsY,
+                           long long csY);
 
 // ---- one-workgroup Householder tridiagonalisation (tridiag.hip): Q n x n col-major (lower triangle read), n <= tridiag_max_n();
 // outputs in the conventions of nleh::tridiag_reduce (V: u_i in column i rows 0..i-1; hs; d, e)
@@ -294,6 +299,10 @@ hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows, const SortedR
 bool sorted_recurrence(GridSpec gs, double hx, double* kappa);
 int sorted_max_width();
 size_t sorted_scol_elems(int W, int nrows_local);  // allocation size of SortedRows::scol
+// the inverse of sort_rows: this rank's rows of the plane (nrows_local x W fp32 at d_out) from the sorted rows and the
+// sample values (the sample pixels are not in the sorted rows); exact for the integer-valued plane sort_rows took
+hipError_t rows_from_sorted(hipStream_t s, GridSpec gs, int row0, int nrows_local, const SortedRows& sr, const Sample4* d_samples,
+                            int p, float* d_out);
 // expand half of the sample-space apply on the sorted rows (nl <= sorted_expand_layers() layers per launch)
 int sorted_expand_layers(GridSpec gs);
 hipError_t sorted_expand(hipStream_t s, GridSpec gs, int nrows, const SortedRows& sr, const double* d_g, size_t gstride, int nl,

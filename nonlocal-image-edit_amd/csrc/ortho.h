@@ -43,7 +43,8 @@ struct Ortho {
 struct OrthoSS {
     int q = 0, K = 0, r_wa = 0, r_q = 0;
     bool chol_wa = false;
-    std::vector<double> Sq, D, Vrows;  // D: p x K, Vrows: p x K (col-major)
+    std::vector<double> Sq, D, Vrows;  // D: p x K, Vrows: p x K (col-major); empty when they were left on the device (DeviceDV)
+    std::vector<std::vector<double>> staged;  // host sources of uploads that may still be on the stream (ortho_ss_device with `place`)
     // state between the two halves
     int p = 0, r = 0;
     std::vector<double> cA, rA, Kr, P, Wa, S, St, A2;  // Q = A2 + S^T (Wab Wab^T) S,  St = S^T
@@ -58,9 +59,16 @@ Ortho orthogonalize_host(const Nystrom& ny, int p, const std::vector<double>& u_
 void ortho_ss_prepare(OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c, const std::vector<double>& sA_r,
                       bool literal_q, bool force_eig, bool trace);
 void ortho_ss_finish(OrthoSS& o, std::vector<double> Gk, int n_eig, int topk_solver, bool trace);
+// where ortho_ss_device leaves D and Vrows when its caller wants them on the device: two p x ldd row-major buffers, ldd >= K,
+// whose padding the caller has zeroed (on the same stream)
+struct DeviceDV {
+    double *D, *Vrows;
+    int ldd;
+};
 // sample-space form with the p x p products (and, where use_dev_solver says so, the solvers) on the device
 void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c,
                      const std::vector<double>& sA_r, double* d_Gk, int n_eig, const std::function<void()>& enqueue_gram,
-                     const std::function<void()>& reduce_gram, double* host_ms, double* host_overlapped_ms, Trace& tr);
+                     const std::function<void()>& reduce_gram, double* host_ms, double* host_overlapped_ms, Trace& tr,
+                     const std::function<DeviceDV(int)>& place = nullptr);
 
 }  // namespace nlep

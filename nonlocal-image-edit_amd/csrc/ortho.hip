@@ -684,10 +684,25 @@ void top_eigenpairs_Qt(nle_ctx* c, OrthoSS& o, const WaRoot& w, const double* d_
     tr.mark(t.on_device ? "ss: eigenvectors of Q (inverse iteration on the host, back-transformation enqueued)" : "ss: eig(Q) (host)");
 }
 
-// T2 = F Vt Sq^-1/2, D = P[:, :q] diag(rA) T2, Vrows = [Wa T2; diag(cA_B) Kr_B D], all on the device; D and Vrows come back
-void D_and_Vrows(hipStream_t st, OrthoSS& o, const SsDevice& dv, const WaRoot& w, QtEig& t, const double* d_Wa, Trace& tr) {
+// T2 = F Vt Sq^-1/2, D = P[:, :q] diag(rA) T2, Vrows = [Wa T2; diag(cA_B) Kr_B D], all on the device.  Without `place`
+// D and Vrows come back to the host (o.D, o.Vrows, p x K column-major) and the stream is drained.  With it they are
+// written where place(K) says (DeviceDV: p x ldd row-major, padding already zero) and nothing comes back: o.D and
+// o.Vrows stay empty, the products are only enqueued, and the host sources of the two uploads move into o.staged,
+// which the caller keeps until it has drained the stream.  The products are the same either way (gemm64s takes any
+// strides), so are the bits.
+void D_and_Vrows(hipStream_t st, OrthoSS& o, const SsDevice& dv, const WaRoot& w, QtEig& t, const double* d_Wa,
+                 const std::function<DeviceDV(int)>& place, Trace& tr) {
     const int p = o.p, r = o.r, q = o.q, m = w.m, K = o.K;
-    DevBuf<double> d_sv(K), d_T2((size_t)q * K), d_D((size_t)p * K), d_Vr((size_t)p * K);
+    DevBuf<double> d_sv(K), d_T2((size_t)q * K), d_Dh, d_Vh;
+    DeviceDV out{nullptr, nullptr, 0};
+    if (place) out = place(K);
+    double *d_D = out.D, *d_Vr = out.Vrows;
+    long long rs = out.ldd, cs = 1;  // (a, k) of D and Vrows at a * rs + k * cs
+    if (!place) {
+        d_Dh.alloc((size_t)p * K);
+        d_Vh.alloc((size_t)p * K);
+        d_D = d_Dh.p, d_Vr = d_Vh.p, rs = 1, cs = p;
+    }
     if (!t.on_device) {
         t.d_Vq.alloc((size_t)m * K);
         HIP_OK(hipMemcpyAsync(t.d_Vq.p, t.Vq.data(), (size_t)m * K * sizeof(double), hipMemcpyHostToDevice, st));
@@ -695,19 +710,26 @@ void D_and_Vrows(hipStream_t st, OrthoSS& o, const SsDevice& dv, const WaRoot& w
     HIP_OK(hipMemcpyAsync(d_sv.p, t.sv.data(), K * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_OK(nlek::gemm64s(st, q, K, m, w.d_F.p, 1, q, t.d_Vq.p, 1, m, d_T2.p, 1, q, nullptr, nullptr, d_sv.p));
     if (r < p) {
-        HIP_OK(nlek::gemm64s(st, p, K, q, dv.P.p, 1, p, d_T2.p, 1, q, d_D.p, 1, p, nullptr, dv.rA.p));  // first q columns of P
+        HIP_OK(nlek::gemm64s(st, p, K, q, dv.P.p, 1, p, d_T2.p, 1, q, d_D, rs, cs, nullptr, dv.rA.p));  // first q columns of P
     } else {  // P = I, q == p: D = diag(rA) T2
-        HIP_OK(hipMemcpyAsync(d_D.p, d_T2.p, (size_t)q * K * sizeof(double), hipMemcpyDeviceToDevice, st));
-        HIP_OK(nlek::scale_rows64(st, d_D.p, p, K, dv.rA.p));
+        HIP_OK(nlek::scale_rows64_to(st, d_T2.p, p, K, dv.rA.p, d_D, rs, cs));
     }
-    HIP_OK(nlek::gemm64s(st, q, K, q, d_Wa, 1, q, d_T2.p, 1, q, d_Vr.p, 1, p));  // top block of :327
+    HIP_OK(nlek::gemm64s(st, q, K, q, d_Wa, 1, q, d_T2.p, 1, q, d_Vr, rs, cs));  // top block of :327
     if (q < p)
-        HIP_OK(nlek::gemm64s(st, p - q, K, p, dv.Kr.p + q, 1, p, d_D.p, 1, p, d_Vr.p + q, 1, p, dv.cA.p + q));
-    o.D.resize((size_t)p * K);
-    o.Vrows.resize((size_t)p * K);
-    HIP_OK(hipMemcpyAsync(o.D.data(), d_D.p, o.D.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(o.Vrows.data(), d_Vr.p, o.Vrows.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(nlek::gemm64s(st, p - q, K, p, dv.Kr.p + q, 1, p, d_D, rs, cs, d_Vr + (long long)q * rs, rs, cs, dv.cA.p + q));
+    if (place && !t.on_device) {
+        o.staged.push_back(std::move(t.Vq));
+        o.staged.push_back(std::move(t.sv));
+        tr.mark("ss: D, Vrows enqueued (device, in the filter's layout)");
+        return;
+    }
+    if (!place) {
+        o.D.resize((size_t)p * K);
+        o.Vrows.resize((size_t)p * K);
+        HIP_OK(hipMemcpyAsync(o.D.data(), d_D, o.D.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(o.Vrows.data(), d_Vr, o.Vrows.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));  // (the device eigensolver's staging block dies with t)
     tr.mark("ss: D, Vrows on the device");
 }
 
@@ -717,11 +739,13 @@ void D_and_Vrows(hipStream_t st, OrthoSS& o, const SsDevice& dv, const WaRoot& w
 // keeps what is inherently serial -- the two symmetric eigensolves (Wa, Q) or their Cholesky shortcut.  `d_Gk`: the local
 // Gram matrix (p x p, device); `enqueue_gram` puts the Gram kernels on the stream (they run under the root of Wa),
 // `reduce_gram` sums d_Gk over the ranks.  On return o.K, o.Sq, o.D, o.Vrows (host, column-major p x K), o.r_wa, o.r_q,
-// o.chol_wa are set exactly as ortho_ss_prepare + ortho_ss_finish set them.
+// o.chol_wa are set exactly as ortho_ss_prepare + ortho_ss_finish set them.  `place` (optional): D and Vrows are left
+// on the device instead, in the buffers place(K) returns (see D_and_Vrows); then the stream may still be busy on return.
 // At cfg4 (p = 200) this takes ~0.6 ms of 200^3 host products off the critical path, at cfg5 (p = 900) ~50 ms.
 void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c,
                      const std::vector<double>& sA_r, double* d_Gk, int n_eig, const std::function<void()>& enqueue_gram,
-                     const std::function<void()>& reduce_gram, double* host_ms, double* host_overlapped_ms, Trace& tr) {
+                     const std::function<void()>& reduce_gram, double* host_ms, double* host_overlapped_ms, Trace& tr,
+                     const std::function<DeviceDV(int)>& place) {
     const int q = ny.r;
     hipStream_t st = c->stream;
     SsDevice dv;
@@ -761,7 +785,7 @@ void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std
     form_Qt(st, o, dv, w, d_Gk, reduce_gram, d_Qm.p);
     QtEig t;
     top_eigenpairs_Qt(c, o, w, d_Qm.p, n_eig, t, host_ms, tr);
-    D_and_Vrows(st, o, dv, w, t, d_Wa.p, tr);
+    D_and_Vrows(st, o, dv, w, t, d_Wa.p, place, tr);
 }
 
 }  // namespace nlep

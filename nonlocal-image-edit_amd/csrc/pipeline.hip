@@ -534,7 +534,17 @@ std::vector<double> padded_rows(const std::vector<double>& X, int p, int K, int 
 nlep::TableFilter::TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet& ss, double hx, double hy, int row0_, int nrows_)
     : gs(ss.gs), p(ss.p), P64(nlek::sink_pass_ld(ss.p)), row0(row0_), nrows(nrows_), nsw(nsw_of(hx)), npw(nsw_of(hy)),
       lum(d_lum), samples(upload_samples(ctx, ss, nlek::sink_pass_ld(ss.p))), c((size_t)nrows_ * ss.gs.W),
-      er((size_t)nrows_ * ss.gs.nSelRows), ecT((size_t)ss.gs.nSelCols * ss.gs.W), Ep((size_t)256 * ss.p) {
+      er((size_t)nrows_ * ss.gs.nSelRows), ecT((size_t)ss.gs.nSelCols * ss.gs.W), Ep((size_t)256 * ss.p),
+      sample_loc((size_t)ss.p) {
+    {  // the samples' pixel index within this rank's rows (-1: another rank's): known before the first kernel
+        const long long pix0 = (long long)row0_ * ss.gs.W, M = (long long)nrows_ * ss.gs.W;
+        h_sample_loc.resize(p);
+        for (int a = 0; a < p; ++a) {
+            const long long loc = ss.pix[a] - pix0;
+            h_sample_loc[a] = (loc >= 0 && loc < M) ? loc : -1;
+        }
+        HIP_OK(hipMemcpyAsync(sample_loc.p, h_sample_loc.data(), p * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    }
     PROFILED(ctx, NLE_K_SMALL, nlek::hist_tables(ctx->stream, gs, samples.p, p, hx, hy, row0, nrows, er.p, ecT.p, Ep.p));
     const nlesw::Switches& sw = ctx->sw;
     if (gs.W > nlek::sorted_max_width() || sw.no_sorted_rows) return;
@@ -563,6 +573,18 @@ nlep::TableFilter::TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet
         sorted.hx = hx;
     }
 }
+
+// The training plane for the consumers that read it after training (V on demand).  On the level-sorted path it was not
+// kept: plane_into rebuilds this rank's rows from the sorted rows and the sample values into `dst` -- exact, the plane is
+// integer valued -- and returns the virtual base of the full image; where the plane is held it returns that and leaves
+// `dst` alone.  ensure_plane keeps the rebuilt rows in `slab` (V is being materialised: 4 bytes per pixel beside 4 K).
+const float* nlep::TableFilter::plane_into(nle_ctx* ctx, DevBuf<float>& dst) const {
+    if (lum || !sorted_rows() || nrows <= 0) return lum;
+    dst.alloc((size_t)nrows * gs.W);
+    PROFILED(ctx, NLE_K_SMALL, nlek::rows_from_sorted(ctx->stream, gs, row0, nrows, sorted, samples.p, p, dst.p));
+    return dst.p - (long long)row0 * gs.W;
+}
+void nlep::TableFilter::ensure_plane(nle_ctx* ctx) { lum = plane_into(ctx, slab); }
 
 namespace {
 
@@ -604,40 +626,54 @@ void train_tables(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleSet
         ProfObserver obs(c, gmap);
         HIP_OK(nlek::gram_hist(c->stream, view, d_gpart.p, d_G.p, &obs));
     };
-    OrthoSS o;
+    // what defines V = diag(c) K_AB^T D implicitly (K' <= 128: tables_apply) stays on the device: D and the exact rows of V
+    // at the sample pixels, p x ldd row-major, zero padded -- the operands of k_apply_small and project64
+    auto place = [&](int K) {
+        t->ldd = nlek::project64_ld(K);
+        const size_t n = (size_t)p * t->ldd;
+        t->D.alloc(n);
+        t->Vrows.alloc(n);
+        HIP_OK(hipMemsetAsync(t->D.p, 0, n * sizeof(double), c->stream));
+        HIP_OK(hipMemsetAsync(t->Vrows.p, 0, n * sizeof(double), c->stream));
+        return DeviceDV{t->D.p, t->Vrows.p, t->ldd};
+    };
+    OrthoSS o;  // (outlives the last synchronisation below: o.staged)
     if (c->topk_solver == 0) {
-        // the q-sized products run on the device, the eigensolves on the host
+        // the q-sized products run on the device, the eigensolves on the host; D and Vrows are written where apply reads
+        // them and never visit the host
         ortho_ss_device(c, o, ny, p, sk.sA_c, sk.sA_r, d_G.p, n_eig, enqueue_gram, [&] { all_reduce(c, d_G.p, g_elems); },
-                        &ms->host, &ms->host_overlapped, tr);
+                        &ms->host, &ms->host_overlapped, tr, place);
         tm_g.stop();
     } else {
         o = ortho_ss_host(c, ny, p, sk, enqueue_gram, d_G.p, g_elems, /*tile16=*/false, n_eig, tm_g, ms, tr);
     }
     adopt_ortho(f, o);
 
-    // keep what defines V = diag(c) K_AB^T D implicitly (K' <= 128: tables_apply); the projection runs only if somebody asks
     tm_p.start();
-    t->ldd = nlek::project64_ld(o.K);
-    const std::vector<double> Dp = padded_rows(o.D, p, o.K, t->ldd), Vr = padded_rows(o.Vrows, p, o.K, t->ldd);
-    std::vector<long long> sloc(p);
-    for (int a = 0; a < p; ++a) {
-        const long long loc = ss.pix[a] - pix0;
-        sloc[a] = (loc >= 0 && loc < M) ? loc : -1;
+    std::vector<double> Dp, Vr;  // host route only: staged until the synchronisation below
+    if (c->topk_solver != 0) {
+        const DeviceDV dst = place(o.K);
+        Dp = padded_rows(o.D, p, o.K, dst.ldd), Vr = padded_rows(o.Vrows, p, o.K, dst.ldd);
+        HIP_OK(hipMemcpyAsync(dst.D, Dp.data(), Dp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_OK(hipMemcpyAsync(dst.Vrows, Vr.data(), Vr.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
-    t->D.alloc(Dp.size());
-    HIP_OK(hipMemcpyAsync(t->D.p, Dp.data(), Dp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    t->Vrows.alloc(Vr.size());
-    t->sample_loc.alloc(p);
-    t->slab.alloc((size_t)M);
-    HIP_OK(hipMemcpyAsync(t->Vrows.p, Vr.data(), Vr.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(t->sample_loc.p, sloc.data(), p * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-    HIP_OK(hipMemcpyAsync(t->slab.p, d_lum + pix0, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));  // the host staging vectors go out of scope
-    t->lum = t->slab.p - pix0;  // the caller's plane is not ours to keep
+    // the caller's plane is not ours to keep.  With level-sorted rows nothing on the apply path reads the plane, and the
+    // rows hold it exactly: it is rebuilt if V is ever asked for (TableFilter::ensure_plane).  Without them the unsorted
+    // kernels read it in every apply: keep a copy of this rank's rows.
+    if (t->sorted_rows()) {
+        t->lum = nullptr;
+    } else {
+        t->slab.alloc((size_t)M);
+        HIP_OK(hipMemcpyAsync(t->slab.p, d_lum + pix0, (size_t)M * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        t->lum = t->slab.p - pix0;
+    }
     t->drop_gram_only();
     f->tables = std::move(t);
-    f->h_Vrows = o.Vrows;
     tm_p.stop();
+    // the one synchronisation after eig(Q): the filter is valid from here, and o.staged / Dp / Vr may go.  (On the stream and
+    // not left to the timers' hipEventSynchronize: with that wait alone the gap from the last product to apply's first copy
+    // was 176 us, with this one 101 us: profiles/r10_handover.txt, section 2)
+    HIP_OK(hipStreamSynchronize(c->stream));
     ms->take(tm_s, tm_g, tm_p);
 }
 
@@ -789,6 +825,19 @@ void train_stream64(nle_ctx* c, nle_filter* f, const float* d_lum, const SampleS
     ms->take(tm_s, tm_g, tm_p);
 }
 
+// the exact sample rows of V of a table filter on the host, p x K column-major (scatter_sample_rows' operand), fetched from
+// the device: only V on demand reads them
+std::vector<double> host_Vrows(const nle_filter* f) {
+    nle_ctx* c = f->ctx;
+    const TableFilter& t = *f->tables;
+    std::vector<double> rows((size_t)t.p * t.ldd), out((size_t)t.p * f->K);
+    HIP_OK(hipMemcpyAsync(rows.data(), t.Vrows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < f->K; ++k)
+        for (int a = 0; a < t.p; ++a) out[(size_t)k * t.p + a] = rows[(size_t)a * t.ldd + k];
+    return out;
+}
+
 // materialise V = diag(c) K D of a table filter (projection kernel + exact sample rows)
 void ensure_V(nle_filter* f) {
     if (f->d_V) return;
@@ -802,12 +851,13 @@ void ensure_V(nle_filter* f) {
         return;
     }
     if (!f->tables) return;
+    f->tables->ensure_plane(c);
     const TableFilter& t = *f->tables;
     const long long M = f->n_local, pix0 = (long long)f->row0 * f->W;
     DevBuf<float> d_V((size_t)std::max<long long>(M, 1) * f->ldv);
     PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, t.lum, t.gs, t.samples.p, t.p, t.nsw, t.npw, pix0, M, t.D.p, f->K,
                                                t.c.p, d_V.p, f->ldv));
-    scatter_sample_rows(c, f->h_sample_pix, f->p, f->h_Vrows, f->K, f->ldv, pix0, M, d_V.p);
+    scatter_sample_rows(c, f->h_sample_pix, f->p, host_Vrows(f), f->K, f->ldv, pix0, M, d_V.p);
     HIP_OK(hipStreamSynchronize(c->stream));
     f->v_bytes = d_V.n * sizeof(float);
     f->d_V = d_V.take();
@@ -1615,6 +1665,20 @@ int nle_row_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int ld, i
     });
 }
 
+int nle_gemm64s(nle_ctx* ctx, int m, int n, int kk, const double* d_A, long long rs_a, long long cs_a, const double* d_B,
+                long long rs_b, long long cs_b, double* d_C, long long rs_c, long long cs_c, const double* d_dl,
+                const double* d_dk, const double* d_dr, const double* d_add, long long rs_add, long long cs_add) {
+    if (!ctx || !d_A || !d_B || !d_C || m < 0 || n < 0 || kk < 0) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        HIP_OK(hipSetDevice(ctx->device));
+        HIP_OK(nlek::gemm64s(ctx->stream, m, n, kk, d_A, rs_a, cs_a, d_B, rs_b, cs_b, d_C, rs_c, cs_c, d_dl, d_dk, d_dr, d_add,
+                             rs_add, cs_add));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int nle_gemm64s_window(void) { return nlek::gemm64s_window(); }
+
 int nle_train(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
               double hy, int n_sinkhorn_iter, int n_eigen_vectors, nle_filter** out) {
     if (!ctx || !d_lum || !out) return NLE_ERR_INVALID;
@@ -1745,6 +1809,8 @@ int nle_filter_eigvec_range(const nle_filter* f, int ncols, double* h_min, doubl
         DevBuf<float> d_tmp;
         if (!f->d_V && f->tables) {
             const TableFilter& t = *f->tables;
+            DevBuf<float> d_plane;  // the filter stays as it is: a plane it does not hold is rebuilt into this temporary
+            const float* lum = t.plane_into(c, d_plane);
             const long long M = f->n_local, pix0 = (long long)f->row0 * f->W;
             const int ldd_full = t.ldd, ldd = nlek::project64_ld(ncols);
             std::vector<double> Dfull((size_t)f->p * ldd_full), Dk((size_t)f->p * ldd, 0.0);
@@ -1756,9 +1822,9 @@ int nle_filter_eigvec_range(const nle_filter* f, int ncols, double* h_min, doubl
             HIP_OK(hipMemcpyAsync(d_Dk.p, Dk.data(), Dk.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
             ldc = ld4(ncols);
             d_tmp.alloc((size_t)std::max<long long>(M, 1) * ldc);
-            PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, t.lum, t.gs, t.samples.p, t.p, t.nsw, t.npw, pix0, M, d_Dk.p,
+            PROFILED(c, NLE_K_PROJECT, nlek::project64(c->stream, lum, t.gs, t.samples.p, t.p, t.nsw, t.npw, pix0, M, d_Dk.p,
                                                        ncols, t.c.p, d_tmp.p, ldc));
-            scatter_sample_rows(c, f->h_sample_pix, f->p, f->h_Vrows, ncols, ldc, pix0, M, d_tmp.p);
+            scatter_sample_rows(c, f->h_sample_pix, f->p, host_Vrows(f), ncols, ldc, pix0, M, d_tmp.p);
             HIP_OK(hipStreamSynchronize(c->stream));  // Dk (host) is consumed
             d_cols = d_tmp.p;
         } else {

@@ -108,7 +108,6 @@ struct nle_filter {
     std::unique_ptr<nlep::TableFilter> tables;
     float* d_plane = nullptr;  // nle_train_host: the uploaded training plane (full image), kept for apply(h_x == NULL)
     size_t plane_bytes = 0;
-    std::vector<double> h_Vrows;                  // p x K col-major: exact rows of V at the sample pixels
     std::vector<long long> h_sample_pix;          // the sample pixels, in the order of the sample set (ascending)
 };
 
@@ -207,7 +206,9 @@ struct TableFilter {
     nlek::GridSpec gs{};
     int p = 0, P64 = 0, row0 = 0, nrows = 0, ldd = 0;  // P64 = sink_pass_ld(p): stride of the p-sized vectors, padding of `samples`
     float nsw = 0.f, npw = 0.f;
-    const float* lum = nullptr;  // virtual base of the full image: the caller's plane while training, `slab` afterwards
+    // virtual base of the full image: the caller's plane while training; afterwards `slab`, or -- with level-sorted rows,
+    // where no apply kernel reads the plane -- null until ensure_plane() has rebuilt `slab`
+    const float* lum = nullptr;
     DevBuf<float4> samples;
     DevBuf<double> c, er, ecT, Ep;  // c_i per local pixel (0 at sample pixels; the last Sinkhorn pass writes it); hist_tables
     // level-sorted rows of the training plane (sorted.hip) where they exist; `sorted` is filled by the constructor and nowhere
@@ -216,13 +217,18 @@ struct TableFilter {
     DevBuf<uint2> desc;
     DevBuf<double> E, E2;
     nlek::SortedRows sorted{};
-    // added when training ends (train_tables): the kept eigenvectors in sample space and the exact rows of V at the sample
-    // pixels (p x ldd row-major), the samples' local pixel index (-1 off this rank), this rank's slab of the training plane
-    DevBuf<double> D, Vrows;
+    // the samples' local pixel index (-1 off this rank); h_sample_loc is the upload's source
     DevBuf<long long> sample_loc;
+    std::vector<long long> h_sample_loc;
+    // added when training ends (train_tables): the kept eigenvectors in sample space and the exact rows of V at the sample
+    // pixels (p x ldd row-major, written on the device by the orthogonalisation's last products), and this rank's rows of
+    // the training plane (without sorted rows: copied; with them: rebuilt on demand)
+    DevBuf<double> D, Vrows;
     DevBuf<float> slab;
 
     TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet& ss, double hx, double hy, int row0, int nrows);
+    const float* plane_into(nle_ctx* ctx, DevBuf<float>& dst) const;
+    void ensure_plane(nle_ctx* ctx);
     void drop_gram_only() { E2.release(), sorted.E2 = nullptr, sorted.hx = 0.0; }
     const nlek::SortedRows* sorted_rows() const { return scol.p ? &sorted : nullptr; }  // null: no sorted rows were made
     nlek::TableView view() const {

@@ -288,6 +288,36 @@ hipError_t sort_rows(hipStream_t s, const float* d_lum, GridSpec gs, int row0, i
     return hipGetLastError();
 }
 
+// The plane back from its sorted rows: one workgroup per local image row, one chunk per thread (every pixel of the chunk
+// has the chunk's level), then the row's sample pixels from the sample table (row, column, value).  Every pixel of the row
+// is in exactly one chunk or is a sample, so every entry is written once.
+__global__ __launch_bounds__(kT) void k_rows_from_sorted(int W, int row0, const unsigned short* __restrict__ scol,
+                                                         const uint2* __restrict__ desc, const Sample4* __restrict__ samples,
+                                                         int p, float* __restrict__ out) {
+    const int lrow = blockIdx.x, k = threadIdx.x;
+    float* orow = out + (size_t)lrow * W;
+    const uint2 d = desc[(size_t)lrow * kT + k];
+    const unsigned short* src = scol + (size_t)lrow * sorted_row_pitch(W) + (size_t)k * dsc_chp(d);
+    const float level = (float)dsc_level(d);
+    for (int i = 0, len = dsc_len(d); i < len; ++i) {
+        const int col = src[i] >> 3;
+        if (col < W) orow[col] = level;
+    }
+    for (int a = k; a < p; a += kT) {
+        const Sample4 sm = samples[a];
+        const int col = (int)sm.y;
+        if ((int)sm.x == row0 + lrow && col >= 0 && col < W) orow[col] = sm.z;
+    }
+}
+
+hipError_t rows_from_sorted(hipStream_t s, GridSpec gs, int row0, int nrows_local, const SortedRows& sr, const Sample4* d_samples,
+                            int p, float* d_out) {
+    if (gs.W > sorted_max_width() || nrows_local <= 0) return nrows_local <= 0 ? hipSuccess : hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rows_from_sorted, dim3((unsigned)nrows_local), dim3(kT), 0, s, gs.W, row0, sr.scol, sr.desc, d_samples, p,
+                       d_out);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ LDS layout shared by the two pass kernels
 // sE [W + 1] doubles | sP [kT][PS] doubles | sfirst [2][260] u16 (this row's and the next row's) | sCk [40] doubles (the
 // quadratic factors of the moment form of k_sorted_pass)
