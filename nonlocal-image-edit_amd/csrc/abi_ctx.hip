@@ -1,7 +1,7 @@
 // C ABI, the part that holds no filter arithmetic of its own: contexts and their resources, transfers, the settings, the
 // RCCL bootstrap, colour conversion and the bilateral pre-filter launches, the host-side eigen-solver entry points, the
 // closed-form helpers (sample grid, row slabs, eigenvalue transforms) and the profiling switches.  The train / apply /
-// stage-level entry points are in pipeline.hip, the device dense solvers' in devsolve.hip.
+// stage-level entry points are in pipeline.hip and literal.hip, the device dense solvers' in devsolve.hip.
 #include <mutex>
 
 #include "lab8_fixed.h"
@@ -57,10 +57,7 @@ void nle_ctx_destroy(nle_ctx* ctx) {
     for (auto e : ctx->prof_pool) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->comm && ctx->own_comm && !ctx->comm_aborted.load()) (void)rccl().CommDestroy(ctx->comm);
-    for (auto* f : ctx->filters) {  // orphaned: the table state goes to the cache freed below, V is freed on destroy
-        f->tables.reset();
-        f->ctx = nullptr;
-    }
+    for (auto* f : ctx->filters) f->orphan();  // the table state goes to the cache freed below, V is freed on destroy
     if (ctx->d_lut) (void)hipFree(ctx->d_lut);
     for (auto e : ctx->copy_ev)
         if (e) (void)hipEventDestroy(e);

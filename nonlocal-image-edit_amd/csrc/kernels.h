@@ -388,7 +388,7 @@ void exact_tables(int H, int W, double hx, double hy, std::vector<double>* es, s
 size_t exact_part_elems(long long N);
 // Y (N x ldy, columns < ncols) = K X (N x ldx, columns < ncols); deterministic, segmented over the source pixels
 hipError_t affinity_product64(hipStream_t s, const ExactPlane& pl, const double* d_X, int ldx, int ncols, double* d_Y, int ldy);
-// the eigensolver's element-wise steps (pipeline.hip: train_exact64)
+// the eigensolver's element-wise steps (exact_train.hip: ExactSolver)
 hipError_t exact_start(hipStream_t s, double* d_X, long long N, int ld, int col0, int ncols, unsigned seed);
 hipError_t exact_scale2(hipStream_t s, const double* d_X, int ldx, long long N, int b, const double* d_c, const double* d_r,
                         double* d_Z);

@@ -1,5 +1,5 @@
 // The orthogonalisation stage (reference src/filter.cpp:282-331) and what it shares with the train orchestration: the
-// Nystrom factors of K_A, the host / device forms of `orthogonalize`.  Implemented in ortho.hip, used by pipeline.hip.
+// Nystrom factors of K_A, the host / device forms of `orthogonalize`.  Implemented in ortho.hip, used by the train paths (train.h).
 #pragma once
 #include "devsolve.h"
 
@@ -68,7 +68,7 @@ struct DeviceDV {
 // sample-space form with the p x p products (and, where use_dev_solver says so, the solvers) on the device
 void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c,
                      const std::vector<double>& sA_r, double* d_Gk, int n_eig, const std::function<void()>& enqueue_gram,
-                     const std::function<void()>& reduce_gram, double* host_ms, double* host_overlapped_ms, Trace& tr,
+                     const std::function<void()>& reduce_gram, double* host_ms, Trace& tr,
                      const std::function<DeviceDV(int)>& place = nullptr);
 
 }  // namespace nlep

@@ -744,7 +744,7 @@ void D_and_Vrows(hipStream_t st, OrthoSS& o, const SsDevice& dv, const WaRoot& w
 // At cfg4 (p = 200) this takes ~0.6 ms of 200^3 host products off the critical path, at cfg5 (p = 900) ~50 ms.
 void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c,
                      const std::vector<double>& sA_r, double* d_Gk, int n_eig, const std::function<void()>& enqueue_gram,
-                     const std::function<void()>& reduce_gram, double* host_ms, double* host_overlapped_ms, Trace& tr,
+                     const std::function<void()>& reduce_gram, double* host_ms, Trace& tr,
                      const std::function<DeviceDV(int)>& place) {
     const int q = ny.r;
     hipStream_t st = c->stream;
@@ -752,7 +752,6 @@ void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std
     scalings_Kr_P(st, o, ny, p, sA_c, sA_r, dv);
     // ---- Wa and a root F of its pseudo-inverse, beside the Gram kernels: on the host below the device solvers' order (use_dev_solver), else on the
     // device on the ctx's second stream (the Gram kernels are on the first)
-    const double h0 = now_ms();
     const bool dev_wa = use_dev_solver(c->sw, q) && !c->sw.host_wa;
     const bool force_eig = c->sw.force_eig;
     // On the device route with Ka resident there (solve_Ka's device Cholesky) Wa is formed on the device; the host copy is
@@ -768,7 +767,6 @@ void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std
     if (!w.on_device) wa_root_host(o, !dev_wa, force_eig, w, tr);
     o.r_wa = w.r_wa;
     o.chol_wa = w.form == WaRoot::kCholesky;
-    *host_overlapped_ms += now_ms() - h0;
     tr.mark(w.on_device ? "ss: Wa root (device, second stream, beside the Gram kernels)" : "ss: Wa root (host, under the Gram kernels)");
     // ---- device: with a factor F of the (pseudo-)inverse of A = sym-lower(Wa), F F^T = A^+, the matrix the reference
     // diagonalises, Q = Wa + S (Wab Wab^T) S with S = A^+1/2 (:296), is similar on range(A) to

@@ -1,7 +1,7 @@
-// Internals shared by the host-side translation units of libnle_hip.so (pipeline.hip, samples.hip, ortho.hip, devsolve.hip,
-// abi_ctx.hip): the ctx / filter structs behind the opaque handles of include/nle.h, error plumbing, the stream-ordered
-// workspace arena, per-kernel event timing, the sample-grid closed form and the RCCL loader.  Not installed, not part of
-// the ABI.
+// Internals shared by the host-side translation units of libnle_hip.so (pipeline.hip and the train paths of train.h,
+// samples.hip, ortho.hip, devsolve.hip, abi_ctx.hip): the ctx / filter structs behind the opaque handles of include/nle.h,
+// error plumbing, the stream-ordered workspace arena, per-kernel event timing, the sample-grid closed form and the RCCL
+// loader.  Not installed, not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -20,7 +20,6 @@
 #include <memory>
 #include <set>
 #include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -30,7 +29,7 @@
 #include "switches.h"
 
 using nlek::GridSpec;
-namespace nlep { struct TableFilter; struct SampleSet; }
+namespace nlep { struct SampleSet; }
 
 // ------------------------------------------------------------------------------ types
 struct nle_ctx {
@@ -89,29 +88,6 @@ struct nle_ctx {
     double prof_ms[NLE_KERNEL_COUNT] = {0};
 };
 
-struct nle_filter {
-    nle_ctx* ctx = nullptr;
-    int H = 0, W = 0, row0 = 0, row1 = 0;
-    long long n_local = 0;
-    int K = 0, ldv = 0, r = 0, p = 0;
-    float* d_V = nullptr;  // m_eigvecs (n_local x ldv fp32); in the table form it is materialised on first request
-    size_t v_bytes = 0;
-    double* d_V64 = nullptr;  // fp64 formulation (generic64.hip): m_eigvecs in fp64, same leading dimension
-    size_t v64_bytes = 0;
-    std::vector<double> eigvals;
-    double chroma_hc = 0.0;  // the chroma bandwidth the filter was trained with (nle_ctx_set_chroma), 0 = without
-    double ms[6] = {0, 0, 0, 0, 0, 0};
-    // nle_filter_diag: formulation taken, eigenvalues kept by the three cuts (:214 on Ka, Wa, Q), Cholesky shortcuts
-    int formulation = 0, r_wa = 0, r_q = 0, chol_ka = 0, chol_wa = 0;
-    // set: the table formulation (TableFilter below), m_eigvecs implicit.  It dies with the filter or with the ctx, whichever
-    // goes first (nle_ctx_destroy): its buffers are the ctx's workspace cache's
-    std::unique_ptr<nlep::TableFilter> tables;
-    float* d_plane = nullptr;  // nle_train_host: the uploaded training plane (full image), kept for apply(h_x == NULL)
-    size_t plane_bytes = 0;
-    std::vector<long long> h_sample_pix;          // the sample pixels, in the order of the sample set (ascending)
-};
-
-
 namespace nlep {
 
 struct Fail {
@@ -158,12 +134,8 @@ inline void* arena_alloc(nle_ctx* c, size_t bytes) {
 }
 
 inline void arena_release(nle_ctx* c, void* p, size_t bytes) {
-    if (!p) return;
-    if (c) {
-        c->arena_free.emplace(bytes, p);
-    } else {
-        (void)hipFree(p);
-    }
+    if (p && c) c->arena_free.emplace(bytes, p);
+    else if (p) (void)hipFree(p);
 }
 
 template <typename T>
@@ -173,9 +145,11 @@ struct DevBuf {
     nle_ctx* owner = nullptr;
     DevBuf() = default;
     explicit DevBuf(size_t count) { alloc(count); }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n), owner(o.owner) { o.take(); }  // (a DevBuf returned from a function)
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n), owner(o.owner) { o.p = nullptr, o.n = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {  // (hands a buffer over; what the target held goes when the source does)
+        std::swap(p, o.p), std::swap(n, o.n), std::swap(owner, o.owner);
+        return *this;
+    }
     void alloc(size_t count) {
         release();
         if (count) {
@@ -188,12 +162,6 @@ struct DevBuf {
         if (p) arena_release(owner, p, n * sizeof(T));
         p = nullptr;
         n = 0;
-    }
-    T* take() {  // ownership moves to the caller (bytes = n * sizeof(T), release with arena_release)
-        T* q = p;
-        p = nullptr;
-        n = 0;
-        return q;
     }
     ~DevBuf() { release(); }
 };
@@ -235,6 +203,34 @@ struct TableFilter {
         return nlek::TableView{lum, gs, p, P64, row0, nrows, er.p, ecT.p, Ep.p, c.p, sorted_rows()};
     }
 };
+
+}  // namespace nlep
+
+struct nle_filter {
+    nle_ctx* ctx = nullptr;
+    int H = 0, W = 0, row0 = 0, row1 = 0;
+    long long n_local = 0;
+    int K = 0, ldv = 0, r = 0, p = 0;
+    // the filter's device state goes back to the workspace cache of the ctx it was made on when the filter dies
+    nlep::DevBuf<float> V;     // m_eigvecs (n_local x ldv fp32); in the table form it is materialised on first request
+    nlep::DevBuf<double> V64;  // fp64 formulation (generic64.hip): m_eigvecs in fp64, same leading dimension
+    std::vector<double> eigvals;
+    double chroma_hc = 0.0;  // the chroma bandwidth the filter was trained with (nle_ctx_set_chroma), 0 = without
+    double ms[6] = {0, 0, 0, 0, 0, 0};
+    // nle_filter_diag: formulation taken, eigenvalues kept by the three cuts (:214 on Ka, Wa, Q), Cholesky shortcuts
+    int formulation = 0, r_wa = 0, r_q = 0, chol_ka = 0, chol_wa = 0;
+    std::unique_ptr<nlep::TableFilter> tables;  // set: the table formulation, m_eigvecs implicit
+    nlep::DevBuf<float> plane;  // nle_train_host: the uploaded training plane (full image), kept for apply(h_x == NULL)
+    std::vector<long long> h_sample_pix;  // the sample pixels, in the order of the sample set (ascending)
+    // the ctx dies first: the table state goes to its cache, freed next; V, V64 and the plane are hipFree'd with the filter
+    void orphan() {
+        tables.reset();
+        V.owner = V64.owner = plane.owner = nullptr;
+        ctx = nullptr;
+    }
+};
+
+namespace nlep {
 
 struct Timer {
     hipEvent_t a = nullptr, b = nullptr;
@@ -431,7 +427,7 @@ inline void all_reduce(nle_ctx* c, double* d, size_t n) {
 // ranks before anything acts on it: the number of ranks on which `flag` holds.  Without this a rank that refuses (or picks
 // another formulation) leaves its peers blocked in their next all-reduce.  One 8-byte all-reduce; nothing when world == 1.
 // (The tests inject a dissenting rank through the all-reduce callback, which sees every call of this one as a one-double
-// all-reduce: the refusals and the streaming choice of pipeline.hip, and the solver fallbacks of ortho.hip.)
+// all-reduce: the refusals and the streaming choice of the train paths, and the solver fallbacks of ortho.hip.)
 inline int ranks_where(nle_ctx* c, bool flag) {
     if (c->world <= 1 && !c->comm) return flag ? 1 : 0;
     DevBuf<double> d(1);

@@ -1,7 +1,7 @@
 // The sample set and the fp64 affinity rows on the host: what an affinity is on the fp64 formulations -- the patch radius
 // (nle_ctx_set_patch_radius), the chroma planes (nle_ctx_set_chroma) and the sampler (nle_ctx_set_sampler) -- is read from
-// the ctx, refused, fetched, turned into Ka and into row launches HERE (samples.hip); pipeline.hip's train paths and stage
-// entry points see an AffinityOpts, a SampleSet and an AffinityRows64.  Not installed, not part of the ABI.
+// the ctx, refused, fetched, turned into Ka and into row launches HERE (samples.hip); the train paths and stage entry points
+// (train.h) see an AffinityOpts, a SampleSet and an AffinityRows64.  Not installed, not part of the ABI.
 #pragma once
 #include "pipeline_internal.h"
 

@@ -71,7 +71,7 @@ def span_of(g, W):
 
 def predicates(g, W, hx, env=()):
     """Python mirror of sorted_moments_ok, sorted_recurrence and sorted_gsum_ok (csrc/sorted.hip: pure bounds, the m_* < 500 /
-    600 terms below) with the exponents they bound, combined as the TableFilter constructor (csrc/pipeline.hip) combines them
+    600 terms below) with the exponents they bound, combined as the TableFilter constructor (csrc/sample_space.hip) combines them
     with `env`: the NLE_* measurement variables that force a plain form."""
     cs, nC = float(g["col_step"]), float(g["n_sel_cols"])
     umax = float(max(g["col_off"], W - 1 - g["col_off"]))

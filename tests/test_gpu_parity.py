@@ -219,7 +219,7 @@ def test_rank_truncated_Ka(nle, oracle, ctx, mode):
 @pytest.mark.parametrize("case", [SMALL_CASES[1], SMALL_CASES[-1]])
 def test_cholesky_and_eigen_forms_of_Ka_agree(nle, oracle, ctx, case, monkeypatch):
     """Full-rank Ka: the Phi-free path factors Ka (and Wa when the 1e-10 cut removes nothing) by Cholesky
-    instead of the eigensolver (pipeline.hip solve_Ka / ortho_ss_prepare); NLE_FORCE_EIG=1 keeps the
+    instead of the eigensolver (pipeline.hip solve_Ka / ortho.hip ortho_ss_prepare); NLE_FORCE_EIG=1 keeps the
     eigenpairs.  Both must match the oracle, and each other far below the parity bar."""
     H, W, nr, nc, hx, hy, T, K, L = case
     x = oracle.synthetic_luminance(H, W)

@@ -1,4 +1,4 @@
-"""What the table formulation hands from train to apply (csrc/pipeline.hip: train_tables), on a 64 x 97 plane with a
+"""What the table formulation hands from train to apply (csrc/sample_space.hip: train_tables), on a 64 x 97 plane with a
 4 x 5 sample grid.
 
 The filter must not depend on the caller's plane once nle_train has returned.  With level-sorted rows it keeps no copy of

@@ -32,7 +32,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK = 8.0e12
 OUT = os.path.join(ROOT, "profiles", "r7_chroma_timing.json")
-CHUNK = 1 << 20  # build_phi64's affinity chunk (pipeline.hip; the rows come from samples.hip's AffinityRows64)
+CHUNK = 1 << 20  # build_phi64's affinity chunk (literal.hip; the rows come from samples.hip's AffinityRows64)
 HC = 20.0
 OFF = [("off_R0", 0, False), ("off_R1", 1, False), ("off_R3", 3, False), ("off_R5", 5, False), ("off_R7", 7, False)]
 CHROMA = [("chroma_R0", 0, True), ("chroma_R1", 1, True), ("chroma_R3", 3, True)]

@@ -23,7 +23,7 @@ import __graft_entry__ as entry  # noqa: E402
 
 HBM_PEAK = 8.0e12
 OUT = os.path.join(ROOT, "profiles", "r5_patch_timing.json")
-CHUNK = 1 << 20  # build_phi64's affinity chunk (pipeline.hip; the rows come from samples.hip's AffinityRows64)
+CHUNK = 1 << 20  # build_phi64's affinity chunk (literal.hip; the rows come from samples.hip's AffinityRows64)
 
 
 def run(nle, ctx, x, cfg, R, mode, reps):
