@@ -453,6 +453,29 @@ int nle_apply_regions(nle_filter* f, const float* d_x, int H, int W, int L, cons
                       const double* h_scale, double spread, double floor, const double* h_weights, int out_kind,
                       void* d_out);
 
+/* ---- several planes through one filter (new in this build) ---- */
+/* Applies f to P planes in one call, each plane with its own set of responses: the channels of a colour image, several guide
+ * planes, the stroke planes of the region edits, the a / b pair of the denoiser.  nle_apply (P = 1, one response) and
+ * nle_apply_layers (P = 1, the layer responses of nle_layer_responses) are its special cases in meaning.
+ *   d_x       plane m at d_x + m x_stride (stride in floats), a full H x W fp32 plane as nle_apply takes it; 1 <= P <= NLE_PLANES_MAX
+ *   h_nresp   P counts, each 1 .. 64: the response vectors of plane m; NULL: one for every plane.  R = their sum <= 128
+ *   h_resp    R x K' fp64, row-major, the rows of plane 0 first
+ *   d_y       output j (the order of h_resp) at d_y + j y_stride, n_local floats each
+ *   out_kind  NLE_REGION_OUT_F32: what nle_apply gives; NLE_REGION_OUT_ROUNDED8: what nle_apply_rounded8 gives, its rule
+ *             included that table filters round the fp64 value and the other formulations their fp32 plane
+ * Contract: for every formulation nle_apply works for, the outputs of plane m are BIT FOR BIT what nle_apply / nle_apply_layers
+ * / nle_apply_rounded8 give for that plane and those responses alone.  What is shared between the planes is only what does
+ * not depend on them: on the default (table) path with level-sorted rows, on one device, the reduce half makes one pass over
+ * the sorted rows per group of four planes (two beyond 12 sample columns) and the expand half takes the R weight vectors in
+ * its usual groups; every other formulation, filters without sorted rows (W > 8192, NLE_NO_SORTED_ROWS) and world > 1 run
+ * the planes one by one.
+ * NLE_ERR_INVALID, with a message, before anything is enqueued and with the ctx left usable: P out of range; a count out of
+ * range or R > 128; a NULL pointer (h_nresp apart); an unknown out kind; a stride smaller than the plane when P (x_stride) or
+ * R (y_stride) exceeds 1; H W that is not the filter's; any output plane overlapping any input plane. */
+#define NLE_PLANES_MAX 16
+int nle_apply_planes(nle_filter* f, const float* d_x, int P, long long x_stride, int H, int W, const int* h_nresp,
+                     const double* h_resp, int out_kind, float* d_y, long long y_stride);
+
 /* ---- colour wrapper on the device (the code either side of the path) ------------------------------- */
 /* cv::cvtColor(COLOR_BGR2Lab) on an 8-bit image as the reference uses it (src/filter.cpp:423,463) and
  * the split / convertTo(CV_64F) of the L channel (:424-426,465-467): d_bgr n x 3 bytes -> d_lab n x 3

@@ -207,6 +207,10 @@ public:
                        int nSinkhornIter, int nEigenVectors, const float* d_a = nullptr, const float* d_b = nullptr);
     // per-layer outputs (L planes, CV_64F) -- what the 1e-4 per-detail-layer bar compares
     std::vector<Image> applyLayers(const Image& channel, int nLayers) const;
+    // several planes through the filter in one call (nle_apply_planes): responses[m] are the transformed eigenvalue
+    // vectors of channels[m] (one or more each); returns one CV_64F plane per response, those of channel 0 first, each bit
+    // for bit what apply(channels[m], responses[m][l]) returns.  Host buffers in and out, like apply.
+    std::vector<Image> applyPlanes(const std::vector<Image>& channels, const std::vector<std::vector<Vec>>& responses) const;
 
     Vec eigvals() const;                 // m_eigvals
     Mat eigvecs() const;                 // m_eigvecs, downloaded (N x K')

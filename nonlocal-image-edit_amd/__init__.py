@@ -40,6 +40,7 @@ SAMPLER_GRID, SAMPLER_FARTHEST = _abi.NLE_SAMPLER_GRID, _abi.NLE_SAMPLER_FARTHES
 REGION_MAX, REGION_LAYERS_MAX = _abi.NLE_REGION_MAX, _abi.NLE_REGION_LAYERS_MAX
 REGION_OUT_F32, REGION_OUT_ROUNDED8, REGION_OUT_U8 = (_abi.NLE_REGION_OUT_F32, _abi.NLE_REGION_OUT_ROUNDED8,
                                                       _abi.NLE_REGION_OUT_U8)
+PLANES_MAX = _abi.NLE_PLANES_MAX  # nle_apply_planes: planes per call (its output kinds are REGION_OUT_F32 / _ROUNDED8)
 
 _lib = None
 
@@ -937,6 +938,43 @@ class NLEFilter:
             out = torch.empty(n, dtype=torch.float32, device=x.device)
         _check(lib().nle_apply(self._f, C.c_void_p(x.data_ptr()), H, W, _np_ptr(fs), C.c_void_p(out.data_ptr())),
                self.ctx._h)
+        return out
+
+    def apply_planes(self, planes, responses, out_kind=0, out=None):
+        """nle_apply_planes: the filter applied to P planes in one call, each with its own responses; every output is bit
+        for bit what `apply` / `apply_layers` / `apply_rounded8` give plane by plane.
+
+        planes: P x H x W float32 (a device tensor may have any stride between its planes; each plane is contiguous).
+        responses: per plane a (K',) vector or an (L_m, K') array (1 <= L_m <= 64), R = sum L_m <= 128; None: one response
+        of ones for every plane.  out_kind: REGION_OUT_F32 or REGION_OUT_ROUNDED8.  Returns (R, n_local) float32, the
+        outputs of plane 0 first; `out` may be such a tensor with any stride between its rows."""
+        torch = _torch()
+        t = torch.as_tensor(planes, dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        if t.ndim != 3:
+            raise NLEError(NLE_ERR_INVALID, "planes must be P x H x W")
+        P, H, W = t.shape
+        if t.stride(2) != 1 or t.stride(1) != W or (P > 1 and t.stride(0) < H * W):
+            t = t.contiguous()
+        self.ctx._sync_in()
+        K = self.info()["K"]
+        if responses is None:
+            responses = [np.ones(K)] * P
+        if len(responses) != P:
+            raise NLEError(NLE_ERR_INVALID, f"one set of responses per plane expected: {P} planes, {len(responses)} sets")
+        rows = [np.atleast_2d(np.asarray(r, dtype=np.float64)) for r in responses]
+        for r in rows:
+            if r.ndim != 2 or r.shape[1] != K:   # nle_apply_planes reads K' doubles per response
+                raise NLEError(NLE_ERR_INVALID, f"every response must hold K' = {K} values, got {r.shape}")
+        nresp = np.ascontiguousarray([r.shape[0] for r in rows], dtype=np.int32)
+        resp = np.ascontiguousarray(np.concatenate(rows, axis=0))
+        R, n = int(nresp.sum()), self.info()["n_local"]
+        if out is None:
+            out = torch.empty((R, n), dtype=torch.float32, device=t.device)
+        elif tuple(out.shape) != (R, n) or out.dtype != torch.float32 or out.stride(1) != 1:
+            raise NLEError(NLE_ERR_INVALID, f"out must be a float32 tensor of shape {(R, n)} with contiguous rows")
+        _check(lib().nle_apply_planes(self._f, C.c_void_p(t.data_ptr()), P, t.stride(0) if P > 1 else H * W, H, W,
+                                      _np_ptr(nresp), _np_ptr(resp), int(out_kind), C.c_void_p(out.data_ptr()),
+                                      out.stride(0) if R > 1 else n), self.ctx._h)
         return out
 
     def _strokes(self, strokes):

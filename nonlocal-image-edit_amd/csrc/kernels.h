@@ -314,6 +314,17 @@ hipError_t sort_rows(hipStream_t s, const float* d_lum, GridSpec gs, int row0, i
 hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows, const SortedRows& sr, const double* d_g,
                        double eps, double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec);
 bool sorted_moments_ok(GridSpec gs, double hx);
+// the XVEC pass for a group of planes in ONE walk over the sorted rows (sorted_planes.hip: k_sorted_reduce_planes): plane m
+// of the group is read at x[m] (virtual base of the full image) and its tables go to h[m], in sorted_pass's layout and with
+// sorted_pass's bits.  2 <= np <= sorted_planes_per_launch(gs): four planes up to 12 columns, two beyond.
+constexpr int kPlanesPerLaunch = 4;
+struct PlaneGroup {
+    const float* x[kPlanesPerLaunch];
+    double* h[kPlanesPerLaunch];
+};
+int sorted_planes_per_launch(GridSpec gs);
+hipError_t sorted_reduce_planes(hipStream_t s, GridSpec gs, int row0, int nrows, const SortedRows& sr, const double* d_cvec,
+                                const PlaneGroup& pg, int np);
 hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows, const SortedRows& sr, const double* d_cvec, double* d_Aout);
 
 // the table pass (three kernels, Ep read once per pass); writes the full column sums to d_z.  d_ybuf (optional): y_i per
@@ -321,6 +332,13 @@ hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows, const SortedR
 size_t hist_tiled_workspace_elems(GridSpec gs, int nrows_local);
 hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const double* d_w, double eps, double* d_ybuf,
                            double* d_ws, double* d_z, LaunchObserver* obs = nullptr, const float* d_xvec = nullptr);
+// reduce half of the sample-space apply for 2 <= np <= sorted_planes_per_launch(v.gs) planes on the level-sorted rows
+// (v.sorted != null): one pixel kernel for the group, then the HH stage and the column sums plane by plane; d_x: np planes
+// (virtual full bases); d_ws: apply_reduce_planes_workspace_elems doubles; d_m: np vectors of stride v.ldp, each the bits
+// sink_hist_tiled(ROWPASS_XVEC) gives that plane
+size_t apply_reduce_planes_workspace_elems(GridSpec gs, int nrows_local, int np);
+hipError_t apply_reduce_planes(hipStream_t s, const TableView& v, const float* const* d_x, int np, double* d_ws, double* d_m,
+                               LaunchObserver* obs = nullptr);
 // sample-space apply (tables): expand half for nl <= apply_layers_per_launch(v) layers (decided there and nowhere else), the
 // p/K-sized middle, and the sample-pixel outputs
 int apply_layers_per_launch(const TableView& v);

@@ -212,7 +212,7 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
 // t = V^T x (all ranks), then Y[l] = V (g_l o t), on a materialised V (fp32 or fp64)
 template <typename T>
 void apply_dense(nle_filter* f, const T* d_V, const float* d_x, const double* h_g /* L x K */, int L, float* d_y,
-                 const LayersDone& done) {
+                 const LayersDone& done, long long ystride) {
     nle_ctx* c = f->ctx;
     const int ld = f->ldv;
     const long long M = f->n_local;
@@ -230,7 +230,7 @@ void apply_dense(nle_filter* f, const T* d_V, const float* d_x, const double* h_
     all_reduce(c, d_t.p, ld);
     for (int l = 0; l < L; ++l)
         PROFILED(c, NLE_K_SMALL, nlek::scale_vec(c->stream, d_resp.p + (size_t)l * ld, d_t.p, ld, d_g.p + (size_t)l * ld));
-    PROFILED(c, NLE_K_APPLY_EXPAND, apply_expand_any(c->stream, d_V, M, ld, f->K, d_g.p, L, d_y, M));
+    PROFILED(c, NLE_K_APPLY_EXPAND, apply_expand_any(c->stream, d_V, M, ld, f->K, d_g.p, L, d_y, ystride > 0 ? ystride : M));
     if (done) done(0, L);
     HIP_OK(hipStreamSynchronize(c->stream));
     prof_flush(c);
@@ -238,8 +238,9 @@ void apply_dense(nle_filter* f, const T* d_V, const float* d_x, const double* h_
 
 // round8: the planes come out clamped to [0, 255] and rounded half to even (src/filter.cpp:434-436) -- on the default path from
 // the fp64 value, before anything is rounded to fp32 (other formulations: their fp32 planes, rounded by the caller)
+// ystride: floats between the output layers (0: n_local)
 void apply_impl(nle_filter* f, const float* d_x_in, int H, int W, const double* h_g /* L x K */, int L,
-                float* d_y, const LayersDone& done = nullptr, int group = 0, bool round8 = false) {
+                float* d_y, const LayersDone& done = nullptr, int group = 0, bool round8 = false, long long ystride = 0) {
     nle_ctx* c = f->ctx;
     // slab-input mode: d_x_in holds this rank's rows only; index it through the virtual base of the full image
     const float* d_x = (c->slab_input && c->world > 1) ? d_x_in - (size_t)f->row0 * f->W : d_x_in;
@@ -248,12 +249,44 @@ void apply_impl(nle_filter* f, const float* d_x_in, int H, int W, const double* 
     if (L < 1 || L > 64) throw Fail{NLE_ERR_INVALID, "number of layers must be in [1, 64]"};
     HIP_OK(hipSetDevice(c->device));
     if (f->tables) {
-        apply_sample_space(f, d_x, h_g, L, d_y, done, group, round8);
+        apply_sample_space(f, d_x, h_g, L, d_y, done, group, round8, ystride);
     } else if (f->V64.p) {
-        apply_dense(f, f->V64.p, d_x, h_g, L, d_y, done);
+        apply_dense(f, f->V64.p, d_x, h_g, L, d_y, done, ystride);
     } else {
         ensure_V(f);
-        apply_dense(f, f->V.p, d_x, h_g, L, d_y, done);
+        apply_dense(f, f->V.p, d_x, h_g, L, d_y, done, ystride);
+    }
+}
+
+// the fp32 planes of the formulations that keep V: clamp to [0, 255] and round half to even (nle_apply_rounded8's rule for them)
+void round8_planes(nle_filter* f, float* d_y, int L, long long ystride) {
+    DevBuf<unsigned char> d_o((size_t)std::max<long long>(f->n_local, 1));
+    for (int l = 0; l < L; ++l) {
+        HIP_OK(nlek::plane_to_u8(f->ctx->stream, d_y + (size_t)l * ystride, f->n_local, d_o.p));
+        HIP_OK(nlek::channel8_plane(f->ctx->stream, d_o.p, f->n_local, d_y + (size_t)l * ystride));
+    }
+    HIP_OK(hipStreamSynchronize(f->ctx->stream));
+}
+
+// P planes, plane m with nresp[m] of the R rows of h_resp (R x K, plane 0's first), output j at d_y + j * ystride: bit for
+// bit apply_impl(f, d_x[m], H, W, resp_m, nresp[m], .., round8) plane by plane (include/nle.h: nle_apply_planes).  A table
+// filter with level-sorted rows on one device takes the batched path (sample_space.hip); everything else goes one by one.
+void apply_planes_impl(nle_filter* f, const float* const* d_x, int P, int H, int W, const int* nresp, const double* h_resp,
+                       float* d_y, long long ystride, bool round8) {
+    nle_ctx* c = f->ctx;
+    if ((long long)H * W != (long long)f->H * f->W)  // reference src/filter.cpp:447-449
+        throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+    int R = 0;
+    for (int m = 0; m < P; ++m) R += nresp[m];
+    if (P > 1 && f->tables && f->tables->sorted_rows() && c->world == 1) {
+        HIP_OK(hipSetDevice(c->device));
+        apply_sample_space_planes(f, d_x, P, nresp, h_resp, R, d_y, ystride, round8);
+        return;
+    }
+    for (int m = 0, j = 0; m < P; j += nresp[m], ++m) {
+        float* y = d_y + (size_t)j * ystride;
+        apply_impl(f, d_x[m], H, W, h_resp + (size_t)j * f->K, nresp[m], y, nullptr, 0, round8, ystride);
+        if (round8 && !f->tables) round8_planes(f, y, nresp[m], ystride);
     }
 }
 
@@ -373,15 +406,23 @@ void region_combine_impl(nle_ctx* c, const float* d_layers, int L, const float* 
     HIP_OK(hipStreamSynchronize(c->stream));
 }
 
-// q_m = apply(s_m, c_m lambda^t), one nle_apply per stroke plane
-void region_spread_impl(nle_filter* f, const float* d_strokes, int M, int H, int W, const double* h_scale, double spread,
-                        float* d_q) {
-    std::vector<double> fS((size_t)f->K);
+// the responses of the spreads, fS_m[k] = c_m lambda_k^t: M rows of K at `out`
+void spread_resp(const nle_filter* f, int M, const double* h_scale, double spread, double* out) {
     for (int m = 0; m < M; ++m) {
         const double cm = h_scale ? h_scale[m] : 1.0;
-        for (int k = 0; k < f->K; ++k) fS[k] = cm * std::pow(f->eigvals[k], spread);
-        apply_impl(f, d_strokes + (size_t)m * H * W, H, W, fS.data(), 1, d_q + (size_t)m * f->n_local);
+        for (int k = 0; k < f->K; ++k) out[(size_t)m * f->K + k] = cm * std::pow(f->eigvals[k], spread);
     }
+}
+
+// q_m = apply(s_m, c_m lambda^t): one batch over the M stroke planes, bitwise one nle_apply per plane
+void region_spread_impl(nle_filter* f, const float* d_strokes, int M, int H, int W, const double* h_scale, double spread,
+                        float* d_q) {
+    std::vector<double> fS((size_t)M * f->K);
+    spread_resp(f, M, h_scale, spread, fS.data());
+    const float* planes[NLE_REGION_MAX];
+    int ones[NLE_REGION_MAX];
+    for (int m = 0; m < M; ++m) planes[m] = d_strokes + (size_t)m * H * W, ones[m] = 1;
+    apply_planes_impl(f, planes, M, H, W, ones, fS.data(), d_q, f->n_local, false);
 }
 
 }  // namespace
@@ -605,12 +646,7 @@ int nle_apply_rounded8(nle_filter* f, const float* d_x, int H, int W, const doub
     if (!f || !f->ctx || !d_x || !h_fS || !d_y) return NLE_ERR_INVALID;
     return guard(f->ctx, [&] {
         apply_impl(f, d_x, H, W, h_fS, 1, d_y, nullptr, 0, /*round8=*/true);
-        if (!f->tables) {  // formulations with fp32 planes: round those
-            DevBuf<unsigned char> d_o((size_t)std::max<long long>(f->n_local, 1));
-            HIP_OK(nlek::plane_to_u8(f->ctx->stream, d_y, f->n_local, d_o.p));
-            HIP_OK(nlek::channel8_plane(f->ctx->stream, d_o.p, f->n_local, d_y));
-            HIP_OK(hipStreamSynchronize(f->ctx->stream));
-        }
+        if (!f->tables) round8_planes(f, d_y, 1, f->n_local);  // formulations with fp32 planes: round those
     });
 }
 
@@ -640,6 +676,50 @@ int nle_apply_u8_host(nle_filter* f, const float* h_x, int H, int W, const doubl
         HIP_OK(nlek::plane_to_u8(c->stream, d_y.p, f->n_local, d_o.p));
         HIP_OK(hipMemcpyAsync(h_out, d_o.p, (size_t)f->n_local, hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int nle_apply_planes(nle_filter* f, const float* d_x, int P, long long x_stride, int H, int W, const int* h_nresp,
+                     const double* h_resp, int out_kind, float* d_y, long long y_stride) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        // every refusal before anything is enqueued
+        if (P < 1 || P > NLE_PLANES_MAX)
+            throw Fail{NLE_ERR_INVALID, "nle_apply_planes takes 1 to " + std::to_string(NLE_PLANES_MAX) + " planes, got " +
+                                            std::to_string(P)};
+        if (!d_x || !h_resp || !d_y) throw Fail{NLE_ERR_INVALID, "nle_apply_planes: NULL pointer"};
+        if (out_kind != NLE_REGION_OUT_F32 && out_kind != NLE_REGION_OUT_ROUNDED8)
+            throw Fail{NLE_ERR_INVALID, "nle_apply_planes: unknown output kind " + std::to_string(out_kind) +
+                                            " (NLE_REGION_OUT_F32 or NLE_REGION_OUT_ROUNDED8)"};
+        int nresp[NLE_PLANES_MAX], R = 0;
+        for (int m = 0; m < P; ++m) {
+            nresp[m] = h_nresp ? h_nresp[m] : 1;
+            if (nresp[m] < 1 || nresp[m] > 64)
+                throw Fail{NLE_ERR_INVALID, "nle_apply_planes: plane " + std::to_string(m) + " has " + std::to_string(nresp[m]) +
+                                                " responses, 1 to 64 are taken"};
+            R += nresp[m];
+        }
+        if (R > 128)
+            throw Fail{NLE_ERR_INVALID, "nle_apply_planes: " + std::to_string(R) + " responses in all, at most 128 are taken"};
+        if (H <= 0 || W <= 0 || (long long)H * W != (long long)f->H * f->W)  // the text of nle_apply's refusal (:447-449)
+            throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+        const nle_ctx* c = f->ctx;
+        const long long nin = (c->slab_input && c->world > 1) ? f->n_local : (long long)H * W, nout = f->n_local;
+        if ((P > 1 && x_stride < nin) || (R > 1 && y_stride < nout) || x_stride < 0 || y_stride < 0)
+            throw Fail{NLE_ERR_INVALID, "nle_apply_planes: a plane stride is smaller than the plane"};
+        // inputs of later planes are read after the outputs of earlier ones are written on the one-by-one route: no output
+        // plane may overlap any input plane
+        for (int m = 0; m < P; ++m)
+            for (int j = 0; j < R; ++j) {
+                const float *x0 = d_x + (size_t)m * x_stride, *y0 = d_y + (size_t)j * y_stride;
+                if (reinterpret_cast<uintptr_t>(x0) < reinterpret_cast<uintptr_t>(y0 + nout) &&
+                    reinterpret_cast<uintptr_t>(y0) < reinterpret_cast<uintptr_t>(x0 + nin))
+                    throw Fail{NLE_ERR_INVALID, "nle_apply_planes: output plane " + std::to_string(j) + " overlaps input plane " +
+                                                    std::to_string(m)};
+            }
+        const float* planes[NLE_PLANES_MAX];
+        for (int m = 0; m < P; ++m) planes[m] = d_x + (size_t)m * x_stride;
+        apply_planes_impl(f, planes, P, H, W, nresp, h_resp, d_y, R > 1 ? y_stride : nout, out_kind == NLE_REGION_OUT_ROUNDED8);
     });
 }
 
@@ -676,10 +756,15 @@ int nle_apply_regions(nle_filter* f, const float* d_x, int H, int W, int L, cons
         region_check_spread(f, M, H, W, h_scale, spread);
         const long long n = f->n_local;  // == H W: world == 1
         DevBuf<float> d_work((size_t)(L + M) * n);
-        std::vector<double> resp((size_t)L * f->K);
+        // one batch over [x; s_1 .. s_M]: the L layers of x (nle_apply_layers) and one spread per stroke (nle_region_spread)
+        std::vector<double> resp((size_t)(L + M) * f->K);
         layer_resp(f->eigvals.data(), f->K, L, resp.data());
-        apply_impl(f, d_x, H, W, resp.data(), L, d_work.p);  // nle_apply_layers
-        region_spread_impl(f, d_strokes, M, H, W, h_scale, spread, d_work.p + (size_t)L * n);
+        spread_resp(f, M, h_scale, spread, resp.data() + (size_t)L * f->K);
+        const float* planes[1 + NLE_REGION_MAX];
+        int nresp[1 + NLE_REGION_MAX];
+        planes[0] = d_x, nresp[0] = L;
+        for (int m = 0; m < M; ++m) planes[1 + m] = d_strokes + (size_t)m * H * W, nresp[1 + m] = 1;
+        apply_planes_impl(f, planes, 1 + M, H, W, nresp, resp.data(), d_work.p, n, false);
         region_combine_impl(c, d_work.p, L, d_work.p + (size_t)L * n, M, n, n, n, h_weights, floor, out_kind, d_out);
     });
 }

@@ -443,11 +443,11 @@ void ensure_V(nle_filter* f) {
 // apply on the p-sized side of a table filter: reduce half (column sums m = sum_i k_i c_i x_i through the
 // tables), the p/K-sized middle (k_apply_small), and one table pass per output layer
 void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L x K */, int L, float* d_y,
-                        const LayersDone& done, int group, bool round8) {
+                        const LayersDone& done, int group, bool round8, long long ystride) {
     nle_ctx* c = f->ctx;
     const TableFilter& t = *f->tables;
     const nlek::TableView view = t.view();
-    const long long M = f->n_local;
+    const long long M = ystride > 0 ? ystride : f->n_local;  // stride of the output layers
     const int p = t.p, K = f->K, P64 = t.P64;
     DevBuf<double> d_ws(nlek::hist_tiled_workspace_elems(t.gs, t.nrows)), d_m(P64), d_resp((size_t)L * K), d_t(K),
         d_Wp((size_t)L * P64), d_YA((size_t)L * p);
@@ -481,6 +481,55 @@ void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L 
         PROFILED(c, NLE_K_SMALL, nlek::scatter_samples(c->stream, p, nl, t.sample_loc.p, d_YA.p + (size_t)l * p,
                                                        d_y + (size_t)l * M, M, round8));
         if (done) done(l, nl);
+    }
+    HIP_OK(hipStreamSynchronize(c->stream));
+    prof_flush(c);
+}
+
+// The batched form.  Reduce half: the planes in groups of sorted_planes_per_launch, one pass over the sorted rows per group
+// (a last group of one plane takes the single pass); the p-sized middle per plane, with that plane's responses.  Expand
+// half: the R weight vectors in groups of apply_layers_per_launch, whatever plane they belong to.  Every input is read
+// before the first output is written.  Workspace: one group's tables, not P or R of them.
+void apply_sample_space_planes(nle_filter* f, const float* const* d_x, int P, const int* nresp, const double* h_g, int R,
+                               float* d_y, long long ystride, bool round8) {
+    nle_ctx* c = f->ctx;
+    const TableFilter& t = *f->tables;
+    const nlek::TableView view = t.view();
+    const int p = t.p, K = f->K, P64 = t.P64;
+    const int NP = std::min(P, nlek::sorted_planes_per_launch(t.gs));
+    DevBuf<double> d_ws(nlek::apply_reduce_planes_workspace_elems(t.gs, t.nrows, NP)), d_m((size_t)NP * P64),
+        d_resp((size_t)R * K), d_t(K), d_xA(p), d_Wp((size_t)R * P64), d_YA((size_t)R * p);
+    HIP_OK(hipMemcpyAsync(d_resp.p, h_g, (size_t)R * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    static const int rmap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_REDUCE, NLE_K_REDUCE, NLE_K_REDUCE};
+    int j = 0;  // first response of the plane in hand
+    for (int m0 = 0; m0 < P; m0 += NP) {
+        const int np = std::min(NP, P - m0);
+        {
+            ProfObserver obs(c, rmap);
+            if (np > 1) HIP_OK(nlek::apply_reduce_planes(c->stream, view, d_x + m0, np, d_ws.p, d_m.p, &obs));
+            else HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_ws.p, d_m.p, &obs, d_x[m0]));
+        }
+        for (int m = m0; m < m0 + np; ++m) {
+            const int L = nresp[m];
+            PROFILED(c, NLE_K_SMALL, nlek::gather_samples_slab(c->stream, d_x[m], t.gs, 0, f->H, d_xA.p));
+            PROFILED(c, NLE_K_SMALL, nlek::apply_small(c->stream, p, K, t.ldd, L, P64, d_m.p + (size_t)(m - m0) * P64, t.D.p,
+                                                       t.Vrows.p, d_xA.p, d_resp.p + (size_t)j * K, d_t.p, d_Wp.p + (size_t)j * P64,
+                                                       d_YA.p + (size_t)j * p));
+            j += L;
+        }
+    }
+    static const int emap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_EXPAND, NLE_K_REDUCE, NLE_K_REDUCE};
+    const int lb = std::min(R, nlek::apply_layers_per_launch(view));
+    DevBuf<double> d_gws((size_t)lb * t.nrows * 256 * t.gs.nSelCols);
+    for (int l = 0; l < R; l += lb) {
+        const int nl = std::min(lb, R - l);
+        {
+            ProfObserver obs(c, emap);
+            HIP_OK(nlek::apply_hist_layers(c->stream, view, d_Wp.p + (size_t)l * P64, P64, nl, d_gws.p, d_y + (size_t)l * ystride,
+                                           ystride, &obs, round8));
+        }
+        PROFILED(c, NLE_K_SMALL, nlek::scatter_samples(c->stream, p, nl, t.sample_loc.p, d_YA.p + (size_t)l * p,
+                                                       d_y + (size_t)l * ystride, ystride, round8));
     }
     HIP_OK(hipStreamSynchronize(c->stream));
     prof_flush(c);

@@ -1,0 +1,288 @@
+// Reduce half of the sample-space apply for a GROUP of planes in one pass over the level-sorted rows.
+//
+// k_sorted_pass in XVEC mode (sorted.hip) turns one plane x into the per-row, per-level tables h_r[x][b] = sum_i e_b(c_i) c_i x_i.
+// Per pixel it reads a 2-byte column index and the 8-byte scaling c_i and forms the column factors e_b -- none of which
+// depends on the plane; only y_i = c_i x_i and the sums do.  k_sorted_reduce_planes walks the rows ONCE for NP planes: the
+// index, c_i and the factors (e_0, rho, rho^2 of the moment form, or the e_b of the table / recurrence forms) are made once
+// per pixel, then each plane's y and its nC sums are updated.  10 + 4 NP bytes per pixel instead of 14 NP.
+//
+// Bitwise contract: the tables of every plane are the bits k_sorted_pass<NC, CF> writes for that plane alone.  The order of a
+// plane's sums is a function of the sorted rows only (one chunk per thread, chunks of a level combined in chunk order), and
+// the per-plane arithmetic below is k_sorted_pass's, operation by operation.  That kernel is compiled with contraction on,
+// and what the compiler makes of its expressions is pinned here instead of left to a second compilation: contraction is OFF
+// in this file's kernel and every fused multiply-add is written out --
+//     moment form     acc_0 = fma(y, e_0, acc_0),  te = y e_0;   acc_1 = fma(te, rho, acc_1),  to = te rho;
+//                     acc_b = fma(t, rho^2, acc_b),  t = t rho^2   (t = te for even b, to for odd b);   acc_b *= C_b at the end
+//     table / recurrence forms   acc_b = fma(e_b, y, acc_b)
+// (read off the ISA of k_sorted_pass<3,2>, <10,2>, <10,0>, <20,1>, <36,0>, <36,1>: no v_add_f64 in any pixel loop).
+// tests/test_apply_planes.py compares the outputs bit for bit on every form and at every column count where a path changes.
+#include "sorted_rows.h"
+
+#include <algorithm>
+
+namespace nlek {
+
+// Structure of k_sorted_pass: persistent workgroups, one level chunk per thread, the chunk's indices in registers, the next
+// row's descriptor and indices requested under the current row's pixel loop.  XVEC only: no g tables, no reciprocal, no ybuf.
+// CF as in k_sorted_pass (0 table reads, 1 recurrence, 2 moments).  Plane m of the group: x at pg.x[m] (virtual base of the
+// full image), table out at pg.h[m] ([nrows][b][x], k_sorted_pass's layout).
+// Registers: 2 NC NP for the sums beside ~70 for the indices of two rows and the pixel's temporaries: four waves per SIMD
+// (two workgroups per CU, as k_sorted_pass up to 12 columns) while that fits 128 without scratch, else two (one workgroup
+// per CU; <10, 2, 3> at four spilled 12 bytes).  No instantiation uses scratch (-Rpass-analysis=kernel-resource-usage).
+__host__ __device__ constexpr int planes_waves_per_simd(int nc, int np) { return nc * np <= 28 ? 4 : 2; }
+
+template <int NC, int CF, int NP>
+__global__ __launch_bounds__(kT, planes_waves_per_simd(NC, NP)) void k_sorted_reduce_planes(
+    const unsigned short* __restrict__ scol, const uint2* __restrict__ desc, const unsigned short* __restrict__ first, GridSpec gs,
+    int row0, int nrows, const double* __restrict__ Etab, const double* __restrict__ cvec, PlaneGroup pg, double kappa,
+    int lev_t0, int lev_nt) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    constexpr int n = kLevels * NC;
+    constexpr int SL = NC < 11 ? NC : 11;  // sums combined per slice, as k_sorted_pass
+    constexpr int PS = SL | 1;
+    constexpr bool REC = CF == 1, MOM = CF == 2;
+    static_assert(!MOM || NC > 1, "the moment form needs two columns");
+    const int W = gs.W;
+    const size_t pitch = sorted_row_pitch(W);
+    double* sE = reinterpret_cast<double*>(smem_raw);
+    double* sP = sE + ((W + 2) & ~1);
+    unsigned short* sfirst = reinterpret_cast<unsigned short*>(sP + (size_t)kT * PS);  // [2][260], rows alternate
+    double* sCk = reinterpret_cast<double*>(sfirst + 2 * 260);                          // [NC] C_b = kappa^(b (b - 1) / 2)
+    const int tid = threadIdx.x;
+    for (int i = tid; i <= W; i += kT) sE[i] = Etab[i];
+    if (MOM && tid == 0) {
+        double ck = 1.0, kp = 1.0;  // C_{b+1} = C_b kappa^b
+        for (int b = 0; b < NC; ++b) {
+            sCk[b] = ck;
+            ck *= kp;
+            kp *= kappa;
+        }
+    }
+    const int cb0 = gs.colOff, cs = gs.colStep;
+    const unsigned sEa = lds_addr(sE);
+
+    const int G = (int)gridDim.x;  // <= nrows
+    int lrow = blockIdx.x, nrow = lrow + G;
+    uint2 dsc = desc[(size_t)lrow * kT + tid];
+    uint2 dsc_n = dsc;
+    if (nrow < nrows) dsc_n = desc[(size_t)nrow * kT + tid];
+    if (tid < 258) sfirst[tid] = first[(size_t)lrow * 258 + tid];
+    uint2 idx[kMaxBlocks];
+    auto load_idx = [&](uint2 (&dst)[kMaxBlocks], const int row, const uint2 d) {
+        const uint2* slot = reinterpret_cast<const uint2*>(scol + (size_t)row * pitch + (size_t)tid * dsc_chp(d));
+        const int ln = dsc_len(d);
+#pragma unroll
+        for (int b = 0; b < kMaxBlocks; ++b) {  // blocks past the chunk: column 0 (the wave may walk further than this lane)
+            uint2 v = make_uint2(0u, 0u);
+            if (4 * b < ln) v = slot[b];
+            dst[b] = v;
+        }
+    };
+    load_idx(idx, lrow, dsc);
+    __syncthreads();  // sE, sfirst, sCk visible
+    for (int par = 0;; par ^= 1) {
+        const bool has_next = nrow < nrows;
+        const int nnrow = nrow + G;
+        const unsigned short* sfc = sfirst + par * 260;
+        const int len = dsc_len(dsc);
+        double acc[NP][NC];
+#pragma unroll
+        for (int m = 0; m < NP; ++m)
+#pragma unroll
+            for (int b = 0; b < NC; ++b) acc[m][b] = 0.0;
+        const double* cv_row = cvec + (size_t)lrow * W;
+        const float* xv_row[NP];
+#pragma unroll
+        for (int m = 0; m < NP; ++m) xv_row[m] = pg.x[m] + (size_t)(row0 + lrow) * W;
+        // in flight under the pixel loop: the descriptor of the row after next, the next row's first-chunk table and indices
+        uint2 dsc_nn = dsc_n;
+        unsigned short sf_n = 0;
+        uint2 idx_n[kMaxBlocks];
+        if (has_next) {
+            if (nnrow < nrows) dsc_nn = desc[(size_t)nnrow * kT + tid];
+            sf_n = first[(size_t)nrow * 258 + (tid < 258 ? tid : 257)];
+            load_idx(idx_n, nrow, dsc_n);
+        }
+        // One pixel at a time for all planes of the group.  The plane-independent part first, exactly k_sorted_pass's; then
+        // per plane y = c x and the sums.  Lanes past their own chunk work on column 0 and add exact zeros.
+        auto pixel_mom = [&](const unsigned c8, const int at) {
+            if constexpr (!MOM) return;
+            else {
+                const double e0 = e_at(sEa, c8, (unsigned)cb0 << 3);
+                double rho = e_at(sEa, c8, (unsigned)(cb0 + cs) << 3);
+                const bool keep = at < len;
+                const double cv = cv_row[c8 >> 3];
+                float xs[NP];
+#pragma unroll
+                for (int m = 0; m < NP; ++m) xs[m] = xv_row[m][c8 >> 3];
+                double r0 = __builtin_amdgcn_rcp(e0);  // e_0 is a normal number here (sorted_moments_ok)
+                r0 = fma(fma(-e0, r0, 1.0), r0, r0);
+                r0 = fma(fma(-e0, r0, 1.0), r0, r0);
+                rho = rho * r0;
+                const double rho2 = rho * rho;
+#pragma unroll
+                for (int m = 0; m < NP; ++m) {
+                    double y = cv * (double)xs[m];  // apply: y_i = c_i x_i
+                    y = keep ? y : 0.0;             // the padding of the slot adds exact zeros
+                    double te = y * e0;
+                    acc[m][0] = fma(y, e0, acc[m][0]);
+                    double to = te * rho;
+                    acc[m][1] = fma(te, rho, acc[m][1]);
+#pragma unroll
+                    for (int b = 2; b < NC; b += 2) {
+                        acc[m][b] = fma(te, rho2, acc[m][b]);
+                        te = te * rho2;
+                        if (b + 1 < NC) {
+                            acc[m][b + 1] = fma(to, rho2, acc[m][b + 1]);
+                            to = to * rho2;
+                        }
+                    }
+                }
+            }
+        };
+        auto pixel = [&](const unsigned c8, const bool on) {
+            const double cv = cv_row[c8 >> 3];
+            double y[NP];
+#pragma unroll
+            for (int m = 0; m < NP; ++m) {
+                const double v = cv * (double)xv_row[m][c8 >> 3];  // apply: y_i = c_i x_i
+                y[m] = on ? v : 0.0;                               // the padding of the slot adds exact zeros
+            }
+            column_factors<NC, REC>(sEa, c8, cb0, cs, kappa, [&](const int b, const double ev) {
+#pragma unroll
+                for (int m = 0; m < NP; ++m) acc[m][b] = fma(ev, y[m], acc[m][b]);
+            });
+        };
+        int wlen = len;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) wlen = max(wlen, __shfl_xor(wlen, off));
+        wlen = __builtin_amdgcn_readfirstlane(wlen);
+#pragma unroll
+        for (int b = 0; b < kMaxBlocks; ++b) {
+            if (4 * b >= wlen) break;
+            const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (4 * b + k < wlen) {
+                    if constexpr (MOM) pixel_mom(cs4[k], 4 * b + k);
+                    else pixel(cs4[k], 4 * b + k < len);
+                    NLE_PIXEL_FENCE();
+                }
+            }
+        }
+        if constexpr (MOM) {
+#pragma unroll
+            for (int m = 0; m < NP; ++m)
+#pragma unroll
+                for (int b = 2; b < NC; ++b) acc[m][b] = acc[m][b] * sCk[b];  // C_0 = C_1 = 1
+        }
+        __builtin_amdgcn_s_setprio(3);
+        // The combine of k_sorted_pass, plane after plane through the same sP: the partial sums of a level's chunks are
+        // written to LDS and every table entry is summed by ONE thread in chunk order, then stored.  No atomics.
+        const int nlev = lev_nt * 16, xlo = lev_t0 * 16;
+        const float inv_nlev = 1.0f / (float)nlev;
+#pragma unroll
+        for (int m = 0; m < NP; ++m) {
+            double* hrow = pg.h[m] + (size_t)lrow * n;
+#pragma unroll
+            for (int s0 = 0; s0 < NC; s0 += SL) {
+#pragma unroll
+                for (int i = 0; i < SL; ++i) sP[tid * PS + i] = (s0 + i < NC) ? acc[m][s0 + i] : 0.0;
+                __syncthreads();
+                if (m == 0 && s0 == 0) {
+                    // take the next row's loads in before the table stores below (all lanes), as k_sorted_pass does
+                    asm volatile("" ::"v"(sf_n), "v"(dsc_nn.x), "v"(dsc_nn.y));
+#pragma unroll
+                    for (int b = 0; b < kMaxBlocks; ++b) asm volatile("" ::"v"(idx_n[b].x), "v"(idx_n[b].y));
+                    // next row's first-chunk table: its last readers left before the previous row's end barrier, its next
+                    // readers come after the barriers of the next row's combine
+                    if (has_next && tid < 258) sfirst[(par ^ 1) * 260 + tid] = sf_n;
+                }
+                const int ns = (NC - s0 < SL) ? NC - s0 : SL;
+                for (int i = tid; i < ns * nlev; i += kT) {
+                    const int bb = (int)(((float)i + 0.5f) * inv_nlev);  // i / nlev, exact (see k_sorted_pass)
+                    const int xx = xlo + (i - bb * nlev);
+                    const int f0 = sfc[xx], f1 = sfc[xx + 1];
+                    double sum = 0.0;
+                    for (int t = f0; t < f1; ++t) sum += sP[t * PS + bb];
+                    hrow[(size_t)(s0 + bb) * kLevels + xx] = sum;
+                }
+                __syncthreads();  // before the next slice / plane / row overwrites sP and sfirst
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        if (!has_next) break;
+        lrow = nrow;
+        nrow = nnrow;
+        dsc = dsc_n;
+        dsc_n = dsc_nn;
+#pragma unroll
+        for (int b = 0; b < kMaxBlocks; ++b) idx[b] = idx_n[b];
+    }
+}
+
+// planes one launch takes: four up to 12 columns, two beyond (registers: 2 NC NP for the sums; no scratch in any instantiation)
+int sorted_planes_per_launch(GridSpec gs) { return gs.nSelCols <= 12 ? kPlanesPerLaunch : 2; }
+
+hipError_t sorted_reduce_planes(hipStream_t s, GridSpec gs, int row0, int nrows_local, const SortedRows& sr, const double* d_cvec,
+                                const PlaneGroup& pg, int np) {
+    const int nC = gs.nSelCols, lev_t0 = sr.lev_t0, lev_nt = sr.lev_nt;
+    if (!tables_apply(gs) || gs.W > sorted_max_width() || lev_t0 < 0 || lev_nt < 1 || lev_t0 + lev_nt > kLevels / 16 || np < 2 ||
+        np > sorted_planes_per_launch(gs))
+        return hipErrorInvalidValue;
+    if (nrows_local <= 0) return hipSuccess;
+    const size_t shm = sorted_lds_bytes(gs.W, (nC < 11 ? nC : 11) | 1);
+    // the grid of the single-plane pass, or one workgroup per CU where the registers leave room for one only
+    SortedRows one = sr;
+    if (planes_waves_per_simd(nC, np) < 4) one.wgs_per_cu = 1;
+    const int grid = sorted_grid(nrows_local, one);
+#define NLE_RP1(NCV, CFV, NPV)                                                                                            \
+    {                                                                                                                     \
+        if (shm > 48 * 1024) {                                                                                            \
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sorted_reduce_planes<NCV, CFV, NPV>),     \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                    \
+            if (ea != hipSuccess) return ea;                                                                              \
+        }                                                                                                                 \
+        hipLaunchKernelGGL((k_sorted_reduce_planes<NCV, CFV, NPV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol,       \
+                           sr.desc, sr.first, gs, row0, nrows_local, sr.E, d_cvec, pg, sr.kappa, lev_t0, lev_nt);         \
+    }
+    // NP: 2, 3 or 4 up to 12 columns, 2 beyond
+#define NLE_RPN(NCV, CFV)                                                                                                 \
+    {                                                                                                                     \
+        if constexpr ((NCV) <= 12) {                                                                                      \
+            if (np == 4) NLE_RP1(NCV, CFV, 4) else if (np == 3) NLE_RP1(NCV, CFV, 3) else NLE_RP1(NCV, CFV, 2)            \
+        } else {                                                                                                          \
+            NLE_RP1(NCV, CFV, 2)                                                                                          \
+        }                                                                                                                 \
+    }
+    // the form a single call would take: sorted_pass's dispatch on sr.mom / sr.rec
+#define NLE_RP(NCV)                                                                                                       \
+    case NCV:                                                                                                             \
+        if constexpr ((NCV) > 1) {                                                                                        \
+            if (sr.mom) {                                                                                                 \
+                NLE_RPN(NCV, 2)                                                                                           \
+                break;                                                                                                    \
+            }                                                                                                             \
+        }                                                                                                                 \
+        if constexpr ((NCV) > 12) {                                                                                       \
+            if (sr.rec) NLE_RPN(NCV, 1) else NLE_RPN(NCV, 0)                                                              \
+        } else {                                                                                                          \
+            if (sr.rec) return hipErrorInvalidValue;                                                                      \
+            NLE_RPN(NCV, 0)                                                                                               \
+        }                                                                                                                 \
+        break;
+    switch (nC) {
+        NLE_RP(1) NLE_RP(2) NLE_RP(3) NLE_RP(4) NLE_RP(5) NLE_RP(6) NLE_RP(7) NLE_RP(8) NLE_RP(9) NLE_RP(10) NLE_RP(11)
+        NLE_RP(12) NLE_RP(13) NLE_RP(14) NLE_RP(15) NLE_RP(16) NLE_RP(17) NLE_RP(18) NLE_RP(19) NLE_RP(20)
+        NLE_RP(21) NLE_RP(22) NLE_RP(23) NLE_RP(24) NLE_RP(25) NLE_RP(26) NLE_RP(27) NLE_RP(28) NLE_RP(29)
+        NLE_RP(30) NLE_RP(31) NLE_RP(32) NLE_RP(33) NLE_RP(34) NLE_RP(35) NLE_RP(36)
+        default: return hipErrorInvalidValue;
+    }
+#undef NLE_RP
+#undef NLE_RPN
+#undef NLE_RP1
+    return hipGetLastError();
+}
+
+}  // namespace nlek

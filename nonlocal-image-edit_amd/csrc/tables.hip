@@ -521,12 +521,30 @@ size_t hist_tiled_workspace_elems(GridSpec gs, int nrows_local) {
     return 2 * (size_t)nrows_local * n + (size_t)nslabs * std::max(n * gs.nSelRows, (size_t)(kLevels / 16) * ldp);
 }
 
+// the HH stage and the column sums behind a pixel kernel's tables d_h: d_z = the p column sums (ldp doubles)
+static hipError_t launch_hist_hh_z(hipStream_t s, const TableView& v, const double* d_h, double* d_HH, double* d_z) {
+    const GridSpec gs = v.gs;
+    const int nC = gs.nSelCols, nR = gs.nSelRows, p = v.p, ldp = v.ldp, nrows_local = v.nrows;
+    const int slab_rows = hist_slab_rows(gs, nrows_local), nslabs = (nrows_local + slab_rows - 1) / slab_rows;
+    const int lev_t0 = v.sorted ? v.sorted->lev_t0 : 0, lev_nt = v.sorted ? v.sorted->lev_nt : kLevels / 16;
+    const size_t shm_hh = (size_t)slab_rows * nR * sizeof(double);  // slab_rows <= 1024 in practice; nR <= 32
+    if (shm_hh > 48 * 1024) {
+        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist_hh),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_hh);
+        if (ea != hipSuccess) return ea;
+    }
+    hipLaunchKernelGGL(k_hist_hh, dim3((unsigned)((nC * lev_nt + 3) / 4), (unsigned)nslabs), dim3(256), shm_hh, s, nC, nR,
+                       nrows_local, slab_rows, lev_t0, lev_nt, v.er, d_h, v.Ep, p, ldp, d_HH);
+    hipLaunchKernelGGL(k_z_reduce, dim3((unsigned)((ldp + 7) / 8)), dim3(256), 0, s, d_HH, nslabs * lev_nt, p, ldp, d_z);
+    return hipGetLastError();
+}
+
 // one Sinkhorn half-iteration, tiled form; d_ws: hist_tiled_workspace_elems doubles; d_z: ldp doubles
 hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const double* d_w, double eps, double* d_ybuf,
                            double* d_ws, double* d_z, LaunchObserver* obs, const float* d_xvec) {
     if (!tables_apply(v.gs)) return hipErrorInvalidValue;
     const GridSpec gs = v.gs;
-    const int nC = gs.nSelCols, nR = gs.nSelRows, p = v.p, ldp = v.ldp, row0 = v.row0, nrows_local = v.nrows;
+    const int nC = gs.nSelCols, p = v.p, row0 = v.row0, nrows_local = v.nrows;
     const SortedRows* sorted = v.sorted;
     const double* d_cvec = mode == ROWPASS_XVEC ? v.cvec : nullptr;  // the other modes do not read it
     struct Scope {
@@ -535,7 +553,6 @@ hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const do
         ~Scope() { if (o) o->end(); }
     };
     const size_t n = (size_t)kLevels * nC;
-    const int slab_rows = hist_slab_rows(gs, nrows_local), nslabs = (nrows_local + slab_rows - 1) / slab_rows;
     double* d_g = d_ws;
     double* d_h = d_g + (size_t)nrows_local * n;
     double* d_HH = d_h + (size_t)nrows_local * n;
@@ -581,18 +598,34 @@ hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const do
 #undef NLE_HP
     }
     Scope sc(obs, SUB_HIST_HH);
-    {
-        const size_t shm_hh = (size_t)slab_rows * nR * sizeof(double);  // slab_rows <= 1024 in practice; nR <= 32
-        if (shm_hh > 48 * 1024) {
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist_hh),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_hh);
-            if (ea != hipSuccess) return ea;
-        }
-        hipLaunchKernelGGL(k_hist_hh, dim3((unsigned)((nC * lev_nt + 3) / 4), (unsigned)nslabs), dim3(256), shm_hh, s, nC, nR,
-                           nrows_local, slab_rows, lev_t0, lev_nt, v.er, d_h, v.Ep, p, ldp, d_HH);
+    return launch_hist_hh_z(s, v, d_h, d_HH, d_z);
+}
+
+size_t apply_reduce_planes_workspace_elems(GridSpec gs, int nrows_local, int np) {
+    // np tables in place of the g and h tables of a single pass
+    return hist_tiled_workspace_elems(gs, nrows_local) + (size_t)std::max(np - 2, 0) * nrows_local * kLevels * gs.nSelCols;
+}
+
+// reduce half of the sample-space apply for np planes on the level-sorted rows: ONE pixel kernel for the group
+// (sorted_reduce_planes), then the HH stage and the column sums of sink_hist_tiled plane by plane, through the same HH buffer
+hipError_t apply_reduce_planes(hipStream_t s, const TableView& v, const float* const* d_x, int np, double* d_ws, double* d_m,
+                               LaunchObserver* obs) {
+    if (!tables_apply(v.gs) || v.sorted == nullptr || np < 2 || np > sorted_planes_per_launch(v.gs)) return hipErrorInvalidValue;
+    const size_t tab = (size_t)v.nrows * kLevels * v.gs.nSelCols;
+    double* d_HH = d_ws + (size_t)np * tab;
+    PlaneGroup pg{};
+    for (int m = 0; m < np; ++m) pg.x[m] = d_x[m], pg.h[m] = d_ws + (size_t)m * tab;
+    if (obs) obs->begin(SUB_HIST_PIX);
+    hipError_t ep = sorted_reduce_planes(s, v.gs, v.row0, v.nrows, *v.sorted, v.cvec, pg, np);
+    if (obs) obs->end();
+    if (ep != hipSuccess) return ep;
+    for (int m = 0; m < np; ++m) {
+        if (obs) obs->begin(SUB_HIST_HH);
+        hipError_t eh = launch_hist_hh_z(s, v, pg.h[m], d_HH, d_m + (size_t)m * v.ldp);
+        if (obs) obs->end();
+        if (eh != hipSuccess) return eh;
     }
-    hipLaunchKernelGGL(k_z_reduce, dim3((unsigned)((ldp + 7) / 8)), dim3(256), 0, s, d_HH, nslabs * lev_nt, p, ldp, d_z);
-    return hipGetLastError();
+    return hipSuccess;
 }
 
 // layers of the sample-space apply's expand half that one launch handles: on the level-sorted rows what sorted_expand takes,

@@ -98,8 +98,15 @@ void ensure_V(nle_filter* f);
 // `done(l0, nl)`, when given, is called after layers [l0, l0 + nl) are complete on the stream (the host-buffer entry
 // points start their download there); `group` caps the layers per launch (0: as many as fit)
 using LayersDone = std::function<void(int, int)>;
+// ystride: floats between the output layers (0: n_local, the layer-major block nle_apply_layers writes)
 void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L x K */, int L, float* d_y,
-                        const LayersDone& done = nullptr, int group = 0, bool round8 = false);
+                        const LayersDone& done = nullptr, int group = 0, bool round8 = false, long long ystride = 0);
+// The same for P planes at once on a table filter with level-sorted rows, world == 1: plane m is
+// d_x[m] with nresp[m] responses, h_g the R = sum nresp rows of K (plane 0's first), output j at d_y + j * ystride.  The
+// reduce half walks the sorted rows once per group of nlek::sorted_planes_per_launch planes; every output is bit for bit
+// what apply_sample_space writes for its plane alone.
+void apply_sample_space_planes(nle_filter* f, const float* const* d_x, int P, const int* nresp, const double* h_g, int R,
+                               float* d_y, long long ystride, bool round8);
 // exact_train.hip
 nle_filter* train_exact_impl(nle_ctx* c, const float* d_lum, int H, int W, double hx, double hy, int T, int n_eig);
 

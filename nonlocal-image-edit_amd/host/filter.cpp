@@ -730,8 +730,7 @@ Image NLEFilter::denoise(const Image& image, DType k, int sigmaColor, int sigmaS
             "Cannot apply filter on image with different size from the image filter was trained on.");
     if (image.depth() != NLE_8U) throw std::runtime_error("Can only enchance RGB image.");
     const size_t np = image.total();
-    Dev d_bgr(ctx_, np * 3), d_lab(ctx_, np * 3), d_L(ctx_, np * 4), d_Y(ctx_, np * 4), d_c(ctx_, np * 4),
-        d_a(ctx_, np * 4), d_b(ctx_, np * 4);
+    Dev d_bgr(ctx_, np * 3), d_lab(ctx_, np * 3), d_L(ctx_, np * 4), d_Y(ctx_, np * 4), d_c(ctx_, np * 8), d_ab(ctx_, np * 8);
     check(nle_dev_upload(ctx_, d_bgr.p, image.ptr<unsigned char>(), np * 3), ctx_);
     check(nle_bgr2lab8(ctx_, static_cast<unsigned char*>(d_bgr.p), (long long)np, static_cast<unsigned char*>(d_lab.p),
                        d_L.f()), ctx_);
@@ -743,13 +742,17 @@ Image NLEFilter::denoise(const Image& image, DType k, int sigmaColor, int sigmaS
         if (verbose) std::cout << "eig " << i << " val: " << ev << std::endl;
         t(i) = std::pow(ev, k);
     }
-    for (int ch = 1; ch <= 2; ++ch) {  // :390-391
-        float* d_out = ch == 1 ? d_a.f() : d_b.f();
-        check(nle_lab8_channel(ctx_, static_cast<unsigned char*>(d_lab.p), (long long)np, ch, d_c.f()), ctx_);
-        check(nle_apply_rounded8(f_, d_c.f(), image.rows, image.cols, t.data(), d_out), ctx_);  // + :394-399
-    }
+    // a and b through the filter in one call (:390-391, + :394-399): two planes, the same response, rounded as
+    // nle_apply_rounded8 rounds
+    for (int ch = 1; ch <= 2; ++ch)
+        check(nle_lab8_channel(ctx_, static_cast<unsigned char*>(d_lab.p), (long long)np, ch, d_c.f() + (size_t)(ch - 1) * np), ctx_);
+    std::vector<double> t2((size_t)2 * t.size());
+    for (int i = 0; i < t.size(); ++i) t2[i] = t2[(size_t)t.size() + i] = t(i);
+    check(nle_apply_planes(f_, d_c.f(), 2, (long long)np, image.rows, image.cols, nullptr, t2.data(), NLE_REGION_OUT_ROUNDED8,
+                           d_ab.f(), (long long)np), ctx_);
+    const float *d_a = d_ab.f(), *d_b = d_ab.f() + np;
     // max(0) / min(255) / convertTo(CV_8U) of the three planes, merge, Lab -> BGR (:393-409)
-    check(nle_lab2bgr8_planes(ctx_, static_cast<unsigned char*>(d_lab.p), d_Y.f(), d_a.f(), d_b.f(), (long long)np,
+    check(nle_lab2bgr8_planes(ctx_, static_cast<unsigned char*>(d_lab.p), d_Y.f(), d_a, d_b, (long long)np,
                               static_cast<unsigned char*>(d_bgr.p)), ctx_);
     Image out(image.rows, image.cols, NLE_8U, 3);
     check(nle_dev_download(ctx_, out.ptr<unsigned char>(), d_bgr.p, np * 3), ctx_);
@@ -769,6 +772,45 @@ Image NLEFilter::apply(const Image& channel, const Vec& transformedEigVals) cons
     Image out(channel.rows, channel.cols, NLE_64F, 1);
     double* d = out.ptr<double>();
     for (size_t i = 0; i < y.size(); ++i) d[i] = y[i];
+    return out;
+}
+
+std::vector<Image> NLEFilter::applyPlanes(const std::vector<Image>& channels,
+                                          const std::vector<std::vector<Vec>>& responses) const {
+    long long n = 0;
+    int K = 0;
+    if (f_) nle_filter_info(f_, &n, &K, nullptr, nullptr, nullptr, nullptr);
+    if (!f_ || channels.empty() || channels.size() != responses.size())
+        throw std::runtime_error("applyPlanes: one set of responses per channel expected");
+    const size_t P = channels.size(), N = channels[0].total();
+    std::vector<int> nresp(P);
+    std::vector<double> resp;
+    std::vector<float> x(P * N);
+    for (size_t m = 0; m < P; ++m) {
+        if ((long long)channels[m].total() != n || channels[m].rows != channels[0].rows || channels[m].cols != channels[0].cols)
+            throw std::runtime_error("Number of values in channel must match that of training image.");
+        nresp[m] = (int)responses[m].size();
+        for (const Vec& r : responses[m]) {
+            if (r.size() != K) throw std::runtime_error("applyPlanes: one transformed eigenvalue per eigenvector expected");
+            resp.insert(resp.end(), r.data(), r.data() + K);
+        }
+        const std::vector<float> xm = plane_f32(channels[m]);
+        std::copy(xm.begin(), xm.end(), x.begin() + m * N);
+    }
+    const size_t R = K > 0 ? resp.size() / (size_t)K : 0;
+    Dev d_x(ctx_, P * N * 4), d_y(ctx_, std::max<size_t>(R, 1) * N * 4);
+    check(nle_dev_upload(ctx_, d_x.p, x.data(), P * N * 4), ctx_);
+    check(nle_apply_planes(f_, d_x.f(), (int)P, (long long)N, channels[0].rows, channels[0].cols, nresp.data(), resp.data(),
+                           NLE_REGION_OUT_F32, d_y.f(), (long long)N), ctx_);
+    std::vector<float> y(R * N);
+    check(nle_dev_download(ctx_, y.data(), d_y.p, R * N * 4), ctx_);
+    std::vector<Image> out;
+    for (size_t j = 0; j < R; ++j) {
+        Image m(channels[0].rows, channels[0].cols, NLE_64F, 1);
+        double* d = m.ptr<double>();
+        for (size_t i = 0; i < N; ++i) d[i] = y[j * N + i];
+        out.push_back(std::move(m));
+    }
     return out;
 }
 
