@@ -311,6 +311,34 @@ int nle_row_scalings(nle_ctx* ctx, const float* d_phi, long long M, int ld, int 
  * uninitialised buffer, NaN); nle_sinkhorn_scalings64 takes r <= 2048 (any ld), more returns NLE_ERR_INVALID. */
 int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
                          double hy, double* h_Ka, double* d_kab);
+/* The Nystrom residual map (new in this build): where the samples fail to explain a pixel.  For pixel i of the FULL H x W plane
+ * with fp64 affinity row k_i (p entries, exactly what nle_compute_kernel64 writes under the ctx's patch radius, chroma planes
+ * and sampler, with the same refusals) and K_A the samples' own affinities:
+ *   r_i = K_ii - k_i^T pinv(K_A) k_i = 1 - sum_{k kept} (v_k^T k_i)^2 / lambda_k
+ * pinv at the reference's cut: the leading run of eigenvalues >= NLE_EPS (src/filter.cpp:213-215,262-271).  In the reference's
+ * terms r_i = 1 - sum_k lambda_k phi_ik^2 with (lambda, phi) of nystromApproximation: the diagonal of K - K~ for exactly the
+ * extension a train uses.  K - K~ is positive semi-definite, so r_i is in [0, 1] up to rounding, |K_ij - K~_ij| <=
+ * sqrt(r_i r_j), and sum_i r_i is the trace-norm error of the extension.  It is computed as 1 - || F^T k_i ||^2 with F F^T =
+ * pinv(K_A): F = V diag(1 / sqrt(lambda)), or L^-T where K_A is certified full rank at the cut and factored by Cholesky, as the
+ * default train factors it (both are legitimate; they differ by rounding).
+ *   d_r        H W floats or NULL: d_r[i] = (float)r_i in natural pixel order, sample pixels included (the same formula),
+ *              not clamped (a few ulp below 0 can occur)
+ *   h_summary  [0] sum_i r_i, [1] max_i r_i, [2] row-major index of the first maximum, [3] number of pixels with r_i > thresh
+ *              -- all from the unrounded fp64 r_i, block partials folded in a fixed order: two runs agree bit for bit in map
+ *              and summary
+ *   form       NLE_RESID_ROWS   explicit fp64 affinity rows chunk by chunk (NLE_STREAM64_CHUNK_MB), any option, p <= 2048;
+ *                               the result does not depend on the chunk size
+ *              NLE_RESID_FUSED  the affinities are generated in fp64 inside the fp64-MFMA kernel, nothing N x p is stored:
+ *                               patch radius 0, no chroma planes, NLE_SAMPLER_GRID, p <= 256
+ *              NLE_RESID_AUTO   FUSED where it applies, else ROWS
+ * NLE_ERR_INVALID with a message, nothing enqueued and the ctx left usable: world > 1 (before any collective), a NULL plane or
+ * summary, thresh not finite, an unknown form, p > 2048, NLE_RESID_FUSED where it does not apply, hx or hy not > 0, and
+ * whatever nle_compute_kernel64 refuses. */
+#define NLE_RESID_AUTO 0
+#define NLE_RESID_ROWS 1
+#define NLE_RESID_FUSED 2
+int nle_nystrom_residual(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
+                         double hy, int form, double thresh, float* d_r, double* h_summary);
 int nle_ts_gemm64(nle_ctx* ctx, const double* d_A, long long M, int lda, int kd, const double* h_B, int nc, double* d_C);
 int nle_sinkhorn_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, const double* h_eigvals,
                             int max_iter, double* h_u_c, double* h_u_r);

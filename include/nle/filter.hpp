@@ -212,6 +212,23 @@ public:
     // for bit what apply(channels[m], responses[m][l]) returns.  Host buffers in and out, like apply.
     std::vector<Image> applyPlanes(const std::vector<Image>& channels, const std::vector<std::vector<Vec>>& responses) const;
 
+    // The Nystrom residual map of a sample grid and bandwidths on this image (nle_nystrom_residual in nle.h; new here): r_i =
+    // 1 - k_i^T pinv(K_A) k_i per pixel, the diagonal of K - K~ for the extension a train with the same arguments uses -- where
+    // the samples fail to explain a pixel.  `image`: a 1-channel CV_64F luminance plane (as trainFilter takes it) or a
+    // 3-channel 8-bit BGR image (as trainForEnhancement takes it: its L channel, and its a and b planes when chromaBandwidth
+    // is set).  Uses patchRadius, sampler and chromaBandwidth like a train -- a bare plane has no a and b planes, so
+    // chromaBandwidth is ignored for it, as trainFilter ignores it; needs no trained filter and leaves one untouched.
+    // One device (not NLE_DEVICES groups); throws std::runtime_error with `exact` set (that filter has no extension) and for
+    // whatever the call refuses.  form: NLE_RESID_AUTO / _ROWS / _FUSED.
+    struct Residual {
+        Image map;                // CV_64F, the fp32 values of the device map
+        double sum = 0, max = 0;  // sum_i r_i (the trace-norm error of the extension), max_i r_i
+        long long argmax = 0;     // row-major index of the first maximum
+        long long count = 0;      // pixels with r_i > thresh
+    };
+    Residual nystromResidual(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int form = 0,
+                             double thresh = 0.5) const;
+
     Vec eigvals() const;                 // m_eigvals
     Mat eigvecs() const;                 // m_eigvecs, downloaded (N x K')
     void timings(double ms[6]) const;    // nle_filter_timings

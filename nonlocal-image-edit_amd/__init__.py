@@ -41,6 +41,7 @@ REGION_MAX, REGION_LAYERS_MAX = _abi.NLE_REGION_MAX, _abi.NLE_REGION_LAYERS_MAX
 REGION_OUT_F32, REGION_OUT_ROUNDED8, REGION_OUT_U8 = (_abi.NLE_REGION_OUT_F32, _abi.NLE_REGION_OUT_ROUNDED8,
                                                       _abi.NLE_REGION_OUT_U8)
 PLANES_MAX = _abi.NLE_PLANES_MAX  # nle_apply_planes: planes per call (its output kinds are REGION_OUT_F32 / _ROUNDED8)
+RESID_AUTO, RESID_ROWS, RESID_FUSED = _abi.NLE_RESID_AUTO, _abi.NLE_RESID_ROWS, _abi.NLE_RESID_FUSED  # nle_nystrom_residual
 
 _lib = None
 
@@ -336,6 +337,22 @@ class Context:
         _check(lib().nle_sample_pixels(self._h, C.c_void_p(x.data_ptr()), H, W, int(n_row_samples), int(n_col_samples),
                                        float(hx), float(hy), _np_ptr(out), C.byref(p)), self._h)
         return out[:p.value]
+
+    def nystrom_residual(self, lum, n_row_samples, n_col_samples, hx, hy, form: int = RESID_AUTO, thresh: float = 0.5,
+                         want_map: bool = True):
+        """the Nystrom residual map r_i = 1 - k_i^T pinv(K_A) k_i of the full plane `lum` under the ctx's affinity options
+        (nle_nystrom_residual): returns (r [H x W float32 CUDA tensor, or None without want_map], summary) with summary =
+        dict(sum, max, argmax (row-major index of the first maximum), count (pixels with r > thresh))"""
+        torch = _torch()
+        x = self._lum(lum)
+        H, W = x.shape
+        r = torch.empty((H, W), dtype=torch.float32, device=x.device) if want_map else None
+        self._sync_in()
+        s = np.zeros(4, dtype=np.float64)
+        _check(lib().nle_nystrom_residual(self._h, C.c_void_p(x.data_ptr()), H, W, int(n_row_samples), int(n_col_samples),
+                                          float(hx), float(hy), int(form), float(thresh),
+                                          C.c_void_p(r.data_ptr()) if want_map else None, _np_ptr(s)), self._h)
+        return r, dict(sum=float(s[0]), max=float(s[1]), argmax=int(s[2]), count=int(s[3]))
 
     def affinity_product64(self, lum, X, hx, hy):
         """Y = K X with K the exact N x N affinity of the H x W plane `lum` (integer valued in [0, 255]; the kernel of

@@ -232,6 +232,23 @@ hipError_t to_f32(hipStream_t s, const double* d_X, long long n, float* d_out);
 hipError_t scale_rows64_to(hipStream_t s, const double* d_X, int m, int n, const double* d_dl, double* d_Y, long long rsY,
                            long long csY);
 
+// ---- the Nystrom residual map (resid.hip): r_i = 1 - || F^T k_i ||^2 per pixel, F (p x m) with F F^T = pinv(K_A)
+// Both routes write (float)r_i to d_r (may be null) and, per tile of kResidTile pixels, the summary partial {sum r, max r, index
+// of the first maximum, count of r > thresh} from the fp64 r_i to d_part (4 resid_num_parts(N) doubles); resid_finish folds
+// the partials into d_out (4 doubles) in a fixed order.
+constexpr int kResidTile = 128;
+inline long long resid_num_parts(long long N) { return (N + kResidTile - 1) / kResidTile; }
+// fused (grid samples, single-value affinities, p <= 256): the fp64 affinities are generated inside the fp64-MFMA kernel.
+// d_F: p x resid_fused_ld(m) row-major, columns >= m zero; sw = 1/hx^2, pw = 1/hy^2; the whole plane (N = H W pixels)
+bool resid_fused_applies(int p);
+int resid_fused_ld(int m);
+hipError_t nystrom_resid64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, double sw, double pw,
+                           long long N, const double* d_F, int m, double thresh, float* d_r, double* d_part);
+// rows: d_T (M x ldt, logical width m) = affinity rows [i0, i0 + M) times F (ts_gemm64); i0 a multiple of kResidTile
+hipError_t resid_rows64(hipStream_t s, const double* d_T, long long M, int ldt, int m, long long i0, double thresh, float* d_r,
+                        double* d_part);
+hipError_t resid_finish(hipStream_t s, const double* d_part, long long nparts, double* d_out);
+
 // ---- one-workgroup Householder tridiagonalisation (tridiag.hip): Q n x n col-major (lower triangle read), n <= tridiag_max_n();
 // outputs in the conventions of nleh::tridiag_reduce (V: u_i in column i rows 0..i-1; hs; d, e)
 int tridiag_max_n();

@@ -218,6 +218,90 @@ void compute_kernel_impl(nle_ctx* ctx, const float* d_lum, int H, int W, int nRo
     prof_flush(ctx);
 }
 
+// nle_nystrom_residual: r_i = 1 - || F^T k_i ||^2 for every pixel, F = B diag(sqrt(lambda)) of solve_Ka (F F^T = pinv(K_A) at
+// the reference's cut; L^-T on the Cholesky route), and its summary.  FUSED (resid.hip: k_nystrom_resid64) generates the fp64
+// affinities inside the MFMA kernel; ROWS runs AffinityRows64 -> ts_gemm64 -> k_resid_rows chunk by chunk, the chunks cut at
+// multiples of the summary tile so that the partials -- and the summary's bits -- do not depend on the chunk size.
+void nystrom_residual_impl(nle_ctx* ctx, const float* d_lum, int H, int W, int nRow, int nCol, double hx, double hy, int form,
+                           double thresh, float* d_r, double* h_summary) {
+    if (ctx->world > 1) throw Fail{NLE_ERR_INVALID, "nle_nystrom_residual: world > 1 is not supported (no slabs)"};
+    if (!d_lum || !h_summary) throw Fail{NLE_ERR_INVALID, "nle_nystrom_residual: the plane and the summary must not be NULL"};
+    if (!std::isfinite(thresh)) throw Fail{NLE_ERR_INVALID, "nle_nystrom_residual: thresh must be finite"};
+    if (form != NLE_RESID_AUTO && form != NLE_RESID_ROWS && form != NLE_RESID_FUSED)
+        throw Fail{NLE_ERR_INVALID, "nle_nystrom_residual: unknown form " + std::to_string(form)};
+    const GridSpec gs = checked_grid(H, W, nRow, nCol);
+    if (!(hx > 0) || !(hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
+    const int p = gs.p(), ldp = ld4(p);
+    if (p > 2048) throw Fail{NLE_ERR_INVALID, "more than 2048 samples is not supported"};
+    const AffinityOpts opts = affinity_opts(ctx);
+    check_affinity_opts(ctx, opts, gs, H, W, hx, hy, Caller::KERNEL64);
+    const bool fused_ok = !opts.any() && nlek::resid_fused_applies(p);
+    if (form == NLE_RESID_FUSED && !fused_ok)
+        throw Fail{NLE_ERR_INVALID, "NLE_RESID_FUSED takes single-value luminance affinities (patch radius 0, no chroma planes), "
+                                    "the grid sampler and at most 256 samples: use NLE_RESID_ROWS or NLE_RESID_AUTO"};
+    const bool fused = form == NLE_RESID_FUSED || (form == NLE_RESID_AUTO && fused_ok);
+    HIP_OK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    std::vector<long long> list;
+    FetchSpec spec;
+    if (opts.listed()) list = farthest_list(ctx, d_lum, gs, hx, hy), spec.list = &list;
+    const SampleSet ss = fetch_samples(ctx, d_lum, gs, opts, spec);
+    require_integer_planes(ctx, ss, /*agree_over_ranks=*/false);
+    const std::vector<double> Ka = build_Ka(ss, hx, hy);
+    const Nystrom ny = solve_Ka(ctx, ctx->sw, Ka, p, /*allow_chol=*/true);  // as the default train factors Ka
+    const int m = ny.r;
+    // F on the device: column-major p x m (ts_gemm64's B) for ROWS, row-major p x ldf (zero padded) for FUSED
+    const int ldf = fused ? nlek::resid_fused_ld(m) : m;
+    DevBuf<double> d_F((size_t)p * ldf);
+    std::vector<double> F;  // host staging: alive until the stream is drained below
+    // device Cholesky (from NLE_DEV_SOLVER_MIN = 288 samples on: the fused form only when that switch is lowered): L^-1 is
+    // p x p column-major there, i.e. F = L^-T row-major
+    if (ny.dev) {
+        if (fused) {
+            HIP_OK(hipMemsetAsync(d_F.p, 0, d_F.n * sizeof(double), st));
+            HIP_OK(hipMemcpy2DAsync(d_F.p, (size_t)ldf * sizeof(double), ny.dev->ch.Linv.p, (size_t)p * sizeof(double),
+                                    (size_t)p * sizeof(double), p, hipMemcpyDeviceToDevice, st));
+        } else {
+            PROFILED(ctx, NLE_K_SMALL, nlek::transpose64(st, p, ny.dev->ch.Linv.p, d_F.p));
+        }
+    } else {
+        F.assign((size_t)p * ldf, 0.0);
+        for (int k = 0; k < m; ++k) {
+            const double s = std::sqrt(ny.lam[k]);
+            for (int a = 0; a < p; ++a) F[fused ? (size_t)a * ldf + k : (size_t)k * p + a] = ny.B[(size_t)k * p + a] * s;
+        }
+        HIP_OK(hipMemcpyAsync(d_F.p, F.data(), F.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    const long long N = (long long)H * W, nparts = nlek::resid_num_parts(N);
+    DevBuf<double> d_part((size_t)nparts * 4), d_sum(4);
+    if (fused) {
+        DevBuf<float4> d_samples = upload_samples(ctx, ss);
+        PROFILED(ctx, NLE_K_NYSTROM, nlek::nystrom_resid64(st, d_lum, gs, d_samples.p, p, 1.0 / (hx * hx), 1.0 / (hy * hy), N,
+                                                           d_F.p, m, thresh, d_r, d_part.p));
+        PROFILED(ctx, NLE_K_SMALL, nlek::resid_finish(st, d_part.p, nparts, d_sum.p));
+        HIP_OK(hipMemcpyAsync(h_summary, d_sum.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    } else {
+        const int ldt = ld4(m);
+        // train_stream64's chunk (NLE_STREAM64_CHUNK_MB of affinity rows), cut down to a multiple of the summary tile
+        const long long rows_fit = (long long)(((size_t)ctx->sw.stream64_chunk_mb << 20) / ((size_t)ldp * sizeof(double)));
+        long long CH = std::max<long long>(256, std::min<long long>(N, rows_fit));
+        if (CH < N) CH -= CH % nlek::kResidTile;
+        const AffinityRows64 kab(ctx, d_lum, ss, hx, hy, /*want_mask=*/false);
+        DevBuf<double> d_K((size_t)CH * ldp), d_T((size_t)CH * ldt);
+        for (long long i0 = 0; i0 < N; i0 += CH) {
+            const long long mc = std::min(CH, N - i0);
+            PROFILED(ctx, NLE_K_AFFINITY, kab.rows(i0, mc, d_K.p));
+            PROFILED(ctx, NLE_K_NYSTROM, nlek::ts_gemm64(st, d_K.p, mc, ldp, p, d_F.p, m, nullptr, d_T.p, ldt));
+            PROFILED(ctx, NLE_K_SMALL, nlek::resid_rows64(st, d_T.p, mc, ldt, m, i0, thresh, d_r, d_part.p));
+        }
+        PROFILED(ctx, NLE_K_SMALL, nlek::resid_finish(st, d_part.p, nparts, d_sum.p));
+        HIP_OK(hipMemcpyAsync(h_summary, d_sum.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    prof_flush(ctx);
+}
+
 // the micro-benchmarks: one untimed launch, then the average of `reps` timed ones
 template <typename Launch>
 double bench_ms(nle_ctx* ctx, int reps, Launch&& launch) {
@@ -398,6 +482,14 @@ int nle_compute_kernel64(nle_ctx* ctx, const float* d_lum, int H, int W, int n_r
                          double hy, double* h_Ka, double* d_kab) {
     if (!ctx || !d_lum) return NLE_ERR_INVALID;
     return guard(ctx, [&] { compute_kernel_impl(ctx, d_lum, H, W, n_row_samples, n_col_samples, hx, hy, h_Ka, d_kab); });
+}
+
+int nle_nystrom_residual(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx, double hy,
+                         int form, double thresh, float* d_r, double* h_summary) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        nystrom_residual_impl(ctx, d_lum, H, W, n_row_samples, n_col_samples, hx, hy, form, thresh, d_r, h_summary);
+    });
 }
 
 int nle_ts_gemm64(nle_ctx* ctx, const double* d_A, long long M, int lda, int kd, const double* h_B, int nc, double* d_C) {

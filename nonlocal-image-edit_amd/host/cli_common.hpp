@@ -10,7 +10,8 @@
 // anything touches the GPU.  For enhance only, region edits (NLEFilter::enhanceRegions): `--region MASK:w1,w2,...`, up to
 // NLE_REGION_MAX times (split at the last `:`; MASK any image the readers decode, its first channel is the stroke; as many
 // weights as positional ones, which are the background's), `--region-spread T` and `--region-floor F` (finite, > 0; only
-// with a region).
+// with a region); and the flag `--nystrom-report` with its optional `--nystrom-map FILE` (NLEFilter::nystromResidual; not
+// with --exact).
 #pragma once
 
 #include <cmath>
@@ -42,6 +43,8 @@ struct FilterArgs {
     };
     std::vector<Region> regions;
     double regionSpread = 4, regionFloor = 0.05;
+    bool nystromReport = false;  // --nystrom-report (enhance only)
+    std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
 
 // a finite number > 0, or exit 2
@@ -58,8 +61,9 @@ inline double positive_option(const char* prog, const std::string& opt, const st
 // false (after printing the usage line to stderr) when fewer than `min_argc` arguments were given
 // allow_chroma: the tool takes `--chroma HC` (enhance); otherwise the option is refused (denoise estimates a and b)
 // allow_regions: the tool takes the region options (enhance); otherwise they are refused (denoise has no layer weights)
+// allow_nystrom: the tool takes `--nystrom-report` / `--nystrom-map FILE` (enhance); otherwise they are refused
 inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false,
-                  bool allow_regions = false) {
+                  bool allow_regions = false, bool allow_nystrom = false) {
     std::vector<char*> shifted;
     int first = 1;  // the first argument after the leading options
     bool spreadGiven = false, floorGiven = false;
@@ -73,6 +77,26 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
         if (opt.rfind("--exact=", 0) == 0) {
             std::cerr << argv[0] << ": --exact takes no value, got '" << opt << "'" << std::endl;
             std::exit(2);
+        }
+        if (opt == "--nystrom-report" || opt == "--nystrom-map" || opt.rfind("--nystrom-report=", 0) == 0) {
+            if (!allow_nystrom) {
+                std::cerr << argv[0] << ": " << opt << " is not supported here: the residual report belongs to enhance" << std::endl;
+                std::exit(2);
+            }
+            if (opt == "--nystrom-report") {
+                a->nystromReport = true;
+                first += 1;
+                continue;
+            }
+            const std::string file = first + 1 < argc ? argv[first + 1] : "";
+            if (opt != "--nystrom-map" || file.empty() || file.rfind("--", 0) == 0) {
+                std::cerr << argv[0] << ": --nystrom-report takes no value and --nystrom-map takes a file name, got '" << opt
+                          << (opt == "--nystrom-map" ? " " + file : "") << "'" << std::endl;
+                std::exit(2);
+            }
+            a->nystromMap = file;
+            first += 2;
+            continue;
         }
         const bool regionOpt = opt == "--region" || opt == "--region-spread" || opt == "--region-floor";
         if (opt != "--patch-radius" && opt != "--sampler" && opt != "--chroma" && !regionOpt) break;
@@ -158,6 +182,15 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
     if (a->chroma != 0 && (a->exact || a->patchRadius > NLE_CHROMA_PATCH_RADIUS_MAX)) {
         std::cerr << argv[0] << ": --chroma does not combine with --exact or with --patch-radius R > "
                   << NLE_CHROMA_PATCH_RADIUS_MAX << std::endl;
+        std::exit(2);
+    }
+    if (!a->nystromMap.empty() && !a->nystromReport) {
+        std::cerr << argv[0] << ": --nystrom-map needs --nystrom-report" << std::endl;
+        std::exit(2);
+    }
+    if (a->nystromReport && a->exact) {
+        std::cerr << argv[0] << ": --nystrom-report and --nystrom-map do not combine with --exact: the exact filter has no "
+                  << "Nystrom extension" << std::endl;
         std::exit(2);
     }
     if ((spreadGiven || floorGiven) && a->regions.empty()) {

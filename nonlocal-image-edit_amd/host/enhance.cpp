@@ -4,12 +4,16 @@
 // Differences: runs headless (no imshow / waitKey, src/enhance.cpp:48-49), reads BMP/PPM and writes
 // BMP/PPM/PNG through nle/image_io.hpp instead of OpenCV.  The hot path runs on the GPU through
 // libnle_hip.so.  New here: leading options (cli_common.hpp), among them the region edits `--region MASK:w1,w2,...`
-// (repeatable), `--region-spread T`, `--region-floor F`: the positional weights are then the background's.
+// (repeatable), `--region-spread T`, `--region-floor F`: the positional weights are then the background's; and
+// `--nystrom-report [--nystrom-map FILE]`: one more stdout line with the Nystrom residual of the sample grid (mean, max and
+// its pixel, share of pixels above 0.5) and the map as an 8-bit grey image, round(255 clamp(r, 0, 1)).
+#include <algorithm>
+
 #include "cli_common.hpp"
 
 int main(int argc, char* argv[]) {
     nlecli::FilterArgs a;
-    if (!nlecli::parse(argc, argv, 10, &a, /*allow_chroma=*/true, /*allow_regions=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
+    if (!nlecli::parse(argc, argv, 10, &a, /*allow_chroma=*/true, /*allow_regions=*/true, /*allow_nystrom=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
     const nle::Image image = nlecli::load(a);
     if (image.empty()) return 0;                        // src/enhance.cpp:34-37
     // the strokes: the first channel of every mask, read before anything touches the GPU
@@ -47,5 +51,24 @@ int main(int argc, char* argv[]) {
                                               : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,
                                                                       a.regionFloor);
     nlecli::report(filter);
-    return nlecli::finish(a, result, "Done. Press any key in result window to exit.");  // src/enhance.cpp:45
+    const int rc = nlecli::finish(a, result, "Done. Press any key in result window to exit.");  // src/enhance.cpp:45
+    if (a.nystromReport) {  // after the reference's banners: one line, and the map as an 8-bit grey image
+        const nle::NLEFilter::Residual res = filter.nystromResidual(image, a.rowSamples, a.colSamples, a.hx, a.hy);
+        const double n = (double)image.total();
+        std::cout << "Nystrom residual: mean " << res.sum / n << " max " << res.max << " at (" << res.argmax / image.cols << ", "
+                  << res.argmax % image.cols << ") share above 0.5: " << (double)res.count / n << std::endl;
+        if (!a.nystromMap.empty()) {
+            nle::Image grey(image.rows, image.cols, nle::NLE_8U, 3);  // grey as three equal channels (what the writers take)
+            for (size_t i = 0; i < image.total(); ++i) {
+                const double r = std::min(1.0, std::max(0.0, res.map.ptr<double>()[i]));
+                const unsigned char v = (unsigned char)std::floor(255.0 * r + 0.5);
+                grey.ptr<unsigned char>()[3 * i] = grey.ptr<unsigned char>()[3 * i + 1] = grey.ptr<unsigned char>()[3 * i + 2] = v;
+            }
+            if (!nle::imwrite(a.nystromMap, grey)) {
+                std::cerr << "Failed to write " << a.nystromMap << std::endl;
+                return 1;
+            }
+        }
+    }
+    return rc;
 }

@@ -1008,6 +1008,55 @@ Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& st
     return out;
 }
 
+NLEFilter::Residual NLEFilter::nystromResidual(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int form,
+                                               double thresh) const {
+    if (exact) throw std::runtime_error("nystromResidual: the exact filter has no Nystrom extension");
+    const bool bgr = image.channels() == 3 && image.depth() == NLE_8U;
+    if (!bgr && !(image.channels() == 1 && image.depth() == NLE_64F))
+        throw std::runtime_error("nystromResidual takes a 1-channel CV_64F plane or a 3-channel 8-bit image");
+    if (nRowSamples > image.rows || nColSamples > image.cols)
+        throw std::runtime_error("Number of samples per row and col must be <= that of image.");
+    nle_ctx* c = shared_ctx();
+    const size_t n = image.total();
+    Dev d_L(c, n * 4), d_r(c, n * 4);
+    std::unique_ptr<Dev> d_a, d_b;
+    if (bgr) {  // getLuminanceChannel (:460-469) on the device, as trainForEnhancement
+        Dev d_bgr(c, n * 3), d_lab(c, n * 3);
+        unsigned char* lab = static_cast<unsigned char*>(d_lab.p);
+        check(nle_dev_upload(c, d_bgr.p, image.ptr<unsigned char>(), n * 3), c);
+        check(nle_bgr2lab8(c, static_cast<unsigned char*>(d_bgr.p), (long long)n, lab, d_L.f()), c);
+        if (chromaBandwidth != 0) {
+            d_a.reset(new Dev(c, n * 4));
+            d_b.reset(new Dev(c, n * 4));
+            check(nle_lab8_channel(c, lab, (long long)n, 1, d_a->f()), c);
+            check(nle_lab8_channel(c, lab, (long long)n, 2, d_b->f()), c);
+        }
+    } else {
+        const std::vector<float> lum = plane_f32(image);
+        check(nle_dev_upload(c, d_L.p, lum.data(), n * 4), c);
+    }
+    // the shared ctx's options as a train sets them, and back whatever happens
+    int st = nle_ctx_set_patch_radius(c, patchRadius);
+    if (st == NLE_OK) st = nle_ctx_set_sampler(c, sampler);
+    if (st == NLE_OK && d_a) st = nle_ctx_set_chroma(c, d_a->f(), d_b->f(), chromaBandwidth);
+    double s[4] = {0, 0, 0, 0};
+    if (st == NLE_OK)
+        st = nle_nystrom_residual(c, d_L.f(), image.rows, image.cols, nRowSamples, nColSamples, hx, hy, form, thresh, d_r.f(), s);
+    const std::string err = st != NLE_OK ? nle_last_error(c) : "";
+    nle_ctx_set_chroma(c, nullptr, nullptr, 0.0);
+    nle_ctx_set_patch_radius(c, 0);
+    nle_ctx_set_sampler(c, NLE_SAMPLER_GRID);
+    if (st != NLE_OK) throw std::runtime_error(err);
+    std::vector<float> h(n);
+    check(nle_dev_download(c, h.data(), d_r.p, n * 4), c);
+    Residual out;
+    out.map = Image(image.rows, image.cols, NLE_64F, 1);
+    double* d = out.map.ptr<double>();
+    for (size_t i = 0; i < n; ++i) d[i] = h[i];
+    out.sum = s[0], out.max = s[1], out.argmax = (long long)s[2], out.count = (long long)s[3];
+    return out;
+}
+
 Vec NLEFilter::eigvals() const {
     if (!f_) return Vec();
     int K = 0;
