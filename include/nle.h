@@ -179,6 +179,13 @@ int nle_sample_pixels(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_
  * the bf16 matrix cores with SPLIT operands (each fp32 value as three bf16, six products, fp32 accumulate: fp32 accuracy at
  * ~2.7x the exact-fp32 MFMA's rate; plain bf16 operands miss the parity bar).  Off by default. */
 int nle_ctx_set_nystrom_bf16x3(nle_ctx* ctx, int on);
+/* Reuse of training's work in apply (default formulation on one rank, level-sorted rows; on by default).  A train leaves the
+ * reduce half of apply for the plane it trained on, computed behind its Gram kernels, and the plane in one byte per pixel; an
+ * apply whose input equals that plane bit for bit (compared by content on the device, never by pointer) takes it over instead
+ * of computing its own.  Outputs are the same bits either way.  on == 0: trains on this ctx leave nothing (one byte per pixel
+ * and ~3 % of a train saved for a caller who filters other planes only) and applies on it compute their own whatever the
+ * filter holds. */
+int nle_ctx_set_train_reduce(nle_ctx* ctx, int on);
 
 /* Slab input (multi-GPU, SURVEY.md section 8e "each GPU uploads / downloads only its slab"): with on != 0 every plane
  * handed to nle_train*, nle_apply* on this ctx holds ONLY the rows [row0, row1) of this rank (nle_slab_rows), n_local

@@ -376,6 +376,10 @@ class Context:
                                             C.c_void_p(Xp.data_ptr()), ldx, ncols, C.c_void_p(Y.data_ptr())), self._h)
         return Y[:, :ncols]
 
+    def set_train_reduce(self, on: bool = True):
+        """trains leave apply's reduce half for their own plane and applies may take it over (nle_ctx_set_train_reduce)"""
+        _check(lib().nle_ctx_set_train_reduce(self._h, 1 if on else 0), self._h)
+
     def set_nystrom_bf16x3(self, on: bool = True):
         """the fused Nystrom GEMM on the bf16 matrix cores with split operands (nle_ctx_set_nystrom_bf16x3)"""
         _check(lib().nle_ctx_set_nystrom_bf16x3(self._h, 1 if on else 0), self._h)

@@ -314,6 +314,12 @@ int nle_ctx_set_nystrom_bf16x3(nle_ctx* ctx, int on) {
     return NLE_OK;
 }
 
+int nle_ctx_set_train_reduce(nle_ctx* ctx, int on) {
+    if (!ctx) return NLE_ERR_INVALID;
+    ctx->train_reduce = on != 0;
+    return NLE_OK;
+}
+
 int nle_ctx_set_patch_radius(nle_ctx* ctx, int radius) {
     if (!ctx) return NLE_ERR_INVALID;
     return guard(ctx, [&] {

@@ -62,7 +62,8 @@ enum RowpassMode { ROWPASS_COLSUM = 0, ROWPASS_RECIP = 1, ROWPASS_XVEC = 2 };
 // out[k] = lum[sel_index(k)] for the p samples
 hipError_t gather_samples(hipStream_t s, const float* d_lum, GridSpec gs, float* d_out);
 // fp64, 0 for samples outside rows [row0, row1) (d_lum: virtual base of the full image, only those rows exist)
-hipError_t gather_samples_slab(hipStream_t s, const float* d_lum, GridSpec gs, int row0, int row1, double* d_out);
+hipError_t gather_samples_slab(hipStream_t s, const float* d_lum, GridSpec gs, int row0, int row1, double* d_out,
+                               const int* d_run_if = nullptr);  // d_run_if: as sink_hist_tiled's
 
 // K_AB rows, natural order: kab[i][s] = exp2(nsw*d2 + npw*dv^2), i in [pix0, pix0+M)
 hipError_t affinity(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples,
@@ -325,11 +326,19 @@ int sorted_expand_layers(GridSpec gs);
 hipError_t sorted_expand(hipStream_t s, GridSpec gs, int nrows, const SortedRows& sr, const double* d_g, size_t gstride, int nl,
                          const double* d_cvec, float* d_out, long long ostride, bool round8);
 hipError_t dist_table(hipStream_t s, int W, double hx, double* d_E);
+// d_lev (optional, nrows_local x W bytes): the level of EVERY pixel of this rank's rows, sample pixels included -- the
+// plane itself, it being integer valued in [0, 255]
 hipError_t sort_rows(hipStream_t s, const float* d_lum, GridSpec gs, int row0, int nrows_local, unsigned short* d_scol,
-                     uint2* d_desc, unsigned short* d_first);
+                     uint2* d_desc, unsigned short* d_first, unsigned char* d_lev = nullptr);
+// *d_flag |= 1 unless d_x[i] has the bits of (float)d_lev[i] for every i < n (d_x: first pixel of the rows d_lev holds);
+// the caller zeroes the flag.  (A -0.0f where the level is 0 counts as different.)
+hipError_t plane_matches_levels(hipStream_t s, const float* d_x, const unsigned char* d_lev, long long n, int* d_flag);
+// gather_samples_slab's values from the level plane of rows [row0, row0 + nrows_local): d_out[k] = the level of sample k
+hipError_t gather_sample_levels(hipStream_t s, const unsigned char* d_lev, GridSpec gs, int row0, int nrows_local, double* d_out);
 // the table columns of sr's level tiles only; the pixel loop in the form sr.mom / sr.rec say
 hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows, const SortedRows& sr, const double* d_g,
-                       double eps, double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec);
+                       double eps, double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec,
+                       const int* d_run_if = nullptr);
 bool sorted_moments_ok(GridSpec gs, double hx);
 // the XVEC pass for a group of planes in ONE walk over the sorted rows (sorted_planes.hip: k_sorted_reduce_planes): plane m
 // of the group is read at x[m] (virtual base of the full image) and its tables go to h[m], in sorted_pass's layout and with
@@ -347,8 +356,11 @@ hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows, const SortedR
 // the table pass (three kernels, Ep read once per pass); writes the full column sums to d_z.  d_ybuf (optional): y_i per
 // local pixel; mode XVEC (apply, reduce half): y_i = cvec_i * xvec_i
 size_t hist_tiled_workspace_elems(GridSpec gs, int nrows_local);
+// d_run_if (optional, sorted rows only): a device int; where it is 0 when the kernels start, they return at once and
+// d_ws, d_z stay as they were -- the caller has the result from elsewhere (apply_sample_space)
 hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const double* d_w, double eps, double* d_ybuf,
-                           double* d_ws, double* d_z, LaunchObserver* obs = nullptr, const float* d_xvec = nullptr);
+                           double* d_ws, double* d_z, LaunchObserver* obs = nullptr, const float* d_xvec = nullptr,
+                           const int* d_run_if = nullptr);
 // reduce half of the sample-space apply for 2 <= np <= sorted_planes_per_launch(v.gs) planes on the level-sorted rows
 // (v.sorted != null): one pixel kernel for the group, then the HH stage and the column sums plane by plane; d_x: np planes
 // (virtual full bases); d_ws: apply_reduce_planes_workspace_elems doubles; d_m: np vectors of stride v.ldp, each the bits
@@ -361,9 +373,11 @@ hipError_t apply_reduce_planes(hipStream_t s, const TableView& v, const float* c
 int apply_layers_per_launch(const TableView& v);
 hipError_t apply_hist_layers(hipStream_t s, const TableView& v, const double* d_wl, int ldw, int nl, double* d_ws, float* d_out,
                              long long ostride, LaunchObserver* obs, bool round8 = false);
+// d_differs (optional): a device int; where it is 0, d_m_same and d_xA_same stand in for d_m and d_xA
 hipError_t apply_small(hipStream_t s, int p, int K, int ldk, int L, int ldw, const double* d_m, const double* d_D,
                        const double* d_Vrows, const double* d_xA /* x at the p sample pixels */, const double* d_resp,
-                       double* d_t, double* d_Wp, double* d_YA);
+                       double* d_t, double* d_Wp, double* d_YA, const int* d_differs = nullptr, const double* d_m_same = nullptr,
+                       const double* d_xA_same = nullptr);
 hipError_t scatter_samples(hipStream_t s, int p, int L, const long long* d_loc, const double* d_YA, float* d_Y,
                            long long ystride, bool round8 = false);  // round8: clamp to [0, 255], round half to even, in fp64
 

@@ -64,6 +64,7 @@ struct nle_ctx {
     hipEvent_t copy_ev[2] = {nullptr, nullptr};
     int mode = 0;  // nle_ctx_set_mode: 0 auto, 1 materialised Phi, 2 Phi-free, 3 Phi-free without look-up tables
     bool slab_input = false;  // nle_ctx_set_slab_input: planes handed in hold this rank's rows only
+    bool train_reduce = true;  // nle_ctx_set_train_reduce: training leaves apply's reduce half for its own plane, apply may use it
     bool nystrom_bf16x3 = false;  // nle_ctx_set_nystrom_bf16x3: the fused Nystrom GEMM on the bf16 MFMA with split operands
     int patch_radius = 0;  // nle_ctx_set_patch_radius: patch (non-local-means) affinities of (2R + 1)^2 pixels (patch.hip)
     // nle_ctx_set_chroma: the a and b planes of 8-bit Lab (borrowed device pointers, full H x W plane) and the chroma
@@ -193,6 +194,12 @@ struct TableFilter {
     // the training plane (without sorted rows: copied; with them: rebuilt on demand)
     DevBuf<double> D, Vrows;
     DevBuf<float> slab;
+    // The reduce half of apply for the training plane itself, left by training (train_tables; single rank with sorted rows,
+    // with nle_ctx::train_reduce on): m_train = K^T (c o x) (P64 doubles) and xA_train = x at the samples (p doubles),
+    // the bits apply_sample_space computes for that plane, and `lev`, the plane in one byte per pixel (k_sort_rows), which
+    // apply compares its input with before it uses them.  m_train unset: apply computes its own.
+    DevBuf<double> m_train, xA_train;
+    DevBuf<unsigned char> lev;
 
     TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet& ss, double hx, double hy, int row0, int nrows);
     const float* plane_into(nle_ctx* ctx, DevBuf<float>& dst) const;

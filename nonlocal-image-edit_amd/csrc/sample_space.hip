@@ -160,7 +160,10 @@ nlep::TableFilter::TableFilter(nle_ctx* ctx, const float* d_lum, const SampleSet
     desc.alloc((size_t)nrows * nlek::kSortedThreads);
     E.alloc((size_t)gs.W + 1);
     PROFILED(ctx, NLE_K_SMALL, nlek::dist_table(ctx->stream, gs.W, hx, E.p));
-    PROFILED(ctx, NLE_K_SMALL, nlek::sort_rows(ctx->stream, d_lum, gs, row0, nrows, scol.p, desc.p, first.p));
+    // single rank: training will leave apply's reduce half for this plane (train_tables), which needs the plane kept in a
+    // form apply can compare its input with -- one byte per pixel, written by the sort
+    if (ctx->world == 1 && !ctx->comm && ctx->train_reduce) lev.alloc((size_t)nrows * gs.W);
+    PROFILED(ctx, NLE_K_SMALL, nlek::sort_rows(ctx->stream, d_lum, gs, row0, nrows, scol.p, desc.p, first.p, lev.p));
     HIP_OK(hipMemsetAsync(c.p, 0, c.n * sizeof(double), ctx->stream));  // sample pixels are never visited
     sorted = nlek::SortedRows{scol.p, desc.p, first.p, E.p, false, 0.0};
     sorted.rec = nlek::sorted_recurrence(gs, hx, &sorted.kappa) && !sw.sorted_table;  // (kappa is set either way)
@@ -224,9 +227,26 @@ void TrainPath::train_tables(const SolveKa& solve) {
     DevBuf<double> d_gpart, d_G(g_elems);
     auto enqueue_gram = [&] {
         d_gpart.alloc(nlek::ghist_workspace_elems(ss.gs, t->nrows));
-        static const int gmap[4] = {NLE_K_GRAM_ROWS, NLE_K_SMALL, NLE_K_GRAM_GEMM, NLE_K_SMALL};
-        ProfObserver obs(c, gmap);
-        HIP_OK(nlek::gram_hist(c->stream, view, d_gpart.p, d_G.p, &obs));
+        {
+            static const int gmap[4] = {NLE_K_GRAM_ROWS, NLE_K_SMALL, NLE_K_GRAM_GEMM, NLE_K_SMALL};
+            ProfObserver obs(c, gmap);
+            HIP_OK(nlek::gram_hist(c->stream, view, d_gpart.p, d_G.p, &obs));
+        }
+        // The reduce half of apply for the plane in hand, m = K^T (c o x): it needs the row scalings and the plane, nothing
+        // that comes after the Sinkhorn iterations, and `enhance` filters the plane it trained on.  Behind the Gram kernels
+        // the stream is idle while the host takes Wa apart, so it runs here, off the critical path -- apply_sample_space's
+        // own launches with its arguments, so the bits are the ones apply would compute (d_hws is free by now).
+        if (t->lev.p) {
+            t->m_train.alloc(t->P64);
+            t->xA_train.alloc(p);
+            {
+                static const int rmap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_REDUCE, NLE_K_REDUCE, NLE_K_REDUCE};
+                ProfObserver obs(c, rmap);
+                HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_hws.p,
+                                             t->m_train.p, &obs, d_lum));
+            }
+            PROFILED(c, NLE_K_SMALL, nlek::gather_sample_levels(c->stream, t->lev.p, ss.gs, t->row0, t->nrows, t->xA_train.p));
+        }
     };
     // what defines V = diag(c) K_AB^T D implicitly (K' <= 128: tables_apply) stays on the device: D and the exact rows of V
     // at the sample pixels, p x ldd row-major, zero padded -- the operands of k_apply_small and project64
@@ -452,21 +472,33 @@ void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L 
     DevBuf<double> d_ws(nlek::hist_tiled_workspace_elems(t.gs, t.nrows)), d_m(P64), d_resp((size_t)L * K), d_t(K),
         d_Wp((size_t)L * P64), d_YA((size_t)L * p);
     HIP_OK(hipMemcpyAsync(d_resp.p, h_g, (size_t)L * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // The plane training left its reduce half for (TableFilter::m_train)?  Decided by content, not by pointer, and on the
+    // device: one streaming pass over x against the kept level plane sets d_differs, the reduce kernels return at once
+    // where it stays 0, and k_apply_small then reads training's m and sample values -- no verdict travels to the host.
+    DevBuf<int> d_differs;
+    if (t.m_train.p && c->world == 1 && !c->comm && c->train_reduce) {
+        d_differs.alloc(1);
+        HIP_OK(hipMemsetAsync(d_differs.p, 0, sizeof(int), c->stream));
+        PROFILED(c, NLE_K_SMALL, nlek::plane_matches_levels(c->stream, d_x + (long long)t.row0 * t.gs.W, t.lev.p,
+                                                            (long long)t.nrows * t.gs.W, d_differs.p));
+    }
     {
         static const int rmap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_REDUCE, NLE_K_REDUCE, NLE_K_REDUCE};
         ProfObserver obs(c, rmap);
-        HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_ws.p, d_m.p, &obs, d_x));
+        HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_ws.p, d_m.p, &obs, d_x,
+                                     d_differs.p));
     }
     all_reduce(c, d_m.p, P64);
     // x at the p sample pixels: every rank's own rows, completed by the all-reduce when the planes are slabs
     DevBuf<double> d_xA(p);
     {
         const bool slabs = c->slab_input && c->world > 1;
-        PROFILED(c, NLE_K_SMALL, nlek::gather_samples_slab(c->stream, d_x, t.gs, slabs ? f->row0 : 0, slabs ? f->row1 : f->H, d_xA.p));
+        PROFILED(c, NLE_K_SMALL, nlek::gather_samples_slab(c->stream, d_x, t.gs, slabs ? f->row0 : 0, slabs ? f->row1 : f->H, d_xA.p,
+                                                           d_differs.p));
         if (slabs) all_reduce(c, d_xA.p, p);
     }
     PROFILED(c, NLE_K_SMALL, nlek::apply_small(c->stream, p, K, t.ldd, L, P64, d_m.p, t.D.p, t.Vrows.p, d_xA.p, d_resp.p,
-                                               d_t.p, d_Wp.p, d_YA.p));
+                                               d_t.p, d_Wp.p, d_YA.p, d_differs.p, t.m_train.p, t.xA_train.p));
     static const int emap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_EXPAND, NLE_K_REDUCE, NLE_K_REDUCE};
     int lb = std::min(L, nlek::apply_layers_per_launch(view));
     if (group > 0) lb = std::min(lb, group);

@@ -90,10 +90,11 @@ hipError_t dist_table(hipStream_t s, int W, double hx, double* d_E) {
 //                j, j + m, j + 2m, ... of a STABLE counting sort, so that the summation order of every later pass is a
 //                function of the image alone;
 //   desc[kT]     one chunk per pass thread (see above);
-//   first[258]   first[x] = first chunk of level x (x = 0..256), first[257] = number of tree steps.
+//   first[258]   first[x] = first chunk of level x (x = 0..256), first[257] = number of tree steps;
+//   lev[W]       (where asked for) the level of every pixel of the row, samples included: the plane in one byte per pixel.
 __global__ __launch_bounds__(kSortThreads) void k_sort_rows(const float* __restrict__ lum, GridSpec gs, int row0,
                                                             unsigned short* __restrict__ scol, uint2* __restrict__ desc,
-                                                            unsigned short* __restrict__ first) {
+                                                            unsigned short* __restrict__ first, unsigned char* __restrict__ lev) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int W = gs.W;
     unsigned short* srow = reinterpret_cast<unsigned short*>(smem_raw);  // [kT * CHP + 4] the row's slots
@@ -112,8 +113,12 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_rows(const float* __restr
     tot[tid] = 0;
     run[tid] = 0;
     __syncthreads();
-    for (int c = tid; c < W; c += kSortThreads)
-        if (!is_sample(c)) atomicAdd(&tot[(int)lrow_p[c]], 1);  // integer counts: order does not matter
+    unsigned char* lev_row = lev ? lev + (size_t)lrow * W : nullptr;
+    for (int c = tid; c < W; c += kSortThreads) {
+        const int x = (int)lrow_p[c];
+        if (lev_row) lev_row[c] = (unsigned char)x;
+        if (!is_sample(c)) atomicAdd(&tot[x], 1);  // integer counts: order does not matter
+    }
     __syncthreads();
     // exclusive prefix over the 256 levels (Hillis-Steele on `off`)
     const int mine = tot[tid];
@@ -218,10 +223,62 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_rows(const float* __restr
 size_t sorted_scol_elems(int W, int nrows_local) { return (size_t)std::max(nrows_local, 0) * sorted_row_pitch(W) + 16; }
 
 hipError_t sort_rows(hipStream_t s, const float* d_lum, GridSpec gs, int row0, int nrows_local, unsigned short* d_scol,
-                     uint2* d_desc, unsigned short* d_first) {
+                     uint2* d_desc, unsigned short* d_first, unsigned char* d_lev) {
     if (gs.W > sorted_max_width() || nrows_local <= 0) return nrows_local <= 0 ? hipSuccess : hipErrorInvalidValue;
     hipLaunchKernelGGL(k_sort_rows, dim3((unsigned)nrows_local), dim3(kSortThreads),
-                       sorted_row_pitch(gs.W) * sizeof(unsigned short), s, d_lum, gs, row0, d_scol, d_desc, d_first);
+                       sorted_row_pitch(gs.W) * sizeof(unsigned short), s, d_lum, gs, row0, d_scol, d_desc, d_first, d_lev);
+    return hipGetLastError();
+}
+
+// Is x the plane the rows were sorted from?  One streaming pass over x (4 bytes per pixel) and the level plane of
+// k_sort_rows (1 byte): x[i] must have the bits of (float)lev[i] -- the plane is integer valued in [0, 255], so the level
+// plane IS the plane.  Compared as bits: NaN never matches, -0.0f does not match level 0 (the caller then takes the path
+// that reads x, which is always right).  Four pixels per thread and load where x is 16-byte aligned, a scalar loop for the
+// rest; a wave that saw a difference sets the flag with one atomicOr.
+__global__ __launch_bounds__(256) void k_plane_matches_levels(const float* __restrict__ x, const unsigned char* __restrict__ lev,
+                                                              long long n, int* __restrict__ flag) {
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
+    bool bad = false;
+    auto differs = [](float v, unsigned char l) { return __float_as_uint(v) != __float_as_uint((float)l); };
+    long long n4 = 0;
+    if ((reinterpret_cast<unsigned long long>(x) & 15ull) == 0 && (reinterpret_cast<unsigned long long>(lev) & 3ull) == 0) {
+        n4 = n >> 2;
+        const float4* x4 = reinterpret_cast<const float4*>(x);
+        const uchar4* l4 = reinterpret_cast<const uchar4*>(lev);
+        for (long long i = tid; i < n4; i += nth) {
+            const float4 v = x4[i];
+            const uchar4 l = l4[i];
+            bad |= differs(v.x, l.x) | differs(v.y, l.y) | differs(v.z, l.z) | differs(v.w, l.w);
+        }
+    }
+    for (long long i = 4 * n4 + tid; i < n; i += nth) bad |= differs(x[i], lev[i]);
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+}
+
+hipError_t plane_matches_levels(hipStream_t s, const float* d_x, const unsigned char* d_lev, long long n, int* d_flag) {
+    if (n <= 0) return hipSuccess;
+    int ncu = 256, dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const long long want = (n / 4 + 255) / 256 + 1;  // one block of four per thread, or the 8 workgroups per CU that fill the chip
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(want, (long long)ncu * 8));
+    hipLaunchKernelGGL(k_plane_matches_levels, dim3(grid), dim3(256), 0, s, d_x, d_lev, n, d_flag);
+    return hipGetLastError();
+}
+
+// x at the sample pixels of rows [row0, row0 + nrows), from the level plane (k_gather_samples_slab's values for the plane
+// the rows were sorted from; 0 for the samples of other rows)
+__global__ void k_gather_sample_levels(const unsigned char* __restrict__ lev, GridSpec gs, int row0, int nrows,
+                                       double* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= gs.p()) return;
+    const int ri = k / gs.nSelCols, ci = k % gs.nSelCols;
+    const int r = gs.rowOff + ri * gs.rowStep - row0, c = gs.colOff + ci * gs.colStep;
+    out[k] = (r >= 0 && r < nrows) ? (double)lev[(size_t)r * gs.W + c] : 0.0;
+}
+
+hipError_t gather_sample_levels(hipStream_t s, const unsigned char* d_lev, GridSpec gs, int row0, int nrows_local, double* d_out) {
+    const int p = gs.p();
+    hipLaunchKernelGGL(k_gather_sample_levels, dim3((p + 255) / 256), dim3(256), 0, s, d_lev, gs, row0, nrows_local, d_out);
     return hipGetLastError();
 }
 
@@ -300,7 +357,9 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
                                                     GridSpec gs, int row0, int nrows, const double* __restrict__ Etab,
                                                     const double* __restrict__ g, double eps, double* __restrict__ ybuf,
                                                     double* __restrict__ hout, const double* __restrict__ cvec,
-                                                    const float* __restrict__ xvec, double kappa, int lev_t0, int lev_nt) {
+                                                    const float* __restrict__ xvec, double kappa, int lev_t0, int lev_nt,
+                                                    const int* __restrict__ run_if) {
+    if (run_if != nullptr && *run_if == 0) return;  // (kernels.h: sink_hist_tiled)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int n = kLevels * NC;
     constexpr int SL = NC < 11 ? NC : 11;  // sums combined per tree (slices of the nC sums when nC > 11)
@@ -621,7 +680,7 @@ bool sorted_moments_ok(GridSpec gs, double hx) {
 }
 
 hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows_local, const SortedRows& sr, const double* d_g,
-                       double eps, double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec) {
+                       double eps, double* d_ybuf, double* d_h, const double* d_cvec, const float* d_xvec, const int* d_run_if) {
     const int nC = gs.nSelCols, lev_t0 = sr.lev_t0, lev_nt = sr.lev_nt;
     if (!tables_apply(gs) || gs.W > sorted_max_width() || lev_t0 < 0 || lev_nt < 1 || lev_t0 + lev_nt > kLevels / 16)
         return hipErrorInvalidValue;
@@ -637,7 +696,7 @@ hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows
         }                                                                                                                 \
         hipLaunchKernelGGL((k_sorted_pass<NCV, CFV>), dim3((unsigned)grid), dim3(kT), shm, s, mode, sr.scol, sr.desc,      \
                            sr.first, gs, row0, nrows_local, sr.E, d_g, eps, d_ybuf, d_h, d_cvec, d_xvec, sr.kappa, lev_t0, \
-                           lev_nt);                                                                                       \
+                           lev_nt, d_run_if);                                                                             \
     }
 #define NLE_SP(NCV)                                                                                                       \
     case NCV:                                                                                                             \
@@ -693,74 +752,169 @@ __global__ __launch_bounds__(kT) void k_sorted_expand(const unsigned short* __re
     const int cb0 = gs.colOff, cs = gs.colStep;
     const unsigned sEa = lds_addr(sE);
     const size_t pitch = sorted_row_pitch(W);
-    __syncthreads();
-    for (int lrow = blockIdx.x; lrow < nrows; lrow += gridDim.x) {
-        const uint2 dsc = desc[(size_t)lrow * kT + tid];
-        const int len = dsc_len(dsc), x = dsc_level(dsc);
-        const uint2* slot = reinterpret_cast<const uint2*>(scol + (size_t)lrow * pitch + (size_t)tid * dsc_chp(dsc));
-        uint2 idx[kMaxBlocks];
+    double gv[kExpL][NC];
+    auto load_idx = [&](uint2 (&dst)[kMaxBlocks], const int row, const uint2 d) {
+        const uint2* slot = reinterpret_cast<const uint2*>(scol + (size_t)row * pitch + (size_t)tid * dsc_chp(d));
+        const int ln = dsc_len(d);
 #pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) {
+        for (int b = 0; b < kMaxBlocks; ++b) {  // blocks past the chunk: column 0 (the wave may walk further than this lane)
             uint2 v = make_uint2(0u, 0u);
-            if (4 * b < len) v = slot[b];
-            idx[b] = v;
+            if (4 * b < ln) v = slot[b];
+            dst[b] = v;
         }
-        double gv[kExpL][NC];
+    };
+    auto load_gv = [&](const int row, const int x) {
 #pragma unroll
         for (int l = 0; l < kExpL; ++l)
 #pragma unroll
-            for (int b = 0; b < NC; ++b) gv[l][b] = (l < nl) ? g[(size_t)l * gstride + (size_t)lrow * n + b * kLevels + x] : 0.0;
-        const double* cv_row = cvec + (size_t)lrow * W;
-        int wlen = len;
+            for (int b = 0; b < NC; ++b) gv[l][b] = (l < nl) ? g[(size_t)l * gstride + (size_t)row * n + b * kLevels + x] : 0.0;
+    };
+    auto pixel = [&](const unsigned c8, const double cv, const bool on) {
+        const unsigned c = c8 >> 3;
+        double e[NC];
+        column_factors<NC, REC>(sEa, c8, cb0, cs, kappa, [&](const int b, const double ev) { e[b] = ev; });
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wlen = max(wlen, __shfl_xor(wlen, off));
-        wlen = __builtin_amdgcn_readfirstlane(wlen);
-        auto pixel = [&](const unsigned c8, const bool on) {
-            const unsigned c = c8 >> 3;
-            const double cv = cv_row[c];
-            double e[NC];
-            column_factors<NC, REC>(sEa, c8, cb0, cs, kappa, [&](const int b, const double ev) { e[b] = ev; });
+        for (int l = 0; l < kExpL; ++l) {
+            double s0 = 0.0, s1 = 0.0;
 #pragma unroll
-            for (int l = 0; l < kExpL; ++l) {
-                double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-                for (int b = 0; b < NC; ++b) {
-                    if (b & 1) s1 += e[b] * gv[l][b];
-                    else s0 += e[b] * gv[l][b];
-                }
-                if (on && l < nl) {
-                    double v = cv * (s0 + s1);
-                    // round8: cv::max(0) / cv::min(255) / convertTo(CV_8U) (src/filter.cpp:434-436) on the fp64 value --
-                    // the plane then holds the 8-bit levels exactly, no fp32 rounding in front of the round-half-even
-                    if (round8) v = rint(fmin(255.0, fmax(0.0, v)));
-                    sOut[l * W + c] = (float)v;
-                }
+            for (int b = 0; b < NC; ++b) {
+                if (b & 1) s1 += e[b] * gv[l][b];
+                else s0 += e[b] * gv[l][b];
             }
-        };
-#pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) {
-            if (4 * b >= wlen) break;
-            pixel(idx[b].x & 0xffffu, 4 * b < len);
-            NLE_PIXEL_FENCE();
-            if (4 * b + 1 < wlen) {
-                pixel(idx[b].x >> 16, 4 * b + 1 < len);
-                NLE_PIXEL_FENCE();
-            }
-            if (4 * b + 2 < wlen) {
-                pixel(idx[b].y & 0xffffu, 4 * b + 2 < len);
-                NLE_PIXEL_FENCE();
-            }
-            if (4 * b + 3 < wlen) {
-                pixel(idx[b].y >> 16, 4 * b + 3 < len);
-                NLE_PIXEL_FENCE();
+            if (on && l < nl) {
+                double v = cv * (s0 + s1);
+                // round8: cv::max(0) / cv::min(255) / convertTo(CV_8U) (src/filter.cpp:434-436) on the fp64 value --
+                // the plane then holds the 8-bit levels exactly, no fp32 rounding in front of the round-half-even
+                if (round8) v = rint(fmin(255.0, fmax(0.0, v)));
+                sOut[l * W + c] = (float)v;
             }
         }
-        __syncthreads();  // the row's outputs are in sOut
+    };
+    auto store_row = [&](const int lrow) {  // sOut leaves coalesced
         for (int l = 0; l < nl; ++l) {
             float* orow = out + (size_t)l * ostride + (size_t)lrow * W;
             for (int c = tid; c < W; c += kT) orow[c] = sOut[l * W + c];
         }
-        __syncthreads();  // before the next row writes sOut
+    };
+    auto wave_max = [](int v) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+        return __builtin_amdgcn_readfirstlane(v);
+    };
+    // Up to 60 table values per thread the registers leave room for a software pipeline over the workgroup's rows (below);
+    // beyond (31 .. 36 columns) a row is taken start to end: descriptor, then indices and table values, then the pixels
+    // with one c value each, then the stores.
+    constexpr bool PIPE = kExpL * NC <= 60;
+    __syncthreads();  // sE visible
+    if constexpr (!PIPE) {
+        for (int lrow = blockIdx.x; lrow < nrows; lrow += gridDim.x) {
+            const uint2 dsc = desc[(size_t)lrow * kT + tid];
+            const int len = dsc_len(dsc);
+            uint2 idx[kMaxBlocks];
+            load_idx(idx, lrow, dsc);
+            load_gv(lrow, dsc_level(dsc));
+            const double* cv_row = cvec + (size_t)lrow * W;
+            const int wlen = wave_max(len);
+#pragma unroll
+            for (int b = 0; b < kMaxBlocks; ++b) {
+                if (4 * b >= wlen) break;
+                const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (4 * b + k < wlen) {
+                        pixel(cs4[k], cv_row[cs4[k] >> 3], 4 * b + k < len);
+                        NLE_PIXEL_FENCE();
+                    }
+                }
+            }
+            __syncthreads();  // the row's outputs are in sOut
+            store_row(lrow);
+            __syncthreads();  // before the next row writes sOut
+        }
+    } else {
+        // k_sorted_pass's pipeline: the chunk descriptor is requested two rows ahead and the indices one row ahead, both
+        // under the pixel loop; the nl NC table values of the next row as soon as this thread has walked its chunk (their
+        // registers are free from there: gv[4][10] twice over does not fit), with the next row's first c values -- in
+        // flight while the other waves finish, and taken in before the row's stores, so that the next row's first pixel
+        // does not wait for those to be acknowledged.  Within a row the c values come a block of four ahead of their use,
+        // not one dependent gather per pixel.
+        // the c values of a block of four pixels (every index of a slot is a column of the row: the padding is column 0)
+        auto load_cv = [&](double (&dst)[4], const double* __restrict__ row, const uint2 v) {
+            dst[0] = row[(v.x & 0xffffu) >> 3];
+            dst[1] = row[v.x >> 19];
+            dst[2] = row[(v.y & 0xffffu) >> 3];
+            dst[3] = row[v.y >> 19];
+        };
+        const int G = (int)gridDim.x;  // <= nrows
+        int lrow = blockIdx.x, nrow = lrow + G;
+        uint2 dsc = desc[(size_t)lrow * kT + tid];
+        uint2 dsc_n = dsc;
+        if (nrow < nrows) dsc_n = desc[(size_t)nrow * kT + tid];
+        uint2 idx[kMaxBlocks];
+        load_idx(idx, lrow, dsc);
+        load_gv(lrow, dsc_level(dsc));
+        double cvb[4];
+        load_cv(cvb, cvec + (size_t)lrow * W, idx[0]);
+        for (;;) {
+            const bool has_next = nrow < nrows;
+            const int nnrow = nrow + G;
+            const int len = dsc_len(dsc);
+            const double* cv_row = cvec + (size_t)lrow * W;
+            const int wlen = wave_max(len);
+            // requested before the pixel loop, in flight under it: the second block's c values first (loads return in
+            // order: the loop's first wait is for these), then the descriptor of the row after next and the next row's indices
+            double cvn[4] = {0.0, 0.0, 0.0, 0.0};
+            if (4 < wlen) load_cv(cvn, cv_row, idx[1]);
+            uint2 dsc_nn = dsc_n;
+            uint2 idx_n[kMaxBlocks];
+            if (has_next) {
+                if (nnrow < nrows) dsc_nn = desc[(size_t)nnrow * kT + tid];
+                load_idx(idx_n, nrow, dsc_n);
+            }
+#pragma unroll
+            for (int b = 0; b < kMaxBlocks; ++b) {
+                if (4 * b >= wlen) break;
+                // the next block's c values, under this block's four pixels (the second block's: above)
+                if (b >= 1 && b + 1 < kMaxBlocks && 4 * (b + 1) < wlen) load_cv(cvn, cv_row, idx[b + 1 < kMaxBlocks ? b + 1 : b]);
+                NLE_PIXEL_FENCE();
+                const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (4 * b + k < wlen) {
+                        pixel(cs4[k], cvb[k], 4 * b + k < len);
+                        NLE_PIXEL_FENCE();
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) cvb[k] = cvn[k];
+            }
+            // this thread's table values have had their last use: the next row's, and its first c values
+            if (has_next) {
+                load_gv(nrow, dsc_level(dsc_n));
+                load_cv(cvb, cvec + (size_t)nrow * W, idx_n[0]);
+            }
+            __syncthreads();  // the row's outputs are in sOut
+            // Were these loads still pending behind the stores below, the next row's first pixel would wait for the stores
+            // to be acknowledged.  Take them in here (all lanes: a divergent use would leave a load pending for the others).
+            asm volatile("" ::"v"(dsc_nn.x), "v"(dsc_nn.y));
+#pragma unroll
+            for (int b = 0; b < kMaxBlocks; ++b) asm volatile("" ::"v"(idx_n[b].x), "v"(idx_n[b].y));
+#pragma unroll
+            for (int l = 0; l < kExpL; ++l)
+#pragma unroll
+                for (int b = 0; b < NC; ++b) asm volatile("" ::"v"(gv[l][b]));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(cvb[k]));
+            store_row(lrow);
+            __syncthreads();  // before the next row writes sOut
+            if (!has_next) break;
+            lrow = nrow;
+            nrow = nnrow;
+            dsc = dsc_n;
+            dsc_n = dsc_nn;
+#pragma unroll
+            for (int b = 0; b < kMaxBlocks; ++b) idx[b] = idx_n[b];
+        }
     }
 }
 

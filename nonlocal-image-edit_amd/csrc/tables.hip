@@ -356,7 +356,9 @@ __global__ __launch_bounds__(256) void k_apply_small(int p, int K, int ldk, int 
                                                      const double* __restrict__ Dm, const double* __restrict__ Vrows,
                                                      const double* __restrict__ xA, const double* __restrict__ resp,
                                                      double* __restrict__ t_out, double* __restrict__ Wp,
-                                                     double* __restrict__ YA) {
+                                                     double* __restrict__ YA, const int* __restrict__ differs,
+                                                     const double* __restrict__ m_same, const double* __restrict__ xA_same) {
+    if (differs != nullptr && *differs == 0) m = m_same, xA = xA_same;  // the plane training left its reduce half for
     // one workgroup per layer l = blockIdx.x; each recomputes t (K values, p terms each: cheaper than a second launch)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     double* sm = reinterpret_cast<double*>(smem_raw);  // [p]
@@ -424,7 +426,9 @@ __global__ void k_scatter_samples(int p, int L, const long long* __restrict__ lo
 // < 1 MB of partials, and one launch goes away.
 __global__ __launch_bounds__(256) void k_hist_hh(int nC, int nR, int nrows, int slab_rows, int lev_t0, int lev_nt,
                                                  const double* __restrict__ er, const double* __restrict__ h,
-                                                 const double* __restrict__ Ep, int p, int ldp, double* __restrict__ zpart) {
+                                                 const double* __restrict__ Ep, int p, int ldp, double* __restrict__ zpart,
+                                                 const int* __restrict__ run_if) {
+    if (run_if != nullptr && *run_if == 0) return;
     // the slab's er rows, staged once for the four waves (they were re-read from global memory inside the MFMA loop: a
     // second dependent latency per 32 rows), and all of a lane's h loads of a 64-row half slab in flight together
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -487,7 +491,8 @@ __global__ __launch_bounds__(256) void k_hist_hh(int nC, int nR, int nrows, int 
 // z[s] = sum over the nparts (slab, level tile) partial rows, in a fixed order; columns s >= p come out as 0.
 // 8 columns x 32 row groups per workgroup: ldp / 8 workgroups, each thread adds nparts / 32 values.
 __global__ __launch_bounds__(256) void k_z_reduce(const double* __restrict__ zpart, int nparts, int p, int ldp,
-                                                  double* __restrict__ z) {
+                                                  double* __restrict__ z, const int* __restrict__ run_if) {
+    if (run_if != nullptr && *run_if == 0) return;
     __shared__ double sm[32][8];
     const int c = threadIdx.x & 7, g = threadIdx.x >> 3, col = blockIdx.x * 8 + c;
     double s = 0.0;
@@ -522,7 +527,8 @@ size_t hist_tiled_workspace_elems(GridSpec gs, int nrows_local) {
 }
 
 // the HH stage and the column sums behind a pixel kernel's tables d_h: d_z = the p column sums (ldp doubles)
-static hipError_t launch_hist_hh_z(hipStream_t s, const TableView& v, const double* d_h, double* d_HH, double* d_z) {
+static hipError_t launch_hist_hh_z(hipStream_t s, const TableView& v, const double* d_h, double* d_HH, double* d_z,
+                                   const int* d_run_if = nullptr) {
     const GridSpec gs = v.gs;
     const int nC = gs.nSelCols, nR = gs.nSelRows, p = v.p, ldp = v.ldp, nrows_local = v.nrows;
     const int slab_rows = hist_slab_rows(gs, nrows_local), nslabs = (nrows_local + slab_rows - 1) / slab_rows;
@@ -534,15 +540,15 @@ static hipError_t launch_hist_hh_z(hipStream_t s, const TableView& v, const doub
         if (ea != hipSuccess) return ea;
     }
     hipLaunchKernelGGL(k_hist_hh, dim3((unsigned)((nC * lev_nt + 3) / 4), (unsigned)nslabs), dim3(256), shm_hh, s, nC, nR,
-                       nrows_local, slab_rows, lev_t0, lev_nt, v.er, d_h, v.Ep, p, ldp, d_HH);
-    hipLaunchKernelGGL(k_z_reduce, dim3((unsigned)((ldp + 7) / 8)), dim3(256), 0, s, d_HH, nslabs * lev_nt, p, ldp, d_z);
+                       nrows_local, slab_rows, lev_t0, lev_nt, v.er, d_h, v.Ep, p, ldp, d_HH, d_run_if);
+    hipLaunchKernelGGL(k_z_reduce, dim3((unsigned)((ldp + 7) / 8)), dim3(256), 0, s, d_HH, nslabs * lev_nt, p, ldp, d_z, d_run_if);
     return hipGetLastError();
 }
 
 // one Sinkhorn half-iteration, tiled form; d_ws: hist_tiled_workspace_elems doubles; d_z: ldp doubles
 hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const double* d_w, double eps, double* d_ybuf,
-                           double* d_ws, double* d_z, LaunchObserver* obs, const float* d_xvec) {
-    if (!tables_apply(v.gs)) return hipErrorInvalidValue;
+                           double* d_ws, double* d_z, LaunchObserver* obs, const float* d_xvec, const int* d_run_if) {
+    if (!tables_apply(v.gs) || (d_run_if != nullptr && v.sorted == nullptr)) return hipErrorInvalidValue;
     const GridSpec gs = v.gs;
     const int nC = gs.nSelCols, p = v.p, row0 = v.row0, nrows_local = v.nrows;
     const SortedRows* sorted = v.sorted;
@@ -566,7 +572,7 @@ hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const do
     }
     if (sorted != nullptr) {
         Scope sc(obs, SUB_HIST_PIX);
-        hipError_t ep = sorted_pass(s, mode, gs, row0, nrows_local, *sorted, d_g, eps, d_ybuf, d_h, d_cvec, d_xvec);
+        hipError_t ep = sorted_pass(s, mode, gs, row0, nrows_local, *sorted, d_g, eps, d_ybuf, d_h, d_cvec, d_xvec, d_run_if);
         if (ep != hipSuccess) return ep;
     } else {
         Scope sc(obs, SUB_HIST_PIX);
@@ -598,7 +604,7 @@ hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const do
 #undef NLE_HP
     }
     Scope sc(obs, SUB_HIST_HH);
-    return launch_hist_hh_z(s, v, d_h, d_HH, d_z);
+    return launch_hist_hh_z(s, v, d_h, d_HH, d_z, d_run_if);
 }
 
 size_t apply_reduce_planes_workspace_elems(GridSpec gs, int nrows_local, int np) {
@@ -684,10 +690,10 @@ hipError_t apply_hist_layers(hipStream_t s, const TableView& v, const double* d_
 
 hipError_t apply_small(hipStream_t s, int p, int K, int ldk, int L, int ldw, const double* d_m, const double* d_D,
                        const double* d_Vrows, const double* d_xA, const double* d_resp, double* d_t, double* d_Wp,
-                       double* d_YA) {
+                       double* d_YA, const int* d_differs, const double* d_m_same, const double* d_xA_same) {
     const size_t shm = (size_t)(2 * p + K + 256) * sizeof(double);
     hipLaunchKernelGGL(k_apply_small, dim3((unsigned)L), dim3(256), shm, s, p, K, ldk, L, ldw, d_m, d_D, d_Vrows, d_xA,
-                       d_resp, d_t, d_Wp, d_YA);
+                       d_resp, d_t, d_Wp, d_YA, d_differs, d_m_same, d_xA_same);
     return hipGetLastError();
 }
 
