@@ -166,15 +166,47 @@ int nle_filter_chroma(const nle_filter* f, double* hc);
  * set (which then apply to the affinities only).  Farthest applies to nle_train* and nle_compute_kernel64, in NLE_MODE_AUTO (which takes NLE_MODE_MATERIALISED_F64,
  * or NLE_MODE_STREAMED_F64 by the memory rule), NLE_MODE_MATERIALISED_F64 and NLE_MODE_STREAMED_F64; the other modes, slab
  * input at world > 1, nle_compute_kernel and nle_nystrom return NLE_ERR_INVALID.  At world > 1 (full-plane input) rank 0
- * selects and the set reaches the other ranks through the fp64 all-reduce. */
+ * selects and the set reaches the other ranks through the fp64 all-reduce.
+ *   NLE_SAMPLER_RESIDUAL  residual-greedy selection: Cholesky with diagonal pivoting on the N x N affinity, same count p as
+ *     the grid would take, p <= 2048.  Every sample is the pixel the samples so far explain worst (the largest Nystrom
+ *     residual r_i = 1 - k_i^T K_A^-1 k_i of nle_nystrom_residual), every pivot is that residual:
+ *       K(i, j) = exp(-(1/hx^2) (double)(dr^2 + dc^2) - (1/hy^2) dy^2)   (dr dc integer, dy = (double)y_i - (double)y_j,
+ *                 single luminance values, libm exp, every operation rounded on its own: no fma)
+ *       d_i = 1 for all i;  s_0 = pixel (H/2, W/2)
+ *       round k:  l_k[i] = (K(i, s_k) - sum_{j<k} l_j[i] l_j[s_k]) / sqrt(d_{s_k})   (j ascending, one accumulator, no fma)
+ *                 d_i -= l_k[i]^2
+ *                 s_{k+1} = argmax over the pixels not chosen of d_i, ties to the smallest row-major index
+ *     while that maximum is >= NLE_EPS (a smaller pivot would put an eigenvalue below the train's own cut into K_A).  From
+ *     the first round whose maximum is below NLE_EPS on, every remaining sample is NLE_SAMPLER_FARTHEST's step: with m_i the
+ *     smallest D(i, s) over ALL samples chosen so far (-1 for a chosen pixel; kept from round 0), the next sample is argmax
+ *     m, ties to the smallest index; once fallen back the rule stays there (no further columns, d is left as it is).  The
+ *     set is used ascending.  Like farthest it keeps this single-value K with a patch radius or chroma planes set, runs
+ *     where farthest runs and is refused where farthest is; NLE_MODE_EXACT_F64 refuses both.  The factor (N rounded up to
+ *     even, times p, doubles: nle_residual_sampler_bytes) is held in device memory: a selection that does not fit returns
+ *     NLE_ERR_INVALID with the bytes needed, before anything runs.
+ * The value 2 is unused (and refused). */
 #define NLE_SAMPLER_GRID 0
 #define NLE_SAMPLER_FARTHEST 1
+#define NLE_SAMPLER_RESIDUAL 3
 int nle_ctx_set_sampler(nle_ctx* ctx, int sampler);
 /* The sample set the ctx's sampler takes on the FULL H x W plane d_lum (fp32; may be NULL for the grid): *p samples, their
  * row-major indices ascending in h_idx (room for nle_sample_grid's n_sel_rows * n_sel_cols; may be NULL to learn *p).  A
- * collective at world > 1 under NLE_SAMPLER_FARTHEST. */
+ * collective at world > 1 under NLE_SAMPLER_FARTHEST and NLE_SAMPLER_RESIDUAL. */
 int nle_sample_pixels(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
                       double hy, long long* h_idx, int* p);
+/* Device bytes NLE_SAMPLER_RESIDUAL's factor takes on an H x W plane with this sample grid: ((H W + 1) & ~1) * p * 8, p the
+ * grid's sample count; -1 for arguments nle_sample_grid refuses.  Host only, no ctx. */
+long long nle_residual_sampler_bytes(int H, int W, int n_row_samples, int n_col_samples);
+/* NLE_SAMPLER_RESIDUAL's selection with its order and pivots (NLE_ERR_INVALID under the other samplers, and at world > 1
+ * before any collective).  h_order (p): the samples in the order chosen.  h_pivot[k]: d of s_k when it was chosen (1 for
+ * k = 0) for k < *n_residual; for later k the farthest-point m of s_k when it was chosen.  *n_residual: how many samples the
+ * residual rule chose, s_0 included.  h_stats (3, may be NULL): {the largest d over the pixels not chosen (0 if there is
+ * none), its first index (-1 if none), sum_i max(d_i, 0)} after the last residual round, folded from per-workgroup
+ * partials in a fixed order.  With *n_residual == *p these are max r and the trace-norm error sum r of nle_nystrom_residual
+ * for the set returned; after a fallback they are upper bounds of them (more samples only lower r).  Two calls give the
+ * same bits. */
+int nle_sample_pixels_order(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
+                            double hy, long long* h_order, double* h_pivot, int* p, int* n_residual, double* h_stats);
 /* The Nystrom-extension GEMM Phi = K_AB^T (V_A Lambda^-1) (src/filter.cpp:275) of NLE_MODE_MATERIALISED and of nle_nystrom on
  * the bf16 matrix cores with SPLIT operands (each fp32 value as three bf16, six products, fp32 accumulate: fp32 accuracy at
  * ~2.7x the exact-fp32 MFMA's rate; plain bf16 operands miss the parity bar).  Off by default. */

@@ -232,6 +232,7 @@ public:
     Vec eigvals() const;                 // m_eigvals
     Mat eigvecs() const;                 // m_eigvecs, downloaded (N x K')
     void timings(double ms[6]) const;    // nle_filter_timings
+    std::vector<long long> samplePixels() const;  // nle_filter_sample_pixels: the set trained on, row-major, ascending
     // nle_filter_diag: {formulation, p, rank Ka, rank Wa, rank Q, K', chol(Ka), chol(Wa)}
     void diag(int info[8]) const;
     bool verbose = true;                 // the reference's stdout stage banners (:483-498,506)
@@ -239,7 +240,8 @@ public:
     // trainForDenoise / trainFilter (nle_ctx_set_patch_radius; new here, 0 = the reference's single-value affinity)
     int patchRadius = 0;
     // sample selection for trainForEnhancement / trainForDenoise / trainFilter (nle_ctx_set_sampler; new here,
-    // NLE_SAMPLER_GRID = the reference's grid, NLE_SAMPLER_FARTHEST = farthest-point selection)
+    // NLE_SAMPLER_GRID = the reference's grid, NLE_SAMPLER_FARTHEST = farthest-point selection, NLE_SAMPLER_RESIDUAL (3) =
+    // residual-greedy selection: pivoted Cholesky on the affinity)
     int sampler = 0;
     // the exact (Nystrom-free) filter for trainForEnhancement / trainForDenoise / trainFilter (NLE_MODE_EXACT_F64 around
     // the train; new here): one device, at most NLE_EXACT_MAX_PIXELS pixels, patchRadius 0 and the grid sampler

@@ -36,6 +36,7 @@ MODE_AUTO, MODE_MATERIALISED, MODE_PHI_FREE, MODE_PHI_FREE_EXP, MODE_MATERIALISE
 MODE_EXACT_F64 = _abi.NLE_MODE_EXACT_F64  # the exact (Nystrom-free) filter, opt-in
 EXACT_MAX_PIXELS = _abi.NLE_EXACT_MAX_PIXELS
 SAMPLER_GRID, SAMPLER_FARTHEST = _abi.NLE_SAMPLER_GRID, _abi.NLE_SAMPLER_FARTHEST
+SAMPLER_RESIDUAL = _abi.NLE_SAMPLER_RESIDUAL
 # region edits: the bounds and the output kinds of nle_region_combine / nle_apply_regions
 REGION_MAX, REGION_LAYERS_MAX = _abi.NLE_REGION_MAX, _abi.NLE_REGION_LAYERS_MAX
 REGION_OUT_F32, REGION_OUT_ROUNDED8, REGION_OUT_U8 = (_abi.NLE_REGION_OUT_F32, _abi.NLE_REGION_OUT_ROUNDED8,
@@ -131,6 +132,12 @@ def sample_grid(H, W, n_row_samples, n_col_samples):
         raise NLEError(st, "Number of samples per row and col must be <= that of image.")
     keys = ("row_step", "row_off", "n_sel_rows", "col_step", "col_off", "n_sel_cols")
     return dict(zip(keys, (o.value for o in out)))
+
+
+def residual_sampler_bytes(H, W, n_row_samples, n_col_samples):
+    """device bytes SAMPLER_RESIDUAL's factor takes on an H x W plane with this sample grid (nle_residual_sampler_bytes);
+    -1 for a grid sample_grid refuses"""
+    return int(lib().nle_residual_sampler_bytes(int(H), int(W), int(n_row_samples), int(n_col_samples)))
 
 
 def slab_rows(H, rank, world):
@@ -323,8 +330,9 @@ class Context:
         self._chroma = (ta, tb)
 
     def set_sampler(self, sampler: int):
-        """sample selection: SAMPLER_GRID (0, default, the reference's grid) or SAMPLER_FARTHEST (1, farthest-point
-        selection in the affinity's metric; nle_ctx_set_sampler)"""
+        """sample selection: SAMPLER_GRID (0, default, the reference's grid), SAMPLER_FARTHEST (1, farthest-point
+        selection in the affinity's metric) or SAMPLER_RESIDUAL (3, residual-greedy: pivoted Cholesky on the affinity;
+        nle_ctx_set_sampler)"""
         _check(lib().nle_ctx_set_sampler(self._h, int(sampler)), self._h)
 
     def sample_pixels(self, lum, n_row_samples, n_col_samples, hx, hy):
@@ -337,6 +345,22 @@ class Context:
         _check(lib().nle_sample_pixels(self._h, C.c_void_p(x.data_ptr()), H, W, int(n_row_samples), int(n_col_samples),
                                        float(hx), float(hy), _np_ptr(out), C.byref(p)), self._h)
         return out[:p.value]
+
+    def sample_pixels_order(self, lum, n_row_samples, n_col_samples, hx, hy):
+        """SAMPLER_RESIDUAL's selection on the full plane `lum` as it was made (nle_sample_pixels_order): dict(order [int64,
+        the samples in the order chosen], pivot [float64: d of the sample when chosen, after the fallback its farthest-point
+        m], n_residual, stats [max d over the pixels not chosen, its first index, sum max(d, 0) after the last residual
+        round])"""
+        x = self._lum(lum)
+        H, W = x.shape
+        g = sample_grid(H, W, n_row_samples, n_col_samples)
+        n = g["n_sel_rows"] * g["n_sel_cols"]
+        order, pivot, stats = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64), np.zeros(3, dtype=np.float64)
+        p, nres = C.c_int(), C.c_int()
+        _check(lib().nle_sample_pixels_order(self._h, C.c_void_p(x.data_ptr()), H, W, int(n_row_samples), int(n_col_samples),
+                                             float(hx), float(hy), _np_ptr(order), _np_ptr(pivot), C.byref(p), C.byref(nres),
+                                             _np_ptr(stats)), self._h)
+        return dict(order=order[:p.value], pivot=pivot[:p.value], n_residual=nres.value, stats=stats)
 
     def nystrom_residual(self, lum, n_row_samples, n_col_samples, hx, hy, form: int = RESID_AUTO, thresh: float = 0.5,
                          want_map: bool = True):

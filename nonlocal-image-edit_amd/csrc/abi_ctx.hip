@@ -356,9 +356,9 @@ int nle_filter_chroma(const nle_filter* f, double* hc) {
 int nle_ctx_set_sampler(nle_ctx* ctx, int sampler) {
     if (!ctx) return NLE_ERR_INVALID;
     return guard(ctx, [&] {
-        if (sampler != NLE_SAMPLER_GRID && sampler != NLE_SAMPLER_FARTHEST)
-            throw Fail{NLE_ERR_INVALID, "sampler must be NLE_SAMPLER_GRID (0) or NLE_SAMPLER_FARTHEST (1), got " +
-                                            std::to_string(sampler)};
+        if (sampler != NLE_SAMPLER_GRID && sampler != NLE_SAMPLER_FARTHEST && sampler != NLE_SAMPLER_RESIDUAL)
+            throw Fail{NLE_ERR_INVALID, "sampler must be NLE_SAMPLER_GRID (0), NLE_SAMPLER_FARTHEST (1) or "
+                                        "NLE_SAMPLER_RESIDUAL (3), got " + std::to_string(sampler)};
         ctx->sampler = sampler;
     });
 }

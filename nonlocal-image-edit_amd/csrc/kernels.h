@@ -199,6 +199,19 @@ hipError_t patch_gather(hipStream_t s, const float* d_lum, int H, int W, int R, 
 int farthest_max_blocks();
 hipError_t farthest_samples(hipStream_t s, const float* d_lum, int H, int W, int p, double sw, double pw, double* d_m,
                             double* d_pv, int* d_pi, int* d_list);
+// residual-greedy (pivoted-Cholesky) sample selection (sampler.hip): the p pixels of NLE_SAMPLER_RESIDUAL in the order
+// chosen into d_list (p ints), their pivots into d_pivot (p doubles), for the full H x W plane d_lum; eps: the pivot below
+// which the rule falls back to the farthest-point step.  Workspace: d_L, the factor (residual_ld(N) * p doubles, column j
+// contiguous over the pixels), d_d and d_m (N doubles each), d_pv (6 farthest_max_blocks() doubles), d_pi (4
+// farthest_max_blocks() ints), d_state (2 kResidHead doubles).  *d_state_final points at the kResidHead doubles the last
+// launch left: {fallen back (0 / 1), n_residual, max d over the pixels not chosen, its first index, sum max(d, 0)}, the last
+// three after the last residual round; with want_stats they include the last sample's own column (one more round)
+constexpr int kResidHead = 8;
+constexpr int kResidMaxSamples = 2048;
+inline long long residual_ld(long long N) { return (N + 1) & ~1ll; }
+hipError_t residual_samples(hipStream_t s, const float* d_lum, int H, int W, int p, double sw, double pw, double eps,
+                            bool want_stats, double* d_L, double* d_d, double* d_m, double* d_pv, int* d_pi, double* d_state,
+                            int* d_list, double* d_pivot, const double** d_state_final);
 // d_out[k] = d_lum[d_pix[k]]
 hipError_t gather_pix(hipStream_t s, const float* d_lum, const long long* d_pix, int n, float* d_out);
 // d_mask (ceil(N / 32) words) = the bitmask of the pixels d_pix[0 .. n)

@@ -195,7 +195,7 @@ void compute_kernel_impl(nle_ctx* ctx, const float* d_lum, int H, int W, int nRo
     HIP_OK(hipSetDevice(ctx->device));
     std::vector<long long> list;
     FetchSpec spec;
-    if (f64 && opts.listed()) list = farthest_list(ctx, d_lum, gs, hx, hy), spec.list = &list;
+    if (f64 && opts.listed()) list = sampler_list(ctx, d_lum, gs, hx, hy), spec.list = &list;
     const SampleSet ss = fetch_samples(ctx, d_lum, gs, f64 ? opts : AffinityOpts{}, spec);
     if (f64) require_integer_planes(ctx, ss, /*agree_over_ranks=*/false);
     if (h_Ka) {
@@ -244,7 +244,7 @@ void nystrom_residual_impl(nle_ctx* ctx, const float* d_lum, int H, int W, int n
     hipStream_t st = ctx->stream;
     std::vector<long long> list;
     FetchSpec spec;
-    if (opts.listed()) list = farthest_list(ctx, d_lum, gs, hx, hy), spec.list = &list;
+    if (opts.listed()) list = sampler_list(ctx, d_lum, gs, hx, hy), spec.list = &list;
     const SampleSet ss = fetch_samples(ctx, d_lum, gs, opts, spec);
     require_integer_planes(ctx, ss, /*agree_over_ranks=*/false);
     const std::vector<double> Ka = build_Ka(ss, hx, hy);

@@ -154,7 +154,7 @@ nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow
     Timer tm_a(c->stream);
     tm_a.start();
     std::vector<long long> list;
-    if (opts.listed()) list = farthest_list(c, d_lum, gs, hx, hy);
+    if (opts.listed()) list = sampler_list(c, d_lum, gs, hx, hy);
     FetchSpec spec;
     spec.check_levels = want_fuse && tables_ok;
     spec.slab_plane = c->slab_input && c->world > 1;
@@ -518,10 +518,10 @@ int nle_sample_pixels(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_
         std::vector<long long> list((size_t)gs.p());
         const AffinityOpts opts = affinity_opts(ctx);
         if (opts.listed()) {
-            if (!d_lum) throw Fail{NLE_ERR_INVALID, "the farthest sampler needs the luminance plane"};
+            if (!d_lum) throw Fail{NLE_ERR_INVALID, std::string(opts.sampler_name()) + " needs the luminance plane"};
             check_affinity_opts(ctx, opts, gs, H, W, hx, hy, Caller::SAMPLE_PIXELS);
             HIP_OK(hipSetDevice(ctx->device));
-            list = farthest_list(ctx, d_lum, gs, hx, hy);
+            list = sampler_list(ctx, d_lum, gs, hx, hy);
             prof_flush(ctx);
         } else {
             for (int k = 0; k < gs.p(); ++k)
@@ -529,6 +529,37 @@ int nle_sample_pixels(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_
         }
         *p = gs.p();
         if (h_idx) std::copy(list.begin(), list.end(), h_idx);
+    });
+}
+
+long long nle_residual_sampler_bytes(int H, int W, int n_row_samples, int n_col_samples) {
+    GridSpec gs;
+    if (!make_grid(H, W, n_row_samples, n_col_samples, &gs)) return -1;
+    return nlek::residual_ld((long long)H * W) * gs.p() * (long long)sizeof(double);
+}
+
+int nle_sample_pixels_order(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
+                            double hy, long long* h_order, double* h_pivot, int* p, int* n_residual, double* h_stats) {
+    if (!ctx || !p || !n_residual) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        const AffinityOpts opts = affinity_opts(ctx);
+        if (opts.sampler != NLE_SAMPLER_RESIDUAL)
+            throw Fail{NLE_ERR_INVALID, "nle_sample_pixels_order: the order and the pivots are the residual sampler's "
+                                        "(nle_ctx_set_sampler(NLE_SAMPLER_RESIDUAL))"};
+        if (ctx->world > 1) throw Fail{NLE_ERR_INVALID, "nle_sample_pixels_order: world > 1 is not supported"};
+        const GridSpec gs = checked_grid(H, W, n_row_samples, n_col_samples);
+        if (gs.p() > 2048) throw Fail{NLE_ERR_INVALID, "more than 2048 samples is not supported"};
+        if (!d_lum) throw Fail{NLE_ERR_INVALID, "the residual sampler needs the luminance plane"};
+        check_affinity_opts(ctx, opts, gs, H, W, hx, hy, Caller::SAMPLE_PIXELS);
+        HIP_OK(hipSetDevice(ctx->device));
+        SamplerOrder o;
+        sampler_list(ctx, d_lum, gs, hx, hy, &o);
+        prof_flush(ctx);
+        *p = gs.p();
+        *n_residual = o.n_residual;
+        if (h_order) std::copy(o.order.begin(), o.order.end(), h_order);
+        if (h_pivot) std::copy(o.pivot.begin(), o.pivot.end(), h_pivot);
+        if (h_stats) std::copy(o.stats, o.stats + 3, h_stats);
     });
 }
 

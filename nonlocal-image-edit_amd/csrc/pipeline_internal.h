@@ -72,7 +72,7 @@ struct nle_ctx {
     const float* chroma_a = nullptr;
     const float* chroma_b = nullptr;
     double chroma_hc = 0.0;
-    int sampler = 0;  // nle_ctx_set_sampler: NLE_SAMPLER_GRID or NLE_SAMPLER_FARTHEST (sampler.hip)
+    int sampler = 0;  // nle_ctx_set_sampler: NLE_SAMPLER_GRID, NLE_SAMPLER_FARTHEST or NLE_SAMPLER_RESIDUAL (sampler.hip)
     int topk_solver = 0;  // nle_ctx_set_topk_solver: 0 full eigensolve of Q (:313-316), 1 Lanczos top-K (:170-199)
     // the environment switches as they stood when the call in progress began (guard() takes the snapshot; nothing below
     // an entry point asks the environment itself)

@@ -13,10 +13,12 @@ struct AffinityOpts {
     const float* d_a = nullptr; // chroma: the full a and b planes of 8-bit Lab on the device (both null = off) ...
     const float* d_b = nullptr;
     double hc = 0.0;            // ... and the chroma bandwidth
-    bool farthest = false;      // NLE_SAMPLER_FARTHEST: the sample set is a list (sampler.hip), not the grid's closed form
+    // NLE_SAMPLER_FARTHEST, NLE_SAMPLER_RESIDUAL: the sample set is a list (sampler.hip), not the grid's closed form
+    int sampler = NLE_SAMPLER_GRID;
     bool patch() const { return R > 0; }
     bool chroma() const { return d_a != nullptr; }
-    bool listed() const { return farthest; }
+    bool listed() const { return sampler != NLE_SAMPLER_GRID; }
+    const char* sampler_name() const { return sampler == NLE_SAMPLER_RESIDUAL ? "the residual sampler" : "the farthest sampler"; }
     bool any() const { return patch() || chroma() || listed(); }
     int patch_len() const { return (2 * R + 1) * (2 * R + 1); }
     double cwd() const { return (1.0 / (hc * hc)) / patch_len(); }  // the chroma weight of S_ab: (1/hc^2) / (2R + 1)^2
@@ -48,14 +50,22 @@ struct FetchSpec {
     bool check_levels = false;  // decide `quantised` and `level_tiles` (always decided with patches or chroma)
     // only this rank's rows exist behind d_lum (a virtual base): values and verdict are completed by an all-reduce; grid only
     bool slab_plane = false;
-    const std::vector<long long>* list = nullptr;  // the sample pixels of NLE_SAMPLER_FARTHEST (ascending, gs.p() of them)
+    const std::vector<long long>* list = nullptr;  // the sample pixels of a listed sampler (ascending, gs.p() of them)
 };
 // d_lum: base of the full plane.  o.patch(): also the samples' patches; o.chroma(): also their a and b values or patches
 // and the level check of the a and b planes
 SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, const AffinityOpts& o, const FetchSpec& spec = {});
 
-// The sample pixels of NLE_SAMPLER_FARTHEST on the full plane d_lum (sampler.hip), ascending; the same on every rank
-std::vector<long long> farthest_list(nle_ctx* c, const float* d_lum, const GridSpec& gs, double hx, double hy);
+// The sample pixels of the ctx's listed sampler (NLE_SAMPLER_FARTHEST or NLE_SAMPLER_RESIDUAL, sampler.hip) on the full
+// plane d_lum, ascending; the same on every rank.  `order` (one rank, the residual sampler): also the selection as it was made
+struct SamplerOrder {
+    std::vector<long long> order;  // the samples in the order chosen
+    std::vector<double> pivot;     // nle_sample_pixels_order's h_pivot
+    int n_residual = 0;
+    double stats[3] = {0, 0, 0};
+};
+std::vector<long long> sampler_list(nle_ctx* c, const float* d_lum, const GridSpec& gs, double hx, double hy,
+                                    SamplerOrder* order = nullptr);
 
 // Patches and chroma need integer-valued planes.  agree_over_ranks (train): refused on every rank if a plane is not integer
 // valued on one -- one ranks_where per option that is on, patch first

@@ -47,7 +47,7 @@ AffinityOpts affinity_opts(const nle_ctx* c) {
     o.d_a = c->chroma_a;  // nle_ctx_set_chroma sets both planes and hc > 0, or neither and 0
     o.d_b = c->chroma_b;
     o.hc = c->chroma_hc;
-    o.farthest = c->sampler == NLE_SAMPLER_FARTHEST;
+    o.sampler = c->sampler;
     return o;
 }
 
@@ -100,9 +100,11 @@ void check_affinity_opts(const nle_ctx* c, const AffinityOpts& o, const GridSpec
                                         "LDS tables (at most 2728 at patch radius 0, 5984 above)"};
     }
     if (o.listed()) {
-        check_mode("the farthest sampler", false);
+        check_mode(o.sampler_name(), false);
         if (!(hx > 0) || !(hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
-        check_slab("the farthest sampler", false);
+        check_slab(o.sampler_name(), false);
+        if (o.sampler == NLE_SAMPLER_RESIDUAL && gs.p() > nlek::kResidMaxSamples)
+            throw Fail{NLE_ERR_INVALID, "the residual sampler takes at most 2048 samples, got " + std::to_string(gs.p())};
     }
 }
 
@@ -185,23 +187,68 @@ SampleSet fetch_samples(nle_ctx* c, const float* d_lum, const GridSpec& gs, cons
     return s;
 }
 
+namespace {
+// NLE_SAMPLER_FARTHEST on this rank: the samples in the order chosen, into v[0 .. p)
+void farthest_select(nle_ctx* c, const float* d_lum, const GridSpec& gs, double hx, double hy, double* v) {
+    const int p = gs.p(), nb = nlek::farthest_max_blocks();
+    DevBuf<double> d_m((size_t)gs.H * gs.W), d_pv((size_t)2 * nb);
+    DevBuf<int> d_pi((size_t)2 * nb), d_list(p);
+    std::vector<int> idx(p);
+    PROFILED(c, NLE_K_SMALL, nlek::farthest_samples(c->stream, d_lum, gs.H, gs.W, p, 1.0 / (hx * hx), 1.0 / (hy * hy), d_m.p,
+                                                    d_pv.p, d_pi.p, d_list.p));
+    HIP_OK(hipMemcpyAsync(idx.data(), d_list.p, p * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < p; ++k) v[k] = (double)idx[k];
+}
+
+// NLE_SAMPLER_RESIDUAL on this rank; `order`: also pivots, n_residual and the statistics of the whole set (one more round)
+void residual_select(nle_ctx* c, const float* d_lum, const GridSpec& gs, double hx, double hy, double* v, SamplerOrder* order) {
+    const int p = gs.p(), nb = nlek::farthest_max_blocks();
+    const size_t N = (size_t)gs.H * gs.W, ld = (size_t)nlek::residual_ld((long long)N);
+    // the factor is the one large buffer: refused before anything is enqueued if it cannot fit (what the cache holds counts
+    // as free: arena_alloc drops it when hipMalloc fails)
+    const size_t need = ld * p * sizeof(double);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + c->arena_bytes)
+        throw Fail{NLE_ERR_INVALID, "the residual sampler holds its factor in device memory: " + std::to_string(need) +
+                                        " bytes needed (nle_residual_sampler_bytes), " +
+                                        std::to_string(free_b + c->arena_bytes) + " free"};
+    DevBuf<double> d_L(ld * p), d_d(N), d_m(N), d_pv((size_t)6 * nb), d_state(2 * nlek::kResidHead), d_pivot(p);
+    DevBuf<int> d_pi((size_t)4 * nb), d_list(p);
+    std::vector<int> idx(p);
+    double state[nlek::kResidHead];
+    const double* d_final = nullptr;
+    PROFILED(c, NLE_K_SMALL, nlek::residual_samples(c->stream, d_lum, gs.H, gs.W, p, 1.0 / (hx * hx), 1.0 / (hy * hy), NLE_EPS,
+                                                    order != nullptr, d_L.p, d_d.p, d_m.p, d_pv.p, d_pi.p, d_state.p, d_list.p,
+                                                    d_pivot.p, &d_final));
+    HIP_OK(hipMemcpyAsync(idx.data(), d_list.p, p * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipMemcpyAsync(state, d_final, sizeof state, hipMemcpyDeviceToHost, c->stream));
+    if (order) {
+        order->pivot.resize(p);
+        HIP_OK(hipMemcpyAsync(order->pivot.data(), d_pivot.p, p * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < p; ++k) v[k] = (double)idx[k];
+    if (order) {
+        order->order.assign(idx.begin(), idx.end());
+        order->n_residual = (int)state[1];
+        std::copy(state + 2, state + 5, order->stats);
+    }
+}
+}  // namespace
+
 // At world > 1 rank 0 selects and the others receive the set through the fp64 all-reduce (they add zeros; indices < 2^31
 // are exact in fp64); the last slot carries rank 0's failure, so that every rank returns the same verdict.
-std::vector<long long> farthest_list(nle_ctx* c, const float* d_lum, const GridSpec& gs, double hx, double hy) {
+std::vector<long long> sampler_list(nle_ctx* c, const float* d_lum, const GridSpec& gs, double hx, double hy,
+                                    SamplerOrder* order) {
     const int p = gs.p();
+    const AffinityOpts o = affinity_opts(c);
     std::vector<long long> list(p);
     std::vector<double> v((size_t)p + 1, 0.0);
     if (c->rank == 0 || c->world <= 1) {
         try {
-            const int nb = nlek::farthest_max_blocks();
-            DevBuf<double> d_m((size_t)gs.H * gs.W), d_pv((size_t)2 * nb);
-            DevBuf<int> d_pi((size_t)2 * nb), d_list(p);
-            std::vector<int> idx(p);
-            PROFILED(c, NLE_K_SMALL, nlek::farthest_samples(c->stream, d_lum, gs.H, gs.W, p, 1.0 / (hx * hx), 1.0 / (hy * hy),
-                                                            d_m.p, d_pv.p, d_pi.p, d_list.p));
-            HIP_OK(hipMemcpyAsync(idx.data(), d_list.p, p * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_OK(hipStreamSynchronize(c->stream));
-            for (int k = 0; k < p; ++k) v[k] = (double)idx[k];
+            if (o.sampler == NLE_SAMPLER_RESIDUAL) residual_select(c, d_lum, gs, hx, hy, v.data(), order);
+            else farthest_select(c, d_lum, gs, hx, hy, v.data());
         } catch (const Fail&) {
             if (c->world <= 1) throw;
             v[p] = 1.0;
@@ -213,7 +260,7 @@ std::vector<long long> farthest_list(nle_ctx* c, const float* d_lum, const GridS
         all_reduce(c, d_v.p, (size_t)p + 1);
         HIP_OK(hipMemcpyAsync(v.data(), d_v.p, v.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_OK(hipStreamSynchronize(c->stream));
-        if (v[p] != 0.0) throw Fail{NLE_ERR_HIP, "the farthest sampler failed on rank 0"};
+        if (v[p] != 0.0) throw Fail{NLE_ERR_HIP, std::string(o.sampler_name()) + " failed on rank 0"};
     }
     for (int k = 0; k < p; ++k) list[k] = (long long)v[k];
     std::sort(list.begin(), list.end());

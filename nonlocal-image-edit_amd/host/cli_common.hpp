@@ -3,8 +3,8 @@
 // print the same usage line when too few arguments are given, parse numbers with std::stoi / std::stod (garbage
 // throws, like the reference: src/enhance.cpp:20-31, src/denoise.cpp:19-31) and return 0 on the two soft failures
 // (usage, unreadable image) for drop-in compatibility.  New here: optional LEADING `--patch-radius R` (patch affinities,
-// NLEFilter::patchRadius), `--sampler grid|farthest` (NLEFilter::sampler) and the flag `--exact` (NLEFilter::exact, no
-// value; not with a non-zero radius or the farthest sampler) and, for enhance only, `--chroma HC` (chroma-aware affinities,
+// NLEFilter::patchRadius), `--sampler grid|farthest|residual` (NLEFilter::sampler) and the flag `--exact` (NLEFilter::exact, no
+// value; not with a non-zero radius or a sampler other than the grid) and, for enhance only, `--chroma HC` (chroma-aware affinities,
 // NLEFilter::chromaBandwidth: a finite number > 0; not with --exact or a radius above NLE_CHROMA_PATCH_RADIUS_MAX), in any order; reference command lines never start with
 // `--`, so they parse exactly as before.  An invalid value prints a message to stderr and exits with status 2 before
 // anything touches the GPU.  For enhance only, region edits (NLEFilter::enhanceRegions): `--region MASK:w1,w2,...`, up to
@@ -33,7 +33,7 @@ struct FilterArgs {
     double hx = 0, hy = 0;
     std::vector<double> extra;  // everything after the eighth argument, as doubles
     int patchRadius = 0;        // --patch-radius R
-    int sampler = NLE_SAMPLER_GRID;  // --sampler grid|farthest
+    int sampler = NLE_SAMPLER_GRID;  // --sampler grid|farthest|residual
     bool exact = false;              // --exact
     double chroma = 0;               // --chroma HC (enhance only)
     // --region MASK:w1,w2,... (enhance only, repeatable), --region-spread T, --region-floor F
@@ -166,17 +166,17 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
             }
             a->patchRadius = (int)r;
         } else {
-            if (v != "grid" && v != "farthest") {
-                std::cerr << argv[0] << ": --sampler takes 'grid' or 'farthest', got '" << v << "'" << std::endl;
+            if (v != "grid" && v != "farthest" && v != "residual") {
+                std::cerr << argv[0] << ": --sampler takes 'grid', 'farthest' or 'residual', got '" << v << "'" << std::endl;
                 std::exit(2);
             }
-            a->sampler = v == "grid" ? NLE_SAMPLER_GRID : NLE_SAMPLER_FARTHEST;
+            a->sampler = v == "grid" ? NLE_SAMPLER_GRID : v == "farthest" ? NLE_SAMPLER_FARTHEST : NLE_SAMPLER_RESIDUAL;
         }
         first += 2;
     }
     if (a->exact && (a->patchRadius != 0 || a->sampler != NLE_SAMPLER_GRID)) {
         std::cerr << argv[0] << ": --exact uses no samples and single-pixel affinities: it does not combine with "
-                  << "--patch-radius R > 0 or --sampler farthest" << std::endl;
+                  << "--patch-radius R > 0, --sampler farthest or --sampler residual" << std::endl;
         std::exit(2);
     }
     if (a->chroma != 0 && (a->exact || a->patchRadius > NLE_CHROMA_PATCH_RADIUS_MAX)) {

@@ -866,7 +866,7 @@ void NLEFilter::trainForEnhancementGroup(const Image& image, int nRowSamples, in
         check(nle_dev_upload(c, d_bgr.p, image.ptr<unsigned char>() + (size_t)r0 * W * 3, nl * 3), c);
         check(nle_bgr2lab8(c, static_cast<unsigned char*>(d_bgr.p), (long long)nl, lab, d_L.f()), c);
         check(nle_ctx_set_patch_radius(c, patchRadius), c);  // refused by the train at world > 1 (slab input) when > 0
-        check(nle_ctx_set_sampler(c, sampler), c);           // likewise when farthest
+        check(nle_ctx_set_sampler(c, sampler), c);           // likewise when not the grid
         if (exact) check(nle_ctx_set_mode(c, NLE_MODE_EXACT_F64), c);  // refused by the train at world > 1
         int st = NLE_OK;
         if (chroma) {  // this rank's slab of a and b: refused by the train at world > 1 (slab input), like a patch radius
@@ -1084,6 +1084,14 @@ Mat NLEFilter::eigvecs() const {
 
 void NLEFilter::timings(double ms[6]) const {
     if (f_) nle_filter_timings(f_, ms);
+}
+
+std::vector<long long> NLEFilter::samplePixels() const {
+    int p = 0;
+    if (!f_ || nle_filter_sample_pixels(f_, nullptr, &p) != NLE_OK) return {};
+    std::vector<long long> idx((size_t)p);
+    nle_filter_sample_pixels(f_, idx.data(), &p);
+    return idx;
 }
 
 void NLEFilter::diag(int info[8]) const {
