@@ -1,0 +1,33 @@
+// Host side of the kernels that are instantiated per column count (tables.hip, sorted.hip, sorted_planes.hip): the map from
+// the run-time count onto its instantiation and the launch itself.  Not installed, not part of kernels.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+#include <utility>
+
+namespace nlek {
+
+// f(std::integral_constant<int, NC>{}) for the NC in [LO, HI] that equals nc; false (and no call) where nc is outside.
+// The rules on which forms a count has are written in f, as `if constexpr` on NC.
+template <int LO, class F, int... I>
+bool dispatch_columns_seq(int nc, F&& f, std::integer_sequence<int, I...>) {
+    return ((nc == LO + I ? (f(std::integral_constant<int, LO + I>{}), true) : false) || ...);
+}
+template <int LO, int HI, class F>
+bool dispatch_columns(int nc, F&& f) {
+    return dispatch_columns_seq<LO>(nc, f, std::make_integer_sequence<int, HI - LO + 1>{});
+}
+
+// Launches `kernel`; beyond 48 KB of dynamic LDS the limit of exactly this instantiation is raised first.
+template <class... P, class... A>
+hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 threads, size_t shm, hipStream_t s, A&&... args) {
+    if (shm > 48 * 1024) {
+        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        if (ea != hipSuccess) return ea;
+    }
+    hipLaunchKernelGGL(kernel, grid, threads, shm, s, static_cast<P>(args)...);
+    return hipGetLastError();
+}
+
+}  // namespace nlek

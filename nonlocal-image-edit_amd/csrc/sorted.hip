@@ -63,6 +63,13 @@ __device__ __forceinline__ int block_max256(int v, int* red) {
     __syncthreads();
     return max(max(red[0], red[1]), max(red[2], red[3]));
 }
+
+// compute units of the current device (256 where it cannot be asked)
+int cu_count() {
+    int ncu = 256, dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    return ncu;
+}
 }  // namespace
 
 int sorted_max_width() { return 8192; }  // 8 W fits 16 bits; chunks of <= 32 pixels (kMaxBlocks)
@@ -257,8 +264,7 @@ __global__ __launch_bounds__(256) void k_plane_matches_levels(const float* __res
 
 hipError_t plane_matches_levels(hipStream_t s, const float* d_x, const unsigned char* d_lev, long long n, int* d_flag) {
     if (n <= 0) return hipSuccess;
-    int ncu = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int ncu = cu_count();
     const long long want = (n / 4 + 255) / 256 + 1;  // one block of four per thread, or the 8 workgroups per CU that fill the chip
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(want, (long long)ncu * 8));
     hipLaunchKernelGGL(k_plane_matches_levels, dim3(grid), dim3(256), 0, s, d_x, d_lev, n, d_flag);
@@ -362,78 +368,46 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
     if (run_if != nullptr && *run_if == 0) return;  // (kernels.h: sink_hist_tiled)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int n = kLevels * NC;
-    constexpr int SL = NC < 11 ? NC : 11;  // sums combined per tree (slices of the nC sums when nC > 11)
-    constexpr int PS = SL | 1;             // odd stride: consecutive threads' rows start on different banks
     constexpr bool KEEP_E = NC <= 32;      // keep the column factors of a pixel in registers between the two loops (254 VGPRs at NC = 30, no spills)
     constexpr bool REC = CF == 1, MOM = CF == 2;
     const int W = gs.W;
-    const size_t pitch = sorted_row_pitch(W);
-    double* sE = reinterpret_cast<double*>(smem_raw);
-    double* sP = sE + ((W + 2) & ~1);
-    unsigned short* sfirst = reinterpret_cast<unsigned short*>(sP + (size_t)kT * PS);  // [2][260], rows alternate
-    double* sCk = reinterpret_cast<double*>(sfirst + 2 * 260);                          // [NC] C_b = kappa^(b (b - 1) / 2)
+    const RowLds lds(smem_raw, W, kPassStride<NC>);
+    double* const sP = lds.sP;
+    unsigned short* const sfirst = lds.sfirst;
+    double* const sCk = lds.sCk;
     const int tid = threadIdx.x;
-    for (int i = tid; i <= W; i += kT) sE[i] = Etab[i];
-    if (MOM && tid == 0) {
-        double ck = 1.0, kp = 1.0;  // C_{b+1} = C_b kappa^b
-        for (int b = 0; b < NC; ++b) {
-            sCk[b] = ck;
-            ck *= kp;
-            kp *= kappa;
-        }
-    }
+    fill_dist_table(lds.sE, Etab, W, tid);
+    if (MOM) fill_moment_factors<NC>(sCk, kappa, tid);
     const int cb0 = gs.colOff, cs = gs.colStep;
     const bool recip = mode == ROWPASS_RECIP, xmode = mode == ROWPASS_XVEC;
-    const unsigned sEa = lds_addr(sE);
+    const unsigned sEa = lds_addr(lds.sE);
 
-    // Software pipeline over the rows of this workgroup: everything a row needs from global memory is requested while
-    // the PREVIOUS row is being combined -- its first indices and its level's table row (their address needs the row's
-    // chunk descriptor, which is therefore requested two rows ahead) -- and taken in before that row's table is stored.
-    // Nothing foreign is pending during the pixel loop, so its waits (the counter retires in order) are exact.
-    const int G = (int)gridDim.x;  // <= nrows
-    int lrow = blockIdx.x, nrow = lrow + G;
-    uint2 dsc = desc[(size_t)lrow * kT + tid];
-    uint2 dsc_n = dsc;
-    if (nrow < nrows) dsc_n = desc[(size_t)nrow * kT + tid];
-    if (tid < 258) sfirst[tid] = first[(size_t)lrow * 258 + tid];
-    // all indices of the chunk (<= kMaxBlocks blocks of four) live in registers: the pixel loop itself loads nothing
-    uint2 idx[kMaxBlocks];
-    auto load_idx = [&](uint2 (&dst)[kMaxBlocks], const int row, const uint2 d) {
-        const uint2* slot = reinterpret_cast<const uint2*>(scol + (size_t)row * pitch + (size_t)tid * dsc_chp(d));
-        const int ln = dsc_len(d);
-#pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) {  // blocks past the chunk: column 0 (the wave may walk further than this lane)
-            uint2 v = make_uint2(0u, 0u);
-            if (4 * b < ln) v = slot[b];
-            dst[b] = v;
-        }
-    };
-    load_idx(idx, lrow, dsc);
+    // The walk's pipeline over the rows of this workgroup (RowWalk), and with it this kernel's own requests: the next
+    // row's first-chunk table entry under the pixel loop and its level's table row (whose address needs the row's chunk
+    // descriptor) while the current row is being combined -- both taken in before the current row's table is stored.
+    RowWalk w(scol, desc, W, nrows, tid);
+    w.start([&] {
+        if (tid < 258) sfirst[tid] = first[(size_t)w.lrow * 258 + tid];
+    });
     double gv[NC];
 #pragma unroll
-    for (int b = 0; b < NC; ++b) gv[b] = recip ? g[(size_t)lrow * n + b * kLevels + dsc_level(dsc)] : 0.0;
+    for (int b = 0; b < NC; ++b) gv[b] = recip ? g[(size_t)w.lrow * n + b * kLevels + dsc_level(w.dsc)] : 0.0;
     __syncthreads();  // sE, sfirst visible
     for (int par = 0;; par ^= 1) {
-        const bool has_next = nrow < nrows;
-        const int nnrow = nrow + G;
+        const bool has_next = w.has_next();
+        const int lrow = w.lrow, nrow = w.nrow;
+        const uint2 dsc_n = w.dsc_n;
         const unsigned short* sfc = sfirst + par * 260;
-        const int len = dsc_len(dsc);
+        const int len = dsc_len(w.dsc);
         double acc[NC];
 #pragma unroll
         for (int b = 0; b < NC; ++b) acc[b] = 0.0;
         const double* cv_row = cvec ? cvec + (size_t)lrow * W : nullptr;
         const float* xv_row = xvec ? xvec + (size_t)(row0 + lrow) * W : nullptr;
         double* yb_row = ybuf ? ybuf + (size_t)lrow * W : nullptr;
-        // requested BEFORE the pixel loop, in flight under it: the descriptor of the row after next, the next row's
-        // first-chunk table entry and its indices (the pixel loop has no wait on the memory counter)
-        uint2 dsc_nn = dsc_n;
         unsigned short sf_n = 0;
-        uint2 idx_n[kMaxBlocks];
-        if (has_next) {
-            if (nnrow < nrows) dsc_nn = desc[(size_t)nnrow * kT + tid];
-            sf_n = first[(size_t)nrow * 258 + (tid < 258 ? tid : 257)];
-            load_idx(idx_n, nrow, dsc_n);
-        }
+        RowWalk::Next nx;
+        w.request_next(nx, [&] { sf_n = first[(size_t)nrow * 258 + (tid < 258 ? tid : 257)]; });
         // MOM: the next row's table row too.  With it requested only after the loop, a workgroup's row is loop (2 us of
         // arithmetic) + a memory round trip + combine + stores (5-7 us of waiting): two workgroups per CU keep the vector
         // units busy for less than half of that.  The moment form leaves the registers for it (no column factor is kept).
@@ -445,9 +419,6 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
                 for (int b = 0; b < NC; ++b) gvn[b] = g[(size_t)nrow * n + b * kLevels + dsc_level(dsc_n)];
             }
         }
-        // One pixel at a time (the column factors of one pixel fill the registers; the scheduling barrier keeps the
-        // unrolled bodies from being interleaved), up to the longest chunk of the WAVE: a scalar bound, so that a wave
-        // whose chunks are all short skips the rest without per-lane bookkeeping.  Lanes past their own chunk add zeros.
         double(&q)[NC] = gv;  // MOM: the polynomial's coefficients C_b g_b of this thread's chunk, in place of g_b
         if constexpr (MOM) {
             if (recip) {
@@ -533,43 +504,10 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
                 column_factors<NC, REC>(sEa, c8, cb0, cs, kappa, [&](const int b, const double ev) { acc[b] += ev * y; });
             }
         };
-        int wlen = len;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wlen = max(wlen, __shfl_xor(wlen, off));
-        wlen = __builtin_amdgcn_readfirstlane(wlen);
-        if constexpr (MOM) {
-#pragma unroll
-            for (int b = 0; b < kMaxBlocks; ++b) {
-                if (4 * b >= wlen) break;
-                const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (4 * b + k < wlen) {
-                        pixel_mom(cs4[k], 4 * b + k);
-                        NLE_PIXEL_FENCE();
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) {
-            if (4 * b >= wlen) break;
-            pixel(idx[b].x & 0xffffu, 4 * b < len);
-            NLE_PIXEL_FENCE();
-            if (4 * b + 1 < wlen) {
-                pixel(idx[b].x >> 16, 4 * b + 1 < len);
-                NLE_PIXEL_FENCE();
-            }
-            if (4 * b + 2 < wlen) {
-                pixel(idx[b].y & 0xffffu, 4 * b + 2 < len);
-                NLE_PIXEL_FENCE();
-            }
-            if (4 * b + 3 < wlen) {
-                pixel(idx[b].y >> 16, 4 * b + 3 < len);
-                NLE_PIXEL_FENCE();
-            }
-        }
-        }
+        for_chunk_pixels(w.idx, wave_max_len(len), [&](const unsigned c8, const int at) {
+            if constexpr (MOM) pixel_mom(c8, at);
+            else pixel(c8, at < len);
+        });
         // The combine / load / store phase is a chain of barriers and memory round trips; the other workgroup of the CU is
         // (usually) in its pixel loop and, being older or younger, wins or loses every issue slot wholesale (the stamps of
         // tools/stamps_run.sh: the second workgroup's combine took 4-5 us against 2.2 us alone).  Raise the priority here,
@@ -590,6 +528,7 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
                 for (int b = 0; b < NC; ++b) gv[b] = g[(size_t)nrow * n + b * kLevels + dsc_level(dsc_n)];
             }
         }
+        constexpr int SL = kPassSlice<NC>, PS = kPassStride<NC>;
         double* hrow = hout + (size_t)lrow * n;
 #pragma unroll
         for (int s0 = 0; s0 < NC; s0 += SL) {
@@ -606,12 +545,9 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
             for (int i = 0; i < SL; ++i) sP[tid * PS + i] = v[i];
             __syncthreads();
             if (s0 == 0) {
-                // Were the loads above still pending behind the table stores below, the next row's first pixel would
-                // wait for those stores to be acknowledged.  Take them in here (all lanes: a divergent use would leave
-                // a load pending for the others).
-                asm volatile("" ::"v"(sf_n), "v"(dsc_nn.x), "v"(dsc_nn.y));
-#pragma unroll
-                for (int b = 0; b < kMaxBlocks; ++b) asm volatile("" ::"v"(idx_n[b].x), "v"(idx_n[b].y));
+                // behind the first barrier and before any store: the next row's loads (RowWalk::take_in), this kernel's with them
+                asm volatile("" ::"v"(sf_n));
+                w.take_in(nx);
 #pragma unroll
                 for (int b = 0; b < NC; ++b) asm volatile("" ::"v"(gv[b]));
                 // next row's first-chunk table (its last readers left before the previous row's end barrier; its next
@@ -635,21 +571,11 @@ __global__ __launch_bounds__(kT, (NC <= 12 ? 4 : 2)) void k_sorted_pass(int mode
         __builtin_amdgcn_s_setprio(0);  // (letting the two workgroups take turns at priority 1 in their loops balanced
                                         // their finish times, 65 / 71 us instead of 61 / 74, but not the kernel's)
         if (!has_next) break;
-        lrow = nrow;
-        nrow = nnrow;
-        dsc = dsc_n;
-        dsc_n = dsc_nn;
-#pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) idx[b] = idx_n[b];
+        w.advance(nx);
     }
 }
 
-int sorted_grid(int nrows, const SortedRows& sr) {
-    int ncu = 256;
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    return std::max(1, std::min(nrows, sr.wgs_per_cu * ncu));
-}
+int sorted_grid(int nrows, const SortedRows& sr) { return std::max(1, std::min(nrows, sr.wgs_per_cu * cu_count())); }
 
 // Where the recurrence of column_factors stays inside the normal range of fp64 (with a wide margin): every e_b =
 // exp(-(u - b cs)^2 / hx^2) and every ratio rho_b = exp((2 cs u - (2 b + 1) cs^2) / hx^2), u = c - cb0, c = 0 .. W-1.
@@ -687,42 +613,24 @@ hipError_t sorted_pass(hipStream_t s, int mode, GridSpec gs, int row0, int nrows
     if (nrows_local <= 0) return hipSuccess;
     const size_t shm = sorted_lds_bytes(gs.W, (nC < 11 ? nC : 11) | 1);
     const int grid = sorted_grid(nrows_local, sr);
-#define NLE_SP1(NCV, CFV)                                                                                                 \
-    {                                                                                                                     \
-        if (shm > 48 * 1024) {                                                                                            \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sorted_pass<NCV, CFV>),                   \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                    \
-            if (ea != hipSuccess) return ea;                                                                              \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((k_sorted_pass<NCV, CFV>), dim3((unsigned)grid), dim3(kT), shm, s, mode, sr.scol, sr.desc,      \
-                           sr.first, gs, row0, nrows_local, sr.E, d_g, eps, d_ybuf, d_h, d_cvec, d_xvec, sr.kappa, lev_t0, \
-                           lev_nt, d_run_if);                                                                             \
-    }
-#define NLE_SP(NCV)                                                                                                       \
-    case NCV:                                                                                                             \
-        if constexpr ((NCV) > 1) {                                                                                        \
-            if (sr.mom) {                                                                                                 \
-                NLE_SP1(NCV, 2)                                                                                           \
-                break;                                                                                                    \
-            }                                                                                                             \
-        }                                                                                                                 \
-        if constexpr ((NCV) > 12) {                                                                                       \
-            if (sr.rec) NLE_SP1(NCV, 1) else NLE_SP1(NCV, 0)                                                              \
-        } else {                                                                                                          \
-            if (sr.rec) return hipErrorInvalidValue;                                                                      \
-            NLE_SP1(NCV, 0)                                                                                               \
-        }                                                                                                                 \
-        break;
-    switch (nC) {
-        NLE_SP(1) NLE_SP(2) NLE_SP(3) NLE_SP(4) NLE_SP(5) NLE_SP(6) NLE_SP(7) NLE_SP(8) NLE_SP(9) NLE_SP(10) NLE_SP(11)
-        NLE_SP(12) NLE_SP(13) NLE_SP(14) NLE_SP(15) NLE_SP(16) NLE_SP(17) NLE_SP(18) NLE_SP(19) NLE_SP(20)
-        NLE_SP(21) NLE_SP(22) NLE_SP(23) NLE_SP(24) NLE_SP(25) NLE_SP(26) NLE_SP(27) NLE_SP(28) NLE_SP(29)
-        NLE_SP(30) NLE_SP(31) NLE_SP(32) NLE_SP(33) NLE_SP(34) NLE_SP(35) NLE_SP(36)
-        default: return hipErrorInvalidValue;
-    }
-#undef NLE_SP
-#undef NLE_SP1
-    return hipGetLastError();
+    const auto run = [&](auto kernel) {
+        return launch(kernel, dim3((unsigned)grid), dim3(kT), shm, s, mode, sr.scol, sr.desc, sr.first, gs, row0, nrows_local, sr.E,
+                      d_g, eps, d_ybuf, d_h, d_cvec, d_xvec, sr.kappa, lev_t0, lev_nt, d_run_if);
+    };
+    hipError_t e = hipErrorInvalidValue;
+    // the moment form from two columns, the recurrence only beyond 12 (sorted_recurrence)
+    dispatch_columns<1, 36>(nC, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        if constexpr (NC > 1) {
+            if (sr.mom) {
+                e = run(k_sorted_pass<NC, 2>);
+                return;
+            }
+        }
+        if constexpr (NC > 12) e = sr.rec ? run(k_sorted_pass<NC, 1>) : run(k_sorted_pass<NC, 0>);
+        else if (!sr.rec) e = run(k_sorted_pass<NC, 0>);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------ apply, expand half, on the sorted rows
@@ -748,21 +656,10 @@ __global__ __launch_bounds__(kT) void k_sorted_expand(const unsigned short* __re
     double* sE = reinterpret_cast<double*>(smem_raw);
     float* sOut = reinterpret_cast<float*>(sE + ((W + 2) & ~1));  // [kExpL][W]
     const int tid = threadIdx.x;
-    for (int i = tid; i <= W; i += kT) sE[i] = Etab[i];
+    fill_dist_table(sE, Etab, W, tid);
     const int cb0 = gs.colOff, cs = gs.colStep;
     const unsigned sEa = lds_addr(sE);
-    const size_t pitch = sorted_row_pitch(W);
     double gv[kExpL][NC];
-    auto load_idx = [&](uint2 (&dst)[kMaxBlocks], const int row, const uint2 d) {
-        const uint2* slot = reinterpret_cast<const uint2*>(scol + (size_t)row * pitch + (size_t)tid * dsc_chp(d));
-        const int ln = dsc_len(d);
-#pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) {  // blocks past the chunk: column 0 (the wave may walk further than this lane)
-            uint2 v = make_uint2(0u, 0u);
-            if (4 * b < ln) v = slot[b];
-            dst[b] = v;
-        }
-    };
     auto load_gv = [&](const int row, const int x) {
 #pragma unroll
         for (int l = 0; l < kExpL; ++l)
@@ -796,11 +693,6 @@ __global__ __launch_bounds__(kT) void k_sorted_expand(const unsigned short* __re
             for (int c = tid; c < W; c += kT) orow[c] = sOut[l * W + c];
         }
     };
-    auto wave_max = [](int v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-        return __builtin_amdgcn_readfirstlane(v);
-    };
     // Up to 60 table values per thread the registers leave room for a software pipeline over the workgroup's rows (below);
     // beyond (31 .. 36 columns) a row is taken start to end: descriptor, then indices and table values, then the pixels
     // with one c value each, then the stores.
@@ -811,22 +703,10 @@ __global__ __launch_bounds__(kT) void k_sorted_expand(const unsigned short* __re
             const uint2 dsc = desc[(size_t)lrow * kT + tid];
             const int len = dsc_len(dsc);
             uint2 idx[kMaxBlocks];
-            load_idx(idx, lrow, dsc);
+            load_chunk_idx(idx, scol, sorted_row_pitch(W), lrow, tid, dsc);
             load_gv(lrow, dsc_level(dsc));
             const double* cv_row = cvec + (size_t)lrow * W;
-            const int wlen = wave_max(len);
-#pragma unroll
-            for (int b = 0; b < kMaxBlocks; ++b) {
-                if (4 * b >= wlen) break;
-                const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (4 * b + k < wlen) {
-                        pixel(cs4[k], cv_row[cs4[k] >> 3], 4 * b + k < len);
-                        NLE_PIXEL_FENCE();
-                    }
-                }
-            }
+            for_chunk_pixels(idx, wave_max_len(len), [&](const unsigned c8, const int at) { pixel(c8, cv_row[c8 >> 3], at < len); });
             __syncthreads();  // the row's outputs are in sOut
             store_row(lrow);
             __syncthreads();  // before the next row writes sOut
@@ -845,32 +725,23 @@ __global__ __launch_bounds__(kT) void k_sorted_expand(const unsigned short* __re
             dst[2] = row[(v.y & 0xffffu) >> 3];
             dst[3] = row[v.y >> 19];
         };
-        const int G = (int)gridDim.x;  // <= nrows
-        int lrow = blockIdx.x, nrow = lrow + G;
-        uint2 dsc = desc[(size_t)lrow * kT + tid];
-        uint2 dsc_n = dsc;
-        if (nrow < nrows) dsc_n = desc[(size_t)nrow * kT + tid];
-        uint2 idx[kMaxBlocks];
-        load_idx(idx, lrow, dsc);
-        load_gv(lrow, dsc_level(dsc));
+        RowWalk w(scol, desc, W, nrows, tid);
+        w.start([] {});
+        const uint2(&idx)[kMaxBlocks] = w.idx;
+        load_gv(w.lrow, dsc_level(w.dsc));
         double cvb[4];
-        load_cv(cvb, cvec + (size_t)lrow * W, idx[0]);
+        load_cv(cvb, cvec + (size_t)w.lrow * W, idx[0]);
         for (;;) {
-            const bool has_next = nrow < nrows;
-            const int nnrow = nrow + G;
-            const int len = dsc_len(dsc);
-            const double* cv_row = cvec + (size_t)lrow * W;
-            const int wlen = wave_max(len);
+            const bool has_next = w.has_next();
+            const int len = dsc_len(w.dsc);
+            const double* cv_row = cvec + (size_t)w.lrow * W;
+            const int wlen = wave_max_len(len);
             // requested before the pixel loop, in flight under it: the second block's c values first (loads return in
-            // order: the loop's first wait is for these), then the descriptor of the row after next and the next row's indices
+            // order: the loop's first wait is for these), then the walk's requests for the rows to come
             double cvn[4] = {0.0, 0.0, 0.0, 0.0};
             if (4 < wlen) load_cv(cvn, cv_row, idx[1]);
-            uint2 dsc_nn = dsc_n;
-            uint2 idx_n[kMaxBlocks];
-            if (has_next) {
-                if (nnrow < nrows) dsc_nn = desc[(size_t)nnrow * kT + tid];
-                load_idx(idx_n, nrow, dsc_n);
-            }
+            RowWalk::Next nx;
+        w.request_next(nx, [] {});
 #pragma unroll
             for (int b = 0; b < kMaxBlocks; ++b) {
                 if (4 * b >= wlen) break;
@@ -890,30 +761,22 @@ __global__ __launch_bounds__(kT) void k_sorted_expand(const unsigned short* __re
             }
             // this thread's table values have had their last use: the next row's, and its first c values
             if (has_next) {
-                load_gv(nrow, dsc_level(dsc_n));
-                load_cv(cvb, cvec + (size_t)nrow * W, idx_n[0]);
+                load_gv(w.nrow, dsc_level(w.dsc_n));
+                load_cv(cvb, cvec + (size_t)w.nrow * W, nx.idx[0]);
             }
             __syncthreads();  // the row's outputs are in sOut
-            // Were these loads still pending behind the stores below, the next row's first pixel would wait for the stores
-            // to be acknowledged.  Take them in here (all lanes: a divergent use would leave a load pending for the others).
-            asm volatile("" ::"v"(dsc_nn.x), "v"(dsc_nn.y));
-#pragma unroll
-            for (int b = 0; b < kMaxBlocks; ++b) asm volatile("" ::"v"(idx_n[b].x), "v"(idx_n[b].y));
+            // taken in with the walk's, before the stores below (RowWalk::take_in)
+            w.take_in(nx);
 #pragma unroll
             for (int l = 0; l < kExpL; ++l)
 #pragma unroll
                 for (int b = 0; b < NC; ++b) asm volatile("" ::"v"(gv[l][b]));
 #pragma unroll
             for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(cvb[k]));
-            store_row(lrow);
+            store_row(w.lrow);
             __syncthreads();  // before the next row writes sOut
             if (!has_next) break;
-            lrow = nrow;
-            nrow = nnrow;
-            dsc = dsc_n;
-            dsc_n = dsc_nn;
-#pragma unroll
-            for (int b = 0; b < kMaxBlocks; ++b) idx[b] = idx_n[b];
+            w.advance(nx);
         }
     }
 }
@@ -928,37 +791,20 @@ hipError_t sorted_expand(hipStream_t s, GridSpec gs, int nrows_local, const Sort
     if (!tables_apply(gs) || gs.W > sorted_max_width() || nl < 1 || nl > lmax) return hipErrorInvalidValue;
     if (nrows_local <= 0) return hipSuccess;
     const size_t shm = (size_t)((gs.W + 2) & ~1) * sizeof(double) + (size_t)lmax * gs.W * sizeof(float);
-    int ncu = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int grid = std::max(1, std::min(nrows_local, ncu));  // one 512-thread workgroup per CU (registers, LDS)
-#define NLE_SX1(NCV, LV, RECV)                                                                                         \
-    {                                                                                                                  \
-        if (shm > 48 * 1024) {                                                                                         \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sorted_expand<NCV, LV, RECV>),         \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                 \
-            if (ea != hipSuccess) return ea;                                                                           \
-        }                                                                                                              \
-        hipLaunchKernelGGL((k_sorted_expand<NCV, LV, RECV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc, \
-                           gs, nrows_local, sr.E, d_g, gstride, nl, d_cvec, d_out, ostride, sr.kappa, round8 ? 1 : 0); \
-    }
-#define NLE_SX(NCV)                                                                                                    \
-    case NCV:                                                                                                          \
-        if constexpr ((NCV) <= 12) {                                                                                   \
-            if (lmax == kExpLayers) NLE_SX1(NCV, kExpLayers, false) else NLE_SX1(NCV, 2, false)                        \
-        } else {                                                                                                       \
-            if (sr.rec) NLE_SX1(NCV, 2, true) else NLE_SX1(NCV, 2, false)                                              \
-        }                                                                                                              \
-        break;
-    switch (nC) {
-        NLE_SX(1) NLE_SX(2) NLE_SX(3) NLE_SX(4) NLE_SX(5) NLE_SX(6) NLE_SX(7) NLE_SX(8) NLE_SX(9) NLE_SX(10) NLE_SX(11)
-        NLE_SX(12) NLE_SX(13) NLE_SX(14) NLE_SX(15) NLE_SX(16) NLE_SX(17) NLE_SX(18) NLE_SX(19) NLE_SX(20) NLE_SX(21)
-        NLE_SX(22) NLE_SX(23) NLE_SX(24) NLE_SX(25) NLE_SX(26) NLE_SX(27) NLE_SX(28) NLE_SX(29) NLE_SX(30) NLE_SX(31)
-        NLE_SX(32) NLE_SX(33) NLE_SX(34) NLE_SX(35) NLE_SX(36)
-        default: return hipErrorInvalidValue;
-    }
-#undef NLE_SX
-#undef NLE_SX1
-    return hipGetLastError();
+    SortedRows one = sr;
+    one.wgs_per_cu = 1;  // one 512-thread workgroup per CU (registers, LDS), whatever the pass kernels run at
+    const int grid = sorted_grid(nrows_local, one);
+    const auto run = [&](auto kernel) {
+        return launch(kernel, dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc, gs, nrows_local, sr.E, d_g, gstride, nl,
+                      d_cvec, d_out, ostride, sr.kappa, round8 ? 1 : 0);
+    };
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_columns<1, 36>(nC, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        if constexpr (NC <= 12) e = lmax == kExpLayers ? run(k_sorted_expand<NC, kExpLayers, false>) : run(k_sorted_expand<NC, 2, false>);
+        else e = sr.rec ? run(k_sorted_expand<NC, 2, true>) : run(k_sorted_expand<NC, 2, false>);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------ Gram, per-row pair tables (nC <= 11: one launch)
@@ -1129,32 +975,19 @@ bool sorted_gsum_ok(GridSpec gs, double hx) {
 
 hipError_t sorted_gram_sums(hipStream_t s, GridSpec gs, int nrows_local, const SortedRows& sr, const double* d_cvec,
                             double* d_Aout) {
-    const int nC = gs.nSelCols, nt = 2 * nC - 1;
+    const int nC = gs.nSelCols;
     if (!tables_apply(gs) || gs.W > sorted_max_width() || sr.E2 == nullptr) return hipErrorInvalidValue;
     if (nrows_local <= 0) return hipSuccess;
     const double cs = gs.colStep, hx = sr.hx;
     const double theta = 2.0 * cs / (hx * hx), kappa1 = std::exp(-cs * cs / (2.0 * hx * hx));
     const size_t shm = sorted_lds_bytes(gs.W, 11) + (size_t)((((gs.W >> 6) + 2) & ~1) + 64) * sizeof(double);
     const int grid = sorted_grid(nrows_local, sr);
-#define NLE_GS(NTV)                                                                                                      \
-    case NTV: {                                                                                                          \
-        if (shm > 48 * 1024) {                                                                                           \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sorted_gsum<NTV>),                       \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                   \
-            if (ea != hipSuccess) return ea;                                                                             \
-        }                                                                                                                \
-        hipLaunchKernelGGL((k_sorted_gsum<NTV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc, sr.first, gs,  \
-                           nrows_local, sr.E2, d_cvec, d_Aout, theta, kappa1);                                           \
-    } break;
-    switch (nt) {
-        NLE_GS(1) NLE_GS(3) NLE_GS(5) NLE_GS(7) NLE_GS(9) NLE_GS(11) NLE_GS(13) NLE_GS(15) NLE_GS(17) NLE_GS(19) NLE_GS(21)
-        NLE_GS(23) NLE_GS(25) NLE_GS(27) NLE_GS(29) NLE_GS(31) NLE_GS(33) NLE_GS(35) NLE_GS(37) NLE_GS(39) NLE_GS(41)
-        NLE_GS(43) NLE_GS(45) NLE_GS(47) NLE_GS(49) NLE_GS(51) NLE_GS(53) NLE_GS(55) NLE_GS(57) NLE_GS(59) NLE_GS(61)
-        NLE_GS(63) NLE_GS(65) NLE_GS(67) NLE_GS(69) NLE_GS(71)
-        default: return hipErrorInvalidValue;
-    }
-#undef NLE_GS
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_columns<1, 36>(nC, [&](auto nc) {
+        e = launch(k_sorted_gsum<2 * decltype(nc)::value - 1>, dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc, sr.first, gs,
+                   nrows_local, sr.E2, d_cvec, d_Aout, theta, kappa1);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------ Gram pair tables for wider grids (12 <= nC <= 36)
@@ -1252,51 +1085,21 @@ hipError_t sorted_gram_rows(hipStream_t s, GridSpec gs, int nrows_local, const S
     if (nrows_local <= 0) return hipSuccess;
     const size_t shm = sorted_lds_bytes(gs.W, 11);
     const int grid = sorted_grid(nrows_local, sr);
-    if (nC > 11) {
-        const int bb = gram_wide_bb(nC);
-#define NLE_SGW(NCV)                                                                                                    \
-    case NCV: {                                                                                                         \
-        if (shm > 48 * 1024) {                                                                                          \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sorted_gram_wide<NCV>),                 \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                  \
-            if (ea != hipSuccess) return ea;                                                                            \
-        }                                                                                                               \
-        for (int b0 = 0; b0 < nC; b0 += bb)                                                                             \
-            hipLaunchKernelGGL((k_sorted_gram_wide<NCV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc,     \
-                               sr.first, gs, nrows_local, sr.E, d_cvec, d_Aout, sr.rec ? 1 : 0, sr.kappa, b0,            \
-                               std::min(bb, nC - b0));                                                                  \
-    } break;
-        switch (nC) {
-            NLE_SGW(12) NLE_SGW(13) NLE_SGW(14) NLE_SGW(15) NLE_SGW(16) NLE_SGW(17) NLE_SGW(18) NLE_SGW(19) NLE_SGW(20)
-            NLE_SGW(21) NLE_SGW(22) NLE_SGW(23) NLE_SGW(24) NLE_SGW(25) NLE_SGW(26) NLE_SGW(27) NLE_SGW(28) NLE_SGW(29)
-            NLE_SGW(30) NLE_SGW(31) NLE_SGW(32) NLE_SGW(33) NLE_SGW(34) NLE_SGW(35) NLE_SGW(36)
-            default: return hipErrorInvalidValue;
-        }
-#undef NLE_SGW
-        return hipGetLastError();
-    }
-#define NLE_SG1(NCV, RECV)                                                                                              \
-    {                                                                                                                   \
-        if (shm > 48 * 1024) {                                                                                          \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sorted_gram<NCV, RECV>),                \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                  \
-            if (ea != hipSuccess) return ea;                                                                            \
-        }                                                                                                               \
-        hipLaunchKernelGGL((k_sorted_gram<NCV, RECV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc,        \
-                           sr.first, gs, nrows_local, sr.E, d_cvec, d_Aout, sr.kappa);                                  \
-    }
-#define NLE_SG(NCV)                                                                                                     \
-    case NCV:                                                                                                           \
-        if (sr.rec) return hipErrorInvalidValue; /* up to 11 columns: table form only */                                 \
-        NLE_SG1(NCV, false)                                                                                             \
-        break;
-    switch (nC) {
-        NLE_SG(1) NLE_SG(2) NLE_SG(3) NLE_SG(4) NLE_SG(5) NLE_SG(6) NLE_SG(7) NLE_SG(8) NLE_SG(9) NLE_SG(10) NLE_SG(11)
-        default: return hipErrorInvalidValue;
-    }
-#undef NLE_SG
-#undef NLE_SG1
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;
+    // up to 11 columns one launch and the table form only; beyond, gram_wide_bb rows of the pair triangle per launch
+    if (!dispatch_columns<1, 11>(nC, [&](auto nc) {
+            if (!sr.rec)
+                e = launch(k_sorted_gram<decltype(nc)::value, false>, dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc,
+                           sr.first, gs, nrows_local, sr.E, d_cvec, d_Aout, sr.kappa);
+        }))
+        dispatch_columns<12, 36>(nC, [&](auto nc) {
+            constexpr int NC = decltype(nc)::value, bb = gram_wide_bb(NC);
+            e = hipSuccess;
+            for (int b0 = 0; b0 < NC && e == hipSuccess; b0 += bb)
+                e = launch(k_sorted_gram_wide<NC>, dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc, sr.first, gs,
+                           nrows_local, sr.E, d_cvec, d_Aout, sr.rec ? 1 : 0, sr.kappa, b0, std::min(bb, NC - b0));
+        });
+    return e;
 }
 
 }  // namespace nlek

@@ -39,53 +39,29 @@ __global__ __launch_bounds__(kT, planes_waves_per_simd(NC, NP)) void k_sorted_re
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int n = kLevels * NC;
-    constexpr int SL = NC < 11 ? NC : 11;  // sums combined per slice, as k_sorted_pass
-    constexpr int PS = SL | 1;
     constexpr bool REC = CF == 1, MOM = CF == 2;
     static_assert(!MOM || NC > 1, "the moment form needs two columns");
     const int W = gs.W;
-    const size_t pitch = sorted_row_pitch(W);
-    double* sE = reinterpret_cast<double*>(smem_raw);
-    double* sP = sE + ((W + 2) & ~1);
-    unsigned short* sfirst = reinterpret_cast<unsigned short*>(sP + (size_t)kT * PS);  // [2][260], rows alternate
-    double* sCk = reinterpret_cast<double*>(sfirst + 2 * 260);                          // [NC] C_b = kappa^(b (b - 1) / 2)
+    const RowLds lds(smem_raw, W, kPassStride<NC>);
+    double* const sP = lds.sP;
+    unsigned short* const sfirst = lds.sfirst;
+    double* const sCk = lds.sCk;
     const int tid = threadIdx.x;
-    for (int i = tid; i <= W; i += kT) sE[i] = Etab[i];
-    if (MOM && tid == 0) {
-        double ck = 1.0, kp = 1.0;  // C_{b+1} = C_b kappa^b
-        for (int b = 0; b < NC; ++b) {
-            sCk[b] = ck;
-            ck *= kp;
-            kp *= kappa;
-        }
-    }
+    fill_dist_table(lds.sE, Etab, W, tid);
+    if (MOM) fill_moment_factors<NC>(sCk, kappa, tid);
     const int cb0 = gs.colOff, cs = gs.colStep;
-    const unsigned sEa = lds_addr(sE);
+    const unsigned sEa = lds_addr(lds.sE);
 
-    const int G = (int)gridDim.x;  // <= nrows
-    int lrow = blockIdx.x, nrow = lrow + G;
-    uint2 dsc = desc[(size_t)lrow * kT + tid];
-    uint2 dsc_n = dsc;
-    if (nrow < nrows) dsc_n = desc[(size_t)nrow * kT + tid];
-    if (tid < 258) sfirst[tid] = first[(size_t)lrow * 258 + tid];
-    uint2 idx[kMaxBlocks];
-    auto load_idx = [&](uint2 (&dst)[kMaxBlocks], const int row, const uint2 d) {
-        const uint2* slot = reinterpret_cast<const uint2*>(scol + (size_t)row * pitch + (size_t)tid * dsc_chp(d));
-        const int ln = dsc_len(d);
-#pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) {  // blocks past the chunk: column 0 (the wave may walk further than this lane)
-            uint2 v = make_uint2(0u, 0u);
-            if (4 * b < ln) v = slot[b];
-            dst[b] = v;
-        }
-    };
-    load_idx(idx, lrow, dsc);
+    RowWalk w(scol, desc, W, nrows, tid);
+    w.start([&] {
+        if (tid < 258) sfirst[tid] = first[(size_t)w.lrow * 258 + tid];
+    });
     __syncthreads();  // sE, sfirst, sCk visible
     for (int par = 0;; par ^= 1) {
-        const bool has_next = nrow < nrows;
-        const int nnrow = nrow + G;
+        const bool has_next = w.has_next();
+        const int lrow = w.lrow;
         const unsigned short* sfc = sfirst + par * 260;
-        const int len = dsc_len(dsc);
+        const int len = dsc_len(w.dsc);
         double acc[NP][NC];
 #pragma unroll
         for (int m = 0; m < NP; ++m)
@@ -95,15 +71,10 @@ __global__ __launch_bounds__(kT, planes_waves_per_simd(NC, NP)) void k_sorted_re
         const float* xv_row[NP];
 #pragma unroll
         for (int m = 0; m < NP; ++m) xv_row[m] = pg.x[m] + (size_t)(row0 + lrow) * W;
-        // in flight under the pixel loop: the descriptor of the row after next, the next row's first-chunk table and indices
-        uint2 dsc_nn = dsc_n;
+        // in flight under the pixel loop, with the walk's requests: the next row's first-chunk table
         unsigned short sf_n = 0;
-        uint2 idx_n[kMaxBlocks];
-        if (has_next) {
-            if (nnrow < nrows) dsc_nn = desc[(size_t)nnrow * kT + tid];
-            sf_n = first[(size_t)nrow * 258 + (tid < 258 ? tid : 257)];
-            load_idx(idx_n, nrow, dsc_n);
-        }
+        RowWalk::Next nx;
+        w.request_next(nx, [&] { sf_n = first[(size_t)w.nrow * 258 + (tid < 258 ? tid : 257)]; });
         // One pixel at a time for all planes of the group.  The plane-independent part first, exactly k_sorted_pass's; then
         // per plane y = c x and the sums.  Lanes past their own chunk work on column 0 and add exact zeros.
         auto pixel_mom = [&](const unsigned c8, const int at) {
@@ -154,23 +125,10 @@ __global__ __launch_bounds__(kT, planes_waves_per_simd(NC, NP)) void k_sorted_re
                 for (int m = 0; m < NP; ++m) acc[m][b] = fma(ev, y[m], acc[m][b]);
             });
         };
-        int wlen = len;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) wlen = max(wlen, __shfl_xor(wlen, off));
-        wlen = __builtin_amdgcn_readfirstlane(wlen);
-#pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) {
-            if (4 * b >= wlen) break;
-            const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (4 * b + k < wlen) {
-                    if constexpr (MOM) pixel_mom(cs4[k], 4 * b + k);
-                    else pixel(cs4[k], 4 * b + k < len);
-                    NLE_PIXEL_FENCE();
-                }
-            }
-        }
+        for_chunk_pixels(w.idx, wave_max_len(len), [&](const unsigned c8, const int at) {
+            if constexpr (MOM) pixel_mom(c8, at);
+            else pixel(c8, at < len);
+        });
         if constexpr (MOM) {
 #pragma unroll
             for (int m = 0; m < NP; ++m)
@@ -178,6 +136,7 @@ __global__ __launch_bounds__(kT, planes_waves_per_simd(NC, NP)) void k_sorted_re
                 for (int b = 2; b < NC; ++b) acc[m][b] = acc[m][b] * sCk[b];  // C_0 = C_1 = 1
         }
         __builtin_amdgcn_s_setprio(3);
+        constexpr int SL = kPassSlice<NC>, PS = kPassStride<NC>;  // sums combined per slice, as k_sorted_pass
         // The combine of k_sorted_pass, plane after plane through the same sP: the partial sums of a level's chunks are
         // written to LDS and every table entry is summed by ONE thread in chunk order, then stored.  No atomics.
         const int nlev = lev_nt * 16, xlo = lev_t0 * 16;
@@ -192,9 +151,8 @@ __global__ __launch_bounds__(kT, planes_waves_per_simd(NC, NP)) void k_sorted_re
                 __syncthreads();
                 if (m == 0 && s0 == 0) {
                     // take the next row's loads in before the table stores below (all lanes), as k_sorted_pass does
-                    asm volatile("" ::"v"(sf_n), "v"(dsc_nn.x), "v"(dsc_nn.y));
-#pragma unroll
-                    for (int b = 0; b < kMaxBlocks; ++b) asm volatile("" ::"v"(idx_n[b].x), "v"(idx_n[b].y));
+                    asm volatile("" ::"v"(sf_n));
+                    w.take_in(nx);
                     // next row's first-chunk table: its last readers left before the previous row's end barrier, its next
                     // readers come after the barriers of the next row's combine
                     if (has_next && tid < 258) sfirst[(par ^ 1) * 260 + tid] = sf_n;
@@ -213,12 +171,7 @@ __global__ __launch_bounds__(kT, planes_waves_per_simd(NC, NP)) void k_sorted_re
         }
         __builtin_amdgcn_s_setprio(0);
         if (!has_next) break;
-        lrow = nrow;
-        nrow = nnrow;
-        dsc = dsc_n;
-        dsc_n = dsc_nn;
-#pragma unroll
-        for (int b = 0; b < kMaxBlocks; ++b) idx[b] = idx_n[b];
+        w.advance(nx);
     }
 }
 
@@ -237,52 +190,33 @@ hipError_t sorted_reduce_planes(hipStream_t s, GridSpec gs, int row0, int nrows_
     SortedRows one = sr;
     if (planes_waves_per_simd(nC, np) < 4) one.wgs_per_cu = 1;
     const int grid = sorted_grid(nrows_local, one);
-#define NLE_RP1(NCV, CFV, NPV)                                                                                            \
-    {                                                                                                                     \
-        if (shm > 48 * 1024) {                                                                                            \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sorted_reduce_planes<NCV, CFV, NPV>),     \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                    \
-            if (ea != hipSuccess) return ea;                                                                              \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((k_sorted_reduce_planes<NCV, CFV, NPV>), dim3((unsigned)grid), dim3(kT), shm, s, sr.scol,       \
-                           sr.desc, sr.first, gs, row0, nrows_local, sr.E, d_cvec, pg, sr.kappa, lev_t0, lev_nt);         \
-    }
-    // NP: 2, 3 or 4 up to 12 columns, 2 beyond
-#define NLE_RPN(NCV, CFV)                                                                                                 \
-    {                                                                                                                     \
-        if constexpr ((NCV) <= 12) {                                                                                      \
-            if (np == 4) NLE_RP1(NCV, CFV, 4) else if (np == 3) NLE_RP1(NCV, CFV, 3) else NLE_RP1(NCV, CFV, 2)            \
-        } else {                                                                                                          \
-            NLE_RP1(NCV, CFV, 2)                                                                                          \
-        }                                                                                                                 \
-    }
-    // the form a single call would take: sorted_pass's dispatch on sr.mom / sr.rec
-#define NLE_RP(NCV)                                                                                                       \
-    case NCV:                                                                                                             \
-        if constexpr ((NCV) > 1) {                                                                                        \
-            if (sr.mom) {                                                                                                 \
-                NLE_RPN(NCV, 2)                                                                                           \
-                break;                                                                                                    \
-            }                                                                                                             \
-        }                                                                                                                 \
-        if constexpr ((NCV) > 12) {                                                                                       \
-            if (sr.rec) NLE_RPN(NCV, 1) else NLE_RPN(NCV, 0)                                                              \
-        } else {                                                                                                          \
-            if (sr.rec) return hipErrorInvalidValue;                                                                      \
-            NLE_RPN(NCV, 0)                                                                                               \
-        }                                                                                                                 \
-        break;
-    switch (nC) {
-        NLE_RP(1) NLE_RP(2) NLE_RP(3) NLE_RP(4) NLE_RP(5) NLE_RP(6) NLE_RP(7) NLE_RP(8) NLE_RP(9) NLE_RP(10) NLE_RP(11)
-        NLE_RP(12) NLE_RP(13) NLE_RP(14) NLE_RP(15) NLE_RP(16) NLE_RP(17) NLE_RP(18) NLE_RP(19) NLE_RP(20)
-        NLE_RP(21) NLE_RP(22) NLE_RP(23) NLE_RP(24) NLE_RP(25) NLE_RP(26) NLE_RP(27) NLE_RP(28) NLE_RP(29)
-        NLE_RP(30) NLE_RP(31) NLE_RP(32) NLE_RP(33) NLE_RP(34) NLE_RP(35) NLE_RP(36)
-        default: return hipErrorInvalidValue;
-    }
-#undef NLE_RP
-#undef NLE_RPN
-#undef NLE_RP1
-    return hipGetLastError();
+    const auto run = [&](auto kernel) {
+        return launch(kernel, dim3((unsigned)grid), dim3(kT), shm, s, sr.scol, sr.desc, sr.first, gs, row0, nrows_local, sr.E, d_cvec,
+                      pg, sr.kappa, lev_t0, lev_nt);
+    };
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_columns<1, 36>(nC, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        // NP: 2, 3 or 4 up to 12 columns, 2 beyond
+        const auto planes = [&](auto cf) {
+            constexpr int CF = decltype(cf)::value;
+            if constexpr (NC <= 12) {
+                if (np == 4) return run(k_sorted_reduce_planes<NC, CF, 4>);
+                if (np == 3) return run(k_sorted_reduce_planes<NC, CF, 3>);
+            }
+            return run(k_sorted_reduce_planes<NC, CF, 2>);
+        };
+        // the form a single call would take: sorted_pass's rules on sr.mom / sr.rec
+        if constexpr (NC > 1) {
+            if (sr.mom) {
+                e = planes(std::integral_constant<int, 2>{});
+                return;
+            }
+        }
+        if constexpr (NC > 12) e = sr.rec ? planes(std::integral_constant<int, 1>{}) : planes(std::integral_constant<int, 0>{});
+        else if (!sr.rec) e = planes(std::integral_constant<int, 0>{});
+    });
+    return e;
 }
 
 }  // namespace nlek

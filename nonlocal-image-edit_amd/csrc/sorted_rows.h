@@ -1,8 +1,15 @@
-// Device helpers and layout constants of the level-sorted rows, shared by the kernels that walk them (sorted.hip,
-// sorted_planes.hip): the LDS distance table and the column factors of a pixel, the chunk descriptor, the slot pitch of a
-// row and the LDS layout of the pass kernels.  Not installed, not part of kernels.h: only those two files include it.
+// The level-sorted rows and their walk, shared by the kernels that walk them (sorted.hip, sorted_planes.hip).  This header
+// owns the layout -- the chunk descriptor, the slot pitch of a row, the LDS layout of the pass kernels -- and every step of
+// the walk that does not depend on who walks: the LDS distance table and the column factors of a pixel, the index load of a
+// chunk, the software pipeline of a persistent workgroup over its rows (RowWalk), the wave's chunk bound, the per-pixel loop
+// over a chunk and the LDS carve-up with its fills.  A kernel brings its per-pixel arithmetic, what it prefetches beyond the
+// walk and its combine.  (The level sum of the two pass kernels and the loop and store tail of the three Gram kernels are
+// still written out in each: as shared functions they changed scratch or occupancy of some instantiations,
+// profiles/r15_sorted_rows_refactor.txt.)
+// Not installed, not part of kernels.h: only those two files include it.
 #pragma once
 #include "kernels.h"
+#include "launch.h"
 
 #define NLE_PIXEL_FENCE() __builtin_amdgcn_sched_barrier(0)
 
@@ -78,6 +85,145 @@ __device__ __forceinline__ int dsc_chp(uint2 d) { return (int)(d.y >> 16); }
 // quadratic factors of the moment form of k_sorted_pass)
 __host__ __device__ inline size_t sorted_lds_bytes(int W, int ps) {
     return ((size_t)((W + 2) & ~1) + (size_t)kT * ps + 40) * sizeof(double) + 2 * 260 * sizeof(unsigned short);
+}
+
+template <int NC>
+constexpr int kPassSlice = NC < 11 ? NC : 11;  // sums of the pass kernels combined at a time (slices of the nC sums when nC > 11)
+template <int NC>
+constexpr int kPassStride = kPassSlice<NC> | 1;  // PS, odd: consecutive threads' rows of sP start on different banks
+struct RowLds {
+    double* sE;
+    double* sP;
+    unsigned short* sfirst;  // [2][260], rows alternate
+    double* sCk;             // [NC] C_b = kappa^(b (b - 1) / 2)
+    __device__ __forceinline__ RowLds(unsigned char* smem, int W, int ps) {
+        sE = reinterpret_cast<double*>(smem);
+        sP = sE + ((W + 2) & ~1);
+        sfirst = reinterpret_cast<unsigned short*>(sP + (size_t)kT * ps);
+        sCk = reinterpret_cast<double*>(sfirst + 2 * 260);
+    }
+};
+__device__ __forceinline__ void fill_dist_table(double* sE, const double* __restrict__ Etab, int W, int tid) {
+    for (int i = tid; i <= W; i += kT) sE[i] = Etab[i];
+}
+template <int NC>
+__device__ __forceinline__ void fill_moment_factors(double* sCk, double kappa, int tid) {
+    if (tid == 0) {
+        double ck = 1.0, kp = 1.0;  // C_{b+1} = C_b kappa^b
+        for (int b = 0; b < NC; ++b) {
+            sCk[b] = ck;
+            ck *= kp;
+            kp *= kappa;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ the walk
+// all indices of a chunk (<= kMaxBlocks blocks of four) into registers: the pixel loops themselves load nothing
+__device__ __forceinline__ void load_chunk_idx(uint2 (&dst)[kMaxBlocks], const unsigned short* __restrict__ scol, size_t pitch,
+                                               int row, int tid, uint2 d) {
+    const uint2* slot = reinterpret_cast<const uint2*>(scol + (size_t)row * pitch + (size_t)tid * dsc_chp(d));
+    const int ln = dsc_len(d);
+#pragma unroll
+    for (int b = 0; b < kMaxBlocks; ++b) {  // blocks past the chunk: column 0 (the wave may walk further than this lane)
+        uint2 v = make_uint2(0u, 0u);
+        if (4 * b < ln) v = slot[b];
+        dst[b] = v;
+    }
+}
+
+// Software pipeline over the rows of a persistent workgroup (rows blockIdx.x, + gridDim.x, ...; gridDim.x <= nrows):
+// everything a row needs from global memory is requested while the PREVIOUS row is being worked on -- its indices one row
+// ahead and, because their address needs the row's chunk descriptor, the descriptor two rows ahead -- and taken in before
+// that row's stores.  Nothing foreign is pending during the pixel loop, so its waits (the counter retires in order) are exact.
+//     RowWalk w(...);  w.start(more);
+//     for (;;) { RowWalk::Next nx;  w.request_next(nx, more);  <pixel loop over w.idx>  ... barrier, w.take_in(nx), stores ...
+//                if (!w.has_next()) break;  w.advance(nx); }
+// `more`: what else the kernel wants requested, between the descriptor and the indices (loads return in that order).
+struct RowWalk {
+    const unsigned short* __restrict__ scol;
+    const uint2* __restrict__ desc;
+    const size_t pitch;
+    const int nrows, tid, G;
+    int lrow, nrow;
+    uint2 dsc, dsc_n;        // this row's chunk of the thread and the next row's
+    uint2 idx[kMaxBlocks];   // this row's indices
+    struct Next {            // in flight under the pixel loop
+        int nnrow;
+        uint2 dsc_nn;
+        uint2 idx[kMaxBlocks];
+    };
+    __device__ __forceinline__ RowWalk(const unsigned short* __restrict__ scol_, const uint2* __restrict__ desc_, int W, int nrows_,
+                                       int tid_)
+        : scol(scol_), desc(desc_), pitch(sorted_row_pitch(W)), nrows(nrows_), tid(tid_), G((int)gridDim.x) {}
+    __device__ __forceinline__ bool has_next() const { return nrow < nrows; }
+    // component by component: an 8-byte copy between members of one struct becomes a 64-bit integer, kept whole in
+    // registers where only a half is still needed
+    static __device__ __forceinline__ void set(uint2& d, const uint2 s) { d.x = s.x, d.y = s.y; }
+    template <class More>
+    __device__ __forceinline__ void start(More&& more) {
+        lrow = blockIdx.x, nrow = lrow + G;
+        set(dsc, desc[(size_t)lrow * kT + tid]);
+        set(dsc_n, dsc);
+        if (nrow < nrows) set(dsc_n, desc[(size_t)nrow * kT + tid]);
+        more();
+        load_chunk_idx(idx, scol, pitch, lrow, tid, dsc);
+    }
+    // requested BEFORE the pixel loop, in flight under it (the loop has no wait on the memory counter): the descriptor of
+    // the row after next and the next row's indices
+    template <class More>
+    __device__ __forceinline__ void request_next(Next& nx, More&& more) const {
+        nx.nnrow = nrow + G;
+        set(nx.dsc_nn, dsc_n);
+        if (has_next()) {
+            if (nx.nnrow < nrows) set(nx.dsc_nn, desc[(size_t)nx.nnrow * kT + tid]);
+            more();
+            load_chunk_idx(nx.idx, scol, pitch, nrow, tid, dsc_n);
+        }
+    }
+    // Were the requested loads still pending behind the stores that end a row, the next row's first pixel would wait for
+    // those stores to be acknowledged.  Take them in before (all lanes: a divergent use would leave a load pending for the
+    // others).
+    __device__ __forceinline__ void take_in(const Next& nx) const {
+        asm volatile("" ::"v"(nx.dsc_nn.x), "v"(nx.dsc_nn.y));
+#pragma unroll
+        for (int b = 0; b < kMaxBlocks; ++b) asm volatile("" ::"v"(nx.idx[b].x), "v"(nx.idx[b].y));
+    }
+    __device__ __forceinline__ void advance(const Next& nx) {
+        lrow = nrow;
+        nrow = nx.nnrow;
+        set(dsc, dsc_n);
+        set(dsc_n, nx.dsc_nn);
+#pragma unroll
+        for (int b = 0; b < kMaxBlocks; ++b) idx[b] = nx.idx[b];
+    }
+};
+
+// the longest chunk of the WAVE: a scalar bound for the pixel loop, so that a wave whose chunks are all short skips the
+// rest without per-lane bookkeeping
+__device__ __forceinline__ int wave_max_len(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
+// pixel(c8, at) for the pixels of a chunk up to the wave's bound, `at` the pixel's place in the chunk.  One pixel at a time:
+// the scheduling barrier keeps the unrolled bodies from being interleaved (the column factors of one pixel fill the
+// registers).  Lanes past their own chunk (and the padding of the last block) get column 0 and must add exact zeros.
+template <class Pixel>
+__device__ __forceinline__ void for_chunk_pixels(const uint2 (&idx)[kMaxBlocks], int wlen, Pixel&& pixel) {
+#pragma unroll
+    for (int b = 0; b < kMaxBlocks; ++b) {
+        if (4 * b >= wlen) break;
+        const unsigned cs4[4] = {idx[b].x & 0xffffu, idx[b].x >> 16, idx[b].y & 0xffffu, idx[b].y >> 16};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (4 * b + k < wlen) {
+                pixel(cs4[k], 4 * b + k);
+                NLE_PIXEL_FENCE();
+            }
+        }
+    }
 }
 
 // workgroups of a persistent pass over `nrows` rows: sr.wgs_per_cu per compute unit, at most one per row

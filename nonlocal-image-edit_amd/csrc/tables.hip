@@ -1,6 +1,7 @@
 // The table formulation: the tiled Sinkhorn pass, the sample-space apply and the Gram on look-up tables
 // of the quantised plane; the composite launchers take one nlek::TableView (kernels.h).  Level-sorted pixel halves: sorted.hip.
 #include "kernels.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -576,32 +577,13 @@ hipError_t sink_hist_tiled(hipStream_t s, int mode, const TableView& v, const do
         if (ep != hipSuccess) return ep;
     } else {
         Scope sc(obs, SUB_HIST_PIX);
-#define NLE_HP(NCV)                                                                                                 \
-    case NCV:                                                                                                       \
-        hipLaunchKernelGGL((k_hist_pix<NCV>), dim3((unsigned)nrows_local), dim3(kPixThreads),                      \
-                           (size_t)2 * kLevels * ((NCV) | 1) * sizeof(double), s, mode,                            \
-                           v.lum, gs, row0, v.ecT, d_g, eps, d_ybuf, d_h, d_cvec, d_xvec);                          \
-        break;
-        if (nC > 11) {
-            hipError_t ea = hipSuccess;
-            switch (nC) {  // > 64 KB of LDS: raise the limit of the instantiation that is about to run
-#define NLE_HPA(NCV) case NCV: ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist_pix<NCV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * kLevels * ((NCV) | 1) * sizeof(double))); break;
-                NLE_HPA(12) NLE_HPA(13) NLE_HPA(14) NLE_HPA(15) NLE_HPA(16) NLE_HPA(17) NLE_HPA(18) NLE_HPA(19) NLE_HPA(20)
-                NLE_HPA(21) NLE_HPA(22) NLE_HPA(23) NLE_HPA(24) NLE_HPA(25) NLE_HPA(26) NLE_HPA(27) NLE_HPA(28) NLE_HPA(29)
-                NLE_HPA(30) NLE_HPA(31) NLE_HPA(32) NLE_HPA(33) NLE_HPA(34) NLE_HPA(35) NLE_HPA(36)
-#undef NLE_HPA
-                default: break;
-            }
-            if (ea != hipSuccess) return ea;
-        }
-        switch (nC) {
-            NLE_HP(1) NLE_HP(2) NLE_HP(3) NLE_HP(4) NLE_HP(5) NLE_HP(6) NLE_HP(7) NLE_HP(8) NLE_HP(9) NLE_HP(10) NLE_HP(11)
-            NLE_HP(12) NLE_HP(13) NLE_HP(14) NLE_HP(15) NLE_HP(16) NLE_HP(17) NLE_HP(18) NLE_HP(19) NLE_HP(20)
-            NLE_HP(21) NLE_HP(22) NLE_HP(23) NLE_HP(24) NLE_HP(25) NLE_HP(26) NLE_HP(27) NLE_HP(28) NLE_HP(29)
-            NLE_HP(30) NLE_HP(31) NLE_HP(32) NLE_HP(33) NLE_HP(34) NLE_HP(35) NLE_HP(36)
-            default: return hipErrorInvalidValue;
-        }
-#undef NLE_HP
+        hipError_t ep = hipErrorInvalidValue;
+        dispatch_columns<1, 36>(nC, [&](auto nc) {
+            constexpr int NC = decltype(nc)::value;  // from 12 columns the two tables are beyond 48 KB of LDS
+            ep = launch(k_hist_pix<NC>, dim3((unsigned)nrows_local), dim3(kPixThreads), (size_t)2 * kLevels * (NC | 1) * sizeof(double),
+                        s, mode, v.lum, gs, row0, v.ecT, d_g, eps, d_ybuf, d_h, d_cvec, d_xvec);
+        });
+        if (ep != hipSuccess) return ep;
     }
     Scope sc(obs, SUB_HIST_HH);
     return launch_hist_hh_z(s, v, d_h, d_HH, d_z, d_run_if);
@@ -665,27 +647,14 @@ hipError_t apply_hist_layers(hipStream_t s, const TableView& v, const double* d_
         if (obs) obs->end();
         return ex;
     }
-#define NLE_HD(NCV)                                                                                                  \
-    case NCV: {                                                                                                      \
-        const size_t shm_d = (size_t)nl * kLevels * ((NCV) | 1) * sizeof(double);                                    \
-        if (shm_d > 48 * 1024) {                                                                                     \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist_dot<NCV>),                      \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_d);             \
-            if (ea != hipSuccess) return ea;                                                                         \
-        }                                                                                                            \
-        hipLaunchKernelGGL((k_hist_dot<NCV>), dim3((unsigned)nrows_local), dim3(kDotThreads), shm_d, s, v.lum, gs,   \
-                           row0, v.ecT, d_ws, gstride, nl, v.cvec, d_out, ostride, round8 ? 1 : 0);                  \
-    } break;
-    switch (nC) {
-        NLE_HD(1) NLE_HD(2) NLE_HD(3) NLE_HD(4) NLE_HD(5) NLE_HD(6) NLE_HD(7) NLE_HD(8) NLE_HD(9) NLE_HD(10) NLE_HD(11)
-        NLE_HD(12) NLE_HD(13) NLE_HD(14) NLE_HD(15) NLE_HD(16) NLE_HD(17) NLE_HD(18) NLE_HD(19) NLE_HD(20)
-        NLE_HD(21) NLE_HD(22) NLE_HD(23) NLE_HD(24) NLE_HD(25) NLE_HD(26) NLE_HD(27) NLE_HD(28) NLE_HD(29)
-        NLE_HD(30) NLE_HD(31) NLE_HD(32) NLE_HD(33) NLE_HD(34) NLE_HD(35) NLE_HD(36)
-        default: return hipErrorInvalidValue;
-    }
-#undef NLE_HD
+    hipError_t ed = hipErrorInvalidValue;
+    dispatch_columns<1, 36>(nC, [&](auto nc) {
+        constexpr int NC = decltype(nc)::value;
+        ed = launch(k_hist_dot<NC>, dim3((unsigned)nrows_local), dim3(kDotThreads), (size_t)nl * kLevels * (NC | 1) * sizeof(double), s,
+                    v.lum, gs, row0, v.ecT, d_ws, gstride, nl, v.cvec, d_out, ostride, round8 ? 1 : 0);
+    });
     if (obs) obs->end();
-    return hipGetLastError();
+    return ed;
 }
 
 hipError_t apply_small(hipStream_t s, int p, int K, int ldk, int L, int ldw, const double* d_m, const double* d_D,
