@@ -22,7 +22,7 @@ LIBDIR = os.path.join(HERE, "lib")
 BINDIR = os.path.join(HERE, "bin")
 LIB = os.path.join(LIBDIR, "libnle_hip.so")
 
-LIB_SOURCES = ["kernels.hip", "tsgemm_bf16x3.hip", "fused.hip", "tables.hip", "sorted.hip", "sorted_planes.hip", "generic64.hip", "patch.hip", "sampler.hip", "exact.hip", "resid.hip", "tridiag.hip", "dense64.hip", "colour.hip", "region.hip", "pipeline.hip", "literal.hip", "sample_space.hip", "exact_train.hip", "samples.hip", "ortho.hip", "abi_ctx.hip", "devsolve.hip", "eigen_sym.cpp", "lab8_tables.cpp"]
+LIB_SOURCES = ["kernels.hip", "tsgemm_bf16x3.hip", "fused.hip", "tables.hip", "sorted.hip", "sorted_planes.hip", "generic64.hip", "patch.hip", "sampler.hip", "exact.hip", "resid.hip", "tridiag.hip", "dense64.hip", "colour.hip", "region.hip", "pipeline.hip", "literal.hip", "sample_space.hip", "exact_train.hip", "samples.hip", "ortho.hip", "abi_ctx.hip", "devsolve.hip", "eigen_sym.cpp", "eigen_reduce.cpp", "eigen_tridiag.cpp", "host_dense.cpp", "lanczos.cpp", "lab8_tables.cpp"]
 ARCH = "gfx950"
 
 

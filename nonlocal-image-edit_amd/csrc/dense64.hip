@@ -15,7 +15,7 @@
 //   potrf / trtri     blocked Cholesky factor and its inverse: 32-column panels (one kernel: every workgroup re-factors the
 //                     32 x 32 diagonal block in LDS and solves its own rows of the panel), trailing update and the inverse's
 //                     block rows on k_gemm64s (fp64 MFMA).
-// The eigenvectors of T for the wanted eigenvalues come from the host's inverse iteration (eigen_sym.cpp, O(n k)).
+// The eigenvectors of T for the wanted eigenvalues come from the host's inverse iteration (eigen_tridiag.cpp, O(n k)).
 #include "kernels.h"
 #include "handoff.h"
 
@@ -66,7 +66,7 @@ __device__ __forceinline__ double lane_bcast(double x, int src_lane /* wave-unif
 // ------------------------------------------------------------------------------------------------ tridiagonalisation
 // pub: (n - 2) records of 2 n + 2 doubles, one per step k: v_k (entries k+1 .. n-1, v_k[k+1] = 1), tau_k at [n], beta_k at
 // [n + 1], then y (entries k+1 .. n-1) from [n + 2].  H_k = I - tau_k v_k v_k^T; T = Q^T A Q, Q = H_0 H_1 .. H_{n-3};
-// d_out[i] = T(i, i), e_out[i] = T(i, i-1) (e_out[0] = 0): the layout eigen_sym.cpp's tridiagonal routines take.
+// d_out[i] = T(i, i), e_out[i] = T(i, i-1) (e_out[0] = 0): the layout eigen_tridiag.cpp's routines take.
 
 // ------------------------------------------------------------------------- tridiagonalisation, ONE hand-off per step
 // Round 3's kernel (k_sytrd_dist, workgroup-wide: v_k out from the owner of column k, y back from everybody) spent 7 us per

@@ -1,6 +1,6 @@
 // Host side of the device dense solvers (dense64.hip): the symmetric eigen-computation split as
 //   device  Householder reduction (one persistent launch) + all eigenvalues by Sturm bisection
-//   host    inverse iteration on the tridiagonal matrix for the few eigenvectors wanted (eigen_sym.cpp, O(n k))
+//   host    inverse iteration on the tridiagonal matrix for the few eigenvectors wanted (tridiag_eigenvectors, eigen_sym.cpp; O(n k))
 //   device  back-transformation of those vectors
 // and the Cholesky factor with its inverse.  Used by the train pipeline for the p x p problems of `eigenDecomposition`
 // (reference src/filter.cpp:204-228 at :287 and :313) and the Cholesky shortcuts when p is large (devsolve.h says when),

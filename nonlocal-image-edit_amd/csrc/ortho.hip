@@ -8,7 +8,7 @@ using namespace nlep;
 namespace {
 
 // ---- small host algebra, column-major ----
-// The p x p products of the orthogonalisation run on the register-blocked kernels of eigen_sym.cpp (a 200^3
+// The p x p products of the orthogonalisation run on the register-blocked kernels of host_dense.cpp (a 200^3
 // product is ~0.2 ms on one core); only products of more than ~80 MFLOP per thread are split by output columns
 // over short-lived threads (nleh::run_parts; thread start-up and remote caches cost more than that on the GPU box).
 template <typename F>

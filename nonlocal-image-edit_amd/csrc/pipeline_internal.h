@@ -25,6 +25,7 @@
 
 #include "../../include/nle.h"
 #include "eigen_sym.h"
+#include "host_dense.h"
 #include "kernels.h"
 #include "switches.h"
 

@@ -1,8 +1,8 @@
 // The library's debugging and measurement switches: one struct, one reader of the process environment.  Nothing else
 // under csrc/ asks the environment.  Lifetime: a ctx takes a snapshot when a call on it begins (pipeline_internal.h:
-// guard()) and everything below the entry point reads that snapshot; the ctx-less host algebra (eigen_sym.cpp) takes its
-// own at each public entry.  INTEGRATION.md section 3 lists the same names for users.  No HIP dependency: eigen_sym.cpp
-// is also compiled stand-alone by a plain C++ compiler.
+// guard()) and everything below the entry point reads that snapshot; the ctx-less host eigensolver takes its own at
+// each public entry (eigen_sym.cpp: read_opts) and hands the two it uses down as an EigOpts.  INTEGRATION.md section 3
+// lists the same names for users.  No HIP dependency: eigen_sym.cpp is also compiled stand-alone by a plain C++ compiler.
 #pragma once
 #include <algorithm>
 #include <cstdlib>

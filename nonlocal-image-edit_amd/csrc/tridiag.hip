@@ -10,7 +10,7 @@
 // not use it.  The O(n^2) rest -- QL, inverse iteration for the K kept eigenvectors, their back-transformation -- is the
 // host's either way (eigen_sym.cpp: eigen_decomposition_top_reduced).
 //
-// Same algorithm, storage and scaling as tridiag_reduce in eigen_sym.cpp (the EISPACK tred2 recurrence: rows n-1 .. 1,
+// Same algorithm, storage and scaling as tridiag_reduce in eigen_reduce.cpp (the EISPACK tred2 recurrence: rows n-1 .. 1,
 // u_i = scaled row i, h_i, p = A u / h, q = p - (u.p / 2h) u, A -= u q^T + q u^T), so the host's back-transformation takes
 // its output as is: V (n x n col-major) holds u_i in column i, rows 0..i-1; hs[i] = h_i; d, e the tridiagonal matrix.
 // Only the order of the floating-point sums differs from the host form.

@@ -11,6 +11,7 @@ import pytest
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "nonlocal-image-edit_amd", "csrc")
+HOST_SOURCES = ("eigen_sym.cpp", "eigen_reduce.cpp", "eigen_tridiag.cpp", "host_dense.cpp", "lanczos.cpp")
 
 DRIVER = textwrap.dedent(r"""
     #include <cmath>
@@ -18,7 +19,8 @@ DRIVER = textwrap.dedent(r"""
     #include <random>
     #include <vector>
     #include "eigen_sym.h"
-    int main() {
+    #include "host_dense.h"
+    static int run_all() {
         std::mt19937 g(7);
         std::normal_distribution<double> N(0, 1);
         int bad = 0;
@@ -128,6 +130,17 @@ DRIVER = textwrap.dedent(r"""
             double tr;
             if (nleh::cholesky_with_inverse(A.data(), 2, L.data(), Li.data(), &tr)) { std::printf("indefinite matrix accepted\n"); ++bad; }
         }
+        return bad;
+    }
+    int main() {
+        // as the library runs by default, then the two paths a host without AVX-512 and every fallback take: inverse
+        // iteration one vector at a time, and the QL iteration for all eigenvalues in place of bisection -- same bounds
+        int bad = run_all();
+        setenv("NLE_EIG_NO_X8", "1", 1);
+        bad += run_all();
+        unsetenv("NLE_EIG_NO_X8");
+        setenv("NLE_EIG_NO_BISECT", "1", 1);
+        bad += run_all();
         std::printf("bad=%d\n", bad);
         return bad;
     }
@@ -140,7 +153,7 @@ def test_eigensolver_under_asan_ubsan(tmp_path):
     drv.write_text(DRIVER)
     exe = tmp_path / "drv"
     cmd = ["g++", "-O1", "-g", "-fopenmp-simd", "-pthread", "-Wno-psabi", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           "-I", CSRC, str(drv), os.path.join(CSRC, "eigen_sym.cpp"), "-o", str(exe)]
+           "-I", CSRC, str(drv)] + [os.path.join(CSRC, s) for s in HOST_SOURCES] + ["-o", str(exe)]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     if b.returncode != 0 and "sanitize" in b.stderr:
         pytest.skip("sanitizer runtime not installed: " + b.stderr[-200:])

@@ -37,6 +37,29 @@ def test_product_sources_read_no_removed_switches():
             assert name not in text, (f, name)
 
 
+# ---------------------------------------------------------------------------- the host algebra's files (csrc/*.cpp)
+def test_every_host_source_is_built_into_the_library():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("nle_build_recipe", os.path.join(PKG_DIR, "build.py"))
+    recipe = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(recipe)
+    on_disk = {os.path.basename(f) for f in glob.glob(os.path.join(PKG_DIR, "csrc", "*.cpp"))}
+    assert on_disk and on_disk <= set(recipe.LIB_SOURCES), sorted(on_disk - set(recipe.LIB_SOURCES))
+
+
+def test_tools_and_tests_link_the_host_sources_and_never_include_them():
+    files = [f for d in ("tools", "tests") for f in glob.glob(os.path.join(ROOT, d, "**", "*"), recursive=True) if os.path.isfile(f)]
+    assert len(files) > 20
+    names = "|".join(re.escape(os.path.basename(f)) for f in glob.glob(os.path.join(PKG_DIR, "csrc", "*.cpp")))
+    included = re.compile(r'#\s*include\s*[<"](?:[^>"\n]*/)?(?:%s)[>"]' % names)   # by any path, also through -I
+    for f in files:
+        assert not included.search(open(f, errors="replace").read()), f
+
+
+def test_sym_eigen_select_is_internal():
+    assert "sym_eigen_select" not in open(os.path.join(PKG_DIR, "csrc", "eigen_sym.h")).read()
+
+
 # ---------------------------------------------------------------------------- the switches that remain: csrc/switches.h
 SWITCHES_H = os.path.join(PKG_DIR, "csrc", "switches.h")
 CLI_VARIABLES = ("NLE_MODE", "NLE_DEVICES", "NLE_DEVICE", "NLE_REPORT")

@@ -1,7 +1,15 @@
-// Phase times of the host eigensolver (csrc/eigen_sym.cpp) next to the classic one-loop form.
-// build: g++ -O3 -fopenmp-simd -pthread -Wno-psabi -o eig_phase_bench eig_phase_bench.cpp ; run: ./eig_phase_bench n ncols threads
-#include "../../nonlocal-image-edit_amd/csrc/eigen_sym.cpp"
+// Phase times of the host eigensolver (the stages of csrc/eigen_stages.h) next to the classic one-loop form.
+// build (from this directory, C = ../../nonlocal-image-edit_amd/csrc):
+//   g++ -O3 -fopenmp-simd -std=c++17 -pthread -Wno-psabi -I $C -o eig_phase_bench eig_phase_bench.cpp $C/eigen_sym.cpp \
+//       $C/eigen_reduce.cpp $C/eigen_tridiag.cpp $C/host_dense.cpp $C/lanczos.cpp
+// run: ./eig_phase_bench n ncols threads
+#include "eigen_stages.h"
+#include "eigen_sym.h"
+#include "host_dense.h"
+#include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <cstdlib>
 #include <cstdio>
 #include <random>
 using namespace nleh;
