@@ -323,7 +323,18 @@ int nle_compute_kernel(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
 int nle_nystrom(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples,
                 int n_col_samples, double hx, double hy, double* h_eigvals, int* r,
                 float* d_phi);
-/* Generic tall-skinny product of :275 for caller-supplied matrices:
+/* Leading dimension of the fp32 device matrices below (d_A / lda of nle_ts_gemm; d_phi / ld of nle_sinkhorn_scalings,
+ * nle_gram, nle_row_scalings).  The kernels read whole rows, one float4 at a time, padding columns included, so
+ *   - the row stride must be a multiple of 4 and >= the logical width, the base pointer 16-byte aligned (nle_ld(width) and
+ *     a fresh device allocation are both): any other stride returns NLE_ERR_INVALID before anything is launched;
+ *   - the columns from the logical width up to the stride must hold ZEROS, as every matrix this library writes (d_kab,
+ *     d_phi, d_C) does.  They enter the sums with a zero weight: a NaN or an Inf there makes the result non-finite, no
+ *     other value is promised to be harmless.  Nothing is ever read beyond M rows of the stride;
+ *   - nle_sinkhorn_scalings and nle_row_scalings take a stride of at most 2048 floats (more returns an error with
+ *     nle_last_error set), nle_gram what 136 * ld bytes of LDS allow.
+ * The fp64 entry points further down take any stride and never read the padding.
+ *
+ * Generic tall-skinny product of :275 for caller-supplied matrices:
  * d_C (M x nle_ld(nc)) = d_A (M x lda, logical width kd) * h_B (kd x nc col-major fp64). */
 int nle_ts_gemm(nle_ctx* ctx, const float* d_A, long long M, int lda, int kd,
                 const double* h_B, int nc, float* d_C);

@@ -581,12 +581,17 @@ class Context:
                                            _np_ptr(uc), _np_ptr(ur)), self._h)
         return uc, ur
 
-    def gram(self, phi, r, u):
+    def gram(self, phi, r, u=None):
+        """sum_i c_i^2 phi_i phi_i^T (r x r), c_i = recip(phi_i . u); u None: c_i = 1 (nle_gram's h_u == NULL)"""
         self._sync_in()
-        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            if u.size < r:
+                raise NLEError(NLE_ERR_INVALID, "gram: need r entries of u")
         G = np.zeros((r, r), dtype=np.float64, order="F")
         M, ldp = phi.shape
-        _check(lib().nle_gram(self._h, C.c_void_p(phi.data_ptr()), M, ldp, r, _np_ptr(u), _np_ptr(G)), self._h)
+        _check(lib().nle_gram(self._h, C.c_void_p(phi.data_ptr()), M, ldp, r, _np_ptr(u) if u is not None else None,
+                              _np_ptr(G)), self._h)
         return np.ascontiguousarray(G)
 
     def row_scalings(self, phi, r, u):
