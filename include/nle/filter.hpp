@@ -260,9 +260,14 @@ private:
     // NLE_DEVICES=<dev>,<dev>,...: trainForEnhancement / enhance shard the image by row slabs over one context (and
     // one host thread per call) per listed device; rank r's filter is group_[r] and f_ == group_[0].get()
     std::vector<std::shared_ptr<nle_filter>> group_;
-    void trainForEnhancementGroup(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
-                                  int nSinkhornIter, int nEigenVectors);
-    Image enhanceGroup(const Image& image, const std::vector<DType>& weights) const;
+    long long n_local() const;  // pixels f_ holds (a rank's rows under a group); 0 when untrained
+    int K() const;              // eigenvectors kept; 0 when untrained
+    // throws `message` unless a trained filter holds exactly `pixels` pixels
+    void requireSize(size_t pixels, const char* message) const;
+    // a train starts on ctx c: the old filter goes, the reference's stage banners are printed
+    void beginTrain(nle_ctx* c);
+    // a train ended: fs (one filter, or one per rank of the group, on ctxs) become the state; the Eigvec lines
+    void adopt(const std::vector<nle_ctx*>& ctxs, const std::vector<nle_filter*>& fs, int rows, int cols, int nEigenVectors);
 };
 
 }  // namespace nle

@@ -24,6 +24,9 @@ LIB = os.path.join(LIBDIR, "libnle_hip.so")
 
 LIB_SOURCES = ["kernels.hip", "tsgemm_bf16x3.hip", "fused.hip", "tables.hip", "sorted.hip", "sorted_planes.hip", "generic64.hip", "patch.hip", "sampler.hip", "exact.hip", "resid.hip", "tridiag.hip", "dense64.hip", "colour.hip", "region.hip", "pipeline.hip", "literal.hip", "sample_space.hip", "exact_train.hip", "samples.hip", "ortho.hip", "abi_ctx.hip", "devsolve.hip", "eigen_sym.cpp", "eigen_reduce.cpp", "eigen_tridiag.cpp", "host_dense.cpp", "lanczos.cpp", "lab8_tables.cpp"]
 ARCH = "gfx950"
+# the C++ surface behind include/nle/filter.hpp (host/): what every tool, and a test's driver, links beside its own main
+HOST_SOURCES = ["filter.cpp", "stages.cpp", "colour.cpp", "device_group.cpp", "image_io.cpp", "jpeg.cpp"]
+HOST_HEADERS = ["surface_internal.hpp", "device_group.hpp", "rank_sum.hpp", "cli_common.hpp"]
 
 
 def _hipcc() -> str:
@@ -90,9 +93,9 @@ def build_host(force: bool = False):
     """C++ surface (filter.hpp names) + enhance CLI + unit-test binary, linked to the .so."""
     os.makedirs(BINDIR, exist_ok=True)
     out = []
-    common = [os.path.join(HOST, "filter.cpp"), os.path.join(HOST, "image_io.cpp"), os.path.join(HOST, "jpeg.cpp")]
+    common = [os.path.join(HOST, s) for s in HOST_SOURCES]
     hdrs = [os.path.join(ROOT, "include", "nle", "filter.hpp"), os.path.join(ROOT, "include", "nle", "image_io.hpp"),
-            os.path.join(ROOT, "include", "nle.h"), os.path.join(HOST, "cli_common.hpp")]
+            os.path.join(ROOT, "include", "nle.h")] + [os.path.join(HOST, h) for h in HOST_HEADERS]
     for name, main in (("enhance", "enhance.cpp"), ("denoise", "denoise.cpp"), ("test_filter", "test_filter.cpp")):
         target = os.path.join(BINDIR, name)
         srcs = common + [os.path.join(HOST, main)]

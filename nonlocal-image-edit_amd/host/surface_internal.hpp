@@ -1,0 +1,161 @@
+// What the translation units of the C++ surface (stages.cpp, colour.cpp, device_group.cpp, filter.cpp) share, and the
+// one owner of every step NLEFilter repeats: the process's shared ctx and its mode, status -> exception, the RAII device
+// buffer, the plane conversions, the options a train sets on a ctx (TrainOptions), the colour prologue (lab_planes) and
+// epilogue (lab_to_rows).  Not installed: include/nle/filter.hpp is the surface.
+#pragma once
+
+#include <cmath>
+#include <cstdlib>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "nle.h"
+#include "nle/filter.hpp"
+
+namespace nle::surface {
+
+// the mode a ctx of this process is created with (NLE_MODE, default auto): what a train with NLEFilter::exact restores
+inline int default_mode() {
+    const char* m = std::getenv("NLE_MODE");
+    return m ? std::atoi(m) : NLE_MODE_AUTO;
+}
+
+// one context per process, created on first use (the reference keeps no global state; this one
+// only holds the HIP stream)
+inline nle_ctx* shared_ctx() {
+    static nle_ctx* ctx = nullptr;
+    if (!ctx) {
+        int dev = 0;
+        if (const char* e = std::getenv("NLE_DEVICE")) dev = std::atoi(e);
+        if (nle_ctx_create(dev, nullptr, &ctx) != NLE_OK)
+            throw std::runtime_error(std::string("nle: cannot create GPU context: ") + nle_last_error(nullptr));
+        nle_ctx_set_mode(ctx, default_mode());
+    }
+    return ctx;
+}
+
+inline void check(int status, nle_ctx* ctx) {
+    if (status != NLE_OK) throw std::runtime_error(nle_last_error(ctx));
+}
+
+// RAII device buffer through the ABI helpers (empty until one is moved in when default-constructed)
+struct Dev {
+    nle_ctx* c = nullptr;
+    void* p = nullptr;
+    Dev() = default;
+    Dev(nle_ctx* ctx, size_t bytes) : c(ctx) { check(nle_dev_alloc(c, bytes, &p), c); }
+    ~Dev() {
+        if (p) nle_dev_free(c, p);
+    }
+    Dev(Dev&& o) noexcept : c(o.c), p(o.p) { o.p = nullptr; }
+    Dev& operator=(Dev&& o) noexcept {
+        std::swap(c, o.c);
+        std::swap(p, o.p);
+        return *this;
+    }
+    float* f() const { return static_cast<float*>(p); }
+    double* d() const { return static_cast<double*>(p); }
+    unsigned char* u8() const { return static_cast<unsigned char*>(p); }
+};
+
+inline double recip0(double v, double eps = EPS) { return std::fabs(v) >= eps ? 1.0 / v : 0.0; }  // :42-54
+
+// ---- plane conversions ----
+inline std::vector<float> plane_f32(const Image& m) {
+    if (m.channels() != 1 || m.depth() != NLE_64F) throw std::runtime_error("expected a 1-channel CV_64F matrix");
+    std::vector<float> v(m.total());
+    const double* s = m.ptr<double>();
+    for (size_t i = 0; i < v.size(); ++i) v[i] = (float)s[i];
+    return v;
+}
+
+// a 1-channel CV_64F plane as fp32 on the device
+inline Dev upload_plane(nle_ctx* c, const Image& m) {
+    const std::vector<float> v = plane_f32(m);
+    Dev d(c, v.size() * 4);
+    check(nle_dev_upload(c, d.p, v.data(), v.size() * 4), c);
+    return d;
+}
+
+// rows x cols fp32 values as a CV_64F image
+inline Image image_f64(const float* v, int rows, int cols) {
+    Image m(rows, cols, NLE_64F, 1);
+    double* d = m.ptr<double>();
+    for (size_t i = 0; i < m.total(); ++i) d[i] = v[i];
+    return m;
+}
+
+// rows of a column-major p x n fp64 matrix's TRANSPOSE, one row per pixel (n x ld), i.e. the reference's `Kab` /
+// `Wab` seen as one row per pixel (the stage-level API runs on fp64 device matrices: nle_*64)
+inline std::vector<double> cols_as_rows_f64(const Mat& m, int ld) {
+    std::vector<double> v((size_t)m.cols() * ld, 0.0);
+    for (int j = 0; j < m.cols(); ++j)
+        for (int i = 0; i < m.rows(); ++i) v[(size_t)j * ld + i] = m(i, j);
+    return v;
+}
+
+// ---- the options a train (or a residual map) sets on a ctx, for the length of one call ----
+// Sets, in this order, the filter's patch radius, sampler, the exact mode and (with planes) chroma; puts back radius 0,
+// the grid sampler, the process's mode and chroma off when the scope ends, however it ends -- also when one of its own
+// setters refuses.  A ctx is shared (the free functions run on shared_ctx()), so nothing else may set these options.
+// The exception of a failure inside the scope is built before the options go back: its text is the first failure's.
+class TrainOptions {
+public:
+    TrainOptions(nle_ctx* c, const NLEFilter& f, const float* d_a, const float* d_b) : c_(c), exact_(f.exact) {
+        int st = nle_ctx_set_patch_radius(c_, f.patchRadius);
+        if (st == NLE_OK) st = nle_ctx_set_sampler(c_, f.sampler);
+        if (st == NLE_OK && exact_) st = nle_ctx_set_mode(c_, NLE_MODE_EXACT_F64);
+        if (st == NLE_OK && (d_a || d_b)) st = nle_ctx_set_chroma(c_, d_a, d_b, f.chromaBandwidth);
+        if (st != NLE_OK) {
+            const std::runtime_error refused(nle_last_error(c_));
+            restore();
+            throw refused;
+        }
+    }
+    ~TrainOptions() { restore(); }
+
+private:
+    void restore() {
+        nle_ctx_set_chroma(c_, nullptr, nullptr, 0.0);  // the planes were borrowed for this call only
+        nle_ctx_set_patch_radius(c_, 0);  // the ctx's other users (the free functions) keep the reference's affinity
+        nle_ctx_set_sampler(c_, NLE_SAMPLER_GRID);          // and its grid
+        if (exact_) nle_ctx_set_mode(c_, default_mode());   // and its mode
+    }
+    nle_ctx* c_;
+    bool exact_;
+};
+
+// ---- colour prologue: n BGR pixels (a whole image, or a rank's rows) -> Lab on the device ----
+// bgr and L (fp32) always; lab (the 8-bit Lab image) and a, b (fp32) when wanted, empty otherwise
+struct LabPlanes {
+    Dev bgr, lab, L, a, b;
+};
+inline LabPlanes lab_planes(nle_ctx* c, const unsigned char* bgr, size_t n, bool want_lab, bool want_ab) {
+    LabPlanes o;
+    o.bgr = Dev(c, n * 3);
+    o.L = Dev(c, n * 4);
+    if (want_lab || want_ab) o.lab = Dev(c, n * 3);
+    check(nle_dev_upload(c, o.bgr.p, bgr, n * 3), c);
+    check(nle_bgr2lab8(c, o.bgr.u8(), (long long)n, o.lab.u8(), o.L.f()), c);
+    if (want_ab) {
+        o.a = Dev(c, n * 4);
+        o.b = Dev(c, n * 4);
+        check(nle_lab8_channel(c, o.lab.u8(), (long long)n, 1, o.a.f()), c);
+        check(nle_lab8_channel(c, o.lab.u8(), (long long)n, 2, o.b.f()), c);
+    }
+    return o;
+}
+
+// ---- colour epilogue: Lab -> BGR into rows [r0, r1) of `out` ----
+// in.lab with its L plane replaced by d_L (clamped and rounded to 8 bit) and, where given, a and b by d_a and d_b
+inline void lab_to_rows(nle_ctx* c, const LabPlanes& in, const float* d_L, const float* d_a, const float* d_b, Image& out,
+                        int r0, int r1) {
+    const size_t n = (size_t)(r1 - r0) * out.cols;
+    if (d_a || d_b) check(nle_lab2bgr8_planes(c, in.lab.u8(), d_L, d_a, d_b, (long long)n, in.bgr.u8()), c);
+    else check(nle_lab2bgr8(c, in.lab.u8(), d_L, (long long)n, in.bgr.u8()), c);
+    check(nle_dev_download(c, out.ptr<unsigned char>(r0), in.bgr.p, n * 3), c);
+}
+
+}  // namespace nle::surface

@@ -8,7 +8,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
+#include <string>
+#include <tuple>
 
 #include "nle/filter.hpp"
 
@@ -258,6 +261,52 @@ int main() {
             threw = true;
         }
         CHECK(threw);
+    }
+    {  // a train that is refused leaves no option on the shared ctx: computeKernel, which runs on it, keeps the
+       // reference's single-value affinities, bit for bit
+        const int H = 12, W = 16;
+        nle::Image L(H, W, nle::NLE_64F, 1);
+        nle::Image bgr(H, W, nle::NLE_8U, 3);
+        for (int r = 0; r < H; ++r)
+            for (int c = 0; c < W; ++c) {
+                L.at<double>(r, c) = (r * 37 + c * 11 + (r * c) % 7) % 256;
+                for (int ch = 0; ch < 3; ++ch) bgr.ptr<unsigned char>(r)[3 * c + ch] = (unsigned char)((r * 17 + c * 29 + ch * 61) % 256);
+            }
+        nle::Permutation P0, P;
+        Mat Ka0, Kab0, Ka, Kab;
+        std::tie(P0, Ka0, Kab0) = nle::computeKernel(L, 3, 4, 4.0, 30.0);
+        auto same_bits = [](const Mat& a, const Mat& b) {
+            return a.rows() == b.rows() && a.cols() == b.cols() &&
+                   std::memcmp(a.data(), b.data(), sizeof(double) * (size_t)a.rows() * a.cols()) == 0;
+        };
+        nle::NLEFilter f;
+        f.verbose = false;
+        f.patchRadius = 1;
+        f.sampler = 7;  // refused on the host, after the radius was taken: nothing is launched
+        bool threw = false;
+        try {
+            f.trainFilter(L, 3, 4, 4.0, 30.0, 10, 5);
+        } catch (const std::runtime_error& e) {
+            threw = std::string(e.what()).find("sampler must be") != std::string::npos;
+        }
+        CHECK(threw);
+        std::tie(P, Ka, Kab) = nle::computeKernel(L, 3, 4, 4.0, 30.0);
+        CHECK(same_bits(Ka, Ka0));
+        CHECK(same_bits(Kab, Kab0));
+        nle::NLEFilter fc;
+        fc.verbose = false;
+        fc.patchRadius = 1;
+        fc.chromaBandwidth = -1;  // refused after radius and sampler were taken
+        threw = false;
+        try {
+            fc.trainForEnhancement(bgr, 3, 4, 4.0, 30.0, 10, 5);
+        } catch (const std::runtime_error& e) {
+            threw = std::string(e.what()).find("chroma bandwidth") != std::string::npos;
+        }
+        CHECK(threw);
+        std::tie(P, Ka, Kab) = nle::computeKernel(L, 3, 4, 4.0, 30.0);
+        CHECK(same_bits(Ka, Ka0));
+        CHECK(same_bits(Kab, Kab0));
     }
     std::printf("%d checks, %d failed\n", g_total, g_fail);
     return g_fail == 0 ? 0 : 1;

@@ -803,7 +803,7 @@ def test_cpp_sampler_3_trains_on_the_c_abi_s_set(tmp_path):
     libdir = os.path.join(PKG_DIR, "lib")
     (tmp_path / "drv.cpp").write_text(CPP_DRIVER)
     b = subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), str(tmp_path / "drv.cpp"),
-                        os.path.join(host, "filter.cpp"), os.path.join(host, "image_io.cpp"), os.path.join(host, "jpeg.cpp"),
+                        *[os.path.join(host, s) for s in ("filter.cpp", "stages.cpp", "colour.cpp", "device_group.cpp", "image_io.cpp", "jpeg.cpp")],
                         "-L", libdir, "-lnle_hip", "-Wl,-rpath," + libdir, "-o", str(tmp_path / "drv")],
                        capture_output=True, text=True, timeout=300)
     assert b.returncode == 0, b.stderr[-3000:]

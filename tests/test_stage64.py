@@ -331,7 +331,7 @@ def _gemm_cases():
     out += [(BIG_ROWS, 33, 33, "r+1", 0), (4099, 200, 50, "ld4", 0), (300, 7, 260, "r", 0), (129, 300, 33, "r+37", 0),
             (1000, 17, 1, "ld4", 0), (257, 1, 33, "r+1", 0), (16, 16, 16, "r", 0), (17, 17, 17, "ld4", 0),
             (300, 8, 5, 2304, 0),
-            # a row sub-block, d_A + q * lda (host/filter.cpp: sinkhorn's Wab from the rows below the samples)
+            # a row sub-block, d_A + q * lda (host/stages.cpp: sinkhorn's Wab from the rows below the samples)
             (257, 33, 31, "ld4", 37), (1000, 16, 15, "r+1", 16), (4099, 5, 33, "r", 4098), (256, 31, 3, "r+37", 1)]
     return out
 
