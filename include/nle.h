@@ -394,6 +394,34 @@ int nle_sinkhorn_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int 
                             int max_iter, double* h_u_c, double* h_u_r);
 int nle_gram64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, const double* h_u, double* h_G);
 int nle_row_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, const double* h_u, double* d_out);
+/* The sample-space stages (csrc/fused.hip), each alone: the launchers NLE_MODE_PHI_FREE_EXP, the table formulation's Sinkhorn
+ * update and V on demand call, with nothing around them.  d_lum: the FULL H x W plane (fp32); the sample grid and hx, hy as
+ * in nle_compute_kernel (the plain fp32 affinity: none of the ctx's affinity options).  Rows [row0, row1) are the local slab,
+ * 0 <= row0 < row1 <= H: M = (row1 - row0) W pixels from pixel row0 W on; coordinates stay global, the indices of d_y, d_c
+ * and d_V are local.  Every call returns with the stream drained.  NLE_ERR_INVALID with nle_last_error set for what a
+ * launcher has no kernel for: more than 256 samples (pass, Gram), K > 128 or more than 32 x 36 samples (projection).
+ *
+ * nle_sample_pass: one Sinkhorn half-iteration, z[s] = sum over the NON-sample local pixels of k_i[s] y_i with y_i = 1
+ *   (recip == 0) or recip(k_i . h_w) (k_sink_pass + k_reduce_partials, the slices added in order).  h_w: p doubles (NULL:
+ *   zeros), d_y: M doubles or NULL (y_i, 0 at the sample pixels), h_z: p doubles.
+ * nle_sample_gram: h_G (p x p, symmetric) = sum over the non-sample local pixels of d_c[i]^2 k_i k_i^T (k_gram64 +
+ *   k_gram64_reduce); d_c at a sample pixel is not read.
+ * nle_sample_project: d_V (M x ldv fp32, K <= ldv <= 16 ceil(K / 16)) = diag(d_c) K_rows h_D, h_D p x K ROW-major, for every
+ *   local pixel, the sample pixels included (k_project64 / k_project64_res; no exact sample rows are scattered).  Columns
+ *   [K, ldv) come out zero.
+ * nle_sample_update: the p-sized update between two passes (k_sink_update_a/b, eps = NLE_EPS) on host operands: h_X1 2p x r
+ *   column-major, h_X2 2p x r row-major, h_lam r, h_z zrows x zld (zld >= p) slices of z, h_sA the p sample row sums the
+ *   pass used (recip != 0; ignored and may be NULL for the column sum).  Out: h_v = [z; y_A] (2p), h_u (r), h_sA_next (p),
+ *   h_w_next (p). */
+int nle_sample_pass(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx, double hy,
+                    int row0, int row1, int recip, const double* h_w, double* d_y, double* h_z);
+int nle_sample_gram(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx, double hy,
+                    int row0, int row1, const double* d_c, double* h_G);
+int nle_sample_project(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
+                       double hy, int row0, int row1, const double* h_D, int K, const double* d_c, float* d_V, int ldv);
+int nle_sample_update(nle_ctx* ctx, int p, int r, int chol, int recip, const double* h_X1, const double* h_X2,
+                      const double* h_lam, const double* h_z, int zrows, int zld, const double* h_sA, double* h_v, double* h_u,
+                      double* h_sA_next, double* h_w_next);
 /* The small dense fp64 product of the p- and q-sized algebra (one launch, fp64 MFMA), all operands on the device:
  * C(i,j) = dl[i] (sum_k A(i,k) dk[k] B(k,j)) dr[j] + add(i,j) for i < m, j < n, k < kk, every matrix given by its pointer
  * and its (row stride, column stride) in doubles, so that transposes, sub-blocks and padded row- or column-major outputs

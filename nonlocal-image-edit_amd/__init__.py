@@ -665,6 +665,82 @@ class Context:
                                         C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    # ---- the sample-space stages (csrc/fused.hip), each alone: nle_sample_pass / _gram / _project / _update ----
+    def _plane(self, lum):
+        torch = _torch()
+        t = torch.as_tensor(lum, dtype=torch.float32, device=f"cuda:{self.device}").contiguous()
+        self._sync_in()
+        return t, int(t.shape[0]), int(t.shape[1])
+
+    def sample_pass(self, lum, nr, nc, hx, hy, w=None, recip=False, rows=None, want_y=True):
+        """one Sinkhorn half-iteration over rows [row0, row1) of the plane: (z (p), y (M, device) or None)"""
+        torch = _torch()
+        t, H, W = self._plane(lum)
+        row0, row1 = rows if rows is not None else (0, H)
+        g = sample_grid(H, W, nr, nc)
+        z = np.zeros(g["n_sel_rows"] * g["n_sel_cols"])
+        w = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+        if w is not None and w.size != z.size:
+            raise NLEError(NLE_ERR_INVALID, "sample_pass: need p entries of w")
+        y = torch.empty(max(row1 - row0, 0) * W, dtype=torch.float64, device=t.device) if want_y else None
+        _check(lib().nle_sample_pass(self._h, C.c_void_p(t.data_ptr()), H, W, nr, nc, hx, hy, row0, row1, int(bool(recip)),
+                                     _np_ptr(w) if w is not None else None, C.c_void_p(y.data_ptr()) if want_y else None,
+                                     _np_ptr(z)), self._h)
+        return z, y
+
+    def sample_gram(self, lum, nr, nc, hx, hy, c, rows=None):
+        """sum over the non-sample pixels of rows [row0, row1) of c_i^2 k_i k_i^T (p x p); c: M doubles on the device"""
+        t, H, W = self._plane(lum)
+        row0, row1 = rows if rows is not None else (0, H)
+        if c.dtype != _torch().float64 or not c.is_cuda or c.numel() != (row1 - row0) * W or not c.is_contiguous():
+            raise NLEError(NLE_ERR_INVALID, "sample_gram: c must be M float64 values on the device")
+        g = sample_grid(H, W, nr, nc)
+        p = g["n_sel_rows"] * g["n_sel_cols"]
+        G = np.zeros((p, p))
+        _check(lib().nle_sample_gram(self._h, C.c_void_p(t.data_ptr()), H, W, nr, nc, hx, hy, row0, row1,
+                                     C.c_void_p(c.data_ptr()), _np_ptr(G)), self._h)
+        return G
+
+    def sample_project(self, lum, nr, nc, hx, hy, D, c, rows=None, out=None):
+        """V (M x ld(K) fp32, device) = diag(c) K_rows D over rows [row0, row1); D: p x K, c: M doubles on the device.
+        out: an (M, ld(K)) float32 device tensor to write into (whatever it holds)"""
+        torch = _torch()
+        t, H, W = self._plane(lum)
+        row0, row1 = rows if rows is not None else (0, H)
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        g = sample_grid(H, W, nr, nc)
+        if D.ndim != 2 or D.shape[0] != g["n_sel_rows"] * g["n_sel_cols"]:
+            raise NLEError(NLE_ERR_INVALID, "sample_project: D must be p x K")
+        K, M = D.shape[1], (row1 - row0) * W
+        if c.dtype != torch.float64 or not c.is_cuda or c.numel() != M or not c.is_contiguous():
+            raise NLEError(NLE_ERR_INVALID, "sample_project: c must be M float64 values on the device")
+        ldv = (K + 3) & ~3
+        V = out if out is not None else torch.empty((M, ldv), dtype=torch.float32, device=t.device)
+        if V.dtype != torch.float32 or tuple(V.shape) != (M, ldv) or not V.is_contiguous() or not V.is_cuda:
+            raise NLEError(NLE_ERR_INVALID, "sample_project: out must be an (M, ld(K)) float32 device tensor")
+        _check(lib().nle_sample_project(self._h, C.c_void_p(t.data_ptr()), H, W, nr, nc, hx, hy, row0, row1, _np_ptr(D), K,
+                                        C.c_void_p(c.data_ptr()), C.c_void_p(V.data_ptr()), ldv), self._h)
+        return V
+
+    def sample_update(self, X1, X2, lam, z, sA=None, chol=False):
+        """the p-sized update between two passes on host operands.  X1, X2: (2p, r) arrays (the library takes the first
+        column-major, the second row-major), z: (zrows, zld) slices, sA None: the column sum -> (v (2p), u (r), sA_next, w_next)"""
+        X = np.asarray(X1, dtype=np.float64)
+        X1c, X2r = np.asfortranarray(X), np.ascontiguousarray(np.asarray(X2, dtype=np.float64))
+        n2, r = X.shape
+        p = n2 // 2
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        z = np.ascontiguousarray(np.atleast_2d(z), dtype=np.float64)
+        sA = None if sA is None else np.ascontiguousarray(sA, dtype=np.float64)
+        if n2 != 2 * p or X2r.shape != (n2, r) or lam.size != r or z.shape[1] < p or (sA is not None and sA.size != p):
+            raise NLEError(NLE_ERR_INVALID, "sample_update: X1, X2 (2p x r), lam (r), z (zrows x zld >= p), sA (p)")
+        v, u, sn, wn = np.zeros(n2), np.zeros(r), np.zeros(p), np.zeros(p)
+        self._sync_in()
+        _check(lib().nle_sample_update(self._h, p, r, int(bool(chol)), int(sA is not None), _np_ptr(X1c), _np_ptr(X2r),
+                                       _np_ptr(lam), _np_ptr(z), z.shape[0], z.shape[1], _np_ptr(sA) if sA is not None else None,
+                                       _np_ptr(v), _np_ptr(u), _np_ptr(sn), _np_ptr(wn)), self._h)
+        return v, u, sn, wn
+
     def gemm64s(self, m, n, kk, A, sA, B, sB, Cm, sC, dl=None, dk=None, dr=None, add=None, sadd=(0, 0)):
         """nle_gemm64s on float64 CUDA tensors, in place in Cm: A, B, Cm (and add) are taken as flat buffers whose entry
         (i, j) sits at i * s[0] + j * s[1] doubles from data_ptr(); dl, dk, dr: vectors or None"""

@@ -658,6 +658,8 @@ __global__ __launch_bounds__(NW * 64) void k_project64_res(const float* __restri
                             const int col = NT * 16 + q;
                             if (col < ldv) V[(size_t)li * ldv + col] = (float)(cf * (mt == 0 ? rem0[q] : rem1[q]));
                         }
+                        // the padding columns [K, ldv) (kernels.h, above project64): no MFMA tile covers them here
+                        for (int col = NT * 16 + REM; col < ldv; ++col) V[(size_t)li * ldv + col] = 0.f;
                     }
                 }
             }

@@ -138,6 +138,9 @@ size_t gram64_partial_elems(long long M, int p);
 hipError_t gram64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, float nsw,
                   float npw, long long pix0, long long M, const double* d_c, double* d_partial, double* d_tiles);
 // V (M x ldv fp32) = diag(c) K D on the fp64 MFMA; D: p x project64_ld(K) fp64 row-major, K <= 128
+// The rule for V's padding, stated here for every route that builds V (project64's 28 forms, ts_gemm, ts_gemm64 behind a
+// memset, scatter_sample_rows): columns [K, ldv) are ZERO, K <= ldv <= project64_ld(K).  apply_dense, rowpass_any and
+// k_apply_expand read whole rows of ldv against a zero-padded g: a NaN bit pattern left there would reach the output.
 int project64_ld(int K);
 hipError_t project64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, float nsw,
                      float npw, long long pix0, long long M, const double* d_D, int K, const double* d_c, float* d_V,

@@ -1,6 +1,6 @@
 // The literal decomposition (reference src/filter.cpp:480-502 as written) with Phi = K_AB^T B materialised, in fp32
 // (NLE_MODE_MATERIALISED) and in fp64 (generic64.hip: auto mode's fallback), its stages, the stage entry points that expose
-// exactly these, and the micro-benchmarks of two of its kernels.
+// exactly these, the four that expose fused.hip's launchers (nle_sample_*), and the micro-benchmarks of two of its kernels.
 #include "train.h"
 
 using namespace nlep;
@@ -322,6 +322,35 @@ SampleSet bench_samples(nle_ctx* ctx, const float* d_lum, int H, int W, int nRow
     slab(H, ctx->rank, ctx->world, row0, row1);
     return fetch_samples(ctx, d_lum, gs, AffinityOpts{});
 }
+
+// nle_sample_pass / _gram / _project: the plane's sample set on the device and the slab [row0, row1), as train_phi_free_exp
+// hands them to fused.hip's launchers (the plain fp32 affinity: none of the ctx's affinity options)
+struct SampleStage {
+    SampleSet ss;
+    DevBuf<float4> d_samples;
+    float nsw, npw;
+    long long pix0, M;
+};
+SampleStage sample_stage(nle_ctx* ctx, const float* d_lum, int H, int W, int nRow, int nCol, double hx, double hy, int row0,
+                         int row1, int max_p, const char* refusal) {
+    const GridSpec gs = checked_grid(H, W, nRow, nCol);
+    if (!(hx > 0) || !(hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
+    if (row0 < 0 || row1 <= row0 || row1 > H) throw Fail{NLE_ERR_INVALID, "need 0 <= row0 < row1 <= H"};
+    if (gs.p() > max_p) throw Fail{NLE_ERR_INVALID, refusal};
+    HIP_OK(hipSetDevice(ctx->device));
+    SampleStage st;
+    st.ss = fetch_samples(ctx, d_lum, gs, AffinityOpts{});
+    st.d_samples = upload_samples(ctx, st.ss, nlek::sink_pass_ld(st.ss.p));
+    st.nsw = nsw_of(hx), st.npw = nsw_of(hy);
+    st.pix0 = (long long)row0 * W, st.M = (long long)(row1 - row0) * W;
+    return st;
+}
+template <typename T>
+DevBuf<T> uploaded(nle_ctx* ctx, const T* h, size_t n) {
+    DevBuf<T> d(n);
+    HIP_OK(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return d;
+}
 }  // namespace
 
 namespace nlep {
@@ -519,6 +548,98 @@ int nle_gram64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, co
 int nle_row_scalings64(nle_ctx* ctx, const double* d_phi, long long M, int ld, int r, const double* h_u, double* d_out) {
     if (!ctx || !d_phi || !h_u || !d_out || M < 0 || r < 1 || ld < r) return NLE_ERR_INVALID;
     return guard(ctx, [&] { row_scalings_impl(ctx, d_phi, M, ld, r, h_u, d_out); });
+}
+
+// ---- the sample-space stages (fused.hip), each alone: the launchers of train_phi_free_exp, SampleSinkhorn and ensure_V ----
+int nle_sample_pass(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx, double hy,
+                    int row0, int row1, int recip, const double* h_w, double* d_y, double* h_z) {
+    if (!ctx || !d_lum || !h_z) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        const SampleStage st = sample_stage(ctx, d_lum, H, W, n_row_samples, n_col_samples, hx, hy, row0, row1,
+                                            nlek::sink_pass_max_p(), "nle_sample_pass: the pass kernel takes at most 256 samples");
+        const int p = st.ss.p, P64 = nlek::sink_pass_ld(p);
+        constexpr int kZS = 8;  // as train_phi_free_exp: slices of the block partials, added in order (k_sink_update_a's loop)
+        const int npart = nlek::sink_pass_rows(st.M);
+        std::vector<double> w(P64, 0.0), z((size_t)kZS * P64);
+        if (h_w) std::copy(h_w, h_w + p, w.begin());
+        DevBuf<double> d_w = uploaded(ctx, w.data(), w.size()), d_z(z.size()), d_partial((size_t)npart * P64);
+        PROFILED(ctx, NLE_K_SINKHORN_PASS,
+                 nlek::sink_pass(ctx->stream, recip ? nlek::ROWPASS_RECIP : nlek::ROWPASS_COLSUM, d_lum, st.ss.gs, st.d_samples.p, p,
+                                 d_w.p, st.nsw, st.npw, st.pix0, st.M, NLE_EPS, d_y, d_partial.p));
+        PROFILED(ctx, NLE_K_REDUCE, nlek::reduce_partials(ctx->stream, d_partial.p, npart, P64, d_z.p, kZS));
+        HIP_OK(hipMemcpyAsync(z.data(), d_z.p, z.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        prof_flush(ctx);
+        for (int a = 0; a < p; ++a) {
+            double t = 0.0;
+            for (int q = 0; q < kZS; ++q) t += z[(size_t)q * P64 + a];
+            h_z[a] = t;
+        }
+    });
+}
+
+int nle_sample_gram(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx, double hy,
+                    int row0, int row1, const double* d_c, double* h_G) {
+    if (!ctx || !d_lum || !d_c || !h_G) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        const SampleStage st = sample_stage(ctx, d_lum, H, W, n_row_samples, n_col_samples, hx, hy, row0, row1,
+                                            nlek::sink_pass_max_p(), "nle_sample_gram: the Gram kernel takes at most 256 samples");
+        const int p = st.ss.p;
+        std::vector<double> tiles((size_t)nlek::gram64_num_tiles(p) * 256);
+        DevBuf<double> d_gpart(nlek::gram64_partial_elems(st.M, p)), d_tiles(tiles.size());
+        PROFILED(ctx, NLE_K_GRAM, nlek::gram64(ctx->stream, d_lum, st.ss.gs, st.d_samples.p, p, st.nsw, st.npw, st.pix0, st.M, d_c,
+                                               d_gpart.p, d_tiles.p));
+        HIP_OK(hipMemcpyAsync(tiles.data(), d_tiles.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        prof_flush(ctx);
+        const std::vector<double> G = unpack_tiles(tiles, nlek::gram64_ld(p), p, 16);
+        std::copy(G.begin(), G.end(), h_G);
+    });
+}
+
+int nle_sample_project(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, double hx,
+                       double hy, int row0, int row1, const double* h_D, int K, const double* d_c, float* d_V, int ldv) {
+    if (!ctx || !d_lum || !h_D || !d_c || !d_V || K < 1) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (K > 128) throw Fail{NLE_ERR_INVALID, "nle_sample_project: the projection kernel takes at most 128 columns"};
+        if (ldv < K || ldv > nlek::project64_ld(K)) throw Fail{NLE_ERR_INVALID, "nle_sample_project: need K <= ldv <= 16 ceil(K / 16)"};
+        const SampleStage st = sample_stage(ctx, d_lum, H, W, n_row_samples, n_col_samples, hx, hy, row0, row1, 32 * 36,
+                                            "nle_sample_project: at most 32 x 36 samples");
+        const int p = st.ss.p;
+        std::vector<double> X((size_t)p * K);  // column-major, as the orthogonalisation leaves D
+        for (int k = 0; k < K; ++k)
+            for (int a = 0; a < p; ++a) X[(size_t)k * p + a] = h_D[(size_t)a * K + k];
+        const std::vector<double> Dp = padded_rows(X, p, K, nlek::project64_ld(K));
+        DevBuf<double> d_D = uploaded(ctx, Dp.data(), Dp.size());
+        PROFILED(ctx, NLE_K_PROJECT, nlek::project64(ctx->stream, d_lum, st.ss.gs, st.d_samples.p, p, st.nsw, st.npw, st.pix0, st.M,
+                                                     d_D.p, K, d_c, d_V, ldv));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        prof_flush(ctx);
+    });
+}
+
+int nle_sample_update(nle_ctx* ctx, int p, int r, int chol, int recip, const double* h_X1, const double* h_X2,
+                      const double* h_lam, const double* h_z, int zrows, int zld, const double* h_sA, double* h_v, double* h_u,
+                      double* h_sA_next, double* h_w_next) {
+    if (!ctx || !h_X1 || !h_X2 || !h_lam || !h_z || !h_v || !h_u || !h_sA_next || !h_w_next || p < 1 || r < 1 || zrows < 1 ||
+        zld < p || (recip && !h_sA) || (chol && r != p))
+        return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        HIP_OK(hipSetDevice(ctx->device));
+        const size_t n2 = (size_t)2 * p;
+        DevBuf<double> d_X1 = uploaded(ctx, h_X1, n2 * r), d_X2 = uploaded(ctx, h_X2, n2 * r), d_lam = uploaded(ctx, h_lam, (size_t)r),
+                       d_z = uploaded(ctx, h_z, (size_t)zrows * zld), d_sA, d_uv(n2 + r), d_out(n2);
+        if (recip) d_sA = uploaded(ctx, h_sA, (size_t)p);
+        PROFILED(ctx, NLE_K_SMALL,
+                 nlek::sink_update(ctx->stream, recip ? nlek::ROWPASS_RECIP : nlek::ROWPASS_COLSUM, p, r, chol != 0, d_X1.p, d_X2.p,
+                                   d_lam.p, d_z.p, zrows, zld, d_sA.p, NLE_EPS, d_uv.p, d_uv.p + n2, d_out.p, d_out.p + p));
+        HIP_OK(hipMemcpyAsync(h_v, d_uv.p, n2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipMemcpyAsync(h_u, d_uv.p + n2, r * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipMemcpyAsync(h_sA_next, d_out.p, p * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipMemcpyAsync(h_w_next, d_out.p + p, p * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        prof_flush(ctx);
+    });
 }
 
 int nle_gemm64s(nle_ctx* ctx, int m, int n, int kk, const double* d_A, long long rs_a, long long cs_a, const double* d_B,

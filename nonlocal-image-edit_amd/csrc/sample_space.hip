@@ -124,15 +124,15 @@ OrthoSS ortho_ss_host(nle_ctx* c, const Nystrom& ny, int p, const SampleSinkhorn
     return o;
 }
 
+}  // namespace
+
 // X (p x K column-major on the host) as the p x ldd row-major, zero-padded operand of project64 / k_apply_small
-std::vector<double> padded_rows(const std::vector<double>& X, int p, int K, int ldd) {
+std::vector<double> nlep::padded_rows(const std::vector<double>& X, int p, int K, int ldd) {
     std::vector<double> R((size_t)p * ldd, 0.0);
     for (int k = 0; k < K; ++k)
         for (int a = 0; a < p; ++a) R[(size_t)a * ldd + k] = X[(size_t)k * p + a];
     return R;
 }
-
-}  // namespace
 
 // quantised luminance + Cartesian sample grid: table look-ups replace the exponentials (tables.hip), and the pixel halves of
 // every table pass run on level-sorted rows, without LDS atomics (sorted.hip; sorted once here).  d_lum: virtual full base.

@@ -93,6 +93,8 @@ struct TrainPath {
     void train_stream64(const SolveKa& solve);
 };
 
+// X (p x K column-major on the host) as the p x ldd row-major, zero-padded operand of project64 (sample_space.hip)
+std::vector<double> padded_rows(const std::vector<double>& X, int p, int K, int ldd);
 std::vector<double> host_Vrows(const nle_filter* f);  // sample_space.hip, as the next two
 void ensure_V(nle_filter* f);
 // `done(l0, nl)`, when given, is called after layers [l0, l0 + nl) are complete on the stream (the host-buffer entry
