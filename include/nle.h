@@ -422,6 +422,65 @@ int nle_sample_project(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row
 int nle_sample_update(nle_ctx* ctx, int p, int r, int chol, int recip, const double* h_X1, const double* h_X2,
                       const double* h_lam, const double* h_z, int zrows, int zld, const double* h_sA, double* h_v, double* h_u,
                       double* h_sA_next, double* h_w_next);
+/* The table path's stages (csrc/tables.hip), each alone: the launchers the default train and apply call (check_levels,
+ * hist_tables, sink_hist_tiled, apply_hist_layers, gram_hist, apply_small, scatter_samples), with nothing around them and no
+ * launch geometry of their own.  d_lum: the FULL H x W plane (fp32, integer valued in [0, 255]); rows [row0, row1) are the local
+ * slab, 0 <= row0 < row1 <= H, nrows = row1 - row0: coordinates stay global, d_cvec, d_y and the outputs are indexed locally.
+ * nR x nC = the realised sample grid (nle_sample_grid), p = nR nC, ldp = 64 ceil(p / 64).  The tables come one of two ways:
+ *   supplied  d_er (nrows x nR), d_ecT (nC x W) and d_Ep (256 x p) are the caller's, on the device (hx, hy are not read): the
+ *             pixel kernels are the LDS-atomic ones and all 16 level tiles are made -- what the library runs on planes wider than
+ *             its level-sorted rows take
+ *   built     d_er = d_ecT = d_Ep = NULL: the tables, the level-sorted rows, the range of level tiles that occur and the kernel
+ *             forms the bandwidth allows, made from the plane, hx and hy exactly as training makes them
+ * d_cvec: nrows W row scalings, may be NULL where no kernel reads them (the column-sum and reciprocal passes).  Whatever it
+ * holds at a sample pixel, a NaN included, is never used.  The expand half writes 0 at the sample pixels of d_out on a
+ * supplied view; on a built view with level-sorted rows it leaves them to nle_table_scatter (their content is unspecified).
+ * Before the launch every workspace and every output is filled with NaN (all bytes 0xff): an element no kernel wrote still
+ * holds it.  Every call returns with the stream drained.
+ * NLE_ERR_INVALID with nle_last_error set, before any launch, for what the launchers have no kernel for: nR > 32, nC > 36,
+ * K > 128, more layers than one launch takes; and for a plane that is not integer valued in [0, 255] (a built view: the whole
+ * plane; a supplied view: the local rows, checked with check_levels first).
+ *
+ * nle_table_workspace: doubles of workspace of nle_table_pass (gram == 0) or nle_table_gram (gram != 0) for nrows local rows;
+ *   -1 for a grid beyond 32 x 36.  Host only.
+ * nle_table_levels: check_levels over n floats at d_x (any 4-byte alignment): *h_bad != 0 when a value is not an integer in
+ *   [0, 255] (NaN included), bit t of *h_mask set when a valid level in [16 t, 16 t + 16) occurs.
+ * nle_table_build: what the view is.  h_info (5 ints): level-sorted rows made, first level tile, number of level tiles, the Gram
+ *   runs on index sums, layers one expand launch takes.  d_er_out, d_ecT_out, d_Ep_out (optional): copies of the tables.
+ * nle_table_pass: one half-iteration (sink_hist_tiled).  mode 0: y = 1; 1: y = recip(d), d_i = sum_b ec[c_i][b] g[r_i][x_i][b],
+ *   g from d_w (p doubles); 2: y_i = d_cvec[i] d_xvec[i], d_xvec the full plane.  y = 0 at sample pixels.  d_y (optional):
+ *   nrows W.  d_ws: ws_elems >= nle_table_workspace doubles, laid out g (nrows x nC x 256, mode 1 only), h (the same shape),
+ *   then the (slab, level tile) partial rows of ldp doubles; d_z: ldp doubles, [p, ldp) come out zero.
+ * nle_table_expand: the expand half of apply for nl layers (apply_hist_layers): the g tables of the weight vectors d_wl (nl
+ *   vectors of stride ldw >= p) into d_gws (nl x nrows x nC x 256), then d_out[l ostride + i] = (float)(c_i sum_b ec g), with
+ *   round8 != 0 clamped to [0, 255] and rounded half to even in fp64.  d_out: nl ostride floats.
+ * nle_table_gram: d_Gk (p x p, symmetric) = sum over the non-sample local pixels of c_i^2 k_i k_i^T (gram_hist).  d_ws: pair
+ *   form A (nrows x NP x 256, NP = nC (nC + 1) / 2), EE (nrows x ldm), C (splits x ldm x NP x 256); index sums (built views
+ *   where the bandwidth allows) S (nrows x (2 nC - 1) x 256), F (nrows x ldm2), T (splits x ldm2 x (2 nC - 1) x 256).
+ *   h_split (2 ints): the image rows per split and the number of splits of the GEMM, in the form the view takes.
+ * nle_table_apply_small: the p- and K-sized middle of apply (k_apply_small), all operands on the device: t = D^T m + Vrows^T xA
+ *   (K), W'[l] = D (resp_l o t) (stride ldw, [p, ldw) zero), YA[l] = Vrows (resp_l o t) (stride p).  D, Vrows: p x ldk
+ *   row-major.  d_differs (optional): a device int; where it is 0, d_m_same and d_xA_same stand in for d_m and d_xA.
+ * nle_table_scatter: d_Y[l ystride + d_loc[a]] = (float)YA[l][a] where d_loc[a] >= 0 (round8 as above); d_Y is otherwise kept. */
+long long nle_table_workspace(int n_sel_rows, int n_sel_cols, int nrows, int gram);
+int nle_table_levels(nle_ctx* ctx, const float* d_x, long long n, int* h_bad, unsigned* h_mask);
+int nle_table_build(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, int row0, int row1,
+                    double hx, double hy, const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_cvec,
+                    double* d_er_out, double* d_ecT_out, double* d_Ep_out, int* h_info);
+int nle_table_pass(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, int row0, int row1,
+                   double hx, double hy, const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_cvec,
+                   int mode, const double* d_w, const float* d_xvec, double* d_y, double* d_ws, long long ws_elems, double* d_z);
+int nle_table_expand(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, int row0, int row1,
+                     double hx, double hy, const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_cvec,
+                     const double* d_wl, int ldw, int nl, int round8, double* d_gws, float* d_out, long long ostride);
+int nle_table_gram(nle_ctx* ctx, const float* d_lum, int H, int W, int n_row_samples, int n_col_samples, int row0, int row1,
+                   double hx, double hy, const double* d_er, const double* d_ecT, const double* d_Ep, const double* d_cvec,
+                   double* d_ws, long long ws_elems, double* d_Gk, int* h_split);
+int nle_table_apply_small(nle_ctx* ctx, int p, int K, int ldk, int L, int ldw, const double* d_m, const double* d_D,
+                          const double* d_Vrows, const double* d_xA, const double* d_resp, double* d_t, double* d_Wp,
+                          double* d_YA, const int* d_differs, const double* d_m_same, const double* d_xA_same);
+int nle_table_scatter(nle_ctx* ctx, int p, int L, const long long* d_loc, const double* d_YA, float* d_Y, long long ystride,
+                      int round8);
 /* The small dense fp64 product of the p- and q-sized algebra (one launch, fp64 MFMA), all operands on the device:
  * C(i,j) = dl[i] (sum_k A(i,k) dk[k] B(k,j)) dr[j] + add(i,j) for i < m, j < n, k < kk, every matrix given by its pointer
  * and its (row stride, column stride) in doubles, so that transposes, sub-blocks and padded row- or column-major outputs

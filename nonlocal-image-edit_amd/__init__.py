@@ -134,6 +134,11 @@ def sample_grid(H, W, n_row_samples, n_col_samples):
     return dict(zip(keys, (o.value for o in out)))
 
 
+def table_workspace(n_sel_rows, n_sel_cols, nrows, gram=False):
+    """doubles of workspace of Context.table_pass (or table_gram) for nrows local rows (nle_table_workspace); -1 beyond 32 x 36"""
+    return int(lib().nle_table_workspace(int(n_sel_rows), int(n_sel_cols), int(nrows), int(bool(gram))))
+
+
 def residual_sampler_bytes(H, W, n_row_samples, n_col_samples):
     """device bytes SAMPLER_RESIDUAL's factor takes on an H x W plane with this sample grid (nle_residual_sampler_bytes);
     -1 for a grid sample_grid refuses"""
@@ -740,6 +745,141 @@ class Context:
                                        _np_ptr(lam), _np_ptr(z), z.shape[0], z.shape[1], _np_ptr(sA) if sA is not None else None,
                                        _np_ptr(v), _np_ptr(u), _np_ptr(sn), _np_ptr(wn)), self._h)
         return v, u, sn, wn
+
+    # ---- the table path's stages (csrc/tables.hip), each alone: nle_table_* ----
+    def _dev64(self, a, what, n=None):
+        """`a` (array or tensor, or None) as a contiguous float64 device tensor of n entries"""
+        if a is None:
+            return None
+        torch = _torch()
+        t = torch.as_tensor(a, dtype=torch.float64, device=f"cuda:{self.device}").contiguous()
+        if n is not None and t.numel() != n:
+            raise NLEError(NLE_ERR_INVALID, f"{what}: need {n} doubles, got {t.numel()}")
+        return t
+
+    def _table_view(self, lum, nr, nc, rows, tables, hx, hy, c, who):
+        """the arguments every nle_table_* call that takes a view starts with, and (tensors to keep alive, grid, row0, nrows)"""
+        t, H, W = self._plane(lum)
+        row0, row1 = rows if rows is not None else (0, H)
+        g = sample_grid(H, W, nr, nc)
+        nR, nC, nrows = g["n_sel_rows"], g["n_sel_cols"], max(row1 - row0, 0)
+        keep = [t]
+        if tables is not None:
+            er, ecT, Ep = (self._dev64(a, who, n) for a, n in zip(tables, (nrows * nR, nC * W, 256 * nR * nC)))
+            keep += [er, ecT, Ep]
+        cv = self._dev64(c, who, nrows * W)
+        keep.append(cv)
+        self._sync_in()
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
+        args = [self._h, ptr(t), H, W, int(nr), int(nc), int(row0), int(row1), float(hx), float(hy)]
+        args += [ptr(a) for a in (keep[1:4] if tables is not None else (None, None, None))] + [ptr(cv)]
+        return args, keep, dict(g, H=H, W=W, row0=row0, nrows=nrows, p=nR * nC, ldp=(nR * nC + 63) & ~63)
+
+    def table_levels(self, x):
+        """check_levels over the float32 device tensor `x` (a view at any element offset): (bad, 16-bit tile mask)"""
+        if x.dtype != _torch().float32 or not x.is_cuda or not x.is_contiguous():
+            raise NLEError(NLE_ERR_INVALID, "table_levels: x must be contiguous float32 values on the device")
+        self._sync_in()
+        bad, mask = C.c_int(-1), C.c_uint(0)
+        _check(lib().nle_table_levels(self._h, C.c_void_p(x.data_ptr()), x.numel(), C.byref(bad), C.byref(mask)), self._h)
+        return bad.value, mask.value
+
+    def table_build(self, lum, nr, nc, hx, hy, rows=None, tables=None):
+        """what the view is (nle_table_build): dict(sorted, lev_t0, lev_nt, index_sums, layers_per_launch, er, ecT, Ep)"""
+        torch = _torch()
+        args, keep, g = self._table_view(lum, nr, nc, rows, tables, hx, hy, None, "table_build")
+        dev = keep[0].device
+        er = torch.empty((g["nrows"], g["n_sel_rows"]), dtype=torch.float64, device=dev)
+        ecT = torch.empty((g["n_sel_cols"], g["W"]), dtype=torch.float64, device=dev)
+        Ep = torch.empty((256, g["p"]), dtype=torch.float64, device=dev)
+        info = (C.c_int * 5)()
+        _check(lib().nle_table_build(*args, C.c_void_p(er.data_ptr()), C.c_void_p(ecT.data_ptr()), C.c_void_p(Ep.data_ptr()), info),
+               self._h)
+        return dict(sorted=bool(info[0]), lev_t0=info[1], lev_nt=info[2], index_sums=bool(info[3]), layers_per_launch=info[4],
+                    er=er, ecT=ecT, Ep=Ep)
+
+    def table_pass(self, lum, nr, nc, mode, rows=None, tables=None, hx=0.0, hy=0.0, c=None, w=None, x=None):
+        """one half-iteration of the table pass (nle_table_pass; mode 0 column sum, 1 reciprocal with w, 2 y = c x with the
+        full plane x): dict(z (ldp), y (nrows W), ws (the whole workspace: g, h, the partial rows), n (nrows nC 256))"""
+        torch = _torch()
+        args, keep, g = self._table_view(lum, nr, nc, rows, tables, hx, hy, c, "table_pass")
+        dev = keep[0].device
+        wv = self._dev64(w, "table_pass: w", g["p"])
+        xv = None if x is None else torch.as_tensor(x, dtype=torch.float32, device=dev).contiguous()
+        if xv is not None and xv.numel() != g["H"] * g["W"]:
+            raise NLEError(NLE_ERR_INVALID, "table_pass: x is the full H x W plane")
+        n_ws = int(lib().nle_table_workspace(g["n_sel_rows"], g["n_sel_cols"], max(g["nrows"], 1), 0))
+        ws = torch.empty(max(n_ws, 1), dtype=torch.float64, device=dev)
+        z = torch.empty(g["ldp"], dtype=torch.float64, device=dev)
+        y = torch.empty(g["nrows"] * g["W"], dtype=torch.float64, device=dev)
+        self._sync_in()
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None  # noqa: E731
+        _check(lib().nle_table_pass(*args, int(mode), ptr(wv), ptr(xv), ptr(y), ptr(ws), ws.numel(), ptr(z)), self._h)
+        return dict(z=z, y=y, ws=ws, n=g["nrows"] * g["n_sel_cols"] * 256)
+
+    def table_expand(self, lum, nr, nc, wl, c, rows=None, tables=None, hx=0.0, hy=0.0, round8=False, ostride=None):
+        """the expand half of apply for the nl weight vectors wl (nl x ldw): (g tables (nl, nrows, nC, 256), planes (nl, ostride))"""
+        torch = _torch()
+        args, keep, g = self._table_view(lum, nr, nc, rows, tables, hx, hy, c, "table_expand")
+        dev = keep[0].device
+        wl = torch.as_tensor(wl, dtype=torch.float64, device=dev).contiguous()
+        if wl.ndim != 2:
+            raise NLEError(NLE_ERR_INVALID, "table_expand: wl must be nl x ldw")
+        nl, ldw = int(wl.shape[0]), int(wl.shape[1])
+        ostride = g["nrows"] * g["W"] if ostride is None else int(ostride)
+        gws = torch.empty((nl, g["nrows"], g["n_sel_cols"], 256), dtype=torch.float64, device=dev)
+        out = torch.empty((nl, ostride), dtype=torch.float32, device=dev)
+        self._sync_in()
+        _check(lib().nle_table_expand(*args, C.c_void_p(wl.data_ptr()), ldw, nl, int(bool(round8)), C.c_void_p(gws.data_ptr()),
+                                      C.c_void_p(out.data_ptr()), ostride), self._h)
+        return gws, out
+
+    def table_gram(self, lum, nr, nc, c, rows=None, tables=None, hx=0.0, hy=0.0):
+        """sum over the non-sample pixels of rows [row0, row1) of c_i^2 k_i k_i^T through the tables: (Gk (p, p), workspace,
+        (rows per GEMM split, number of splits))"""
+        torch = _torch()
+        args, keep, g = self._table_view(lum, nr, nc, rows, tables, hx, hy, c, "table_gram")
+        dev = keep[0].device
+        n_ws = int(lib().nle_table_workspace(g["n_sel_rows"], g["n_sel_cols"], max(g["nrows"], 1), 1))
+        ws = torch.empty(max(n_ws, 1), dtype=torch.float64, device=dev)
+        Gk = torch.empty((g["p"], g["p"]), dtype=torch.float64, device=dev)
+        self._sync_in()
+        split = (C.c_int * 2)()
+        _check(lib().nle_table_gram(*args, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(Gk.data_ptr()), split), self._h)
+        return Gk, ws, (split[0], split[1])
+
+    def table_apply_small(self, m, D, Vrows, xA, resp, ldw, differs=None, m_same=None, xA_same=None):
+        """the p- and K-sized middle of apply on host operands.  D, Vrows: (p, ldk) with K = resp.shape[1] <= ldk logical
+        columns, resp: (L, K), differs: None, 0 or 1 -> (t (K), W' (L, ldw), YA (L, p))"""
+        torch = _torch()
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        resp = np.ascontiguousarray(np.atleast_2d(resp), dtype=np.float64)
+        (p, ldk), (L, K) = D.shape, resp.shape
+        dev = f"cuda:{self.device}"
+        d = {k: self._dev64(v, "table_apply_small") for k, v in dict(m=m, D=D, V=Vrows, xA=xA, resp=resp, ms=m_same, xs=xA_same).items()}
+        flag = None if differs is None else torch.tensor([int(differs)], dtype=torch.int32, device=dev)
+        t = torch.empty(max(K, 1), dtype=torch.float64, device=dev)
+        Wp = torch.empty((L, max(int(ldw), 1)), dtype=torch.float64, device=dev)
+        YA = torch.empty((L, p), dtype=torch.float64, device=dev)
+        self._sync_in()
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None  # noqa: E731
+        _check(lib().nle_table_apply_small(self._h, p, K, ldk, L, int(ldw), ptr(d["m"]), ptr(d["D"]), ptr(d["V"]), ptr(d["xA"]),
+                                           ptr(d["resp"]), ptr(t), ptr(Wp), ptr(YA), ptr(flag), ptr(d["ms"]), ptr(d["xs"])), self._h)
+        return t.cpu().numpy()[:K], Wp.cpu().numpy(), YA.cpu().numpy()
+
+    def table_scatter(self, loc, YA, Y, round8=False):
+        """Y[l, loc[a]] = (float)YA[l, a] where loc[a] >= 0, in place in the (L, ystride) float32 device tensor Y"""
+        torch = _torch()
+        dev = f"cuda:{self.device}"
+        YA = self._dev64(np.atleast_2d(YA), "table_scatter")
+        L, p = int(YA.shape[0]), int(YA.shape[1])
+        loc = torch.as_tensor(np.ascontiguousarray(loc, dtype=np.int64), device=dev)
+        if Y.dtype != torch.float32 or not Y.is_cuda or not Y.is_contiguous() or Y.ndim != 2 or Y.shape[0] != L or loc.numel() != p:
+            raise NLEError(NLE_ERR_INVALID, "table_scatter: Y must be an (L, ystride) float32 device tensor, loc p indices")
+        self._sync_in()
+        _check(lib().nle_table_scatter(self._h, p, L, C.c_void_p(loc.data_ptr()), C.c_void_p(YA.data_ptr()), C.c_void_p(Y.data_ptr()),
+                                       int(Y.shape[1]), int(bool(round8))), self._h)
+        return Y
 
     def gemm64s(self, m, n, kk, A, sA, B, sB, Cm, sC, dl=None, dk=None, dr=None, add=None, sadd=(0, 0)):
         """nle_gemm64s on float64 CUDA tensors, in place in Cm: A, B, Cm (and add) are taken as flat buffers whose entry

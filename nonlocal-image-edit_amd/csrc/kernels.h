@@ -321,7 +321,10 @@ struct TableView {
     int p, ldp;                    // samples; ldp = sink_pass_ld(p), the stride of the p-sized vectors
     int row0, nrows;
     const double *er, *ecT, *Ep;   // hist_tables
-    const double* cvec;            // c_i per local pixel (0 at sample pixels): the last Sinkhorn pass writes it
+    // c_i per local pixel: the last Sinkhorn pass writes it.  The rule for the sample pixels: no kernel uses c there -- the
+    // sorted rows leave them out, the LDS-atomic kernels (k_hist_pix, k_hist_dot, k_ghist_rows*) test the grid's predicate
+    // before they read -- so whatever the buffer holds at a sample pixel, a NaN included, reaches no sum and no output
+    const double* cvec;
     const SortedRows* sorted;      // null: the pixel kernels are the LDS-atomic ones (k_hist_pix, k_hist_dot, k_ghist_rows*)
 };
 
@@ -400,6 +403,8 @@ hipError_t scatter_samples(hipStream_t s, int p, int L, const long long* d_loc, 
 // Gram in sample space through the same tables; d_Gk: p x p
 size_t ghist_workspace_elems(GridSpec gs, int nrows_local);
 hipError_t gram_hist(hipStream_t s, const TableView& v, double* d_ws, double* d_Gk, LaunchObserver* obs = nullptr);
+// image rows per split and number of splits of gram_hist's GEMM on this view (the C or T part of d_ws holds nsplit products)
+void gram_hist_split(const TableView& v, int* ksplit, int* nsplit);
 
 // 8-bit BGR <-> Lab (colour.hip): d_lut = the fixed-point tables of nle_lab8_tables as one blob; d_lab / d_L optional outputs
 hipError_t bgr2lab8(hipStream_t s, const unsigned char* d_bgr, long long n, const double* d_lut, unsigned char* d_lab,

@@ -1,6 +1,7 @@
 // The literal decomposition (reference src/filter.cpp:480-502 as written) with Phi = K_AB^T B materialised, in fp32
 // (NLE_MODE_MATERIALISED) and in fp64 (generic64.hip: auto mode's fallback), its stages, the stage entry points that expose
-// exactly these, the four that expose fused.hip's launchers (nle_sample_*), and the micro-benchmarks of two of its kernels.
+// exactly these, the four that expose fused.hip's launchers (nle_sample_*), those that expose the table path's (nle_table_*),
+// and the micro-benchmarks of two of its kernels.
 #include "train.h"
 
 using namespace nlep;
@@ -446,6 +447,64 @@ void TrainPath::train_generic64(const Nystrom& ny) {
 
 }  // namespace nlep
 
+namespace {
+// nle_table_*: the TableView the table path's launchers take (tables.hip), made one of two ways.  Supplied: the caller's
+// tables on the device, no sorted rows, all 16 level tiles -- what the library runs beyond sorted_max_width() columns.
+// Built: a TableFilter constructed as train_tables constructs it (fetch_samples with the level check, hist_tables, sorted
+// rows, level-tile range, bandwidth predicates); the caller's row scalings, where given, are copied into it.
+struct TableArgs {
+    const float* d_lum;
+    int H, W, nRow, nCol, row0, row1;
+    double hx, hy;
+    const double *d_er, *d_ecT, *d_Ep, *d_cvec;
+};
+struct TableStage {
+    std::unique_ptr<TableFilter> built;
+    nlek::TableView view{};
+};
+TableStage table_stage(nle_ctx* ctx, const TableArgs& a) {
+    const GridSpec gs = checked_grid(a.H, a.W, a.nRow, a.nCol);
+    if (a.row0 < 0 || a.row1 <= a.row0 || a.row1 > a.H) throw Fail{NLE_ERR_INVALID, "need 0 <= row0 < row1 <= H"};
+    if (gs.nSelRows > 32) throw Fail{NLE_ERR_INVALID, "the table kernels take at most 32 sample rows, got " + std::to_string(gs.nSelRows)};
+    if (gs.nSelCols > 36) throw Fail{NLE_ERR_INVALID, "the table kernels take at most 36 sample columns, got " + std::to_string(gs.nSelCols)};
+    HIP_OK(hipSetDevice(ctx->device));
+    TableStage st;
+    const int nrows = a.row1 - a.row0;
+    if (a.d_er || a.d_ecT || a.d_Ep) {
+        if (!a.d_er || !a.d_ecT || !a.d_Ep) throw Fail{NLE_ERR_INVALID, "supplied tables: er, ecT and Ep go together"};
+        // the pixel kernels index their LDS tables with the level: the local rows must hold levels, as a built view's do
+        DevBuf<int> d_flag(2);
+        int fl[2] = {1, 0};
+        PROFILED(ctx, NLE_K_SMALL, nlek::check_levels(ctx->stream, a.d_lum + (size_t)a.row0 * a.W, (long long)nrows * a.W, d_flag.p));
+        HIP_OK(hipMemcpyAsync(fl, d_flag.p, sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        if (fl[0] != 0) throw Fail{NLE_ERR_INVALID, "the table kernels need local rows that are integer valued in [0, 255]"};
+        st.view = nlek::TableView{a.d_lum, gs,     gs.p(),  nlek::sink_pass_ld(gs.p()), a.row0, nrows,
+                                  a.d_er,  a.d_ecT, a.d_Ep, a.d_cvec,                   nullptr};
+        return st;
+    }
+    if (!(a.hx > 0) || !(a.hy > 0)) throw Fail{NLE_ERR_INVALID, "hx and hy must be > 0"};
+    FetchSpec spec;
+    spec.check_levels = true;
+    const SampleSet ss = fetch_samples(ctx, a.d_lum, gs, AffinityOpts{}, spec);
+    if (!ss.quantised) throw Fail{NLE_ERR_INVALID, "the table formulation needs a plane that is integer valued in [0, 255]"};
+    st.built = std::make_unique<TableFilter>(ctx, a.d_lum, ss, a.hx, a.hy, a.row0, nrows);
+    if (a.d_cvec)
+        HIP_OK(hipMemcpyAsync(st.built->c.p, a.d_cvec, st.built->c.n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    st.view = st.built->view();
+    return st;
+}
+// the sentinel of the nle_table_* entry points: every byte 0xff is a NaN in fp64 and in fp32
+template <typename T>
+void fill_nan(nle_ctx* ctx, T* d, size_t n) {
+    if (d && n) HIP_OK(hipMemsetAsync(d, 0xff, n * sizeof(T), ctx->stream));
+}
+void drain(nle_ctx* ctx) {
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    prof_flush(ctx);
+}
+}  // namespace
+
 // ------------------------------------------------------------------------------ C ABI
 extern "C" {
 
@@ -639,6 +698,137 @@ int nle_sample_update(nle_ctx* ctx, int p, int r, int chol, int recip, const dou
         HIP_OK(hipMemcpyAsync(h_w_next, d_out.p + p, p * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(hipStreamSynchronize(ctx->stream));
         prof_flush(ctx);
+    });
+}
+
+// ---- the table path's stages (tables.hip), each alone: the launchers train_tables and apply_sample_space call.  Every
+// workspace and output is filled with the NaN sentinel before the launch ----
+#define NLE_TABLE_PARAMS                                                                                                    \
+    nle_ctx *ctx, const float *d_lum, int H, int W, int n_row_samples, int n_col_samples, int row0, int row1, double hx,   \
+        double hy, const double *d_er, const double *d_ecT, const double *d_Ep, const double *d_cvec
+#define NLE_TABLE_ARGS TableArgs{d_lum, H, W, n_row_samples, n_col_samples, row0, row1, hx, hy, d_er, d_ecT, d_Ep, d_cvec}
+
+long long nle_table_workspace(int n_sel_rows, int n_sel_cols, int nrows, int gram) {
+    if (n_sel_rows < 1 || n_sel_rows > 32 || n_sel_cols < 1 || n_sel_cols > 36 || nrows < 1) return -1;
+    GridSpec gs{};
+    gs.nSelRows = n_sel_rows, gs.nSelCols = n_sel_cols;
+    return (long long)(gram ? nlek::ghist_workspace_elems(gs, nrows) : nlek::hist_tiled_workspace_elems(gs, nrows));
+}
+
+int nle_table_levels(nle_ctx* ctx, const float* d_x, long long n, int* h_bad, unsigned* h_mask) {
+    if (!ctx || !d_x || n < 1 || !h_bad || !h_mask) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        HIP_OK(hipSetDevice(ctx->device));
+        DevBuf<int> d_flag(2);
+        int fl[2] = {0, 0};
+        PROFILED(ctx, NLE_K_SMALL, nlek::check_levels(ctx->stream, d_x, n, d_flag.p));
+        HIP_OK(hipMemcpyAsync(fl, d_flag.p, sizeof fl, hipMemcpyDeviceToHost, ctx->stream));
+        drain(ctx);
+        *h_bad = fl[0], *h_mask = (unsigned)fl[1];
+    });
+}
+
+int nle_table_build(NLE_TABLE_PARAMS, double* d_er_out, double* d_ecT_out, double* d_Ep_out, int* h_info) {
+    if (!ctx || !d_lum || !h_info) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        const TableStage st = table_stage(ctx, NLE_TABLE_ARGS);
+        const nlek::TableView& v = st.view;
+        h_info[0] = v.sorted ? 1 : 0;
+        h_info[1] = v.sorted ? v.sorted->lev_t0 : 0;
+        h_info[2] = v.sorted ? v.sorted->lev_nt : 16;
+        h_info[3] = (v.sorted && v.sorted->E2) ? 1 : 0;
+        h_info[4] = nlek::apply_layers_per_launch(v);
+        const size_t n_er = (size_t)v.nrows * v.gs.nSelRows, n_ec = (size_t)v.gs.nSelCols * v.gs.W, n_ep = (size_t)256 * v.p;
+        if (d_er_out) HIP_OK(hipMemcpyAsync(d_er_out, v.er, n_er * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        if (d_ecT_out) HIP_OK(hipMemcpyAsync(d_ecT_out, v.ecT, n_ec * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        if (d_Ep_out) HIP_OK(hipMemcpyAsync(d_Ep_out, v.Ep, n_ep * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        drain(ctx);
+    });
+}
+
+int nle_table_pass(NLE_TABLE_PARAMS, int mode, const double* d_w, const float* d_xvec, double* d_y, double* d_ws,
+                   long long ws_elems, double* d_z) {
+    if (!ctx || !d_lum || !d_ws || !d_z) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (mode != nlek::ROWPASS_COLSUM && mode != nlek::ROWPASS_RECIP && mode != nlek::ROWPASS_XVEC)
+            throw Fail{NLE_ERR_INVALID, "nle_table_pass: mode is 0 (column sum), 1 (reciprocal) or 2 (x vector)"};
+        if (mode == nlek::ROWPASS_RECIP && !d_w) throw Fail{NLE_ERR_INVALID, "nle_table_pass: the reciprocal pass needs w"};
+        if (mode == nlek::ROWPASS_XVEC && (!d_xvec || !d_cvec)) throw Fail{NLE_ERR_INVALID, "nle_table_pass: the x-vector pass needs x and c"};
+        const TableStage st = table_stage(ctx, NLE_TABLE_ARGS);
+        const nlek::TableView& v = st.view;
+        const size_t need = nlek::hist_tiled_workspace_elems(v.gs, v.nrows);
+        if (ws_elems < (long long)need) throw Fail{NLE_ERR_INVALID, "nle_table_pass: the workspace is smaller than nle_table_workspace says"};
+        fill_nan(ctx, d_ws, need);
+        fill_nan(ctx, d_z, (size_t)v.ldp);
+        fill_nan(ctx, d_y, (size_t)v.nrows * v.gs.W);
+        ProfObserver obs(ctx, kProfTablePass);
+        HIP_OK(nlek::sink_hist_tiled(ctx->stream, mode, v, d_w, NLE_EPS, d_y, d_ws, d_z, &obs, d_xvec));
+        drain(ctx);
+    });
+}
+
+int nle_table_expand(NLE_TABLE_PARAMS, const double* d_wl, int ldw, int nl, int round8, double* d_gws, float* d_out,
+                     long long ostride) {
+    if (!ctx || !d_lum || !d_wl || !d_gws || !d_out || !d_cvec) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        const TableStage st = table_stage(ctx, NLE_TABLE_ARGS);
+        const nlek::TableView& v = st.view;
+        const int lmax = nlek::apply_layers_per_launch(v);
+        if (nl < 1 || nl > lmax)
+            throw Fail{NLE_ERR_INVALID, "nle_table_expand: one launch takes 1 .. " + std::to_string(lmax) + " layers on this grid, got " + std::to_string(nl)};
+        if (ldw < v.p || ostride < (long long)v.nrows * v.gs.W) throw Fail{NLE_ERR_INVALID, "nle_table_expand: need ldw >= p and ostride >= nrows W"};
+        fill_nan(ctx, d_gws, (size_t)nl * v.nrows * 256 * v.gs.nSelCols);
+        fill_nan(ctx, d_out, (size_t)nl * ostride);
+        ProfObserver obs(ctx, kProfTableExpand);
+        HIP_OK(nlek::apply_hist_layers(ctx->stream, v, d_wl, ldw, nl, d_gws, d_out, ostride, &obs, round8 != 0));
+        drain(ctx);
+    });
+}
+
+int nle_table_gram(NLE_TABLE_PARAMS, double* d_ws, long long ws_elems, double* d_Gk, int* h_split) {
+    if (!ctx || !d_lum || !d_cvec || !d_ws || !d_Gk || !h_split) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        const TableStage st = table_stage(ctx, NLE_TABLE_ARGS);
+        const nlek::TableView& v = st.view;
+        const size_t need = nlek::ghist_workspace_elems(v.gs, v.nrows);
+        if (ws_elems < (long long)need) throw Fail{NLE_ERR_INVALID, "nle_table_gram: the workspace is smaller than nle_table_workspace says"};
+        fill_nan(ctx, d_ws, need);
+        fill_nan(ctx, d_Gk, (size_t)v.p * v.p);
+        nlek::gram_hist_split(v, &h_split[0], &h_split[1]);
+        ProfObserver obs(ctx, kProfTableGram);
+        HIP_OK(nlek::gram_hist(ctx->stream, v, d_ws, d_Gk, &obs));
+        drain(ctx);
+    });
+}
+#undef NLE_TABLE_PARAMS
+#undef NLE_TABLE_ARGS
+
+int nle_table_apply_small(nle_ctx* ctx, int p, int K, int ldk, int L, int ldw, const double* d_m, const double* d_D,
+                          const double* d_Vrows, const double* d_xA, const double* d_resp, double* d_t, double* d_Wp, double* d_YA,
+                          const int* d_differs, const double* d_m_same, const double* d_xA_same) {
+    if (!ctx || !d_m || !d_D || !d_Vrows || !d_xA || !d_resp || !d_t || !d_Wp || !d_YA) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (K > 128) throw Fail{NLE_ERR_INVALID, "nle_table_apply_small: at most 128 eigenvectors, got " + std::to_string(K)};
+        if (p < 1 || p > 32 * 36 || K < 1 || L < 1 || ldk < K || ldw < p)
+            throw Fail{NLE_ERR_INVALID, "nle_table_apply_small: need 1 <= p <= 32 x 36, 1 <= K <= ldk, L >= 1, ldw >= p"};
+        if (d_differs && (!d_m_same || !d_xA_same)) throw Fail{NLE_ERR_INVALID, "nle_table_apply_small: the flag needs the vectors it selects"};
+        HIP_OK(hipSetDevice(ctx->device));
+        fill_nan(ctx, d_t, (size_t)K);
+        fill_nan(ctx, d_Wp, (size_t)L * ldw);
+        fill_nan(ctx, d_YA, (size_t)L * p);
+        PROFILED(ctx, NLE_K_SMALL, nlek::apply_small(ctx->stream, p, K, ldk, L, ldw, d_m, d_D, d_Vrows, d_xA, d_resp, d_t, d_Wp, d_YA,
+                                                     d_differs, d_m_same, d_xA_same));
+        drain(ctx);
+    });
+}
+
+int nle_table_scatter(nle_ctx* ctx, int p, int L, const long long* d_loc, const double* d_YA, float* d_Y, long long ystride,
+                      int round8) {
+    if (!ctx || !d_loc || !d_YA || !d_Y || p < 1 || L < 1 || ystride < 1) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        HIP_OK(hipSetDevice(ctx->device));
+        PROFILED(ctx, NLE_K_SMALL, nlek::scatter_samples(ctx->stream, p, L, d_loc, d_YA, d_Y, ystride, round8 != 0));
+        drain(ctx);
     });
 }
 

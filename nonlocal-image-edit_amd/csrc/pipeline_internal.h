@@ -322,6 +322,13 @@ struct ProfObserver : nlek::LaunchObserver {
     ~ProfObserver() override { end(); }
 };
 
+// which timed kernel id each sub-kernel of the table path's composite launchers is booked under (SUB_HIST_*, SUB_GHIST_*): one
+// definition for the trains, the applies and the nle_table_* stage entry points
+inline constexpr int kProfTablePass[4] = {NLE_K_SINK_TABLES, NLE_K_SINKHORN_PASS, NLE_K_REDUCE, NLE_K_REDUCE};
+inline constexpr int kProfTableReduce[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_REDUCE, NLE_K_REDUCE, NLE_K_REDUCE};
+inline constexpr int kProfTableExpand[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_EXPAND, NLE_K_REDUCE, NLE_K_REDUCE};
+inline constexpr int kProfTableGram[4] = {NLE_K_GRAM_ROWS, NLE_K_SMALL, NLE_K_GRAM_GEMM, NLE_K_SMALL};
+
 // resolve pending records; the caller has synchronised the stream
 inline void prof_flush(nle_ctx* c) {
     for (auto& r : c->prof_pending) {

@@ -209,8 +209,7 @@ void TrainPath::train_tables(const SolveKa& solve) {
     SampleSinkhorn sk(c, p, t->P64, T);
     tr.mark("ss: alloc+upload");
     auto pass_pixels = [&](int mode, bool last) {  // the N-sized half: the local column sums, straight into d_z
-        static const int kmap[4] = {NLE_K_SINK_TABLES, NLE_K_SINKHORN_PASS, NLE_K_REDUCE, NLE_K_REDUCE};
-        ProfObserver obs(c, kmap);
+        ProfObserver obs(c, kProfTablePass);
         HIP_OK(nlek::sink_hist_tiled(c->stream, mode, view, sk.d_w.p, NLE_EPS, last ? t->c.p : nullptr, d_hws.p, d_z.p, &obs));
     };
     const Nystrom ny = sk.run(solve, pass_pixels, d_z.p, 1);
@@ -228,8 +227,7 @@ void TrainPath::train_tables(const SolveKa& solve) {
     auto enqueue_gram = [&] {
         d_gpart.alloc(nlek::ghist_workspace_elems(ss.gs, t->nrows));
         {
-            static const int gmap[4] = {NLE_K_GRAM_ROWS, NLE_K_SMALL, NLE_K_GRAM_GEMM, NLE_K_SMALL};
-            ProfObserver obs(c, gmap);
+            ProfObserver obs(c, kProfTableGram);
             HIP_OK(nlek::gram_hist(c->stream, view, d_gpart.p, d_G.p, &obs));
         }
         // The reduce half of apply for the plane in hand, m = K^T (c o x): it needs the row scalings and the plane, nothing
@@ -240,8 +238,7 @@ void TrainPath::train_tables(const SolveKa& solve) {
             t->m_train.alloc(t->P64);
             t->xA_train.alloc(p);
             {
-                static const int rmap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_REDUCE, NLE_K_REDUCE, NLE_K_REDUCE};
-                ProfObserver obs(c, rmap);
+                ProfObserver obs(c, kProfTableReduce);
                 HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_hws.p,
                                              t->m_train.p, &obs, d_lum));
             }
@@ -483,8 +480,7 @@ void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L 
                                                             (long long)t.nrows * t.gs.W, d_differs.p));
     }
     {
-        static const int rmap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_REDUCE, NLE_K_REDUCE, NLE_K_REDUCE};
-        ProfObserver obs(c, rmap);
+        ProfObserver obs(c, kProfTableReduce);
         HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_ws.p, d_m.p, &obs, d_x,
                                      d_differs.p));
     }
@@ -499,14 +495,13 @@ void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L 
     }
     PROFILED(c, NLE_K_SMALL, nlek::apply_small(c->stream, p, K, t.ldd, L, P64, d_m.p, t.D.p, t.Vrows.p, d_xA.p, d_resp.p,
                                                d_t.p, d_Wp.p, d_YA.p, d_differs.p, t.m_train.p, t.xA_train.p));
-    static const int emap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_EXPAND, NLE_K_REDUCE, NLE_K_REDUCE};
     int lb = std::min(L, nlek::apply_layers_per_launch(view));
     if (group > 0) lb = std::min(lb, group);
     DevBuf<double> d_gws((size_t)lb * t.nrows * 256 * t.gs.nSelCols);
     for (int l = 0; l < L; l += lb) {
         const int nl = std::min(lb, L - l);
         {
-            ProfObserver obs(c, emap);
+            ProfObserver obs(c, kProfTableExpand);
             HIP_OK(nlek::apply_hist_layers(c->stream, view, d_Wp.p + (size_t)l * P64, P64, nl, d_gws.p, d_y + (size_t)l * M, M,
                                            &obs, round8));
         }
@@ -532,12 +527,11 @@ void apply_sample_space_planes(nle_filter* f, const float* const* d_x, int P, co
     DevBuf<double> d_ws(nlek::apply_reduce_planes_workspace_elems(t.gs, t.nrows, NP)), d_m((size_t)NP * P64),
         d_resp((size_t)R * K), d_t(K), d_xA(p), d_Wp((size_t)R * P64), d_YA((size_t)R * p);
     HIP_OK(hipMemcpyAsync(d_resp.p, h_g, (size_t)R * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    static const int rmap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_REDUCE, NLE_K_REDUCE, NLE_K_REDUCE};
     int j = 0;  // first response of the plane in hand
     for (int m0 = 0; m0 < P; m0 += NP) {
         const int np = std::min(NP, P - m0);
         {
-            ProfObserver obs(c, rmap);
+            ProfObserver obs(c, kProfTableReduce);
             if (np > 1) HIP_OK(nlek::apply_reduce_planes(c->stream, view, d_x + m0, np, d_ws.p, d_m.p, &obs));
             else HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_ws.p, d_m.p, &obs, d_x[m0]));
         }
@@ -550,13 +544,12 @@ void apply_sample_space_planes(nle_filter* f, const float* const* d_x, int P, co
             j += L;
         }
     }
-    static const int emap[4] = {NLE_K_SINK_TABLES, NLE_K_APPLY_EXPAND, NLE_K_REDUCE, NLE_K_REDUCE};
     const int lb = std::min(R, nlek::apply_layers_per_launch(view));
     DevBuf<double> d_gws((size_t)lb * t.nrows * 256 * t.gs.nSelCols);
     for (int l = 0; l < R; l += lb) {
         const int nl = std::min(lb, R - l);
         {
-            ProfObserver obs(c, emap);
+            ProfObserver obs(c, kProfTableExpand);
             HIP_OK(nlek::apply_hist_layers(c->stream, view, d_Wp.p + (size_t)l * P64, P64, nl, d_gws.p, d_y + (size_t)l * ystride,
                                            ystride, &obs, round8));
         }

@@ -270,8 +270,8 @@ __global__ __launch_bounds__(kPixThreads) void k_hist_pix(int mode, const float*
 #pragma unroll
         for (int b = 0; b < NC; ++b) e[b] = ecT[(size_t)b * W + c];
         double y = 1.0;
-        if (mode == ROWPASS_XVEC) {  // apply: y_i = c_i x_i (c is 0 at sample pixels)
-            y = cvec[(size_t)lrow * W + c] * (double)xvec[(size_t)r * W + c];
+        if (mode == ROWPASS_XVEC) {  // apply: y_i = c_i x_i; c at a sample pixel is not read (kernels.h)
+            y = smp ? 0.0 : cvec[(size_t)lrow * W + c] * (double)xvec[(size_t)r * W + c];
         } else if (mode == ROWPASS_RECIP) {
             double gv[NC];
 #pragma unroll
@@ -328,9 +328,13 @@ __global__ __launch_bounds__(kDotThreads) void k_hist_dot(const float* __restric
         for (int i = tid; i < n; i += kDotThreads) sg[l * TS + (i & (kLevels - 1)) * NS + i / kLevels] = grow[i];  // b-major -> level-major
     }
     __syncthreads();
+    const int dr = r - gs.rowOff;
+    const bool sample_row = dr >= 0 && (dr % gs.rowStep) == 0 && (dr / gs.rowStep) < gs.nSelRows;
     for (int c = tid; c < W; c += kDotThreads) {
         const int x = (int)lum[(size_t)r * W + c];
-        const double cv = cvec[(size_t)lrow * W + c];
+        const int dc = c - gs.colOff;
+        const bool smp = sample_row && dc >= 0 && (dc % gs.colStep) == 0 && (dc / gs.colStep) < NC;
+        const double cv = smp ? 0.0 : cvec[(size_t)lrow * W + c];  // c at a sample pixel is nobody's to read (kernels.h)
         double e[NC];
 #pragma unroll
         for (int b = 0; b < NC; ++b) e[b] = ecT[(size_t)b * W + c];
@@ -696,10 +700,14 @@ __global__ __launch_bounds__(kGhistRowsThreads) void k_ghist_rows(const float* _
     const int tid = threadIdx.x, lrow = blockIdx.x, r = row0 + lrow;
     for (int i = tid; i < kLevels * NP; i += kGhistRowsThreads) A[i] = 0.0;
     __syncthreads();
+    const int dr = r - gs.rowOff;
+    const bool sample_row = dr >= 0 && (dr % gs.rowStep) == 0 && (dr / gs.rowStep) < gs.nSelRows;
     for (int c0 = 0; c0 < W; c0 += kGhistRowsThreads) {  // wave-uniform trip count: the body uses cross-lane sums
         const bool inside = c0 + tid < W;
         const int c = inside ? c0 + tid : W - 1;
-        const double cf = inside ? cvec[(size_t)lrow * W + c] : 0.0;  // 0 at sample pixels
+        const int dc = c - gs.colOff;
+        const bool smp = sample_row && dc >= 0 && (dc % gs.colStep) == 0 && (dc / gs.colStep) < nC;
+        const double cf = (inside && !smp) ? cvec[(size_t)lrow * W + c] : 0.0;  // c at a sample pixel is not read (kernels.h)
         const int x = (int)lum[(size_t)r * W + c];
         double q[11];
 #pragma unroll
@@ -749,10 +757,14 @@ __global__ __launch_bounds__(kGhistRowsThreads) void k_ghist_rows_chunk(const fl
     const int tid = threadIdx.x, lrow = blockIdx.x, r = row0 + lrow;
     for (int i = tid; i < kLevels * npairs; i += kGhistRowsThreads) A[i] = 0.0;
     __syncthreads();
+    const int dr = r - gs.rowOff;
+    const bool sample_row = dr >= 0 && (dr % gs.rowStep) == 0 && (dr / gs.rowStep) < gs.nSelRows;
     for (int c0 = 0; c0 < W; c0 += kGhistRowsThreads) {  // wave-uniform trip count: the body uses cross-lane sums
         const bool inside = c0 + tid < W;
         const int c = inside ? c0 + tid : W - 1;
-        const double cf = inside ? cvec[(size_t)lrow * W + c] : 0.0;  // 0 at sample pixels
+        const int dc = c - gs.colOff;
+        const bool smp = sample_row && dc >= 0 && (dc % gs.colStep) == 0 && (dc / gs.colStep) < nC;
+        const double cf = (inside && !smp) ? cvec[(size_t)lrow * W + c] : 0.0;  // c at a sample pixel is not read (kernels.h)
         const int x = (int)lum[(size_t)r * W + c];
         double q[kGhistMaxCols];
 #pragma unroll
@@ -987,6 +999,13 @@ size_t ghist_workspace_elems(GridSpec gs, int nrows_local) {
     ghist_split((long long)N2, (int)ldm2, nrows_local, &ks, &ns);
     const size_t sums = (size_t)nrows_local * N2 + (size_t)nrows_local * ldm2 + (size_t)ns * ldm2 * N2;
     return std::max(pairs, sums);
+}
+
+// the split of the image rows gram_hist's GEMM takes for this view, in the form it takes (pairs or index sums)
+void gram_hist_split(const TableView& v, int* ksplit, int* nsplit) {
+    const int nC = v.gs.nSelCols, nR = v.gs.nSelRows;
+    if (v.sorted != nullptr && v.sorted->E2 != nullptr) ghist_split((long long)kLevels * (2 * nC - 1), gsum_ldm(nR), v.nrows, ksplit, nsplit);
+    else ghist_split((long long)kLevels * (nC * (nC + 1) / 2), ghist_ldm(nR), v.nrows, ksplit, nsplit);
 }
 
 // d_ws: ghist_workspace_elems doubles; d_Gk: p x p doubles (full symmetric matrix of this rank's rows)
