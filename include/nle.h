@@ -671,6 +671,32 @@ int nle_lab2bgr8_planes(nle_ctx* ctx, const unsigned char* d_lab, const float* d
 /* cv::split + convertTo of one channel (0, 1, 2) of an interleaved 8-bit 3-channel image (:363,376-378) */
 int nle_lab8_channel(nle_ctx* ctx, const unsigned char* d_lab, long long n, int channel, float* d_out);
 
+/* ---- deep colour (new in this build: the reference is 8-bit only, so this text and DESIGN.md section 3.13 are the definition) ---- */
+/* 16-bit sRGB <-> float Lab, fp64 per pixel, every operation rounded on its own (no fma) and in the order written.
+ * Tables (host only, no ctx): h_lin[c], c = 0 .. 65535: with v = c / 65535, v <= 0.04045 ? v / 12.92 : pow((v + 0.055) / 1.055,
+ * 2.4).  h_thr[0] = -inf, h_thr[c] = the same curve at (c - 0.5) / 65535: strictly increasing; the encoding is DEFINED through
+ * it, code(v) = (number of c with h_thr[c] <= v) - 1, a NaN gives 0 -- no pow on the device, no rounding ties.  h_coeffs[0 .. 9):
+ * OpenCV's sRGB -> XYZ (D65) matrix, rows X, Y, Z and columns R, G, B, each row divided by its sum (m0 + m1) + m2 (white goes
+ * to X = Y = Z = 1); h_coeffs[9 .. 18): the fp64 inverse of that matrix, rows R, G, B and columns X, Y, Z.
+ * nle_bgr16_to_lab: d_bgr n x 3 uint16 (B, G, R interleaved) -> fp32 planes on the 8-bit path's scales, so that hy, the
+ * chroma bandwidth and the layer weights mean what they mean there:
+ *   t_X = (m0 lin[R] + m1 lin[G]) + m2 lin[B] with row X of the matrix, t_Y and t_Z alike
+ *   f(t) = t > 216 / 24389 ? cbrt(t) : ((24389 / 27) t + 16) / 116
+ *   L = ((116 f_Y - 16) 255) / 100,  a = 500 (f_X - f_Y) + 128,  b = 200 (f_Y - f_Z) + 128, each rounded once to fp32
+ *   guide = round-half-even of the fp64 L, clamped to [0, 255]: the integer plane a train takes (the table path)
+ * d_a, d_b and d_guide may each be NULL.
+ * nle_lab_to_bgr16: L' = L > 0 ? (L < 255 ? L : 255) : 0 (a NaN counts as 0); a and b are not clamped;
+ *   f_Y = ((L' 100) / 255 + 16) / 116,  f_X = f_Y + (a - 128) / 500,  f_Z = f_Y - (b - 128) / 200
+ *   t = f > 6 / 29 ? (f f) f : ((116 f - 16) 27) / 24389
+ *   channel = code((i0 t_X + i1 t_Y) + i2 t_Z) with its row of the inverse matrix: out-of-gamut values saturate at 0 and 65535.
+ * The forward direction followed by fp32 storage and the inverse is the identity on every grey and on millions of random
+ * triples (tests/test_deep_colour.py): fp32 planes lose nothing of a 16-bit image.
+ * NLE_ERR_INVALID with a message, nothing enqueued and the ctx left usable: NULL d_bgr or d_L (either direction; the inverse
+ * needs d_a and d_b too), n <= 0.  The tables go to the device once per ctx, on first use. */
+int nle_srgb16_tables(double* h_lin /*65536*/, double* h_thr /*65536*/, double* h_coeffs /*18*/);
+int nle_bgr16_to_lab(nle_ctx* ctx, const unsigned short* d_bgr, long long n, float* d_L, float* d_a, float* d_b, float* d_guide);
+int nle_lab_to_bgr16(nle_ctx* ctx, const float* d_L, const float* d_a, const float* d_b, long long n, unsigned short* d_bgr);
+
 /* ---- denoise wrapper (src/denoise.cpp, src/filter.cpp:349-410,521-538): the bilateral prefilter ------------- */
 /* cv::bilateralFilter(src, dst, -1, sigmaColor, sigmaSpace, BORDER_DEFAULT) on a single-channel 8-bit plane, as
  * OpenCV documents it for CV_8UC1: radius = round(1.5 sigmaSpace) >= 1, circular window, fp32 weights

@@ -101,8 +101,9 @@ struct Permutation {
     int size() const { return (int)idx.size(); }
 };
 
-// continuous cv::Mat stand-in: ROW-major, interleaved channels; depth CV_8U or CV_64F
-enum { NLE_8U = 0, NLE_64F = 6 };
+// continuous cv::Mat stand-in: ROW-major, interleaved channels; depth CV_8U, CV_16U (deep-colour images: imread16,
+// trainForEnhancement, enhance) or CV_64F
+enum { NLE_8U = 0, NLE_16U = 2, NLE_64F = 6 };
 const int OPENCV_MAT_TYPE = NLE_64F;  // include/filter.hpp:13
 class Image {
 public:
@@ -110,7 +111,7 @@ public:
     Image() = default;
     Image(int r, int c, int depth, int channels = 1)
         : rows(r), cols(c), depth_(depth), ch_(channels),
-          buf_((size_t)r * c * channels * (depth == NLE_64F ? 8 : 1)) {}
+          buf_((size_t)r * c * channels * (depth == NLE_64F ? 8 : depth == NLE_16U ? 2 : 1)) {}
     int channels() const { return ch_; }
     int depth() const { return depth_; }
     size_t total() const { return (size_t)rows * cols; }
@@ -179,6 +180,11 @@ public:
     void trainForEnhancement(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
                              int nSinkhornIter = 10, int nEigenVectors = 5);
     Image enhance(const Image& I, const std::vector<DType>& weights) const;
+    // Deep colour (new here): both also take a 16UC3 image (imread16).  The train converts 16-bit
+    // sRGB to float Lab on the device and runs on the guide, L rounded to the 256 levels of the 8-bit path (patchRadius,
+    // sampler, exact and chromaBandwidth apply as they do there; chroma takes a and b rounded the same way); enhance applies
+    // the filter to the unrounded L and returns a 16UC3 image: nothing is rounded to 8 bits.  One device; enhanceRegions,
+    // trainForDenoise and denoise throw for a 16-bit image.
     // region edits (new here; nle_apply_regions in nle.h states the rule): enhance with layer weights of its own for every
     // scribbled region.  strokes[m]: a one-channel 8-bit image of I's size, a pixel belongs to the stroke where its byte is
     // >= 128; regionWeights[m]: the weights of region m, as many as `weights`, which is the background's row.  Each stroke

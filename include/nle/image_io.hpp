@@ -10,5 +10,9 @@
 
 namespace nle {
 Image imread(const std::string& path);                  // empty Image on failure (like cv::imread)
-bool imwrite(const std::string& path, const Image& bgr);  // false on failure
+// deep colour: the same files as 16UC3 BGR.  A PNG with 16-bit samples (grey / RGB / with alpha, dropped) keeps every
+// sample whole; whatever the readers decode to 8 bits is widened x257.  imread itself keeps only the high byte of such a PNG.
+Image imread16(const std::string& path);
+// false on failure.  A 16UC3 image goes to a 16-bit RGB PNG (big-endian samples, "stored" blocks); to any other extension: false
+bool imwrite(const std::string& path, const Image& bgr);
 }  // namespace nle

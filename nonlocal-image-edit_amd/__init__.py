@@ -123,6 +123,16 @@ def lab8_inverse_tables():
     return yf.reshape(256, 2), ab, ig, k.reshape(3, 3)
 
 
+def srgb16_tables():
+    """tables of the 16-bit sRGB <-> float Lab conversion (nle_srgb16_tables): lin[65536], thr[65536] (thr[0] = -inf),
+    forward[3][3] (rows X, Y, Z; columns R, G, B), inverse[3][3] (rows R, G, B; columns X, Y, Z), all float64"""
+    lin = np.zeros(65536, dtype=np.float64)
+    thr = np.zeros(65536, dtype=np.float64)
+    k = np.zeros(18, dtype=np.float64)
+    _check(lib().nle_srgb16_tables(_np_ptr(lin), _np_ptr(thr), _np_ptr(k)))
+    return lin, thr, k[:9].reshape(3, 3).copy(), k[9:].reshape(3, 3).copy()
+
+
 def sample_grid(H, W, n_row_samples, n_col_samples):
     """`samplePixels` (src/filter.cpp:56-80) in closed form.
     Returns dict(row_step,row_off,n_sel_rows,col_step,col_off,n_sel_cols)."""
@@ -921,6 +931,42 @@ class Context:
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         _check(lib().nle_lab2bgr8_planes(self._h, C.c_void_p(lab.data_ptr()), ptr(L), ptr(a), ptr(b), H * W,
                                          C.c_void_p(out.data_ptr())), self._h)
+        return out
+
+    # ---- deep colour: 16-bit sRGB <-> float Lab (device tensors; 16-bit images as torch.uint16) ----
+    def _u16(self, bgr):
+        """an (..., 3) 16-bit BGR image on the device, contiguous (numpy uint16 or a torch.uint16 tensor)"""
+        torch = _torch()
+        if isinstance(bgr, np.ndarray):
+            bgr = torch.from_numpy(np.array(bgr, dtype=np.uint16, order="C"))  # a copy: the caller's array may be read-only
+        if bgr.dtype != torch.uint16 or bgr.shape[-1] != 3:
+            raise NLEError(NLE_ERR_INVALID, "a 16-bit image is (..., 3) uint16 in B, G, R order")
+        return bgr.to(f"cuda:{self.device}").contiguous()
+
+    def bgr16_to_lab(self, bgr, want_ab=True, want_guide=True):
+        """nle_bgr16_to_lab on an (..., 3) uint16 BGR image: (L, a, b, guide) float32 planes of the image's leading shape,
+        a and b None without want_ab, guide None without want_guide"""
+        torch = _torch()
+        t = self._u16(bgr)
+        self._sync_in()
+        shape, n = t.shape[:-1], t.numel() // 3
+        new = lambda: torch.empty(shape, dtype=torch.float32, device=t.device)  # noqa: E731
+        L, a, b, g = new(), (new() if want_ab else None), (new() if want_ab else None), (new() if want_guide else None)
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
+        _check(lib().nle_bgr16_to_lab(self._h, ptr(t), n, ptr(L), ptr(a), ptr(b), ptr(g)), self._h)
+        return L, a, b, g
+
+    def lab_to_bgr16(self, L, a, b):
+        """nle_lab_to_bgr16 on float32 planes of one shape: the (..., 3) torch.uint16 BGR image"""
+        torch = _torch()
+        dev = f"cuda:{self.device}"
+        L, a, b = (torch.as_tensor(x, dtype=torch.float32, device=dev).contiguous() for x in (L, a, b))
+        if a.shape != L.shape or b.shape != L.shape:
+            raise NLEError(NLE_ERR_INVALID, "L, a and b must have one shape")
+        self._sync_in()
+        out = torch.empty(tuple(L.shape) + (3,), dtype=torch.uint16, device=L.device)
+        _check(lib().nle_lab_to_bgr16(self._h, C.c_void_p(L.data_ptr()), C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                                      L.numel(), C.c_void_p(out.data_ptr())), self._h)
         return out
 
     def bilateral8(self, plane, sigma_color, sigma_space):

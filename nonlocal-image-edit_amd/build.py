@@ -22,7 +22,7 @@ LIBDIR = os.path.join(HERE, "lib")
 BINDIR = os.path.join(HERE, "bin")
 LIB = os.path.join(LIBDIR, "libnle_hip.so")
 
-LIB_SOURCES = ["kernels.hip", "tsgemm_bf16x3.hip", "fused.hip", "tables.hip", "sorted.hip", "sorted_planes.hip", "generic64.hip", "patch.hip", "sampler.hip", "exact.hip", "resid.hip", "tridiag.hip", "dense64.hip", "colour.hip", "region.hip", "pipeline.hip", "literal.hip", "sample_space.hip", "exact_train.hip", "samples.hip", "ortho.hip", "abi_ctx.hip", "devsolve.hip", "eigen_sym.cpp", "eigen_reduce.cpp", "eigen_tridiag.cpp", "host_dense.cpp", "lanczos.cpp", "lab8_tables.cpp"]
+LIB_SOURCES = ["kernels.hip", "tsgemm_bf16x3.hip", "fused.hip", "tables.hip", "sorted.hip", "sorted_planes.hip", "generic64.hip", "patch.hip", "sampler.hip", "exact.hip", "resid.hip", "tridiag.hip", "dense64.hip", "colour.hip", "colour16.hip", "region.hip", "pipeline.hip", "literal.hip", "sample_space.hip", "exact_train.hip", "samples.hip", "ortho.hip", "abi_ctx.hip", "devsolve.hip", "eigen_sym.cpp", "eigen_reduce.cpp", "eigen_tridiag.cpp", "host_dense.cpp", "lanczos.cpp", "lab8_tables.cpp", "srgb16_tables.cpp"]
 ARCH = "gfx950"
 # the C++ surface behind include/nle/filter.hpp (host/): what every tool, and a test's driver, links beside its own main
 HOST_SOURCES = ["filter.cpp", "stages.cpp", "colour.cpp", "device_group.cpp", "image_io.cpp", "jpeg.cpp"]
@@ -73,8 +73,9 @@ def build_lib(force: bool = False) -> str:
         objs.append(o)
         if force or _newer(o, [s] + sorted(_includes(s))):
             if s.endswith(".cpp"):  # host-only fp64 algebra: plain g++ (needs function multiversioning)
-                # lab8_tables.cpp reproduces single-precision table arithmetic operation by operation: no contraction
-                extra = ["-ffp-contract=off"] if os.path.basename(s) == "lab8_tables.cpp" else []
+                # lab8_tables.cpp reproduces single-precision table arithmetic operation by operation, srgb16_tables.cpp
+                # states fp64 arithmetic a test restates: no contraction
+                extra = ["-ffp-contract=off"] if os.path.basename(s) in ("lab8_tables.cpp", "srgb16_tables.cpp") else []
                 jobs.append(["g++", "-O3", "-fopenmp-simd", "-std=c++17", "-fPIC", "-pthread", "-Wno-psabi"] + extra +
                             ["-I", os.path.join(ROOT, "include"), "-c", s, "-o", o])
             else:

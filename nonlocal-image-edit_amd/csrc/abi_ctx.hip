@@ -2,10 +2,12 @@
 // RCCL bootstrap, colour conversion and the bilateral pre-filter launches, the host-side eigen-solver entry points, the
 // closed-form helpers (sample grid, row slabs, eigenvalue transforms) and the profiling switches.  The train / apply /
 // stage-level entry points are in pipeline.hip and literal.hip, the device dense solvers' in devsolve.hip.
+#include <limits>
 #include <mutex>
 
 #include "lab8_fixed.h"
 #include "pipeline_internal.h"
+#include "srgb16.h"
 
 using nlek::GridSpec;
 using namespace nlep;
@@ -59,6 +61,7 @@ void nle_ctx_destroy(nle_ctx* ctx) {
     if (ctx->comm && ctx->own_comm && !ctx->comm_aborted.load()) (void)rccl().CommDestroy(ctx->comm);
     for (auto* f : ctx->filters) f->orphan();  // the table state goes to the cache freed below, V is freed on destroy
     if (ctx->d_lut) (void)hipFree(ctx->d_lut);
+    if (ctx->d_srgb16) (void)hipFree(ctx->d_srgb16);
     for (auto e : ctx->copy_ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -151,6 +154,32 @@ const double* colour_lut(nle_ctx* c) {
     }
     return c->d_lut;
 }
+
+// the tables of the 16-bit sRGB <-> float Lab conversion (srgb16.h), built once per process; the part the kernels read
+// (lin, the coefficients, the threshold pairs) is uploaded once per ctx
+const double* srgb16_host() {
+    static std::vector<double> blob(nlesrgb16::kHostDoubles);
+    static std::once_flag once;
+    std::call_once(once, [] {
+        nlesrgb16::tables(blob.data() + nlesrgb16::kOffLin, blob.data() + nlesrgb16::kOffThrHost,
+                          blob.data() + nlesrgb16::kOffCoeffs);
+        const double* thr = blob.data() + nlesrgb16::kOffThrHost;
+        double* pairs = blob.data() + nlesrgb16::kOffPairs;
+        for (int c = 0; c < nlesrgb16::kCodes; ++c) {
+            pairs[2 * c] = thr[c];
+            pairs[2 * c + 1] = c + 1 < nlesrgb16::kCodes ? thr[c + 1] : std::numeric_limits<double>::infinity();
+        }
+    });
+    return blob.data();
+}
+const double* srgb16_tab(nle_ctx* c) {
+    if (!c->d_srgb16) {
+        constexpr size_t bytes = nlesrgb16::kBlobDoubles * sizeof(double);
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&c->d_srgb16), bytes));
+        HIP_OK(hipMemcpy(c->d_srgb16, srgb16_host(), bytes, hipMemcpyHostToDevice));
+    }
+    return c->d_srgb16;
+}
 }  // namespace
 
 int nle_lab8_tables(unsigned short* h_gamma, unsigned short* h_cbrt, int* h_coeffs) {
@@ -185,6 +214,38 @@ int nle_lab2bgr8_planes(nle_ctx* ctx, const unsigned char* d_lab, const float* d
     return guard(ctx, [&] {
         HIP_OK(hipSetDevice(ctx->device));
         HIP_OK(nlek::lab2bgr8(ctx->stream, d_lab, d_L, d_a, d_b, n, colour_lut(ctx), d_bgr));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int nle_srgb16_tables(double* h_lin, double* h_thr, double* h_coeffs) {
+    if (!h_lin || !h_thr || !h_coeffs) return NLE_ERR_INVALID;
+    const double* blob = srgb16_host();
+    std::copy_n(blob + nlesrgb16::kOffLin, nlesrgb16::kCodes, h_lin);
+    std::copy_n(blob + nlesrgb16::kOffThrHost, nlesrgb16::kCodes, h_thr);
+    std::copy_n(blob + nlesrgb16::kOffCoeffs, nlesrgb16::kCoeffs, h_coeffs);
+    return NLE_OK;
+}
+
+int nle_bgr16_to_lab(nle_ctx* ctx, const unsigned short* d_bgr, long long n, float* d_L, float* d_a, float* d_b,
+                     float* d_guide) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_bgr || !d_L) throw Fail{NLE_ERR_INVALID, "nle_bgr16_to_lab: d_bgr and d_L must not be NULL"};
+        if (n <= 0) throw Fail{NLE_ERR_INVALID, "nle_bgr16_to_lab: n must be > 0"};
+        HIP_OK(hipSetDevice(ctx->device));
+        HIP_OK(nlek::bgr16_to_lab(ctx->stream, d_bgr, n, srgb16_tab(ctx), d_L, d_a, d_b, d_guide));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int nle_lab_to_bgr16(nle_ctx* ctx, const float* d_L, const float* d_a, const float* d_b, long long n, unsigned short* d_bgr) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_L || !d_a || !d_b || !d_bgr) throw Fail{NLE_ERR_INVALID, "nle_lab_to_bgr16: d_L, d_a, d_b and d_bgr must not be NULL"};
+        if (n <= 0) throw Fail{NLE_ERR_INVALID, "nle_lab_to_bgr16: n must be > 0"};
+        HIP_OK(hipSetDevice(ctx->device));
+        HIP_OK(nlek::lab_to_bgr16(ctx->stream, d_L, d_a, d_b, n, srgb16_tab(ctx), d_bgr));
         HIP_OK(hipStreamSynchronize(ctx->stream));
     });
 }

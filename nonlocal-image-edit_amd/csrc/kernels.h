@@ -415,6 +415,12 @@ hipError_t channel8(hipStream_t s, const unsigned char* d_img, long long n, int 
 // cv::max(y, 0) / cv::min(y, 255) / convertTo(CV_8U) of a filtered plane (src/filter.cpp:434-436): round half to even
 hipError_t plane_to_u8(hipStream_t s, const float* d_y, long long n, unsigned char* d_out);
 hipError_t channel8_plane(hipStream_t s, const unsigned char* d_u8, long long n, float* d_out);  // bytes -> fp32 levels
+// 16-bit sRGB <-> float Lab (colour16.hip): d_tab = lin | coeffs | threshold pairs as one blob
+// (srgb16.h: the tables of nle_srgb16_tables in the form the kernels read); d_a, d_b, d_guide optional outputs of the forward direction
+hipError_t bgr16_to_lab(hipStream_t s, const unsigned short* d_bgr, long long n, const double* d_tab, float* d_L,
+                        float* d_a, float* d_b, float* d_guide);
+hipError_t lab_to_bgr16(hipStream_t s, const float* d_L, const float* d_a, const float* d_b, long long n,
+                        const double* d_tab, unsigned short* d_bgr);
 // region edits (region.hip; the rule is stated in include/nle.h at nle_region_combine): per pixel the memberships of the M
 // spread stroke planes d_q blend the rows of wt ((M + 1) x L, row 0 the background) into one weight per layer, and the L
 // layer planes d_layers are summed under those weights -- fp64, every operation rounded on its own.  Planes by base pointer

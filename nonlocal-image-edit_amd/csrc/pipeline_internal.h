@@ -56,6 +56,7 @@ struct nle_ctx {
     std::multimap<size_t, void*> arena_free;
     size_t arena_bytes = 0;
     double* d_lut = nullptr;        // sRGB decode table of the colour wrapper
+    double* d_srgb16 = nullptr;     // tables of the 16-bit colour wrapper (srgb16.h), on first use
     std::set<nle_filter*> filters;  // live filters trained on this ctx (orphaned if the ctx dies first)
     hipEvent_t aux_ev = nullptr;
     void* h_stage = nullptr;  // page-locked staging block for the solvers' larger transfers (pinned_take())

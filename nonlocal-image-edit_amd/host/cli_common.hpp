@@ -10,10 +10,12 @@
 // anything touches the GPU.  For enhance only, region edits (NLEFilter::enhanceRegions): `--region MASK:w1,w2,...`, up to
 // NLE_REGION_MAX times (split at the last `:`; MASK any image the readers decode, its first channel is the stroke; as many
 // weights as positional ones, which are the background's), `--region-spread T` and `--region-floor F` (finite, > 0; only
-// with a region); and the flag `--nystrom-report` with its optional `--nystrom-map FILE` (NLEFilter::nystromResidual; not
-// with --exact).
+// with a region); the flag `--nystrom-report` with its optional `--nystrom-map FILE` (NLEFilter::nystromResidual; not
+// with --exact); and the flag `--deep` (no value): the input is read with imread16 -- a 16-bit PNG keeps every sample -- and
+// the result is written as a 16-bit PNG (the output name must end in .png; not with --region).
 #pragma once
 
+#include <cctype>
 #include <cmath>
 #include <cstdlib>
 #include <fstream>
@@ -43,6 +45,7 @@ struct FilterArgs {
     };
     std::vector<Region> regions;
     double regionSpread = 4, regionFloor = 0.05;
+    bool deep = false;               // --deep (enhance only): 16-bit PNG in, 16-bit PNG out
     bool nystromReport = false;  // --nystrom-report (enhance only)
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
@@ -62,8 +65,9 @@ inline double positive_option(const char* prog, const std::string& opt, const st
 // allow_chroma: the tool takes `--chroma HC` (enhance); otherwise the option is refused (denoise estimates a and b)
 // allow_regions: the tool takes the region options (enhance); otherwise they are refused (denoise has no layer weights)
 // allow_nystrom: the tool takes `--nystrom-report` / `--nystrom-map FILE` (enhance); otherwise they are refused
+// allow_deep: the tool takes `--deep` (enhance); otherwise it is refused (denoise has no 16-bit path)
 inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false,
-                  bool allow_regions = false, bool allow_nystrom = false) {
+                  bool allow_regions = false, bool allow_nystrom = false, bool allow_deep = false) {
     std::vector<char*> shifted;
     int first = 1;  // the first argument after the leading options
     bool spreadGiven = false, floorGiven = false;
@@ -77,6 +81,19 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
         if (opt.rfind("--exact=", 0) == 0) {
             std::cerr << argv[0] << ": --exact takes no value, got '" << opt << "'" << std::endl;
             std::exit(2);
+        }
+        if (opt == "--deep" || opt.rfind("--deep=", 0) == 0) {
+            if (!allow_deep) {
+                std::cerr << argv[0] << ": --deep is not supported here: deep colour (16 bit) is built for enhance only" << std::endl;
+                std::exit(2);
+            }
+            if (opt != "--deep") {
+                std::cerr << argv[0] << ": --deep takes no value, got '" << opt << "'" << std::endl;
+                std::exit(2);
+            }
+            a->deep = true;
+            first += 1;
+            continue;
         }
         if (opt == "--nystrom-report" || opt == "--nystrom-map" || opt.rfind("--nystrom-report=", 0) == 0) {
             if (!allow_nystrom) {
@@ -193,6 +210,10 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
                   << "Nystrom extension" << std::endl;
         std::exit(2);
     }
+    if (a->deep && !a->regions.empty()) {
+        std::cerr << argv[0] << ": --deep does not combine with --region: region edits take an 8-bit image" << std::endl;
+        std::exit(2);
+    }
     if ((spreadGiven || floorGiven) && a->regions.empty()) {
         std::cerr << argv[0] << ": --region-spread and --region-floor need at least one --region" << std::endl;
         std::exit(2);
@@ -213,6 +234,15 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
     }
     a->input = argv[1];
     a->output = argv[2];
+    if (a->deep) {  // the only 16-bit writer is the PNG one
+        const std::string& o = a->output;
+        std::string ext = o.size() >= 4 ? o.substr(o.size() - 4) : "";
+        for (char& ch : ext) ch = (char)std::tolower((unsigned char)ch);
+        if (ext != ".png") {
+            std::cerr << argv[0] << ": --deep writes a 16-bit PNG: the output name must end in .png, got '" << o << "'" << std::endl;
+            std::exit(2);
+        }
+    }
     int* ints[] = {&a->rowSamples, &a->colSamples, nullptr, nullptr, &a->sinkhornIters, &a->eigenVectors};
     double* reals[] = {nullptr, nullptr, &a->hx, &a->hy, nullptr, nullptr};
     for (int i = 0; i < 6; ++i) {
@@ -238,7 +268,7 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
 
 // reads the input (empty image + message on stderr if that fails)
 inline nle::Image load(const FilterArgs& a) {
-    nle::Image image = nle::imread(a.input);
+    nle::Image image = a.deep ? nle::imread16(a.input) : nle::imread(a.input);
     if (image.empty()) std::cerr << "Failed to read file from " << a.input << std::endl;
     return image;
 }

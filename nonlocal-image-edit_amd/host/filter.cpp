@@ -57,6 +57,30 @@ void enhance_rows(nle_ctx* c, nle_filter* f, const Image& image, const Vec& fS, 
     lab_to_rows(c, in, d_y.f(), nullptr, nullptr, out, r0, r1);
 }
 
+const char kDeepOneDevice[] = "Deep colour (16-bit images) runs on one device: unset NLE_DEVICES.";
+
+bool is_deep(const Image& image) { return image.channels() == 3 && image.depth() == NLE_16U; }
+
+// The planes a deep-colour train (or residual map) takes: the guide for L and, with a chroma bandwidth, a and b rounded
+// half to even and clamped to [0, 255] like the guide -- the chroma affinity sums integer differences (nle_ctx_set_chroma).
+// The rounding of these two opt-in planes is done on the host.
+struct DeepChroma {
+    Dev a, b;
+};
+DeepChroma deep_chroma_planes(nle_ctx* c, const Lab16Planes& in, size_t n, bool chroma) {
+    DeepChroma o;
+    if (!chroma) return o;
+    std::vector<float> h(2 * n);
+    check(nle_dev_download(c, h.data(), in.a.p, n * 4), c);
+    check(nle_dev_download(c, h.data() + n, in.b.p, n * 4), c);
+    for (float& v : h) v = std::fmin(255.f, std::fmax(0.f, std::nearbyint(v)));
+    o.a = Dev(c, n * 4);
+    o.b = Dev(c, n * 4);
+    check(nle_dev_upload(c, o.a.p, h.data(), n * 4), c);
+    check(nle_dev_upload(c, o.b.p, h.data() + n, n * 4), c);
+    return o;
+}
+
 // fn(ctx, rank, r0, r1) on every rank's rows of an H-row image, one thread per rank of the group; without a group
 // here, on all rows, on ctx c
 template <typename Fn>
@@ -147,8 +171,21 @@ void NLEFilter::trainOnDevice(const float* d_lum, int rows, int cols, int nRowSa
 
 void NLEFilter::trainForEnhancement(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
                                     int nSinkhornIter, int nEigenVectors) {  // :514-519
-    if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enhance RGB image.");
+    if (image.channels() != 3 || (image.depth() != NLE_8U && image.depth() != NLE_16U))
+        throw std::runtime_error("Can only enhance RGB image.");
     if (nRowSamples > image.rows || nColSamples > image.cols) throw std::runtime_error(kSampleCount);
+    if (is_deep(image)) {
+        // deep colour: 16-bit sRGB -> float Lab on the device, then the train on the guide (L rounded to 256 levels: the
+        // default table path, and the affinities need no more); enhance applies the filter to the unrounded L
+        // as for 8-bit images a group forms only when NLE_DEVICES lists two devices or more
+        if (devices_env() != nullptr && device_group(-1) != nullptr) throw std::runtime_error(kDeepOneDevice);
+        nle_ctx* c = shared_ctx();
+        const Lab16Planes in = lab16_planes(c, image, chromaBandwidth != 0, true);
+        const DeepChroma ab = deep_chroma_planes(c, in, image.total(), chromaBandwidth != 0);
+        trainOnDevice(in.guide.f(), image.rows, image.cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors,
+                      ab.a.f(), ab.b.f());
+        return;
+    }
     const TrainArgs a{nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors};
     const int H = image.rows, W = image.cols;
     DeviceGroup* g = nullptr;
@@ -167,6 +204,7 @@ void NLEFilter::trainForEnhancement(const Image& image, int nRowSamples, int nCo
 
 void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
                                 int nSinkhornIter, int nEigenVectors, int sigmaColor, int sigmaSpace) {  // :521-538
+    if (is_deep(image)) throw std::runtime_error("Denoise takes an 8-bit image: deep colour (16 bit) is built for enhance only.");
     if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enchance RGB image.");
     if (nRowSamples > image.rows || nColSamples > image.cols) throw std::runtime_error(kSampleCount);
     if (chromaBandwidth != 0)
@@ -182,6 +220,7 @@ void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSam
 
 Image NLEFilter::denoise(const Image& image, DType k, int sigmaColor, int sigmaSpace) const {  // :349-410
     if (image.channels() != 3) throw std::runtime_error("Can only enchance RGB image.");  // (sic) :351-353
+    if (is_deep(image)) throw std::runtime_error("Denoise takes an 8-bit image: deep colour (16 bit) is built for enhance only.");
     requireSize(image.total(), kTrainedSize);
     if (image.depth() != NLE_8U) throw std::runtime_error("Can only enchance RGB image.");
     const size_t np = image.total();
@@ -261,6 +300,15 @@ std::vector<Image> NLEFilter::applyLayers(const Image& channel, int nLayers) con
 Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights) const {  // :412-443
     if (image.channels() != 3) throw std::runtime_error("Can only enhance RGB image.");
     const int H = image.rows, W = image.cols;
+    if (is_deep(image)) {  // deep colour: float Lab in, the filter on the unrounded L, 16-bit codes out; nothing is rounded to 8 bit
+        if (!group_.empty()) throw std::runtime_error(kDeepOneDevice);
+        requireSize(image.total(), kTrainedSize);
+        const Vec fS = transformEigenValues(eigvals(), weights);
+        const Lab16Planes in = lab16_planes(ctx_, image, true, false);
+        Dev d_y(ctx_, image.total() * 4);
+        check(nle_apply(f_, in.L.f(), H, W, fS.data(), d_y.f()), ctx_);
+        return lab16_to_image(ctx_, in, d_y.f(), H, W);
+    }
     DeviceGroup* g = nullptr;
     if (!group_.empty()) {  // trained over NLE_DEVICES: every rank its rows
         if (image.depth() != NLE_8U) throw std::runtime_error("Can only enhance RGB image.");
@@ -281,6 +329,7 @@ Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights) 
 Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& strokes,
                                  const std::vector<std::vector<DType>>& regionWeights, const std::vector<DType>& weights,
                                  DType spread, DType floor) const {
+    if (is_deep(image)) throw std::runtime_error("Region edits take an 8-bit image: deep colour (16 bit) is built for enhance only.");
     if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enhance RGB image.");
     if (!group_.empty())
         throw std::runtime_error("Region edits run on one device: this filter was trained on a device group (NLE_DEVICES).");
@@ -327,15 +376,24 @@ Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& st
 NLEFilter::Residual NLEFilter::nystromResidual(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int form,
                                                double thresh) const {
     if (exact) throw std::runtime_error("nystromResidual: the exact filter has no Nystrom extension");
-    const bool bgr = image.channels() == 3 && image.depth() == NLE_8U;
-    if (!bgr && !(image.channels() == 1 && image.depth() == NLE_64F))
-        throw std::runtime_error("nystromResidual takes a 1-channel CV_64F plane or a 3-channel 8-bit image");
+    const bool bgr = image.channels() == 3 && image.depth() == NLE_8U, deep = is_deep(image);
+    if (!bgr && !deep && !(image.channels() == 1 && image.depth() == NLE_64F))
+        throw std::runtime_error("nystromResidual takes a 1-channel CV_64F plane or a 3-channel 8-bit or 16-bit image");
     if (nRowSamples > image.rows || nColSamples > image.cols) throw std::runtime_error(kSampleCount);
     nle_ctx* c = shared_ctx();
     const size_t n = image.total();
     LabPlanes in;
-    if (bgr) in = lab_planes(c, image.ptr<unsigned char>(), n, true, chromaBandwidth != 0);  // as trainForEnhancement
-    else in.L = upload_plane(c, image);
+    if (bgr) {
+        in = lab_planes(c, image.ptr<unsigned char>(), n, true, chromaBandwidth != 0);  // as trainForEnhancement
+    } else if (deep) {  // as trainForEnhancement on a 16-bit image: the guide, and the rounded a and b
+        Lab16Planes in16 = lab16_planes(c, image, chromaBandwidth != 0, true);
+        DeepChroma ab = deep_chroma_planes(c, in16, n, chromaBandwidth != 0);
+        in.L = std::move(in16.guide);
+        in.a = std::move(ab.a);
+        in.b = std::move(ab.b);
+    } else {
+        in.L = upload_plane(c, image);
+    }
     Dev d_r(c, n * 4);
     double s[4] = {0, 0, 0, 0};
     {  // the shared ctx's options as a train sets them

@@ -98,8 +98,8 @@ Image read_ppm(const std::vector<unsigned char>& b) {
 }
 
 // ---- PNG reader: zlib inflate (stored, fixed and dynamic Huffman blocks) + the five scanline filters.  8-bit and
-// 16-bit samples (high byte kept), grey / RGB / palette / with alpha (dropped), non-interlaced -- what `enhance` writes
-// and what common tools produce.  Interlaced files are refused.
+// 16-bit samples (imread keeps the high byte, imread16 the whole sample), grey / RGB / palette / with alpha (dropped),
+// non-interlaced -- what `enhance` writes and what common tools produce.  Interlaced files are refused.
 struct BitReader {
     const unsigned char* p;
     size_t n, pos = 0;
@@ -266,7 +266,8 @@ bool inflate_zlib(const std::vector<unsigned char>& z, std::vector<unsigned char
 
 uint32_t rd32be(const unsigned char* p) { return ((uint32_t)p[0] << 24) | (p[1] << 16) | (p[2] << 8) | p[3]; }
 
-Image read_png(const std::vector<unsigned char>& b) {
+// deep: every sample whole as 16UC3 (8-bit samples and palette entries widened x257) instead of 8UC3
+Image read_png(const std::vector<unsigned char>& b, bool deep = false) {
     static const unsigned char sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
     if (b.size() < 33 || std::memcmp(b.data(), sig, 8) != 0) return Image();
     uint32_t w = 0, h = 0;
@@ -311,7 +312,7 @@ Image read_png(const std::vector<unsigned char>& b) {
     std::vector<unsigned char> raw;
     if (!inflate_zlib(idat, &raw, (stride + 1) * (size_t)h)) return Image();
     std::vector<unsigned char> prev(stride, 0), cur(stride);
-    Image img((int)h, (int)w, NLE_8U, 3);
+    Image img((int)h, (int)w, deep ? NLE_16U : NLE_8U, 3);
     for (uint32_t r = 0; r < h; ++r) {
         const unsigned char* line = &raw[(stride + 1) * (size_t)r];
         const int ft = line[0];
@@ -344,6 +345,22 @@ Image read_png(const std::vector<unsigned char>& b) {
                 const unsigned char* px = &cur[(size_t)x * ch * step];
                 if (ch <= 2) R = G = B = px[0];
                 else R = px[0], G = px[step], B = px[2 * step];
+                if (deep && depth == 16) {  // big-endian samples, whole
+                    const unsigned char* pg = ch <= 2 ? px : px + step;
+                    const unsigned char* pb = ch <= 2 ? px : px + 2 * step;
+                    unsigned short* d16 = img.ptr<unsigned short>((int)r);
+                    d16[3 * x + 0] = (unsigned short)((pb[0] << 8) | pb[1]);
+                    d16[3 * x + 1] = (unsigned short)((pg[0] << 8) | pg[1]);
+                    d16[3 * x + 2] = (unsigned short)((px[0] << 8) | px[1]);
+                    continue;
+                }
+            }
+            if (deep) {
+                unsigned short* d16 = img.ptr<unsigned short>((int)r);
+                d16[3 * x + 0] = (unsigned short)(B * 257);
+                d16[3 * x + 1] = (unsigned short)(G * 257);
+                d16[3 * x + 2] = (unsigned short)(R * 257);
+                continue;
             }
             dst[3 * x + 0] = B;  // BGR like cv::imread
             dst[3 * x + 1] = G;
@@ -420,8 +437,23 @@ Image imread(const std::string& path) {
     return Image();
 }
 
+Image imread16(const std::string& path) {
+    std::vector<unsigned char> b;
+    if (!read_file(path, &b) || b.size() < 2) return Image();
+    if (b[0] == 0x89 && b[1] == 'P') return read_png(b, true);
+    const Image m = imread(path);  // what the other readers decode is 8 bit: widened x257 (255 -> 65535)
+    if (m.empty()) return Image();
+    Image wide(m.rows, m.cols, NLE_16U, 3);
+    const unsigned char* s = m.ptr<unsigned char>();
+    unsigned short* d = wide.ptr<unsigned short>();
+    for (size_t i = 0; i < m.total() * 3; ++i) d[i] = (unsigned short)(s[i] * 257);
+    return wide;
+}
+
 bool imwrite(const std::string& path, const Image& img) {
-    if (img.empty() || img.channels() != 3 || img.depth() != NLE_8U) return false;
+    if (img.empty() || img.channels() != 3 || (img.depth() != NLE_8U && img.depth() != NLE_16U)) return false;
+    const bool deep = img.depth() == NLE_16U;
+    if (deep && !ends_with(path, ".png")) return false;  // the only 16-bit writer
     const int w = img.cols, h = img.rows;
     std::vector<unsigned char> out;
     if (ends_with(path, ".ppm")) {
@@ -446,14 +478,23 @@ bool imwrite(const std::string& path, const Image& img) {
         std::vector<unsigned char> ihdr;
         wr32be(ihdr, (uint32_t)w);
         wr32be(ihdr, (uint32_t)h);
-        const unsigned char tail[5] = {8, 2, 0, 0, 0};  // 8-bit RGB, deflate, no filter, no interlace
+        const unsigned char tail[5] = {(unsigned char)(deep ? 16 : 8), 2, 0, 0, 0};  // RGB, deflate, no filter, no interlace
         ihdr.insert(ihdr.end(), tail, tail + 5);
         png_chunk(out, "IHDR", ihdr);
-        // raw scanlines: filter byte 0 + RGB
+        // raw scanlines: filter byte 0 + RGB (16-bit samples big endian)
         std::vector<unsigned char> raw;
-        raw.reserve((size_t)h * (1 + 3 * (size_t)w));
+        raw.reserve((size_t)h * (1 + (deep ? 6 : 3) * (size_t)w));
         for (int r = 0; r < h; ++r) {
             raw.push_back(0);
+            if (deep) {
+                const unsigned short* s = img.ptr<unsigned short>(r);
+                for (int c = 0; c < w; ++c)
+                    for (int k = 2; k >= 0; --k) {
+                        raw.push_back((unsigned char)(s[3 * c + k] >> 8));
+                        raw.push_back((unsigned char)(s[3 * c + k] & 0xff));
+                    }
+                continue;
+            }
             const unsigned char* s = img.ptr<unsigned char>(r);
             for (int c = 0; c < w; ++c) {
                 raw.push_back(s[3 * c + 2]);

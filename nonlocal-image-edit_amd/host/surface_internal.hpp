@@ -1,7 +1,7 @@
 // What the translation units of the C++ surface (stages.cpp, colour.cpp, device_group.cpp, filter.cpp) share, and the
 // one owner of every step NLEFilter repeats: the process's shared ctx and its mode, status -> exception, the RAII device
 // buffer, the plane conversions, the options a train sets on a ctx (TrainOptions), the colour prologue (lab_planes) and
-// epilogue (lab_to_rows).  Not installed: include/nle/filter.hpp is the surface.
+// epilogue (lab_to_rows), and their deep-colour forms (lab16_planes, lab16_to_image).  Not installed: include/nle/filter.hpp is the surface.
 #pragma once
 
 #include <cmath>
@@ -156,6 +156,34 @@ inline void lab_to_rows(nle_ctx* c, const LabPlanes& in, const float* d_L, const
     if (d_a || d_b) check(nle_lab2bgr8_planes(c, in.lab.u8(), d_L, d_a, d_b, (long long)n, in.bgr.u8()), c);
     else check(nle_lab2bgr8(c, in.lab.u8(), d_L, (long long)n, in.bgr.u8()), c);
     check(nle_dev_download(c, out.ptr<unsigned char>(r0), in.bgr.p, n * 3), c);
+}
+
+// ---- deep colour (16UC3 images): the same two steps on float Lab planes ----
+// prologue: n 16-bit BGR pixels -> L (fp32, unrounded) always; a and b (likewise) and the guide (L rounded to the 256
+// levels a train takes) when wanted, empty otherwise
+struct Lab16Planes {
+    Dev bgr, L, a, b, guide;
+};
+inline Lab16Planes lab16_planes(nle_ctx* c, const Image& image, bool want_ab, bool want_guide) {
+    const size_t n = image.total();
+    Lab16Planes o;
+    o.bgr = Dev(c, n * 6);
+    o.L = Dev(c, n * 4);
+    if (want_ab) o.a = Dev(c, n * 4);
+    if (want_ab) o.b = Dev(c, n * 4);
+    if (want_guide) o.guide = Dev(c, n * 4);
+    check(nle_dev_upload(c, o.bgr.p, image.ptr<unsigned short>(), n * 6), c);
+    check(nle_bgr16_to_lab(c, static_cast<const unsigned short*>(o.bgr.p), (long long)n, o.L.f(), o.a.f(), o.b.f(), o.guide.f()), c);
+    return o;
+}
+
+// epilogue: d_L with in's a and b -> a 16UC3 image of the input's size; nothing is rounded before the 16-bit codes
+inline Image lab16_to_image(nle_ctx* c, const Lab16Planes& in, const float* d_L, int rows, int cols) {
+    Image out(rows, cols, NLE_16U, 3);
+    const size_t n = out.total();
+    check(nle_lab_to_bgr16(c, d_L, in.a.f(), in.b.f(), (long long)n, static_cast<unsigned short*>(in.bgr.p)), c);
+    check(nle_dev_download(c, out.ptr<unsigned short>(), in.bgr.p, n * 6), c);
+    return out;
 }
 
 }  // namespace nle::surface
