@@ -697,6 +697,34 @@ int nle_srgb16_tables(double* h_lin /*65536*/, double* h_thr /*65536*/, double* 
 int nle_bgr16_to_lab(nle_ctx* ctx, const unsigned short* d_bgr, long long n, float* d_L, float* d_a, float* d_b, float* d_guide);
 int nle_lab_to_bgr16(nle_ctx* ctx, const float* d_L, const float* d_a, const float* d_b, long long n, unsigned short* d_bgr);
 
+/* ---- HDR tone mapping (new in this build: no reference, so this text and DESIGN.md section 3.14 are the definition) ---- */
+/* Linear-light float images through the filter: log-luminance on the scale of an 8-bit L plane in, 16-bit sRGB out.  fp64
+ * per pixel on the device, every operation rounded on its own (no fma) and in the order written; planes are stored as fp32.
+ * d_bgr: n x 3 fp32 (B, G, R interleaved, linear light).  Y = (0.212671 R + 0.715160 G) + 0.072169 B (the Y row of the matrix
+ * above, not renormalised).
+ * nle_hdr_range: Ymax = the largest finite Y, Ymin+ = the smallest finite Y > 0 over the n pixels (two kernels, per-block
+ *   pairs read in a fixed order, no atomics); on the host l_hi = log2(Ymax), l_lo = max(log2(Ymin+), l_hi - 24),
+ *   *h_range = R = l_hi - l_lo, and R = 1 when R < 2^-20 (a flat image).  No pixel with a finite positive Y: NLE_ERR_INVALID.
+ * nle_hdr_to_loglum: x = 255 ((log2(Y) - l_hi) / R) + 255, then clamped into [0, 255]: the clamp of Y into
+ *   [2^(l_hi - R), 2^l_hi], taken after the logarithm where it is exact.  Y <= 0, -inf and NaN give 0 (the floor), +inf gives
+ *   255 (the ceiling).  x is stored as fp32; guide = round-half-even of the fp64 x, the integer plane a train takes (table
+ *   path).  With these scales hy means what it means for L planes.  d_x or d_guide may be NULL, not both.  Near x = 0 the sum
+ *   cancels: there x carries the absolute error of the other values, a few 1e-14 / R.
+ * nle_loglum_to_bgr16: from the filtered plane d_y (y = V f(Lambda) V^T x by nle_apply on the unrounded x) and the original
+ *   colours: Yout = exp2(((y - 255 c) R) / 255) with c = base_weight = f(1), the last layer weight -- a constant plane 255
+ *   comes out of the filter as 255 c, which anchors white; a NaN y gives Yout = 0.  Yin = Y clamped into [exp2(l_hi - R),
+ *   exp2(l_hi)] (both ends evaluated on the host; a NaN Y, -inf and Y <= 0 count as the floor, +inf as the ceiling).  Per
+ *   channel C of B, G, R: r = max(C, 0) / Yin (a NaN C counts as 0), Cout = (s == 1 ? r : pow(r, s)) Yout with s =
+ *   saturation, and the 16-bit code of Cout is code(Cout) through h_thr exactly as nle_lab_to_bgr16 encodes: values out of
+ *   range saturate at 0 and 65535, a NaN Cout (0 times inf) gives 0.  No gamut mapping beyond that.
+ * NLE_ERR_INVALID with a message, nothing enqueued and the ctx left usable: a NULL input or output (both of d_x and d_guide),
+ * n < 0, a non-finite l_hi or base_weight, a range or saturation that is not finite or not > 0, a saturation above 2.  No
+ * pointer needs more than its type's alignment (the kernels take two pixels per thread where 8 bytes are given). */
+int nle_hdr_range(nle_ctx* ctx, const float* d_bgr, long long n, double* h_l_hi, double* h_range);
+int nle_hdr_to_loglum(nle_ctx* ctx, const float* d_bgr, long long n, double l_hi, double range, float* d_x, float* d_guide);
+int nle_loglum_to_bgr16(nle_ctx* ctx, const float* d_y, const float* d_bgr, long long n, double l_hi, double range,
+                        double base_weight, double saturation, unsigned short* d_bgr16);
+
 /* ---- denoise wrapper (src/denoise.cpp, src/filter.cpp:349-410,521-538): the bilateral prefilter ------------- */
 /* cv::bilateralFilter(src, dst, -1, sigmaColor, sigmaSpace, BORDER_DEFAULT) on a single-channel 8-bit plane, as
  * OpenCV documents it for CV_8UC1: radius = round(1.5 sigmaSpace) >= 1, circular window, fp32 weights

@@ -102,8 +102,8 @@ struct Permutation {
 };
 
 // continuous cv::Mat stand-in: ROW-major, interleaved channels; depth CV_8U, CV_16U (deep-colour images: imread16,
-// trainForEnhancement, enhance) or CV_64F
-enum { NLE_8U = 0, NLE_16U = 2, NLE_64F = 6 };
+// trainForEnhancement, enhance), CV_32F (linear-light HDR images: imreadHDR, trainForToneMapping, toneMap) or CV_64F
+enum { NLE_8U = 0, NLE_16U = 2, NLE_32F = 5, NLE_64F = 6 };
 const int OPENCV_MAT_TYPE = NLE_64F;  // include/filter.hpp:13
 class Image {
 public:
@@ -111,7 +111,7 @@ public:
     Image() = default;
     Image(int r, int c, int depth, int channels = 1)
         : rows(r), cols(c), depth_(depth), ch_(channels),
-          buf_((size_t)r * c * channels * (depth == NLE_64F ? 8 : depth == NLE_16U ? 2 : 1)) {}
+          buf_((size_t)r * c * channels * (depth == NLE_64F ? 8 : depth == NLE_32F ? 4 : depth == NLE_16U ? 2 : 1)) {}
     int channels() const { return ch_; }
     int depth() const { return depth_; }
     size_t total() const { return (size_t)rows * cols; }
@@ -185,6 +185,16 @@ public:
     // sampler, exact and chromaBandwidth apply as they do there; chroma takes a and b rounded the same way); enhance applies
     // the filter to the unrounded L and returns a 16UC3 image: nothing is rounded to 8 bits.  One device; enhanceRegions,
     // trainForDenoise and denoise throw for a 16-bit image.
+    // HDR tone mapping (new here; DESIGN.md section 3.14, the arithmetic is stated in nle.h at nle_hdr_range): a 32FC3
+    // linear-light BGR image (imreadHDR).  The train finds the image's luminance range on the device, writes log-luminance
+    // on the scale of an 8-bit L plane and trains on its 256-level guide (patchRadius, sampler and exact apply as for
+    // enhance); it keeps the range in the filter.  toneMap applies the filter to the unrounded log-luminance of `I` with the
+    // trained range -- the last weight multiplies the base layer, so one below 1 compresses the large-scale variation and
+    // keeps the detail -- and returns a 16UC3 sRGB image; saturation in (0, 2] is the exponent of the colour ratios.  One
+    // device; both throw with a non-zero chromaBandwidth, and the 8- and 16-bit methods throw for a 32F image.
+    void trainForToneMapping(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
+                             int nSinkhornIter = 10, int nEigenVectors = 5);
+    Image toneMap(const Image& I, const std::vector<DType>& weights, DType saturation = 1) const;
     // region edits (new here; nle_apply_regions in nle.h states the rule): enhance with layer weights of its own for every
     // scribbled region.  strokes[m]: a one-channel 8-bit image of I's size, a pixel belongs to the stroke where its byte is
     // >= 128; regionWeights[m]: the weights of region m, as many as `weights`, which is the background's row.  Each stroke
@@ -263,6 +273,7 @@ private:
     std::shared_ptr<nle_filter> fh_;  // nle_filter_destroy when the last copy goes
     nle_filter* f_ = nullptr;         // == fh_.get()
     int rows_ = 0, cols_ = 0;
+    double hdrHi_ = 0, hdrRange_ = 0;  // trainForToneMapping: log2 of the largest luminance and the range in stops (0: none)
     // NLE_DEVICES=<dev>,<dev>,...: trainForEnhancement / enhance shard the image by row slabs over one context (and
     // one host thread per call) per listed device; rank r's filter is group_[r] and f_ == group_[0].get()
     std::vector<std::shared_ptr<nle_filter>> group_;

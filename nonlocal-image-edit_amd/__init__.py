@@ -969,6 +969,51 @@ class Context:
                                       L.numel(), C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    # ---- HDR tone mapping: linear-light float BGR -> log-luminance planes -> 16-bit sRGB (device tensors) ----
+    def _f32bgr(self, bgr):
+        """an (..., 3) linear-light float32 BGR image on the device, contiguous (numpy or torch)"""
+        torch = _torch()
+        if isinstance(bgr, np.ndarray) and bgr.dtype == np.float32:
+            bgr = torch.from_numpy(np.array(bgr, order="C"))  # a copy: the caller's array may be read-only
+        t = torch.as_tensor(bgr)
+        if t.dtype != torch.float32 or t.dim() < 1 or t.shape[-1] != 3:
+            raise NLEError(NLE_ERR_INVALID, "an HDR image is (..., 3) float32 in B, G, R order")
+        return t.to(f"cuda:{self.device}").contiguous()
+
+    def hdr_range(self, bgr):
+        """nle_hdr_range on an (..., 3) float32 BGR image: (l_hi, range) as Python floats"""
+        t = self._f32bgr(bgr)
+        self._sync_in()
+        l_hi, rng = C.c_double(0.0), C.c_double(0.0)
+        _check(lib().nle_hdr_range(self._h, C.c_void_p(t.data_ptr()), t.numel() // 3, C.byref(l_hi), C.byref(rng)), self._h)
+        return l_hi.value, rng.value
+
+    def hdr_to_loglum(self, bgr, l_hi, rng, want_x=True, want_guide=True):
+        """nle_hdr_to_loglum: (x, guide) float32 planes of the image's leading shape, None where not wanted"""
+        torch = _torch()
+        t = self._f32bgr(bgr)
+        self._sync_in()
+        shape = t.shape[:-1]
+        x = torch.empty(shape, dtype=torch.float32, device=t.device) if want_x else None
+        g = torch.empty(shape, dtype=torch.float32, device=t.device) if want_guide else None
+        ptr = lambda v: C.c_void_p(v.data_ptr()) if v is not None else None  # noqa: E731
+        _check(lib().nle_hdr_to_loglum(self._h, ptr(t), t.numel() // 3, float(l_hi), float(rng), ptr(x), ptr(g)), self._h)
+        return x, g
+
+    def loglum_to_bgr16(self, y, bgr, l_hi, rng, base_weight, saturation=1.0):
+        """nle_loglum_to_bgr16 on the filtered plane y and the original (..., 3) float32 BGR image: the (..., 3) torch.uint16
+        BGR image"""
+        torch = _torch()
+        t = self._f32bgr(bgr)
+        y = torch.as_tensor(y, dtype=torch.float32, device=t.device).contiguous()
+        if y.numel() != t.numel() // 3:
+            raise NLEError(NLE_ERR_INVALID, "y must have one value per pixel of the image")
+        self._sync_in()
+        out = torch.empty(t.shape, dtype=torch.uint16, device=t.device)
+        _check(lib().nle_loglum_to_bgr16(self._h, C.c_void_p(y.data_ptr()), C.c_void_p(t.data_ptr()), y.numel(), float(l_hi),
+                                         float(rng), float(base_weight), float(saturation), C.c_void_p(out.data_ptr())), self._h)
+        return out
+
     def bilateral8(self, plane, sigma_color, sigma_space):
         """`cv::bilateralFilter(plane, -1, sigmaColor, sigmaSpace)` on an integer-valued float32 plane"""
         torch = _torch()

@@ -250,6 +250,66 @@ int nle_lab_to_bgr16(nle_ctx* ctx, const float* d_L, const float* d_a, const flo
     });
 }
 
+// ---- HDR tone mapping (tonemap.hip; the definition is at the declarations in nle.h) ----
+int nle_hdr_range(nle_ctx* ctx, const float* d_bgr, long long n, double* h_l_hi, double* h_range) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_bgr || !h_l_hi || !h_range) throw Fail{NLE_ERR_INVALID, "nle_hdr_range: d_bgr, h_l_hi and h_range must not be NULL"};
+        if (n < 0) throw Fail{NLE_ERR_INVALID, "nle_hdr_range: n must be >= 0"};
+        double pair[2] = {0.0, 0.0};
+        if (n > 0) {
+            HIP_OK(hipSetDevice(ctx->device));
+            DevBuf<double> ws((size_t)2 * nlek::hdr_range_blocks(n) + 2);  // the blocks' pairs, then the result
+            double* d_pair = ws.p + ws.n - 2;
+            HIP_OK(nlek::hdr_range(ctx->stream, d_bgr, n, ws.p, d_pair));
+            HIP_OK(hipMemcpyAsync(pair, d_pair, sizeof pair, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_OK(hipStreamSynchronize(ctx->stream));
+        }
+        if (!(pair[0] > 0.0)) throw Fail{NLE_ERR_INVALID, "nle_hdr_range: no pixel has a finite luminance > 0"};
+        const double l_hi = std::log2(pair[0]), l_lo = std::max(std::log2(pair[1]), l_hi - 24.0);
+        const double range = l_hi - l_lo;
+        *h_l_hi = l_hi;
+        *h_range = range < 0x1p-20 ? 1.0 : range;
+    });
+}
+
+namespace {
+void hdr_scale_check(const char* fn, double l_hi, double range) {
+    if (!std::isfinite(l_hi)) throw Fail{NLE_ERR_INVALID, std::string(fn) + ": l_hi must be finite"};
+    if (!std::isfinite(range) || !(range > 0)) throw Fail{NLE_ERR_INVALID, std::string(fn) + ": range must be finite and > 0"};
+}
+}  // namespace
+
+int nle_hdr_to_loglum(nle_ctx* ctx, const float* d_bgr, long long n, double l_hi, double range, float* d_x, float* d_guide) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_bgr) throw Fail{NLE_ERR_INVALID, "nle_hdr_to_loglum: d_bgr must not be NULL"};
+        if (!d_x && !d_guide) throw Fail{NLE_ERR_INVALID, "nle_hdr_to_loglum: d_x and d_guide must not both be NULL"};
+        if (n < 0) throw Fail{NLE_ERR_INVALID, "nle_hdr_to_loglum: n must be >= 0"};
+        hdr_scale_check("nle_hdr_to_loglum", l_hi, range);
+        HIP_OK(hipSetDevice(ctx->device));
+        HIP_OK(nlek::hdr_to_loglum(ctx->stream, d_bgr, n, l_hi, range, d_x, d_guide));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int nle_loglum_to_bgr16(nle_ctx* ctx, const float* d_y, const float* d_bgr, long long n, double l_hi, double range,
+                        double base_weight, double saturation, unsigned short* d_bgr16) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_y || !d_bgr || !d_bgr16) throw Fail{NLE_ERR_INVALID, "nle_loglum_to_bgr16: d_y, d_bgr and d_bgr16 must not be NULL"};
+        if (n < 0) throw Fail{NLE_ERR_INVALID, "nle_loglum_to_bgr16: n must be >= 0"};
+        hdr_scale_check("nle_loglum_to_bgr16", l_hi, range);
+        if (!std::isfinite(base_weight)) throw Fail{NLE_ERR_INVALID, "nle_loglum_to_bgr16: base_weight must be finite"};
+        if (!std::isfinite(saturation) || !(saturation > 0) || saturation > 2)
+            throw Fail{NLE_ERR_INVALID, "nle_loglum_to_bgr16: saturation must be a finite number in (0, 2]"};
+        HIP_OK(hipSetDevice(ctx->device));
+        HIP_OK(nlek::loglum_to_bgr16(ctx->stream, d_y, d_bgr, n, range, 255.0 * base_weight, saturation, std::exp2(l_hi - range),
+                                     std::exp2(l_hi), srgb16_tab(ctx), d_bgr16));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
 int nle_lab8_channel(nle_ctx* ctx, const unsigned char* d_lab, long long n, int channel, float* d_out) {
     if (!ctx || !d_lab || !d_out || n < 0 || channel < 0 || channel > 2) return NLE_ERR_INVALID;
     return guard(ctx, [&] {

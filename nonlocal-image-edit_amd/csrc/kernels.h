@@ -421,6 +421,15 @@ hipError_t bgr16_to_lab(hipStream_t s, const unsigned short* d_bgr, long long n,
                         float* d_a, float* d_b, float* d_guide);
 hipError_t lab_to_bgr16(hipStream_t s, const float* d_L, const float* d_a, const float* d_b, long long n,
                         const double* d_tab, unsigned short* d_bgr);
+// HDR tone mapping (tonemap.hip): interleaved linear-light BGR fp32 in.  hdr_range: d_partial holds
+// 2 * hdr_range_blocks(n) doubles of workspace, d_pair receives (Ymax, Ymin+), Ymax = 0 when no luminance is finite and > 0.
+// hdr_to_loglum: d_x and d_guide optional.  loglum_to_bgr16: white = 255 c, [y_lo, y_hi] = [2^(l_hi - range), 2^l_hi];
+// d_tab as for lab_to_bgr16 (its threshold pairs).
+int hdr_range_blocks(long long n);
+hipError_t hdr_range(hipStream_t s, const float* d_bgr, long long n, double* d_partial, double* d_pair);
+hipError_t hdr_to_loglum(hipStream_t s, const float* d_bgr, long long n, double l_hi, double range, float* d_x, float* d_guide);
+hipError_t loglum_to_bgr16(hipStream_t s, const float* d_y, const float* d_bgr, long long n, double range, double white,
+                           double saturation, double y_lo, double y_hi, const double* d_tab, unsigned short* d_bgr16);
 // region edits (region.hip; the rule is stated in include/nle.h at nle_region_combine): per pixel the memberships of the M
 // spread stroke planes d_q blend the rows of wt ((M + 1) x L, row 0 the background) into one weight per layer, and the L
 // layer planes d_layers are summed under those weights -- fp64, every operation rounded on its own.  Planes by base pointer

@@ -12,7 +12,10 @@
 // weights as positional ones, which are the background's), `--region-spread T` and `--region-floor F` (finite, > 0; only
 // with a region); the flag `--nystrom-report` with its optional `--nystrom-map FILE` (NLEFilter::nystromResidual; not
 // with --exact); and the flag `--deep` (no value): the input is read with imread16 -- a 16-bit PNG keeps every sample -- and
-// the result is written as a 16-bit PNG (the output name must end in .png; not with --region).
+// the result is written as a 16-bit PNG (the output name must end in .png; not with --region); and the flag `--tonemap`
+// (no value) with its optional `--tonemap-saturation S` (a finite number in (0, 2]): the input is an HDR file read with
+// imreadHDR, the positional weights are the layer weights of NLEFilter::toneMap -- the last one is the base compression --
+// and the result is a 16-bit PNG (not with --chroma, --region, --deep or --nystrom-report).
 #pragma once
 
 #include <cctype>
@@ -46,6 +49,8 @@ struct FilterArgs {
     std::vector<Region> regions;
     double regionSpread = 4, regionFloor = 0.05;
     bool deep = false;               // --deep (enhance only): 16-bit PNG in, 16-bit PNG out
+    bool tonemap = false;            // --tonemap (enhance only): Radiance / PFM in, 16-bit PNG out
+    double tonemapSaturation = 1;    // --tonemap-saturation S (with --tonemap)
     bool nystromReport = false;  // --nystrom-report (enhance only)
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
@@ -66,11 +71,13 @@ inline double positive_option(const char* prog, const std::string& opt, const st
 // allow_regions: the tool takes the region options (enhance); otherwise they are refused (denoise has no layer weights)
 // allow_nystrom: the tool takes `--nystrom-report` / `--nystrom-map FILE` (enhance); otherwise they are refused
 // allow_deep: the tool takes `--deep` (enhance); otherwise it is refused (denoise has no 16-bit path)
+// allow_tonemap: the tool takes `--tonemap` / `--tonemap-saturation S` (enhance); otherwise they are refused
 inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false,
-                  bool allow_regions = false, bool allow_nystrom = false, bool allow_deep = false) {
+                  bool allow_regions = false, bool allow_nystrom = false, bool allow_deep = false,
+                  bool allow_tonemap = false) {
     std::vector<char*> shifted;
     int first = 1;  // the first argument after the leading options
-    bool spreadGiven = false, floorGiven = false;
+    bool spreadGiven = false, floorGiven = false, saturationGiven = false;
     while (first < argc) {
         const std::string opt = argv[first];
         if (opt == "--exact") {
@@ -93,6 +100,34 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
             }
             a->deep = true;
             first += 1;
+            continue;
+        }
+        if (opt.rfind("--tonemap", 0) == 0) {
+            if (!allow_tonemap) {
+                std::cerr << argv[0] << ": " << opt << " is not supported here: --tonemap (HDR tone mapping) is built for enhance only"
+                          << std::endl;
+                std::exit(2);
+            }
+            if (opt == "--tonemap") {
+                a->tonemap = true;
+                first += 1;
+                continue;
+            }
+            if (opt != "--tonemap-saturation") {
+                std::cerr << argv[0] << ": --tonemap takes no value and --tonemap-saturation takes a number, got '" << opt << "'"
+                          << std::endl;
+                std::exit(2);
+            }
+            const std::string v = first + 1 < argc ? argv[first + 1] : "";
+            char* end = nullptr;
+            const double x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            if (v.empty() || *end != '\0' || !std::isfinite(x) || !(x > 0) || x > 2) {
+                std::cerr << argv[0] << ": --tonemap-saturation takes a finite number in (0, 2], got '" << v << "'" << std::endl;
+                std::exit(2);
+            }
+            a->tonemapSaturation = x;
+            saturationGiven = true;
+            first += 2;
             continue;
         }
         if (opt == "--nystrom-report" || opt == "--nystrom-map" || opt.rfind("--nystrom-report=", 0) == 0) {
@@ -214,6 +249,15 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
         std::cerr << argv[0] << ": --deep does not combine with --region: region edits take an 8-bit image" << std::endl;
         std::exit(2);
     }
+    if (saturationGiven && !a->tonemap) {
+        std::cerr << argv[0] << ": --tonemap-saturation needs --tonemap" << std::endl;
+        std::exit(2);
+    }
+    if (a->tonemap && (a->chroma != 0 || !a->regions.empty() || a->deep || a->nystromReport)) {
+        std::cerr << argv[0] << ": --tonemap does not combine with --chroma, --region, --deep or --nystrom-report: those take "
+                  << "an 8-bit or 16-bit sRGB image" << std::endl;
+        std::exit(2);
+    }
     if ((spreadGiven || floorGiven) && a->regions.empty()) {
         std::cerr << argv[0] << ": --region-spread and --region-floor need at least one --region" << std::endl;
         std::exit(2);
@@ -234,12 +278,13 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
     }
     a->input = argv[1];
     a->output = argv[2];
-    if (a->deep) {  // the only 16-bit writer is the PNG one
+    if (a->deep || a->tonemap) {  // the only 16-bit writer is the PNG one
         const std::string& o = a->output;
         std::string ext = o.size() >= 4 ? o.substr(o.size() - 4) : "";
         for (char& ch : ext) ch = (char)std::tolower((unsigned char)ch);
         if (ext != ".png") {
-            std::cerr << argv[0] << ": --deep writes a 16-bit PNG: the output name must end in .png, got '" << o << "'" << std::endl;
+            std::cerr << argv[0] << ": " << (a->deep ? "--deep" : "--tonemap")
+                      << " writes a 16-bit PNG: the output name must end in .png, got '" << o << "'" << std::endl;
             std::exit(2);
         }
     }
@@ -268,7 +313,7 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
 
 // reads the input (empty image + message on stderr if that fails)
 inline nle::Image load(const FilterArgs& a) {
-    nle::Image image = a.deep ? nle::imread16(a.input) : nle::imread(a.input);
+    nle::Image image = a.tonemap ? nle::imreadHDR(a.input) : a.deep ? nle::imread16(a.input) : nle::imread(a.input);
     if (image.empty()) std::cerr << "Failed to read file from " << a.input << std::endl;
     return image;
 }

@@ -7,7 +7,9 @@
 // (repeatable), `--region-spread T`, `--region-floor F`: the positional weights are then the background's; and
 // `--nystrom-report [--nystrom-map FILE]`: one more stdout line with the Nystrom residual of the sample grid (mean, max and
 // its pixel, share of pixels above 0.5) and the map as an 8-bit grey image, round(255 clamp(r, 0, 1)); and `--deep`: 16-bit
-// PNG in, 16-bit PNG out through the float Lab path (NLEFilter on a 16UC3 image), same banners.
+// PNG in, 16-bit PNG out through the float Lab path (NLEFilter on a 16UC3 image), same banners; and `--tonemap
+// [--tonemap-saturation S]`: a Radiance or PFM file in, 16-bit PNG out through NLEFilter::trainForToneMapping / toneMap, the
+// weights being the layer weights (the last one compresses the base layer), same banners.
 #include <algorithm>
 
 #include "cli_common.hpp"
@@ -15,7 +17,7 @@
 int main(int argc, char* argv[]) {
     nlecli::FilterArgs a;
     if (!nlecli::parse(argc, argv, 10, &a, /*allow_chroma=*/true, /*allow_regions=*/true, /*allow_nystrom=*/true,
-                       /*allow_deep=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
+                       /*allow_deep=*/true, /*allow_tonemap=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
     const nle::Image image = nlecli::load(a);
     if (image.empty()) return 0;                        // src/enhance.cpp:34-37
     // the strokes: the first channel of every mask, read before anything touches the GPU
@@ -48,10 +50,12 @@ int main(int argc, char* argv[]) {
     filter.sampler = a.sampler;
     filter.exact = a.exact;
     filter.chromaBandwidth = a.chroma;
-    filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
-    const nle::Image result = strokes.empty() ? filter.enhance(image, a.extra)  // the weights are argv[9..]
-                                              : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,
-                                                                      a.regionFloor);
+    if (a.tonemap) filter.trainForToneMapping(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
+    else filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
+    const nle::Image result = a.tonemap        ? filter.toneMap(image, a.extra, a.tonemapSaturation)
+                              : strokes.empty() ? filter.enhance(image, a.extra)  // the weights are argv[9..]
+                                                : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,
+                                                                        a.regionFloor);
     nlecli::report(filter);
     const int rc = nlecli::finish(a, result, "Done. Press any key in result window to exit.");  // src/enhance.cpp:45
     if (a.nystromReport) {  // after the reference's banners: one line, and the map as an 8-bit grey image

@@ -61,6 +61,14 @@ const char kDeepOneDevice[] = "Deep colour (16-bit images) runs on one device: u
 
 bool is_deep(const Image& image) { return image.channels() == 3 && image.depth() == NLE_16U; }
 
+// HDR (32F) images have their own pair of methods; every other one refuses them by name
+const char kHdrOneDevice[] = "Tone mapping runs on one device: unset NLE_DEVICES.";
+const char kHdrNoChroma[] = "Tone mapping does not take chroma affinities (chromaBandwidth must be 0): a linear-light image has no 8-bit a and b planes.";
+void refuse_hdr(const Image& image, const char* method) {
+    if (image.depth() == NLE_32F)
+        throw std::runtime_error(std::string(method) + " does not take a 32F (HDR) image: use trainForToneMapping and toneMap.");
+}
+
 // The planes a deep-colour train (or residual map) takes: the guide for L and, with a chroma bandwidth, a and b rounded
 // half to even and clamped to [0, 255] like the guide -- the chroma affinity sums integer differences (nle_ctx_set_chroma).
 // The rounding of these two opt-in planes is done on the host.
@@ -119,6 +127,7 @@ void NLEFilter::beginTrain(nle_ctx* c) {
     fh_.reset();
     f_ = nullptr;
     group_.clear();
+    hdrHi_ = hdrRange_ = 0;  // trainForToneMapping sets them after its train
     if (verbose) {
         // the four stages run as one fused GPU pipeline; the banners keep the reference's stdout (:483-498)
         std::cout << "Computing kernel" << std::endl;
@@ -171,6 +180,7 @@ void NLEFilter::trainOnDevice(const float* d_lum, int rows, int cols, int nRowSa
 
 void NLEFilter::trainForEnhancement(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
                                     int nSinkhornIter, int nEigenVectors) {  // :514-519
+    refuse_hdr(image, "trainForEnhancement");
     if (image.channels() != 3 || (image.depth() != NLE_8U && image.depth() != NLE_16U))
         throw std::runtime_error("Can only enhance RGB image.");
     if (nRowSamples > image.rows || nColSamples > image.cols) throw std::runtime_error(kSampleCount);
@@ -202,8 +212,39 @@ void NLEFilter::trainForEnhancement(const Image& image, int nRowSamples, int nCo
     adopt(ctxs, fs, H, W, nEigenVectors);
 }
 
+void NLEFilter::trainForToneMapping(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,
+                                    int nEigenVectors) {
+    if (image.channels() != 3 || image.depth() != NLE_32F) throw std::runtime_error("Can only tone-map a 32F RGB image.");
+    if (nRowSamples > image.rows || nColSamples > image.cols) throw std::runtime_error(kSampleCount);
+    if (chromaBandwidth != 0) throw std::runtime_error(kHdrNoChroma);
+    // as for 8-bit images a group forms only when NLE_DEVICES lists two devices or more
+    if (devices_env() != nullptr && device_group(-1) != nullptr) throw std::runtime_error(kHdrOneDevice);
+    // the image's range, log-luminance on the scale of an L plane, then the train on its guide (256 levels: the default
+    // table path); toneMap applies the filter to the unrounded plane on the same scale
+    nle_ctx* c = shared_ctx();
+    const HdrPlanes in = hdr_planes(c, image, true, 0, 0, false, true);
+    trainOnDevice(in.guide.f(), image.rows, image.cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors);
+    hdrHi_ = in.l_hi;
+    hdrRange_ = in.range;
+}
+
+Image NLEFilter::toneMap(const Image& image, const std::vector<DType>& weights, DType saturation) const {
+    if (image.channels() != 3 || image.depth() != NLE_32F) throw std::runtime_error("Can only tone-map a 32F RGB image.");
+    if (chromaBandwidth != 0) throw std::runtime_error(kHdrNoChroma);
+    if (!group_.empty()) throw std::runtime_error(kHdrOneDevice);
+    requireSize(image.total(), kTrainedSize);
+    if (!(hdrRange_ > 0)) throw std::runtime_error("toneMap needs a filter trained by trainForToneMapping.");
+    if (weights.empty()) throw std::runtime_error("toneMap needs at least one layer weight.");
+    const Vec fS = transformEigenValues(eigvals(), weights);
+    const HdrPlanes in = hdr_planes(ctx_, image, false, hdrHi_, hdrRange_, true, false);
+    Dev d_y(ctx_, image.total() * 4);
+    check(nle_apply(f_, in.x.f(), image.rows, image.cols, fS.data(), d_y.f()), ctx_);
+    return hdr_to_image(ctx_, in, d_y.f(), weights.back(), saturation, image.rows, image.cols);  // c = f(1), the base weight
+}
+
 void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
                                 int nSinkhornIter, int nEigenVectors, int sigmaColor, int sigmaSpace) {  // :521-538
+    refuse_hdr(image, "trainForDenoise");
     if (is_deep(image)) throw std::runtime_error("Denoise takes an 8-bit image: deep colour (16 bit) is built for enhance only.");
     if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enchance RGB image.");
     if (nRowSamples > image.rows || nColSamples > image.cols) throw std::runtime_error(kSampleCount);
@@ -219,6 +260,7 @@ void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSam
 }
 
 Image NLEFilter::denoise(const Image& image, DType k, int sigmaColor, int sigmaSpace) const {  // :349-410
+    refuse_hdr(image, "denoise");
     if (image.channels() != 3) throw std::runtime_error("Can only enchance RGB image.");  // (sic) :351-353
     if (is_deep(image)) throw std::runtime_error("Denoise takes an 8-bit image: deep colour (16 bit) is built for enhance only.");
     requireSize(image.total(), kTrainedSize);
@@ -298,6 +340,7 @@ std::vector<Image> NLEFilter::applyLayers(const Image& channel, int nLayers) con
 }
 
 Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights) const {  // :412-443
+    refuse_hdr(image, "enhance");
     if (image.channels() != 3) throw std::runtime_error("Can only enhance RGB image.");
     const int H = image.rows, W = image.cols;
     if (is_deep(image)) {  // deep colour: float Lab in, the filter on the unrounded L, 16-bit codes out; nothing is rounded to 8 bit
@@ -329,6 +372,7 @@ Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights) 
 Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& strokes,
                                  const std::vector<std::vector<DType>>& regionWeights, const std::vector<DType>& weights,
                                  DType spread, DType floor) const {
+    refuse_hdr(image, "enhanceRegions");
     if (is_deep(image)) throw std::runtime_error("Region edits take an 8-bit image: deep colour (16 bit) is built for enhance only.");
     if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enhance RGB image.");
     if (!group_.empty())
@@ -375,6 +419,7 @@ Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& st
 
 NLEFilter::Residual NLEFilter::nystromResidual(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int form,
                                                double thresh) const {
+    refuse_hdr(image, "nystromResidual");
     if (exact) throw std::runtime_error("nystromResidual: the exact filter has no Nystrom extension");
     const bool bgr = image.channels() == 3 && image.depth() == NLE_8U, deep = is_deep(image);
     if (!bgr && !deep && !(image.channels() == 1 && image.depth() == NLE_64F))

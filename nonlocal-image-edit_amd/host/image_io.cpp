@@ -1,11 +1,15 @@
 // Image file I/O for the enhance CLI (stand-in for OpenCV highgui/imgcodecs, which the reference
-// uses at src/enhance.cpp:33,47).  No arithmetic of the filter lives here.  BMP / PPM / PNG here, JPEG in jpeg.cpp.
+// uses at src/enhance.cpp:33,47).  No arithmetic of the filter lives here.  BMP / PPM / PNG and the HDR readers (Radiance
+// RGBE, PFM) here, JPEG in jpeg.cpp.
 #include "nle/image_io.hpp"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace nle {
@@ -425,7 +429,155 @@ bool ends_with(const std::string& s, const char* suf) {
     return true;
 }
 
+// ---- HDR readers: Radiance RGBE pictures and PFM, both to 32FC3 linear-light BGR.  Every read is checked against the
+// buffer's end; the dimensions are bounded like read_png's (1 .. 65535 each) before any arithmetic on them, and the data
+// a header promises must be there before the image is allocated.
+// the line that starts at *pos, without its '\n'; false at the end of the buffer or without a '\n'
+bool next_line(const std::vector<unsigned char>& b, size_t* pos, std::string* line) {
+    size_t e = *pos;
+    while (e < b.size() && b[e] != '\n') ++e;
+    if (e >= b.size()) return false;
+    line->assign(reinterpret_cast<const char*>(b.data()) + *pos, e - *pos);
+    *pos = e + 1;
+    return true;
+}
+
+// a decimal number of at most 5 digits at s[*i], in [1, 65535]; 0 if there is none
+long small_dim(const std::string& s, size_t* i) {
+    long v = 0;
+    size_t digits = 0;
+    while (*i < s.size() && s[*i] >= '0' && s[*i] <= '9' && digits < 6) v = v * 10 + (s[(*i)++] - '0'), ++digits;
+    return digits >= 1 && digits <= 5 && v >= 1 && v <= 65535 ? v : 0;
+}
+
+// mantissa m with exponent e: m 2^(e - 136), e = 0 gives 0
+float rgbe_value(unsigned m, unsigned e) { return e == 0 ? 0.f : std::ldexp((float)m, (int)e - 136); }
+
+Image read_radiance(const std::vector<unsigned char>& b) {
+    size_t pos = 0;
+    std::string line;
+    if (!next_line(b, &pos, &line) || (line != "#?RADIANCE" && line != "#?RGBE")) return Image();
+    bool format = false;
+    for (;;) {  // the header's variables, up to the empty line
+        if (!next_line(b, &pos, &line)) return Image();
+        if (line.empty()) break;
+        if (line.rfind("FORMAT=", 0) == 0) {
+            if (line != "FORMAT=32-bit_rle_rgbe") return Image();
+            format = true;
+        }
+    }
+    if (!format || !next_line(b, &pos, &line)) return Image();
+    size_t i = 3;  // the resolution line: "-Y H +X W" and nothing else
+    if (line.rfind("-Y ", 0) != 0) return Image();
+    const long h = small_dim(line, &i);
+    if (h == 0 || line.compare(i, 4, " +X ") != 0) return Image();
+    i += 4;
+    const long w = small_dim(line, &i);
+    if (w == 0 || i != line.size()) return Image();
+    const bool rle_ok = w >= 8 && w <= 32767;
+    // the fewest bytes a scanline takes: flat 4 w, run-length 4 + four components of ceil(w / 127) two-byte runs
+    const size_t flat = 4 * (size_t)w, least = rle_ok ? std::min(flat, 4 + 8 * (((size_t)w + 126) / 127)) : flat;
+    if (least * (size_t)h > b.size() - pos) return Image();
+    Image img((int)h, (int)w, NLE_32F, 3);
+    std::vector<unsigned char> comp(rle_ok ? 4 * (size_t)w : 0);
+    for (long r = 0; r < h; ++r) {
+        float* dst = img.ptr<float>((int)r);
+        if (b.size() - pos < 4) return Image();
+        const unsigned char* s = &b[pos];
+        if (rle_ok && s[0] == 2 && s[1] == 2 && s[2] < 128 && ((long)s[2] << 8 | s[3]) == w) {
+            pos += 4;
+            for (int k = 0; k < 4; ++k) {  // R, G, B, E: each component's w bytes in runs and literals
+                unsigned char* out = &comp[(size_t)k * w];
+                long x = 0;
+                while (x < w) {
+                    if (pos >= b.size()) return Image();
+                    const int c = b[pos++];
+                    if (c > 128) {
+                        const int len = c - 128;
+                        if (len > w - x || pos >= b.size()) return Image();
+                        std::memset(out + x, b[pos++], (size_t)len);
+                        x += len;
+                    } else {
+                        if (c == 0 || c > w - x || (size_t)c > b.size() - pos) return Image();
+                        std::memcpy(out + x, &b[pos], (size_t)c);
+                        pos += (size_t)c;
+                        x += c;
+                    }
+                }
+            }
+            for (long x = 0; x < w; ++x) {
+                const unsigned e = comp[3 * (size_t)w + x];
+                dst[3 * x + 0] = rgbe_value(comp[2 * (size_t)w + x], e);  // BGR like cv::imread
+                dst[3 * x + 1] = rgbe_value(comp[(size_t)w + x], e);
+                dst[3 * x + 2] = rgbe_value(comp[x], e);
+            }
+        } else {
+            if (b.size() - pos < flat) return Image();
+            for (long x = 0; x < w; ++x) {
+                const unsigned e = s[4 * x + 3];
+                dst[3 * x + 0] = rgbe_value(s[4 * x + 2], e);
+                dst[3 * x + 1] = rgbe_value(s[4 * x + 1], e);
+                dst[3 * x + 2] = rgbe_value(s[4 * x + 0], e);
+            }
+            pos += flat;
+        }
+    }
+    return img;
+}
+
+Image read_pfm(const std::vector<unsigned char>& b) {
+    const int ch = b[1] == 'F' ? 3 : 1;
+    size_t pos = 2;
+    // the next whitespace-separated token of the header, at most 63 characters
+    auto token = [&]() -> std::string {
+        while (pos < b.size() && (b[pos] == ' ' || b[pos] == '\n' || b[pos] == '\r' || b[pos] == '\t')) ++pos;
+        std::string t;
+        while (pos < b.size() && !(b[pos] == ' ' || b[pos] == '\n' || b[pos] == '\r' || b[pos] == '\t') && t.size() < 64)
+            t.push_back((char)b[pos++]);
+        return t.size() < 64 ? t : std::string();
+    };
+    if (b.size() < 3 || !(b[2] == ' ' || b[2] == '\n' || b[2] == '\r' || b[2] == '\t')) return Image();
+    const std::string tw = token(), th = token(), ts = token();
+    size_t iw = 0, ih = 0;
+    const long w = small_dim(tw, &iw), h = small_dim(th, &ih);
+    if (w == 0 || h == 0 || iw != tw.size() || ih != th.size() || ts.empty()) return Image();
+    char* end = nullptr;
+    const double scale = std::strtod(ts.c_str(), &end);
+    if (*end != '\0' || !(scale < 0 || scale > 0)) return Image();  // zero and NaN name no byte order
+    if (pos >= b.size()) return Image();
+    ++pos;  // the single whitespace after the scale
+    const size_t row = (size_t)w * ch * 4;
+    if (row * (size_t)h > b.size() - pos) return Image();
+    const bool little = scale < 0;
+    Image img((int)h, (int)w, NLE_32F, 3);
+    for (long r = 0; r < h; ++r) {  // the file's rows run bottom to top
+        const unsigned char* s = &b[pos + row * (size_t)(h - 1 - r)];
+        float* dst = img.ptr<float>((int)r);
+        for (long x = 0; x < w; ++x) {
+            float v[3];
+            for (int k = 0; k < ch; ++k) {
+                const unsigned char* p = s + ((size_t)x * ch + k) * 4;
+                const uint32_t bits = little ? rd32(p) : rd32be(p);
+                std::memcpy(&v[k], &bits, 4);
+            }
+            if (ch == 1) v[1] = v[2] = v[0];
+            dst[3 * x + 0] = v[2];  // the file is R, G, B
+            dst[3 * x + 1] = v[1];
+            dst[3 * x + 2] = v[0];
+        }
+    }
+    return img;
+}
+
 }  // namespace
+
+Image imreadHDR(const std::string& path) {
+    std::vector<unsigned char> b;
+    if (!read_file(path, &b) || b.size() < 2) return Image();
+    if (b[0] == '#' && b[1] == '?') return read_radiance(b);
+    if (b[0] == 'P' && (b[1] == 'F' || b[1] == 'f')) return read_pfm(b);
+    return Image();
+}
 
 Image imread(const std::string& path) {
     std::vector<unsigned char> b;

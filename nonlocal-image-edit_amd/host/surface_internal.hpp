@@ -1,7 +1,8 @@
 // What the translation units of the C++ surface (stages.cpp, colour.cpp, device_group.cpp, filter.cpp) share, and the
 // one owner of every step NLEFilter repeats: the process's shared ctx and its mode, status -> exception, the RAII device
 // buffer, the plane conversions, the options a train sets on a ctx (TrainOptions), the colour prologue (lab_planes) and
-// epilogue (lab_to_rows), and their deep-colour forms (lab16_planes, lab16_to_image).  Not installed: include/nle/filter.hpp is the surface.
+// epilogue (lab_to_rows), their deep-colour forms (lab16_planes, lab16_to_image) and their tone-mapping forms (hdr_planes,
+// hdr_to_image).  Not installed: include/nle/filter.hpp is the surface.
 #pragma once
 
 #include <cmath>
@@ -183,6 +184,40 @@ inline Image lab16_to_image(nle_ctx* c, const Lab16Planes& in, const float* d_L,
     const size_t n = out.total();
     check(nle_lab_to_bgr16(c, d_L, in.a.f(), in.b.f(), (long long)n, static_cast<unsigned short*>(in.bgr.p)), c);
     check(nle_dev_download(c, out.ptr<unsigned short>(), in.bgr.p, n * 6), c);
+    return out;
+}
+
+// ---- HDR tone mapping (32FC3 linear-light images): the same two steps on log-luminance ----
+// prologue: the image on the device and, on the scale (l_hi, range), x (the unrounded log-luminance plane) or the guide (x
+// rounded to the 256 levels a train takes), whichever is wanted; with find_range the scale is first taken from the image
+struct HdrPlanes {
+    Dev bgr, x, guide;
+    double l_hi = 0, range = 0;
+};
+inline HdrPlanes hdr_planes(nle_ctx* c, const Image& image, bool find_range, double l_hi, double range, bool want_x,
+                            bool want_guide) {
+    const size_t n = image.total();
+    HdrPlanes o;
+    o.bgr = Dev(c, n * 12);
+    if (want_x) o.x = Dev(c, n * 4);
+    if (want_guide) o.guide = Dev(c, n * 4);
+    check(nle_dev_upload(c, o.bgr.p, image.ptr<float>(), n * 12), c);
+    if (find_range) check(nle_hdr_range(c, o.bgr.f(), (long long)n, &l_hi, &range), c);
+    o.l_hi = l_hi;
+    o.range = range;
+    check(nle_hdr_to_loglum(c, o.bgr.f(), (long long)n, l_hi, range, o.x.f(), o.guide.f()), c);
+    return o;
+}
+
+// epilogue: the filtered plane d_y with in's colours -> a 16UC3 sRGB image of the input's size
+inline Image hdr_to_image(nle_ctx* c, const HdrPlanes& in, const float* d_y, double base_weight, double saturation, int rows,
+                          int cols) {
+    Image out(rows, cols, NLE_16U, 3);
+    const size_t n = out.total();
+    Dev d_out(c, n * 6);
+    check(nle_loglum_to_bgr16(c, d_y, in.bgr.f(), (long long)n, in.l_hi, in.range, base_weight, saturation,
+                              static_cast<unsigned short*>(d_out.p)), c);
+    check(nle_dev_download(c, out.ptr<unsigned short>(), d_out.p, n * 6), c);
     return out;
 }
 
