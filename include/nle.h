@@ -618,6 +618,45 @@ int nle_apply_regions(nle_filter* f, const float* d_x, int H, int W, int L, cons
                       const double* h_scale, double spread, double floor, const double* h_weights, int out_kind,
                       void* d_out);
 
+/* ---- the out-of-span detail layer and the detail curve (new in this build: no reference, so this text and DESIGN.md
+ * section 3.15 are the definition) ---- */
+/* The layers of nle_apply_layers sum to V V^T x, not to x: what of the plane lies outside the span of the K' trained
+ * eigenvectors belongs to no layer, and no layer weight brings it back.  Here that residual is one more weighted layer, and
+ * the detail layers may pass a monotone gain curve that boosts (or cores) small amplitudes and leaves edges their size.
+ * Per pixel i, in fp64, every operation rounded on its own (no fma), in the order written.  Inputs: the plane x; the layers
+ * Y_0 .. Y_{L-1}, fp32, 1 <= L <= NLE_REGION_LAYERS_MAX; the weights w_0 .. w_{L-1}; the residual weight w_rho; the gain a;
+ * the amplitude sigma.
+ *   S    = ((Y_0 + Y_1) + ..) + Y_{L-1}
+ *   rho  = x - S
+ *   g(d) = d                                    if sigma == 0 or a == 1 (no exp is evaluated)
+ *   g(d) = d (1 + (a - 1) exp(-(t t))),  t = d / sigma, otherwise      (a - 1 is formed once on the host)
+ *   y    = w_rho g(rho) + w_0 g(Y_0) + .. + w_{L-2} g(Y_{L-2}) + w_{L-1} Y_{L-1}
+ * The sum for y runs left to right.  The base layer Y_{L-1} is never remapped; for L = 1 the rule is y = w_rho g(rho) +
+ * w_0 Y_0.
+ * g has slope a at 0 and tends to d for |d| >> sigma: small amplitudes are boosted (a > 1) or cored (a < 1), edges keep their
+ * size, so nothing clips and no halo appears.  g' = 1 + (a - 1) e^(-t^2) (1 - 2 t^2), whose second factor lies in [-0.4463, 1]
+ * (minimum at t^2 = 3/2): g is strictly increasing for 0 < a < 3.24, non-decreasing at a = 0, and Lipschitz with the constant
+ * max(a, 1.4463 - 0.4463 a).
+ * Accepted: a finite in [0, 3]; sigma finite and >= 0, 0 meaning the curve is off; w_rho and the weights finite.
+ * Output kinds: the three of nle_region_combine with its store rule ((float)y, then the saturating round for _ROUNDED8 / _U8).
+ * Identity: with every weight 1, w_rho = 1 and the curve off, y = x up to a few fp64 ulp of sum |Y_l|; for an integer plane
+ * (float)y == x exactly (at x = 0 that residue has no integer to round to: NLE_REGION_OUT_F32 stores it as it is, the other
+ * two kinds store 0).  The sign of a zero level is not specified.
+ * nle_detail_combine is the stage call, the rule alone, on any planes: d_x n floats, layer l at d_layers + l layer_stride
+ * (stride in floats, >= n), h_weights L doubles, d_out n floats, or n bytes for NLE_REGION_OUT_U8.  No alignment is required
+ * of pointers or strides; x and the layers are read once.
+ * nle_apply_detail runs nle_apply_layers into the ctx's workspace and then the combine: bitwise what the two calls give, for
+ * every formulation nle_apply_layers works for.
+ * Both return NLE_ERR_INVALID with a message, enqueue nothing and leave the ctx usable for: L out of range, a NULL pointer,
+ * a weight (w_rho included) that is not finite, a gain outside [0, 3] or not finite, a sigma that is negative or not finite,
+ * an unknown out kind, d_out overlapping an input, n < 1 or a layer stride smaller than n (the stage call), H W that is not
+ * the filter's and world > 1 (nle_apply_detail: slabs and device groups are not built for it, as for regions). */
+#define NLE_DETAIL_GAIN_MAX 3
+int nle_detail_combine(nle_ctx* ctx, const float* d_x, const float* d_layers, int L, long long n, long long layer_stride,
+                       const double* h_weights, double w_rho, double gain, double sigma, int out_kind, void* d_out);
+int nle_apply_detail(nle_filter* f, const float* d_x, int H, int W, int L, const double* h_weights, double w_rho, double gain,
+                     double sigma, int out_kind, void* d_out);
+
 /* ---- several planes through one filter (new in this build) ---- */
 /* Applies f to P planes in one call, each plane with its own set of responses: the channels of a colour image, several guide
  * planes, the stroke planes of the region edits, the a / b pair of the denoiser.  nle_apply (P = 1, one response) and

@@ -169,6 +169,12 @@ Image lab2bgr8_device(const Image& lab);
 Image bilateralFilter8(const Image& plane, double sigmaColor, double sigmaSpace);
 Image bilateralFilter8_device(const Image& plane, double sigmaColor, double sigmaSpace);
 
+// the options of NLEFilter::enhance / toneMap with the out-of-span detail layer and the detail curve (new here; see there)
+struct DetailOptions {
+    double residualWeight = 0, gain = 1, sigma = 0;
+    bool active() const { return !(residualWeight == 0 && (sigma == 0 || gain == 1)); }
+};
+
 // include/filter.hpp:35-54.  The trained state (m_eigvecs N x K', m_eigvals) lives on the GPU.
 class NLEFilter {
 public:
@@ -195,6 +201,17 @@ public:
     void trainForToneMapping(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
                              int nSinkhornIter = 10, int nEigenVectors = 5);
     Image toneMap(const Image& I, const std::vector<DType>& weights, DType saturation = 1) const;
+    // The out-of-span detail layer and the detail curve (new here; DESIGN.md section 3.15, nle_detail_combine in nle.h states
+    // the rule).  The layers that `weights` scale sum to V V^T x, not to x: what of the plane the trained eigenvectors do not
+    // span is in no layer.  residualWeight gives that residual back as one more layer (1: weights of all ones return the
+    // plane), and gain in [0, 3] with sigma > 0 sends the residual and every layer but the base through a monotone curve of
+    // slope `gain` at 0 that tends to the identity for amplitudes far above sigma -- texture is boosted (or cored, gain < 1)
+    // and edges keep their size.  Options with residualWeight == 0 and (sigma == 0 or gain == 1) are inactive: the call is
+    // the plain method's, bit for bit.  Active options run nle_apply_detail on the plane the plain method filters (8 bit:
+    // rounded to levels; 16 bit: the unrounded L; 32F: the unrounded log-luminance, the last weight still the base weight).
+    // One device: a filter trained on a device group throws; 1 to NLE_REGION_LAYERS_MAX weights.
+    Image enhance(const Image& I, const std::vector<DType>& weights, const DetailOptions& detail) const;
+    Image toneMap(const Image& I, const std::vector<DType>& weights, DType saturation, const DetailOptions& detail) const;
     // region edits (new here; nle_apply_regions in nle.h states the rule): enhance with layer weights of its own for every
     // scribbled region.  strokes[m]: a one-channel 8-bit image of I's size, a pixel belongs to the stroke where its byte is
     // >= 128; regionWeights[m]: the weights of region m, as many as `weights`, which is the background's row.  Each stroke

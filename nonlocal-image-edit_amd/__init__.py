@@ -41,6 +41,7 @@ SAMPLER_RESIDUAL = _abi.NLE_SAMPLER_RESIDUAL
 REGION_MAX, REGION_LAYERS_MAX = _abi.NLE_REGION_MAX, _abi.NLE_REGION_LAYERS_MAX
 REGION_OUT_F32, REGION_OUT_ROUNDED8, REGION_OUT_U8 = (_abi.NLE_REGION_OUT_F32, _abi.NLE_REGION_OUT_ROUNDED8,
                                                       _abi.NLE_REGION_OUT_U8)
+DETAIL_GAIN_MAX = _abi.NLE_DETAIL_GAIN_MAX  # nle_detail_combine / nle_apply_detail: the gain lies in [0, DETAIL_GAIN_MAX]
 PLANES_MAX = _abi.NLE_PLANES_MAX  # nle_apply_planes: planes per call (its output kinds are REGION_OUT_F32 / _ROUNDED8)
 RESID_AUTO, RESID_ROWS, RESID_FUSED = _abi.NLE_RESID_AUTO, _abi.NLE_RESID_ROWS, _abi.NLE_RESID_FUSED  # nle_nystrom_residual
 
@@ -1044,6 +1045,25 @@ class Context:
                                         float(floor), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    def detail_combine(self, x, layers, weights, residual_weight=0.0, gain=1.0, sigma=0.0, out_kind=0, out=None):
+        """nle_detail_combine, the rule alone: x (n,) and layers (L, n) float32 device tensors, the rows of layers contiguous
+        and any stride >= n apart (a view into a larger buffer, at any offset, is taken as it is); weights L float64 values.
+        Returns n float32 values, or n bytes for REGION_OUT_U8."""
+        torch = _torch()
+        self._sync_in()
+        L, n = layers.shape
+        if x.shape != (n,) or x.stride(0) != 1 or layers.stride(1) != 1:
+            raise NLEError(NLE_ERR_INVALID, "detail_combine: x (n,) and layers (L, n) with contiguous rows")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (L,):
+            raise NLEError(NLE_ERR_INVALID, f"detail_combine: weights must hold L = {L} values, got {w.shape}")
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32, device=layers.device)
+        _check(lib().nle_detail_combine(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(layers.data_ptr()), L, n,
+                                        layers.stride(0) if L > 1 else n, _np_ptr(w), float(residual_weight), float(gain),
+                                        float(sigma), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
+        return out
+
     def bench_affinity(self, lum, n_row_samples, n_col_samples, hx, hy, reps=10):
         torch = _torch()
         lum = self._lum(lum)
@@ -1382,6 +1402,24 @@ class NLEFilter:
         _check(lib().nle_apply_regions(self._f, C.c_void_p(x.data_ptr()), H, W, int(n_layers), C.c_void_p(s.data_ptr()), M,
                                        cp, float(spread), float(floor), _np_ptr(w), int(out_kind),
                                        C.c_void_p(out.data_ptr())), self.ctx._h)
+        return out
+
+    def apply_detail(self, x, weights, residual_weight=0.0, gain=1.0, sigma=0.0, out_kind=0, out=None):
+        """nle_apply_detail: the len(weights) layers of x and the detail combine in one call -- the out-of-span residual
+        x - sum of the layers as one more layer under residual_weight, and the gain curve (gain, sigma) on the residual and
+        on every layer but the last.  Returns n_local float32 values, or bytes for REGION_OUT_U8."""
+        torch = _torch()
+        x = self.ctx._lum(x)
+        H, W = x.shape
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 1:
+            raise NLEError(NLE_ERR_INVALID, f"weights must be a vector, got {w.shape}")
+        if out is None:
+            out = torch.empty(self.info()["n_local"], dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32,
+                              device=x.device)
+        _check(lib().nle_apply_detail(self._f, C.c_void_p(x.data_ptr()), H, W, int(w.shape[0]), _np_ptr(w),
+                                      float(residual_weight), float(gain), float(sigma), int(out_kind),
+                                      C.c_void_p(out.data_ptr())), self.ctx._h)
         return out
 
     def apply_layers(self, x, n_layers, out=None):

@@ -441,6 +441,14 @@ struct RegionWeights {
 hipError_t region_combine(hipStream_t s, const float* d_layers, long long layer_stride, int L, const float* d_q,
                           long long q_stride, int M, long long n, const RegionWeights& wt, double floor, int out_kind,
                           void* d_out);
+// the out-of-span detail layer and the detail curve (detail.hip; the rule is stated in include/nle.h at nle_detail_combine):
+// per pixel rho = x - sum of the L layers joins them as one more weighted layer, and rho and every layer but the last pass
+// the gain curve g first -- fp64, every operation rounded on its own.  Planes and out_kind as for region_combine.
+struct DetailWeights {
+    double w[kRegionLayersMax];  // the first L entries are read
+};
+hipError_t detail_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
+                          const DetailWeights& w, double w_rho, double gain, double sigma, int out_kind, void* d_out);
 // single-channel 8-bit bilateral filter (fp32 planes holding integers); tables from the host: space_w (2r+1)^2 with 0
 // outside the circle, colour_w 256 entries
 int bilateral8_max_radius();

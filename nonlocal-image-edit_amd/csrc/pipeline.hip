@@ -425,6 +425,42 @@ void region_spread_impl(nle_filter* f, const float* d_strokes, int M, int H, int
     apply_planes_impl(f, planes, M, H, W, ones, fS.data(), d_q, f->n_local, false);
 }
 
+// ---- the out-of-span detail layer and the detail curve (include/nle.h at nle_detail_combine; the kernel is detail.hip) ----
+// every refusal the two entry points share, before anything is enqueued
+void detail_check(const char* who, int L, const double* h_weights, double w_rho, double gain, double sigma, int out_kind) {
+    const std::string name(who);
+    if (L < 1 || L > NLE_REGION_LAYERS_MAX)
+        throw Fail{NLE_ERR_INVALID, name + " takes 1 to " + std::to_string(NLE_REGION_LAYERS_MAX) + " layers, got " +
+                                        std::to_string(L)};
+    if (!h_weights) throw Fail{NLE_ERR_INVALID, name + ": NULL pointer"};
+    for (int l = 0; l < L; ++l)
+        if (!std::isfinite(h_weights[l])) throw Fail{NLE_ERR_INVALID, name + ": weight " + std::to_string(l) + " is not finite"};
+    if (!std::isfinite(w_rho)) throw Fail{NLE_ERR_INVALID, name + ": the residual weight is not finite"};
+    if (!std::isfinite(gain) || gain < 0 || gain > NLE_DETAIL_GAIN_MAX)
+        throw Fail{NLE_ERR_INVALID, name + ": the detail gain must be finite and in [0, " + std::to_string(NLE_DETAIL_GAIN_MAX) +
+                                        "], got " + std::to_string(gain)};
+    if (!std::isfinite(sigma) || sigma < 0)
+        throw Fail{NLE_ERR_INVALID, name + ": the detail sigma must be finite and >= 0, got " + std::to_string(sigma)};
+    if (out_kind != NLE_REGION_OUT_F32 && out_kind != NLE_REGION_OUT_ROUNDED8 && out_kind != NLE_REGION_OUT_U8)
+        throw Fail{NLE_ERR_INVALID, name + ": unknown output kind " + std::to_string(out_kind) + " (NLE_REGION_OUT_*)"};
+}
+
+// d_out (n floats, or n bytes for NLE_REGION_OUT_U8) must not overlap the n floats at d_in
+void detail_check_overlap(const char* who, const float* d_in, const void* d_out, long long n, int out_kind, const char* what) {
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), i1 = i0 + (uintptr_t)n * sizeof(float);
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (uintptr_t)n * (out_kind == NLE_REGION_OUT_U8 ? 1 : 4);
+    if (i0 < o1 && o0 < i1) throw Fail{NLE_ERR_INVALID, std::string(who) + ": d_out overlaps " + what};
+}
+
+void detail_combine_impl(nle_ctx* c, const float* d_x, const float* d_layers, int L, long long n, long long layer_stride,
+                         const double* h_weights, double w_rho, double gain, double sigma, int out_kind, void* d_out) {
+    nlek::DetailWeights w{};
+    std::copy(h_weights, h_weights + L, w.w);
+    HIP_OK(hipSetDevice(c->device));
+    HIP_OK(nlek::detail_combine(c->stream, d_x, d_layers, layer_stride, L, n, w, w_rho, gain, sigma, out_kind, d_out));
+    HIP_OK(hipStreamSynchronize(c->stream));
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------ C ABI
@@ -797,6 +833,43 @@ int nle_apply_regions(nle_filter* f, const float* d_x, int H, int W, int L, cons
         for (int m = 0; m < M; ++m) planes[1 + m] = d_strokes + (size_t)m * H * W, nresp[1 + m] = 1;
         apply_planes_impl(f, planes, 1 + M, H, W, nresp, resp.data(), d_work.p, n, false);
         region_combine_impl(c, d_work.p, L, d_work.p + (size_t)L * n, M, n, n, n, h_weights, floor, out_kind, d_out);
+    });
+}
+
+int nle_detail_combine(nle_ctx* ctx, const float* d_x, const float* d_layers, int L, long long n, long long layer_stride,
+                       const double* h_weights, double w_rho, double gain, double sigma, int out_kind, void* d_out) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_x || !d_layers || !h_weights || !d_out) throw Fail{NLE_ERR_INVALID, "nle_detail_combine: NULL pointer"};
+        detail_check("nle_detail_combine", L, h_weights, w_rho, gain, sigma, out_kind);
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_detail_combine: n must be >= 1"};
+        if ((L > 1 && layer_stride < n) || layer_stride < 0)
+            throw Fail{NLE_ERR_INVALID, "nle_detail_combine: the layer stride is smaller than n"};
+        detail_check_overlap("nle_detail_combine", d_x, d_out, n, out_kind, "the plane");
+        for (int l = 0; l < L; ++l)
+            detail_check_overlap("nle_detail_combine", d_layers + (size_t)l * layer_stride, d_out, n, out_kind, "a layer");
+        detail_combine_impl(ctx, d_x, d_layers, L, n, layer_stride, h_weights, w_rho, gain, sigma, out_kind, d_out);
+    });
+}
+
+int nle_apply_detail(nle_filter* f, const float* d_x, int H, int W, int L, const double* h_weights, double w_rho, double gain,
+                     double sigma, int out_kind, void* d_out) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        nle_ctx* c = f->ctx;
+        if (!d_x || !h_weights || !d_out) throw Fail{NLE_ERR_INVALID, "nle_apply_detail: NULL pointer"};
+        detail_check("nle_apply_detail", L, h_weights, w_rho, gain, sigma, out_kind);
+        if (c->world > 1)
+            throw Fail{NLE_ERR_INVALID, "nle_apply_detail runs on one device only (world == 1): slabs and device groups are not built"};
+        if (H <= 0 || W <= 0 || (long long)H * W != (long long)f->H * f->W)  // the text of nle_apply's refusal (:447-449)
+            throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+        const long long n = f->n_local;  // == H W: world == 1
+        detail_check_overlap("nle_apply_detail", d_x, d_out, n, out_kind, "the plane");
+        DevBuf<float> d_work((size_t)L * n);
+        std::vector<double> resp((size_t)L * f->K);
+        layer_resp(f->eigvals.data(), f->K, L, resp.data());
+        apply_impl(f, d_x, H, W, resp.data(), L, d_work.p);  // nle_apply_layers
+        detail_combine_impl(c, d_x, d_work.p, L, n, n, h_weights, w_rho, gain, sigma, out_kind, d_out);
     });
 }
 

@@ -15,7 +15,10 @@
 // the result is written as a 16-bit PNG (the output name must end in .png; not with --region); and the flag `--tonemap`
 // (no value) with its optional `--tonemap-saturation S` (a finite number in (0, 2]): the input is an HDR file read with
 // imreadHDR, the positional weights are the layer weights of NLEFilter::toneMap -- the last one is the base compression --
-// and the result is a 16-bit PNG (not with --chroma, --region, --deep or --nystrom-report).
+// and the result is a 16-bit PNG (not with --chroma, --region, --deep or --nystrom-report); and `--residual-weight WR` (a
+// finite number), `--detail-gain A` (finite, in [0, NLE_DETAIL_GAIN_MAX]) and `--detail-sigma S` (finite, >= 0):
+// nle::DetailOptions of NLEFilter::enhance / toneMap, with --deep and --tonemap too (a gain other than 1 needs a sigma > 0;
+// not with --region).
 #pragma once
 
 #include <cctype>
@@ -51,6 +54,7 @@ struct FilterArgs {
     bool deep = false;               // --deep (enhance only): 16-bit PNG in, 16-bit PNG out
     bool tonemap = false;            // --tonemap (enhance only): Radiance / PFM in, 16-bit PNG out
     double tonemapSaturation = 1;    // --tonemap-saturation S (with --tonemap)
+    nle::DetailOptions detail;       // --residual-weight WR, --detail-gain A, --detail-sigma S (enhance only)
     bool nystromReport = false;  // --nystrom-report (enhance only)
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
@@ -72,12 +76,14 @@ inline double positive_option(const char* prog, const std::string& opt, const st
 // allow_nystrom: the tool takes `--nystrom-report` / `--nystrom-map FILE` (enhance); otherwise they are refused
 // allow_deep: the tool takes `--deep` (enhance); otherwise it is refused (denoise has no 16-bit path)
 // allow_tonemap: the tool takes `--tonemap` / `--tonemap-saturation S` (enhance); otherwise they are refused
+// allow_detail: the tool takes `--residual-weight WR` / `--detail-gain A` / `--detail-sigma S` (enhance); otherwise refused
 inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false,
                   bool allow_regions = false, bool allow_nystrom = false, bool allow_deep = false,
-                  bool allow_tonemap = false) {
+                  bool allow_tonemap = false, bool allow_detail = false) {
     std::vector<char*> shifted;
     int first = 1;  // the first argument after the leading options
     bool spreadGiven = false, floorGiven = false, saturationGiven = false;
+    std::string detailGiven;  // the last of --residual-weight / --detail-gain / --detail-sigma seen
     while (first < argc) {
         const std::string opt = argv[first];
         if (opt == "--exact") {
@@ -147,6 +153,40 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
                 std::exit(2);
             }
             a->nystromMap = file;
+            first += 2;
+            continue;
+        }
+        if (opt == "--residual-weight" || opt == "--detail-gain" || opt == "--detail-sigma") {
+            if (!allow_detail) {
+                std::cerr << argv[0] << ": " << opt << " is not supported here: the detail options weigh layers, which this tool "
+                          << "does not take" << std::endl;
+                std::exit(2);
+            }
+            const std::string v = first + 1 < argc ? argv[first + 1] : "";
+            char* end = nullptr;
+            const double x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            const bool number = !v.empty() && *end == '\0' && std::isfinite(x);
+            if (opt == "--residual-weight") {
+                if (!number) {
+                    std::cerr << argv[0] << ": --residual-weight takes a finite number, got '" << v << "'" << std::endl;
+                    std::exit(2);
+                }
+                a->detail.residualWeight = x;
+            } else if (opt == "--detail-gain") {
+                if (!number || x < 0 || x > NLE_DETAIL_GAIN_MAX) {
+                    std::cerr << argv[0] << ": --detail-gain takes a finite number in [0, " << NLE_DETAIL_GAIN_MAX << "], got '" << v
+                              << "'" << std::endl;
+                    std::exit(2);
+                }
+                a->detail.gain = x;
+            } else {
+                if (!number || x < 0) {
+                    std::cerr << argv[0] << ": --detail-sigma takes a finite number >= 0, got '" << v << "'" << std::endl;
+                    std::exit(2);
+                }
+                a->detail.sigma = x;
+            }
+            detailGiven = opt;
             first += 2;
             continue;
         }
@@ -258,6 +298,16 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
                   << "an 8-bit or 16-bit sRGB image" << std::endl;
         std::exit(2);
     }
+    if (a->detail.gain != 1 && !(a->detail.sigma > 0)) {
+        std::cerr << argv[0] << ": --detail-gain other than 1 needs --detail-sigma S > 0 (the amplitude the gain acts below)"
+                  << std::endl;
+        std::exit(2);
+    }
+    if (!detailGiven.empty() && !a->regions.empty()) {
+        std::cerr << argv[0] << ": " << detailGiven << " does not combine with --region: region edits have no residual layer "
+                  << "and no detail curve" << std::endl;
+        std::exit(2);
+    }
     if ((spreadGiven || floorGiven) && a->regions.empty()) {
         std::cerr << argv[0] << ": --region-spread and --region-floor need at least one --region" << std::endl;
         std::exit(2);
@@ -295,6 +345,11 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
         else *reals[i] = std::stod(argv[3 + i]);
     }
     for (int i = 9; i < argc; ++i) a->extra.push_back(std::stod(argv[i]));
+    if (a->detail.active() && (int)a->extra.size() > NLE_REGION_LAYERS_MAX) {
+        std::cerr << argv[0] << ": " << detailGiven << " takes at most " << NLE_REGION_LAYERS_MAX << " weights, got "
+                  << a->extra.size() << std::endl;
+        std::exit(2);
+    }
     if (!a->regions.empty()) {  // every region has the background's weight count
         if ((int)a->extra.size() > NLE_REGION_LAYERS_MAX) {
             std::cerr << argv[0] << ": --region takes at most " << NLE_REGION_LAYERS_MAX << " weights, got "

@@ -9,7 +9,8 @@
 // its pixel, share of pixels above 0.5) and the map as an 8-bit grey image, round(255 clamp(r, 0, 1)); and `--deep`: 16-bit
 // PNG in, 16-bit PNG out through the float Lab path (NLEFilter on a 16UC3 image), same banners; and `--tonemap
 // [--tonemap-saturation S]`: a Radiance or PFM file in, 16-bit PNG out through NLEFilter::trainForToneMapping / toneMap, the
-// weights being the layer weights (the last one compresses the base layer), same banners.
+// weights being the layer weights (the last one compresses the base layer), same banners; and `--residual-weight WR`,
+// `--detail-gain A`, `--detail-sigma S`: nle::DetailOptions of enhance / toneMap (the out-of-span layer and the detail curve).
 #include <algorithm>
 
 #include "cli_common.hpp"
@@ -17,7 +18,7 @@
 int main(int argc, char* argv[]) {
     nlecli::FilterArgs a;
     if (!nlecli::parse(argc, argv, 10, &a, /*allow_chroma=*/true, /*allow_regions=*/true, /*allow_nystrom=*/true,
-                       /*allow_deep=*/true, /*allow_tonemap=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
+                       /*allow_deep=*/true, /*allow_tonemap=*/true, /*allow_detail=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
     const nle::Image image = nlecli::load(a);
     if (image.empty()) return 0;                        // src/enhance.cpp:34-37
     // the strokes: the first channel of every mask, read before anything touches the GPU
@@ -52,8 +53,9 @@ int main(int argc, char* argv[]) {
     filter.chromaBandwidth = a.chroma;
     if (a.tonemap) filter.trainForToneMapping(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
     else filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
-    const nle::Image result = a.tonemap        ? filter.toneMap(image, a.extra, a.tonemapSaturation)
-                              : strokes.empty() ? filter.enhance(image, a.extra)  // the weights are argv[9..]
+    // (inactive detail options are the plain methods)
+    const nle::Image result = a.tonemap        ? filter.toneMap(image, a.extra, a.tonemapSaturation, a.detail)
+                              : strokes.empty() ? filter.enhance(image, a.extra, a.detail)  // the weights are argv[9..]
                                                 : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,
                                                                         a.regionFloor);
     nlecli::report(filter);

@@ -369,6 +369,60 @@ Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights) 
     return out;
 }
 
+namespace {
+
+const char kDetailOneDevice[] = "DetailOptions (residualWeight, gain, sigma) run on one device: this filter was trained on a device group (NLE_DEVICES).";
+
+// the layer count of a call with active DetailOptions
+int detail_layers(const std::vector<DType>& weights) {
+    if (weights.empty() || (int)weights.size() > NLE_REGION_LAYERS_MAX)
+        throw std::runtime_error("DetailOptions take 1 to " + std::to_string(NLE_REGION_LAYERS_MAX) + " weights.");
+    return (int)weights.size();
+}
+
+}  // namespace
+
+Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights, const DetailOptions& detail) const {
+    if (!detail.active()) return enhance(image, weights);
+    refuse_hdr(image, "enhance");
+    if (image.channels() != 3 || (image.depth() != NLE_8U && image.depth() != NLE_16U))
+        throw std::runtime_error("Can only enhance RGB image.");
+    if (!group_.empty()) throw std::runtime_error(kDetailOneDevice);
+    requireSize(image.total(), kTrainedSize);
+    const int H = image.rows, W = image.cols, L = detail_layers(weights);
+    Dev d_y(ctx_, image.total() * 4);
+    if (is_deep(image)) {  // enhance's deep body with nle_apply_detail in place of nle_apply: the unrounded L, nothing rounded
+        const Lab16Planes in = lab16_planes(ctx_, image, true, false);
+        check(nle_apply_detail(f_, in.L.f(), H, W, L, weights.data(), detail.residualWeight, detail.gain, detail.sigma,
+                               NLE_REGION_OUT_F32, d_y.f()), ctx_);
+        return lab16_to_image(ctx_, in, d_y.f(), H, W);
+    }
+    // enhance_rows' body with nle_apply_detail in place of nle_apply_rounded8
+    const LabPlanes in = lab_planes(ctx_, image.ptr<unsigned char>(), image.total(), true, false);
+    check(nle_apply_detail(f_, in.L.f(), H, W, L, weights.data(), detail.residualWeight, detail.gain, detail.sigma,
+                           NLE_REGION_OUT_ROUNDED8, d_y.f()), ctx_);
+    Image out(H, W, NLE_8U, 3);
+    lab_to_rows(ctx_, in, d_y.f(), nullptr, nullptr, out, 0, H);
+    return out;
+}
+
+Image NLEFilter::toneMap(const Image& image, const std::vector<DType>& weights, DType saturation,
+                         const DetailOptions& detail) const {
+    if (!detail.active()) return toneMap(image, weights, saturation);
+    if (image.channels() != 3 || image.depth() != NLE_32F) throw std::runtime_error("Can only tone-map a 32F RGB image.");
+    if (chromaBandwidth != 0) throw std::runtime_error(kHdrNoChroma);
+    if (!group_.empty()) throw std::runtime_error(kDetailOneDevice);
+    requireSize(image.total(), kTrainedSize);
+    if (!(hdrRange_ > 0)) throw std::runtime_error("toneMap needs a filter trained by trainForToneMapping.");
+    const int L = detail_layers(weights);
+    // toneMap's body with nle_apply_detail in place of nle_apply: the unrounded log-luminance
+    const HdrPlanes in = hdr_planes(ctx_, image, false, hdrHi_, hdrRange_, true, false);
+    Dev d_y(ctx_, image.total() * 4);
+    check(nle_apply_detail(f_, in.x.f(), image.rows, image.cols, L, weights.data(), detail.residualWeight, detail.gain,
+                           detail.sigma, NLE_REGION_OUT_F32, d_y.f()), ctx_);
+    return hdr_to_image(ctx_, in, d_y.f(), weights.back(), saturation, image.rows, image.cols);  // c = the base weight
+}
+
 Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& strokes,
                                  const std::vector<std::vector<DType>>& regionWeights, const std::vector<DType>& weights,
                                  DType spread, DType floor) const {
