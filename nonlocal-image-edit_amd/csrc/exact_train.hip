@@ -116,8 +116,11 @@ struct ExactSolver {
     }
     // Block W = Q[:, m : m+b] against Q[:, :m] (CGS2; the coefficients are the off-diagonal block of the Gram matrix of
     // Q[:, :m+b], so gram64d serves as the cross product) and within itself (CholQR2).  C1 (m x b, column-major): the
-    // first pass's coefficients Q[:, :m]^T W.  false: W is numerically rank deficient.
-    bool orth(double* Q, int ldq, int m, int b, double* T, std::vector<double>* C1) {
+    // first pass's coefficients Q[:, :m]^T W; w2 (m > 0): the largest squared column norm of W as it came.  false: W is
+    // numerically rank deficient.  The first CholQR pass refuses such a block and leaves it as the projection made it; a
+    // first pass that went through (condition below 1e12) leaves a block the second pass cannot refuse but for rounding,
+    // and then W is rescaled already: `deflate` takes either.
+    bool orth(double* Q, int ldq, int m, int b, double* T, std::vector<double>* C1, double* w2 = nullptr) {
         double* Wp = Q + m;
         const int n = m + b;
         for (int pass = 0; pass < 2 && m > 0; ++pass) {
@@ -126,6 +129,10 @@ struct ExactSolver {
             for (int j = 0; j < b; ++j)
                 for (int i = 0; i < m; ++i) Cm[(size_t)j * m + i] = G[(size_t)(m + j) * n + i];
             if (pass == 0 && C1) *C1 = Cm;
+            if (pass == 0 && w2) {
+                *w2 = 0.0;
+                for (int j = 0; j < b; ++j) *w2 = std::max(*w2, G[(size_t)(m + j) * n + m + j]);
+            }
             gemm(Q, ldq, m, Cm, b, T, b);
             HIP_OK(nlek::exact_axpby(c->stream, Wp, ldq, 1.0, T, b, -1.0, Wp, ldq, N, b, b));
         }
@@ -243,6 +250,36 @@ struct ExactLanczos {
         }
         throw Fail{NLE_ERR_NUMERIC, "exact filter: cannot extend the Krylov basis"};
     }
+    // The block Q[:, at : at+b] is orthogonal to the basis but numerically rank deficient (Ws of rank below the basis, as
+    // for a plane of few levels under a wide spatial bandwidth).  Its independent directions stay: without them a range
+    // whose dimension is no multiple of b never enters the basis whole, and no Ritz pair converges.  Kept: the singular
+    // directions within 1e-6 of the block's largest and above 1e-10 of the block as it came (w2: its largest squared
+    // column norm), so what the projection left is signal and not its rounding; start vectors fill the other columns.
+    // D holds eigenvalues of the Gram matrix, squared singular values: the two thresholds stand squared in the code,
+    // 1e-12 and 1e-20.  (After a refusal in orth's second pass the block is near orthonormal and w2 no longer its scale:
+    // the second test then passes for every direction and the first one decides.)
+    void deflate(int at, double w2) {
+        const std::vector<double> G = sv.gram(Q.p + at, ldq, b);
+        const double h0 = now_ms();
+        std::vector<double> U((size_t)b * b), D(b), B((size_t)b * b, 0.0);
+        if (!nleh::sym_eigen(G.data(), b, U.data(), D.data()))
+            throw Fail{NLE_ERR_NUMERIC, "exact filter: cannot extend the Krylov basis"};
+        int r = 0;  // D ascending
+        while (r < b && D[b - 1 - r] > 0.0 && D[b - 1 - r] >= 1e-12 * D[b - 1] && D[b - 1 - r] >= 1e-20 * w2) ++r;
+        for (int k = 0; k < r; ++k) {
+            const double s = 1.0 / std::sqrt(D[b - 1 - k]);
+            for (int i = 0; i < b; ++i) B[(size_t)k * b + i] = s * U[(size_t)(b - 1 - k) * b + i];
+        }
+        sv.ms_host += now_ms() - h0;
+        if (r == 0) return fresh(at);
+        sv.gemm(Q.p + at, ldq, b, B, b, Tb.p, b);
+        HIP_OK(nlek::exact_axpby(c->stream, Tb.p, b, 1.0, nullptr, 0, 0.0, Q.p + at, ldq, N, b, b));
+        for (int tries = 0; tries < 3; ++tries) {
+            if (r < b) HIP_OK(nlek::exact_start(c->stream, Q.p, N, ldq, at + r, b - r, seed++));
+            if (sv.orth(Q.p, ldq, at, b, Tb.p, nullptr)) return;
+        }
+        fresh(at);
+    }
     // one block step: Ws of the unmultiplied columns, then the next block
     void extend() {
         if (sv.products >= kExactMaxBlockProducts)
@@ -252,13 +289,14 @@ struct ExactLanczos {
         // the next block: Ws of this one against the basis; the first CGS pass's coefficients are T's new columns
         HIP_OK(nlek::exact_axpby(c->stream, AQ.p + m, ldq, 1.0, nullptr, 0, 0.0, Q.p + qn, ldq, N, b, b));
         std::vector<double> C1;
-        const bool ok = sv.orth(Q.p, ldq, qn, b, Tb.p, &C1);
+        double w2 = 0.0;
+        const bool ok = sv.orth(Q.p, ldq, qn, b, Tb.p, &C1, &w2);
         for (int j = 0; j < b; ++j)
             for (int i = 0; i < qn; ++i) {
                 Tm[(size_t)(m + j) * ldq + i] = C1[(size_t)j * qn + i];
                 Tm[(size_t)i * ldq + m + j] = C1[(size_t)j * qn + i];
             }
-        if (!ok) fresh(qn);
+        if (!ok) deflate(qn, w2);
         m = qn;
         qn = m + b;
     }
