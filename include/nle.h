@@ -776,6 +776,53 @@ int nle_bilateral8(nle_ctx* ctx, const float* d_src, int H, int W, double sigma_
  * the circle and h_colour_w 256 floats when both are non-NULL */
 int nle_bilateral_tables(double sigma_color, double sigma_space, int* radius, float* h_space_w, float* h_colour_w);
 
+/* ---- MSE-guided denoise (new in this build: the reference's denoise stops short of Talebi & Milanfar, "Global Image
+ * Denoising", IEEE TIP 23(2), 2014, which it set out to implement; this text and DESIGN.md section 3.16 are the definition) ---- */
+/* nle_nlm8: non-local means on a single-channel 8-bit plane, the pre-filter of that method.  Planes are fp32 holding integers
+ * 0..255, H x W.  P = patch_radius in [1, NLE_NLM_PATCH_RADIUS_MAX], S = search_radius in [1, NLE_NLM_SEARCH_RADIUS_MAX],
+ * n = (2P + 1)^2, rho = reflect-101 (BORDER_REFLECT_101) applied to every coordinate the patch and search windows touch:
+ *   SSD(p, q) = sum_{delta in [-P, P]^2} (u(rho(p + delta)) - u(rho(q + delta)))^2     (an exact integer, <= 49 255^2 < 2^24)
+ *   Tf = (float)(2 sigma^2 n),  cf = (float)(1 / (n h^2))                              (fp64 on the host, rounded once)
+ *   w(p, q) = exp(-max((float)SSD - Tf, 0) cf)   in fp32, for every q in the (2S + 1)^2 window around p; w(p, p) = 1
+ *   raw(p) = sum_q w u(rho(q)) / sum_q w        fp32 sums, row by row of the window and then over the rows, a fixed order
+ *   dst(p) = rintf(raw(p))                       an integer plane again: a train takes it on the table path
+ * d_raw (may be NULL) receives raw.  The weight sum is >= 1, no division can fail.  sigma >= 0 is the noise level the
+ * threshold 2 sigma^2 per pixel forgives, h > 0 the filtering strength; both finite, and so must Tf and cf be.
+ * NLE_ERR_INVALID with a message, nothing enqueued and the ctx left usable: a parameter out of range, a NULL d_src or d_dst,
+ * d_dst or d_raw aliasing d_src (or each other), a plane that is not integer valued in [0, 255], H or W < 1. */
+#define NLE_NLM_PATCH_RADIUS_MAX 3
+#define NLE_NLM_SEARCH_RADIUS_MAX 10
+int nle_nlm8(nle_ctx* ctx, const float* d_src, int H, int W, int patch_radius, int search_radius, double sigma, double h,
+             float* d_dst, float* d_raw);
+/* nle_plane_noise: Immerkaer's noise estimate of an 8-bit plane (fp32 holding integers 0..255), H, W >= 3.  With the mask
+ * M = [1 -2 1; -2 4 -2; 1 -2 1]:  S = sum over the (H - 2)(W - 2) interior pixels of |(x * M)(i, j)| -- every term an integer
+ * <= 2040, summed in 64-bit integers (per-block partials, a second kernel adds them in a fixed order, no atomics): exact and
+ * bitwise reproducible -- and sigma = sqrt(pi / 2) S / (6 (H - 2)(W - 2)), fp64 on the host.  *h_abs_sum = S (may be NULL),
+ * *h_sigma = sigma.  The mask removes what is locally linear, not texture: texture counts as noise, so this is an UPPER
+ * estimate -- the safe side for a denoiser.  NLE_ERR_INVALID as above for H or W < 3, NULL d_x or h_sigma and a plane that is
+ * not integer valued in [0, 255]. */
+int nle_plane_noise(nle_ctx* ctx, const float* d_x, int H, int W, long long* h_abs_sum, double* h_sigma);
+/* nle_filter_coefficients: t = V^T x of P planes (plane m at d_x + m x_stride, a full H x W fp32 plane as nle_apply takes it;
+ * 1 <= P <= NLE_PLANES_MAX): h_t is P x K' fp64, row-major.  For every formulation nle_apply works for, row m holds bit for bit
+ * the K'-vector nle_apply on that plane forms internally (the table path: the reduce half, the sample rows' term and, where
+ * apply takes them, training's own reduce half; the materialised forms and the exact filter: their row pass) -- so P planes
+ * in one call equal P calls.  On the table path with level-sorted rows the planes share the reduce pass as in
+ * nle_apply_planes.  NLE_ERR_INVALID with a message, nothing enqueued: P out of range, a NULL pointer, a stride smaller than
+ * the plane when P > 1, H W that is not the filter's, and world > 1 (a sharded ctx: not built, refused before any collective). */
+int nle_filter_coefficients(nle_filter* f, const float* d_x, int P, long long x_stride, int H, int W, double* h_t);
+/* nle_mse_shrink (host only, no ctx): the power k of the shrinkage mu^k that minimises the estimated mean squared error when
+ * the coefficients h_b (K values; those of a pre-filtered plane stand in for the clean signal's) meet noise of level sigma:
+ *   mu_j = min(max(lambda_j, 0), 1);   k_i = k_max i / n_grid,  i = 0 .. n_grid
+ *   MSE_i = sum_j [(1 - mu_j^k_i)^2 b_j^2 + sigma^2 mu_j^(2 k_i)]      fp64, std::pow (pow(0, 0) = 1), summed in index order
+ * *h_k = k_i of the smallest i that attains the minimum; h_mse (n_grid + 1 values, may be NULL) receives every MSE_i.  k = 0
+ * leaves the span untouched, a large k keeps only the modes with lambda = 1.  NLE_ERR_INVALID: K < 1, n_grid < 1 or > 65536,
+ * sigma or k_max negative or not finite, NULL h_eigvals, h_b or h_k. */
+int nle_mse_shrink(const double* h_eigvals, const double* h_b, int K, double sigma, double k_max, int n_grid, double* h_k,
+                   double* h_mse);
+/* the pre-filters of the denoise wrapper (nle::DenoiseOptions, `denoise --prefilter`) */
+#define NLE_PREFILTER_BILATERAL 0
+#define NLE_PREFILTER_NLM 1
+
 /* leading dimension used for a logical width n: (n + 3) & ~3 */
 int nle_ld(int n);
 
@@ -794,7 +841,10 @@ enum {
     NLE_K_SINK_TABLES = 9,   /* table pass: per-row g tables (k_hist_g)                  */
     NLE_K_GRAM_ROWS = 10,    /* table Gram: per-row histograms (k_ghist_rows)            */
     NLE_K_GRAM_GEMM = 11,    /* table Gram: fp64 MFMA GEMM (k_ghist_gemm)                */
-    NLE_KERNEL_COUNT = 12
+    NLE_KERNEL_COUNT = 12,   /* the ids of the train / apply path end here (kept: callers size their tables by it) */
+    NLE_K_NLM8 = 12,         /* non-local-means pre-filter (k_nlm8)                      */
+    NLE_K_PLANE_NOISE = 13,  /* Immerkaer noise sum: per-block partials + their fold     */
+    NLE_KERNEL_COUNT_ALL = 14 /* every id nle_kernel_name and nle_ctx_kernel_stats take  */
 };
 const char* nle_kernel_name(int kid);
 /* enable != 0: bracket kernel launches of the ctx with HIP events recorded on the ctx's stream and

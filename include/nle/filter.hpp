@@ -175,6 +175,33 @@ struct DetailOptions {
     bool active() const { return !(residualWeight == 0 && (sigma == 0 || gain == 1)); }
 };
 
+// the options of NLEFilter::trainForDenoise / denoise for the MSE-guided denoiser (new here; DESIGN.md section 3.16, the
+// arithmetic is stated in nle.h at nle_nlm8).  The two choices are independent; the defaults are the reference's flow.
+//   prefilter   NLE_PREFILTER_BILATERAL (0): cv::bilateralFilter as the reference calls it; NLE_PREFILTER_NLM (1): wherever
+//               that flow calls the bilateral filter -- the plane the filter is trained on, the L that replaces the image's --
+//               nle_nlm8 runs instead, with sigma = noiseSigma or nle_plane_noise of the plane being filtered and P, S, h from
+//               the table for grey images of Buades, Coll & Morel, "Non-Local Means Denoising", IPOL 2011, cut to the kernel's
+//               limits: sigma <= 15: P 1, S 10, h 0.40 sigma; <= 30: P 2, S 10, h 0.40 sigma; above: P 3, S 10, h 0.35 sigma
+//               (taken from the literature, not tuned here).  nlmH > 0 replaces h; h == 0 (sigma == 0): the plane is copied.
+//               sigmaColor and sigmaSpace are then unused.
+//   glide       denoise shrinks every plane, L included, by mu^k with k chosen per plane by nle_mse_shrink: sigma per plane
+//               (given or estimated), all three noisy planes pre-filtered, the coefficients V^T of the pre-filtered planes
+//               standing in for the clean signal's, k searched on [0, the call's shrink factor] in 256 steps; then the filter
+//               runs on the NOISY planes.  Needs a filter trained by trainForDenoise.
+//   noiseSigma  >= 0: the noise level of every plane; < 0: estimated per plane (an upper estimate, see nle_plane_noise)
+// One device (a filter trained on a device group throws); 8-bit images only.
+struct DenoiseOptions {
+    int prefilter = 0;  // NLE_PREFILTER_BILATERAL
+    bool glide = false;
+    double noiseSigma = -1;
+    double nlmH = 0;
+};
+// what the last denoise with DenoiseOptions::glide chose for L, a and b: the noise level used, the power k and MSE(k)
+struct DenoiseReport {
+    double sigma[3] = {0, 0, 0}, k[3] = {0, 0, 0}, mse[3] = {0, 0, 0};
+    bool valid = false;
+};
+
 // include/filter.hpp:35-54.  The trained state (m_eigvecs N x K', m_eigvals) lives on the GPU.
 class NLEFilter {
 public:
@@ -228,6 +255,11 @@ public:
     void trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,
                          int nEigenVectors, int sigmaColor = 10, int sigmaSpace = 10);
     Image denoise(const Image& I, DType k, int sigmaColor = 10, int sigmaSpace = 10) const;
+    // the same with DenoiseOptions (new here, see there); default options are the two methods above, byte for byte
+    void trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,
+                         int nEigenVectors, int sigmaColor, int sigmaSpace, const DenoiseOptions& options);
+    Image denoise(const Image& I, DType k, int sigmaColor, int sigmaSpace, const DenoiseOptions& options) const;
+    DenoiseReport lastDenoiseReport() const { return denoiseReport_; }
 
     // private in the reference (include/filter.hpp:47-50); public here so tests and other hosts can
     // drive the hot path on a luminance plane directly
@@ -290,6 +322,8 @@ private:
     std::shared_ptr<nle_filter> fh_;  // nle_filter_destroy when the last copy goes
     nle_filter* f_ = nullptr;         // == fh_.get()
     int rows_ = 0, cols_ = 0;
+    bool denoiseTrained_ = false;            // the filter in hand came from trainForDenoise (what glide needs)
+    mutable DenoiseReport denoiseReport_;    // denoise with DenoiseOptions::glide
     double hdrHi_ = 0, hdrRange_ = 0;  // trainForToneMapping: log2 of the largest luminance and the range in stops (0: none)
     // NLE_DEVICES=<dev>,<dev>,...: trainForEnhancement / enhance shard the image by row slabs over one context (and
     // one host thread per call) per listed device; rank r's filter is group_[r] and f_ == group_[0].get()

@@ -44,6 +44,11 @@ REGION_OUT_F32, REGION_OUT_ROUNDED8, REGION_OUT_U8 = (_abi.NLE_REGION_OUT_F32, _
 DETAIL_GAIN_MAX = _abi.NLE_DETAIL_GAIN_MAX  # nle_detail_combine / nle_apply_detail: the gain lies in [0, DETAIL_GAIN_MAX]
 PLANES_MAX = _abi.NLE_PLANES_MAX  # nle_apply_planes: planes per call (its output kinds are REGION_OUT_F32 / _ROUNDED8)
 RESID_AUTO, RESID_ROWS, RESID_FUSED = _abi.NLE_RESID_AUTO, _abi.NLE_RESID_ROWS, _abi.NLE_RESID_FUSED  # nle_nystrom_residual
+# the MSE-guided denoiser: nle_nlm8's limits, the pre-filters of the denoise wrapper, every timed kernel id (KERNEL_COUNT
+# stays the count of the train / apply path's ids)
+NLM_PATCH_RADIUS_MAX, NLM_SEARCH_RADIUS_MAX = _abi.NLE_NLM_PATCH_RADIUS_MAX, _abi.NLE_NLM_SEARCH_RADIUS_MAX
+PREFILTER_BILATERAL, PREFILTER_NLM = _abi.NLE_PREFILTER_BILATERAL, _abi.NLE_PREFILTER_NLM
+KERNEL_COUNT_ALL = _abi.NLE_KERNEL_COUNT_ALL
 
 _lib = None
 
@@ -243,6 +248,22 @@ def layer_responses(eigvals, n_layers):
 
 
 # ------------------------------------------------------------------ device side
+def mse_shrink(eigvals, b, sigma, k_max, n_grid=256):
+    """nle_mse_shrink (host only): (k, mse) -- the power k on the grid k_max i / n_grid that minimises the estimated MSE of the
+    shrinkage min(max(lambda, 0), 1)^k for coefficients b under noise sigma, and the n_grid + 1 MSE values"""
+    ev = np.ascontiguousarray(eigvals, dtype=np.float64).ravel()
+    bb = np.ascontiguousarray(b, dtype=np.float64).ravel()
+    if bb.size != ev.size:
+        raise NLEError(NLE_ERR_INVALID, f"one coefficient per eigenvalue expected: {ev.size} eigenvalues, {bb.size} coefficients")
+    n_grid = int(n_grid)
+    mse = np.zeros(max(n_grid, 0) + 1)
+    k = C.c_double(0.0)
+    st = lib().nle_mse_shrink(_np_ptr(ev), _np_ptr(bb), ev.size, float(sigma), float(k_max), n_grid, C.byref(k), _np_ptr(mse))
+    if st != NLE_OK:
+        raise NLEError(st, "nle_mse_shrink: K >= 1, 1 <= n_grid <= 65536, sigma and k_max finite and >= 0 expected")
+    return k.value, mse
+
+
 def _torch():
     import torch
     return torch
@@ -500,7 +521,7 @@ class Context:
     def kernel_stats(self):
         """{kernel name: (launches, total_ms)} accumulated since `profile(True)`."""
         out = {}
-        for kid in range(KERNEL_COUNT):
+        for kid in range(KERNEL_COUNT_ALL):
             n, ms = C.c_longlong(), C.c_double()
             _check(lib().nle_ctx_kernel_stats(self._h, kid, C.byref(n), C.byref(ms)), self._h)
             out[lib().nle_kernel_name(kid).decode()] = (n.value, ms.value)
@@ -1025,6 +1046,25 @@ class Context:
                                     C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    def nlm8(self, plane, patch_radius, search_radius, sigma, h, want_raw=False):
+        """nle_nlm8 on an integer-valued float32 plane: the rounded plane, or (rounded, raw) with want_raw"""
+        torch = _torch()
+        src = self._lum(plane)
+        H, W = src.shape
+        out = torch.empty_like(src)
+        raw = torch.empty_like(src) if want_raw else None
+        _check(lib().nle_nlm8(self._h, C.c_void_p(src.data_ptr()), H, W, int(patch_radius), int(search_radius), float(sigma),
+                              float(h), C.c_void_p(out.data_ptr()), C.c_void_p(raw.data_ptr()) if want_raw else None), self._h)
+        return (out, raw) if want_raw else out
+
+    def plane_noise(self, plane):
+        """nle_plane_noise on an integer-valued float32 plane: (S, sigma) -- Immerkaer's absolute sum (exact) and estimate"""
+        src = self._lum(plane)
+        H, W = src.shape
+        S, sigma = C.c_longlong(0), C.c_double(0.0)
+        _check(lib().nle_plane_noise(self._h, C.c_void_p(src.data_ptr()), H, W, C.byref(S), C.byref(sigma)), self._h)
+        return S.value, sigma.value
+
     def region_combine(self, layers, q, weights, floor=0.05, out_kind=0, out=None):
         """nle_region_combine, the rule alone: layers (L, n) and q (M, n) float32 device tensors whose rows are contiguous
         and may lie any stride >= n apart (a view into a larger buffer, at any offset, is taken as it is); weights
@@ -1352,6 +1392,24 @@ class NLEFilter:
         _check(lib().nle_apply_planes(self._f, C.c_void_p(t.data_ptr()), P, t.stride(0) if P > 1 else H * W, H, W,
                                       _np_ptr(nresp), _np_ptr(resp), int(out_kind), C.c_void_p(out.data_ptr()),
                                       out.stride(0) if R > 1 else n), self.ctx._h)
+        return out
+
+    def coefficients(self, planes):
+        """nle_filter_coefficients: t = V^T x of P planes (P x H x W float32, or one H x W plane) as a (P, K') float64 array,
+        row m bit for bit the vector `apply` forms for plane m"""
+        torch = _torch()
+        t = torch.as_tensor(planes, dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        if t.ndim == 2:
+            t = t[None]
+        if t.ndim != 3:
+            raise NLEError(NLE_ERR_INVALID, "planes must be P x H x W")
+        P, H, W = t.shape
+        if t.stride(2) != 1 or t.stride(1) != W or (P > 1 and t.stride(0) < H * W):
+            t = t.contiguous()
+        self.ctx._sync_in()
+        out = np.zeros((max(P, 1), self.info()["K"]))
+        _check(lib().nle_filter_coefficients(self._f, C.c_void_p(t.data_ptr()), P, t.stride(0) if P > 1 else H * W, H, W,
+                                             _np_ptr(out)), self.ctx._h)
         return out
 
     def _strokes(self, strokes):

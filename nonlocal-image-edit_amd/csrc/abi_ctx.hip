@@ -598,12 +598,12 @@ int nle_transform_eigenvalues(const double* h_eigvals, int K, const double* h_we
     return NLE_OK;
 }
 
-static const char* const kKernelNames[NLE_KERNEL_COUNT] = {
+static const char* const kKernelNames[NLE_KERNEL_COUNT_ALL] = {
     "affinity", "nystrom_extend", "sinkhorn_pass", "reduce_partials", "gram",
     "project",  "apply_reduce",   "apply_expand",  "small",           "sink_tables", "gram_rows",
-    "gram_gemm"};
+    "gram_gemm", "nlm8", "plane_noise"};
 
-const char* nle_kernel_name(int kid) { return (kid >= 0 && kid < NLE_KERNEL_COUNT) ? kKernelNames[kid] : ""; }
+const char* nle_kernel_name(int kid) { return (kid >= 0 && kid < NLE_KERNEL_COUNT_ALL) ? kKernelNames[kid] : ""; }
 
 int nle_ctx_profile(nle_ctx* ctx, int enable) {
     if (!ctx) return NLE_ERR_INVALID;
@@ -612,7 +612,7 @@ int nle_ctx_profile(nle_ctx* ctx, int enable) {
         prof_flush(ctx);
         ctx->profiling = enable != 0;
         ctx->profile_all = enable >= 2;
-        for (int k = 0; k < NLE_KERNEL_COUNT; ++k) {
+        for (int k = 0; k < NLE_KERNEL_COUNT_ALL; ++k) {
             ctx->prof_launches[k] = 0;
             ctx->prof_ms[k] = 0.0;
         }
@@ -620,7 +620,7 @@ int nle_ctx_profile(nle_ctx* ctx, int enable) {
 }
 
 int nle_ctx_kernel_stats(nle_ctx* ctx, int kid, long long* launches, double* total_ms) {
-    if (!ctx || kid < 0 || kid >= NLE_KERNEL_COUNT) return NLE_ERR_INVALID;
+    if (!ctx || kid < 0 || kid >= NLE_KERNEL_COUNT_ALL) return NLE_ERR_INVALID;
     return guard(ctx, [&] {
         HIP_OK(hipStreamSynchronize(ctx->stream));
         prof_flush(ctx);

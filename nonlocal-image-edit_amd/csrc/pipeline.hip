@@ -290,6 +290,33 @@ void apply_planes_impl(nle_filter* f, const float* const* d_x, int P, int H, int
     }
 }
 
+// t = V^T x on a materialised V (fp32 or fp64): apply_dense's row pass and fold, the first K of the ld sums handed out
+template <typename T>
+void coefficients_dense(nle_filter* f, const T* d_V, const float* d_x, double* h_t) {
+    nle_ctx* c = f->ctx;
+    const int ld = f->ldv;
+    const long long M = f->n_local;
+    DevBuf<double> d_partial((size_t)nlek::kRowpassMaxBlocks * ld), d_t(ld);
+    int nb = 0;
+    PROFILED(c, NLE_K_APPLY_REDUCE, rowpass_any(c->stream, nlek::ROWPASS_XVEC, d_V, M, ld, ld, nullptr, nullptr, d_x, NLE_EPS,
+                                                d_partial.p, &nb));
+    PROFILED(c, NLE_K_REDUCE, nlek::reduce_partials(c->stream, d_partial.p, nb, ld, d_t.p));
+    HIP_OK(hipMemcpyAsync(h_t, d_t.p, (size_t)f->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    prof_flush(c);
+}
+
+// nle_filter_coefficients on one device: the t of apply_impl, formulation by formulation
+void coefficients_impl(nle_filter* f, const float* const* d_x, int P, double* h_t) {
+    HIP_OK(hipSetDevice(f->ctx->device));
+    if (f->tables) return coefficients_sample_space(f, d_x, P, h_t);
+    if (!f->V64.p) ensure_V(f);
+    for (int m = 0; m < P; ++m) {
+        if (f->V64.p) coefficients_dense(f, f->V64.p, d_x[m], h_t + (size_t)m * f->K);
+        else coefficients_dense(f, f->V.p, d_x[m], h_t + (size_t)m * f->K);
+    }
+}
+
 void layer_resp(const double* ev, int K, int L, double* out) {
     // detail layer j <-> lambda^j - lambda^(j+1); base <-> lambda^(L-1)  (reference :334-347)
     for (int j = 0; j < L; ++j)
@@ -810,6 +837,25 @@ int nle_region_spread(nle_filter* f, const float* d_strokes, int M, int H, int W
         if (!d_strokes || !d_q) throw Fail{NLE_ERR_INVALID, "nle_region_spread: NULL pointer"};
         region_check_spread(f, M, H, W, h_scale, spread);
         region_spread_impl(f, d_strokes, M, H, W, h_scale, spread, d_q);
+    });
+}
+
+int nle_filter_coefficients(nle_filter* f, const float* d_x, int P, long long x_stride, int H, int W, double* h_t) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        if (f->ctx->world > 1)
+            throw Fail{NLE_ERR_INVALID, "nle_filter_coefficients runs on one device: a sharded ctx (world > 1) is not built"};
+        if (P < 1 || P > NLE_PLANES_MAX)
+            throw Fail{NLE_ERR_INVALID, "nle_filter_coefficients takes 1 to " + std::to_string(NLE_PLANES_MAX) + " planes, got " +
+                                            std::to_string(P)};
+        if (!d_x || !h_t) throw Fail{NLE_ERR_INVALID, "nle_filter_coefficients: NULL pointer"};
+        if (H < 1 || W < 1 || (long long)H * W != (long long)f->H * f->W)  // reference src/filter.cpp:447-449
+            throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+        if (P > 1 && x_stride < (long long)H * W)
+            throw Fail{NLE_ERR_INVALID, "nle_filter_coefficients: the plane stride is smaller than the plane"};
+        const float* planes[NLE_PLANES_MAX];
+        for (int m = 0; m < P; ++m) planes[m] = d_x + (size_t)m * (size_t)(P > 1 ? x_stride : 0);
+        coefficients_impl(f, planes, P, h_t);
     });
 }
 

@@ -87,8 +87,8 @@ struct nle_ctx {
     };
     std::vector<ProfRec> prof_pending;
     std::vector<hipEvent_t> prof_pool;
-    long long prof_launches[NLE_KERNEL_COUNT] = {0};
-    double prof_ms[NLE_KERNEL_COUNT] = {0};
+    long long prof_launches[NLE_KERNEL_COUNT_ALL] = {0};
+    double prof_ms[NLE_KERNEL_COUNT_ALL] = {0};
 };
 
 namespace nlep {

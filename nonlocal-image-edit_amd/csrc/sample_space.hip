@@ -560,6 +560,50 @@ void apply_sample_space_planes(nle_filter* f, const float* const* d_x, int P, co
     prof_flush(c);
 }
 
+// t = V^T x of P planes on a table filter (nle_filter_coefficients): the reduce half and the p-sized middle exactly as the
+// two applies above run them -- one plane, or a filter without level-sorted rows: apply_sample_space's, training's own
+// reduce half included where that apply takes it; several planes on sorted rows: apply_sample_space_planes' groups -- with
+// one response of ones, whose W' and YA are dropped: what k_apply_small writes to t_out is the vector handed out.  world == 1.
+void coefficients_sample_space(nle_filter* f, const float* const* d_x, int P, double* h_t) {
+    nle_ctx* c = f->ctx;
+    const TableFilter& t = *f->tables;
+    const nlek::TableView view = t.view();
+    const int p = t.p, K = f->K, P64 = t.P64;
+    const bool batched = P > 1 && t.sorted_rows() != nullptr;
+    const int NP = batched ? std::min(P, nlek::sorted_planes_per_launch(t.gs)) : 1;
+    DevBuf<double> d_ws(batched ? nlek::apply_reduce_planes_workspace_elems(t.gs, t.nrows, NP)
+                                : nlek::hist_tiled_workspace_elems(t.gs, t.nrows)),
+        d_m((size_t)NP * P64), d_resp(K), d_t((size_t)P * K), d_xA(p), d_Wp(P64), d_YA(p);
+    const std::vector<double> ones((size_t)K, 1.0);
+    HIP_OK(hipMemcpyAsync(d_resp.p, ones.data(), (size_t)K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    DevBuf<int> d_differs;
+    const bool reuse = !batched && t.m_train.p && !c->comm && c->train_reduce;
+    if (reuse) d_differs.alloc(1);
+    for (int m0 = 0; m0 < P; m0 += NP) {
+        const int np = std::min(NP, P - m0);
+        if (reuse) {
+            HIP_OK(hipMemsetAsync(d_differs.p, 0, sizeof(int), c->stream));
+            PROFILED(c, NLE_K_SMALL, nlek::plane_matches_levels(c->stream, d_x[m0] + (long long)t.row0 * t.gs.W, t.lev.p,
+                                                                (long long)t.nrows * t.gs.W, d_differs.p));
+        }
+        {
+            ProfObserver obs(c, kProfTableReduce);
+            if (np > 1) HIP_OK(nlek::apply_reduce_planes(c->stream, view, d_x + m0, np, d_ws.p, d_m.p, &obs));
+            else HIP_OK(nlek::sink_hist_tiled(c->stream, nlek::ROWPASS_XVEC, view, nullptr, NLE_EPS, nullptr, d_ws.p, d_m.p, &obs,
+                                              d_x[m0], d_differs.p));
+        }
+        for (int m = m0; m < m0 + np; ++m) {
+            PROFILED(c, NLE_K_SMALL, nlek::gather_samples_slab(c->stream, d_x[m], t.gs, 0, f->H, d_xA.p, d_differs.p));
+            PROFILED(c, NLE_K_SMALL, nlek::apply_small(c->stream, p, K, t.ldd, 1, P64, d_m.p + (size_t)(m - m0) * P64, t.D.p,
+                                                       t.Vrows.p, d_xA.p, d_resp.p, d_t.p + (size_t)m * K, d_Wp.p, d_YA.p,
+                                                       d_differs.p, t.m_train.p, t.xA_train.p));
+        }
+    }
+    HIP_OK(hipMemcpyAsync(h_t, d_t.p, (size_t)P * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    prof_flush(c);
+}
+
 }  // namespace nlep
 
 extern "C" int nle_filter_level_tiles(const nle_filter* f, int* first_tile, int* n_tiles) {

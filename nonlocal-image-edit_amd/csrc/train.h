@@ -109,6 +109,9 @@ void apply_sample_space(nle_filter* f, const float* d_x, const double* h_g /* L 
 // what apply_sample_space writes for its plane alone.
 void apply_sample_space_planes(nle_filter* f, const float* const* d_x, int P, const int* nresp, const double* h_g, int R,
                                float* d_y, long long ystride, bool round8);
+// t = V^T x of P planes on a table filter, world == 1: h_t P x K, row m the bits the applies above form for plane m
+// (nle_filter_coefficients)
+void coefficients_sample_space(nle_filter* f, const float* const* d_x, int P, double* h_t);
 // exact_train.hip
 nle_filter* train_exact_impl(nle_ctx* c, const float* d_lum, int H, int W, double hx, double hy, int T, int n_eig);
 

@@ -18,7 +18,9 @@
 // and the result is a 16-bit PNG (not with --chroma, --region, --deep or --nystrom-report); and `--residual-weight WR` (a
 // finite number), `--detail-gain A` (finite, in [0, NLE_DETAIL_GAIN_MAX]) and `--detail-sigma S` (finite, >= 0):
 // nle::DetailOptions of NLEFilter::enhance / toneMap, with --deep and --tonemap too (a gain other than 1 needs a sigma > 0;
-// not with --region).
+// not with --region).  For denoise only, the MSE-guided denoiser (nle::DenoiseOptions): `--prefilter bilateral|nlm`, the flag
+// `--glide` (no value), `--noise-sigma S` (finite, >= 0; needs --glide or --prefilter nlm) and `--nlm-h H` (finite, > 0; needs
+// --prefilter nlm); under --glide the positional shrink factor is the upper end of the searched range.
 #pragma once
 
 #include <cctype>
@@ -55,6 +57,7 @@ struct FilterArgs {
     bool tonemap = false;            // --tonemap (enhance only): Radiance / PFM in, 16-bit PNG out
     double tonemapSaturation = 1;    // --tonemap-saturation S (with --tonemap)
     nle::DetailOptions detail;       // --residual-weight WR, --detail-gain A, --detail-sigma S (enhance only)
+    nle::DenoiseOptions denoise;     // --prefilter bilateral|nlm, --glide, --noise-sigma S, --nlm-h H (denoise only)
     bool nystromReport = false;  // --nystrom-report (enhance only)
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
@@ -77,13 +80,15 @@ inline double positive_option(const char* prog, const std::string& opt, const st
 // allow_deep: the tool takes `--deep` (enhance); otherwise it is refused (denoise has no 16-bit path)
 // allow_tonemap: the tool takes `--tonemap` / `--tonemap-saturation S` (enhance); otherwise they are refused
 // allow_detail: the tool takes `--residual-weight WR` / `--detail-gain A` / `--detail-sigma S` (enhance); otherwise refused
+// allow_denoise: the tool takes `--prefilter` / `--glide` / `--noise-sigma` / `--nlm-h` (denoise); otherwise they are refused
 inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false,
                   bool allow_regions = false, bool allow_nystrom = false, bool allow_deep = false,
-                  bool allow_tonemap = false, bool allow_detail = false) {
+                  bool allow_tonemap = false, bool allow_detail = false, bool allow_denoise = false) {
     std::vector<char*> shifted;
     int first = 1;  // the first argument after the leading options
     bool spreadGiven = false, floorGiven = false, saturationGiven = false;
     std::string detailGiven;  // the last of --residual-weight / --detail-gain / --detail-sigma seen
+    bool noiseSigmaGiven = false, nlmHGiven = false;
     while (first < argc) {
         const std::string opt = argv[first];
         if (opt == "--exact") {
@@ -190,6 +195,44 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
             first += 2;
             continue;
         }
+        if (opt == "--glide" || opt.rfind("--glide=", 0) == 0 || opt == "--prefilter" || opt == "--noise-sigma" || opt == "--nlm-h") {
+            if (!allow_denoise) {
+                std::cerr << argv[0] << ": " << opt << " is not supported here: the pre-filter and the MSE-guided shrinkage belong "
+                          << "to denoise" << std::endl;
+                std::exit(2);
+            }
+            if (opt.rfind("--glide", 0) == 0) {
+                if (opt != "--glide") {
+                    std::cerr << argv[0] << ": --glide takes no value, got '" << opt << "'" << std::endl;
+                    std::exit(2);
+                }
+                a->denoise.glide = true;
+                first += 1;
+                continue;
+            }
+            const std::string v = first + 1 < argc ? argv[first + 1] : "";
+            if (opt == "--prefilter") {
+                if (v != "bilateral" && v != "nlm") {
+                    std::cerr << argv[0] << ": --prefilter takes 'bilateral' or 'nlm', got '" << v << "'" << std::endl;
+                    std::exit(2);
+                }
+                a->denoise.prefilter = v == "nlm" ? NLE_PREFILTER_NLM : NLE_PREFILTER_BILATERAL;
+            } else if (opt == "--noise-sigma") {
+                char* end = nullptr;
+                const double x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+                if (v.empty() || *end != '\0' || !std::isfinite(x) || x < 0) {
+                    std::cerr << argv[0] << ": --noise-sigma takes a finite number >= 0, got '" << v << "'" << std::endl;
+                    std::exit(2);
+                }
+                a->denoise.noiseSigma = x;
+                noiseSigmaGiven = true;
+            } else {
+                a->denoise.nlmH = positive_option(argv[0], opt, v);
+                nlmHGiven = true;
+            }
+            first += 2;
+            continue;
+        }
         const bool regionOpt = opt == "--region" || opt == "--region-spread" || opt == "--region-floor";
         if (opt != "--patch-radius" && opt != "--sampler" && opt != "--chroma" && !regionOpt) break;
         const std::string v = first + 1 < argc ? argv[first + 1] : "";
@@ -265,6 +308,14 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
             a->sampler = v == "grid" ? NLE_SAMPLER_GRID : v == "farthest" ? NLE_SAMPLER_FARTHEST : NLE_SAMPLER_RESIDUAL;
         }
         first += 2;
+    }
+    if (noiseSigmaGiven && !a->denoise.glide && a->denoise.prefilter != NLE_PREFILTER_NLM) {
+        std::cerr << argv[0] << ": --noise-sigma needs --glide or --prefilter nlm (nothing else uses a noise level)" << std::endl;
+        std::exit(2);
+    }
+    if (nlmHGiven && a->denoise.prefilter != NLE_PREFILTER_NLM) {
+        std::cerr << argv[0] << ": --nlm-h needs --prefilter nlm" << std::endl;
+        std::exit(2);
     }
     if (a->exact && (a->patchRadius != 0 || a->sampler != NLE_SAMPLER_GRID)) {
         std::cerr << argv[0] << ": --exact uses no samples and single-pixel affinities: it does not combine with "
@@ -390,7 +441,17 @@ inline void report(const nle::NLEFilter& filter) {
        << ", \"eigvals\": [";
     for (int i = 0; i < ev.size(); ++i) os << (i ? ", " : "") << ev(i);
     os << "], \"ms\": {\"samples\": " << ms[0] << ", \"sinkhorn\": " << ms[1] << ", \"gram\": " << ms[2]
-       << ", \"project\": " << ms[3] << ", \"host\": " << ms[4] << ", \"train_total\": " << ms[5] << "}}" << std::endl;
+       << ", \"project\": " << ms[3] << ", \"host\": " << ms[4] << ", \"train_total\": " << ms[5] << "}";
+    const nle::DenoiseReport g = filter.lastDenoiseReport();  // denoise --glide: (sigma, k, MSE(k)) of L, a and b
+    if (g.valid) {
+        os << ", \"glide\": {";
+        const char* names[3] = {"L", "a", "b"};
+        for (int ch = 0; ch < 3; ++ch)
+            os << (ch ? ", " : "") << "\"" << names[ch] << "\": {\"sigma\": " << g.sigma[ch] << ", \"k\": " << g.k[ch]
+               << ", \"mse\": " << g.mse[ch] << "}";
+        os << "}";
+    }
+    os << "}" << std::endl;
 }
 
 // `banner`: the line the reference prints before it writes the file (src/enhance.cpp:45, src/denoise.cpp:45); the

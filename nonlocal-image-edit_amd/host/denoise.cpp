@@ -4,11 +4,14 @@
 // (the reference's usage line still lists four weights -- it was copied from enhance -- and is kept verbatim;
 // sigma color / sigma space are parsed as doubles and truncated to int by the NLEFilter signatures, :28-29,44-46).
 // Differences: headless (no imshow / waitKey, :50-51), BMP/PPM in and BMP/PPM/PNG out through nle/image_io.hpp.
+// New here, as leading options: --prefilter bilateral|nlm, --glide, --noise-sigma S, --nlm-h H (nle::DenoiseOptions;
+// cli_common.hpp).  With --glide the shrink factor is the upper end of the searched range and one more line is printed
+// before the banner: the noise level and the power k chosen for L, a and b.
 #include "cli_common.hpp"
 
 int main(int argc, char* argv[]) {
     nlecli::FilterArgs a;
-    if (!nlecli::parse(argc, argv, 12, &a)) return 0;  // usage: src/denoise.cpp:14-17 (exit code 0 on purpose)
+    if (!nlecli::parse(argc, argv, 12, &a, false, false, false, false, false, false, /*allow_denoise=*/true)) return 0;  // usage: src/denoise.cpp:14-17 (exit code 0 on purpose)
     const int sigmaColor = (int)a.extra[0], sigmaSpace = (int)a.extra[1];
     const double shrinkFactor = a.extra[2];
     const nle::Image image = nlecli::load(a);
@@ -18,8 +21,17 @@ int main(int argc, char* argv[]) {
     filter.sampler = a.sampler;
     filter.exact = a.exact;
     filter.trainForDenoise(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors, sigmaColor,
-                           sigmaSpace);
-    const nle::Image result = filter.denoise(image, shrinkFactor, sigmaColor, sigmaSpace);
+                           sigmaSpace, a.denoise);
+    const nle::Image result = filter.denoise(image, shrinkFactor, sigmaColor, sigmaSpace, a.denoise);
+    if (a.denoise.glide) {
+        const nle::DenoiseReport g = filter.lastDenoiseReport();
+        const char* names[3] = {"L", "a", "b"};
+        std::cout.precision(6);
+        std::cout << "glide:";
+        for (int ch = 0; ch < 3; ++ch)
+            std::cout << (ch ? "  " : " ") << names[ch] << " sigma=" << g.sigma[ch] << " k=" << g.k[ch];
+        std::cout << std::endl;
+    }
     nlecli::report(filter);
     return nlecli::finish(a, result, "Done. Press any key in result window to exit.");  // src/denoise.cpp:45
 }

@@ -128,6 +128,8 @@ void NLEFilter::beginTrain(nle_ctx* c) {
     f_ = nullptr;
     group_.clear();
     hdrHi_ = hdrRange_ = 0;  // trainForToneMapping sets them after its train
+    denoiseTrained_ = false;  // trainForDenoise likewise
+    denoiseReport_ = DenoiseReport();
     if (verbose) {
         // the four stages run as one fused GPU pipeline; the banners keep the reference's stdout (:483-498)
         std::cout << "Computing kernel" << std::endl;
@@ -244,6 +246,20 @@ Image NLEFilter::toneMap(const Image& image, const std::vector<DType>& weights, 
 
 void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
                                 int nSinkhornIter, int nEigenVectors, int sigmaColor, int sigmaSpace) {  // :521-538
+    trainForDenoise(image, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors, sigmaColor, sigmaSpace, DenoiseOptions());
+}
+
+Image NLEFilter::denoise(const Image& image, DType k, int sigmaColor, int sigmaSpace) const {  // :349-410
+    return denoise(image, k, sigmaColor, sigmaSpace, DenoiseOptions());
+}
+
+namespace {
+const char kDenoiseOneDevice[] = "The denoise options (NLM pre-filter, glide) run on one device: unset NLE_DEVICES.";
+bool default_options(const DenoiseOptions& o) { return o.prefilter == NLE_PREFILTER_BILATERAL && !o.glide; }
+}  // namespace
+
+void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,
+                                int nEigenVectors, int sigmaColor, int sigmaSpace, const DenoiseOptions& options) {
     refuse_hdr(image, "trainForDenoise");
     if (is_deep(image)) throw std::runtime_error("Denoise takes an 8-bit image: deep colour (16 bit) is built for enhance only.");
     if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enchance RGB image.");
@@ -251,30 +267,77 @@ void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSam
     if (chromaBandwidth != 0)
         throw std::runtime_error("trainForDenoise does not take chroma affinities (chromaBandwidth must be 0): the a and b "
                                  "planes are what it estimates");
-    // BGR -> Lab, L, bilateral filter (8 bit), convertTo(double), trainFilter -- all on the device
+    if (!default_options(options)) {
+        check_denoise_options(options, sigmaColor, sigmaSpace);
+        if (devices_env() != nullptr && device_group(-1) != nullptr) throw std::runtime_error(kDenoiseOneDevice);
+    }
+    // BGR -> Lab, L, the pre-filter (8 bit: the bilateral filter, or non-local means), convertTo(double), trainFilter -- all on
+    // the device
     nle_ctx* c = shared_ctx();
     const LabPlanes in = lab_planes(c, image.ptr<unsigned char>(), image.total(), false, false);
     Dev d_Y(c, image.total() * 4);
-    check(nle_bilateral8(c, in.L.f(), image.rows, image.cols, sigmaColor, sigmaSpace, d_Y.f()), c);
+    const double sigma = options.prefilter == NLE_PREFILTER_NLM ? plane_sigma(c, options, in.L.f(), image.rows, image.cols) : 0;
+    prefilter_plane(c, options, in.L.f(), image.rows, image.cols, sigmaColor, sigmaSpace, sigma, d_Y.f());
     trainOnDevice(d_Y.f(), image.rows, image.cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors);
+    denoiseTrained_ = true;
 }
 
-Image NLEFilter::denoise(const Image& image, DType k, int sigmaColor, int sigmaSpace) const {  // :349-410
+Image NLEFilter::denoise(const Image& image, DType k, int sigmaColor, int sigmaSpace, const DenoiseOptions& options) const {
     refuse_hdr(image, "denoise");
     if (image.channels() != 3) throw std::runtime_error("Can only enchance RGB image.");  // (sic) :351-353
     if (is_deep(image)) throw std::runtime_error("Denoise takes an 8-bit image: deep colour (16 bit) is built for enhance only.");
     requireSize(image.total(), kTrainedSize);
     if (image.depth() != NLE_8U) throw std::runtime_error("Can only enchance RGB image.");
+    if (!default_options(options)) {
+        check_denoise_options(options, sigmaColor, sigmaSpace);
+        if (!group_.empty()) throw std::runtime_error(kDenoiseOneDevice);
+        if (options.glide && !denoiseTrained_) throw std::runtime_error("denoise with glide needs a filter trained by trainForDenoise.");
+        if (options.glide && (!std::isfinite(k) || k < 0))
+            throw std::runtime_error("denoise with glide searches k on [0, shrink factor]: the shrink factor must be finite and >= 0.");
+    }
     const size_t np = image.total();
+    const int H = image.rows, W = image.cols;
     const LabPlanes in = lab_planes(ctx_, image.ptr<unsigned char>(), np, true, false);
+    Image out(H, W, NLE_8U, 3);
+    const Vec ev = eigvals();
+    const int K = ev.size();
+    if (options.glide) {
+        // L, a and b of the noisy image; their noise levels; all three pre-filtered; the coefficients of the pre-filtered
+        // planes choose k per plane; the filter then runs on the noisy planes, L included
+        Dev d_noisy(ctx_, 3 * np * 4), d_pre(ctx_, 3 * np * 4), d_out(ctx_, 3 * np * 4);
+        DenoiseReport rep;
+        for (int ch = 0; ch < 3; ++ch) {
+            check(nle_lab8_channel(ctx_, in.lab.u8(), (long long)np, ch, d_noisy.f() + (size_t)ch * np), ctx_);
+            rep.sigma[ch] = plane_sigma(ctx_, options, d_noisy.f() + (size_t)ch * np, H, W);
+            prefilter_plane(ctx_, options, d_noisy.f() + (size_t)ch * np, H, W, sigmaColor, sigmaSpace, rep.sigma[ch],
+                            d_pre.f() + (size_t)ch * np);
+        }
+        std::vector<double> b((size_t)3 * K), resp((size_t)3 * K), mse(257);
+        check(nle_filter_coefficients(f_, d_pre.f(), 3, (long long)np, H, W, b.data()), ctx_);
+        for (int ch = 0; ch < 3; ++ch) {
+            if (nle_mse_shrink(ev.data(), b.data() + (size_t)ch * K, K, rep.sigma[ch], k, 256, &rep.k[ch], mse.data()) != NLE_OK)
+                throw std::runtime_error("nle_mse_shrink refused its arguments");
+            rep.mse[ch] = *std::min_element(mse.begin(), mse.end());
+            for (int i = 0; i < K; ++i) resp[(size_t)ch * K + i] = std::pow(std::min(std::max(ev(i), 0.0), 1.0), rep.k[ch]);
+        }
+        if (verbose)
+            for (int i = 0; i < K; ++i) std::cout << "eig " << i << " val: " << std::min(ev(i), 1.0) << std::endl;
+        check(nle_apply_planes(f_, d_noisy.f(), 3, (long long)np, H, W, nullptr, resp.data(), NLE_REGION_OUT_ROUNDED8, d_out.f(),
+                               (long long)np), ctx_);
+        lab_to_rows(ctx_, in, d_out.f(), d_out.f() + np, d_out.f() + 2 * np, out, 0, H);
+        rep.valid = true;
+        denoiseReport_ = rep;
+        return out;
+    }
     Dev d_Y(ctx_, np * 4), d_c(ctx_, np * 8), d_ab(ctx_, np * 8);
-    // the L channel becomes its bilateral-filtered version (:370-373; `apply` on it is commented out, :389)
-    check(nle_bilateral8(ctx_, in.L.f(), image.rows, image.cols, sigmaColor, sigmaSpace, d_Y.f()), ctx_);
-    Vec t = eigvals();
+    // the L channel becomes its pre-filtered version (:370-373; `apply` on it is commented out, :389)
+    const double sigma = options.prefilter == NLE_PREFILTER_NLM ? plane_sigma(ctx_, options, in.L.f(), H, W) : 0;
+    prefilter_plane(ctx_, options, in.L.f(), H, W, sigmaColor, sigmaSpace, sigma, d_Y.f());
+    Vec t = ev;
     for (int i = 0; i < t.size(); ++i) {  // :380-387
-        const DType ev = std::min(t(i), 1.0);
-        if (verbose) std::cout << "eig " << i << " val: " << ev << std::endl;
-        t(i) = std::pow(ev, k);
+        const DType e = std::min(t(i), 1.0);
+        if (verbose) std::cout << "eig " << i << " val: " << e << std::endl;
+        t(i) = std::pow(e, k);
     }
     // a and b through the filter in one call (:390-391, + :394-399): two planes, the same response, rounded as
     // nle_apply_rounded8 rounds
@@ -282,11 +345,10 @@ Image NLEFilter::denoise(const Image& image, DType k, int sigmaColor, int sigmaS
         check(nle_lab8_channel(ctx_, in.lab.u8(), (long long)np, ch, d_c.f() + (size_t)(ch - 1) * np), ctx_);
     std::vector<double> t2((size_t)2 * t.size());
     for (int i = 0; i < t.size(); ++i) t2[i] = t2[(size_t)t.size() + i] = t(i);
-    check(nle_apply_planes(f_, d_c.f(), 2, (long long)np, image.rows, image.cols, nullptr, t2.data(), NLE_REGION_OUT_ROUNDED8,
-                           d_ab.f(), (long long)np), ctx_);
+    check(nle_apply_planes(f_, d_c.f(), 2, (long long)np, H, W, nullptr, t2.data(), NLE_REGION_OUT_ROUNDED8, d_ab.f(),
+                           (long long)np), ctx_);
     // max(0) / min(255) / convertTo(CV_8U) of the three planes, merge, Lab -> BGR (:393-409)
-    Image out(image.rows, image.cols, NLE_8U, 3);
-    lab_to_rows(ctx_, in, d_Y.f(), d_ab.f(), d_ab.f() + np, out, 0, image.rows);
+    lab_to_rows(ctx_, in, d_Y.f(), d_ab.f(), d_ab.f() + np, out, 0, H);
     return out;
 }
 

@@ -159,6 +159,43 @@ inline void lab_to_rows(nle_ctx* c, const LabPlanes& in, const float* d_L, const
     check(nle_dev_download(c, out.ptr<unsigned char>(r0), in.bgr.p, n * 3), c);
 }
 
+// ---- the pre-filter of the denoise flow (DenoiseOptions): one owner for train and denoise ----
+// what a non-default DenoiseOptions may hold; sigmaColor / sigmaSpace are checked as nle_bilateral8 checks them, also when
+// the NLM pre-filter leaves them unused
+inline void check_denoise_options(const DenoiseOptions& o, int sigmaColor, int sigmaSpace) {
+    if (o.prefilter != NLE_PREFILTER_BILATERAL && o.prefilter != NLE_PREFILTER_NLM)
+        throw std::runtime_error("DenoiseOptions::prefilter must be NLE_PREFILTER_BILATERAL or NLE_PREFILTER_NLM");
+    if (std::isnan(o.noiseSigma) || std::isinf(o.noiseSigma))
+        throw std::runtime_error("DenoiseOptions::noiseSigma must be finite (negative: estimated)");
+    if (!std::isfinite(o.nlmH) || o.nlmH < 0) throw std::runtime_error("DenoiseOptions::nlmH must be finite and >= 0 (0: from the noise level)");
+    int radius = 0;
+    nle_bilateral_tables(sigmaColor, sigmaSpace, &radius, nullptr, nullptr);
+    if (radius > 64) throw std::runtime_error("bilateral filter: sigma_space above 42 (radius > 64) is not supported");
+}
+
+// the noise level of an 8-bit plane on the device: the caller's, or Immerkaer's estimate (nle_plane_noise)
+inline double plane_sigma(nle_ctx* c, const DenoiseOptions& o, const float* d_x, int H, int W) {
+    if (o.noiseSigma >= 0) return o.noiseSigma;
+    double sigma = 0;
+    check(nle_plane_noise(c, d_x, H, W, nullptr, &sigma), c);
+    return sigma;
+}
+
+// d_dst = the pre-filtered d_src (H x W levels as fp32).  Bilateral: the reference's call.  NLM: nle_nlm8 with the IPOL
+// table's P, S and h for `sigma` (see DenoiseOptions); h == 0: a copy, no kernel runs
+inline void prefilter_plane(nle_ctx* c, const DenoiseOptions& o, const float* d_src, int H, int W, int sigmaColor,
+                            int sigmaSpace, double sigma, float* d_dst) {
+    if (o.prefilter == NLE_PREFILTER_BILATERAL) return check(nle_bilateral8(c, d_src, H, W, sigmaColor, sigmaSpace, d_dst), c);
+    const int P = sigma <= 15 ? 1 : sigma <= 30 ? 2 : 3, S = 10;
+    const double h = o.nlmH > 0 ? o.nlmH : (sigma <= 30 ? 0.40 : 0.35) * sigma;
+    if (h == 0) {
+        std::vector<float> v((size_t)H * W);
+        check(nle_dev_download(c, v.data(), d_src, v.size() * 4), c);
+        return check(nle_dev_upload(c, d_dst, v.data(), v.size() * 4), c);
+    }
+    check(nle_nlm8(c, d_src, H, W, P, S, sigma, h, d_dst, nullptr), c);
+}
+
 // ---- deep colour (16UC3 images): the same two steps on float Lab planes ----
 // prologue: n 16-bit BGR pixels -> L (fp32, unrounded) always; a and b (likewise) and the guide (L rounded to the 256
 // levels a train takes) when wanted, empty otherwise
