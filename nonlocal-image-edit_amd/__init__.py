@@ -264,6 +264,14 @@ def mse_shrink(eigvals, b, sigma, k_max, n_grid=256):
     return k.value, mse
 
 
+def _combine_out(out, n, out_kind, device):
+    """the output of a pointwise combine: `out` if given, else n float32 values, or n bytes for REGION_OUT_U8"""
+    if out is not None:
+        return out
+    torch = _torch()
+    return torch.empty(n, dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32, device=device)
+
+
 def _torch():
     import torch
     return torch
@@ -1069,7 +1077,6 @@ class Context:
         """nle_region_combine, the rule alone: layers (L, n) and q (M, n) float32 device tensors whose rows are contiguous
         and may lie any stride >= n apart (a view into a larger buffer, at any offset, is taken as it is); weights
         (M + 1, L) float64, row 0 the background.  Returns n float32 values, or n bytes for REGION_OUT_U8."""
-        torch = _torch()
         self._sync_in()
         L, n = layers.shape
         M = q.shape[0]
@@ -1078,8 +1085,7 @@ class Context:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.shape != (M + 1, L):
             raise NLEError(NLE_ERR_INVALID, f"region_combine: weights must be {(M + 1, L)}, got {w.shape}")
-        if out is None:
-            out = torch.empty(n, dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32, device=layers.device)
+        out = _combine_out(out, n, out_kind, layers.device)
         _check(lib().nle_region_combine(self._h, C.c_void_p(layers.data_ptr()), L, C.c_void_p(q.data_ptr()), M, n,
                                         layers.stride(0) if L > 1 else n, q.stride(0) if M > 1 else n, _np_ptr(w),
                                         float(floor), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
@@ -1089,7 +1095,6 @@ class Context:
         """nle_detail_combine, the rule alone: x (n,) and layers (L, n) float32 device tensors, the rows of layers contiguous
         and any stride >= n apart (a view into a larger buffer, at any offset, is taken as it is); weights L float64 values.
         Returns n float32 values, or n bytes for REGION_OUT_U8."""
-        torch = _torch()
         self._sync_in()
         L, n = layers.shape
         if x.shape != (n,) or x.stride(0) != 1 or layers.stride(1) != 1:
@@ -1097,8 +1102,7 @@ class Context:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.shape != (L,):
             raise NLEError(NLE_ERR_INVALID, f"detail_combine: weights must hold L = {L} values, got {w.shape}")
-        if out is None:
-            out = torch.empty(n, dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32, device=layers.device)
+        out = _combine_out(out, n, out_kind, layers.device)
         _check(lib().nle_detail_combine(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(layers.data_ptr()), L, n,
                                         layers.stride(0) if L > 1 else n, _np_ptr(w), float(residual_weight), float(gain),
                                         float(sigma), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
@@ -1357,6 +1361,21 @@ class NLEFilter:
                self.ctx._h)
         return out
 
+    def _planes(self, planes, one_ok):
+        """planes as a P x H x W float32 device tensor, each plane contiguous, any stride >= H W between them (one_ok: one
+        H x W plane is taken as P = 1) -> (tensor, P, H, W)"""
+        torch = _torch()
+        t = torch.as_tensor(planes, dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        if one_ok and t.ndim == 2:
+            t = t[None]
+        if t.ndim != 3:
+            raise NLEError(NLE_ERR_INVALID, "planes must be P x H x W")
+        P, H, W = t.shape
+        if t.stride(2) != 1 or t.stride(1) != W or (P > 1 and t.stride(0) < H * W):
+            t = t.contiguous()
+        self.ctx._sync_in()
+        return t, P, H, W
+
     def apply_planes(self, planes, responses, out_kind=0, out=None):
         """nle_apply_planes: the filter applied to P planes in one call, each with its own responses; every output is bit
         for bit what `apply` / `apply_layers` / `apply_rounded8` give plane by plane.
@@ -1366,13 +1385,7 @@ class NLEFilter:
         of ones for every plane.  out_kind: REGION_OUT_F32 or REGION_OUT_ROUNDED8.  Returns (R, n_local) float32, the
         outputs of plane 0 first; `out` may be such a tensor with any stride between its rows."""
         torch = _torch()
-        t = torch.as_tensor(planes, dtype=torch.float32, device=f"cuda:{self.ctx.device}")
-        if t.ndim != 3:
-            raise NLEError(NLE_ERR_INVALID, "planes must be P x H x W")
-        P, H, W = t.shape
-        if t.stride(2) != 1 or t.stride(1) != W or (P > 1 and t.stride(0) < H * W):
-            t = t.contiguous()
-        self.ctx._sync_in()
+        t, P, H, W = self._planes(planes, one_ok=False)
         K = self.info()["K"]
         if responses is None:
             responses = [np.ones(K)] * P
@@ -1397,16 +1410,7 @@ class NLEFilter:
     def coefficients(self, planes):
         """nle_filter_coefficients: t = V^T x of P planes (P x H x W float32, or one H x W plane) as a (P, K') float64 array,
         row m bit for bit the vector `apply` forms for plane m"""
-        torch = _torch()
-        t = torch.as_tensor(planes, dtype=torch.float32, device=f"cuda:{self.ctx.device}")
-        if t.ndim == 2:
-            t = t[None]
-        if t.ndim != 3:
-            raise NLEError(NLE_ERR_INVALID, "planes must be P x H x W")
-        P, H, W = t.shape
-        if t.stride(2) != 1 or t.stride(1) != W or (P > 1 and t.stride(0) < H * W):
-            t = t.contiguous()
-        self.ctx._sync_in()
+        t, P, H, W = self._planes(planes, one_ok=True)
         out = np.zeros((max(P, 1), self.info()["K"]))
         _check(lib().nle_filter_coefficients(self._f, C.c_void_p(t.data_ptr()), P, t.stride(0) if P > 1 else H * W, H, W,
                                              _np_ptr(out)), self.ctx._h)
@@ -1445,7 +1449,6 @@ class NLEFilter:
     def apply_regions(self, x, n_layers, strokes, weights, scale=None, spread=4.0, floor=0.05, out_kind=0, out=None):
         """nle_apply_regions: the layers of x, the spreads of the stroke planes and the combine in one call.  weights:
         (M + 1, n_layers) float64, row 0 the background.  Returns n_local float32 values, or bytes for REGION_OUT_U8."""
-        torch = _torch()
         x = self.ctx._lum(x)
         H, W = x.shape
         s = self._strokes(strokes)
@@ -1454,9 +1457,7 @@ class NLEFilter:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.shape != (M + 1, int(n_layers)):
             raise NLEError(NLE_ERR_INVALID, f"weights must be {(M + 1, int(n_layers))}, got {w.shape}")
-        if out is None:
-            out = torch.empty(self.info()["n_local"], dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32,
-                              device=x.device)
+        out = _combine_out(out, self.info()["n_local"], out_kind, x.device)
         _check(lib().nle_apply_regions(self._f, C.c_void_p(x.data_ptr()), H, W, int(n_layers), C.c_void_p(s.data_ptr()), M,
                                        cp, float(spread), float(floor), _np_ptr(w), int(out_kind),
                                        C.c_void_p(out.data_ptr())), self.ctx._h)
@@ -1466,15 +1467,12 @@ class NLEFilter:
         """nle_apply_detail: the len(weights) layers of x and the detail combine in one call -- the out-of-span residual
         x - sum of the layers as one more layer under residual_weight, and the gain curve (gain, sigma) on the residual and
         on every layer but the last.  Returns n_local float32 values, or bytes for REGION_OUT_U8."""
-        torch = _torch()
         x = self.ctx._lum(x)
         H, W = x.shape
         w = np.ascontiguousarray(weights, dtype=np.float64)
         if w.ndim != 1:
             raise NLEError(NLE_ERR_INVALID, f"weights must be a vector, got {w.shape}")
-        if out is None:
-            out = torch.empty(self.info()["n_local"], dtype=torch.uint8 if out_kind == REGION_OUT_U8 else torch.float32,
-                              device=x.device)
+        out = _combine_out(out, self.info()["n_local"], out_kind, x.device)
         _check(lib().nle_apply_detail(self._f, C.c_void_p(x.data_ptr()), H, W, int(w.shape[0]), _np_ptr(w),
                                       float(residual_weight), float(gain), float(sigma), int(out_kind),
                                       C.c_void_p(out.data_ptr())), self.ctx._h)

@@ -9,10 +9,9 @@
 // one plane out, nothing kept between pixels.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "kernels.h"
 #include "nle.h"
+#include "plane_combine.h"
 
 // the rule fixes where every rounding happens: a contracted fma would round a product and a sum once instead of twice
 #pragma clang fp contract(off)
@@ -30,26 +29,6 @@ struct DetailArgs {
     DetailWeights w;
 };
 
-__device__ __forceinline__ float sat8f(float v) {
-    return fminf(255.f, fmaxf(0.f, rintf(v)));  // k_plane_to_u8's rule: round half to even, saturate
-}
-
-template <int P>
-struct Pack;
-template <>
-struct Pack<1> {
-    float v[1];
-    __device__ __forceinline__ void load(const float* p) { v[0] = *p; }
-};
-template <>
-struct Pack<4> {
-    float v[4];
-    __device__ __forceinline__ void load(const float* p) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    }
-};
-
 __device__ __forceinline__ double remap(const DetailArgs& a, double d) {
     const double t = d / a.sigma;
     return d * (1.0 + a.gain_m1 * exp(-(t * t)));
@@ -60,7 +39,7 @@ __device__ __forceinline__ double remap(const DetailArgs& a, double d) {
 // stay in registers (a runtime-indexed array would go to scratch) and all L + 1 loads are in flight together.  LMAX is 4 or
 // kRegionLayersMax: the registers of sixteen layers would halve the occupancy of the usual four.
 // CURVE is the uniform switch a.curve as a template argument: with the curve off no exp is in the instruction stream.
-template <int P, int LMAX, bool CURVE>
+template <int LMAX, bool CURVE, int P>
 __device__ __forceinline__ void detail_pixels(const DetailArgs& a, long long i, double (&y)[P]) {
     const int L = a.L;
     Pack<P> X, Y[LMAX];
@@ -93,61 +72,21 @@ __device__ __forceinline__ void detail_pixels(const DetailArgs& a, long long i, 
         }
 }
 
-template <int OUT>
-__device__ __forceinline__ void detail_store1(void* out, long long i, double y) {
-    const float v = (float)y;
-    if constexpr (OUT == NLE_REGION_OUT_F32) static_cast<float*>(out)[i] = v;
-    else if constexpr (OUT == NLE_REGION_OUT_ROUNDED8) static_cast<float*>(out)[i] = sat8f(v);
-    else static_cast<unsigned char*>(out)[i] = (unsigned char)(int)sat8f(v);
-}
-
 }  // namespace
 
-// Four pixels per thread (16-byte loads, one 16-byte store, or one 4-byte store of four bytes) where every plane allows
-// it; the last n mod 4 pixels, and everything when a base pointer or the layer stride breaks the alignment, go one pixel at
-// a time, as in k_region_combine.  Grid-stride.
+// plane_combine.h's skeleton over detail_pixels; the 16-byte loads need both base pointers aligned, and the layer stride
+// where a second layer is read
 template <int OUT, int LMAX>
 __global__ __launch_bounds__(256) void k_detail_combine(const DetailArgs a, void* __restrict__ out) {
-    const long long n = a.n, n4 = n >> 2;
-    const size_t out_mask = OUT == NLE_REGION_OUT_U8 ? 3 : 15;
-    const bool vec = (((reinterpret_cast<size_t>(a.layers) | reinterpret_cast<size_t>(a.x)) & 15) |
-                      (reinterpret_cast<size_t>(out) & out_mask) | (size_t)(a.L > 1 ? a.layer_stride & 3 : 0)) == 0;
-    const long long step = (long long)gridDim.x * 256;
-    if (vec) {
-        for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n4; g += step) {
-            double y[4];
-            if (a.curve) detail_pixels<4, LMAX, true>(a, g * 4, y);
-            else detail_pixels<4, LMAX, false>(a, g * 4, y);
-            if constexpr (OUT == NLE_REGION_OUT_U8) {
-                const unsigned r = (unsigned)(int)sat8f((float)y[0]) | ((unsigned)(int)sat8f((float)y[1]) << 8) |
-                                   ((unsigned)(int)sat8f((float)y[2]) << 16) | ((unsigned)(int)sat8f((float)y[3]) << 24);
-                static_cast<unsigned*>(out)[g] = r;
-            } else {
-                float4 r = make_float4((float)y[0], (float)y[1], (float)y[2], (float)y[3]);
-                if constexpr (OUT == NLE_REGION_OUT_ROUNDED8) r = make_float4(sat8f(r.x), sat8f(r.y), sat8f(r.z), sat8f(r.w));
-                static_cast<float4*>(out)[g] = r;
-            }
-        }
-    }
-    for (long long i = (vec ? n4 * 4 : 0) + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
-        double y[1];
-        if (a.curve) detail_pixels<1, LMAX, true>(a, i, y);
-        else detail_pixels<1, LMAX, false>(a, i, y);
-        detail_store1<OUT>(out, i, y[0]);
-    }
+    const size_t misaligned = ((reinterpret_cast<size_t>(a.layers) | reinterpret_cast<size_t>(a.x)) & 15) |
+                              (size_t)(a.L > 1 ? a.layer_stride & 3 : 0);
+    combine_planes<OUT>(a.n, misaligned, out, [&a](long long i, auto& y) {
+        if (a.curve) detail_pixels<LMAX, true>(a, i, y);
+        else detail_pixels<LMAX, false>(a, i, y);
+    });
 }
-
-namespace {
 
 constexpr int kDetailFewLayers = 4;  // up to here the LMAX = 4 instantiation runs
-
-template <int OUT>
-void detail_launch(bool few, unsigned grid, hipStream_t s, const DetailArgs& a, void* d_out) {
-    if (few) hipLaunchKernelGGL((k_detail_combine<OUT, kDetailFewLayers>), dim3(grid), dim3(256), 0, s, a, d_out);
-    else hipLaunchKernelGGL((k_detail_combine<OUT, kRegionLayersMax>), dim3(grid), dim3(256), 0, s, a, d_out);
-}
-
-}  // namespace
 
 hipError_t detail_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
                           const DetailWeights& w, double w_rho, double gain, double sigma, int out_kind, void* d_out) {
@@ -164,22 +103,12 @@ hipError_t detail_combine(hipStream_t s, const float* d_x, const float* d_layers
     a.gain_m1 = gain - 1.0;
     a.sigma = sigma;
     a.w = w;
-    const unsigned grid = (unsigned)std::min<long long>((n / 4 + 255) / 256 + 1, 4096);  // k_region_combine's cap
-    const bool few = L <= kDetailFewLayers;
-    switch (out_kind) {
-        case NLE_REGION_OUT_F32:
-            detail_launch<NLE_REGION_OUT_F32>(few, grid, s, a, d_out);
-            break;
-        case NLE_REGION_OUT_ROUNDED8:
-            detail_launch<NLE_REGION_OUT_ROUNDED8>(few, grid, s, a, d_out);
-            break;
-        case NLE_REGION_OUT_U8:
-            detail_launch<NLE_REGION_OUT_U8>(few, grid, s, a, d_out);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_for_out_kind(out_kind, [&](auto out) {
+        constexpr int OUT = decltype(out)::value;
+        if (L <= kDetailFewLayers)
+            hipLaunchKernelGGL((k_detail_combine<OUT, kDetailFewLayers>), dim3(combine_grid(n)), dim3(256), 0, s, a, d_out);
+        else hipLaunchKernelGGL((k_detail_combine<OUT, kRegionLayersMax>), dim3(combine_grid(n)), dim3(256), 0, s, a, d_out);
+    });
 }
 
 }  // namespace nlek

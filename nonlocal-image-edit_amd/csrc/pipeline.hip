@@ -107,6 +107,21 @@ nle_filter* end_train(std::unique_ptr<nle_filter> f, double t_begin) {
 
 namespace {
 
+// The refusal of a plane that does not have the training image's size, with the reference's text (src/filter.cpp:447-449).
+// each_positive: H and W are looked at one by one as well (the entry points that take them from the caller)
+void check_plane_size(const nle_filter* f, int H, int W, bool each_positive) {
+    if ((each_positive && (H <= 0 || W <= 0)) || (long long)H * W != (long long)f->H * f->W)
+        throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+}
+
+// The refusal of an output kind that is no NLE_REGION_OUT_* (with_u8: NLE_REGION_OUT_U8 is one the caller takes).
+// before: the caller's text up to the number
+void check_out_kind(const std::string& before, int out_kind, bool with_u8) {
+    if (out_kind == NLE_REGION_OUT_F32 || out_kind == NLE_REGION_OUT_ROUNDED8 || (with_u8 && out_kind == NLE_REGION_OUT_U8)) return;
+    throw Fail{NLE_ERR_INVALID, before + std::to_string(out_kind) +
+                                    (with_u8 ? " (NLE_REGION_OUT_*)" : " (NLE_REGION_OUT_F32 or NLE_REGION_OUT_ROUNDED8)")};
+}
+
 // d_lum_in: the full H x W plane, or -- ctx in slab-input mode -- this rank's rows [row0, row1) only
 nle_filter* train_impl(nle_ctx* c, const float* d_lum_in, int H, int W, int nRow, int nCol, double hx,
                        double hy, int T, int n_eig) {
@@ -244,8 +259,7 @@ void apply_impl(nle_filter* f, const float* d_x_in, int H, int W, const double* 
     nle_ctx* c = f->ctx;
     // slab-input mode: d_x_in holds this rank's rows only; index it through the virtual base of the full image
     const float* d_x = (c->slab_input && c->world > 1) ? d_x_in - (size_t)f->row0 * f->W : d_x_in;
-    if ((long long)H * W != (long long)f->H * f->W)  // reference src/filter.cpp:447-449
-        throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+    check_plane_size(f, H, W, false);
     if (L < 1 || L > 64) throw Fail{NLE_ERR_INVALID, "number of layers must be in [1, 64]"};
     HIP_OK(hipSetDevice(c->device));
     if (f->tables) {
@@ -274,8 +288,7 @@ void round8_planes(nle_filter* f, float* d_y, int L, long long ystride) {
 void apply_planes_impl(nle_filter* f, const float* const* d_x, int P, int H, int W, const int* nresp, const double* h_resp,
                        float* d_y, long long ystride, bool round8) {
     nle_ctx* c = f->ctx;
-    if ((long long)H * W != (long long)f->H * f->W)  // reference src/filter.cpp:447-449
-        throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+    check_plane_size(f, H, W, false);
     int R = 0;
     for (int m = 0; m < P; ++m) R += nresp[m];
     if (P > 1 && f->tables && f->tables->sorted_rows() && c->world == 1) {
@@ -346,8 +359,7 @@ DevBuf<T> upload_train_plane(nle_ctx* ctx, const T* h_plane, int H, int W, size_
 // into d_xbuf, or the training plane the filter kept
 const float* host_apply_input(nle_filter* f, const float* h_x, int H, int W, DevBuf<float>& d_xbuf) {
     nle_ctx* c = f->ctx;
-    if ((long long)H * W != (long long)f->H * f->W)
-        throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+    check_plane_size(f, H, W, false);
     if (!h_x && !f->plane.p)
         throw Fail{NLE_ERR_INVALID, "h_x == NULL needs a filter trained by nle_train_host (it keeps the training plane)"};
     HIP_OK(hipSetDevice(c->device));
@@ -405,8 +417,7 @@ void region_check_combine(int L, int M, double floor, int out_kind) {
                                         std::to_string(M)};
     if (!std::isfinite(floor) || !(floor > 0))
         throw Fail{NLE_ERR_INVALID, "the region floor must be finite and > 0, got " + std::to_string(floor)};
-    if (out_kind != NLE_REGION_OUT_F32 && out_kind != NLE_REGION_OUT_ROUNDED8 && out_kind != NLE_REGION_OUT_U8)
-        throw Fail{NLE_ERR_INVALID, "unknown region output kind " + std::to_string(out_kind) + " (NLE_REGION_OUT_*)"};
+    check_out_kind("unknown region output kind ", out_kind, true);
 }
 
 void region_check_spread(const nle_filter* f, int M, int H, int W, const double* h_scale, double spread) {
@@ -420,8 +431,7 @@ void region_check_spread(const nle_filter* f, int M, int H, int W, const double*
             throw Fail{NLE_ERR_INVALID, "the scale of region " + std::to_string(m + 1) + " is not finite"};
     if (f->ctx->world > 1)
         throw Fail{NLE_ERR_INVALID, "region edits run on one device only (world == 1): slabs and device groups are not built"};
-    if (H <= 0 || W <= 0 || (long long)H * W != (long long)f->H * f->W)  // the text of nle_apply's refusal (:447-449)
-        throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+    check_plane_size(f, H, W, true);
 }
 
 void region_combine_impl(nle_ctx* c, const float* d_layers, int L, const float* d_q, int M, long long n, long long layer_stride,
@@ -468,8 +478,7 @@ void detail_check(const char* who, int L, const double* h_weights, double w_rho,
                                         "], got " + std::to_string(gain)};
     if (!std::isfinite(sigma) || sigma < 0)
         throw Fail{NLE_ERR_INVALID, name + ": the detail sigma must be finite and >= 0, got " + std::to_string(sigma)};
-    if (out_kind != NLE_REGION_OUT_F32 && out_kind != NLE_REGION_OUT_ROUNDED8 && out_kind != NLE_REGION_OUT_U8)
-        throw Fail{NLE_ERR_INVALID, name + ": unknown output kind " + std::to_string(out_kind) + " (NLE_REGION_OUT_*)"};
+    check_out_kind(name + ": unknown output kind ", out_kind, true);
 }
 
 // d_out (n floats, or n bytes for NLE_REGION_OUT_U8) must not overlap the n floats at d_in
@@ -782,9 +791,7 @@ int nle_apply_planes(nle_filter* f, const float* d_x, int P, long long x_stride,
             throw Fail{NLE_ERR_INVALID, "nle_apply_planes takes 1 to " + std::to_string(NLE_PLANES_MAX) + " planes, got " +
                                             std::to_string(P)};
         if (!d_x || !h_resp || !d_y) throw Fail{NLE_ERR_INVALID, "nle_apply_planes: NULL pointer"};
-        if (out_kind != NLE_REGION_OUT_F32 && out_kind != NLE_REGION_OUT_ROUNDED8)
-            throw Fail{NLE_ERR_INVALID, "nle_apply_planes: unknown output kind " + std::to_string(out_kind) +
-                                            " (NLE_REGION_OUT_F32 or NLE_REGION_OUT_ROUNDED8)"};
+        check_out_kind("nle_apply_planes: unknown output kind ", out_kind, false);
         int nresp[NLE_PLANES_MAX], R = 0;
         for (int m = 0; m < P; ++m) {
             nresp[m] = h_nresp ? h_nresp[m] : 1;
@@ -795,8 +802,7 @@ int nle_apply_planes(nle_filter* f, const float* d_x, int P, long long x_stride,
         }
         if (R > 128)
             throw Fail{NLE_ERR_INVALID, "nle_apply_planes: " + std::to_string(R) + " responses in all, at most 128 are taken"};
-        if (H <= 0 || W <= 0 || (long long)H * W != (long long)f->H * f->W)  // the text of nle_apply's refusal (:447-449)
-            throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+        check_plane_size(f, H, W, true);
         const nle_ctx* c = f->ctx;
         const long long nin = (c->slab_input && c->world > 1) ? f->n_local : (long long)H * W, nout = f->n_local;
         if ((P > 1 && x_stride < nin) || (R > 1 && y_stride < nout) || x_stride < 0 || y_stride < 0)
@@ -849,8 +855,7 @@ int nle_filter_coefficients(nle_filter* f, const float* d_x, int P, long long x_
             throw Fail{NLE_ERR_INVALID, "nle_filter_coefficients takes 1 to " + std::to_string(NLE_PLANES_MAX) + " planes, got " +
                                             std::to_string(P)};
         if (!d_x || !h_t) throw Fail{NLE_ERR_INVALID, "nle_filter_coefficients: NULL pointer"};
-        if (H < 1 || W < 1 || (long long)H * W != (long long)f->H * f->W)  // reference src/filter.cpp:447-449
-            throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+        check_plane_size(f, H, W, true);
         if (P > 1 && x_stride < (long long)H * W)
             throw Fail{NLE_ERR_INVALID, "nle_filter_coefficients: the plane stride is smaller than the plane"};
         const float* planes[NLE_PLANES_MAX];
@@ -907,8 +912,7 @@ int nle_apply_detail(nle_filter* f, const float* d_x, int H, int W, int L, const
         detail_check("nle_apply_detail", L, h_weights, w_rho, gain, sigma, out_kind);
         if (c->world > 1)
             throw Fail{NLE_ERR_INVALID, "nle_apply_detail runs on one device only (world == 1): slabs and device groups are not built"};
-        if (H <= 0 || W <= 0 || (long long)H * W != (long long)f->H * f->W)  // the text of nle_apply's refusal (:447-449)
-            throw Fail{NLE_ERR_INVALID, "Number of values in channel must match that of training image."};
+        check_plane_size(f, H, W, true);
         const long long n = f->n_local;  // == H W: world == 1
         detail_check_overlap("nle_apply_detail", d_x, d_out, n, out_kind, "the plane");
         DevBuf<float> d_work((size_t)L * n);

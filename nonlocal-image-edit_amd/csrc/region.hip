@@ -8,10 +8,9 @@
 // reproduced bit for bit.  Memory bound: L + M fp32 planes in, one plane out, nothing kept between pixels.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "kernels.h"
 #include "nle.h"
+#include "plane_combine.h"
 
 // the rule fixes where every rounding happens: a contracted fma would round a product and a sum once instead of twice
 #pragma clang fp contract(off)
@@ -27,26 +26,6 @@ struct RegionArgs {
     int L, M;
     double floor;
     RegionWeights w;
-};
-
-__device__ __forceinline__ float sat8f(float v) {
-    return fminf(255.f, fmaxf(0.f, rintf(v)));  // k_plane_to_u8's rule: round half to even, saturate
-}
-
-template <int P>
-struct Pack;
-template <>
-struct Pack<1> {
-    float v[1];
-    __device__ __forceinline__ void load(const float* p) { v[0] = *p; }
-};
-template <>
-struct Pack<4> {
-    float v[4];
-    __device__ __forceinline__ void load(const float* p) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    }
 };
 
 // y of the P consecutive pixels from i on.  The loop over the regions is unrolled to kRegionMax under the uniform guard
@@ -105,46 +84,14 @@ __device__ __forceinline__ void region_pixels(const RegionArgs& a, long long i, 
     }
 }
 
-template <int OUT>
-__device__ __forceinline__ void region_store1(void* out, long long i, double y) {
-    const float v = (float)y;
-    if constexpr (OUT == NLE_REGION_OUT_F32) static_cast<float*>(out)[i] = v;
-    else if constexpr (OUT == NLE_REGION_OUT_ROUNDED8) static_cast<float*>(out)[i] = sat8f(v);
-    else static_cast<unsigned char*>(out)[i] = (unsigned char)(int)sat8f(v);
-}
-
 }  // namespace
 
-// Four pixels per thread (16-byte loads, one 16-byte store, or one 4-byte store of four bytes) where every plane allows
-// it; the last n mod 4 pixels, and everything when a base pointer or a plane stride breaks the alignment, go one pixel at a
-// time, as in k_plane_to_u8.  Grid-stride.
+// plane_combine.h's skeleton over region_pixels; the 16-byte loads need both base pointers and both plane strides aligned
 template <int OUT>
 __global__ __launch_bounds__(256) void k_region_combine(const RegionArgs a, void* __restrict__ out) {
-    const long long n = a.n, n4 = n >> 2;
-    const size_t out_mask = OUT == NLE_REGION_OUT_U8 ? 3 : 15;
-    const bool vec = (((reinterpret_cast<size_t>(a.layers) | reinterpret_cast<size_t>(a.q)) & 15) |
-                      (reinterpret_cast<size_t>(out) & out_mask) | (size_t)((a.layer_stride | a.q_stride) & 3)) == 0;
-    const long long step = (long long)gridDim.x * 256;
-    if (vec) {
-        for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < n4; g += step) {
-            double y[4];
-            region_pixels<4>(a, g * 4, y);
-            if constexpr (OUT == NLE_REGION_OUT_U8) {
-                const unsigned r = (unsigned)(int)sat8f((float)y[0]) | ((unsigned)(int)sat8f((float)y[1]) << 8) |
-                                   ((unsigned)(int)sat8f((float)y[2]) << 16) | ((unsigned)(int)sat8f((float)y[3]) << 24);
-                static_cast<unsigned*>(out)[g] = r;
-            } else {
-                float4 r = make_float4((float)y[0], (float)y[1], (float)y[2], (float)y[3]);
-                if constexpr (OUT == NLE_REGION_OUT_ROUNDED8) r = make_float4(sat8f(r.x), sat8f(r.y), sat8f(r.z), sat8f(r.w));
-                static_cast<float4*>(out)[g] = r;
-            }
-        }
-    }
-    for (long long i = (vec ? n4 * 4 : 0) + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += step) {
-        double y[1];
-        region_pixels<1>(a, i, y);
-        region_store1<OUT>(out, i, y[0]);
-    }
+    const size_t misaligned = ((reinterpret_cast<size_t>(a.layers) | reinterpret_cast<size_t>(a.q)) & 15) |
+                              (size_t)((a.layer_stride | a.q_stride) & 3);
+    combine_planes<OUT>(a.n, misaligned, out, [&a](long long i, auto& y) { region_pixels(a, i, y); });
 }
 
 hipError_t region_combine(hipStream_t s, const float* d_layers, long long layer_stride, int L, const float* d_q,
@@ -163,21 +110,9 @@ hipError_t region_combine(hipStream_t s, const float* d_layers, long long layer_
     a.M = M;
     a.floor = floor;
     a.w = wt;
-    const unsigned grid = (unsigned)std::min<long long>((n / 4 + 255) / 256 + 1, 4096);  // plane_to_u8's cap
-    switch (out_kind) {
-        case NLE_REGION_OUT_F32:
-            hipLaunchKernelGGL(k_region_combine<NLE_REGION_OUT_F32>, dim3(grid), dim3(256), 0, s, a, d_out);
-            break;
-        case NLE_REGION_OUT_ROUNDED8:
-            hipLaunchKernelGGL(k_region_combine<NLE_REGION_OUT_ROUNDED8>, dim3(grid), dim3(256), 0, s, a, d_out);
-            break;
-        case NLE_REGION_OUT_U8:
-            hipLaunchKernelGGL(k_region_combine<NLE_REGION_OUT_U8>, dim3(grid), dim3(256), 0, s, a, d_out);
-            break;
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_for_out_kind(out_kind, [&](auto out) {
+        hipLaunchKernelGGL(k_region_combine<decltype(out)::value>, dim3(combine_grid(n)), dim3(256), 0, s, a, d_out);
+    });
 }
 
 }  // namespace nlek

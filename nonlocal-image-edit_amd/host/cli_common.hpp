@@ -2,25 +2,10 @@
 //   <image> <output> <# row samples> <# col samples> <hx> <hy> <# sinkhorn iterations> <# eigen vectors> ...
 // print the same usage line when too few arguments are given, parse numbers with std::stoi / std::stod (garbage
 // throws, like the reference: src/enhance.cpp:20-31, src/denoise.cpp:19-31) and return 0 on the two soft failures
-// (usage, unreadable image) for drop-in compatibility.  New here: optional LEADING `--patch-radius R` (patch affinities,
-// NLEFilter::patchRadius), `--sampler grid|farthest|residual` (NLEFilter::sampler) and the flag `--exact` (NLEFilter::exact, no
-// value; not with a non-zero radius or a sampler other than the grid) and, for enhance only, `--chroma HC` (chroma-aware affinities,
-// NLEFilter::chromaBandwidth: a finite number > 0; not with --exact or a radius above NLE_CHROMA_PATCH_RADIUS_MAX), in any order; reference command lines never start with
-// `--`, so they parse exactly as before.  An invalid value prints a message to stderr and exits with status 2 before
-// anything touches the GPU.  For enhance only, region edits (NLEFilter::enhanceRegions): `--region MASK:w1,w2,...`, up to
-// NLE_REGION_MAX times (split at the last `:`; MASK any image the readers decode, its first channel is the stroke; as many
-// weights as positional ones, which are the background's), `--region-spread T` and `--region-floor F` (finite, > 0; only
-// with a region); the flag `--nystrom-report` with its optional `--nystrom-map FILE` (NLEFilter::nystromResidual; not
-// with --exact); and the flag `--deep` (no value): the input is read with imread16 -- a 16-bit PNG keeps every sample -- and
-// the result is written as a 16-bit PNG (the output name must end in .png; not with --region); and the flag `--tonemap`
-// (no value) with its optional `--tonemap-saturation S` (a finite number in (0, 2]): the input is an HDR file read with
-// imreadHDR, the positional weights are the layer weights of NLEFilter::toneMap -- the last one is the base compression --
-// and the result is a 16-bit PNG (not with --chroma, --region, --deep or --nystrom-report); and `--residual-weight WR` (a
-// finite number), `--detail-gain A` (finite, in [0, NLE_DETAIL_GAIN_MAX]) and `--detail-sigma S` (finite, >= 0):
-// nle::DetailOptions of NLEFilter::enhance / toneMap, with --deep and --tonemap too (a gain other than 1 needs a sigma > 0;
-// not with --region).  For denoise only, the MSE-guided denoiser (nle::DenoiseOptions): `--prefilter bilateral|nlm`, the flag
-// `--glide` (no value), `--noise-sigma S` (finite, >= 0; needs --glide or --prefilter nlm) and `--nlm-h H` (finite, > 0; needs
-// --prefilter nlm); under --glide the positional shrink factor is the upper end of the searched range.
+// (usage, unreadable image) for drop-in compatibility.  New here: LEADING options, in any order, one row of kOptions each
+// (the table says what an option is, which tool takes it and what it takes); reference command lines never start with
+// `--`, so they parse exactly as before.  The first word that is no option ends them and is <image>.  An invalid value or
+// combination prints one line to stderr and exits with status 2 before anything touches the GPU.
 #pragma once
 
 #include <cctype>
@@ -62,307 +47,225 @@ struct FilterArgs {
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
 
-// a finite number > 0, or exit 2
-inline double positive_option(const char* prog, const std::string& opt, const std::string& v) {
-    char* end = nullptr;
-    const double x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
-    if (v.empty() || *end != '\0' || !std::isfinite(x) || !(x > 0)) {
-        std::cerr << prog << ": " << opt << " takes a finite number > 0, got '" << v << "'" << std::endl;
-        std::exit(2);
+enum class Tool { Enhance = 1, Denoise = 2 };
+constexpr int kEnhance = (int)Tool::Enhance, kDenoise = (int)Tool::Denoise, kBoth = kEnhance | kDenoise;
+
+// what an option takes.  A flag is the word alone, `--flag=...` is refused; FlagAnySuffix also claims every other word
+// that starts with its name (and refuses it).  The numbers are finite doubles: any, > 0, >= 0, in [lo, hi], in (lo, hi];
+// Integer is a whole number in [lo, hi]; Word is one of `words`; FileName is a word that does not start with `--`; Region
+// is MASK:w1,w2,... split at the last `:`, finite weights.
+enum class Takes { Flag, FlagAnySuffix, Finite, Positive, NonNegative, Closed, HalfOpen, Integer, Word, FileName, Region };
+
+struct Word {
+    const char* word;
+    int value;
+};
+struct Value {  // a parsed value: the number (or the word's constant), the text as given, the region
+    double x = 0;
+    std::string text;
+    FilterArgs::Region region;
+};
+
+struct Option {
+    const char* name;
+    const char* what;  // one line on what it does
+    int tools;         // kEnhance, kDenoise or kBoth
+    Takes takes;
+    double lo, hi;      // Closed, HalfOpen, Integer
+    const Word* words;  // Word: ends with {nullptr, 0}
+    void (*set)(FilterArgs&, const Value&);  // where the value goes
+    const char* takesText;      // "<this> takes ...": the refusal of a bad value ends ", got '<value>'"
+    const char* elsewhereText;  // the other tool's refusal: "<word> is not supported here: <this>"
+    bool elsewhereSaysName = false;  // ... with the option's name in place of the word as given (--deep=1 reads --deep)
+};
+
+#define NLECLI_STR2(x) #x
+#define NLECLI_STR(x) NLECLI_STR2(x)
+
+inline const Word kSamplers[] = {{"grid", NLE_SAMPLER_GRID}, {"farthest", NLE_SAMPLER_FARTHEST}, {"residual", NLE_SAMPLER_RESIDUAL},
+                                 {nullptr, 0}};
+inline const Word kPrefilters[] = {{"bilateral", NLE_PREFILTER_BILATERAL}, {"nlm", NLE_PREFILTER_NLM}, {nullptr, 0}};
+inline const char kRegionElsewhere[] = "region edits give layer weights, which this tool does not take";
+inline const char kNystromTakes[] = "--nystrom-report takes no value and --nystrom-map takes a file name";
+inline const char kNystromElsewhere[] = "the residual report belongs to enhance";
+inline const char kTonemapElsewhere[] = "--tonemap (HDR tone mapping) is built for enhance only";
+inline const char kDetailElsewhere[] = "the detail options weigh layers, which this tool does not take";
+inline const char kDenoiseElsewhere[] = "the pre-filter and the MSE-guided shrinkage belong to denoise";
+
+// One row per option.  What holds between options (--noise-sigma needs ..., --exact does not combine with ...) is the
+// ordered list in parse(), after the loop.
+inline const Option kOptions[] = {
+    {"--patch-radius", "patch affinities of radius R (NLEFilter::patchRadius)", kBoth, Takes::Integer, 0, NLE_PATCH_RADIUS_MAX, nullptr,
+     [](FilterArgs& a, const Value& v) { a.patchRadius = (int)v.x; },
+     "--patch-radius takes an integer in [0, " NLECLI_STR(NLE_PATCH_RADIUS_MAX) "]", ""},
+    {"--sampler", "how the Nystrom samples are chosen (NLEFilter::sampler)", kBoth, Takes::Word, 0, 0, kSamplers,
+     [](FilterArgs& a, const Value& v) { a.sampler = (int)v.x; }, "--sampler takes 'grid', 'farthest' or 'residual'", ""},
+    {"--exact", "the exact, Nystrom-free filter (NLEFilter::exact)", kBoth, Takes::Flag, 0, 0, nullptr,
+     [](FilterArgs& a, const Value&) { a.exact = true; }, "--exact takes no value", ""},
+    {"--chroma", "chroma-aware affinities of bandwidth HC (NLEFilter::chromaBandwidth)", kEnhance, Takes::Positive, 0, 0, nullptr,
+     [](FilterArgs& a, const Value& v) { a.chroma = v.x; }, "--chroma takes a finite number > 0 (the chroma bandwidth)",
+     "the a and b planes are what this tool estimates"},
+    {"--region", "a region edit (NLEFilter::enhanceRegions): MASK is any image the readers decode, its first channel the stroke; as "
+                 "many weights as positional ones, which are then the background's; up to NLE_REGION_MAX times",
+     kEnhance, Takes::Region, 0, 0, nullptr, [](FilterArgs& a, const Value& v) { a.regions.push_back(v.region); },
+     "--region takes MASK:w1,w2,... (an image and finite weights)", kRegionElsewhere},
+    {"--region-spread", "how far a stroke spreads (enhanceRegions' spread)", kEnhance, Takes::Positive, 0, 0, nullptr,
+     [](FilterArgs& a, const Value& v) { a.regionSpread = v.x; }, "--region-spread takes a finite number > 0", kRegionElsewhere},
+    {"--region-floor", "the membership floor of the background (enhanceRegions' floor)", kEnhance, Takes::Positive, 0, 0, nullptr,
+     [](FilterArgs& a, const Value& v) { a.regionFloor = v.x; }, "--region-floor takes a finite number > 0", kRegionElsewhere},
+    {"--nystrom-report", "one more stdout line: the Nystrom residual of the sample grid (NLEFilter::nystromResidual)", kEnhance,
+     Takes::Flag, 0, 0, nullptr, [](FilterArgs& a, const Value&) { a.nystromReport = true; }, kNystromTakes, kNystromElsewhere},
+    {"--nystrom-map", "the residual map as an 8-bit grey image, written to FILE", kEnhance, Takes::FileName, 0, 0, nullptr,
+     [](FilterArgs& a, const Value& v) { a.nystromMap = v.text; }, kNystromTakes, kNystromElsewhere},
+    {"--deep", "deep colour: the input is read with imread16, the result is a 16-bit PNG", kEnhance, Takes::Flag, 0, 0, nullptr,
+     [](FilterArgs& a, const Value&) { a.deep = true; }, "--deep takes no value", "deep colour (16 bit) is built for enhance only", true},
+    {"--tonemap", "HDR tone mapping (NLEFilter::toneMap): the input is read with imreadHDR, the weights are the layer weights -- "
+                  "the last one is the base compression -- and the result is a 16-bit PNG",
+     kEnhance, Takes::FlagAnySuffix, 0, 0, nullptr, [](FilterArgs& a, const Value&) { a.tonemap = true; },
+     "--tonemap takes no value and --tonemap-saturation takes a number", kTonemapElsewhere},
+    {"--tonemap-saturation", "toneMap's colour saturation", kEnhance, Takes::HalfOpen, 0, 2, nullptr,
+     [](FilterArgs& a, const Value& v) { a.tonemapSaturation = v.x; }, "--tonemap-saturation takes a finite number in (0, 2]",
+     kTonemapElsewhere},
+    {"--residual-weight", "the weight of the out-of-span layer (nle::DetailOptions of enhance / toneMap)", kEnhance, Takes::Finite, 0, 0,
+     nullptr, [](FilterArgs& a, const Value& v) { a.detail.residualWeight = v.x; }, "--residual-weight takes a finite number",
+     kDetailElsewhere},
+    {"--detail-gain", "the detail curve's gain below --detail-sigma (nle::DetailOptions)", kEnhance, Takes::Closed, 0, NLE_DETAIL_GAIN_MAX,
+     nullptr, [](FilterArgs& a, const Value& v) { a.detail.gain = v.x; },
+     "--detail-gain takes a finite number in [0, " NLECLI_STR(NLE_DETAIL_GAIN_MAX) "]", kDetailElsewhere},
+    {"--detail-sigma", "the amplitude the detail curve's gain acts below (nle::DetailOptions)", kEnhance, Takes::NonNegative, 0, 0, nullptr,
+     [](FilterArgs& a, const Value& v) { a.detail.sigma = v.x; }, "--detail-sigma takes a finite number >= 0", kDetailElsewhere},
+    {"--prefilter", "the pre-filter of the MSE-guided denoiser (nle::DenoiseOptions)", kDenoise, Takes::Word, 0, 0, kPrefilters,
+     [](FilterArgs& a, const Value& v) { a.denoise.prefilter = (int)v.x; }, "--prefilter takes 'bilateral' or 'nlm'", kDenoiseElsewhere},
+    {"--glide", "shrink every plane by the power the MSE estimate picks; the positional shrink factor is the upper end of the search",
+     kDenoise, Takes::Flag, 0, 0, nullptr, [](FilterArgs& a, const Value&) { a.denoise.glide = true; }, "--glide takes no value",
+     kDenoiseElsewhere},
+    {"--noise-sigma", "the noise level of every plane, in place of the estimate", kDenoise, Takes::NonNegative, 0, 0, nullptr,
+     [](FilterArgs& a, const Value& v) { a.denoise.noiseSigma = v.x; }, "--noise-sigma takes a finite number >= 0", kDenoiseElsewhere},
+    {"--nlm-h", "the NLM pre-filter's h, in place of the table's", kDenoise, Takes::Positive, 0, 0, nullptr,
+     [](FilterArgs& a, const Value& v) { a.denoise.nlmH = v.x; }, "--nlm-h takes a finite number > 0", kDenoiseElsewhere},
+};
+
+// every refusal: one line on stderr, status 2
+[[noreturn]] inline void refuse(const char* prog, const std::string& text) {
+    std::cerr << prog << ": " << text << std::endl;
+    std::exit(2);
+}
+
+// the row that claims `word`: its name, a flag's `name=...`, or any other word that starts with a FlagAnySuffix name
+inline const Option* find_option(const std::string& word) {
+    for (const Option& o : kOptions)
+        if (word == o.name) return &o;
+    for (const Option& o : kOptions) {
+        if (o.takes == Takes::Flag && word.rfind(std::string(o.name) + "=", 0) == 0) return &o;
+        if (o.takes == Takes::FlagAnySuffix && word.rfind(o.name, 0) == 0) return &o;
     }
-    return x;
+    return nullptr;
+}
+
+// the whole of `v` as a number the row takes
+inline bool number(const Option& o, const std::string& v, double* x) {
+    char* end = nullptr;
+    if (o.takes == Takes::Integer) {
+        const long r = v.empty() ? -1 : std::strtol(v.c_str(), &end, 10);
+        *x = (double)r;
+        return !v.empty() && *end == '\0' && r >= o.lo && r <= o.hi;
+    }
+    *x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+    if (v.empty() || *end != '\0' || !std::isfinite(*x)) return false;
+    switch (o.takes) {
+        case Takes::Positive: return *x > 0;
+        case Takes::NonNegative: return !(*x < 0);
+        case Takes::Closed: return !(*x < o.lo || *x > o.hi);
+        case Takes::HalfOpen: return *x > o.lo && !(*x > o.hi);
+        default: return true;
+    }
+}
+
+// MASK:w1,w2,... split at the last `:`
+inline bool region(const std::string& v, FilterArgs::Region* r) {
+    static const Option weight = {"", "", 0, Takes::Finite, 0, 0, nullptr, nullptr, "", ""};
+    const size_t colon = v.rfind(':');
+    if (colon == std::string::npos || colon == 0 || colon + 1 >= v.size()) return false;
+    r->mask = v.substr(0, colon);
+    const std::string list = v.substr(colon + 1) + ",";
+    for (size_t p = 0, q; (q = list.find(',', p)) != std::string::npos; p = q + 1) {
+        double x;
+        if (!number(weight, list.substr(p, q - p), &x)) return false;
+        r->weights.push_back(x);
+    }
+    return true;
 }
 
 // false (after printing the usage line to stderr) when fewer than `min_argc` arguments were given
-// allow_chroma: the tool takes `--chroma HC` (enhance); otherwise the option is refused (denoise estimates a and b)
-// allow_regions: the tool takes the region options (enhance); otherwise they are refused (denoise has no layer weights)
-// allow_nystrom: the tool takes `--nystrom-report` / `--nystrom-map FILE` (enhance); otherwise they are refused
-// allow_deep: the tool takes `--deep` (enhance); otherwise it is refused (denoise has no 16-bit path)
-// allow_tonemap: the tool takes `--tonemap` / `--tonemap-saturation S` (enhance); otherwise they are refused
-// allow_detail: the tool takes `--residual-weight WR` / `--detail-gain A` / `--detail-sigma S` (enhance); otherwise refused
-// allow_denoise: the tool takes `--prefilter` / `--glide` / `--noise-sigma` / `--nlm-h` (denoise); otherwise they are refused
-inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allow_chroma = false,
-                  bool allow_regions = false, bool allow_nystrom = false, bool allow_deep = false,
-                  bool allow_tonemap = false, bool allow_detail = false, bool allow_denoise = false) {
+inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool) {
+    const char* prog = argv[0];
     std::vector<char*> shifted;
-    int first = 1;  // the first argument after the leading options
-    bool spreadGiven = false, floorGiven = false, saturationGiven = false;
-    std::string detailGiven;  // the last of --residual-weight / --detail-gain / --detail-sigma seen
-    bool noiseSigmaGiven = false, nlmHGiven = false;
+    std::vector<const Option*> given;  // the options read, in their order
+    int first = 1;                     // the first argument after the leading options
     while (first < argc) {
-        const std::string opt = argv[first];
-        if (opt == "--exact") {
-            a->exact = true;
-            first += 1;
-            continue;
+        const std::string word = argv[first];
+        const Option* o = find_option(word);
+        if (!o) break;
+        if (!(o->tools & (int)tool))
+            refuse(prog, (o->elsewhereSaysName ? o->name : word) + " is not supported here: " + o->elsewhereText);
+        const bool flag = o->takes == Takes::Flag || o->takes == Takes::FlagAnySuffix;
+        Value v;
+        v.text = flag ? word : first + 1 < argc ? argv[first + 1] : "";
+        std::string got = v.text;
+        bool ok = false;
+        switch (o->takes) {
+            case Takes::Flag:
+            case Takes::FlagAnySuffix: ok = word == o->name; break;
+            case Takes::Word:
+                for (const Word* w = o->words; w->word && !ok; ++w)
+                    if (v.text == w->word) v.x = w->value, ok = true;
+                break;
+            case Takes::FileName:
+                ok = !v.text.empty() && v.text.rfind("--", 0) != 0;
+                got = word + " " + v.text;
+                break;
+            case Takes::Region: ok = region(v.text, &v.region); break;
+            default: ok = number(*o, v.text, &v.x);
         }
-        if (opt.rfind("--exact=", 0) == 0) {
-            std::cerr << argv[0] << ": --exact takes no value, got '" << opt << "'" << std::endl;
-            std::exit(2);
-        }
-        if (opt == "--deep" || opt.rfind("--deep=", 0) == 0) {
-            if (!allow_deep) {
-                std::cerr << argv[0] << ": --deep is not supported here: deep colour (16 bit) is built for enhance only" << std::endl;
-                std::exit(2);
-            }
-            if (opt != "--deep") {
-                std::cerr << argv[0] << ": --deep takes no value, got '" << opt << "'" << std::endl;
-                std::exit(2);
-            }
-            a->deep = true;
-            first += 1;
-            continue;
-        }
-        if (opt.rfind("--tonemap", 0) == 0) {
-            if (!allow_tonemap) {
-                std::cerr << argv[0] << ": " << opt << " is not supported here: --tonemap (HDR tone mapping) is built for enhance only"
-                          << std::endl;
-                std::exit(2);
-            }
-            if (opt == "--tonemap") {
-                a->tonemap = true;
-                first += 1;
-                continue;
-            }
-            if (opt != "--tonemap-saturation") {
-                std::cerr << argv[0] << ": --tonemap takes no value and --tonemap-saturation takes a number, got '" << opt << "'"
-                          << std::endl;
-                std::exit(2);
-            }
-            const std::string v = first + 1 < argc ? argv[first + 1] : "";
-            char* end = nullptr;
-            const double x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
-            if (v.empty() || *end != '\0' || !std::isfinite(x) || !(x > 0) || x > 2) {
-                std::cerr << argv[0] << ": --tonemap-saturation takes a finite number in (0, 2], got '" << v << "'" << std::endl;
-                std::exit(2);
-            }
-            a->tonemapSaturation = x;
-            saturationGiven = true;
-            first += 2;
-            continue;
-        }
-        if (opt == "--nystrom-report" || opt == "--nystrom-map" || opt.rfind("--nystrom-report=", 0) == 0) {
-            if (!allow_nystrom) {
-                std::cerr << argv[0] << ": " << opt << " is not supported here: the residual report belongs to enhance" << std::endl;
-                std::exit(2);
-            }
-            if (opt == "--nystrom-report") {
-                a->nystromReport = true;
-                first += 1;
-                continue;
-            }
-            const std::string file = first + 1 < argc ? argv[first + 1] : "";
-            if (opt != "--nystrom-map" || file.empty() || file.rfind("--", 0) == 0) {
-                std::cerr << argv[0] << ": --nystrom-report takes no value and --nystrom-map takes a file name, got '" << opt
-                          << (opt == "--nystrom-map" ? " " + file : "") << "'" << std::endl;
-                std::exit(2);
-            }
-            a->nystromMap = file;
-            first += 2;
-            continue;
-        }
-        if (opt == "--residual-weight" || opt == "--detail-gain" || opt == "--detail-sigma") {
-            if (!allow_detail) {
-                std::cerr << argv[0] << ": " << opt << " is not supported here: the detail options weigh layers, which this tool "
-                          << "does not take" << std::endl;
-                std::exit(2);
-            }
-            const std::string v = first + 1 < argc ? argv[first + 1] : "";
-            char* end = nullptr;
-            const double x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
-            const bool number = !v.empty() && *end == '\0' && std::isfinite(x);
-            if (opt == "--residual-weight") {
-                if (!number) {
-                    std::cerr << argv[0] << ": --residual-weight takes a finite number, got '" << v << "'" << std::endl;
-                    std::exit(2);
-                }
-                a->detail.residualWeight = x;
-            } else if (opt == "--detail-gain") {
-                if (!number || x < 0 || x > NLE_DETAIL_GAIN_MAX) {
-                    std::cerr << argv[0] << ": --detail-gain takes a finite number in [0, " << NLE_DETAIL_GAIN_MAX << "], got '" << v
-                              << "'" << std::endl;
-                    std::exit(2);
-                }
-                a->detail.gain = x;
-            } else {
-                if (!number || x < 0) {
-                    std::cerr << argv[0] << ": --detail-sigma takes a finite number >= 0, got '" << v << "'" << std::endl;
-                    std::exit(2);
-                }
-                a->detail.sigma = x;
-            }
-            detailGiven = opt;
-            first += 2;
-            continue;
-        }
-        if (opt == "--glide" || opt.rfind("--glide=", 0) == 0 || opt == "--prefilter" || opt == "--noise-sigma" || opt == "--nlm-h") {
-            if (!allow_denoise) {
-                std::cerr << argv[0] << ": " << opt << " is not supported here: the pre-filter and the MSE-guided shrinkage belong "
-                          << "to denoise" << std::endl;
-                std::exit(2);
-            }
-            if (opt.rfind("--glide", 0) == 0) {
-                if (opt != "--glide") {
-                    std::cerr << argv[0] << ": --glide takes no value, got '" << opt << "'" << std::endl;
-                    std::exit(2);
-                }
-                a->denoise.glide = true;
-                first += 1;
-                continue;
-            }
-            const std::string v = first + 1 < argc ? argv[first + 1] : "";
-            if (opt == "--prefilter") {
-                if (v != "bilateral" && v != "nlm") {
-                    std::cerr << argv[0] << ": --prefilter takes 'bilateral' or 'nlm', got '" << v << "'" << std::endl;
-                    std::exit(2);
-                }
-                a->denoise.prefilter = v == "nlm" ? NLE_PREFILTER_NLM : NLE_PREFILTER_BILATERAL;
-            } else if (opt == "--noise-sigma") {
-                char* end = nullptr;
-                const double x = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
-                if (v.empty() || *end != '\0' || !std::isfinite(x) || x < 0) {
-                    std::cerr << argv[0] << ": --noise-sigma takes a finite number >= 0, got '" << v << "'" << std::endl;
-                    std::exit(2);
-                }
-                a->denoise.noiseSigma = x;
-                noiseSigmaGiven = true;
-            } else {
-                a->denoise.nlmH = positive_option(argv[0], opt, v);
-                nlmHGiven = true;
-            }
-            first += 2;
-            continue;
-        }
-        const bool regionOpt = opt == "--region" || opt == "--region-spread" || opt == "--region-floor";
-        if (opt != "--patch-radius" && opt != "--sampler" && opt != "--chroma" && !regionOpt) break;
-        const std::string v = first + 1 < argc ? argv[first + 1] : "";
-        if (regionOpt) {
-            if (!allow_regions) {
-                std::cerr << argv[0] << ": " << opt << " is not supported here: region edits give layer weights, which this "
-                          << "tool does not take" << std::endl;
-                std::exit(2);
-            }
-            if (opt == "--region-spread") {
-                a->regionSpread = positive_option(argv[0], opt, v);
-                spreadGiven = true;
-            } else if (opt == "--region-floor") {
-                a->regionFloor = positive_option(argv[0], opt, v);
-                floorGiven = true;
-            } else {
-                const size_t colon = v.rfind(':');
-                FilterArgs::Region r;
-                bool ok = colon != std::string::npos && colon > 0 && colon + 1 < v.size();
-                if (ok) {
-                    r.mask = v.substr(0, colon);
-                    const std::string list = v.substr(colon + 1) + ",";
-                    for (size_t p = 0, q; ok && (q = list.find(',', p)) != std::string::npos; p = q + 1) {
-                        const std::string w = list.substr(p, q - p);
-                        char* end = nullptr;
-                        const double x = w.empty() ? 0.0 : std::strtod(w.c_str(), &end);
-                        ok = !w.empty() && *end == '\0' && std::isfinite(x);
-                        r.weights.push_back(x);
-                    }
-                }
-                if (!ok) {
-                    std::cerr << argv[0] << ": --region takes MASK:w1,w2,... (an image and finite weights), got '" << v << "'"
-                              << std::endl;
-                    std::exit(2);
-                }
-                if ((int)a->regions.size() == NLE_REGION_MAX) {
-                    std::cerr << argv[0] << ": --region can be given at most " << NLE_REGION_MAX << " times" << std::endl;
-                    std::exit(2);
-                }
-                a->regions.push_back(r);
-            }
-            first += 2;
-            continue;
-        }
-        if (opt == "--chroma") {
-            if (!allow_chroma) {
-                std::cerr << argv[0] << ": --chroma is not supported here: the a and b planes are what this tool estimates"
-                          << std::endl;
-                std::exit(2);
-            }
-            char* end = nullptr;
-            const double hc = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
-            if (v.empty() || *end != '\0' || !std::isfinite(hc) || !(hc > 0)) {
-                std::cerr << argv[0] << ": --chroma takes a finite number > 0 (the chroma bandwidth), got '" << v << "'"
-                          << std::endl;
-                std::exit(2);
-            }
-            a->chroma = hc;
-        } else if (opt == "--patch-radius") {
-            char* end = nullptr;
-            const long r = v.empty() ? -1 : std::strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end != '\0' || r < 0 || r > NLE_PATCH_RADIUS_MAX) {
-                std::cerr << argv[0] << ": --patch-radius takes an integer in [0, " << NLE_PATCH_RADIUS_MAX << "], got '" << v
-                          << "'" << std::endl;
-                std::exit(2);
-            }
-            a->patchRadius = (int)r;
-        } else {
-            if (v != "grid" && v != "farthest" && v != "residual") {
-                std::cerr << argv[0] << ": --sampler takes 'grid', 'farthest' or 'residual', got '" << v << "'" << std::endl;
-                std::exit(2);
-            }
-            a->sampler = v == "grid" ? NLE_SAMPLER_GRID : v == "farthest" ? NLE_SAMPLER_FARTHEST : NLE_SAMPLER_RESIDUAL;
-        }
-        first += 2;
+        if (!ok) refuse(prog, std::string(o->takesText) + ", got '" + got + "'");
+        if (o->takes == Takes::Region && (int)a->regions.size() == NLE_REGION_MAX)
+            refuse(prog, "--region can be given at most " NLECLI_STR(NLE_REGION_MAX) " times");
+        o->set(*a, v);
+        given.push_back(o);
+        first += flag ? 1 : 2;
     }
-    if (noiseSigmaGiven && !a->denoise.glide && a->denoise.prefilter != NLE_PREFILTER_NLM) {
-        std::cerr << argv[0] << ": --noise-sigma needs --glide or --prefilter nlm (nothing else uses a noise level)" << std::endl;
-        std::exit(2);
-    }
-    if (nlmHGiven && a->denoise.prefilter != NLE_PREFILTER_NLM) {
-        std::cerr << argv[0] << ": --nlm-h needs --prefilter nlm" << std::endl;
-        std::exit(2);
-    }
-    if (a->exact && (a->patchRadius != 0 || a->sampler != NLE_SAMPLER_GRID)) {
-        std::cerr << argv[0] << ": --exact uses no samples and single-pixel affinities: it does not combine with "
-                  << "--patch-radius R > 0, --sampler farthest or --sampler residual" << std::endl;
-        std::exit(2);
-    }
-    if (a->chroma != 0 && (a->exact || a->patchRadius > NLE_CHROMA_PATCH_RADIUS_MAX)) {
-        std::cerr << argv[0] << ": --chroma does not combine with --exact or with --patch-radius R > "
-                  << NLE_CHROMA_PATCH_RADIUS_MAX << std::endl;
-        std::exit(2);
-    }
-    if (!a->nystromMap.empty() && !a->nystromReport) {
-        std::cerr << argv[0] << ": --nystrom-map needs --nystrom-report" << std::endl;
-        std::exit(2);
-    }
-    if (a->nystromReport && a->exact) {
-        std::cerr << argv[0] << ": --nystrom-report and --nystrom-map do not combine with --exact: the exact filter has no "
-                  << "Nystrom extension" << std::endl;
-        std::exit(2);
-    }
-    if (a->deep && !a->regions.empty()) {
-        std::cerr << argv[0] << ": --deep does not combine with --region: region edits take an 8-bit image" << std::endl;
-        std::exit(2);
-    }
-    if (saturationGiven && !a->tonemap) {
-        std::cerr << argv[0] << ": --tonemap-saturation needs --tonemap" << std::endl;
-        std::exit(2);
-    }
-    if (a->tonemap && (a->chroma != 0 || !a->regions.empty() || a->deep || a->nystromReport)) {
-        std::cerr << argv[0] << ": --tonemap does not combine with --chroma, --region, --deep or --nystrom-report: those take "
-                  << "an 8-bit or 16-bit sRGB image" << std::endl;
-        std::exit(2);
-    }
-    if (a->detail.gain != 1 && !(a->detail.sigma > 0)) {
-        std::cerr << argv[0] << ": --detail-gain other than 1 needs --detail-sigma S > 0 (the amplitude the gain acts below)"
-                  << std::endl;
-        std::exit(2);
-    }
-    if (!detailGiven.empty() && !a->regions.empty()) {
-        std::cerr << argv[0] << ": " << detailGiven << " does not combine with --region: region edits have no residual layer "
-                  << "and no detail curve" << std::endl;
-        std::exit(2);
-    }
-    if ((spreadGiven || floorGiven) && a->regions.empty()) {
-        std::cerr << argv[0] << ": --region-spread and --region-floor need at least one --region" << std::endl;
-        std::exit(2);
-    }
+    // the name of the last option given among `names`, "" if none was
+    const auto last = [&](std::initializer_list<const char*> names) {
+        for (auto g = given.rbegin(); g != given.rend(); ++g)
+            for (const char* n : names)
+                if (std::string((*g)->name) == n) return std::string(n);
+        return std::string();
+    };
+    const auto is_given = [&](const char* name) { return !last({name}).empty(); };
+    // what holds between options, in the order the refusals have
+    if (is_given("--noise-sigma") && !a->denoise.glide && a->denoise.prefilter != NLE_PREFILTER_NLM)
+        refuse(prog, "--noise-sigma needs --glide or --prefilter nlm (nothing else uses a noise level)");
+    if (is_given("--nlm-h") && a->denoise.prefilter != NLE_PREFILTER_NLM) refuse(prog, "--nlm-h needs --prefilter nlm");
+    if (a->exact && (a->patchRadius != 0 || a->sampler != NLE_SAMPLER_GRID))
+        refuse(prog, "--exact uses no samples and single-pixel affinities: it does not combine with --patch-radius R > 0, "
+                     "--sampler farthest or --sampler residual");
+    if (a->chroma != 0 && (a->exact || a->patchRadius > NLE_CHROMA_PATCH_RADIUS_MAX))
+        refuse(prog, "--chroma does not combine with --exact or with --patch-radius R > " NLECLI_STR(NLE_CHROMA_PATCH_RADIUS_MAX));
+    if (!a->nystromMap.empty() && !a->nystromReport) refuse(prog, "--nystrom-map needs --nystrom-report");
+    if (a->nystromReport && a->exact)
+        refuse(prog, "--nystrom-report and --nystrom-map do not combine with --exact: the exact filter has no Nystrom extension");
+    if (a->deep && !a->regions.empty()) refuse(prog, "--deep does not combine with --region: region edits take an 8-bit image");
+    if (is_given("--tonemap-saturation") && !a->tonemap) refuse(prog, "--tonemap-saturation needs --tonemap");
+    if (a->tonemap && (a->chroma != 0 || !a->regions.empty() || a->deep || a->nystromReport))
+        refuse(prog, "--tonemap does not combine with --chroma, --region, --deep or --nystrom-report: those take an 8-bit or "
+                     "16-bit sRGB image");
+    if (a->detail.gain != 1 && !(a->detail.sigma > 0))
+        refuse(prog, "--detail-gain other than 1 needs --detail-sigma S > 0 (the amplitude the gain acts below)");
+    const std::string detailGiven = last({"--residual-weight", "--detail-gain", "--detail-sigma"});
+    if (!detailGiven.empty() && !a->regions.empty())
+        refuse(prog, detailGiven + " does not combine with --region: region edits have no residual layer and no detail curve");
+    if ((is_given("--region-spread") || is_given("--region-floor")) && a->regions.empty())
+        refuse(prog, "--region-spread and --region-floor need at least one --region");
     if (first > 1) {
         shifted.push_back(argv[0]);  // the rest parses as a reference command line
         for (int i = first; i < argc; ++i) shifted.push_back(argv[i]);
@@ -383,11 +286,9 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
         const std::string& o = a->output;
         std::string ext = o.size() >= 4 ? o.substr(o.size() - 4) : "";
         for (char& ch : ext) ch = (char)std::tolower((unsigned char)ch);
-        if (ext != ".png") {
-            std::cerr << argv[0] << ": " << (a->deep ? "--deep" : "--tonemap")
-                      << " writes a 16-bit PNG: the output name must end in .png, got '" << o << "'" << std::endl;
-            std::exit(2);
-        }
+        if (ext != ".png")
+            refuse(prog, std::string(a->deep ? "--deep" : "--tonemap") + " writes a 16-bit PNG: the output name must end in .png, got '" +
+                             o + "'");
     }
     int* ints[] = {&a->rowSamples, &a->colSamples, nullptr, nullptr, &a->sinkhornIters, &a->eigenVectors};
     double* reals[] = {nullptr, nullptr, &a->hx, &a->hy, nullptr, nullptr};
@@ -396,23 +297,14 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, bool allo
         else *reals[i] = std::stod(argv[3 + i]);
     }
     for (int i = 9; i < argc; ++i) a->extra.push_back(std::stod(argv[i]));
-    if (a->detail.active() && (int)a->extra.size() > NLE_REGION_LAYERS_MAX) {
-        std::cerr << argv[0] << ": " << detailGiven << " takes at most " << NLE_REGION_LAYERS_MAX << " weights, got "
-                  << a->extra.size() << std::endl;
-        std::exit(2);
-    }
+    const std::string most = " takes at most " NLECLI_STR(NLE_REGION_LAYERS_MAX) " weights, got " + std::to_string(a->extra.size());
+    if (a->detail.active() && (int)a->extra.size() > NLE_REGION_LAYERS_MAX) refuse(prog, detailGiven + most);
     if (!a->regions.empty()) {  // every region has the background's weight count
-        if ((int)a->extra.size() > NLE_REGION_LAYERS_MAX) {
-            std::cerr << argv[0] << ": --region takes at most " << NLE_REGION_LAYERS_MAX << " weights, got "
-                      << a->extra.size() << std::endl;
-            std::exit(2);
-        }
+        if ((int)a->extra.size() > NLE_REGION_LAYERS_MAX) refuse(prog, "--region" + most);
         for (const auto& r : a->regions)
-            if (r.weights.size() != a->extra.size()) {
-                std::cerr << argv[0] << ": --region " << r.mask << " has " << r.weights.size() << " weights, the command line "
-                          << "has " << a->extra.size() << std::endl;
-                std::exit(2);
-            }
+            if (r.weights.size() != a->extra.size())
+                refuse(prog, "--region " + r.mask + " has " + std::to_string(r.weights.size()) + " weights, the command line has " +
+                                 std::to_string(a->extra.size()));
     }
     return true;
 }

@@ -4,14 +4,13 @@
 // (the reference's usage line still lists four weights -- it was copied from enhance -- and is kept verbatim;
 // sigma color / sigma space are parsed as doubles and truncated to int by the NLEFilter signatures, :28-29,44-46).
 // Differences: headless (no imshow / waitKey, :50-51), BMP/PPM in and BMP/PPM/PNG out through nle/image_io.hpp.
-// New here, as leading options: --prefilter bilateral|nlm, --glide, --noise-sigma S, --nlm-h H (nle::DenoiseOptions;
-// cli_common.hpp).  With --glide the shrink factor is the upper end of the searched range and one more line is printed
-// before the banner: the noise level and the power k chosen for L, a and b.
+// New here: leading options; nlecli::kOptions (cli_common.hpp) lists them.  With --glide the shrink factor is the upper end
+// of the searched range and one more line is printed before the banner: the noise level and the power k chosen for L, a and b.
 #include "cli_common.hpp"
 
 int main(int argc, char* argv[]) {
     nlecli::FilterArgs a;
-    if (!nlecli::parse(argc, argv, 12, &a, false, false, false, false, false, false, /*allow_denoise=*/true)) return 0;  // usage: src/denoise.cpp:14-17 (exit code 0 on purpose)
+    if (!nlecli::parse(argc, argv, 12, &a, nlecli::Tool::Denoise)) return 0;  // usage: src/denoise.cpp:14-17 (exit code 0 on purpose)
     const int sigmaColor = (int)a.extra[0], sigmaSpace = (int)a.extra[1];
     const double shrinkFactor = a.extra[2];
     const nle::Image image = nlecli::load(a);

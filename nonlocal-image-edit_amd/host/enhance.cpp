@@ -3,22 +3,17 @@
 //           <# eigen vectors> <weight 1> [<weight 2> ...]
 // Differences: runs headless (no imshow / waitKey, src/enhance.cpp:48-49), reads BMP/PPM and writes
 // BMP/PPM/PNG through nle/image_io.hpp instead of OpenCV.  The hot path runs on the GPU through
-// libnle_hip.so.  New here: leading options (cli_common.hpp), among them the region edits `--region MASK:w1,w2,...`
-// (repeatable), `--region-spread T`, `--region-floor F`: the positional weights are then the background's; and
-// `--nystrom-report [--nystrom-map FILE]`: one more stdout line with the Nystrom residual of the sample grid (mean, max and
-// its pixel, share of pixels above 0.5) and the map as an 8-bit grey image, round(255 clamp(r, 0, 1)); and `--deep`: 16-bit
-// PNG in, 16-bit PNG out through the float Lab path (NLEFilter on a 16UC3 image), same banners; and `--tonemap
-// [--tonemap-saturation S]`: a Radiance or PFM file in, 16-bit PNG out through NLEFilter::trainForToneMapping / toneMap, the
-// weights being the layer weights (the last one compresses the base layer), same banners; and `--residual-weight WR`,
-// `--detail-gain A`, `--detail-sigma S`: nle::DetailOptions of enhance / toneMap (the out-of-span layer and the detail curve).
+// libnle_hip.so.  New here: leading options; nlecli::kOptions (cli_common.hpp) lists them.  With `--region` the positional
+// weights are the background's; `--nystrom-report` prints one more stdout line with the Nystrom residual of the sample grid
+// (mean, max and its pixel, share of pixels above 0.5) and `--nystrom-map FILE` writes the map as an 8-bit grey image,
+// round(255 clamp(r, 0, 1)); `--deep` and `--tonemap` print the same banners.
 #include <algorithm>
 
 #include "cli_common.hpp"
 
 int main(int argc, char* argv[]) {
     nlecli::FilterArgs a;
-    if (!nlecli::parse(argc, argv, 10, &a, /*allow_chroma=*/true, /*allow_regions=*/true, /*allow_nystrom=*/true,
-                       /*allow_deep=*/true, /*allow_tonemap=*/true, /*allow_detail=*/true)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
+    if (!nlecli::parse(argc, argv, 10, &a, nlecli::Tool::Enhance)) return 0;  // usage: src/enhance.cpp:15-18 (exit code 0 on purpose)
     const nle::Image image = nlecli::load(a);
     if (image.empty()) return 0;                        // src/enhance.cpp:34-37
     // the strokes: the first channel of every mask, read before anything touches the GPU

@@ -47,14 +47,51 @@ nle_filter* train_rows(nle_ctx* c, const NLEFilter& o, const Image& image, int r
     return train_step(c, o, in.L.f(), image.rows, image.cols, a, in.a.f(), in.b.f());
 }
 
-// rows [r0, r1) of `image` through filter f of ctx c into the same rows of `out` (:422-440 on the device): BGR -> Lab,
-// L -> float, apply, clamp + round to 8 bit, merge with a, b, Lab -> BGR
-void enhance_rows(nle_ctx* c, nle_filter* f, const Image& image, const Vec& fS, int r0, int r1, Image& out) {
+// One luminance edit per image kind.  The kind fixes the prologue and the epilogue; `op(d_x, d_y)` is the operator on the
+// plane: it fills the floats at d_y from those at d_x (nle_apply / nle_apply_rounded8, nle_apply_detail, nle_apply_regions)
+// and does its own check().
+// 8 bit, rows [r0, r1) of `image` on ctx c into the same rows of `out` (:422-440 on the device): BGR -> Lab, L -> float, op
+// (which clamps and rounds to 8 bit), merge with a, b, Lab -> BGR
+template <typename Op>
+void edit_rows(nle_ctx* c, const Image& image, int r0, int r1, Image& out, Op&& op) {
     const size_t n = (size_t)(r1 - r0) * image.cols;
     const LabPlanes in = lab_planes(c, image.ptr<unsigned char>(r0), n, true, false);
     Dev d_y(c, n * 4);
-    check(nle_apply_rounded8(f, in.L.f(), image.rows, image.cols, fS.data(), d_y.f()), c);  // :431-436
+    op(in.L.f(), d_y.f());
     lab_to_rows(c, in, d_y.f(), nullptr, nullptr, out, r0, r1);
+}
+
+// ... the whole image
+template <typename Op>
+Image edit_8bit(nle_ctx* c, const Image& image, Op&& op) {
+    Image out(image.rows, image.cols, NLE_8U, 3);
+    edit_rows(c, image, 0, image.rows, out, op);
+    return out;
+}
+
+// deep colour: float Lab in, op on the unrounded L, 16-bit codes out; nothing is rounded to 8 bit
+template <typename Op>
+Image edit_deep(nle_ctx* c, const Image& image, Op&& op) {
+    const Lab16Planes in = lab16_planes(c, image, true, false);
+    Dev d_y(c, image.total() * 4);
+    op(in.L.f(), d_y.f());
+    return lab16_to_image(c, in, d_y.f(), image.rows, image.cols);
+}
+
+// HDR: the unrounded log-luminance on the scale of the train (hi, range), op, then base compression and saturation
+template <typename Op>
+Image edit_hdr(nle_ctx* c, const Image& image, double hi, double range, DType base, DType saturation, Op&& op) {
+    const HdrPlanes in = hdr_planes(c, image, false, hi, range, true, false);
+    Dev d_y(c, image.total() * 4);
+    op(in.x.f(), d_y.f());
+    return hdr_to_image(c, in, d_y.f(), base, saturation, image.rows, image.cols);
+}
+
+// rows [r0, r1) through filter f of ctx c: the plain enhance of a rank's rows, or of all of them (:431-436)
+void enhance_rows(nle_ctx* c, nle_filter* f, const Image& image, const Vec& fS, int r0, int r1, Image& out) {
+    edit_rows(c, image, r0, r1, out, [&](const float* d_x, float* d_y) {
+        check(nle_apply_rounded8(f, d_x, image.rows, image.cols, fS.data(), d_y), c);
+    });
 }
 
 const char kDeepOneDevice[] = "Deep colour (16-bit images) runs on one device: unset NLE_DEVICES.";
@@ -231,17 +268,7 @@ void NLEFilter::trainForToneMapping(const Image& image, int nRowSamples, int nCo
 }
 
 Image NLEFilter::toneMap(const Image& image, const std::vector<DType>& weights, DType saturation) const {
-    if (image.channels() != 3 || image.depth() != NLE_32F) throw std::runtime_error("Can only tone-map a 32F RGB image.");
-    if (chromaBandwidth != 0) throw std::runtime_error(kHdrNoChroma);
-    if (!group_.empty()) throw std::runtime_error(kHdrOneDevice);
-    requireSize(image.total(), kTrainedSize);
-    if (!(hdrRange_ > 0)) throw std::runtime_error("toneMap needs a filter trained by trainForToneMapping.");
-    if (weights.empty()) throw std::runtime_error("toneMap needs at least one layer weight.");
-    const Vec fS = transformEigenValues(eigvals(), weights);
-    const HdrPlanes in = hdr_planes(ctx_, image, false, hdrHi_, hdrRange_, true, false);
-    Dev d_y(ctx_, image.total() * 4);
-    check(nle_apply(f_, in.x.f(), image.rows, image.cols, fS.data(), d_y.f()), ctx_);
-    return hdr_to_image(ctx_, in, d_y.f(), weights.back(), saturation, image.rows, image.cols);  // c = f(1), the base weight
+    return toneMap(image, weights, saturation, DetailOptions());
 }
 
 void NLEFilter::trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy,
@@ -405,14 +432,11 @@ Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights) 
     refuse_hdr(image, "enhance");
     if (image.channels() != 3) throw std::runtime_error("Can only enhance RGB image.");
     const int H = image.rows, W = image.cols;
-    if (is_deep(image)) {  // deep colour: float Lab in, the filter on the unrounded L, 16-bit codes out; nothing is rounded to 8 bit
+    if (is_deep(image)) {
         if (!group_.empty()) throw std::runtime_error(kDeepOneDevice);
         requireSize(image.total(), kTrainedSize);
         const Vec fS = transformEigenValues(eigvals(), weights);
-        const Lab16Planes in = lab16_planes(ctx_, image, true, false);
-        Dev d_y(ctx_, image.total() * 4);
-        check(nle_apply(f_, in.L.f(), H, W, fS.data(), d_y.f()), ctx_);
-        return lab16_to_image(ctx_, in, d_y.f(), H, W);
+        return edit_deep(ctx_, image, [&](const float* d_x, float* d_y) { check(nle_apply(f_, d_x, H, W, fS.data(), d_y), ctx_); });
     }
     DeviceGroup* g = nullptr;
     if (!group_.empty()) {  // trained over NLE_DEVICES: every rank its rows
@@ -442,6 +466,15 @@ int detail_layers(const std::vector<DType>& weights) {
     return (int)weights.size();
 }
 
+// nle_apply_detail as the operator of a luminance edit (the weight count is refused here, before the edit begins)
+auto detail_op(nle_ctx* c, nle_filter* f, const Image& image, const std::vector<DType>& weights, const DetailOptions& detail,
+               int out_kind) {
+    const int H = image.rows, W = image.cols, L = detail_layers(weights);
+    return [=, &weights](const float* d_x, float* d_y) {
+        check(nle_apply_detail(f, d_x, H, W, L, weights.data(), detail.residualWeight, detail.gain, detail.sigma, out_kind, d_y), c);
+    };
+}
+
 }  // namespace
 
 Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights, const DetailOptions& detail) const {
@@ -451,38 +484,29 @@ Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights, 
         throw std::runtime_error("Can only enhance RGB image.");
     if (!group_.empty()) throw std::runtime_error(kDetailOneDevice);
     requireSize(image.total(), kTrainedSize);
-    const int H = image.rows, W = image.cols, L = detail_layers(weights);
-    Dev d_y(ctx_, image.total() * 4);
-    if (is_deep(image)) {  // enhance's deep body with nle_apply_detail in place of nle_apply: the unrounded L, nothing rounded
-        const Lab16Planes in = lab16_planes(ctx_, image, true, false);
-        check(nle_apply_detail(f_, in.L.f(), H, W, L, weights.data(), detail.residualWeight, detail.gain, detail.sigma,
-                               NLE_REGION_OUT_F32, d_y.f()), ctx_);
-        return lab16_to_image(ctx_, in, d_y.f(), H, W);
-    }
-    // enhance_rows' body with nle_apply_detail in place of nle_apply_rounded8
-    const LabPlanes in = lab_planes(ctx_, image.ptr<unsigned char>(), image.total(), true, false);
-    check(nle_apply_detail(f_, in.L.f(), H, W, L, weights.data(), detail.residualWeight, detail.gain, detail.sigma,
-                           NLE_REGION_OUT_ROUNDED8, d_y.f()), ctx_);
-    Image out(H, W, NLE_8U, 3);
-    lab_to_rows(ctx_, in, d_y.f(), nullptr, nullptr, out, 0, H);
-    return out;
+    if (is_deep(image)) return edit_deep(ctx_, image, detail_op(ctx_, f_, image, weights, detail, NLE_REGION_OUT_F32));
+    return edit_8bit(ctx_, image, detail_op(ctx_, f_, image, weights, detail, NLE_REGION_OUT_ROUNDED8));
 }
 
+// inactive options: the plain toneMap, nle_apply under the transformed eigenvalues (the one-device and the weight-count
+// refusals keep each form's own text)
 Image NLEFilter::toneMap(const Image& image, const std::vector<DType>& weights, DType saturation,
                          const DetailOptions& detail) const {
-    if (!detail.active()) return toneMap(image, weights, saturation);
+    const bool plain = !detail.active();
     if (image.channels() != 3 || image.depth() != NLE_32F) throw std::runtime_error("Can only tone-map a 32F RGB image.");
     if (chromaBandwidth != 0) throw std::runtime_error(kHdrNoChroma);
-    if (!group_.empty()) throw std::runtime_error(kDetailOneDevice);
+    if (!group_.empty()) throw std::runtime_error(plain ? kHdrOneDevice : kDetailOneDevice);
     requireSize(image.total(), kTrainedSize);
     if (!(hdrRange_ > 0)) throw std::runtime_error("toneMap needs a filter trained by trainForToneMapping.");
-    const int L = detail_layers(weights);
-    // toneMap's body with nle_apply_detail in place of nle_apply: the unrounded log-luminance
-    const HdrPlanes in = hdr_planes(ctx_, image, false, hdrHi_, hdrRange_, true, false);
-    Dev d_y(ctx_, image.total() * 4);
-    check(nle_apply_detail(f_, in.x.f(), image.rows, image.cols, L, weights.data(), detail.residualWeight, detail.gain,
-                           detail.sigma, NLE_REGION_OUT_F32, d_y.f()), ctx_);
-    return hdr_to_image(ctx_, in, d_y.f(), weights.back(), saturation, image.rows, image.cols);  // c = the base weight
+    if (!plain) {
+        const auto op = detail_op(ctx_, f_, image, weights, detail, NLE_REGION_OUT_F32);
+        return edit_hdr(ctx_, image, hdrHi_, hdrRange_, weights.back(), saturation, op);  // c = f(1): the base weight
+    }
+    if (weights.empty()) throw std::runtime_error("toneMap needs at least one layer weight.");
+    const Vec fS = transformEigenValues(eigvals(), weights);
+    return edit_hdr(ctx_, image, hdrHi_, hdrRange_, weights.back(), saturation, [&](const float* d_x, float* d_y) {
+        check(nle_apply(f_, d_x, image.rows, image.cols, fS.data(), d_y), ctx_);
+    });
 }
 
 Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& strokes,
@@ -522,15 +546,12 @@ Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& st
         if (!(sum > 0)) throw std::runtime_error("Stroke " + std::to_string(m + 1) + " is empty (no byte >= 128).");
         scale[m] = (double)np / sum;
     }
-    // enhance's body (:422-440 on the device) with nle_apply_regions in place of nle_apply_rounded8
-    Dev d_s(ctx_, planes.size() * 4), d_y(ctx_, np * 4);
+    Dev d_s(ctx_, planes.size() * 4);
     check(nle_dev_upload(ctx_, d_s.p, planes.data(), planes.size() * 4), ctx_);
-    const LabPlanes in = lab_planes(ctx_, image.ptr<unsigned char>(), np, true, false);
-    check(nle_apply_regions(f_, in.L.f(), image.rows, image.cols, L, d_s.f(), M, scale.data(), spread, floor, Wt.data(),
-                            NLE_REGION_OUT_ROUNDED8, d_y.f()), ctx_);
-    Image out(image.rows, image.cols, NLE_8U, 3);
-    lab_to_rows(ctx_, in, d_y.f(), nullptr, nullptr, out, 0, image.rows);
-    return out;
+    return edit_8bit(ctx_, image, [&](const float* d_x, float* d_y) {
+        check(nle_apply_regions(f_, d_x, image.rows, image.cols, L, d_s.f(), M, scale.data(), spread, floor, Wt.data(),
+                                NLE_REGION_OUT_ROUNDED8, d_y), ctx_);
+    });
 }
 
 NLEFilter::Residual NLEFilter::nystromResidual(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int form,

@@ -174,14 +174,16 @@ def kron_ref(y, hx, hy, X, s_lower=False):
     gr = torch.from_numpy(np.ascontiguousarray(y[:, 0] if row_kind else np.zeros(H)))
     gc = torch.from_numpy(np.ascontiguousarray(np.zeros(W) if row_kind else y[0]))
     sw, pw = 1.0 / (hx * hx), 1.0 / (hy * hy)
+    def both_factors(Z):
+        m = Z.shape[1]
+        Z = factor_apply(gr, sw, pw, Z.reshape(H, W * m))
+        Z = Z.reshape(H, W, m).permute(1, 0, 2).reshape(W, H * m)
+        return factor_apply(gc, sw, pw, Z).reshape(W, H, m).permute(1, 0, 2).reshape(H * W, m).numpy()
+    # K X in products of its own: a host BLAS may round a column differently when the matrix it stands in has other
+    # columns beside it, and K X must not depend on which S is asked for
     Xt = torch.from_numpy(X)
-    Z = torch.cat([Xt, torch.ones(H * W, 1, dtype=torch.float64) if s_lower else Xt.abs()], dim=1)
-    m = Z.shape[1]
-    Z = factor_apply(gr, sw, pw, Z.reshape(H, W * m))
-    Z = Z.reshape(H, W, m).permute(1, 0, 2).reshape(W, H * m)
-    Z = factor_apply(gc, sw, pw, Z).reshape(W, H, m).permute(1, 0, 2).reshape(H * W, m).numpy()
-    nc = X.shape[1]
-    return Z[:, :nc], (np.repeat(Z[:, nc:], nc, axis=1) if s_lower else Z[:, nc:])
+    KX, S = both_factors(Xt), both_factors(torch.ones(H * W, 1, dtype=torch.float64) if s_lower else Xt.abs())
+    return KX, (np.repeat(S, X.shape[1], axis=1) if s_lower else S)
 
 
 def rows_ref(y, hx, hy, rows, X):
