@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "launch.h"
 #include "lab8_fixed.h"
 
 namespace nlek {
@@ -207,12 +208,8 @@ hipError_t bilateral8(hipStream_t s, const float* d_src, int H, int W, int radiu
     if (radius < 1 || radius > bilateral8_max_radius()) return hipErrorInvalidValue;
     const int d = 2 * radius + 1;
     const size_t shm = ((size_t)(kBfTx + 2 * radius) * (kBfTy + 2 * radius) + (size_t)d * d + 256) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_bilateral8),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bilateral8, dim3((unsigned)((W + kBfTx - 1) / kBfTx), (unsigned)((H + kBfTy - 1) / kBfTy)),
-                       dim3(kBfTx, kBfTy), shm, s, d_src, H, W, radius, d_space_w, d_colour_w, d_dst);
-    return hipGetLastError();
+    return launch(k_bilateral8, dim3((unsigned)((W + kBfTx - 1) / kBfTx), (unsigned)((H + kBfTy - 1) / kBfTy)), dim3(kBfTx, kBfTy), shm,
+                  s, d_src, H, W, radius, d_space_w, d_colour_w, d_dst);
 }
 
 // per-block min / max of the first ncols columns of X (M x ld): out[block][2*ncols]

@@ -17,6 +17,7 @@
 //                     block rows on k_gemm64s (fp64 MFMA).
 // The eigenvectors of T for the wanted eigenvalues come from the host's inverse iteration (eigen_tridiag.cpp, O(n k)).
 #include "kernels.h"
+#include "launch.h"
 #include "handoff.h"
 
 #include <algorithm>
@@ -412,22 +413,11 @@ hipError_t sytrd_dist(hipStream_t s, int n, int G, const double* d_A, const doub
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(d_status, 0, sizeof(int), s);
     if (e != hipSuccess) return e;
-#define NLE_SYW(R)                                                                                                          \
-    {                                                                                                                       \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_sytrd_wave<R>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)shm);                                                                                  \
-        if (e != hipSuccess) return e;                                                                                      \
-        hipLaunchKernelGGL((k_sytrd_wave<R>), dim3(G), dim3(kSyT), shm, s, n, G, cw, ldc, d_A, d_diag_add, d_pub, d_d, d_e,  \
-                           d_status);                                                                                       \
-    }
-    if (rpl == 5) NLE_SYW(5)
-    else if (rpl == 7) NLE_SYW(7)
-    else if (rpl == 10) NLE_SYW(10)
-    else if (rpl == 13) NLE_SYW(13)
-    else if (rpl == 15) NLE_SYW(15)
-    else NLE_SYW(18)
-#undef NLE_SYW
-    return hipGetLastError();
+    e = hipErrorInvalidValue;  // sytrd_rpl yields listed values only for n <= sytrd_max_n() (64 * 18 rows)
+    dispatch_values<5, 7, 10, 13, 15, 18>(rpl, [&](auto r) {
+        e = launch(k_sytrd_wave<decltype(r)::value>, dim3(G), dim3(kSyT), shm, s, n, G, cw, ldc, d_A, d_diag_add, d_pub, d_d, d_e, d_status);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------------------------------------ eigenvalues of T

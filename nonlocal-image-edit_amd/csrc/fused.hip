@@ -13,6 +13,7 @@
 // Sample pixels (whose rows are the exact V_A rows, :275 top block) are skipped by the
 // N-sized kernels and handled in fp64 by k_sink_update / the host.
 #include "kernels.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -155,33 +156,12 @@ hipError_t sink_pass(hipStream_t s, int mode, const float* d_lum, GridSpec gs, c
                      double* d_ybuf, double* d_partial) {
     const int pp = (p + 15) & ~15;
     const int grid = sink_grid(M);
-#define NLE_SP_CASE(PPV)                                                                                  \
-    case PPV:                                                                                             \
-        hipLaunchKernelGGL((k_sink_pass<PPV>), dim3(grid), dim3(256), 0, s, mode, d_lum, gs, d_samples,  \
-                           d_w, nsw, npw, (unsigned)pix0, M, eps, d_ybuf, d_partial);                     \
-        break;
-    switch (pp) {
-        NLE_SP_CASE(16)
-        NLE_SP_CASE(32)
-        NLE_SP_CASE(48)
-        NLE_SP_CASE(64)
-        NLE_SP_CASE(80)
-        NLE_SP_CASE(96)
-        NLE_SP_CASE(112)
-        NLE_SP_CASE(128)
-        NLE_SP_CASE(144)
-        NLE_SP_CASE(160)
-        NLE_SP_CASE(176)
-        NLE_SP_CASE(192)
-        NLE_SP_CASE(208)
-        NLE_SP_CASE(224)
-        NLE_SP_CASE(240)
-        NLE_SP_CASE(256)
-        default:
-            return hipErrorInvalidValue;
-    }
-#undef NLE_SP_CASE
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;  // p outside 1 .. 256: no launch
+    dispatch_values<16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(pp, [&](auto ppv) {
+        e = launch(k_sink_pass<decltype(ppv)::value>, dim3(grid), dim3(256), 0, s, mode, d_lum, gs, d_samples, d_w, nsw, npw, pix0, M, eps,
+                   d_ybuf, d_partial);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------ Sinkhorn update (p-, r-sized)
@@ -423,19 +403,6 @@ __global__ __launch_bounds__(256) void k_gram64_reduce(const double* __restrict_
     tiles[e] = (s0 + s1) + (s2 + s3);
 }
 
-template <int TPW>
-static hipError_t launch_gram64(hipStream_t s, dim3 grid, size_t shm, const float* d_lum, GridSpec gs,
-                                const Sample4* d_samples, int p, int ld16, int ldz, float nsw, float npw,
-                                long long pix0, long long M, const double* d_c, int fl, int ntiles,
-                                double* d_partial) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gram64<TPW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_gram64<TPW>), grid, dim3(256), shm, s, d_lum, gs, d_samples, p, ld16, ldz, nsw, npw,
-                       (unsigned)pix0, M, d_c, fl, ntiles, d_partial);
-    return hipGetLastError();
-}
-
 hipError_t gram64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, float nsw,
                   float npw, long long pix0, long long M, const double* d_c, double* d_partial, double* d_tiles) {
     if (p > 256) return hipErrorInvalidValue;
@@ -455,17 +422,11 @@ hipError_t gram64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4*
         }
     const int groups = (ntiles + 4 * tpw - 1) / (4 * tpw);
     const dim3 grid((unsigned)nchunks, (unsigned)groups);
-    hipError_t e;
-#define NLE_G64(T) e = launch_gram64<T>(s, grid, shm, d_lum, gs, d_samples, p, ld16, ldz, nsw, npw, pix0, M, d_c, fl, ntiles, d_partial)
-    switch (tpw) {
-        case 4: NLE_G64(4); break;
-        case 8: NLE_G64(8); break;
-        case 12: NLE_G64(12); break;
-        case 16: NLE_G64(16); break;
-        case 20: NLE_G64(20); break;
-        default: NLE_G64(kG64TilesPerWave); break;
-    }
-#undef NLE_G64
+    hipError_t e = hipErrorInvalidValue;  // the loop above yields listed values only
+    dispatch_values<4, 8, 12, 16, 20, kG64TilesPerWave>(tpw, [&](auto t) {
+        e = launch(k_gram64<decltype(t)::value>, grid, dim3(256), shm, s, d_lum, gs, d_samples, p, ld16, ldz, nsw, npw, pix0, M, d_c, fl,
+                   ntiles, d_partial);
+    });
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_gram64_reduce, dim3((unsigned)ntiles), dim3(256), 0, s, d_partial, (int)nchunks, ntiles,
                        d_tiles);
@@ -667,22 +628,6 @@ __global__ __launch_bounds__(NW * 64) void k_project64_res(const float* __restri
     }
 }
 
-template <int NT, int NW, int REM>
-static hipError_t launch_project64_res(hipStream_t s, long long M, const float* d_lum, GridSpec gs,
-                                       const Sample4* d_samples, int p, float nsw, float npw, long long pix0,
-                                       const double* d_D, int ldd, const double* d_c, float* d_V, int ldv) {
-    const int p4 = (p + 3) & ~3;
-    const size_t shm = (size_t)p4 * project64_res_ldb(NT, REM) * sizeof(double) + (size_t)p4 * sizeof(Sample4);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_project64_res<NT, NW, REM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return e;
-    const long long ntiles = (M + NW * 32 - 1) / (NW * 32);
-    const unsigned grid = (unsigned)std::min<long long>(ntiles, 256);
-    hipLaunchKernelGGL((k_project64_res<NT, NW, REM>), dim3(grid), dim3(NW * 64), shm, s, d_lum, gs, d_samples, p, nsw,
-                       npw, (unsigned)pix0, M, d_D, ldd, d_c, d_V, ldv);
-    return hipGetLastError();
-}
-
 int project64_ld(int K) { return (K + 15) & ~15; }
 
 hipError_t project64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p, float nsw,
@@ -701,36 +646,26 @@ hipError_t project64(hipStream_t s, const float* d_lum, GridSpec gs, const Sampl
         const int p4 = (p + 3) & ~3;
         const size_t shm = (size_t)p4 * project64_res_ldb(nt_r, rem) * sizeof(double) + (size_t)p4 * sizeof(Sample4);
         if (nt_r <= 4 && shm <= 150 * 1024) {
-#define NLE_PR(NTV, REMV) \
-    if (nt_r == NTV && rem == REMV) \
-        return launch_project64_res<NTV, 16, REMV>(s, M, d_lum, gs, d_samples, p, nsw, npw, pix0, d_D, ldd, d_c, d_V, ldv);
-            NLE_PR(1, 0) NLE_PR(1, 1) NLE_PR(1, 2) NLE_PR(1, 3) NLE_PR(1, 4)
-            NLE_PR(2, 0) NLE_PR(2, 1) NLE_PR(2, 2) NLE_PR(2, 3) NLE_PR(2, 4)
-            NLE_PR(3, 0) NLE_PR(3, 1) NLE_PR(3, 2) NLE_PR(3, 3) NLE_PR(3, 4)
-            NLE_PR(4, 0) NLE_PR(4, 1) NLE_PR(4, 2) NLE_PR(4, 3) NLE_PR(4, 4)
-#undef NLE_PR
+            constexpr int NW = 16;
+            const long long ntiles = (M + NW * 32 - 1) / (NW * 32);
+            const unsigned grid = (unsigned)std::min<long long>(ntiles, 256);
+            hipError_t e = hipSuccess;
+            bool hit = false;  // nt_r = 0 (K = 0) has no resident form: the refusal below
+            dispatch_columns<1, 4>(nt_r, [&](auto ntv) {
+                hit = dispatch_columns<0, 4>(rem, [&](auto remv) {
+                    e = launch(k_project64_res<decltype(ntv)::value, NW, decltype(remv)::value>, dim3(grid), dim3(NW * 64), shm, s, d_lum, gs,
+                               d_samples, p, nsw, npw, pix0, M, d_D, ldd, d_c, d_V, ldv);
+                });
+            });
+            if (hit) return e;
         }
     }
     const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-#define NLE_PJ_CASE(NTV)                                                                                   \
-    case NTV:                                                                                              \
-        hipLaunchKernelGGL((k_project64<NTV>), grid, block, 0, s, d_lum, gs, d_samples, p, nsw, npw,      \
-                           (unsigned)pix0, M, d_D, ldd, d_c, d_V, ldv);                                    \
-        break;
-    switch (nt) {
-        NLE_PJ_CASE(1)
-        NLE_PJ_CASE(2)
-        NLE_PJ_CASE(3)
-        NLE_PJ_CASE(4)
-        NLE_PJ_CASE(5)
-        NLE_PJ_CASE(6)
-        NLE_PJ_CASE(7)
-        NLE_PJ_CASE(8)
-        default:
-            return hipErrorInvalidValue;
-    }
-#undef NLE_PJ_CASE
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;  // K beyond 128 columns: no launch
+    dispatch_columns<1, 8>(nt, [&](auto ntv) {
+        e = launch(k_project64<decltype(ntv)::value>, grid, block, 0, s, d_lum, gs, d_samples, p, nsw, npw, pix0, M, d_D, ldd, d_c, d_V, ldv);
+    });
+    return e;
 }
 
 }  // namespace nlek

@@ -14,6 +14,7 @@
 // It is a fallback, sized for correctness first: operands come straight from global memory (L2), one wave per 16 x 16
 // output tile; N x r fp64 is 26.8 GB at cfg4, which 288 GB of HBM holds comfortably.
 #include "kernels.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -121,6 +122,8 @@ hipError_t launch_affinity64(hipStream_t s, const Affinity64Args& a, long long p
     if (a.ld & 1) return hipErrorInvalidValue;   // rows are written two doubles at a time (ld = nle_ld(p) is a multiple of 4)
     const long long ngroups = (M + kAff64Pix - 1) / kAff64Pix;
     const int grid = (int)std::min<long long>(ngroups, 16384);
+    // not through launch(): no template dispatch, and a sample set whose tables pass the default dynamic-LDS allowance is
+    // left to fail at the launch as before (ADVICE.md lists the limit as a fix of its own)
     hipLaunchKernelGGL(k_affinity64<false>, dim3((unsigned)grid), dim3(256), (size_t)a.ld * (sizeof(int2) + sizeof(double)), s,
                        a.lum, a.gs, a.samples, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, nullptr,
                        nullptr, nullptr, 0.0);
@@ -473,24 +476,14 @@ hipError_t rowpass64(hipStream_t s, int mode, const double* d_X, long long M, in
     nb = std::max<long long>(1, std::min<long long>(nb, kRowpassMaxBlocks));
     *nblocks = (int)nb;
     const size_t shm = (size_t)4 * lw * sizeof(double);
-#define NLE_RP64(NCLV)                                                                                                  \
-    {                                                                                                                   \
-        if (shm > 48 * 1024) {                                                                                          \
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rowpass64<NCLV>),                       \
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                  \
-            if (ea != hipSuccess) return ea;                                                                            \
-        }                                                                                                               \
-        hipLaunchKernelGGL((k_rowpass64<NCLV>), dim3((unsigned)nb), dim3(256), shm, s, mode, d_X, M, ld, w, lw, d_t_in, \
-                           d_lam, d_xvec, eps, d_partial);                                                              \
-    }
-    if (lw <= 64) NLE_RP64(1)
-    else if (lw <= 128) NLE_RP64(2)
-    else if (lw <= 256) NLE_RP64(4)
-    else if (lw <= 512) NLE_RP64(8)
-    else if (lw <= 1024) NLE_RP64(16)
-    else NLE_RP64(32)
-#undef NLE_RP64
-    return hipGetLastError();
+    int ncl = 1;  // columns per lane: the smallest power of two that covers lw, at most kRp64Cols by the check on w above
+    while (64 * ncl < lw) ncl *= 2;
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_values<1, 2, 4, 8, 16, 32>(ncl, [&](auto nclv) {
+        e = launch(k_rowpass64<decltype(nclv)::value>, dim3((unsigned)nb), dim3(256), shm, s, mode, d_X, M, ld, w, lw, d_t_in, d_lam,
+                   d_xvec, eps, d_partial);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------ Gram on the fp64 MFMA
@@ -603,18 +596,13 @@ hipError_t apply_expand64(hipStream_t s, const double* d_V, long long M, int ld,
     const int lmax = per_layer ? (int)std::min<size_t>(kApplyLdsBytes / per_layer, (size_t)L) : L;
     const int ngroups = (L + lmax - 1) / lmax, lg = (L + ngroups - 1) / ngroups;
     const long long nb = std::min<long long>((M + 255) / 256, 4096);
-    for (int l0 = 0; l0 < L; l0 += lg) {
+    hipError_t e = hipSuccess;
+    for (int l0 = 0; l0 < L && e == hipSuccess; l0 += lg) {
         const int ln = std::min(lg, L - l0);
-        const size_t shm = (size_t)ln * per_layer;
-        if (shm > 48 * 1024) {
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_apply_expand64),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-            if (ea != hipSuccess) return ea;
-        }
-        hipLaunchKernelGGL(k_apply_expand64, dim3((unsigned)nb), dim3(256), shm, s, d_V, M, ld, K, d_g + (size_t)l0 * ld, ln,
-                           d_Y + (size_t)l0 * ystride, ystride);
+        e = launch(k_apply_expand64, dim3((unsigned)nb), dim3(256), (size_t)ln * per_layer, s, d_V, M, ld, K, d_g + (size_t)l0 * ld, ln,
+                   d_Y + (size_t)l0 * ystride, ystride);
     }
-    return hipGetLastError();
+    return e;
 }
 
 // X[idx[k]][0..ld) = src[k][0..ld)

@@ -15,6 +15,7 @@
 //   k_gram          :296               Wab * Wab^T (its N-sized part, Phi^T C^2 Phi)
 //   k_apply_expand  :456               m_eigvecs * (diag * ...)
 #include "kernels.h"
+#include "launch.h"
 
 namespace nlek {
 
@@ -258,24 +259,9 @@ static hipError_t launch_tsgemm(hipStream_t s, const TsArgs& a) {
     const int panels = (ntiles + 7) / 8;
     const int nt = (ntiles + panels - 1) / panels;
     const dim3 grid((unsigned)((a.M + 127) / 128), (unsigned)panels), block(256);
-    switch (nt) {
-#define NLE_TS_CASE(NTV)                                                              \
-    case NTV:                                                                         \
-        hipLaunchKernelGGL((k_tsgemm<NTV, FUSED>), grid, block, 0, s, a);             \
-        break;
-        NLE_TS_CASE(1)
-        NLE_TS_CASE(2)
-        NLE_TS_CASE(3)
-        NLE_TS_CASE(4)
-        NLE_TS_CASE(5)
-        NLE_TS_CASE(6)
-        NLE_TS_CASE(7)
-        NLE_TS_CASE(8)
-#undef NLE_TS_CASE
-        default:
-            return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;  // nt outside 1 .. 8: no launch
+    dispatch_columns<1, 8>(nt, [&](auto ntv) { e = launch(k_tsgemm<decltype(ntv)::value, FUSED>, grid, block, 0, s, a); });
+    return e;
 }
 
 hipError_t ts_gemm(hipStream_t s, bool fused, const float* d_A, int lda, const float* d_lum,
@@ -324,25 +310,13 @@ static bool pick_gq(int ld, int* G, int* Q) {
     return false;
 }
 
-#define NLE_DISPATCH_Q(GV, Q, ...)                                      \
-    switch (Q) {                                                        \
-        case 1: { constexpr int G_ = GV, Q_ = 1; __VA_ARGS__; } break;  \
-        case 2: { constexpr int G_ = GV, Q_ = 2; __VA_ARGS__; } break;  \
-        case 4: { constexpr int G_ = GV, Q_ = 4; __VA_ARGS__; } break;  \
-        case 6: { constexpr int G_ = GV, Q_ = 6; __VA_ARGS__; } break;  \
-        case 7: { constexpr int G_ = GV, Q_ = 7; __VA_ARGS__; } break;  \
-        case 8: { constexpr int G_ = GV, Q_ = 8; __VA_ARGS__; } break;  \
-        default: return hipErrorInvalidValue;                           \
-    }
-#define NLE_DISPATCH_GQ(G, Q, ...)                                      \
-    switch (G) {                                                        \
-        case 4: NLE_DISPATCH_Q(4, Q, __VA_ARGS__) break;                \
-        case 8: NLE_DISPATCH_Q(8, Q, __VA_ARGS__) break;                \
-        case 16: NLE_DISPATCH_Q(16, Q, __VA_ARGS__) break;              \
-        case 32: NLE_DISPATCH_Q(32, Q, __VA_ARGS__) break;              \
-        case 64: NLE_DISPATCH_Q(64, Q, __VA_ARGS__) break;              \
-        default: return hipErrorInvalidValue;                           \
-    }
+// f(G, Q) as two integral constants for the pair pick_gq chose; false (and no call) where the pair has no instantiation
+template <class F>
+static bool dispatch_gq(int G, int Q, F&& f) {
+    bool hit = false;
+    dispatch_values<4, 8, 16, 32, 64>(G, [&](auto g) { hit = dispatch_values<1, 2, 4, 6, 7, 8>(Q, [&](auto q) { f(g, q); }); });
+    return hit;
+}
 
 template <int G, int QPL>
 __global__ __launch_bounds__(256) void k_rowpass(int mode, const float* __restrict__ X, long long M,
@@ -436,10 +410,12 @@ hipError_t rowpass(hipStream_t s, int mode, const float* d_X, long long M, int l
     if (nb < 1) nb = 1;
     *nblocks = (int)nb;
     const size_t shm = ((size_t)4 * ld + (size_t)G * Q * 4) * sizeof(double);
-    NLE_DISPATCH_GQ(G, Q,
-                    hipLaunchKernelGGL((k_rowpass<G_, Q_>), dim3((unsigned)nb), dim3(256), shm, s, mode,
-                                       d_X, M, ld, d_t_in, d_lam, d_xvec, eps, d_partial))
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_gq(G, Q, [&](auto g, auto q) {
+        e = launch(k_rowpass<decltype(g)::value, decltype(q)::value>, dim3((unsigned)nb), dim3(256), shm, s, mode, d_X, M, ld, d_t_in,
+                   d_lam, d_xvec, eps, d_partial);
+    });
+    return e;
 }
 
 // partial [nb][ld] -> t_out[nslices][ld]; block (x, y) = 32 columns x the y-th contiguous slice of
@@ -518,10 +494,12 @@ hipError_t row_scalings(hipStream_t s, const float* d_X, long long M, int ld, co
     const int rows_per_block = 4 * (64 / G);
     long long nb = (M + rows_per_block - 1) / rows_per_block;
     if (nb > 2048) nb = 2048;
-    NLE_DISPATCH_GQ(G, Q,
-                    hipLaunchKernelGGL((k_row_scalings<G_, Q_>), dim3((unsigned)nb), dim3(256), 0, s, d_X, M,
-                                       ld, d_u, eps, d_out))
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_gq(G, Q, [&](auto g, auto q) {
+        e = launch(k_row_scalings<decltype(g)::value, decltype(q)::value>, dim3((unsigned)nb), dim3(256), 0, s, d_X, M, ld, d_u, eps,
+                   d_out);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------ Gram
@@ -680,12 +658,8 @@ hipError_t gram(hipStream_t s, const float* d_X, long long M, int ld, const doub
     const long long nchunks = gram_num_chunks(M);
     const int groups = (ntiles + 4 * kGramTilesPerWave - 1) / (4 * kGramTilesPerWave);
     const size_t shm = (size_t)ld * sizeof(double) + (size_t)kGramRowsPerStage * ld * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gram),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_gram, dim3((unsigned)nchunks, (unsigned)groups), dim3(256), shm, s, d_X, M, ld, d_u,
-                       eps, fl, ntiles, d_partial);
-    e = hipGetLastError();
+    hipError_t e = launch(k_gram, dim3((unsigned)nchunks, (unsigned)groups), dim3(256), shm, s, d_X, M, ld, d_u, eps, fl, ntiles,
+                          d_partial);
     if (e != hipSuccess) return e;
     return gram_reduce(s, d_partial, (int)nchunks, ntiles, d_tiles);
 }
@@ -752,20 +726,16 @@ hipError_t apply_expand(hipStream_t s, const float* d_V, long long M, int ld, co
     if (per_layer > kApplyLdsBytes) return hipErrorInvalidValue;
     const int lmax = (int)std::min<size_t>(kApplyLdsBytes / per_layer, (size_t)L);
     const int ngroups = (L + lmax - 1) / lmax, lg = (L + ngroups - 1) / ngroups;
-    for (int l0 = 0; l0 < L; l0 += lg) {
-        const int ln = std::min(lg, L - l0);
-        const size_t shm = (size_t)ln * per_layer;
-        NLE_DISPATCH_GQ(G, Q, {
-            if (shm > 48 * 1024) {
-                hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_apply_expand<G_, Q_>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-                if (ea != hipSuccess) return ea;
-            }
-            hipLaunchKernelGGL((k_apply_expand<G_, Q_>), dim3((unsigned)nb), dim3(256), shm, s, d_V, M, ld,
-                               d_g + (size_t)l0 * ld, ln, d_Y + (size_t)l0 * ystride, ystride);
-        })
-    }
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_gq(G, Q, [&](auto g, auto q) {
+        e = hipSuccess;
+        for (int l0 = 0; l0 < L && e == hipSuccess; l0 += lg) {
+            const int ln = std::min(lg, L - l0);
+            e = launch(k_apply_expand<decltype(g)::value, decltype(q)::value>, dim3((unsigned)nb), dim3(256), (size_t)ln * per_layer, s,
+                       d_V, M, ld, d_g + (size_t)l0 * ld, ln, d_Y + (size_t)l0 * ystride, ystride);
+        }
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------ scatter rows

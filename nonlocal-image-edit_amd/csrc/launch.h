@@ -1,5 +1,5 @@
-// Host side of the kernels that are instantiated per column count (tables.hip, sorted.hip, sorted_planes.hip): the map from
-// the run-time count onto its instantiation and the launch itself.  Not installed, not part of kernels.h.
+// Host side of every kernel that is instantiated per size or launched with dynamic LDS: the map from the run-time count
+// onto its instantiation and the launch itself.  Not installed, not part of kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,11 +8,16 @@
 
 namespace nlek {
 
-// f(std::integral_constant<int, NC>{}) for the NC in [LO, HI] that equals nc; false (and no call) where nc is outside.
-// The rules on which forms a count has are written in f, as `if constexpr` on NC.
+// f(std::integral_constant<int, V>{}) for the listed V that equals v; false (and no call) where v is none of them.
+// The rules on which forms a value has are written in f, as `if constexpr` on V; two run-time values nest two dispatches.
+template <int... V, class F>
+bool dispatch_values(int v, F&& f) {
+    return ((v == V ? (f(std::integral_constant<int, V>{}), true) : false) || ...);
+}
+// the contiguous case: every NC in [LO, HI]
 template <int LO, class F, int... I>
 bool dispatch_columns_seq(int nc, F&& f, std::integer_sequence<int, I...>) {
-    return ((nc == LO + I ? (f(std::integral_constant<int, LO + I>{}), true) : false) || ...);
+    return dispatch_values<(LO + I)...>(nc, f);
 }
 template <int LO, int HI, class F>
 bool dispatch_columns(int nc, F&& f) {

@@ -20,6 +20,7 @@
 // With chroma planes (nle_ctx_set_chroma, R <= 3) the KC > 0 instantiations add the term cwd S_ab of the a and b patches:
 // see the comment at the kernel.
 #include "kernels.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -289,19 +290,13 @@ hipError_t launch_patch_affinity64(hipStream_t s, const Affinity64Args& a, long 
     const int grid = (int)std::min<long long>(ngroups, 8192);
     const size_t lds = (size_t)a.ld * (sizeof(int2) + sizeof(int)) + kPatchPix * sizeof(int) +
                        (size_t)kPatchPix * kPatchDotLd * sizeof(int);
-    const int ks = patch_kpad(a.R) / 64;
-#define NLE_PATCH_LAUNCH(KS_)                                                                                               \
-    hipLaunchKernelGGL((k_patch_affinity64<KS_, 0>), dim3((unsigned)grid), dim3(256), lds, s, a.lum, a.gs, a.R, a.samples,   \
-                       a.spatch, a.snorm, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, nullptr,    \
-                       nullptr, nullptr, nullptr, 0.0)
-    switch (ks) {
-        case 1: NLE_PATCH_LAUNCH(1); break;
-        case 2: NLE_PATCH_LAUNCH(2); break;
-        case 3: NLE_PATCH_LAUNCH(3); break;
-        default: NLE_PATCH_LAUNCH(4); break;
-    }
-#undef NLE_PATCH_LAUNCH
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;  // patch_kpad(R) / 64 is one of 1 .. 4 for the R in 1 .. 7 admitted above
+    dispatch_columns<1, 4>(patch_kpad(a.R) / 64, [&](auto ks) {
+        e = launch(k_patch_affinity64<decltype(ks)::value, 0>, dim3((unsigned)grid), dim3(256), lds, s, a.lum, a.gs, a.R, a.samples,
+                   a.spatch, a.snorm, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, nullptr, nullptr, nullptr,
+                   nullptr, 0.0);
+    });
+    return e;
 }
 
 hipError_t launch_patch_affinity64_chroma(hipStream_t s, const Affinity64Args& a, long long pix0, long long M, double* d_kab,
@@ -313,23 +308,13 @@ hipError_t launch_patch_affinity64_chroma(hipStream_t s, const Affinity64Args& a
     if (lds > kPatchChromaLdsMax) return hipErrorInvalidValue;  // (the caller refuses such a sample set with a message)
     const long long ngroups = (M + kPatchPix - 1) / kPatchPix;
     const int grid = (int)std::min<long long>(ngroups, 8192);
-    hipError_t e = hipSuccess;
-#define NLE_PATCH_LAUNCH(KC_)                                                                                               \
-    do {                                                                                                                    \
-        if (lds > kDynLdsDefault)                                                                                           \
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_patch_affinity64<1, KC_>),                              \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                  \
-        if (e != hipSuccess) return e;                                                                                      \
-        hipLaunchKernelGGL((k_patch_affinity64<1, KC_>), dim3((unsigned)grid), dim3(256), lds, s, a.lum, a.gs, a.R, a.samples, \
-                           a.spatch, a.snorm, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, a.a, a.b, \
-                           a.cpatch, a.cnorm, a.cw);                                                                        \
-    } while (0)
-    if (patch_ckpad(a.R) == 64)
-        NLE_PATCH_LAUNCH(1);
-    else
-        NLE_PATCH_LAUNCH(2);
-#undef NLE_PATCH_LAUNCH
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;  // patch_ckpad(R) / 64 is 1 or 2 for the R in 1 .. 3 admitted above
+    dispatch_columns<1, 2>(patch_ckpad(a.R) / 64, [&](auto kc) {
+        e = launch(k_patch_affinity64<1, decltype(kc)::value>, dim3((unsigned)grid), dim3(256), lds, s, a.lum, a.gs, a.R, a.samples,
+                   a.spatch, a.snorm, a.p, a.ld, a.sw, a.pw, pix0, M, d_kab, skip_samples ? 1 : 0, a.smask, a.a, a.b, a.cpatch,
+                   a.cnorm, a.cw);
+    });
+    return e;
 }
 }  // namespace
 

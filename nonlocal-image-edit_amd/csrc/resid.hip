@@ -7,6 +7,7 @@
 // Both write (float)r_i and one summary partial {sum r, max r, index of the first maximum, count r > thresh} per tile of
 // kResidTile pixels, all from the unrounded fp64 r_i; k_resid_finish folds the partials in a fixed order.
 #include "kernels.h"
+#include "launch.h"
 
 #include <algorithm>
 
@@ -161,6 +162,8 @@ __global__ __launch_bounds__(kResidWaves * 64) void k_nystrom_resid64(const floa
 bool resid_fused_applies(int p) { return p >= 1 && p <= kResidMaxP; }
 int resid_fused_ld(int m) { return (m + 15) & ~15; }
 
+// Not through launch(): the LDS size is a constant of the instantiation, so its limit is raised once per process and not
+// asked about again on every call of a map that is launched chunk after chunk.
 template <int NT>
 static hipError_t launch_nystrom_resid64(hipStream_t s, const float* d_lum, GridSpec gs, const Sample4* d_samples, int p,
                                          double sw, double pw, long long N, const double* d_F, int ldf, double thresh,
@@ -179,15 +182,11 @@ hipError_t nystrom_resid64(hipStream_t s, const float* d_lum, GridSpec gs, const
     if (N <= 0) return hipSuccess;
     if (!resid_fused_applies(p) || m < 1 || m > p) return hipErrorInvalidValue;
     const int ldf = resid_fused_ld(m);
-    switch (ldf / 16) {
-#define NLE_RS_CASE(NTV) \
-    case NTV: return launch_nystrom_resid64<NTV>(s, d_lum, gs, d_samples, p, sw, pw, N, d_F, ldf, thresh, d_r, d_part);
-        NLE_RS_CASE(1) NLE_RS_CASE(2) NLE_RS_CASE(3) NLE_RS_CASE(4) NLE_RS_CASE(5) NLE_RS_CASE(6) NLE_RS_CASE(7) NLE_RS_CASE(8)
-        NLE_RS_CASE(9) NLE_RS_CASE(10) NLE_RS_CASE(11) NLE_RS_CASE(12) NLE_RS_CASE(13) NLE_RS_CASE(14) NLE_RS_CASE(15)
-        NLE_RS_CASE(16)
-#undef NLE_RS_CASE
-        default: return hipErrorInvalidValue;
-    }
+    hipError_t e = hipErrorInvalidValue;  // m beyond 256 columns: no launch
+    dispatch_columns<1, 16>(ldf / 16, [&](auto nt) {
+        e = launch_nystrom_resid64<decltype(nt)::value>(s, d_lum, gs, d_samples, p, sw, pw, N, d_F, ldf, thresh, d_r, d_part);
+    });
+    return e;
 }
 
 // ------------------------------------------------------------------ ROWS: r_i = 1 - sum_j T(i, j)^2, j ascending

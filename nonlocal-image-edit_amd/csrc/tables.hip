@@ -225,14 +225,8 @@ static hipError_t launch_hist_g(hipStream_t s, GridSpec gs, int p, int nrows_loc
     const int chunks = std::max(1, std::min(ntiles, std::max((640 + gx - 1) / gx, (ntiles + cap - 1) / cap)));
     const int tpw = (ntiles + chunks - 1) / chunks;
     const size_t shm = (size_t)tpw * 16 * gs.nSelRows * sizeof(double);
-    if (shm > 48 * 1024) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist_g), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)shm);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(k_hist_g, dim3((unsigned)gx, (unsigned)((ntiles + tpw - 1) / tpw)), dim3(256), shm, s, gs, p,
-                       nrows_local, tpw, lev_t0, lev_nt, d_er, d_Ep, d_w, d_g);
-    return hipGetLastError();
+    return launch(k_hist_g, dim3((unsigned)gx, (unsigned)((ntiles + tpw - 1) / tpw)), dim3(256), shm, s, gs, p, nrows_local, tpw,
+                  lev_t0, lev_nt, d_er, d_Ep, d_w, d_g);
 }
 
 constexpr int kPixThreads = 512;
@@ -539,13 +533,9 @@ static hipError_t launch_hist_hh_z(hipStream_t s, const TableView& v, const doub
     const int slab_rows = hist_slab_rows(gs, nrows_local), nslabs = (nrows_local + slab_rows - 1) / slab_rows;
     const int lev_t0 = v.sorted ? v.sorted->lev_t0 : 0, lev_nt = v.sorted ? v.sorted->lev_nt : kLevels / 16;
     const size_t shm_hh = (size_t)slab_rows * nR * sizeof(double);  // slab_rows <= 1024 in practice; nR <= 32
-    if (shm_hh > 48 * 1024) {
-        hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(k_hist_hh),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_hh);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(k_hist_hh, dim3((unsigned)((nC * lev_nt + 3) / 4), (unsigned)nslabs), dim3(256), shm_hh, s, nC, nR,
-                       nrows_local, slab_rows, lev_t0, lev_nt, v.er, d_h, v.Ep, p, ldp, d_HH, d_run_if);
+    hipError_t e = launch(k_hist_hh, dim3((unsigned)((nC * lev_nt + 3) / 4), (unsigned)nslabs), dim3(256), shm_hh, s, nC, nR,
+                          nrows_local, slab_rows, lev_t0, lev_nt, v.er, d_h, v.Ep, p, ldp, d_HH, d_run_if);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_z_reduce, dim3((unsigned)((ldp + 7) / 8)), dim3(256), 0, s, d_HH, nslabs * lev_nt, p, ldp, d_z, d_run_if);
     return hipGetLastError();
 }
@@ -1051,13 +1041,11 @@ hipError_t gram_hist(hipStream_t s, const TableView& v, double* d_ws, double* d_
         e = sorted_gram_rows(s, gs, nrows_local, *sorted, v.cvec, d_A);
         if (e != hipSuccess) return e;
     } else if (nC <= 11) {
-        const size_t shm = (size_t)kLevels * NP * sizeof(double);
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ghist_rows), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)shm);
+        e = launch(k_ghist_rows, dim3((unsigned)nrows_local), dim3(kGhistRowsThreads), (size_t)kLevels * NP * sizeof(double), s, v.lum,
+                   gs, row0, v.ecT, v.cvec, d_A);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_ghist_rows, dim3((unsigned)nrows_local), dim3(kGhistRowsThreads), shm, s, v.lum, gs, row0,
-                           v.ecT, v.cvec, d_A);
     } else {
+        // not through launch(): the chunks differ in size, so the limit is raised once, to the largest, ahead of the loop
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ghist_rows_chunk),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kLevels * kGhistChunkPairs * (int)sizeof(double));
         if (e != hipSuccess) return e;

@@ -14,6 +14,7 @@
 // operand comes pre-split (k_split_b3: [split][k / 8][column][8] bf16, so a lane's fragment is one 16-byte read) through a
 // double-buffered LDS tile; the next tile's global loads are in flight under the current step's 6 NT MFMAs.
 #include "kernels.h"
+#include "launch.h"
 
 namespace nlek {
 
@@ -208,13 +209,9 @@ hipError_t ts_gemm_bf16x3(hipStream_t s, const float* d_lum, GridSpec gs, const 
     const int panels = (ntiles + 6) / 7;
     const int nt = (ntiles + panels - 1) / panels;
     const dim3 grid((unsigned)((M + 127) / 128), (unsigned)panels), block(256);
-    switch (nt) {
-#define NLE_T3(NTV) case NTV: hipLaunchKernelGGL((k_tsgemm_bf16x3<NTV>), grid, block, 0, s, a); break;
-        NLE_T3(1) NLE_T3(2) NLE_T3(3) NLE_T3(4) NLE_T3(5) NLE_T3(6) NLE_T3(7)
-#undef NLE_T3
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;  // nt outside 1 .. 7: no launch
+    dispatch_columns<1, 7>(nt, [&](auto ntv) { e = launch(k_tsgemm_bf16x3<decltype(ntv)::value>, grid, block, 0, s, a); });
+    return e;
 }
 
 }  // namespace nlek

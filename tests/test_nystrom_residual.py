@@ -51,6 +51,8 @@ CASES = {
     "sq_hx40": (64, 64, 8, 8, 40.0, 30.0, 64),
     "one_row": (1, 300, 1, 17, 40.0, 25.0, 17),
     "panels": (120, 160, 10, 20, 40.0, 30.0, 200),  # 13 column tiles, m not a multiple of 16; several staged chunks
+    "p255": (45, 51, 15, 17, 3.0, 30.0, 255),       # FUSED: the widest instantiation (16 column tiles), the last one ragged;
+                                                    # the narrowest (m <= 16) is the rank-truncated case below (m = 10)
     "p288": (120, 160, 16, 18, 30.0, 20.0, 288),    # ROWS only: FUSED must refuse (and the device Cholesky factors K_A)
 }
 FUSED_CASES = [k for k, c in CASES.items() if c[6] <= 256]

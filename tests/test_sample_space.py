@@ -424,21 +424,28 @@ def check_update(res, X1, X2, lam, z, sA, chol, exact):
 # ------------------------------------------------------------------ CPU: the mirrors are the source's, the tables reach every instantiation
 def test_mirrors_match_the_source():
     src = fused_source()
-    assert [int(v) for v in re.findall(r"NLE_SP_CASE\((\d+)\)", src)] == ALL_PP
+    def listed(pattern):
+        """the values of the one dispatch_values<...> / dispatch_columns<LO, HI> of the source that selects on `pattern`"""
+        (form, args), = re.findall(r"dispatch_(values|columns)<([^<>]*)>\(%s," % pattern, src)
+        vals = [a.strip() for a in args.split(",")]
+        return vals if form == "values" else [str(v) for v in range(int(vals[0]), int(vals[1]) + 1)]
+    assert [int(v) for v in listed("pp")] == ALL_PP
     assert "const int pp = (p + 15) & ~15;" in src and "constexpr int P64 = (PP + 63) & ~63;" in src and "constexpr int NJ = P64 / 64;" in src
     assert "int sink_pass_ld(int p) { return (p + 63) & ~63; }" in src and "if (g > 1024) g = 1024;" in src
     assert all(sink_nj(p) == ((sink_pp(p) + 63) & ~63) // 64 for p in range(1, 257))
     assert "static const int kTpw[6] = {4, 8, 12, 16, 20, kG64TilesPerWave};" in src
     with open(os.path.join(ROOT, "nonlocal-image-edit_amd", "csrc", "kernels.h")) as f:
         assert "constexpr int kG64TilesPerWave = 23;" in f.read()
-    assert [int(v) for v in re.findall(r"case (\d+): NLE_G64\(\1\)", src)] == list(GRAM_TPW[:-1])
+    assert listed("tpw") == [str(v) for v in GRAM_TPW[:-1]] + ["kG64TilesPerWave"] and "k_gram64<decltype(t)::value>" in src
     assert "const int ldz = ld16 + ((ld16 % 32 == 16) ? 0 : 16);" in src and "constexpr int kG64Rows = 32;" in src
     assert "long long fl = (M + 511) / 512;" in src and "if (p > 256) return hipErrorInvalidValue;" in src
-    assert [(True, int(a), int(b)) for a, b in re.findall(r"NLE_PR\((\d), (\d)\)", src)] == ALL_PROJECT[:20]
-    assert [(False, int(a), 0) for a in re.findall(r"NLE_PJ_CASE\((\d)\)", src)] == ALL_PROJECT[20:]
+    assert [(True, int(a), int(b)) for a in listed("nt_r") for b in listed("rem")] == ALL_PROJECT[:20]
+    assert [(False, int(a), 0) for a in listed("nt")] == ALL_PROJECT[20:] and "k_project64<decltype(ntv)::value>" in src
     assert "if (nt_r <= 4 && shm <= 150 * 1024) {" in src and "if (rem > 4 || nt_r == 0) {" in src
     assert "const unsigned grid = (unsigned)std::min<long long>(ntiles, 256);" in src
-    assert "launch_project64_res<NTV, 16, REMV>" in src and "constexpr int LDB = NT * 16 + ((NT & 1) ? 0 : 16);" in src
+    assert "k_project64_res<decltype(ntv)::value, NW, decltype(remv)::value>" in src and "constexpr int NW = 16;" in src and \
+        "const long long ntiles = (M + NW * 32 - 1) / (NW * 32);" in src and \
+"constexpr int LDB = NT * 16 + ((NT & 1) ? 0 : 16);" in src
     for nt, rem in ((1, 0), (2, 0), (2, 3), (3, 4), (4, 0), (4, 4)):   # == 16 (mod 32) doubles, the smallest that holds the row
         ldb = project64_res_ldb(nt, rem)
         assert ldb % 32 == 16 and ldb >= nt * 16 + rem and ldb - 32 < nt * 16 + rem

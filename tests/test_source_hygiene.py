@@ -37,6 +37,90 @@ def test_product_sources_read_no_removed_switches():
             assert name not in text, (f, name)
 
 
+# The per-site launch macros that csrc/launch.h's dispatch_values / dispatch_columns / launch() replaced: no source defines
+# one again (a kernel that is instantiated per size is selected and launched through launch.h)
+REMOVED_LAUNCH_MACROS = ("NLE_TS_CASE", "NLE_DISPATCH_Q", "NLE_DISPATCH_GQ", "NLE_T3", "NLE_SP_CASE", "NLE_G64", "NLE_PR",
+                         "NLE_PJ_CASE", "NLE_RP64", "NLE_PATCH_LAUNCH", "NLE_RS_CASE", "NLE_SYW")
+
+
+def test_product_sources_define_no_removed_launch_macros():
+    for f in glob.glob(os.path.join(PKG_DIR, "csrc", "*")) + glob.glob(os.path.join(PKG_DIR, "host", "*")):
+        text = open(f, errors="replace").read()
+        for name in REMOVED_LAUNCH_MACROS:
+            assert not re.search(r"\b%s\b" % name, text), (f, name)
+
+
+def test_attribute_calls_live_in_launch_h_and_the_documented_exceptions():
+    """the dynamic-LDS limit is raised by launch(); outside it only the once-per-process attribute of the residual map
+    (resid.hip) and the one ahead of the chunk loop of the pair tables (tables.hip), and no macro launches a kernel"""
+    calls = {}
+    for f in glob.glob(os.path.join(PKG_DIR, "csrc", "*")):
+        text = open(f, errors="replace").read()
+        n = len(re.findall(r"hipFuncSetAttribute\s*\(", text))
+        if n:
+            calls[os.path.basename(f)] = n
+        for body in re.findall(r"^[ \t]*#[ \t]*define[^\n]*(?:\\\n[^\n]*)*", text, flags=re.M):
+            assert "hipLaunchKernelGGL" not in body and "hipFuncSetAttribute" not in body and "launch(" not in body, (f, body[:80])
+    assert calls == {"launch.h": 1, "resid.hip": 1, "tables.hip": 1}, calls
+
+
+DISPATCH_DRIVER = textwrap.dedent(r"""
+    #include "launch.h"
+    #include <cstdio>
+    using namespace nlek;
+    int main() {
+        for (int v = -2; v <= 260; ++v) {   // a list with gaps: the multiples of 16 up to 256
+            int calls = 0, got = -1;
+            const bool r = dispatch_values<16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
+                v, [&](auto c) { ++calls, got = decltype(c)::value; });
+            std::printf("L %d %d %d %d\n", v, (int)r, calls, got);
+        }
+        for (int v = 0; v <= 12; ++v) {     // a range
+            int calls = 0, got = -1;
+            const bool r = dispatch_columns<3, 9>(v, [&](auto c) { ++calls, got = decltype(c)::value; });
+            std::printf("R %d %d %d %d\n", v, (int)r, calls, got);
+        }
+        for (int g = 0; g <= 66; ++g)       // two levels: a list inside a list
+            for (int q = 0; q <= 9; ++q) {
+                int calls = 0, gg = -1, gq = -1;
+                bool inner = false;
+                const bool r = dispatch_values<4, 8, 16, 32, 64>(g, [&](auto cg) {
+                    inner = dispatch_values<1, 2, 4, 6, 7, 8>(q, [&](auto cq) { ++calls, gg = decltype(cg)::value, gq = decltype(cq)::value; });
+                });
+                std::printf("N %d %d %d %d %d %d\n", g, q, (int)(r && inner), calls, gg, gq);
+            }
+        return 0;
+    }
+""")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_dispatch_calls_once_for_a_listed_value_and_never_outside(tmp_path):
+    """csrc/launch.h alone on the host: the list form and the range form call f exactly once, with the matching constant,
+    for every listed value (lowest, highest, around each gap) and not at all outside, and say so in what they return"""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    rocm = os.environ.get("ROCM_PATH") or os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    (tmp_path / "drv.cpp").write_text(DISPATCH_DRIVER)
+    b = subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+                        "-I", os.path.join(PKG_DIR, "csrc"), str(tmp_path / "drv.cpp"), "-o", str(tmp_path / "drv")],
+                       capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([str(tmp_path / "drv")], capture_output=True, text=True, timeout=30)
+    assert r.returncode == 0, r.stderr
+    rows = [line.split() for line in r.stdout.splitlines()]
+    nkey = {"L": 1, "R": 1, "N": 2}   # a row: the form, the value(s) asked for, then what came back
+    got = {(t[0], *map(int, t[1:1 + nkey[t[0]]])): tuple(map(int, t[1 + nkey[t[0]]:])) for t in rows}
+    want = {}
+    for v in range(-2, 261):
+        want[("L", v)] = (1, 1, v) if v in range(16, 257, 16) else (0, 0, -1)
+    for v in range(0, 13):
+        want[("R", v)] = (1, 1, v) if 3 <= v <= 9 else (0, 0, -1)
+    for g in range(0, 67):
+        for q in range(0, 10):
+            want[("N", g, q)] = (1, 1, g, q) if g in (4, 8, 16, 32, 64) and q in (1, 2, 4, 6, 7, 8) else (0, 0, -1, -1)
+    assert len(rows) == len(want) and got == want, [(k, got.get(k), w) for k, w in want.items() if got.get(k) != w][:10]
+
+
 # ---------------------------------------------------------------------------- the host algebra's files (csrc/*.cpp)
 def test_every_host_source_is_built_into_the_library():
     import importlib.util
