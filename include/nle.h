@@ -657,6 +657,61 @@ int nle_detail_combine(nle_ctx* ctx, const float* d_x, const float* d_layers, in
 int nle_apply_detail(nle_filter* f, const float* d_x, int H, int W, int L, const double* h_weights, double w_rho, double gain,
                      double sigma, int out_kind, void* d_out);
 
+/* ---- the base tone curve: shadows, highlights, auto levels, equalise (new in this build: no reference, so this text and
+ * DESIGN.md section 3.18 are the definition) ---- */
+/* The detail rule above never remaps the base layer.  Here its weighted value Bw = w_{L-1} Y_{L-1} passes a monotone curve,
+ * piecewise linear through NLE_TONE_KNOTS = N + 1 knots over a range [lo, hi]; everything else of the detail rule stays.  All
+ * arithmetic is fp64, every operation rounded on its own (no fma), in the order written.
+ * nle_plane_histogram: the histogram of a scaled plane, n >= 1 floats at d_x.  Per pixel
+ *   v = (double)x scale;  b = floor((v + 256) 4)
+ *   a NaN v -> counts[4097];  b < 0 -> counts[0];  b >= 4096 -> counts[4097];  otherwise counts[1 + b]
+ * NLE_TONE_BINS = 4096 bins of a quarter level over [-256, 768) between an underflow and an overflow counter.  h_counts is
+ * long long[NLE_TONE_BINS + 2]; the counts are integers, so the result is exact and independent of the order of the pixels
+ * and of the merges.  The call returns with the counts on the host.  No alignment is required of d_x.
+ * nle_tone_curve (host only, no ctx; its message is nle_last_error(NULL)): h_curve is double[NLE_TONE_KNOTS + 2] and
+ * receives [lo, hi, T_0 .. T_N].  s = shadows and h = highlights in [-1, 1], P = clip_percent, A = equalise in [0, 1].
+ * h_counts may be NULL when P < 0 and A == 0.  n = the sum of all counts.
+ *   levels  P < 0: lo = 0, hi = 255.  P in [0, 25]: need = P / 100 n; klo = the first bin k in 0 .. 4095 with
+ *           counts[0] + sum_{j <= k} counts[1 + j] > need; khi = the last bin k with counts[4097] + sum_{j >= k} counts[1 + j]
+ *           > need; lo = -256 + 0.25 klo, hi = -256 + 0.25 (khi + 1); where a bin does not exist or hi - lo < 1: lo = 0, hi = 255
+ *   F(v)    the share of pixels below v, linear inside a bin: q = (v + 256) 4, k = min(floor(q), 4095), phi = q - k,
+ *           F = ((counts[0] + sum_{j < k} counts[1 + j]) + phi counts[1 + k]) / n      (the integer sum is exact)
+ *   E_k     = (F(lo + t_k (hi - lo)) - F(lo)) / (F(hi) - F(lo)),  t_k = k / N;  E_k = t_k where the denominator is 0
+ *   m_k     = (1 - A) t_k + A E_k                     (A == 0: m_k = t_k, the counts are not read)
+ *   C(t)    = (t + (s t)(u u)) - (h (t t)) u,  u = 1 - t
+ *   T_k     = 255 C(m_k)
+ * C(0) = 0, C(1) = 1, C is C1 with slope 1 + s at 0 and 1 + h at 1, and non-decreasing for every (s, h) of the square (the
+ * slope reaches 0 only at its corners): T is non-decreasing.  |C - t| <= (4 / 27)(|s| + |h|): 0.1482, which is 37.8 levels,
+ * for one of the two at +-1 and the other at 0.
+ * nle_tone_combine: the stage call, nle_detail_combine with the base term replaced.  With S, rho and g exactly as stated
+ * there and h_curve = [lo, hi, T_0 .. T_N]:
+ *   Bw = w_{L-1} Y_{L-1}
+ *   u  = (Bw - lo) ks,   ks = N / (hi - lo), formed once on the host
+ *   j  = min(max((int)floor(u), 0), N - 1);   f = u - (double)j
+ *   B' = T_j + f (T_{j+1} - T_j)              (f < 0 or f > 1 continues the end segments linearly)
+ *   y  = w_rho g(rho) + w_0 g(Y_0) + .. + w_{L-2} g(Y_{L-2}) + B'
+ * The sums run left to right; for L = 1 the rule is y = w_rho g(rho) + B'.  Output kinds and store rule: the three of
+ * nle_region_combine.  A NaN Bw gives a NaN y: NaN in NLE_REGION_OUT_F32, 0 in the other two kinds.  The stage call always
+ * applies the curve it is given, any finite knots over any finite lo < hi.
+ * nle_apply_tone: nle_apply_layers into the ctx's workspace; the histogram of layer L - 1 with scale = w_{L-1}, only when
+ * P >= 0 or A > 0; the curve; the combine -- bitwise what the four calls give.  The curve is INACTIVE when s == 0, h == 0,
+ * P < 0 and A == 0: the call then is nle_apply_detail, bit for bit.  h_curve_out (may be NULL) receives the curve either way.
+ * NLE_ERR_INVALID with a message, nothing enqueued and the ctx left usable: what nle_detail_combine / nle_apply_detail
+ * refuse; n < 1, a NULL pointer or a scale that is not finite (the histogram); s, h, P or A out of range or not finite, P > 25,
+ * NULL counts where they are needed, a negative count, counts that sum to 0 (the curve); lo, hi or a knot that is not finite,
+ * hi - lo that is not > 0 (the stage combine). */
+#define NLE_TONE_KNOTS 1025
+#define NLE_TONE_BINS 4096
+int nle_plane_histogram(nle_ctx* ctx, const float* d_x, long long n, double scale, long long* h_counts);
+int nle_tone_curve(const long long* h_counts, double shadows, double highlights, double clip_percent, double equalise,
+                   double* h_curve);
+int nle_tone_combine(nle_ctx* ctx, const float* d_x, const float* d_layers, int L, long long n, long long layer_stride,
+                     const double* h_weights, double w_rho, double gain, double sigma, const double* h_curve, int out_kind,
+                     void* d_out);
+int nle_apply_tone(nle_filter* f, const float* d_x, int H, int W, int L, const double* h_weights, double w_rho, double gain,
+                   double sigma, double shadows, double highlights, double clip_percent, double equalise, int out_kind,
+                   void* d_out, double* h_curve_out);
+
 /* ---- several planes through one filter (new in this build) ---- */
 /* Applies f to P planes in one call, each plane with its own set of responses: the channels of a colour image, several guide
  * planes, the stroke planes of the region edits, the a / b pair of the denoiser.  nle_apply (P = 1, one response) and
@@ -844,7 +899,9 @@ enum {
     NLE_KERNEL_COUNT = 12,   /* the ids of the train / apply path end here (kept: callers size their tables by it) */
     NLE_K_NLM8 = 12,         /* non-local-means pre-filter (k_nlm8)                      */
     NLE_K_PLANE_NOISE = 13,  /* Immerkaer noise sum: per-block partials + their fold     */
-    NLE_KERNEL_COUNT_ALL = 14 /* every id nle_kernel_name and nle_ctx_kernel_stats take  */
+    NLE_K_PLANE_HIST = 14,   /* histogram of a scaled plane (k_plane_hist)                */
+    NLE_K_TONE_COMBINE = 15, /* detail combine with the base tone curve (k_tone_combine) */
+    NLE_KERNEL_COUNT_ALL = 16 /* every id nle_kernel_name and nle_ctx_kernel_stats take  */
 };
 const char* nle_kernel_name(int kid);
 /* enable != 0: bracket kernel launches of the ctx with HIP events recorded on the ctx's stream and

@@ -175,6 +175,17 @@ struct DetailOptions {
     bool active() const { return !(residualWeight == 0 && (sigma == 0 || gain == 1)); }
 };
 
+// the options of NLEFilter::enhance with the base tone curve (new here; see there)
+struct ToneOptions {
+    double shadows = 0, highlights = 0, clipPercent = -1, equalise = 0;
+    bool active() const { return !(shadows == 0 && highlights == 0 && clipPercent < 0 && equalise == 0); }
+};
+// the range [lo, hi] the last enhance with active ToneOptions laid its curve over (0, 255 without auto levels)
+struct ToneLevels {
+    double lo = 0, hi = 255;
+    bool valid = false;
+};
+
 // the options of NLEFilter::trainForDenoise / denoise for the MSE-guided denoiser (new here; DESIGN.md section 3.16, the
 // arithmetic is stated in nle.h at nle_nlm8).  The two choices are independent; the defaults are the reference's flow.
 //   prefilter   NLE_PREFILTER_BILATERAL (0): cv::bilateralFilter as the reference calls it; NLE_PREFILTER_NLM (1): wherever
@@ -239,6 +250,17 @@ public:
     // One device: a filter trained on a device group throws; 1 to NLE_REGION_LAYERS_MAX weights.
     Image enhance(const Image& I, const std::vector<DType>& weights, const DetailOptions& detail) const;
     Image toneMap(const Image& I, const std::vector<DType>& weights, DType saturation, const DetailOptions& detail) const;
+    // The base tone curve (new here; DESIGN.md section 3.18, nle_tone_combine in nle.h states the rule): the weighted base
+    // layer -- the one plane the detail options never remap -- passes a monotone curve before the layers are summed.
+    // shadows and highlights in [-1, 1] change the curve's slope at its dark and its bright end to 1 + shadows and
+    // 1 + highlights; clipPercent in [0, 25] lays the curve over the range that remains when that share of the base
+    // layer's pixels is clipped at either end (auto levels; < 0: the range [0, 255]); equalise in [0, 1] blends the curve
+    // with the equalisation of the base layer's histogram inside that range.  The detail layers pass unchanged: no halo.
+    // Inactive options (all four at their defaults) are the method above, bit for bit.  Active options run nle_apply_tone
+    // on the plane that method filters, for 8-bit and 16-bit images.  One device: a filter trained on a device group
+    // throws; 1 to NLE_REGION_LAYERS_MAX weights.  lastToneCurve(): the range of the last such call.
+    Image enhance(const Image& I, const std::vector<DType>& weights, const DetailOptions& detail, const ToneOptions& tone) const;
+    ToneLevels lastToneCurve() const { return toneLevels_; }
     // region edits (new here; nle_apply_regions in nle.h states the rule): enhance with layer weights of its own for every
     // scribbled region.  strokes[m]: a one-channel 8-bit image of I's size, a pixel belongs to the stroke where its byte is
     // >= 128; regionWeights[m]: the weights of region m, as many as `weights`, which is the background's row.  Each stroke
@@ -323,6 +345,7 @@ private:
     nle_filter* f_ = nullptr;         // == fh_.get()
     int rows_ = 0, cols_ = 0;
     bool denoiseTrained_ = false;            // the filter in hand came from trainForDenoise (what glide needs)
+    mutable ToneLevels toneLevels_;          // enhance with active ToneOptions
     mutable DenoiseReport denoiseReport_;    // denoise with DenoiseOptions::glide
     double hdrHi_ = 0, hdrRange_ = 0;  // trainForToneMapping: log2 of the largest luminance and the range in stops (0: none)
     // NLE_DEVICES=<dev>,<dev>,...: trainForEnhancement / enhance shard the image by row slabs over one context (and

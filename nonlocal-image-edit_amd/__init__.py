@@ -49,6 +49,9 @@ RESID_AUTO, RESID_ROWS, RESID_FUSED = _abi.NLE_RESID_AUTO, _abi.NLE_RESID_ROWS, 
 NLM_PATCH_RADIUS_MAX, NLM_SEARCH_RADIUS_MAX = _abi.NLE_NLM_PATCH_RADIUS_MAX, _abi.NLE_NLM_SEARCH_RADIUS_MAX
 PREFILTER_BILATERAL, PREFILTER_NLM = _abi.NLE_PREFILTER_BILATERAL, _abi.NLE_PREFILTER_NLM
 KERNEL_COUNT_ALL = _abi.NLE_KERNEL_COUNT_ALL
+# the base tone curve: the knots of a curve (a curve is [lo, hi, T_0 .. T_N]: TONE_KNOTS + 2 values), the histogram's bins
+# (its counts: underflow, the bins, overflow and NaN: TONE_BINS + 2 values)
+TONE_KNOTS, TONE_BINS = _abi.NLE_TONE_KNOTS, _abi.NLE_TONE_BINS
 
 _lib = None
 
@@ -262,6 +265,27 @@ def mse_shrink(eigvals, b, sigma, k_max, n_grid=256):
     if st != NLE_OK:
         raise NLEError(st, "nle_mse_shrink: K >= 1, 1 <= n_grid <= 65536, sigma and k_max finite and >= 0 expected")
     return k.value, mse
+
+
+def tone_curve(counts, shadows=0.0, highlights=0.0, clip_percent=-1.0, equalise=0.0):
+    """nle_tone_curve (host only): the TONE_KNOTS + 2 values [lo, hi, T_0 .. T_N] of the base tone curve from the TONE_BINS + 2
+    counts of Context.plane_histogram; counts may be None when clip_percent < 0 and equalise == 0"""
+    cp = None
+    if counts is not None:
+        cnt = np.ascontiguousarray(counts, dtype=np.int64).ravel()
+        if cnt.size != TONE_BINS + 2:
+            raise NLEError(NLE_ERR_INVALID, f"tone_curve: {TONE_BINS + 2} counts expected, got {cnt.size}")
+        cp = _np_ptr(cnt)
+    curve = np.zeros(TONE_KNOTS + 2)
+    _check(lib().nle_tone_curve(cp, float(shadows), float(highlights), float(clip_percent), float(equalise), _np_ptr(curve)))
+    return curve
+
+
+def _curve_ptr(curve, who):
+    c = np.ascontiguousarray(curve, dtype=np.float64).ravel()
+    if c.size != TONE_KNOTS + 2:
+        raise NLEError(NLE_ERR_INVALID, f"{who}: a curve holds {TONE_KNOTS + 2} values [lo, hi, T_0 .. T_N], got {c.size}")
+    return c
 
 
 def _combine_out(out, n, out_kind, device):
@@ -1108,6 +1132,36 @@ class Context:
                                         float(sigma), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    def plane_histogram(self, x, scale=1.0):
+        """nle_plane_histogram: the TONE_BINS + 2 int64 counts of the float32 device values x (any shape, contiguous) times
+        scale, in quarter levels over [-256, 768) between an underflow counter and one for overflow and NaN"""
+        torch = _torch()
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32), device=f"cuda:{self.device}")
+        self._sync_in()
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise NLEError(NLE_ERR_INVALID, "plane_histogram: contiguous float32 values expected")
+        counts = np.zeros(TONE_BINS + 2, dtype=np.int64)
+        _check(lib().nle_plane_histogram(self._h, C.c_void_p(x.data_ptr()), x.numel(), float(scale), _np_ptr(counts)), self._h)
+        return counts
+
+    def tone_combine(self, x, layers, weights, curve, residual_weight=0.0, gain=1.0, sigma=0.0, out_kind=0, out=None):
+        """nle_tone_combine, the rule alone: detail_combine with the base term w_{L-1} Y_{L-1} passed through `curve`
+        ([lo, hi, T_0 .. T_N], what tone_curve returns).  Planes and result as for detail_combine."""
+        self._sync_in()
+        L, n = layers.shape
+        if x.shape != (n,) or x.stride(0) != 1 or layers.stride(1) != 1:
+            raise NLEError(NLE_ERR_INVALID, "tone_combine: x (n,) and layers (L, n) with contiguous rows")
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (L,):
+            raise NLEError(NLE_ERR_INVALID, f"tone_combine: weights must hold L = {L} values, got {w.shape}")
+        cv = _curve_ptr(curve, "tone_combine")
+        out = _combine_out(out, n, out_kind, layers.device)
+        _check(lib().nle_tone_combine(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(layers.data_ptr()), L, n,
+                                      layers.stride(0) if L > 1 else n, _np_ptr(w), float(residual_weight), float(gain),
+                                      float(sigma), _np_ptr(cv), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
+        return out
+
     def bench_affinity(self, lum, n_row_samples, n_col_samples, hx, hy, reps=10):
         torch = _torch()
         lum = self._lum(lum)
@@ -1477,6 +1531,24 @@ class NLEFilter:
                                       float(residual_weight), float(gain), float(sigma), int(out_kind),
                                       C.c_void_p(out.data_ptr())), self.ctx._h)
         return out
+
+    def apply_tone(self, x, weights, residual_weight=0.0, gain=1.0, sigma=0.0, shadows=0.0, highlights=0.0, clip_percent=-1.0,
+                   equalise=0.0, out_kind=0, out=None, want_curve=False):
+        """nle_apply_tone: apply_detail with the base layer passed through the tone curve of (shadows, highlights,
+        clip_percent, equalise) -- the layers, the histogram of the weighted base layer where the curve needs it, the curve
+        and the combine in one call.  All four at their defaults: apply_detail, bit for bit.  want_curve: (out, curve)."""
+        x = self.ctx._lum(x)
+        H, W = x.shape
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 1:
+            raise NLEError(NLE_ERR_INVALID, f"weights must be a vector, got {w.shape}")
+        out = _combine_out(out, self.info()["n_local"], out_kind, x.device)
+        curve = np.zeros(TONE_KNOTS + 2)
+        _check(lib().nle_apply_tone(self._f, C.c_void_p(x.data_ptr()), H, W, int(w.shape[0]), _np_ptr(w),
+                                    float(residual_weight), float(gain), float(sigma), float(shadows), float(highlights),
+                                    float(clip_percent), float(equalise), int(out_kind), C.c_void_p(out.data_ptr()),
+                                    _np_ptr(curve) if want_curve else None), self.ctx._h)
+        return (out, curve) if want_curve else out
 
     def apply_layers(self, x, n_layers, out=None):
         torch = _torch()

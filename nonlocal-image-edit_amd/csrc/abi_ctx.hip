@@ -601,7 +601,7 @@ int nle_transform_eigenvalues(const double* h_eigvals, int K, const double* h_we
 static const char* const kKernelNames[NLE_KERNEL_COUNT_ALL] = {
     "affinity", "nystrom_extend", "sinkhorn_pass", "reduce_partials", "gram",
     "project",  "apply_reduce",   "apply_expand",  "small",           "sink_tables", "gram_rows",
-    "gram_gemm", "nlm8", "plane_noise"};
+    "gram_gemm", "nlm8", "plane_noise", "plane_hist", "tone_combine"};
 
 const char* nle_kernel_name(int kid) { return (kid >= 0 && kid < NLE_KERNEL_COUNT_ALL) ? kKernelNames[kid] : ""; }
 

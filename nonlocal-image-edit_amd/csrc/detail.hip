@@ -7,6 +7,10 @@
 // in fp64, the sums left to right, every operation rounded on its own (no fma): the numpy restatement of the tests is
 // reproduced bit for bit with the curve off, and up to the last bit of exp with it on.  Memory bound: L + 1 fp32 planes in,
 // one plane out, nothing kept between pixels.
+// The base tone curve of nle_tone_combine / nle_apply_tone is the same rule with the last term replaced:
+//   Bw = w_{L-1} Y_{L-1};  u = (Bw - lo) ks;  j = min(max(floor(u), 0), N - 1);  f = u - j;  B' = T_j + f (T_{j+1} - T_j)
+// k_tone_combine is k_detail_combine with that term: one statement of the detail rule (detail_pixels), the base term a
+// functor.  Its NLE_TONE_KNOTS knots come from a device buffer and are staged into LDS once per workgroup (8 KB).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -29,6 +33,24 @@ struct DetailArgs {
     DetailWeights w;
 };
 
+// the base term of the detail rule: w_{L-1} Y_{L-1} as it is
+struct PlainBase {};
+
+// the base term of the tone rule: the piecewise-linear curve through the knots T (in LDS), end segments continued linearly.
+// A NaN Bw fails both comparisons: j = 0, f = NaN, B' = NaN.
+struct ToneBase {
+    const double* T;
+    double lo, ks;
+    __device__ __forceinline__ double operator()(double Bw) const {
+        constexpr int N = NLE_TONE_KNOTS - 1;
+        const double u = (Bw - lo) * ks;
+        const int j = u >= 0.0 ? (u < (double)N ? (int)u : N - 1) : 0;
+        const double f = u - (double)j;
+        const double t0 = T[j], t1 = T[j + 1];
+        return t0 + f * (t1 - t0);
+    }
+};
+
 __device__ __forceinline__ double remap(const DetailArgs& a, double d) {
     const double t = d / a.sigma;
     return d * (1.0 + a.gain_m1 * exp(-(t * t)));
@@ -39,8 +61,9 @@ __device__ __forceinline__ double remap(const DetailArgs& a, double d) {
 // stay in registers (a runtime-indexed array would go to scratch) and all L + 1 loads are in flight together.  LMAX is 4 or
 // kRegionLayersMax: the registers of sixteen layers would halve the occupancy of the usual four.
 // CURVE is the uniform switch a.curve as a template argument: with the curve off no exp is in the instruction stream.
-template <int LMAX, bool CURVE, int P>
-__device__ __forceinline__ void detail_pixels(const DetailArgs& a, long long i, double (&y)[P]) {
+// Base: PlainBase, or the functor the last layer's weighted value passes (ToneBase).
+template <int LMAX, bool CURVE, int P, class Base>
+__device__ __forceinline__ void detail_pixels(const DetailArgs& a, long long i, double (&y)[P], const Base& base) {
     const int L = a.L;
     Pack<P> X, Y[LMAX];
     X.load(a.x + i);
@@ -67,7 +90,8 @@ __device__ __forceinline__ void detail_pixels(const DetailArgs& a, long long i, 
 #pragma unroll
             for (int j = 0; j < P; ++j) {
                 const double d = (double)Y[l].v[j];
-                y[j] = y[j] + wl * (curved ? remap(a, d) : d);
+                if constexpr (std::is_same_v<Base, PlainBase>) y[j] = y[j] + wl * (curved ? remap(a, d) : d);
+                else y[j] = y[j] + (l < L - 1 ? wl * (curved ? remap(a, d) : d) : base(wl * d));
             }
         }
 }
@@ -81,17 +105,32 @@ __global__ __launch_bounds__(256) void k_detail_combine(const DetailArgs a, void
     const size_t misaligned = ((reinterpret_cast<size_t>(a.layers) | reinterpret_cast<size_t>(a.x)) & 15) |
                               (size_t)(a.L > 1 ? a.layer_stride & 3 : 0);
     combine_planes<OUT>(a.n, misaligned, out, [&a](long long i, auto& y) {
-        if (a.curve) detail_pixels<LMAX, true>(a, i, y);
-        else detail_pixels<LMAX, false>(a, i, y);
+        if (a.curve) detail_pixels<LMAX, true>(a, i, y, PlainBase());
+        else detail_pixels<LMAX, false>(a, i, y, PlainBase());
+    });
+}
+
+// the same over the tone rule: d_knots holds T_0 .. T_N
+template <int OUT, int LMAX>
+__global__ __launch_bounds__(256) void k_tone_combine(const DetailArgs a, const double* __restrict__ d_knots, double lo, double ks,
+                                                      void* __restrict__ out) {
+    __shared__ double sT[NLE_TONE_KNOTS];
+    for (int k = threadIdx.x; k < NLE_TONE_KNOTS; k += 256) sT[k] = d_knots[k];
+    __syncthreads();
+    const ToneBase base{sT, lo, ks};
+    const size_t misaligned = ((reinterpret_cast<size_t>(a.layers) | reinterpret_cast<size_t>(a.x)) & 15) |
+                              (size_t)(a.L > 1 ? a.layer_stride & 3 : 0);
+    combine_planes<OUT>(a.n, misaligned, out, [&a, &base](long long i, auto& y) {
+        if (a.curve) detail_pixels<LMAX, true>(a, i, y, base);
+        else detail_pixels<LMAX, false>(a, i, y, base);
     });
 }
 
 constexpr int kDetailFewLayers = 4;  // up to here the LMAX = 4 instantiation runs
 
-hipError_t detail_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
-                          const DetailWeights& w, double w_rho, double gain, double sigma, int out_kind, void* d_out) {
-    if (L < 1 || L > kRegionLayersMax || n < 0 || layer_stride < 0) return hipErrorInvalidValue;
-    if (n == 0) return hipSuccess;
+namespace {
+DetailArgs detail_args(const float* d_x, const float* d_layers, long long layer_stride, int L, long long n, const DetailWeights& w,
+                       double w_rho, double gain, double sigma) {
     DetailArgs a;
     a.x = d_x;
     a.layers = d_layers;
@@ -103,11 +142,34 @@ hipError_t detail_combine(hipStream_t s, const float* d_x, const float* d_layers
     a.gain_m1 = gain - 1.0;
     a.sigma = sigma;
     a.w = w;
+    return a;
+}
+}  // namespace
+
+hipError_t detail_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
+                          const DetailWeights& w, double w_rho, double gain, double sigma, int out_kind, void* d_out) {
+    if (L < 1 || L > kRegionLayersMax || n < 0 || layer_stride < 0) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const DetailArgs a = detail_args(d_x, d_layers, layer_stride, L, n, w, w_rho, gain, sigma);
     return launch_for_out_kind(out_kind, [&](auto out) {
         constexpr int OUT = decltype(out)::value;
         if (L <= kDetailFewLayers)
             hipLaunchKernelGGL((k_detail_combine<OUT, kDetailFewLayers>), dim3(combine_grid(n)), dim3(256), 0, s, a, d_out);
         else hipLaunchKernelGGL((k_detail_combine<OUT, kRegionLayersMax>), dim3(combine_grid(n)), dim3(256), 0, s, a, d_out);
+    });
+}
+
+hipError_t tone_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
+                        const DetailWeights& w, double w_rho, double gain, double sigma, const double* d_knots, double lo, double ks,
+                        int out_kind, void* d_out) {
+    if (L < 1 || L > kRegionLayersMax || n < 0 || layer_stride < 0 || !d_knots) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const DetailArgs a = detail_args(d_x, d_layers, layer_stride, L, n, w, w_rho, gain, sigma);
+    return launch_for_out_kind(out_kind, [&](auto out) {
+        constexpr int OUT = decltype(out)::value;
+        if (L <= kDetailFewLayers)
+            hipLaunchKernelGGL((k_tone_combine<OUT, kDetailFewLayers>), dim3(combine_grid(n)), dim3(256), 0, s, a, d_knots, lo, ks, d_out);
+        else hipLaunchKernelGGL((k_tone_combine<OUT, kRegionLayersMax>), dim3(combine_grid(n)), dim3(256), 0, s, a, d_knots, lo, ks, d_out);
     });
 }
 

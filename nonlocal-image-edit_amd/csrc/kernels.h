@@ -449,6 +449,18 @@ struct DetailWeights {
 };
 hipError_t detail_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
                           const DetailWeights& w, double w_rho, double gain, double sigma, int out_kind, void* d_out);
+// the base tone curve (tone.hip, detail.hip; the rule is stated in include/nle.h at nle_tone_combine).  plane_hist: d_counts
+// receives the kToneCounts counters of nle_plane_histogram (zeroed on the stream first).  tone_curve: the host rule of
+// nle_tone_curve; null, or the message of its refusal (tone_check: of the four parameters alone).  tone_combine: detail_combine with the base term passed through the
+// curve of the NLE_TONE_KNOTS knots at d_knots (device), u = (Bw - lo) ks.
+constexpr int kToneCounts = 4098;  // NLE_TONE_BINS + 2: underflow, the bins, overflow and NaN
+hipError_t plane_hist(hipStream_t s, const float* d_x, long long n, double scale, unsigned long long* d_counts);
+const char* tone_check(double shadows, double highlights, double clip_percent, double equalise);
+const char* tone_curve(const long long* counts, double shadows, double highlights, double clip_percent, double equalise,
+                       double* curve);
+hipError_t tone_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
+                        const DetailWeights& w, double w_rho, double gain, double sigma, const double* d_knots, double lo, double ks,
+                        int out_kind, void* d_out);
 // single-channel 8-bit bilateral filter (fp32 planes holding integers); tables from the host: space_w (2r+1)^2 with 0
 // outside the circle, colour_w 256 entries
 int bilateral8_max_radius();

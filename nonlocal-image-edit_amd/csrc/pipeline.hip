@@ -497,6 +497,50 @@ void detail_combine_impl(nle_ctx* c, const float* d_x, const float* d_layers, in
     HIP_OK(hipStreamSynchronize(c->stream));
 }
 
+// ---- the base tone curve (include/nle.h at nle_tone_combine; the kernels are tone.hip and detail.hip) ----
+void tone_curve_impl(const long long* h_counts, double shadows, double highlights, double clip_percent, double equalise,
+                     double* h_curve) {
+    if (const char* refused = nlek::tone_curve(h_counts, shadows, highlights, clip_percent, equalise, h_curve))
+        throw Fail{NLE_ERR_INVALID, refused};
+}
+
+void plane_histogram_impl(nle_ctx* c, const float* d_x, long long n, double scale, long long* h_counts) {
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<unsigned long long> d_counts(nlek::kToneCounts);
+    PROFILED(c, NLE_K_PLANE_HIST, nlek::plane_hist(c->stream, d_x, n, scale, d_counts.p));
+    HIP_OK(hipMemcpyAsync(h_counts, d_counts.p, sizeof(long long) * nlek::kToneCounts, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    prof_flush(c);
+}
+
+// what the stage combine asks of the curve it is given, before anything is enqueued
+void tone_check_curve(const char* who, const double* h_curve) {
+    const std::string name(who);
+    if (!h_curve) throw Fail{NLE_ERR_INVALID, name + ": NULL pointer"};
+    const double lo = h_curve[0], hi = h_curve[1];
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(hi - lo > 0) || !std::isfinite((double)(NLE_TONE_KNOTS - 1) / (hi - lo)))
+        throw Fail{NLE_ERR_INVALID, name + ": the curve's range needs finite lo < hi, got " + std::to_string(lo) + " and " +
+                                        std::to_string(hi)};
+    for (int k = 0; k < NLE_TONE_KNOTS; ++k)
+        if (!std::isfinite(h_curve[2 + k])) throw Fail{NLE_ERR_INVALID, name + ": knot " + std::to_string(k) + " is not finite"};
+}
+
+// the knots go to a buffer of the ctx's workspace; the call returns with the stream drained, so h_curve outlives the copy
+void tone_combine_impl(nle_ctx* c, const float* d_x, const float* d_layers, int L, long long n, long long layer_stride,
+                       const double* h_weights, double w_rho, double gain, double sigma, const double* h_curve, int out_kind,
+                       void* d_out) {
+    nlek::DetailWeights w{};
+    std::copy(h_weights, h_weights + L, w.w);
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<double> d_knots(NLE_TONE_KNOTS);
+    HIP_OK(hipMemcpyAsync(d_knots.p, h_curve + 2, sizeof(double) * NLE_TONE_KNOTS, hipMemcpyHostToDevice, c->stream));
+    const double lo = h_curve[0], ks = (double)(NLE_TONE_KNOTS - 1) / (h_curve[1] - lo);
+    PROFILED(c, NLE_K_TONE_COMBINE, nlek::tone_combine(c->stream, d_x, d_layers, layer_stride, L, n, w, w_rho, gain, sigma,
+                                                        d_knots.p, lo, ks, out_kind, d_out));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    prof_flush(c);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------ C ABI
@@ -920,6 +964,70 @@ int nle_apply_detail(nle_filter* f, const float* d_x, int H, int W, int L, const
         layer_resp(f->eigvals.data(), f->K, L, resp.data());
         apply_impl(f, d_x, H, W, resp.data(), L, d_work.p);  // nle_apply_layers
         detail_combine_impl(c, d_x, d_work.p, L, n, n, h_weights, w_rho, gain, sigma, out_kind, d_out);
+    });
+}
+
+int nle_plane_histogram(nle_ctx* ctx, const float* d_x, long long n, double scale, long long* h_counts) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_x || !h_counts) throw Fail{NLE_ERR_INVALID, "nle_plane_histogram: NULL pointer"};
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_plane_histogram: n must be >= 1"};
+        if (!std::isfinite(scale)) throw Fail{NLE_ERR_INVALID, "nle_plane_histogram: the scale is not finite"};
+        plane_histogram_impl(ctx, d_x, n, scale, h_counts);
+    });
+}
+
+int nle_tone_curve(const long long* h_counts, double shadows, double highlights, double clip_percent, double equalise,
+                   double* h_curve) {
+    return guard(nullptr, [&] { tone_curve_impl(h_counts, shadows, highlights, clip_percent, equalise, h_curve); });
+}
+
+int nle_tone_combine(nle_ctx* ctx, const float* d_x, const float* d_layers, int L, long long n, long long layer_stride,
+                     const double* h_weights, double w_rho, double gain, double sigma, const double* h_curve, int out_kind,
+                     void* d_out) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_x || !d_layers || !h_weights || !h_curve || !d_out) throw Fail{NLE_ERR_INVALID, "nle_tone_combine: NULL pointer"};
+        detail_check("nle_tone_combine", L, h_weights, w_rho, gain, sigma, out_kind);
+        tone_check_curve("nle_tone_combine", h_curve);
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_tone_combine: n must be >= 1"};
+        if ((L > 1 && layer_stride < n) || layer_stride < 0)
+            throw Fail{NLE_ERR_INVALID, "nle_tone_combine: the layer stride is smaller than n"};
+        detail_check_overlap("nle_tone_combine", d_x, d_out, n, out_kind, "the plane");
+        for (int l = 0; l < L; ++l)
+            detail_check_overlap("nle_tone_combine", d_layers + (size_t)l * layer_stride, d_out, n, out_kind, "a layer");
+        tone_combine_impl(ctx, d_x, d_layers, L, n, layer_stride, h_weights, w_rho, gain, sigma, h_curve, out_kind, d_out);
+    });
+}
+
+int nle_apply_tone(nle_filter* f, const float* d_x, int H, int W, int L, const double* h_weights, double w_rho, double gain,
+                   double sigma, double shadows, double highlights, double clip_percent, double equalise, int out_kind,
+                   void* d_out, double* h_curve_out) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        nle_ctx* c = f->ctx;
+        if (!d_x || !h_weights || !d_out) throw Fail{NLE_ERR_INVALID, "nle_apply_tone: NULL pointer"};
+        detail_check("nle_apply_tone", L, h_weights, w_rho, gain, sigma, out_kind);
+        // the curve's own refusals, on the parameters alone (the counts that come later are this call's own: n >= 1 of them)
+        if (const char* refused = nlek::tone_check(shadows, highlights, clip_percent, equalise)) throw Fail{NLE_ERR_INVALID, refused};
+        std::vector<double> curve(NLE_TONE_KNOTS + 2);
+        const bool stats = clip_percent >= 0 || equalise > 0;
+        std::vector<long long> counts(stats ? nlek::kToneCounts : 0);
+        if (c->world > 1)
+            throw Fail{NLE_ERR_INVALID, "nle_apply_tone runs on one device only (world == 1): slabs and device groups are not built"};
+        check_plane_size(f, H, W, true);
+        const long long n = f->n_local;  // == H W: world == 1
+        detail_check_overlap("nle_apply_tone", d_x, d_out, n, out_kind, "the plane");
+        DevBuf<float> d_work((size_t)L * n);
+        std::vector<double> resp((size_t)L * f->K);
+        layer_resp(f->eigvals.data(), f->K, L, resp.data());
+        apply_impl(f, d_x, H, W, resp.data(), L, d_work.p);  // nle_apply_layers
+        if (stats) plane_histogram_impl(c, d_work.p + (size_t)(L - 1) * n, n, h_weights[L - 1], counts.data());
+        tone_curve_impl(stats ? counts.data() : nullptr, shadows, highlights, clip_percent, equalise, curve.data());
+        if (h_curve_out) std::copy(curve.begin(), curve.end(), h_curve_out);
+        if (shadows == 0 && highlights == 0 && clip_percent < 0 && equalise == 0)  // inactive: nle_apply_detail
+            detail_combine_impl(c, d_x, d_work.p, L, n, n, h_weights, w_rho, gain, sigma, out_kind, d_out);
+        else tone_combine_impl(c, d_x, d_work.p, L, n, n, h_weights, w_rho, gain, sigma, curve.data(), out_kind, d_out);
     });
 }
 

@@ -42,6 +42,8 @@ struct FilterArgs {
     bool tonemap = false;            // --tonemap (enhance only): Radiance / PFM in, 16-bit PNG out
     double tonemapSaturation = 1;    // --tonemap-saturation S (with --tonemap)
     nle::DetailOptions detail;       // --residual-weight WR, --detail-gain A, --detail-sigma S (enhance only)
+    nle::ToneOptions tone;           // --shadows S, --highlights Hh, --auto-levels P, --equalise A (enhance only)
+    bool toneLine = false;           // --auto-levels or --equalise was given: one more stdout line, the curve's range
     nle::DenoiseOptions denoise;     // --prefilter bilateral|nlm, --glide, --noise-sigma S, --nlm-h H (denoise only)
     bool nystromReport = false;  // --nystrom-report (enhance only)
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
@@ -90,6 +92,7 @@ inline const char kNystromTakes[] = "--nystrom-report takes no value and --nystr
 inline const char kNystromElsewhere[] = "the residual report belongs to enhance";
 inline const char kTonemapElsewhere[] = "--tonemap (HDR tone mapping) is built for enhance only";
 inline const char kDetailElsewhere[] = "the detail options weigh layers, which this tool does not take";
+inline const char kToneElsewhere[] = "the base tone curve remaps a layer, which this tool does not take";
 inline const char kDenoiseElsewhere[] = "the pre-filter and the MSE-guided shrinkage belong to denoise";
 
 // One row per option.  What holds between options (--noise-sigma needs ..., --exact does not combine with ...) is the
@@ -134,6 +137,17 @@ inline const Option kOptions[] = {
      "--detail-gain takes a finite number in [0, " NLECLI_STR(NLE_DETAIL_GAIN_MAX) "]", kDetailElsewhere},
     {"--detail-sigma", "the amplitude the detail curve's gain acts below (nle::DetailOptions)", kEnhance, Takes::NonNegative, 0, 0, nullptr,
      [](FilterArgs& a, const Value& v) { a.detail.sigma = v.x; }, "--detail-sigma takes a finite number >= 0", kDetailElsewhere},
+    {"--shadows", "the base tone curve's slope at its dark end is 1 + S (nle::ToneOptions of enhance)", kEnhance, Takes::Closed, -1, 1,
+     nullptr, [](FilterArgs& a, const Value& v) { a.tone.shadows = v.x; }, "--shadows takes a finite number in [-1, 1]", kToneElsewhere},
+    {"--highlights", "the base tone curve's slope at its bright end is 1 + Hh (nle::ToneOptions)", kEnhance, Takes::Closed, -1, 1, nullptr,
+     [](FilterArgs& a, const Value& v) { a.tone.highlights = v.x; }, "--highlights takes a finite number in [-1, 1]", kToneElsewhere},
+    {"--auto-levels", "the base tone curve spans what is left of the base layer when P percent are clipped at either end "
+                      "(nle::ToneOptions::clipPercent)",
+     kEnhance, Takes::Closed, 0, 25, nullptr, [](FilterArgs& a, const Value& v) { a.tone.clipPercent = v.x, a.toneLine = true; },
+     "--auto-levels takes a finite number in [0, 25]", kToneElsewhere},
+    {"--equalise", "the share of histogram equalisation in the base tone curve (nle::ToneOptions)", kEnhance, Takes::Closed, 0, 1, nullptr,
+     [](FilterArgs& a, const Value& v) { a.tone.equalise = v.x, a.toneLine = true; }, "--equalise takes a finite number in [0, 1]",
+     kToneElsewhere},
     {"--prefilter", "the pre-filter of the MSE-guided denoiser (nle::DenoiseOptions)", kDenoise, Takes::Word, 0, 0, kPrefilters,
      [](FilterArgs& a, const Value& v) { a.denoise.prefilter = (int)v.x; }, "--prefilter takes 'bilateral' or 'nlm'", kDenoiseElsewhere},
     {"--glide", "shrink every plane by the power the MSE estimate picks; the positional shrink factor is the upper end of the search",
@@ -264,6 +278,10 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
     const std::string detailGiven = last({"--residual-weight", "--detail-gain", "--detail-sigma"});
     if (!detailGiven.empty() && !a->regions.empty())
         refuse(prog, detailGiven + " does not combine with --region: region edits have no residual layer and no detail curve");
+    const std::string toneGiven = last({"--shadows", "--highlights", "--auto-levels", "--equalise"});
+    if (!toneGiven.empty() && (!a->regions.empty() || a->tonemap))
+        refuse(prog, toneGiven + " does not combine with --region or --tonemap: the base tone curve is built for the plain 8-bit and "
+                                 "16-bit enhance");
     if ((is_given("--region-spread") || is_given("--region-floor")) && a->regions.empty())
         refuse(prog, "--region-spread and --region-floor need at least one --region");
     if (first > 1) {
@@ -299,6 +317,7 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
     for (int i = 9; i < argc; ++i) a->extra.push_back(std::stod(argv[i]));
     const std::string most = " takes at most " NLECLI_STR(NLE_REGION_LAYERS_MAX) " weights, got " + std::to_string(a->extra.size());
     if (a->detail.active() && (int)a->extra.size() > NLE_REGION_LAYERS_MAX) refuse(prog, detailGiven + most);
+    if (a->tone.active() && (int)a->extra.size() > NLE_REGION_LAYERS_MAX) refuse(prog, toneGiven + most);
     if (!a->regions.empty()) {  // every region has the background's weight count
         if ((int)a->extra.size() > NLE_REGION_LAYERS_MAX) refuse(prog, "--region" + most);
         for (const auto& r : a->regions)

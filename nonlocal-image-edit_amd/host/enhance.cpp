@@ -6,7 +6,9 @@
 // libnle_hip.so.  New here: leading options; nlecli::kOptions (cli_common.hpp) lists them.  With `--region` the positional
 // weights are the background's; `--nystrom-report` prints one more stdout line with the Nystrom residual of the sample grid
 // (mean, max and its pixel, share of pixels above 0.5) and `--nystrom-map FILE` writes the map as an 8-bit grey image,
-// round(255 clamp(r, 0, 1)); `--deep` and `--tonemap` print the same banners.
+// round(255 clamp(r, 0, 1)); `--deep` and `--tonemap` print the same banners.  `--shadows`, `--highlights`, `--auto-levels`
+// and `--equalise` pass the base layer through a tone curve (nle::ToneOptions); with either of the last two one more stdout
+// line follows the banner, `Tone curve: levels <lo> <hi>`: the range the curve was laid over.
 #include <algorithm>
 
 #include "cli_common.hpp"
@@ -48,13 +50,17 @@ int main(int argc, char* argv[]) {
     filter.chromaBandwidth = a.chroma;
     if (a.tonemap) filter.trainForToneMapping(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
     else filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
-    // (inactive detail options are the plain methods)
+    // (inactive detail and tone options are the plain methods)
     const nle::Image result = a.tonemap        ? filter.toneMap(image, a.extra, a.tonemapSaturation, a.detail)
-                              : strokes.empty() ? filter.enhance(image, a.extra, a.detail)  // the weights are argv[9..]
+                              : strokes.empty() ? filter.enhance(image, a.extra, a.detail, a.tone)  // the weights are argv[9..]
                                                 : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,
                                                                         a.regionFloor);
     nlecli::report(filter);
     const int rc = nlecli::finish(a, result, "Done. Press any key in result window to exit.");  // src/enhance.cpp:45
+    if (a.toneLine) {
+        const nle::ToneLevels t = filter.lastToneCurve();
+        std::cout << "Tone curve: levels " << t.lo << " " << t.hi << std::endl;
+    }
     if (a.nystromReport) {  // after the reference's banners: one line, and the map as an 8-bit grey image
         const nle::NLEFilter::Residual res = filter.nystromResidual(image, a.rowSamples, a.colSamples, a.hx, a.hy);
         const double n = (double)image.total();

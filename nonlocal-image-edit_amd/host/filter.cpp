@@ -488,6 +488,30 @@ Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights, 
     return edit_8bit(ctx_, image, detail_op(ctx_, f_, image, weights, detail, NLE_REGION_OUT_ROUNDED8));
 }
 
+// nle_apply_tone as the operator of the same edits; the curve's range is kept for lastToneCurve()
+Image NLEFilter::enhance(const Image& image, const std::vector<DType>& weights, const DetailOptions& detail,
+                         const ToneOptions& tone) const {
+    if (!tone.active()) return enhance(image, weights, detail);
+    refuse_hdr(image, "enhance");
+    if (image.channels() != 3 || (image.depth() != NLE_8U && image.depth() != NLE_16U))
+        throw std::runtime_error("Can only enhance RGB image.");
+    if (!group_.empty())
+        throw std::runtime_error("ToneOptions (shadows, highlights, clipPercent, equalise) run on one device: this filter was trained on a device group (NLE_DEVICES).");
+    requireSize(image.total(), kTrainedSize);
+    const int H = image.rows, W = image.cols, L = detail_layers(weights);
+    const bool deep = is_deep(image);
+    std::vector<double> curve(NLE_TONE_KNOTS + 2);
+    const auto op = [&](const float* d_x, float* d_y) {
+        check(nle_apply_tone(f_, d_x, H, W, L, weights.data(), detail.residualWeight, detail.gain, detail.sigma, tone.shadows,
+                             tone.highlights, tone.clipPercent, tone.equalise, deep ? NLE_REGION_OUT_F32 : NLE_REGION_OUT_ROUNDED8,
+                             d_y, curve.data()),
+              ctx_);
+    };
+    Image out = deep ? edit_deep(ctx_, image, op) : edit_8bit(ctx_, image, op);
+    toneLevels_.lo = curve[0], toneLevels_.hi = curve[1], toneLevels_.valid = true;
+    return out;
+}
+
 // inactive options: the plain toneMap, nle_apply under the transformed eigenvalues (the one-device and the weight-count
 // refusals keep each form's own text)
 Image NLEFilter::toneMap(const Image& image, const std::vector<DType>& weights, DType saturation,
