@@ -712,6 +712,71 @@ int nle_apply_tone(nle_filter* f, const float* d_x, int H, int W, int L, const d
                    double sigma, double shadows, double highlights, double clip_percent, double equalise, int out_kind,
                    void* d_out, double* h_curve_out);
 
+/* ---- automatic regions: kernel k-means on the trained affinity (new in this build: no reference, so this text and
+ * DESIGN.md section 3.19 are the definition) ---- */
+/* Proposes the regions a region edit needs, instead of hand-drawn stroke masks.  The eigenpairs (V, lambda) of a trained
+ * filter define the diffusion affinity G = V lambda^t V^T that nle_region_spread spreads strokes with; clustering the pixels
+ * by G is spectral segmentation.  V is never materialised on the default path, and kernel k-means does not need it: one
+ * iteration needs G applied to the C indicator planes of the current labels, which is one nle_region_spread.
+ * Inputs: a trained filter f over N = H W pixels; C clusters, 1 <= C <= NLE_REGION_MAX; labels l_i in 0 .. C - 1, one byte
+ * per pixel; the spread t > 0; a cap on the iterations, 1 .. NLE_SEGMENT_ITERATIONS_MAX.
+ * One iteration, from labels l:
+ *   Counts     n_c = #{i : l_i = c}.  A cluster with n_c = 0 is INACTIVE and stays empty for good.
+ *   Spread     s_c = the 0 / 1 fp32 indicator plane of cluster c;  q = nle_region_spread(f, s, C, scale, t) with
+ *              scale_c = N / n_c, and 0 for an inactive cluster -- bit for bit that call (the CLI's own stroke scaling: the
+ *              spreads have mean ~ 1 and everything below is O(1)).
+ *   Means      m_c = (sum_{i : l_i = c} (double)q_c[i]) / n_c in fp64, +inf for an inactive cluster.
+ *   Reassign   per pixel, in fp64, every operation rounded on its own:  score_c = m_c - 2 (double)q_c[i];  a NaN score and
+ *              an inactive cluster count as +inf;  l'_i = the smallest c with the smallest score;  where every score is
+ *              +inf the pixel keeps l_i.  This is kernel k-means on G: N |psi_i - mu_c|^2 = score_c + a term that does not
+ *              depend on c, with psi = V lambda^(t/2) and mu_c the mean of cluster c.
+ *   Objective  J = ((n_0 m_0 + n_1 m_1) + ..) / N over the active clusters in ascending c, reported for the labels that
+ *              ENTERED the iteration.  In exact arithmetic it never decreases.
+ * Stop when an iteration changes no label, or after the cap.  Nothing is random anywhere.
+ * Start (nle_segment_init): equal-population cuts of a plane x on the counts of nle_plane_histogram(x, scale = 1):
+ *   cum(k) = counts[0] + sum_{j <= k} counts[1 + j];  b_c = the first bin k in 0 .. 4095 with cum(k) >= floor(N c / C) + 1,
+ *   for c = 1 .. C - 1, 4096 where none exists;  l_i = #{c : bin(x_i) >= b_c} with bin(x) = floor((x + 256) 4) clamped to
+ *   [-1, 4096] and a NaN taken as 4096.  Equal cuts give empty clusters: that is allowed and reported.
+ * The stage calls, each the rule alone on any planes.  Plane c of d_q lies at d_q + c q_stride (stride in floats, >= n); no
+ * alignment is required of any pointer or stride; each returns with its results on the host.
+ *   nle_segment_init    h_cuts (may be NULL) receives b_1 .. b_{C-1}; d_labels n bytes.
+ *   nle_segment_stats   h_counts[c] = n_c and h_sums[c] = the fp64 sum of q_c over the members of c, every pixel reading
+ *                       the one value q_{l_i}[i].  The sums go through per-workgroup partials on a grid that depends on n
+ *                       alone and are folded in a fixed order: two calls on the same buffers give the same bits.  The
+ *                       order inside a workgroup depends on the placement: with d_q 16-byte aligned, q_stride a multiple
+ *                       of 4 and d_labels 4-byte aligned, four aligned pixels that share a label enter as ((a + b) + c) + d,
+ *                       added once; otherwise pixel by pixel -- the sums of two placements may differ in their last bits
+ *                       (both within n_c 2^-52 sum |q| of the exact sum).  q_stride = 0 is legal: all
+ *                       planes are then one plane and the sums are its per-cluster sums.  A label >= C is refused after
+ *                       the pass (counted with an integer atomic, never used as an index).
+ *   nle_segment_assign  h_m: the C values m_c, +inf for an inactive cluster.  d_labels is read and rewritten;
+ *                       d_indicators (may be NULL) receives the C indicator planes of the new labels, plane c at
+ *                       d_indicators + c ind_stride; h_counts the new n_c; h_changed the number of labels that changed
+ *                       (integer atomics: exact, independent of the order).  A label >= C is refused after the pass:
+ *                       such a pixel is left as it is and belongs to no indicator plane.  The planes, the labels and the
+ *                       indicator planes must not overlap.
+ * nle_filter_segment runs the loop from the labels at d_labels with the work planes in the ctx's workspace: bit for bit
+ * the composition of nle_region_spread, nle_segment_stats, the division m_c = sum_c / n_c and nle_segment_assign on planes
+ * placed as its own are -- 16-byte aligned, n floats apart -- and on the caller's d_labels (see nle_segment_stats on
+ * placements), with one small download per iteration.  d_labels receives the result, h_counts its C counts, h_objective[0 .. iters) the
+ * objective of every iteration made (the rest is not written), *h_iters their number, *h_converged 1 when the last one
+ * changed no label.  d_q (may be NULL) receives the C spreads of the RETURNED labels, plane c at d_q + c q_stride: the last
+ * iteration's when it changed nothing, otherwise one more spread is made.  They are the membership planes
+ * nle_region_combine takes.  Works for every formulation nle_apply_planes works for.
+ * NLE_ERR_INVALID with a message, nothing enqueued and the ctx left usable: C out of range, n < 1, a stride smaller than n
+ * (q_stride = 0 apart, in the two stage calls), a NULL pointer (h_cuts, d_indicators and d_q apart), overlapping buffers; for
+ * nle_filter_segment also a spread that is not finite and > 0, max_iter out of range, H W that is not the filter's and
+ * world > 1 (slabs and device groups are not built; refused before any collective). */
+#define NLE_SEGMENT_ITERATIONS_MAX 200
+int nle_segment_init(nle_ctx* ctx, const float* d_x, long long n, int C, unsigned char* d_labels, int* h_cuts);
+int nle_segment_stats(nle_ctx* ctx, const float* d_q, int C, long long n, long long q_stride, const unsigned char* d_labels,
+                      long long* h_counts, double* h_sums);
+int nle_segment_assign(nle_ctx* ctx, const float* d_q, int C, long long n, long long q_stride, const double* h_m,
+                       unsigned char* d_labels, float* d_indicators, long long ind_stride, long long* h_counts,
+                       long long* h_changed);
+int nle_filter_segment(nle_filter* f, int H, int W, int C, double spread, int max_iter, unsigned char* d_labels, float* d_q,
+                       long long q_stride, long long* h_counts, double* h_objective, int* h_iters, int* h_converged);
+
 /* ---- several planes through one filter (new in this build) ---- */
 /* Applies f to P planes in one call, each plane with its own set of responses: the channels of a colour image, several guide
  * planes, the stroke planes of the region edits, the a / b pair of the denoiser.  nle_apply (P = 1, one response) and

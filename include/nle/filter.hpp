@@ -186,6 +186,25 @@ struct ToneLevels {
     bool valid = false;
 };
 
+// the options of NLEFilter::segment (new here; see there): the number of segments, how far a segment's indicator spreads
+// (the t of G = V lambda^t V^T), the cap on the iterations, and the membership floor enhanceSegments combines with
+struct SegmentOptions {
+    int count = 0;
+    double spread = 4;
+    int maxIterations = 40;
+    double floor = 0.05;
+};
+// what the last NLEFilter::segment found: per segment its pixels and their mean L on the plane the filter was trained on
+// (0 for an empty segment), the iterations made, whether the last one changed no label, and its objective
+struct SegmentReport {
+    std::vector<long long> counts;
+    std::vector<double> meanL;
+    int iterations = 0;
+    bool converged = false;
+    double objective = 0;
+    bool valid = false;
+};
+
 // the options of NLEFilter::trainForDenoise / denoise for the MSE-guided denoiser (new here; DESIGN.md section 3.16, the
 // arithmetic is stated in nle.h at nle_nlm8).  The two choices are independent; the defaults are the reference's flow.
 //   prefilter   NLE_PREFILTER_BILATERAL (0): cv::bilateralFilter as the reference calls it; NLE_PREFILTER_NLM (1): wherever
@@ -272,6 +291,19 @@ public:
     Image enhanceRegions(const Image& I, const std::vector<Image>& strokes,
                          const std::vector<std::vector<DType>>& regionWeights, const std::vector<DType>& weights,
                          DType spread = 4, DType floor = 0.05) const;
+    // automatic regions (new here; nle_filter_segment in nle.h states the rule): the regions a
+    // region edit needs, proposed by the trained filter itself instead of hand-drawn strokes -- kernel k-means of the pixels
+    // on the affinity V lambda^spread V^T, from equal-population cuts of the plane the filter was trained on; nothing is
+    // random, so two calls give the same labels.  segment needs a filter trained by trainForEnhancement on one device with
+    // keepTrainPlane set (see there); it returns the labels as an 8UC1 image and keeps the segments' spreads on the device.
+    // enhanceSegments is enhanceRegions with those spreads as the memberships and options.floor as the floor: `weights` is
+    // the background's row, segmentWeights[c] the row of segment c -- `weights` again where it is empty or missing; 8-bit
+    // images.  Both throw std::runtime_error for a count outside 1 .. NLE_REGION_MAX, whatever nle_filter_segment refuses,
+    // a filter trained on a device group, and enhanceSegments without a segment() since the last train.
+    Image segment(const SegmentOptions& options);
+    SegmentReport lastSegments() const { return segmentReport_; }
+    Image enhanceSegments(const Image& I, const std::vector<DType>& weights,
+                          const std::vector<std::vector<DType>>& segmentWeights) const;
     // include/filter.hpp:40-45: the filter is trained on the bilateral-filtered L channel; denoise shrinks the
     // eigenvalues to min(lambda, 1)^k on the a and b channels (src/filter.cpp:349-410, 521-538)
     void trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,
@@ -338,6 +370,9 @@ public:
     // patchRadius <= NLE_CHROMA_PATCH_RADIUS_MAX and not `exact`.  trainFilter takes a bare luminance plane, has no
     // chroma and ignores it; trainForDenoise throws if it is set (a and b are what that path estimates)
     double chromaBandwidth = 0;
+    // trainForEnhancement on one device leaves its fp32 L plane on the device for segment() to start from (new here; 4 bytes
+    // per pixel for the life of the filter, so only on request)
+    bool keepTrainPlane = false;
 
 private:
     nle_ctx* ctx_ = nullptr;
@@ -347,6 +382,12 @@ private:
     bool denoiseTrained_ = false;            // the filter in hand came from trainForDenoise (what glide needs)
     mutable ToneLevels toneLevels_;          // enhance with active ToneOptions
     mutable DenoiseReport denoiseReport_;    // denoise with DenoiseOptions::glide
+    // segment(): the plane trainForEnhancement trained on (fp32, on the device; keepTrainPlane), the spreads of the last segmentation
+    // (count planes) with its floor, and what it found
+    std::shared_ptr<void> trainPlane_, segmentSpreads_;
+    int segmentCount_ = 0;
+    double segmentFloor_ = 0.05;
+    SegmentReport segmentReport_;
     double hdrHi_ = 0, hdrRange_ = 0;  // trainForToneMapping: log2 of the largest luminance and the range in stops (0: none)
     // NLE_DEVICES=<dev>,<dev>,...: trainForEnhancement / enhance shard the image by row slabs over one context (and
     // one host thread per call) per listed device; rank r's filter is group_[r] and f_ == group_[0].get()

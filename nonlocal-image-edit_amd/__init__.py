@@ -52,6 +52,7 @@ KERNEL_COUNT_ALL = _abi.NLE_KERNEL_COUNT_ALL
 # the base tone curve: the knots of a curve (a curve is [lo, hi, T_0 .. T_N]: TONE_KNOTS + 2 values), the histogram's bins
 # (its counts: underflow, the bins, overflow and NaN: TONE_BINS + 2 values)
 TONE_KNOTS, TONE_BINS = _abi.NLE_TONE_KNOTS, _abi.NLE_TONE_BINS
+SEGMENT_ITERATIONS_MAX = _abi.NLE_SEGMENT_ITERATIONS_MAX  # nle_filter_segment: the cap on its iterations (C: 1 .. REGION_MAX)
 
 _lib = None
 
@@ -1162,6 +1163,80 @@ class Context:
                                       float(sigma), _np_ptr(cv), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    def _here(self, t):
+        """t is a tensor on this ctx's device (its pointer is handed to kernels)"""
+        return t.is_cuda and (t.device.index or 0) == self.device
+
+    def _labels(self, labels, who, n):
+        """the n labels as uint8 on this ctx's device: host values are uploaded, a device tensor is taken as it is"""
+        torch = _torch()
+        if not isinstance(labels, torch.Tensor):
+            labels = torch.as_tensor(np.ascontiguousarray(labels, dtype=np.uint8), device=f"cuda:{self.device}")
+        if (labels.dtype != torch.uint8 or labels.ndim != 1 or labels.stride(0) != 1 or labels.numel() != n or
+                not self._here(labels)):
+            raise NLEError(NLE_ERR_INVALID, f"{who}: labels must be {n} contiguous bytes on cuda:{self.device} (a view at any "
+                                            "offset is taken as it is)")
+        return labels
+
+    def _segment_planes(self, q, who):
+        """(C, n) of float32 planes on this ctx's device with contiguous rows"""
+        torch = _torch()
+        if (not isinstance(q, torch.Tensor) or q.dtype != torch.float32 or q.ndim != 2 or q.stride(1) != 1 or
+                not self._here(q)):
+            raise NLEError(NLE_ERR_INVALID, f"{who}: (C, n) float32 planes on cuda:{self.device} with contiguous rows expected")
+        return q.shape
+
+    def segment_init(self, x, count):
+        """nle_segment_init: the equal-population start of `count` clusters on the float32 device values x (any shape,
+        contiguous; a view at any offset is taken as it is).  Returns (labels: n uint8 on the device, cuts: count - 1 ints)."""
+        torch = _torch()
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32), device=f"cuda:{self.device}")
+        if x.dtype != torch.float32 or not x.is_contiguous() or not self._here(x):
+            raise NLEError(NLE_ERR_INVALID, f"segment_init: contiguous float32 values on cuda:{self.device} expected")
+        self._sync_in()
+        labels = torch.zeros(x.numel(), dtype=torch.uint8, device=x.device)
+        cuts = np.zeros(max(int(count) - 1, 1), dtype=np.int32)
+        _check(lib().nle_segment_init(self._h, C.c_void_p(x.data_ptr()), x.numel(), int(count), C.c_void_p(labels.data_ptr()),
+                                      _np_ptr(cuts)), self._h)
+        return labels, cuts[:max(int(count) - 1, 0)]
+
+    def segment_stats(self, q, labels):
+        """nle_segment_stats: q (C, n) float32 device planes with contiguous rows any stride >= n apart (stride 0, an
+        expanded plane, is taken as it is: every cluster then reads the one plane), labels n uint8.  Returns (counts int64,
+        sums float64), C values each."""
+        Cn, n = self._segment_planes(q, "segment_stats")
+        labels = self._labels(labels, "segment_stats", n)
+        self._sync_in()
+        counts, sums = np.zeros(max(Cn, 1), dtype=np.int64), np.zeros(max(Cn, 1))
+        _check(lib().nle_segment_stats(self._h, C.c_void_p(q.data_ptr()), Cn, n, q.stride(0) if Cn > 1 else n,
+                                       C.c_void_p(labels.data_ptr()),
+                                       _np_ptr(counts), _np_ptr(sums)), self._h)
+        return counts[:Cn], sums[:Cn]
+
+    def segment_assign(self, q, means, labels, want_indicators=False, indicators=None):
+        """nle_segment_assign: q (C, n) as for segment_stats, means C float64 values (+inf: inactive), labels n uint8 on the
+        device, REWRITTEN in place.  Returns (counts int64, changed), and the (C, n) float32 indicator planes of the new
+        labels as a third value when want_indicators is set or `indicators` (rows contiguous, any stride >= n) is given."""
+        torch = _torch()
+        Cn, n = self._segment_planes(q, "segment_assign")
+        labels = self._labels(labels, "segment_assign", n)
+        m = np.ascontiguousarray(means, dtype=np.float64)
+        if m.shape != (Cn,):
+            raise NLEError(NLE_ERR_INVALID, f"segment_assign: {Cn} means expected, got {m.shape}")
+        if indicators is None and want_indicators:
+            indicators = torch.empty((Cn, n), dtype=torch.float32, device=q.device)
+        if indicators is not None and tuple(self._segment_planes(indicators, "segment_assign (indicators)")) != (Cn, n):
+            raise NLEError(NLE_ERR_INVALID, f"segment_assign: indicators must be float32 {(Cn, n)} with contiguous rows")
+        self._sync_in()
+        counts, changed = np.zeros(max(Cn, 1), dtype=np.int64), C.c_longlong(0)
+        _check(lib().nle_segment_assign(self._h, C.c_void_p(q.data_ptr()), Cn, n, q.stride(0) if Cn > 1 else n, _np_ptr(m),
+                                        C.c_void_p(labels.data_ptr()),
+                                        C.c_void_p(indicators.data_ptr()) if indicators is not None else None,
+                                        (indicators.stride(0) if Cn > 1 else n) if indicators is not None else 0,
+                                        _np_ptr(counts), C.byref(changed)), self._h)
+        return (counts[:Cn], changed.value) if indicators is None else (counts[:Cn], changed.value, indicators)
+
     def bench_affinity(self, lum, n_row_samples, n_col_samples, hx, hy, reps=10):
         torch = _torch()
         lum = self._lum(lum)
@@ -1204,11 +1279,13 @@ class NLEFilter:
         self.ctx = ctx
         self._f = C.c_void_p()
         self.shape = None
+        self._train_plane = None
 
     def close(self):
         if self._f:
             lib().nle_filter_destroy(self._f)
             self._f = C.c_void_p()
+        self._train_plane = None
 
     def __del__(self):
         try:
@@ -1240,6 +1317,7 @@ class NLEFilter:
                                float(hx), float(hy), int(n_sinkhorn_iter), int(n_eigen_vectors), C.byref(self._f)),
                self.ctx._h)
         self.shape = (H, W)
+        self._train_plane = lum if self.ctx.world == 1 else None  # the start of segment()
         return self
 
     def train_filter_host(self, lum, n_row_samples, n_col_samples, hx, hy, n_sinkhorn_iter=10, n_eigen_vectors=5,
@@ -1515,6 +1593,33 @@ class NLEFilter:
         _check(lib().nle_apply_regions(self._f, C.c_void_p(x.data_ptr()), H, W, int(n_layers), C.c_void_p(s.data_ptr()), M,
                                        cp, float(spread), float(floor), _np_ptr(w), int(out_kind),
                                        C.c_void_p(out.data_ptr())), self.ctx._h)
+        return out
+
+    def segment(self, count, spread=4.0, max_iter=40, labels=None, want_spreads=False):
+        """nle_filter_segment: kernel k-means of the pixels on the trained affinity, `count` clusters.  labels: the start, n
+        uint8 values (a device tensor is REWRITTEN in place); None: the equal-population start (Context.segment_init) on the
+        plane train_filter was given.  Returns a dict: labels (n uint8 on the device), counts, objective (one value per
+        iteration made), iterations, converged, and -- want_spreads -- spreads, the (count, n) float32 spreads of the
+        returned labels (the membership planes Context.region_combine takes)."""
+        torch = _torch()
+        H, W = self.shape
+        if labels is None:
+            if self._train_plane is None:
+                raise NLEError(NLE_ERR_INVALID, "segment: no start labels given and the training plane is not on the device")
+            labels, _ = self.ctx.segment_init(self._train_plane, count)
+        Cn, n = int(count), H * W
+        labels = self.ctx._labels(labels, "segment", n)
+        self.ctx._sync_in()
+        q = torch.empty((max(Cn, 1), n), dtype=torch.float32, device=labels.device) if want_spreads else None
+        counts, obj = np.zeros(max(Cn, 1), dtype=np.int64), np.full(max(int(max_iter), 1), np.nan)
+        iters, conv = C.c_int(0), C.c_int(0)
+        _check(lib().nle_filter_segment(self._f, H, W, Cn, float(spread), int(max_iter), C.c_void_p(labels.data_ptr()),
+                                        C.c_void_p(q.data_ptr()) if q is not None else None, n, _np_ptr(counts), _np_ptr(obj),
+                                        C.byref(iters), C.byref(conv)), self.ctx._h)
+        out = dict(labels=labels, counts=counts[:Cn], objective=obj[:iters.value], iterations=iters.value,
+                   converged=bool(conv.value))
+        if want_spreads:
+            out["spreads"] = q
         return out
 
     def apply_detail(self, x, weights, residual_weight=0.0, gain=1.0, sigma=0.0, out_kind=0, out=None):

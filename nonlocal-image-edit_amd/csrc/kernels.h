@@ -461,6 +461,30 @@ const char* tone_curve(const long long* counts, double shadows, double highlight
 hipError_t tone_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
                         const DetailWeights& w, double w_rho, double gain, double sigma, const double* d_knots, double lo, double ks,
                         int out_kind, void* d_out);
+// automatic regions (segment.hip; the rule is stated in include/nle.h at nle_filter_segment).  Labels are one byte per
+// pixel, planes go by base pointer and stride in floats, C is 1 .. kRegionMax.  Everything a step leaves for the host sits
+// in one SegmentResult on the device (zeroed by the launcher where the kernels add to it).
+//   segment_init    label = the number of cuts b_1 <= .. <= b_{C-1} the pixel's quarter-level bin has reached
+//   segment_stats   count[c], sum[c] = the fp64 sum of q_{label}[i] over the members, mean[c] = sum / count (+inf for an
+//                   empty cluster), bad = the labels >= C (never used as an index).  The sums go through
+//                   segment_stats_blocks(n) x kRegionMax per-workgroup partials at d_partial and are folded in a fixed order.
+//   segment_assign  label' = the smallest c with the smallest mean[c] - 2 q_c[i], read from r->mean; d_ind (may be null)
+//                   receives the C indicator planes of the new labels; new_count, changed and bad_new are added to.  d_q
+//                   null: no plane is read and no label moves -- the indicator planes and counts of the labels as they are.
+struct SegmentResult {
+    unsigned long long count[kRegionMax], bad;
+    double sum[kRegionMax], mean[kRegionMax];
+    unsigned long long new_count[kRegionMax], changed, bad_new;
+};
+struct SegmentCuts {
+    int b[kRegionMax - 1];  // the first C - 1 entries are read
+};
+int segment_stats_blocks(long long n);
+hipError_t segment_init(hipStream_t s, const float* d_x, long long n, int C, const SegmentCuts& cuts, unsigned char* d_labels);
+hipError_t segment_stats(hipStream_t s, const float* d_q, long long q_stride, int C, long long n, const unsigned char* d_labels,
+                         double* d_partial, SegmentResult* d_r);
+hipError_t segment_assign(hipStream_t s, const float* d_q, long long q_stride, int C, long long n, unsigned char* d_labels,
+                          float* d_ind, long long ind_stride, SegmentResult* d_r);
 // single-channel 8-bit bilateral filter (fp32 planes holding integers); tables from the host: space_w (2r+1)^2 with 0
 // outside the circle, colour_w 256 entries
 int bilateral8_max_radius();

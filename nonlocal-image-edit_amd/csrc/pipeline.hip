@@ -541,6 +541,75 @@ void tone_combine_impl(nle_ctx* c, const float* d_x, const float* d_layers, int 
     prof_flush(c);
 }
 
+// ---- automatic regions (include/nle.h "automatic regions"; the kernels are segment.hip) ----
+void segment_check_count(const char* who, int C) {
+    if (C < 1 || C > NLE_REGION_MAX)
+        throw Fail{NLE_ERR_INVALID, std::string(who) + " takes 1 to " + std::to_string(NLE_REGION_MAX) + " segments, got " +
+                                        std::to_string(C)};
+}
+
+// the C planes of n floats `stride` apart must not meet the `bytes` bytes at p
+bool segment_overlaps(const float* planes, int C, long long n, long long stride, const void* p, size_t bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(planes), a1 = a0 + ((size_t)(C - 1) * stride + n) * sizeof(float);
+    const uintptr_t b0 = reinterpret_cast<uintptr_t>(p), b1 = b0 + bytes;
+    return a0 < b1 && b0 < a1;
+}
+
+// the step's results on the device and their copy on the host; one download per fetch()
+struct SegmentStep {
+    nle_ctx* c;
+    DevBuf<nlek::SegmentResult> d_r;
+    DevBuf<double> d_partial;
+    nlek::SegmentResult r{};
+    SegmentStep(nle_ctx* ctx, long long n) : c(ctx), d_r(1), d_partial((size_t)nlek::segment_stats_blocks(n) * nlek::kRegionMax) {
+        HIP_OK(hipMemsetAsync(d_r.p, 0, sizeof(nlek::SegmentResult), c->stream));
+    }
+    void stats(const float* d_q, long long q_stride, int C, long long n, const unsigned char* d_labels) {
+        HIP_OK(nlek::segment_stats(c->stream, d_q, q_stride, C, n, d_labels, d_partial.p, d_r.p));
+    }
+    void means(const double* h_m, int C) {
+        HIP_OK(hipMemcpyAsync(&d_r.p->mean[0], h_m, sizeof(double) * C, hipMemcpyHostToDevice, c->stream));
+    }
+    void assign(const float* d_q, long long q_stride, int C, long long n, unsigned char* d_labels, float* d_ind, long long ind_stride) {
+        HIP_OK(nlek::segment_assign(c->stream, d_q, q_stride, C, n, d_labels, d_ind, ind_stride, d_r.p));
+    }
+    void fetch() {
+        HIP_OK(hipMemcpyAsync(&r, d_r.p, sizeof r, hipMemcpyDeviceToHost, c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+    }
+};
+
+// b_1 .. b_{C-1} of the start from the counts of nle_plane_histogram(x, 1)
+void segment_cuts(const long long* counts, long long n, int C, int* cuts) {
+    for (int k = 1; k < C; ++k) {
+        const long long need = (long long)((__int128)n * k / C) + 1;
+        long long cum = counts[0];
+        int b = NLE_TONE_BINS;
+        for (int j = 0; j < NLE_TONE_BINS; ++j) {
+            cum += counts[1 + j];
+            if (cum >= need) {
+                b = j;
+                break;
+            }
+        }
+        cuts[k - 1] = b;
+    }
+}
+
+void segment_init_impl(nle_ctx* c, const float* d_x, long long n, int C, unsigned char* d_labels, int* h_cuts) {
+    std::vector<long long> counts(nlek::kToneCounts);
+    plane_histogram_impl(c, d_x, n, 1.0, counts.data());
+    nlek::SegmentCuts cuts{};
+    segment_cuts(counts.data(), n, C, cuts.b);
+    if (h_cuts) std::copy(cuts.b, cuts.b + (C - 1), h_cuts);
+    HIP_OK(nlek::segment_init(c->stream, d_x, n, C, cuts, d_labels));
+    HIP_OK(hipStreamSynchronize(c->stream));
+}
+
+[[noreturn]] void segment_bad_label(const char* who, unsigned long long bad, int C) {
+    throw Fail{NLE_ERR_INVALID, std::string(who) + ": " + std::to_string(bad) + " labels are not below C = " + std::to_string(C)};
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------ C ABI
@@ -974,6 +1043,122 @@ int nle_plane_histogram(nle_ctx* ctx, const float* d_x, long long n, double scal
         if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_plane_histogram: n must be >= 1"};
         if (!std::isfinite(scale)) throw Fail{NLE_ERR_INVALID, "nle_plane_histogram: the scale is not finite"};
         plane_histogram_impl(ctx, d_x, n, scale, h_counts);
+    });
+}
+
+int nle_segment_init(nle_ctx* ctx, const float* d_x, long long n, int C, unsigned char* d_labels, int* h_cuts) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_x || !d_labels) throw Fail{NLE_ERR_INVALID, "nle_segment_init: NULL pointer"};
+        segment_check_count("nle_segment_init", C);
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_segment_init: n must be >= 1"};
+        segment_init_impl(ctx, d_x, n, C, d_labels, h_cuts);
+    });
+}
+
+int nle_segment_stats(nle_ctx* ctx, const float* d_q, int C, long long n, long long q_stride, const unsigned char* d_labels,
+                      long long* h_counts, double* h_sums) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_q || !d_labels || !h_counts || !h_sums) throw Fail{NLE_ERR_INVALID, "nle_segment_stats: NULL pointer"};
+        segment_check_count("nle_segment_stats", C);
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_segment_stats: n must be >= 1"};
+        if (q_stride != 0 && q_stride < n) throw Fail{NLE_ERR_INVALID, "nle_segment_stats: the plane stride is neither 0 nor >= n"};
+        HIP_OK(hipSetDevice(ctx->device));
+        SegmentStep step(ctx, n);
+        step.stats(d_q, q_stride, C, n, d_labels);
+        step.fetch();
+        if (step.r.bad) segment_bad_label("nle_segment_stats", step.r.bad, C);
+        for (int c = 0; c < C; ++c) h_counts[c] = (long long)step.r.count[c], h_sums[c] = step.r.sum[c];
+    });
+}
+
+int nle_segment_assign(nle_ctx* ctx, const float* d_q, int C, long long n, long long q_stride, const double* h_m,
+                       unsigned char* d_labels, float* d_indicators, long long ind_stride, long long* h_counts,
+                       long long* h_changed) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_q || !h_m || !d_labels || !h_counts || !h_changed) throw Fail{NLE_ERR_INVALID, "nle_segment_assign: NULL pointer"};
+        segment_check_count("nle_segment_assign", C);
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_segment_assign: n must be >= 1"};
+        if (q_stride != 0 && q_stride < n) throw Fail{NLE_ERR_INVALID, "nle_segment_assign: the plane stride is neither 0 nor >= n"};
+        if (d_indicators && C > 1 && ind_stride < n)
+            throw Fail{NLE_ERR_INVALID, "nle_segment_assign: the indicator stride is smaller than n"};
+        if (segment_overlaps(d_q, C, n, q_stride, d_labels, (size_t)n))
+            throw Fail{NLE_ERR_INVALID, "nle_segment_assign: the labels overlap the planes"};
+        if (d_indicators && (segment_overlaps(d_indicators, C, n, C > 1 ? ind_stride : n, d_labels, (size_t)n) ||
+                             segment_overlaps(d_indicators, C, n, C > 1 ? ind_stride : n, d_q,
+                                              ((size_t)(C - 1) * q_stride + n) * sizeof(float))))
+            throw Fail{NLE_ERR_INVALID, "nle_segment_assign: the indicator planes overlap an input"};
+        HIP_OK(hipSetDevice(ctx->device));
+        SegmentStep step(ctx, n);
+        step.means(h_m, C);
+        step.assign(d_q, q_stride, C, n, d_labels, d_indicators, C > 1 ? ind_stride : n);
+        step.fetch();
+        if (step.r.bad_new) segment_bad_label("nle_segment_assign", step.r.bad_new, C);
+        for (int c = 0; c < C; ++c) h_counts[c] = (long long)step.r.new_count[c];
+        *h_changed = (long long)step.r.changed;
+    });
+}
+
+int nle_filter_segment(nle_filter* f, int H, int W, int C, double spread, int max_iter, unsigned char* d_labels, float* d_q,
+                       long long q_stride, long long* h_counts, double* h_objective, int* h_iters, int* h_converged) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        nle_ctx* c = f->ctx;
+        if (!d_labels || !h_counts || !h_objective || !h_iters || !h_converged)
+            throw Fail{NLE_ERR_INVALID, "nle_filter_segment: NULL pointer"};
+        segment_check_count("nle_filter_segment", C);
+        if (!std::isfinite(spread) || !(spread > 0))
+            throw Fail{NLE_ERR_INVALID, "the segment spread must be finite and > 0, got " + std::to_string(spread)};
+        if (max_iter < 1 || max_iter > NLE_SEGMENT_ITERATIONS_MAX)
+            throw Fail{NLE_ERR_INVALID, "nle_filter_segment takes 1 to " + std::to_string(NLE_SEGMENT_ITERATIONS_MAX) +
+                                            " iterations, got " + std::to_string(max_iter)};
+        if (c->world > 1)
+            throw Fail{NLE_ERR_INVALID, "nle_filter_segment runs on one device only (world == 1): slabs and device groups are not built"};
+        check_plane_size(f, H, W, true);
+        const long long n = f->n_local;  // == H W: world == 1
+        if (d_q && C > 1 && q_stride < n) throw Fail{NLE_ERR_INVALID, "nle_filter_segment: the plane stride is smaller than n"};
+        if (d_q && segment_overlaps(d_q, C, n, C > 1 ? q_stride : n, d_labels, (size_t)n))
+            throw Fail{NLE_ERR_INVALID, "nle_filter_segment: the labels overlap the planes"};
+        HIP_OK(hipSetDevice(c->device));
+        DevBuf<float> d_ind((size_t)C * n), d_work((size_t)C * n);
+        SegmentStep step(c, n);
+        double scale[NLE_REGION_MAX];
+        long long counts[NLE_REGION_MAX];
+        auto spread_now = [&] {
+            for (int k = 0; k < C; ++k) scale[k] = counts[k] ? (double)n / (double)counts[k] : 0.0;
+            region_spread_impl(f, d_ind.p, C, H, W, scale, spread, d_work.p);
+        };
+        // the indicator planes and the counts of the start: the assignment kernel without planes, which keeps every label
+        step.assign(nullptr, 0, C, n, d_labels, d_ind.p, n);
+        step.fetch();
+        if (step.r.bad_new) segment_bad_label("nle_filter_segment", step.r.bad_new, C);
+        for (int k = 0; k < C; ++k) counts[k] = (long long)step.r.new_count[k];
+        int iters = 0;
+        bool converged = false;
+        while (iters < max_iter && !converged) {
+            spread_now();
+            step.stats(d_work.p, n, C, n, d_labels);
+            step.assign(d_work.p, n, C, n, d_labels, d_ind.p, n);
+            step.fetch();  // the iteration's one download
+            double J = 0.0;
+            for (int k = 0; k < C; ++k)
+                if (step.r.count[k]) J += (double)step.r.count[k] * step.r.mean[k];
+            h_objective[iters++] = J / (double)n;
+            for (int k = 0; k < C; ++k) counts[k] = (long long)step.r.new_count[k];
+            converged = step.r.changed == 0;
+        }
+        if (d_q) {
+            if (!converged) spread_now();  // the last assignment moved labels: the spreads of what is returned
+            for (int k = 0; k < C; ++k)
+                HIP_OK(hipMemcpyAsync(d_q + (size_t)k * (C > 1 ? q_stride : n), d_work.p + (size_t)k * n, (size_t)n * sizeof(float),
+                                      hipMemcpyDeviceToDevice, c->stream));
+            HIP_OK(hipStreamSynchronize(c->stream));
+        }
+        std::copy(counts, counts + C, h_counts);
+        *h_iters = iters;
+        *h_converged = converged ? 1 : 0;
     });
 }
 

@@ -45,6 +45,14 @@ struct FilterArgs {
     nle::ToneOptions tone;           // --shadows S, --highlights Hh, --auto-levels P, --equalise A (enhance only)
     bool toneLine = false;           // --auto-levels or --equalise was given: one more stdout line, the curve's range
     nle::DenoiseOptions denoise;     // --prefilter bilateral|nlm, --glide, --noise-sigma S, --nlm-h H (denoise only)
+    // --segments C (enhance only), --segment-spread T, --segment-iterations I, --segment-map FILE, --segment-weights
+    // c:w1,w2,... (repeatable; Region::mask holds c as given, segmentOf its number)
+    int segments = 0;
+    double segmentSpread = 4;
+    int segmentIterations = 40;
+    std::string segmentMap;
+    std::vector<Region> segmentWeights;
+    std::vector<int> segmentOf;
     bool nystromReport = false;  // --nystrom-report (enhance only)
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
@@ -55,8 +63,8 @@ constexpr int kEnhance = (int)Tool::Enhance, kDenoise = (int)Tool::Denoise, kBot
 // what an option takes.  A flag is the word alone, `--flag=...` is refused; FlagAnySuffix also claims every other word
 // that starts with its name (and refuses it).  The numbers are finite doubles: any, > 0, >= 0, in [lo, hi], in (lo, hi];
 // Integer is a whole number in [lo, hi]; Word is one of `words`; FileName is a word that does not start with `--`; Region
-// is MASK:w1,w2,... split at the last `:`, finite weights.
-enum class Takes { Flag, FlagAnySuffix, Finite, Positive, NonNegative, Closed, HalfOpen, Integer, Word, FileName, Region };
+// is MASK:w1,w2,... split at the last `:`, finite weights; SegmentWeights is c:w1,w2,... likewise, c a whole number in [lo, hi].
+enum class Takes { Flag, FlagAnySuffix, Finite, Positive, NonNegative, Closed, HalfOpen, Integer, Word, FileName, Region, SegmentWeights };
 
 struct Word {
     const char* word;
@@ -93,6 +101,7 @@ inline const char kNystromElsewhere[] = "the residual report belongs to enhance"
 inline const char kTonemapElsewhere[] = "--tonemap (HDR tone mapping) is built for enhance only";
 inline const char kDetailElsewhere[] = "the detail options weigh layers, which this tool does not take";
 inline const char kToneElsewhere[] = "the base tone curve remaps a layer, which this tool does not take";
+inline const char kSegmentElsewhere[] = "automatic regions propose where layer weights go, which this tool does not take";
 inline const char kDenoiseElsewhere[] = "the pre-filter and the MSE-guided shrinkage belong to denoise";
 
 // One row per option.  What holds between options (--noise-sigma needs ..., --exact does not combine with ...) is the
@@ -148,6 +157,21 @@ inline const Option kOptions[] = {
     {"--equalise", "the share of histogram equalisation in the base tone curve (nle::ToneOptions)", kEnhance, Takes::Closed, 0, 1, nullptr,
      [](FilterArgs& a, const Value& v) { a.tone.equalise = v.x, a.toneLine = true; }, "--equalise takes a finite number in [0, 1]",
      kToneElsewhere},
+    {"--segments", "automatic regions (NLEFilter::segment): C segments proposed by the trained filter; two more kinds of stdout line",
+     kEnhance, Takes::Integer, 2, NLE_REGION_MAX, nullptr, [](FilterArgs& a, const Value& v) { a.segments = (int)v.x; },
+     "--segments takes an integer in [2, " NLECLI_STR(NLE_REGION_MAX) "]", kSegmentElsewhere},
+    {"--segment-spread", "how far a segment's indicator spreads (nle::SegmentOptions::spread)", kEnhance, Takes::Positive, 0, 0, nullptr,
+     [](FilterArgs& a, const Value& v) { a.segmentSpread = v.x; }, "--segment-spread takes a finite number > 0", kSegmentElsewhere},
+    {"--segment-iterations", "the cap on the iterations (nle::SegmentOptions::maxIterations)", kEnhance, Takes::Integer, 1,
+     NLE_SEGMENT_ITERATIONS_MAX, nullptr, [](FilterArgs& a, const Value& v) { a.segmentIterations = (int)v.x; },
+     "--segment-iterations takes an integer in [1, " NLECLI_STR(NLE_SEGMENT_ITERATIONS_MAX) "]", kSegmentElsewhere},
+    {"--segment-map", "the labels as an 8-bit grey image, segment c at round(255 c / (C - 1)), written to FILE", kEnhance, Takes::FileName,
+     0, 0, nullptr, [](FilterArgs& a, const Value& v) { a.segmentMap = v.text; }, "--segment-map takes a file name", kSegmentElsewhere},
+    {"--segment-weights", "the layer weights of segment c (NLEFilter::enhanceSegments): as many as positional ones, which every other "
+                          "segment keeps; once per segment",
+     kEnhance, Takes::SegmentWeights, 0, NLE_REGION_MAX - 1, nullptr,
+     [](FilterArgs& a, const Value& v) { a.segmentWeights.push_back(v.region), a.segmentOf.push_back((int)v.x); },
+     "--segment-weights takes c:w1,w2,... (a segment number and finite weights)", kSegmentElsewhere},
     {"--prefilter", "the pre-filter of the MSE-guided denoiser (nle::DenoiseOptions)", kDenoise, Takes::Word, 0, 0, kPrefilters,
      [](FilterArgs& a, const Value& v) { a.denoise.prefilter = (int)v.x; }, "--prefilter takes 'bilateral' or 'nlm'", kDenoiseElsewhere},
     {"--glide", "shrink every plane by the power the MSE estimate picks; the positional shrink factor is the upper end of the search",
@@ -239,6 +263,11 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
                 got = word + " " + v.text;
                 break;
             case Takes::Region: ok = region(v.text, &v.region); break;
+            case Takes::SegmentWeights: {
+                const Option segment = {"", "", 0, Takes::Integer, o->lo, o->hi, nullptr, nullptr, "", ""};
+                ok = region(v.text, &v.region) && number(segment, v.region.mask, &v.x);
+                break;
+            }
             default: ok = number(*o, v.text, &v.x);
         }
         if (!ok) refuse(prog, std::string(o->takesText) + ", got '" + got + "'");
@@ -284,6 +313,25 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
                                  "16-bit enhance");
     if ((is_given("--region-spread") || is_given("--region-floor")) && a->regions.empty())
         refuse(prog, "--region-spread and --region-floor need at least one --region");
+    const std::string segmentGiven = last({"--segment-spread", "--segment-iterations", "--segment-map", "--segment-weights"});
+    if (!segmentGiven.empty() && a->segments == 0) refuse(prog, segmentGiven + " needs --segments C");
+    if (a->segments != 0) {
+        if (!a->regions.empty() || a->deep || a->tonemap)
+            refuse(prog, "--segments does not combine with --region, --deep or --tonemap: the segments are the regions of an 8-bit "
+                         "region edit");
+        if (!detailGiven.empty() || !toneGiven.empty())
+            refuse(prog, (detailGiven.empty() ? toneGiven : detailGiven) +
+                             " does not combine with --segments: region edits have no residual layer, no detail curve and no tone curve");
+        for (size_t k = 0; k < a->segmentOf.size(); ++k) {
+            if (a->segmentOf[k] >= a->segments)
+                refuse(prog, "--segment-weights " + a->segmentWeights[k].mask + ": there are " + std::to_string(a->segments) +
+                                 " segments, numbered from 0");
+            for (size_t j = 0; j < k; ++j)
+                if (a->segmentOf[j] == a->segmentOf[k])
+                    refuse(prog, "--segment-weights can be given once per segment, segment " + std::to_string(a->segmentOf[k]) +
+                                     " has two");
+        }
+    }
     if (first > 1) {
         shifted.push_back(argv[0]);  // the rest parses as a reference command line
         for (int i = first; i < argc; ++i) shifted.push_back(argv[i]);
@@ -324,6 +372,13 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
             if (r.weights.size() != a->extra.size())
                 refuse(prog, "--region " + r.mask + " has " + std::to_string(r.weights.size()) + " weights, the command line has " +
                                  std::to_string(a->extra.size()));
+    }
+    if (!a->segmentWeights.empty()) {  // every segment has the positional weight count
+        if ((int)a->extra.size() > NLE_REGION_LAYERS_MAX) refuse(prog, "--segment-weights" + most);
+        for (const auto& r : a->segmentWeights)
+            if (r.weights.size() != a->extra.size())
+                refuse(prog, "--segment-weights " + r.mask + " has " + std::to_string(r.weights.size()) +
+                                 " weights, the command line has " + std::to_string(a->extra.size()));
     }
     return true;
 }

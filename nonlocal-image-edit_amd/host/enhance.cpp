@@ -8,7 +8,12 @@
 // (mean, max and its pixel, share of pixels above 0.5) and `--nystrom-map FILE` writes the map as an 8-bit grey image,
 // round(255 clamp(r, 0, 1)); `--deep` and `--tonemap` print the same banners.  `--shadows`, `--highlights`, `--auto-levels`
 // and `--equalise` pass the base layer through a tone curve (nle::ToneOptions); with either of the last two one more stdout
-// line follows the banner, `Tone curve: levels <lo> <hi>`: the range the curve was laid over.
+// line follows the banner, `Tone curve: levels <lo> <hi>`: the range the curve was laid over.  `--segments C` lets the trained
+// filter propose C regions (NLEFilter::segment): after the banner `Segments: <C> iterations <I> converged <yes|no> objective
+// <J>` and one line `Segment <c>: <n> pixels, mean L <m>` per segment; `--segment-map FILE` writes the labels as an 8-bit grey
+// image, segment c at round(255 c / (C - 1)); `--segment-weights c:w1,w2,...` gives segment c layer weights of its own
+// (NLEFilter::enhanceSegments) -- without one the image written is the plain command's, byte for byte.  Two runs give the same
+// labels: the first to look at the map and the lines, the second with weights.
 #include <algorithm>
 
 #include "cli_common.hpp"
@@ -48,15 +53,43 @@ int main(int argc, char* argv[]) {
     filter.sampler = a.sampler;
     filter.exact = a.exact;
     filter.chromaBandwidth = a.chroma;
+    filter.keepTrainPlane = a.segments != 0;  // segment() starts from the plane the train ran on
     if (a.tonemap) filter.trainForToneMapping(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
     else filter.trainForEnhancement(image, a.rowSamples, a.colSamples, a.hx, a.hy, a.sinkhornIters, a.eigenVectors);
-    // (inactive detail and tone options are the plain methods)
-    const nle::Image result = a.tonemap        ? filter.toneMap(image, a.extra, a.tonemapSaturation, a.detail)
-                              : strokes.empty() ? filter.enhance(image, a.extra, a.detail, a.tone)  // the weights are argv[9..]
-                                                : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,
-                                                                        a.regionFloor);
+    nle::Image labels;
+    std::vector<std::vector<double>> segmentWeights((size_t)a.segments);
+    if (a.segments) {
+        nle::SegmentOptions o;
+        o.count = a.segments, o.spread = a.segmentSpread, o.maxIterations = a.segmentIterations;
+        labels = filter.segment(o);
+        for (size_t k = 0; k < a.segmentOf.size(); ++k) segmentWeights[a.segmentOf[k]] = a.segmentWeights[k].weights;
+    }
+    // (inactive detail and tone options are the plain methods; segments without weights of their own leave the plain edit)
+    const nle::Image result = a.tonemap                  ? filter.toneMap(image, a.extra, a.tonemapSaturation, a.detail)
+                              : !a.segmentWeights.empty() ? filter.enhanceSegments(image, a.extra, segmentWeights)
+                              : strokes.empty()           ? filter.enhance(image, a.extra, a.detail, a.tone)  // the weights are argv[9..]
+                                                          : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,
+                                                                                  a.regionFloor);
     nlecli::report(filter);
     const int rc = nlecli::finish(a, result, "Done. Press any key in result window to exit.");  // src/enhance.cpp:45
+    if (a.segments) {
+        const nle::SegmentReport s = filter.lastSegments();
+        std::cout << "Segments: " << a.segments << " iterations " << s.iterations << " converged " << (s.converged ? "yes" : "no")
+                  << " objective " << s.objective << std::endl;
+        for (int c = 0; c < a.segments; ++c)
+            std::cout << "Segment " << c << ": " << s.counts[c] << " pixels, mean L " << s.meanL[c] << std::endl;
+        if (!a.segmentMap.empty()) {
+            nle::Image grey(image.rows, image.cols, nle::NLE_8U, 3);  // grey as three equal channels (what the writers take)
+            for (size_t i = 0; i < image.total(); ++i) {
+                const unsigned char v = (unsigned char)std::nearbyint(255.0 * labels.ptr<unsigned char>()[i] / (a.segments - 1));
+                grey.ptr<unsigned char>()[3 * i] = grey.ptr<unsigned char>()[3 * i + 1] = grey.ptr<unsigned char>()[3 * i + 2] = v;
+            }
+            if (!nle::imwrite(a.segmentMap, grey)) {
+                std::cerr << "Failed to write " << a.segmentMap << std::endl;
+                return 1;
+            }
+        }
+    }
     if (a.toneLine) {
         const nle::ToneLevels t = filter.lastToneCurve();
         std::cout << "Tone curve: levels " << t.lo << " " << t.hi << std::endl;

@@ -37,14 +37,28 @@ nle_filter* train_step(nle_ctx* c, const NLEFilter& o, const float* d_lum, int r
     return f;
 }
 
+// a device buffer handed over to shared ownership (the copies of an NLEFilter share what its train left)
+std::shared_ptr<void> keep_plane(Dev& d) {
+    nle_ctx* c = d.c;
+    void* p = d.p;
+    d.p = nullptr;
+    return std::shared_ptr<void>(p, [c](void* q) {
+        if (q) nle_dev_free(c, q);
+    });
+}
+
 // rows [r0, r1) of a BGR image -- all of it, or a rank's slab (slab input: the train still takes the image's size) --
 // on ctx c: getLuminanceChannel (:460-469) on the device, BGR -> Lab (8 bit) -> L as float (and the a and b planes of
 // the same Lab image, alive for the train, when the filter has a chroma bandwidth), then the train step.  Under a group
 // a patch radius, a sampler other than the grid, the exact mode and chroma are refused by the train (world > 1).
-nle_filter* train_rows(nle_ctx* c, const NLEFilter& o, const Image& image, int r0, int r1, const TrainArgs& a) {
+// keepL (may be null) receives the L plane after the train: what NLEFilter::segment starts from.
+nle_filter* train_rows(nle_ctx* c, const NLEFilter& o, const Image& image, int r0, int r1, const TrainArgs& a,
+                       std::shared_ptr<void>* keepL) {
     const bool chroma = o.chromaBandwidth != 0;
-    const LabPlanes in = lab_planes(c, image.ptr<unsigned char>(r0), (size_t)(r1 - r0) * image.cols, chroma, chroma);
-    return train_step(c, o, in.L.f(), image.rows, image.cols, a, in.a.f(), in.b.f());
+    LabPlanes in = lab_planes(c, image.ptr<unsigned char>(r0), (size_t)(r1 - r0) * image.cols, chroma, chroma);
+    nle_filter* f = train_step(c, o, in.L.f(), image.rows, image.cols, a, in.a.f(), in.b.f());
+    if (keepL) *keepL = keep_plane(in.L);
+    return f;
 }
 
 // One luminance edit per image kind.  The kind fixes the prologue and the epilogue; `op(d_x, d_y)` is the operator on the
@@ -167,6 +181,10 @@ void NLEFilter::beginTrain(nle_ctx* c) {
     hdrHi_ = hdrRange_ = 0;  // trainForToneMapping sets them after its train
     denoiseTrained_ = false;  // trainForDenoise likewise
     denoiseReport_ = DenoiseReport();
+    trainPlane_.reset();  // trainForEnhancement sets it after its train; a segmentation belongs to the filter it was made on
+    segmentSpreads_.reset();
+    segmentCount_ = 0;
+    segmentReport_ = SegmentReport();
     if (verbose) {
         // the four stages run as one fused GPU pipeline; the banners keep the reference's stdout (:483-498)
         std::cout << "Computing kernel" << std::endl;
@@ -229,10 +247,11 @@ void NLEFilter::trainForEnhancement(const Image& image, int nRowSamples, int nCo
         // as for 8-bit images a group forms only when NLE_DEVICES lists two devices or more
         if (devices_env() != nullptr && device_group(-1) != nullptr) throw std::runtime_error(kDeepOneDevice);
         nle_ctx* c = shared_ctx();
-        const Lab16Planes in = lab16_planes(c, image, chromaBandwidth != 0, true);
+        Lab16Planes in = lab16_planes(c, image, chromaBandwidth != 0, true);
         const DeepChroma ab = deep_chroma_planes(c, in, image.total(), chromaBandwidth != 0);
         trainOnDevice(in.guide.f(), image.rows, image.cols, nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors,
                       ab.a.f(), ab.b.f());
+        if (keepTrainPlane) trainPlane_ = keep_plane(in.guide);
         return;
     }
     const TrainArgs a{nRowSamples, nColSamples, hx, hy, nSinkhornIter, nEigenVectors};
@@ -247,8 +266,12 @@ void NLEFilter::trainForEnhancement(const Image& image, int nRowSamples, int nCo
     const std::vector<nle_ctx*> ctxs = g ? g->ctx : std::vector<nle_ctx*>{shared_ctx()};
     beginTrain(ctxs[0]);
     std::vector<nle_filter*> fs(ctxs.size(), nullptr);
-    on_rows(g, ctxs[0], H, [&](nle_ctx* c, int r, int r0, int r1) { fs[r] = train_rows(c, *this, image, r0, r1, a); });
+    std::shared_ptr<void> plane;  // one device, on request: the L plane stays for segment()
+    on_rows(g, ctxs[0], H, [&](nle_ctx* c, int r, int r0, int r1) {
+        fs[r] = train_rows(c, *this, image, r0, r1, a, !g && keepTrainPlane ? &plane : nullptr);
+    });
     adopt(ctxs, fs, H, W, nEigenVectors);
+    trainPlane_ = plane;
 }
 
 void NLEFilter::trainForToneMapping(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,
@@ -575,6 +598,73 @@ Image NLEFilter::enhanceRegions(const Image& image, const std::vector<Image>& st
     return edit_8bit(ctx_, image, [&](const float* d_x, float* d_y) {
         check(nle_apply_regions(f_, d_x, image.rows, image.cols, L, d_s.f(), M, scale.data(), spread, floor, Wt.data(),
                                 NLE_REGION_OUT_ROUNDED8, d_y), ctx_);
+    });
+}
+
+Image NLEFilter::segment(const SegmentOptions& o) {
+    if (!f_) throw std::runtime_error("segment needs a trained filter.");
+    if (!group_.empty())
+        throw std::runtime_error("Automatic regions run on one device: this filter was trained on a device group (NLE_DEVICES).");
+    if (!trainPlane_)
+        throw std::runtime_error("segment needs a filter trained by trainForEnhancement with keepTrainPlane set (it starts from that plane).");
+    const int C = o.count;
+    if (C < 1 || C > NLE_REGION_MAX)
+        throw std::runtime_error("Automatic regions take 1 to " + std::to_string(NLE_REGION_MAX) + " segments.");
+    if (!std::isfinite(o.floor) || !(o.floor > 0)) throw std::runtime_error("The segment floor must be finite and > 0.");
+    const size_t n = (size_t)rows_ * cols_;
+    const float* d_x = static_cast<const float*>(trainPlane_.get());
+    Dev d_labels(ctx_, n), d_q(ctx_, (size_t)C * n * 4);
+    check(nle_segment_init(ctx_, d_x, (long long)n, C, d_labels.u8(), nullptr), ctx_);
+    SegmentReport r;
+    r.counts.assign(C, 0);
+    r.meanL.assign(C, 0.0);
+    std::vector<double> objective((size_t)std::max(o.maxIterations, 1)), sums(C);
+    int converged = 0;
+    check(nle_filter_segment(f_, rows_, cols_, C, o.spread, o.maxIterations, d_labels.u8(), d_q.f(), (long long)n, r.counts.data(),
+                             objective.data(), &r.iterations, &converged), ctx_);
+    // the mean L of a segment: the per-segment sums of the one plane (q_stride 0)
+    check(nle_segment_stats(ctx_, d_x, C, (long long)n, 0, d_labels.u8(), r.counts.data(), sums.data()), ctx_);
+    for (int c = 0; c < C; ++c) r.meanL[c] = r.counts[c] ? sums[c] / (double)r.counts[c] : 0.0;
+    r.converged = converged != 0;
+    r.objective = objective[r.iterations - 1];
+    r.valid = true;
+    Image labels(rows_, cols_, NLE_8U, 1);
+    check(nle_dev_download(ctx_, labels.ptr<unsigned char>(), d_labels.p, n), ctx_);
+    segmentSpreads_ = keep_plane(d_q);
+    segmentCount_ = C;
+    segmentFloor_ = o.floor;
+    segmentReport_ = r;
+    return labels;
+}
+
+Image NLEFilter::enhanceSegments(const Image& image, const std::vector<DType>& weights,
+                                  const std::vector<std::vector<DType>>& segmentWeights) const {
+    refuse_hdr(image, "enhanceSegments");
+    if (is_deep(image)) throw std::runtime_error("Segment edits take an 8-bit image: deep colour (16 bit) is built for enhance only.");
+    if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enhance RGB image.");
+    if (!group_.empty())
+        throw std::runtime_error("Automatic regions run on one device: this filter was trained on a device group (NLE_DEVICES).");
+    requireSize(image.total(), kTrainedSize);
+    if (!segmentSpreads_) throw std::runtime_error("enhanceSegments needs a segment() of this filter first.");
+    const int C = segmentCount_, L = (int)weights.size();
+    if (L < 1 || L > NLE_REGION_LAYERS_MAX)
+        throw std::runtime_error("Segment edits take 1 to " + std::to_string(NLE_REGION_LAYERS_MAX) + " weights.");
+    if ((int)segmentWeights.size() > C)
+        throw std::runtime_error("Segment edits take at most one weight vector per segment (" + std::to_string(C) + ").");
+    std::vector<double> Wt(weights);  // row 0 the background, row 1 + c segment c
+    for (int c = 0; c < C; ++c) {
+        const std::vector<DType>& w = c < (int)segmentWeights.size() && !segmentWeights[c].empty() ? segmentWeights[c] : weights;
+        if ((int)w.size() != L)
+            throw std::runtime_error("Segment " + std::to_string(c) + " has " + std::to_string(w.size()) +
+                                     " weights, the background has " + std::to_string(L) + ".");
+        Wt.insert(Wt.end(), w.begin(), w.end());
+    }
+    const long long n = (long long)image.total();
+    const float* d_q = static_cast<const float*>(segmentSpreads_.get());
+    Dev d_layers(ctx_, (size_t)L * n * 4);
+    return edit_8bit(ctx_, image, [&](const float* d_x, float* d_y) {
+        check(nle_apply_layers(f_, d_x, image.rows, image.cols, L, d_layers.f()), ctx_);
+        check(nle_region_combine(ctx_, d_layers.f(), L, d_q, C, n, n, n, Wt.data(), segmentFloor_, NLE_REGION_OUT_ROUNDED8, d_y), ctx_);
     });
 }
 
