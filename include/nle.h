@@ -777,6 +777,68 @@ int nle_segment_assign(nle_ctx* ctx, const float* d_q, int C, long long n, long 
 int nle_filter_segment(nle_filter* f, int H, int W, int C, double spread, int max_iter, unsigned char* d_labels, float* d_q,
                        long long q_stride, long long* h_counts, double* h_objective, int* h_iters, int* h_converged);
 
+/* ---- local adjustments: per-region detail, tone and saturation (new in this build: no reference, so this text and
+ * DESIGN.md section 3.20 are the definition) ---- */
+/* Every region gets the whole edit of its own -- layer weights, residual weight, detail curve, base tone curve, saturation --
+ * and the memberships of the region edits blend the results.  All arithmetic is per pixel i, in fp64, every operation rounded
+ * on its own (no fma), sums left to right in ascending m and l.
+ * Inputs: the plane x; the layers Y_0 .. Y_{L-1}, 1 <= L <= NLE_REGION_LAYERS_MAX; the memberships' source planes q_1 .. q_M,
+ * 1 <= M <= NLE_REGION_MAX (spread strokes, or the spreads of nle_filter_segment); the floor phi > 0; and for every row
+ * m = 0 .. M (row 0 the background): the weights W[m][0 .. L-1]; w_rho[m], the gain a_m in [0, NLE_DETAIL_GAIN_MAX] and
+ * sigma_m >= 0; a flag for a base curve; where it is on, a curve [lo_m, hi_m, T^m_0 .. T^m_N] in nle_tone_curve's layout.
+ *   Memberships  exactly nle_region_combine's:  u_m = q_m[i] > 0 ? (double)q_m[i] : 0 (a NaN q counts as 0);
+ *                sigma = u_1 + .. + u_M;  d = sigma > phi ? sigma : phi;  alpha_m = u_m / d;  alpha_0 = 1 - sigma / d
+ *   S, rho, g_m  exactly nle_detail_combine's, with row m's a_m and sigma_m; the curve of row m is off when sigma_m == 0 or
+ *                a_m == 1, and no exp is evaluated for it then
+ *   Row results  y_m = w_rho[m] g_m(rho) + W[m][0] g_m(Y_0) + .. + W[m][L-2] g_m(Y_{L-2}) + B_m, left to right, with
+ *                B_m = W[m][L-1] Y_{L-1} where row m has no base curve and nle_tone_combine's B' on row m's curve otherwise
+ *                (Bw = W[m][L-1] Y_{L-1}; ks_m = N / (hi_m - lo_m) formed once on the host)
+ *   Blend        c_m = alpha_m > 0 ? alpha_m y_m : 0;   y = ((c_0 + c_1) + ..) + c_M
+ *                A row without influence on a pixel contributes nothing, not even its NaN: the kernel does not evaluate it.
+ *   Output       the three NLE_REGION_OUT_* kinds with nle_region_combine's store rule; a NaN y is NaN in _F32, 0 in the others
+ *   Chroma       a saturation s_m in [0, 4] per row; planes a, b on the project's scale (128 is neutral, 8-bit and deep alike):
+ *                cm_m = alpha_m > 0 ? alpha_m s_m : 0;  c = ((cm_0 + cm_1) + ..) + cm_M
+ *                a' = 128 + c (a - 128);  b' = 128 + c (b - 128), each rounded once to fp32
+ * Consequences:
+ *   (a) where every q <= 0 (or NaN): alpha_0 = 1 and the output is bit for bit nle_detail_combine / nle_tone_combine with
+ *       row 0's parameters.  The sign of a zero is left open.
+ *   (b) M = 1 and q_1 >= phi everywhere: alpha_1 = 1, alpha_0 = 0, the output is bit for bit the same calls with row 1's.
+ *   (c) all rows equal: the alpha_m sum to 1 up to rounding, and y differs from the single-row result by at most (2 M + 4)
+ *       fp64 roundings of y; a _F32 output by at most one spacing; the 8-bit kinds are equal wherever the single-row value is
+ *       not within 1e-9 of a tie.
+ *   (d) every curve off, w_rho = 0 and no base curve: y is nle_region_combine's value up to the different association (the
+ *       rows are blended after the layers are summed, not before): not bitwise.
+ *   (e) all s_m = 1: c is 1 up to rounding (|c - 1| <= (2 M + 4) 2^-53, as in (c)), a' = a up to one fp32 spacing.  The C++ surface and the
+ *       CLI do not launch the chroma kernel then: the bytes are the plain command's.
+ * nle_local_combine is the stage call, the rule alone, on any planes: d_x n floats; layer l at d_layers + l layer_stride and
+ * plane m at d_q + (m - 1) q_stride (strides in floats, >= n); h_weights (M + 1) x L row-major; h_detail (M + 1) x 3 =
+ * (w_rho, gain, sigma) per row; h_curve_on M + 1 ints (NULL: no row has a base curve); h_curves (M + 1) x
+ * (NLE_TONE_KNOTS + 2), of which only the rows that are on are read (NULL exactly when none is on); d_out n floats, or n
+ * bytes for NLE_REGION_OUT_U8.  No alignment is required of pointers or strides; every plane is read once.  Only the curves
+ * that are on go to the device (8200 B of LDS each).
+ * nle_local_chroma: d_a, d_b n floats; d_q as above; h_saturation M + 1 doubles; d_a_out, d_b_out n floats each.  In place
+ * (d_a_out == d_a, d_b_out == d_b) is allowed; any other overlap of an output with an input or the other output is refused.
+ * nle_apply_local is nle_apply_layers + nle_region_spread + nle_local_combine with the L + M work planes in the ctx's workspace:
+ * bitwise what the three calls give, for every formulation nle_apply works for.  Strokes, scales, spread and floor as for
+ * nle_apply_regions.  d_q_out (may be NULL) receives the M spreads, plane m at d_q_out + (m - 1) H W: the membership planes
+ * nle_local_chroma takes, so that the chroma call does not spread twice.
+ * All three return NLE_ERR_INVALID with a message that starts with the function's name, enqueue nothing and leave the ctx
+ * usable for: M or L out of range; a NULL pointer (h_curve_on, h_scale and d_q_out apart; h_curves NULL while a flag is on);
+ * a weight, w_rho or saturation that is not finite, a saturation outside [0, 4]; a gain outside [0, 3] or not finite; a sigma
+ * that is negative or not finite; a floor or spread that is not finite and > 0; a scale that is not finite; a curve that is on
+ * with lo, hi or a knot not finite or hi - lo not > 0; an unknown out kind; an output overlapping an input (chroma's in-place
+ * case apart); n < 1 or a stride smaller than n (the stage calls); H W that is not the filter's and world > 1
+ * (nle_apply_local: slabs and device groups are not built for it, as for regions). */
+#define NLE_LOCAL_SATURATION_MAX 4
+int nle_local_combine(nle_ctx* ctx, const float* d_x, const float* d_layers, int L, const float* d_q, int M, long long n,
+                      long long layer_stride, long long q_stride, const double* h_weights, const double* h_detail,
+                      const int* h_curve_on, const double* h_curves, double floor, int out_kind, void* d_out);
+int nle_local_chroma(nle_ctx* ctx, const float* d_a, const float* d_b, const float* d_q, int M, long long n, long long q_stride,
+                     const double* h_saturation, double floor, float* d_a_out, float* d_b_out);
+int nle_apply_local(nle_filter* f, const float* d_x, int H, int W, int L, const float* d_strokes, int M, const double* h_scale,
+                    double spread, double floor, const double* h_weights, const double* h_detail, const int* h_curve_on,
+                    const double* h_curves, int out_kind, void* d_out, float* d_q_out);
+
 /* ---- several planes through one filter (new in this build) ---- */
 /* Applies f to P planes in one call, each plane with its own set of responses: the channels of a colour image, several guide
  * planes, the stroke planes of the region edits, the a / b pair of the denoiser.  nle_apply (P = 1, one response) and

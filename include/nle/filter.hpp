@@ -186,6 +186,15 @@ struct ToneLevels {
     bool valid = false;
 };
 
+// one row of NLEFilter::enhanceLocal / enhanceSegmentsLocal (new here; see there): the whole edit of a region, or of the
+// background -- layer weights (empty: the background's), the detail options, the two slopes of a base tone curve of its own
+// (both 0: no curve) and the saturation of a and b (1: untouched)
+struct LocalEdit {
+    std::vector<DType> weights;
+    DetailOptions detail;
+    DType shadows = 0, highlights = 0, saturation = 1;
+};
+
 // the options of NLEFilter::segment (new here; see there): the number of segments, how far a segment's indicator spreads
 // (the t of G = V lambda^t V^T), the cap on the iterations, and the membership floor enhanceSegments combines with
 struct SegmentOptions {
@@ -304,6 +313,20 @@ public:
     SegmentReport lastSegments() const { return segmentReport_; }
     Image enhanceSegments(const Image& I, const std::vector<DType>& weights,
                           const std::vector<std::vector<DType>>& segmentWeights) const;
+    // local adjustments (new here; nle_local_combine in nle.h states the rule): every region gets the
+    // whole edit of its own -- its layer weights, residual weight and detail curve, a base tone curve from its shadows and
+    // highlights (nle_tone_curve(NULL, shadows, highlights, -1, 0), switched on where one of the two is non-zero) and the
+    // saturation of a and b about 128 -- and the memberships of the region edits blend the rows' results, pixel by pixel.
+    // enhanceLocal: strokes, spread and floor as enhanceRegions takes them, edits[m] the row of strokes[m], `background` row 0
+    // (its weights give the layer count); 8-bit and 16-bit images (the latter on the unrounded L, a and b).
+    // enhanceSegmentsLocal: the same on the spreads and floor of the last segment(), like enhanceSegments: edits[c] is the row
+    // of segment c, the background's where it is missing; 8-bit images.  An edit with empty weights takes the background's.
+    // With every saturation 1 the chroma planes are not touched.  Both throw std::runtime_error for an HDR image, a filter
+    // trained on a device group, counts out of range, a weight count other than the background's, a saturation outside
+    // [0, NLE_LOCAL_SATURATION_MAX] and whatever nle_apply_local / nle_local_combine / nle_tone_curve refuse.
+    Image enhanceLocal(const Image& I, const std::vector<Image>& strokes, const std::vector<LocalEdit>& edits,
+                       const LocalEdit& background, DType spread = 4, DType floor = 0.05) const;
+    Image enhanceSegmentsLocal(const Image& I, const LocalEdit& background, const std::vector<LocalEdit>& edits) const;
     // include/filter.hpp:40-45: the filter is trained on the bilateral-filtered L channel; denoise shrinks the
     // eigenvalues to min(lambda, 1)^k on the a and b channels (src/filter.cpp:349-410, 521-538)
     void trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,

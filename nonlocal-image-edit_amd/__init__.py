@@ -52,6 +52,7 @@ KERNEL_COUNT_ALL = _abi.NLE_KERNEL_COUNT_ALL
 # the base tone curve: the knots of a curve (a curve is [lo, hi, T_0 .. T_N]: TONE_KNOTS + 2 values), the histogram's bins
 # (its counts: underflow, the bins, overflow and NaN: TONE_BINS + 2 values)
 TONE_KNOTS, TONE_BINS = _abi.NLE_TONE_KNOTS, _abi.NLE_TONE_BINS
+LOCAL_SATURATION_MAX = _abi.NLE_LOCAL_SATURATION_MAX  # nle_local_chroma: a row's saturation lies in [0, LOCAL_SATURATION_MAX]
 SEGMENT_ITERATIONS_MAX = _abi.NLE_SEGMENT_ITERATIONS_MAX  # nle_filter_segment: the cap on its iterations (C: 1 .. REGION_MAX)
 
 _lib = None
@@ -287,6 +288,28 @@ def _curve_ptr(curve, who):
     if c.size != TONE_KNOTS + 2:
         raise NLEError(NLE_ERR_INVALID, f"{who}: a curve holds {TONE_KNOTS + 2} values [lo, hi, T_0 .. T_N], got {c.size}")
     return c
+
+
+def _local_rows(who, M, L, weights, detail, curves):
+    """the per-row arguments of nle_local_combine / nle_apply_local as contiguous arrays: weights (M + 1, L); detail
+    (M + 1, 3) = (w_rho, gain, sigma) per row, None: (0, 1, 0) for every row; curves: None, or M + 1 entries, each None (no
+    base curve for that row) or a curve [lo, hi, T_0 .. T_N].  Returns (w, d, on, cv) with on / cv None where no curve is on."""
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.shape != (M + 1, L):
+        raise NLEError(NLE_ERR_INVALID, f"{who}: weights must be {(M + 1, L)}, got {w.shape}")
+    d = np.tile([0.0, 1.0, 0.0], (M + 1, 1)) if detail is None else np.ascontiguousarray(detail, dtype=np.float64)
+    if d.shape != (M + 1, 3):
+        raise NLEError(NLE_ERR_INVALID, f"{who}: detail must be {(M + 1, 3)} (w_rho, gain, sigma per row), got {d.shape}")
+    if curves is None or all(c is None for c in curves):
+        return w, d, None, None
+    if len(curves) != M + 1:
+        raise NLEError(NLE_ERR_INVALID, f"{who}: curves must hold M + 1 = {M + 1} entries, got {len(curves)}")
+    on = np.array([c is not None for c in curves], dtype=np.int32)
+    cv = np.zeros((M + 1, TONE_KNOTS + 2))
+    for m, c in enumerate(curves):
+        if c is not None:
+            cv[m] = _curve_ptr(c, who)
+    return w, d, on, cv
 
 
 def _combine_out(out, n, out_kind, device):
@@ -1163,6 +1186,42 @@ class Context:
                                       float(sigma), _np_ptr(cv), int(out_kind), C.c_void_p(out.data_ptr())), self._h)
         return out
 
+    def local_combine(self, x, layers, q, weights, detail=None, curves=None, floor=0.05, out_kind=0, out=None):
+        """nle_local_combine, the rule alone: x (n,), layers (L, n) and q (M, n) float32 device tensors, rows contiguous and
+        any stride >= n apart; weights (M + 1, L), row 0 the background; detail (M + 1, 3) = (w_rho, gain, sigma) per row
+        (None: 0, 1, 0); curves: None, or M + 1 entries, each None or a curve of tone_curve for that row's base layer.
+        Returns n float32 values, or n bytes for REGION_OUT_U8."""
+        self._sync_in()
+        L, n = layers.shape
+        M = q.shape[0]
+        if x.shape != (n,) or x.stride(0) != 1 or q.shape[1] != n or layers.stride(1) != 1 or q.stride(1) != 1:
+            raise NLEError(NLE_ERR_INVALID, "local_combine: x (n,), layers (L, n) and q (M, n) with contiguous rows")
+        w, d, on, cv = _local_rows("local_combine", M, L, weights, detail, curves)
+        out = _combine_out(out, n, out_kind, layers.device)
+        _check(lib().nle_local_combine(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(layers.data_ptr()), L,
+                                       C.c_void_p(q.data_ptr()), M, n, layers.stride(0) if L > 1 else n,
+                                       q.stride(0) if M > 1 else n, _np_ptr(w), _np_ptr(d), _np_ptr(on) if on is not None else None,
+                                       _np_ptr(cv) if cv is not None else None, float(floor), int(out_kind),
+                                       C.c_void_p(out.data_ptr())), self._h)
+        return out
+
+    def local_chroma(self, a, b, q, saturation, floor=0.05, out=None):
+        """nle_local_chroma: a, b (n,) and q (M, n) float32 device tensors; saturation M + 1 values, row 0 the background.
+        out: None (two new tensors), "inplace" (a and b are rewritten) or a pair of (n,) float32 tensors.  Returns (a', b')."""
+        torch = _torch()
+        self._sync_in()
+        M, n = q.shape
+        if a.shape != (n,) or b.shape != (n,) or a.stride(0) != 1 or b.stride(0) != 1 or q.stride(1) != 1:
+            raise NLEError(NLE_ERR_INVALID, "local_chroma: a (n,), b (n,) and q (M, n) with contiguous rows")
+        s = np.ascontiguousarray(saturation, dtype=np.float64)
+        if s.shape != (M + 1,):
+            raise NLEError(NLE_ERR_INVALID, f"local_chroma: saturation must hold M + 1 = {M + 1} values, got {s.shape}")
+        ao, bo = (a, b) if isinstance(out, str) and out == "inplace" else out if out is not None else (torch.empty_like(a), torch.empty_like(b))
+        _check(lib().nle_local_chroma(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(q.data_ptr()), M, n,
+                                      q.stride(0) if M > 1 else n, _np_ptr(s), float(floor), C.c_void_p(ao.data_ptr()),
+                                      C.c_void_p(bo.data_ptr())), self._h)
+        return ao, bo
+
     def _here(self, t):
         """t is a tensor on this ctx's device (its pointer is handed to kernels)"""
         return t.is_cuda and (t.device.index or 0) == self.device
@@ -1594,6 +1653,27 @@ class NLEFilter:
                                        cp, float(spread), float(floor), _np_ptr(w), int(out_kind),
                                        C.c_void_p(out.data_ptr())), self.ctx._h)
         return out
+
+    def apply_local(self, x, n_layers, strokes, weights, detail=None, curves=None, scale=None, spread=4.0, floor=0.05,
+                    out_kind=0, out=None, want_spreads=False):
+        """nle_apply_local: the layers of x, the spreads of the stroke planes and the local combine in one call.  weights,
+        detail and curves as for Context.local_combine.  want_spreads: (out, q) with q the (M, n_local) spreads, the membership
+        planes Context.local_chroma takes.  Returns n_local float32 values, or bytes for REGION_OUT_U8."""
+        torch = _torch()
+        x = self.ctx._lum(x)
+        H, W = x.shape
+        s = self._strokes(strokes)
+        M = s.shape[0]
+        c, cp = self._scale(scale, M)
+        w, d, on, cv = _local_rows("apply_local", M, int(n_layers), weights, detail, curves)
+        n = self.info()["n_local"]
+        out = _combine_out(out, n, out_kind, x.device)
+        q = torch.empty((M, n), dtype=torch.float32, device=x.device) if want_spreads else None
+        _check(lib().nle_apply_local(self._f, C.c_void_p(x.data_ptr()), H, W, int(n_layers), C.c_void_p(s.data_ptr()), M, cp,
+                                     float(spread), float(floor), _np_ptr(w), _np_ptr(d), _np_ptr(on) if on is not None else None,
+                                     _np_ptr(cv) if cv is not None else None, int(out_kind), C.c_void_p(out.data_ptr()),
+                                     C.c_void_p(q.data_ptr()) if q is not None else None), self.ctx._h)
+        return (out, q) if want_spreads else out
 
     def segment(self, count, spread=4.0, max_iter=40, labels=None, want_spreads=False):
         """nle_filter_segment: kernel k-means of the pixels on the trained affinity, `count` clusters.  labels: the start, n

@@ -13,6 +13,7 @@
 // functor.  Its NLE_TONE_KNOTS knots come from a device buffer and are staged into LDS once per workgroup (8 KB).
 #include <hip/hip_runtime.h>
 
+#include "detail_rule.h"
 #include "kernels.h"
 #include "nle.h"
 #include "plane_combine.h"
@@ -36,25 +37,9 @@ struct DetailArgs {
 // the base term of the detail rule: w_{L-1} Y_{L-1} as it is
 struct PlainBase {};
 
-// the base term of the tone rule: the piecewise-linear curve through the knots T (in LDS), end segments continued linearly.
-// A NaN Bw fails both comparisons: j = 0, f = NaN, B' = NaN.
-struct ToneBase {
-    const double* T;
-    double lo, ks;
-    __device__ __forceinline__ double operator()(double Bw) const {
-        constexpr int N = NLE_TONE_KNOTS - 1;
-        const double u = (Bw - lo) * ks;
-        const int j = u >= 0.0 ? (u < (double)N ? (int)u : N - 1) : 0;
-        const double f = u - (double)j;
-        const double t0 = T[j], t1 = T[j + 1];
-        return t0 + f * (t1 - t0);
-    }
-};
-
-__device__ __forceinline__ double remap(const DetailArgs& a, double d) {
-    const double t = d / a.sigma;
-    return d * (1.0 + a.gain_m1 * exp(-(t * t)));
-}
+// g with the curve on, and ToneBase, the base term of the tone rule (the curve through the knots T in LDS), are stated in
+// detail_rule.h, which local.hip shares
+__device__ __forceinline__ double remap(const DetailArgs& a, double d) { return detail_remap(a.sigma, a.gain_m1, d); }
 
 // y of the P consecutive pixels from i on.  rho needs every layer before the first term of y is formed, and each plane is
 // read once: the loop over the layers is unrolled to LMAX >= L under the uniform guard l < L, so that the loaded values
@@ -73,10 +58,7 @@ __device__ __forceinline__ void detail_pixels(const DetailArgs& a, long long i, 
     double S[P];
 #pragma unroll
     for (int l = 0; l < LMAX; ++l)
-        if (l < L) {
-#pragma unroll
-            for (int j = 0; j < P; ++j) S[j] = l == 0 ? (double)Y[l].v[j] : S[j] + (double)Y[l].v[j];
-        }
+        if (l < L) detail_sum_step(l, Y[l], S);
 #pragma unroll
     for (int j = 0; j < P; ++j) {
         const double rho = (double)X.v[j] - S[j];

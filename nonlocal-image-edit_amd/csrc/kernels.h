@@ -461,6 +461,24 @@ const char* tone_curve(const long long* counts, double shadows, double highlight
 hipError_t tone_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, long long n,
                         const DetailWeights& w, double w_rho, double gain, double sigma, const double* d_knots, double lo, double ks,
                         int out_kind, void* d_out);
+// local adjustments (local.hip; the rule is stated in include/nle.h at nle_local_combine): region_combine's memberships blend
+// the results of M + 1 rows, each the detail / tone rule with parameters of its own.  Row m: curve != 0 when sigma > 0 and
+// gain != 1; slot >= 0 is the index of its tone curve among the ncurves active ones (NLE_TONE_KNOTS knots each at d_knots,
+// device), u = (Bw - lo) ks; slot < 0: no base curve.  wt as RegionWeights.  local_chroma: a' = 128 + c (a - 128) with
+// c = the memberships' blend of saturation[0 .. M]; in place allowed.
+struct LocalRow {
+    double w_rho, gain_m1, sigma, lo, ks;
+    int curve, slot;
+};
+struct LocalRows {
+    LocalRow row[kRegionMax + 1];                    // the first M + 1 entries are read
+    double wt[(kRegionMax + 1) * kRegionLayersMax];  // the first (M + 1) * L entries are read
+};
+hipError_t local_combine(hipStream_t s, const float* d_x, const float* d_layers, long long layer_stride, int L, const float* d_q,
+                         long long q_stride, int M, long long n, const LocalRows& rows, const double* d_knots, int ncurves,
+                         double floor, int out_kind, void* d_out);
+hipError_t local_chroma(hipStream_t s, const float* d_a, const float* d_b, const float* d_q, long long q_stride, int M, long long n,
+                        const double* saturation, double floor, float* d_a_out, float* d_b_out);
 // automatic regions (segment.hip; the rule is stated in include/nle.h at nle_filter_segment).  Labels are one byte per
 // pixel, planes go by base pointer and stride in floats, C is 1 .. kRegionMax.  Everything a step leaves for the host sits
 // in one SegmentResult on the device (zeroed by the launcher where the kernels add to it).

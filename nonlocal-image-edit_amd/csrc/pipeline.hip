@@ -541,6 +541,72 @@ void tone_combine_impl(nle_ctx* c, const float* d_x, const float* d_layers, int 
     prof_flush(c);
 }
 
+// ---- local adjustments (include/nle.h "local adjustments"; the kernels are local.hip) ----
+// every refusal the stage combine and nle_apply_local share, before anything is enqueued: per row what nle_region_combine,
+// nle_detail_combine and nle_tone_combine refuse
+void local_check(const char* who, int L, int M, const double* h_weights, const double* h_detail, const int* h_curve_on,
+                 const double* h_curves, double floor, int out_kind) {
+    const std::string name(who);
+    if (L < 1 || L > NLE_REGION_LAYERS_MAX)
+        throw Fail{NLE_ERR_INVALID, name + " takes 1 to " + std::to_string(NLE_REGION_LAYERS_MAX) + " layers, got " + std::to_string(L)};
+    if (M < 1 || M > NLE_REGION_MAX)
+        throw Fail{NLE_ERR_INVALID, name + " takes 1 to " + std::to_string(NLE_REGION_MAX) + " regions, got " + std::to_string(M)};
+    if (!h_weights || !h_detail) throw Fail{NLE_ERR_INVALID, name + ": NULL pointer"};
+    if (!std::isfinite(floor) || !(floor > 0))
+        throw Fail{NLE_ERR_INVALID, name + ": the region floor must be finite and > 0, got " + std::to_string(floor)};
+    for (int m = 0; m <= M; ++m) {
+        const std::string row = name + ": row " + std::to_string(m) + ": ";
+        for (int l = 0; l < L; ++l)
+            if (!std::isfinite(h_weights[(size_t)m * L + l])) throw Fail{NLE_ERR_INVALID, row + "weight " + std::to_string(l) + " is not finite"};
+        const double w_rho = h_detail[3 * m], gain = h_detail[3 * m + 1], sigma = h_detail[3 * m + 2];
+        if (!std::isfinite(w_rho)) throw Fail{NLE_ERR_INVALID, row + "the residual weight is not finite"};
+        if (!std::isfinite(gain) || gain < 0 || gain > NLE_DETAIL_GAIN_MAX)
+            throw Fail{NLE_ERR_INVALID, row + "the detail gain must be finite and in [0, " + std::to_string(NLE_DETAIL_GAIN_MAX) +
+                                            "], got " + std::to_string(gain)};
+        if (!std::isfinite(sigma) || sigma < 0)
+            throw Fail{NLE_ERR_INVALID, row + "the detail sigma must be finite and >= 0, got " + std::to_string(sigma)};
+        if (h_curve_on && h_curve_on[m]) {
+            if (!h_curves) throw Fail{NLE_ERR_INVALID, name + ": NULL curves while the base curve of row " + std::to_string(m) + " is on"};
+            tone_check_curve((name + ": row " + std::to_string(m)).c_str(), h_curves + (size_t)m * (NLE_TONE_KNOTS + 2));
+        }
+    }
+    check_out_kind(name + ": unknown output kind ", out_kind, true);
+}
+
+// the curves that are on go to a buffer of the ctx's workspace, one after the other; the call returns with the stream
+// drained, so the host copy outlives the upload
+void local_combine_impl(nle_ctx* c, const float* d_x, const float* d_layers, int L, const float* d_q, int M, long long n,
+                        long long layer_stride, long long q_stride, const double* h_weights, const double* h_detail,
+                        const int* h_curve_on, const double* h_curves, double floor, int out_kind, void* d_out) {
+    nlek::LocalRows rows{};
+    std::copy(h_weights, h_weights + (size_t)(M + 1) * L, rows.wt);
+    std::vector<double> knots;
+    int ncurves = 0;
+    for (int m = 0; m <= M; ++m) {
+        nlek::LocalRow& r = rows.row[m];
+        const double gain = h_detail[3 * m + 1];
+        r.w_rho = h_detail[3 * m];
+        r.gain_m1 = gain - 1.0;
+        r.sigma = h_detail[3 * m + 2];
+        r.curve = r.sigma != 0.0 && gain != 1.0;
+        r.slot = -1;
+        r.lo = 0.0, r.ks = 0.0;
+        if (h_curve_on && h_curve_on[m]) {
+            const double* cv = h_curves + (size_t)m * (NLE_TONE_KNOTS + 2);
+            r.lo = cv[0];
+            r.ks = (double)(NLE_TONE_KNOTS - 1) / (cv[1] - cv[0]);
+            r.slot = ncurves++;
+            knots.insert(knots.end(), cv + 2, cv + 2 + NLE_TONE_KNOTS);
+        }
+    }
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<double> d_knots(std::max<size_t>(knots.size(), 1));
+    if (ncurves) HIP_OK(hipMemcpyAsync(d_knots.p, knots.data(), sizeof(double) * knots.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(nlek::local_combine(c->stream, d_x, d_layers, layer_stride, L, d_q, q_stride, M, n, rows, d_knots.p, ncurves, floor,
+                               out_kind, d_out));
+    HIP_OK(hipStreamSynchronize(c->stream));
+}
+
 // ---- automatic regions (include/nle.h "automatic regions"; the kernels are segment.hip) ----
 void segment_check_count(const char* who, int C) {
     if (C < 1 || C > NLE_REGION_MAX)
@@ -1213,6 +1279,100 @@ int nle_apply_tone(nle_filter* f, const float* d_x, int H, int W, int L, const d
         if (shadows == 0 && highlights == 0 && clip_percent < 0 && equalise == 0)  // inactive: nle_apply_detail
             detail_combine_impl(c, d_x, d_work.p, L, n, n, h_weights, w_rho, gain, sigma, out_kind, d_out);
         else tone_combine_impl(c, d_x, d_work.p, L, n, n, h_weights, w_rho, gain, sigma, curve.data(), out_kind, d_out);
+    });
+}
+
+int nle_local_combine(nle_ctx* ctx, const float* d_x, const float* d_layers, int L, const float* d_q, int M, long long n,
+                      long long layer_stride, long long q_stride, const double* h_weights, const double* h_detail,
+                      const int* h_curve_on, const double* h_curves, double floor, int out_kind, void* d_out) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_x || !d_layers || !d_q || !d_out) throw Fail{NLE_ERR_INVALID, "nle_local_combine: NULL pointer"};
+        local_check("nle_local_combine", L, M, h_weights, h_detail, h_curve_on, h_curves, floor, out_kind);
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_local_combine: n must be >= 1"};
+        if ((L > 1 && layer_stride < n) || (M > 1 && q_stride < n) || layer_stride < 0 || q_stride < 0)
+            throw Fail{NLE_ERR_INVALID, "nle_local_combine: a plane stride is smaller than n"};
+        detail_check_overlap("nle_local_combine", d_x, d_out, n, out_kind, "the plane");
+        for (int l = 0; l < L; ++l)
+            detail_check_overlap("nle_local_combine", d_layers + (size_t)l * layer_stride, d_out, n, out_kind, "a layer");
+        for (int m = 0; m < M; ++m)
+            detail_check_overlap("nle_local_combine", d_q + (size_t)m * q_stride, d_out, n, out_kind, "a membership plane");
+        local_combine_impl(ctx, d_x, d_layers, L, d_q, M, n, layer_stride, q_stride, h_weights, h_detail, h_curve_on, h_curves,
+                           floor, out_kind, d_out);
+    });
+}
+
+int nle_local_chroma(nle_ctx* ctx, const float* d_a, const float* d_b, const float* d_q, int M, long long n, long long q_stride,
+                     const double* h_saturation, double floor, float* d_a_out, float* d_b_out) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_a || !d_b || !d_q || !h_saturation || !d_a_out || !d_b_out) throw Fail{NLE_ERR_INVALID, "nle_local_chroma: NULL pointer"};
+        if (M < 1 || M > NLE_REGION_MAX)
+            throw Fail{NLE_ERR_INVALID, "nle_local_chroma takes 1 to " + std::to_string(NLE_REGION_MAX) + " regions, got " +
+                                            std::to_string(M)};
+        for (int m = 0; m <= M; ++m)
+            if (!std::isfinite(h_saturation[m]) || h_saturation[m] < 0 || h_saturation[m] > NLE_LOCAL_SATURATION_MAX)
+                throw Fail{NLE_ERR_INVALID, "nle_local_chroma: row " + std::to_string(m) + ": the saturation must be finite and in [0, " +
+                                                std::to_string(NLE_LOCAL_SATURATION_MAX) + "], got " + std::to_string(h_saturation[m])};
+        if (!std::isfinite(floor) || !(floor > 0))
+            throw Fail{NLE_ERR_INVALID, "nle_local_chroma: the region floor must be finite and > 0, got " + std::to_string(floor)};
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_local_chroma: n must be >= 1"};
+        if ((M > 1 && q_stride < n) || q_stride < 0) throw Fail{NLE_ERR_INVALID, "nle_local_chroma: a plane stride is smaller than n"};
+        // in place is each output on its own input, exactly; everything else must lie apart
+        const auto apart = [&](const float* p, const float* out, const char* out_name, const char* what) {
+            const uintptr_t i0 = reinterpret_cast<uintptr_t>(p), o0 = reinterpret_cast<uintptr_t>(out), len = (uintptr_t)n * sizeof(float);
+            if (i0 < o0 + len && o0 < i0 + len)
+                throw Fail{NLE_ERR_INVALID, std::string("nle_local_chroma: ") + out_name + " overlaps " + what};
+        };
+        if (d_a_out != d_a) apart(d_a, d_a_out, "d_a_out", "d_a");
+        if (d_b_out != d_b) apart(d_b, d_b_out, "d_b_out", "d_b");
+        apart(d_b, d_a_out, "d_a_out", "d_b");
+        apart(d_a, d_b_out, "d_b_out", "d_a");
+        apart(d_a_out, d_b_out, "d_b_out", "d_a_out");
+        for (int m = 0; m < M; ++m) {
+            apart(d_q + (size_t)m * q_stride, d_a_out, "d_a_out", "a membership plane");
+            apart(d_q + (size_t)m * q_stride, d_b_out, "d_b_out", "a membership plane");
+        }
+        HIP_OK(hipSetDevice(ctx->device));
+        HIP_OK(nlek::local_chroma(ctx->stream, d_a, d_b, d_q, q_stride, M, n, h_saturation, floor, d_a_out, d_b_out));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+int nle_apply_local(nle_filter* f, const float* d_x, int H, int W, int L, const float* d_strokes, int M, const double* h_scale,
+                    double spread, double floor, const double* h_weights, const double* h_detail, const int* h_curve_on,
+                    const double* h_curves, int out_kind, void* d_out, float* d_q_out) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        nle_ctx* c = f->ctx;
+        if (!d_x || !d_strokes || !d_out) throw Fail{NLE_ERR_INVALID, "nle_apply_local: NULL pointer"};
+        local_check("nle_apply_local", L, M, h_weights, h_detail, h_curve_on, h_curves, floor, out_kind);
+        try {
+            region_check_spread(f, M, H, W, h_scale, spread);
+        } catch (const Fail& e) {
+            throw Fail{e.code, "nle_apply_local: " + e.msg};
+        }
+        const long long n = f->n_local;  // == H W: world == 1
+        detail_check_overlap("nle_apply_local", d_x, d_out, n, out_kind, "the plane");
+        for (int m = 0; m < M; ++m)
+            detail_check_overlap("nle_apply_local", d_strokes + (size_t)m * n, d_out, n, out_kind, "a stroke plane");
+        if (d_q_out)
+            for (int m = 0; m < M; ++m)
+                detail_check_overlap("nle_apply_local", d_q_out + (size_t)m * n, d_out, n, out_kind, "d_q_out");
+        DevBuf<float> d_work((size_t)(L + M) * n);
+        // one batch over [x; s_1 .. s_M], as nle_apply_regions makes it: the L layers of x and one spread per stroke
+        std::vector<double> resp((size_t)(L + M) * f->K);
+        layer_resp(f->eigvals.data(), f->K, L, resp.data());
+        spread_resp(f, M, h_scale, spread, resp.data() + (size_t)L * f->K);
+        const float* planes[1 + NLE_REGION_MAX];
+        int nresp[1 + NLE_REGION_MAX];
+        planes[0] = d_x, nresp[0] = L;
+        for (int m = 0; m < M; ++m) planes[1 + m] = d_strokes + (size_t)m * H * W, nresp[1 + m] = 1;
+        apply_planes_impl(f, planes, 1 + M, H, W, nresp, resp.data(), d_work.p, n, false);
+        if (d_q_out)
+            HIP_OK(hipMemcpyAsync(d_q_out, d_work.p + (size_t)L * n, (size_t)M * n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        local_combine_impl(c, d_x, d_work.p, L, d_work.p + (size_t)L * n, M, n, n, n, h_weights, h_detail, h_curve_on, h_curves,
+                           floor, out_kind, d_out);
     });
 }
 

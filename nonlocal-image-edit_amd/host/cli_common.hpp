@@ -53,6 +53,17 @@ struct FilterArgs {
     std::string segmentMap;
     std::vector<Region> segmentWeights;
     std::vector<int> segmentOf;
+    // --local TARGET:key=value[,key=value...] (enhance only, repeatable): TARGET a mask file or @c; `given` and `value` by
+    // key in the order of kLocalKeys (entry 0, weights, keeps its values in `weights`); --saturation C: the background's
+    struct Local {
+        std::string target;
+        int segment = -1;  // c of @c; -1: a mask
+        std::vector<double> weights;
+        bool given[7] = {false, false, false, false, false, false, false};
+        double value[7] = {0, 0, 0, 0, 0, 0, 0};
+    };
+    std::vector<Local> locals;
+    double saturation = 1;
     bool nystromReport = false;  // --nystrom-report (enhance only)
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
@@ -64,7 +75,8 @@ constexpr int kEnhance = (int)Tool::Enhance, kDenoise = (int)Tool::Denoise, kBot
 // that starts with its name (and refuses it).  The numbers are finite doubles: any, > 0, >= 0, in [lo, hi], in (lo, hi];
 // Integer is a whole number in [lo, hi]; Word is one of `words`; FileName is a word that does not start with `--`; Region
 // is MASK:w1,w2,... split at the last `:`, finite weights; SegmentWeights is c:w1,w2,... likewise, c a whole number in [lo, hi].
-enum class Takes { Flag, FlagAnySuffix, Finite, Positive, NonNegative, Closed, HalfOpen, Integer, Word, FileName, Region, SegmentWeights };
+// Local is TARGET:key=value[,key=value...] split at the last `:`, the keys those of kLocalKeys.
+enum class Takes { Flag, FlagAnySuffix, Finite, Positive, NonNegative, Closed, HalfOpen, Integer, Word, FileName, Region, SegmentWeights, Local };
 
 struct Word {
     const char* word;
@@ -74,6 +86,7 @@ struct Value {  // a parsed value: the number (or the word's constant), the text
     double x = 0;
     std::string text;
     FilterArgs::Region region;
+    FilterArgs::Local local;
 };
 
 struct Option {
@@ -102,6 +115,7 @@ inline const char kTonemapElsewhere[] = "--tonemap (HDR tone mapping) is built f
 inline const char kDetailElsewhere[] = "the detail options weigh layers, which this tool does not take";
 inline const char kToneElsewhere[] = "the base tone curve remaps a layer, which this tool does not take";
 inline const char kSegmentElsewhere[] = "automatic regions propose where layer weights go, which this tool does not take";
+inline const char kLocalElsewhere[] = "local adjustments edit layers and colour per region, which this tool does not take";
 inline const char kDenoiseElsewhere[] = "the pre-filter and the MSE-guided shrinkage belong to denoise";
 
 // One row per option.  What holds between options (--noise-sigma needs ..., --exact does not combine with ...) is the
@@ -172,6 +186,16 @@ inline const Option kOptions[] = {
      kEnhance, Takes::SegmentWeights, 0, NLE_REGION_MAX - 1, nullptr,
      [](FilterArgs& a, const Value& v) { a.segmentWeights.push_back(v.region), a.segmentOf.push_back((int)v.x); },
      "--segment-weights takes c:w1,w2,... (a segment number and finite weights)", kSegmentElsewhere},
+    {"--local", "a local adjustment (NLEFilter::enhanceLocal / enhanceSegmentsLocal): TARGET is a mask as --region takes it, or @c, "
+                "segment c of --segments C; the keys are weights=w1/w2/... (as many as positional ones), residual, gain, sigma, "
+                "shadows, highlights and saturation, each at most once; a key not named is the background's, which is the "
+                "positional weights, --residual-weight, --detail-gain, --detail-sigma, --shadows, --highlights and --saturation; up "
+                "to NLE_REGION_MAX times",
+     kEnhance, Takes::Local, 0, 0, nullptr, [](FilterArgs& a, const Value& v) { a.locals.push_back(v.local); },
+     "--local takes TARGET:key=value[,key=value...] (a mask or @c, then at least one key)", kLocalElsewhere},
+    {"--saturation", "the background's saturation of a and b about 128 in a local adjustment (nle::LocalEdit::saturation)", kEnhance,
+     Takes::Closed, 0, NLE_LOCAL_SATURATION_MAX, nullptr, [](FilterArgs& a, const Value& v) { a.saturation = v.x; },
+     "--saturation takes a finite number in [0, " NLECLI_STR(NLE_LOCAL_SATURATION_MAX) "]", kLocalElsewhere},
     {"--prefilter", "the pre-filter of the MSE-guided denoiser (nle::DenoiseOptions)", kDenoise, Takes::Word, 0, 0, kPrefilters,
      [](FilterArgs& a, const Value& v) { a.denoise.prefilter = (int)v.x; }, "--prefilter takes 'bilateral' or 'nlm'", kDenoiseElsewhere},
     {"--glide", "shrink every plane by the power the MSE estimate picks; the positional shrink factor is the upper end of the search",
@@ -234,6 +258,95 @@ inline bool region(const std::string& v, FilterArgs::Region* r) {
     return true;
 }
 
+// the keys of --local, in the order of FilterArgs::Local::given; `takes` says what the value is (entry 0: a list)
+struct LocalKey {
+    const char* name;
+    Takes takes;
+    double lo, hi;
+    const char* takesText;
+};
+inline const LocalKey kLocalKeys[] = {
+    {"weights", Takes::Finite, 0, 0, "finite numbers w1/w2/..."},
+    {"residual", Takes::Finite, 0, 0, "a finite number"},
+    {"gain", Takes::Closed, 0, NLE_DETAIL_GAIN_MAX, "a finite number in [0, " NLECLI_STR(NLE_DETAIL_GAIN_MAX) "]"},
+    {"sigma", Takes::NonNegative, 0, 0, "a finite number >= 0"},
+    {"shadows", Takes::Closed, -1, 1, "a finite number in [-1, 1]"},
+    {"highlights", Takes::Closed, -1, 1, "a finite number in [-1, 1]"},
+    {"saturation", Takes::Closed, 0, NLE_LOCAL_SATURATION_MAX, "a finite number in [0, " NLECLI_STR(NLE_LOCAL_SATURATION_MAX) "]"},
+};
+constexpr int kLocalKeyCount = (int)(sizeof(kLocalKeys) / sizeof(kLocalKeys[0]));
+enum { kLocalWeights = 0, kLocalResidual, kLocalGain, kLocalSigma, kLocalShadows, kLocalHighlights, kLocalSaturation };
+
+// TARGET:key=value[,key=value...] split at the last `:`.  False with *why empty: the shape is wrong (the row's own text
+// says what it takes); false with *why set: what is wrong inside the spec
+inline bool local(const std::string& v, FilterArgs::Local* r, std::string* why) {
+    const size_t colon = v.rfind(':');
+    if (colon == std::string::npos || colon == 0 || colon + 1 >= v.size()) return false;
+    r->target = v.substr(0, colon);
+    if (r->target[0] == '@') {
+        const Option segment = {"", "", 0, Takes::Integer, 0, NLE_REGION_MAX - 1, nullptr, nullptr, "", ""};
+        double c;
+        if (!number(segment, r->target.substr(1), &c)) {
+            *why = "a segment target is @c with c a whole number in [0, " + std::to_string(NLE_REGION_MAX - 1) + "]";
+            return false;
+        }
+        r->segment = (int)c;
+    }
+    const std::string list = v.substr(colon + 1) + ",";
+    for (size_t p = 0, q; (q = list.find(',', p)) != std::string::npos; p = q + 1) {
+        const std::string item = list.substr(p, q - p);
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos || eq == 0) return false;
+        const std::string key = item.substr(0, eq), val = item.substr(eq + 1);
+        int k = 0;
+        while (k < kLocalKeyCount && key != kLocalKeys[k].name) ++k;
+        if (k == kLocalKeyCount) {
+            *why = "unknown key '" + key + "' (the keys are weights, residual, gain, sigma, shadows, highlights, saturation)";
+            return false;
+        }
+        if (r->given[k]) {
+            *why = "key '" + key + "' is given twice";
+            return false;
+        }
+        r->given[k] = true;
+        const Option one = {"", "", 0, kLocalKeys[k].takes, kLocalKeys[k].lo, kLocalKeys[k].hi, nullptr, nullptr, "", ""};
+        bool ok = true;
+        if (k == kLocalWeights) {
+            const std::string ws = val + "/";
+            for (size_t a = 0, b; ok && (b = ws.find('/', a)) != std::string::npos; a = b + 1) {
+                double x;
+                ok = number(one, ws.substr(a, b - a), &x);
+                r->weights.push_back(x);
+            }
+        } else {
+            ok = number(one, val, &r->value[k]);
+        }
+        if (!ok) {
+            *why = key + " takes " + kLocalKeys[k].takesText + ", got '" + val + "'";
+            return false;
+        }
+    }
+    return true;
+}
+
+// row `l` of a local adjustment (null: the background's row) as the C++ surface takes it: what the spec names, and the
+// background's for every key it does not
+inline nle::LocalEdit local_edit(const FilterArgs& a, const FilterArgs::Local* l) {
+    nle::LocalEdit e;
+    e.weights = a.extra;
+    e.detail = a.detail;
+    e.shadows = a.tone.shadows, e.highlights = a.tone.highlights, e.saturation = a.saturation;
+    if (!l) return e;
+    if (l->given[kLocalWeights]) e.weights = l->weights;
+    if (l->given[kLocalResidual]) e.detail.residualWeight = l->value[kLocalResidual];
+    if (l->given[kLocalGain]) e.detail.gain = l->value[kLocalGain];
+    if (l->given[kLocalSigma]) e.detail.sigma = l->value[kLocalSigma];
+    if (l->given[kLocalShadows]) e.shadows = l->value[kLocalShadows];
+    if (l->given[kLocalHighlights]) e.highlights = l->value[kLocalHighlights];
+    if (l->given[kLocalSaturation]) e.saturation = l->value[kLocalSaturation];
+    return e;
+}
+
 // false (after printing the usage line to stderr) when fewer than `min_argc` arguments were given
 inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool) {
     const char* prog = argv[0];
@@ -268,9 +381,17 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
                 ok = region(v.text, &v.region) && number(segment, v.region.mask, &v.x);
                 break;
             }
+            case Takes::Local: {
+                std::string why;
+                ok = local(v.text, &v.local, &why);
+                if (!ok && !why.empty()) refuse(prog, "--local " + v.text + ": " + why);
+                break;
+            }
             default: ok = number(*o, v.text, &v.x);
         }
         if (!ok) refuse(prog, std::string(o->takesText) + ", got '" + got + "'");
+        if (o->takes == Takes::Local && (int)a->locals.size() == NLE_REGION_MAX)
+            refuse(prog, "--local can be given at most " NLECLI_STR(NLE_REGION_MAX) " times");
         if (o->takes == Takes::Region && (int)a->regions.size() == NLE_REGION_MAX)
             refuse(prog, "--region can be given at most " NLECLI_STR(NLE_REGION_MAX) " times");
         o->set(*a, v);
@@ -311,7 +432,33 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
     if (!toneGiven.empty() && (!a->regions.empty() || a->tonemap))
         refuse(prog, toneGiven + " does not combine with --region or --tonemap: the base tone curve is built for the plain 8-bit and "
                                  "16-bit enhance");
-    if ((is_given("--region-spread") || is_given("--region-floor")) && a->regions.empty())
+    // local adjustments: what --local does not combine with, then its targets
+    bool localMasks = false, localSegments = false;
+    for (const auto& l : a->locals) (l.segment < 0 ? localMasks : localSegments) = true;
+    if (is_given("--saturation") && a->locals.empty())
+        refuse(prog, "--saturation needs --local (it is the background's saturation in a local adjustment)");
+    if (!a->locals.empty()) {
+        if (!a->regions.empty() || !a->segmentWeights.empty() || a->tonemap || is_given("--auto-levels") || is_given("--equalise"))
+            refuse(prog, "--local does not combine with --region, --segment-weights, --tonemap, --auto-levels or --equalise: a region "
+                         "has one kind of edit, and a whole-image histogram has no per-region meaning yet");
+        if (localMasks && localSegments)
+            refuse(prog, "--local targets are all masks or all segments (@c), got both");
+        if (localSegments && a->segments == 0) refuse(prog, "--local @c needs --segments C");
+        if (localMasks && a->segments != 0)
+            refuse(prog, "--local with a mask does not combine with --segments: the segments are targeted as @c");
+        for (size_t k = 0; k < a->locals.size(); ++k) {
+            const auto& l = a->locals[k];
+            if (l.segment >= a->segments && l.segment >= 0)
+                refuse(prog, "--local " + l.target + ": there are " + std::to_string(a->segments) + " segments, numbered from 0");
+            for (size_t j = 0; j < k; ++j)
+                if (l.segment >= 0 && a->locals[j].segment == l.segment)
+                    refuse(prog, "--local can be given once per segment, segment " + std::to_string(l.segment) + " has two");
+            const nle::LocalEdit e = local_edit(*a, &l);
+            if (e.detail.gain != 1 && !(e.detail.sigma > 0))
+                refuse(prog, "--local " + l.target + ": a gain other than 1 needs a sigma > 0, its own or --detail-sigma's");
+        }
+    }
+    if ((is_given("--region-spread") || is_given("--region-floor")) && a->regions.empty() && !localMasks)
         refuse(prog, "--region-spread and --region-floor need at least one --region");
     const std::string segmentGiven = last({"--segment-spread", "--segment-iterations", "--segment-map", "--segment-weights"});
     if (!segmentGiven.empty() && a->segments == 0) refuse(prog, segmentGiven + " needs --segments C");
@@ -319,7 +466,7 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
         if (!a->regions.empty() || a->deep || a->tonemap)
             refuse(prog, "--segments does not combine with --region, --deep or --tonemap: the segments are the regions of an 8-bit "
                          "region edit");
-        if (!detailGiven.empty() || !toneGiven.empty())
+        if ((!detailGiven.empty() || !toneGiven.empty()) && a->locals.empty())  // (with --local they are the background's row)
             refuse(prog, (detailGiven.empty() ? toneGiven : detailGiven) +
                              " does not combine with --segments: region edits have no residual layer, no detail curve and no tone curve");
         for (size_t k = 0; k < a->segmentOf.size(); ++k) {
@@ -371,6 +518,13 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
         for (const auto& r : a->regions)
             if (r.weights.size() != a->extra.size())
                 refuse(prog, "--region " + r.mask + " has " + std::to_string(r.weights.size()) + " weights, the command line has " +
+                                 std::to_string(a->extra.size()));
+    }
+    if (!a->locals.empty()) {  // every row that names weights has the positional weight count
+        if ((int)a->extra.size() > NLE_REGION_LAYERS_MAX) refuse(prog, "--local" + most);
+        for (const auto& l : a->locals)
+            if (l.given[kLocalWeights] && l.weights.size() != a->extra.size())
+                refuse(prog, "--local " + l.target + " has " + std::to_string(l.weights.size()) + " weights, the command line has " +
                                  std::to_string(a->extra.size()));
     }
     if (!a->segmentWeights.empty()) {  // every segment has the positional weight count

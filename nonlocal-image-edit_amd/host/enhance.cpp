@@ -13,7 +13,10 @@
 // <J>` and one line `Segment <c>: <n> pixels, mean L <m>` per segment; `--segment-map FILE` writes the labels as an 8-bit grey
 // image, segment c at round(255 c / (C - 1)); `--segment-weights c:w1,w2,...` gives segment c layer weights of its own
 // (NLEFilter::enhanceSegments) -- without one the image written is the plain command's, byte for byte.  Two runs give the same
-// labels: the first to look at the map and the lines, the second with weights.
+// labels: the first to look at the map and the lines, the second with weights.  `--local TARGET:key=value,...` gives a
+// region -- a mask, or segment @c of `--segments C` -- the whole edit of its own (NLEFilter::enhanceLocal /
+// enhanceSegmentsLocal): weights, residual, gain, sigma, shadows, highlights, saturation; what a spec does not name is the
+// background's, which is the positional weights, the detail options, `--shadows`, `--highlights` and `--saturation`.
 #include <algorithm>
 
 #include "cli_common.hpp"
@@ -26,12 +29,13 @@ int main(int argc, char* argv[]) {
     // the strokes: the first channel of every mask, read before anything touches the GPU
     std::vector<nle::Image> strokes;
     std::vector<std::vector<double>> regionWeights;
-    for (const auto& r : a.regions) {
-        const nle::Image mask = nle::imread(r.mask);
+    // false, after one line on stderr, for a mask that cannot be read, has another size or marks no pixel
+    const auto read_stroke = [&](const char* option, const std::string& path) {
+        const nle::Image mask = nle::imread(path);
         if (mask.empty() || mask.rows != image.rows || mask.cols != image.cols) {
-            std::cerr << argv[0] << ": --region mask " << r.mask
+            std::cerr << argv[0] << ": " << option << " mask " << path
                       << (mask.empty() ? " cannot be read" : " does not have the image's size") << std::endl;
-            return 2;
+            return false;
         }
         nle::Image s(mask.rows, mask.cols, nle::NLE_8U, 1);
         const int ch = mask.channels();
@@ -41,12 +45,28 @@ int main(int argc, char* argv[]) {
             any = any || s.ptr<unsigned char>()[i] >= 128;
         }
         if (!any) {
-            std::cerr << argv[0] << ": --region mask " << r.mask << " marks no pixel (no byte >= 128 in its first channel)"
+            std::cerr << argv[0] << ": " << option << " mask " << path << " marks no pixel (no byte >= 128 in its first channel)"
                       << std::endl;
-            return 2;
+            return false;
         }
         strokes.push_back(s);
+        return true;
+    };
+    for (const auto& r : a.regions) {
+        if (!read_stroke("--region", r.mask)) return 2;
         regionWeights.push_back(r.weights);
+    }
+    // the rows of a local adjustment: one per mask in the order given, or one per segment that has a spec
+    std::vector<nle::LocalEdit> localEdits;
+    const bool localSegments = !a.locals.empty() && a.locals[0].segment >= 0;
+    if (localSegments) localEdits.assign((size_t)a.segments, nlecli::local_edit(a, nullptr));
+    for (const auto& l : a.locals) {
+        if (localSegments) {
+            localEdits[(size_t)l.segment] = nlecli::local_edit(a, &l);
+        } else {
+            if (!read_stroke("--local", l.target)) return 2;
+            localEdits.push_back(nlecli::local_edit(a, &l));
+        }
     }
     nle::NLEFilter filter;
     filter.patchRadius = a.patchRadius;
@@ -66,6 +86,9 @@ int main(int argc, char* argv[]) {
     }
     // (inactive detail and tone options are the plain methods; segments without weights of their own leave the plain edit)
     const nle::Image result = a.tonemap                  ? filter.toneMap(image, a.extra, a.tonemapSaturation, a.detail)
+                              : localSegments             ? filter.enhanceSegmentsLocal(image, nlecli::local_edit(a, nullptr), localEdits)
+                              : !a.locals.empty()         ? filter.enhanceLocal(image, strokes, localEdits, nlecli::local_edit(a, nullptr),
+                                                                                a.regionSpread, a.regionFloor)
                               : !a.segmentWeights.empty() ? filter.enhanceSegments(image, a.extra, segmentWeights)
                               : strokes.empty()           ? filter.enhance(image, a.extra, a.detail, a.tone)  // the weights are argv[9..]
                                                           : filter.enhanceRegions(image, strokes, regionWeights, a.extra, a.regionSpread,

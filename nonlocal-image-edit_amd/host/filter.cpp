@@ -92,6 +92,27 @@ Image edit_deep(nle_ctx* c, const Image& image, Op&& op) {
     return lab16_to_image(c, in, d_y.f(), image.rows, image.cols);
 }
 
+// the same two edits with an operator that also sees the chroma planes: op(d_x, d_y, d_a, d_b) may rewrite a and b in place.
+// 8 bit without `chroma`: a and b are not made (op gets null pointers) and the edit is edit_8bit's, byte for byte
+template <typename Op>
+Image edit_8bit_lab(nle_ctx* c, const Image& image, bool chroma, Op&& op) {
+    Image out(image.rows, image.cols, NLE_8U, 3);
+    const size_t n = image.total();
+    const LabPlanes in = lab_planes(c, image.ptr<unsigned char>(), n, true, chroma);
+    Dev d_y(c, n * 4);
+    op(in.L.f(), d_y.f(), in.a.f(), in.b.f());
+    lab_to_rows(c, in, d_y.f(), in.a.f(), in.b.f(), out, 0, image.rows);
+    return out;
+}
+
+template <typename Op>
+Image edit_deep_lab(nle_ctx* c, const Image& image, Op&& op) {
+    const Lab16Planes in = lab16_planes(c, image, true, false);
+    Dev d_y(c, image.total() * 4);
+    op(in.L.f(), d_y.f(), in.a.f(), in.b.f());
+    return lab16_to_image(c, in, d_y.f(), image.rows, image.cols);
+}
+
 // HDR: the unrounded log-luminance on the scale of the train (hi, range), op, then base compression and saturation
 template <typename Op>
 Image edit_hdr(nle_ctx* c, const Image& image, double hi, double range, DType base, DType saturation, Op&& op) {
@@ -665,6 +686,119 @@ Image NLEFilter::enhanceSegments(const Image& image, const std::vector<DType>& w
     return edit_8bit(ctx_, image, [&](const float* d_x, float* d_y) {
         check(nle_apply_layers(f_, d_x, image.rows, image.cols, L, d_layers.f()), ctx_);
         check(nle_region_combine(ctx_, d_layers.f(), L, d_q, C, n, n, n, Wt.data(), segmentFloor_, NLE_REGION_OUT_ROUNDED8, d_y), ctx_);
+    });
+}
+
+namespace {
+
+// the M + 1 rows of a local edit as nle_local_combine / nle_local_chroma take them; row 0 the background
+struct LocalRowsHost {
+    int L = 0;
+    std::vector<double> weights, detail, curves, saturation;
+    std::vector<int> curveOn;
+    bool anyCurve = false, chroma = false;
+};
+
+LocalRowsHost local_rows(const LocalEdit& background, const std::vector<const LocalEdit*>& edits) {
+    LocalRowsHost r;
+    r.L = (int)background.weights.size();
+    if (r.L < 1 || r.L > NLE_REGION_LAYERS_MAX)
+        throw std::runtime_error("Local adjustments take 1 to " + std::to_string(NLE_REGION_LAYERS_MAX) + " weights.");
+    const size_t rows = edits.size() + 1;
+    r.curves.assign(rows * (NLE_TONE_KNOTS + 2), 0.0);
+    for (size_t m = 0; m < rows; ++m) {
+        const LocalEdit& e = m == 0 ? background : *edits[m - 1];
+        const std::vector<DType>& w = e.weights.empty() ? background.weights : e.weights;
+        if ((int)w.size() != r.L)
+            throw std::runtime_error("Row " + std::to_string(m) + " of the local adjustment has " + std::to_string(w.size()) +
+                                     " weights, the background has " + std::to_string(r.L) + ".");
+        r.weights.insert(r.weights.end(), w.begin(), w.end());
+        r.detail.insert(r.detail.end(), {e.detail.residualWeight, e.detail.gain, e.detail.sigma});
+        if (!std::isfinite(e.saturation) || e.saturation < 0 || e.saturation > NLE_LOCAL_SATURATION_MAX)
+            throw std::runtime_error("Row " + std::to_string(m) + " of the local adjustment: the saturation must be finite and in [0, " +
+                                     std::to_string(NLE_LOCAL_SATURATION_MAX) + "].");
+        r.saturation.push_back(e.saturation);
+        r.chroma = r.chroma || e.saturation != 1;
+        const bool on = !(e.shadows == 0 && e.highlights == 0);
+        r.curveOn.push_back(on ? 1 : 0);
+        r.anyCurve = r.anyCurve || on;
+        if (on) check(nle_tone_curve(nullptr, e.shadows, e.highlights, -1, 0, r.curves.data() + m * (NLE_TONE_KNOTS + 2)), nullptr);
+    }
+    return r;
+}
+
+const char kLocalOneDevice[] = "Local adjustments run on one device: this filter was trained on a device group (NLE_DEVICES).";
+
+}  // namespace
+
+Image NLEFilter::enhanceLocal(const Image& image, const std::vector<Image>& strokes, const std::vector<LocalEdit>& edits,
+                              const LocalEdit& background, DType spread, DType floor) const {
+    refuse_hdr(image, "enhanceLocal");
+    if (image.channels() != 3 || (image.depth() != NLE_8U && image.depth() != NLE_16U))
+        throw std::runtime_error("Can only enhance RGB image.");
+    if (!group_.empty()) throw std::runtime_error(kLocalOneDevice);
+    requireSize(image.total(), kTrainedSize);
+    const int M = (int)strokes.size();
+    if (M < 1 || M > NLE_REGION_MAX)
+        throw std::runtime_error("Local adjustments take 1 to " + std::to_string(NLE_REGION_MAX) + " strokes.");
+    if ((int)edits.size() != M) throw std::runtime_error("Local adjustments need one edit per stroke.");
+    std::vector<const LocalEdit*> rows;
+    for (const LocalEdit& e : edits) rows.push_back(&e);
+    const LocalRowsHost r = local_rows(background, rows);
+    const size_t np = image.total();
+    // the stroke planes as 0 / 1 and their scales c_m = N / sum s_m, as enhanceRegions makes them
+    std::vector<double> scale((size_t)M);
+    std::vector<float> planes((size_t)M * np);
+    for (int m = 0; m < M; ++m) {
+        const Image& s = strokes[m];
+        if (s.channels() != 1 || s.depth() != NLE_8U || s.rows != image.rows || s.cols != image.cols)
+            throw std::runtime_error("Stroke " + std::to_string(m + 1) + " must be a one-channel 8-bit image of the image's size.");
+        const unsigned char* b = s.ptr<unsigned char>();
+        double sum = 0.0;
+        for (size_t i = 0; i < np; ++i) {
+            const float v = b[i] >= 128 ? 1.f : 0.f;
+            planes[(size_t)m * np + i] = v;
+            sum += v;
+        }
+        if (!(sum > 0)) throw std::runtime_error("Stroke " + std::to_string(m + 1) + " is empty (no byte >= 128).");
+        scale[m] = (double)np / sum;
+    }
+    Dev d_s(ctx_, planes.size() * 4), d_q;  // d_q: the spreads, kept only for the chroma call
+    if (r.chroma) d_q = Dev(ctx_, planes.size() * 4);
+    check(nle_dev_upload(ctx_, d_s.p, planes.data(), planes.size() * 4), ctx_);
+    const bool deep = is_deep(image);
+    const auto op = [&](const float* d_x, float* d_y, float* d_a, float* d_b) {
+        check(nle_apply_local(f_, d_x, image.rows, image.cols, r.L, d_s.f(), M, scale.data(), spread, floor, r.weights.data(),
+                              r.detail.data(), r.anyCurve ? r.curveOn.data() : nullptr, r.anyCurve ? r.curves.data() : nullptr,
+                              deep ? NLE_REGION_OUT_F32 : NLE_REGION_OUT_ROUNDED8, d_y, r.chroma ? d_q.f() : nullptr), ctx_);
+        if (r.chroma)
+            check(nle_local_chroma(ctx_, d_a, d_b, d_q.f(), M, (long long)np, (long long)np, r.saturation.data(), floor, d_a, d_b), ctx_);
+    };
+    return deep ? edit_deep_lab(ctx_, image, op) : edit_8bit_lab(ctx_, image, r.chroma, op);
+}
+
+Image NLEFilter::enhanceSegmentsLocal(const Image& image, const LocalEdit& background, const std::vector<LocalEdit>& edits) const {
+    refuse_hdr(image, "enhanceSegmentsLocal");
+    if (is_deep(image)) throw std::runtime_error("Segment edits take an 8-bit image: deep colour (16 bit) is built for enhance only.");
+    if (image.channels() != 3 || image.depth() != NLE_8U) throw std::runtime_error("Can only enhance RGB image.");
+    if (!group_.empty()) throw std::runtime_error(kLocalOneDevice);
+    requireSize(image.total(), kTrainedSize);
+    if (!segmentSpreads_) throw std::runtime_error("enhanceSegmentsLocal needs a segment() of this filter first.");
+    const int C = segmentCount_;
+    if ((int)edits.size() > C)
+        throw std::runtime_error("Segment edits take at most one edit per segment (" + std::to_string(C) + ").");
+    std::vector<const LocalEdit*> rows;
+    for (int c = 0; c < C; ++c) rows.push_back(c < (int)edits.size() ? &edits[c] : &background);
+    const LocalRowsHost r = local_rows(background, rows);
+    const long long n = (long long)image.total();
+    const float* d_q = static_cast<const float*>(segmentSpreads_.get());
+    Dev d_layers(ctx_, (size_t)r.L * n * 4);
+    return edit_8bit_lab(ctx_, image, r.chroma, [&](const float* d_x, float* d_y, float* d_a, float* d_b) {
+        check(nle_apply_layers(f_, d_x, image.rows, image.cols, r.L, d_layers.f()), ctx_);
+        check(nle_local_combine(ctx_, d_x, d_layers.f(), r.L, d_q, C, n, n, n, r.weights.data(), r.detail.data(),
+                                r.anyCurve ? r.curveOn.data() : nullptr, r.anyCurve ? r.curves.data() : nullptr, segmentFloor_,
+                                NLE_REGION_OUT_ROUNDED8, d_y), ctx_);
+        if (r.chroma) check(nle_local_chroma(ctx_, d_a, d_b, d_q, C, n, n, r.saturation.data(), segmentFloor_, d_a, d_b), ctx_);
     });
 }
 
