@@ -839,6 +839,52 @@ int nle_apply_local(nle_filter* f, const float* d_x, int H, int W, int L, const 
                     double spread, double floor, const double* h_weights, const double* h_detail, const int* h_curve_on,
                     const double* h_curves, int out_kind, void* d_out, float* d_q_out);
 
+/* ---- per-region histograms: auto levels and equalise for a region of its own (new in this build: no reference, so this
+ * text and DESIGN.md section 3.21 are the definition) ---- */
+/* The local adjustments above give a row a base curve of two slopes only; the levels and the equalisation of nle_tone_curve
+ * need a histogram, and a region's histogram is the plane's with every pixel counted by its membership.
+ * Per pixel i, in fp64, every operation rounded on its own (no fma), in the order written.  Inputs: the plane y (the base
+ * layer); the memberships' source planes q_1 .. q_M, 1 <= M <= NLE_REGION_MAX; the floor phi > 0; a scale per row m = 0 .. M.
+ *   Memberships  exactly nle_region_combine's:  u_m = q_m[i] > 0 ? (double)q_m[i] : 0 (a NaN q counts as 0);
+ *                sigma = u_1 + .. + u_M;  d = sigma > phi ? sigma : phi;  alpha_m = u_m / d;  alpha_0 = 1 - sigma / d
+ *   Weight       omega_m = (long long)(alpha_m 65536.0 + 0.5), a truncation (alpha_m >= 0): 0 .. NLE_REGION_WEIGHT_ONE.
+ *                An alpha_m that is not > 0 (0, or the NaN an infinite q makes) has omega_m = 0.
+ *   Bin          per row m nle_plane_histogram's rule on v = (double)y[i] scale_m: a NaN v -> counts[4097]; b < 0 -> counts[0];
+ *                b >= 4096 -> counts[4097]; otherwise counts[1 + b].  Every row has a scale of its own; the callers pass
+ *                W[m][L-1], the row's weight of the base layer.
+ *   Count        counts[m][bin_m] += omega_m, for the rows that are switched on and where omega_m > 0
+ * The counts are integers: the result is exact, independent of the order of the pixels and of the merges, and bit-equal from
+ * run to run.  nle_tone_curve takes a row as it is: its counts are long long, and every step of it (need, the comparisons,
+ * the shares F) is invariant under a common factor 2^16 of all counts.
+ * Consequences:
+ *   (a) where every q <= 0 (or NaN): row 0 is 65536 x nle_plane_histogram(y, scale_0) and every other row is zero.
+ *   (b) hard memberships (every pixel has one q >= phi and the others <= 0): row m is 65536 x the histogram of region m's
+ *       pixels alone, and the curve nle_tone_curve makes from row m is bit for bit the curve it makes from
+ *       nle_plane_histogram over those pixels.
+ *   (c) |sum_m omega_m - 65536| <= (M + 1) / 2 + 1 per pixel: a pixel's mass is one up to the roundings.
+ *   (d) a tie rounds up: M = 1, phi = 0.5 and q = (2 k + 1) / 262144 give alpha 65536 = k + 0.5 exactly and omega = k + 1.
+ * nle_region_histograms is the stage call: d_y n floats; plane m at d_q + (m - 1) q_stride (stride in floats, >= n); h_scale
+ * M + 1 doubles; h_row_on M + 1 ints (NULL: every row is on), rows that are off come back as zeros; h_counts (M + 1) x
+ * (NLE_TONE_BINS + 2) long long, row-major.  No alignment is required of pointers or strides; every plane is read once; the
+ * call returns with the counts on the host.  NLE_ERR_INVALID with a message that starts with the function's name, nothing
+ * enqueued and the ctx left usable, for: M out of range; n < 1; a stride below n; a NULL pointer (h_row_on apart); a scale or
+ * floor that is not finite; a floor that is not > 0.
+ * nle_apply_local_auto is nle_apply_local with the rows' curves made here.  h_tone is (M + 1) x 4 = (shadows, highlights,
+ * clip_percent P, equalise A) per row, in nle_tone_curve's ranges.  It is these calls in this order, and bitwise what they
+ * give: nle_apply_layers; nle_region_spread; nle_region_histograms on layer L - 1 with scale_m = W[m][L-1], only the rows
+ * with P >= 0 or A > 0 switched on, skipped when no row is; one nle_tone_curve per row whose four numbers are not all
+ * inactive (s == 0, h == 0, P < 0, A == 0: the row then has no base curve); nle_local_combine.  A row whose counts sum to
+ * less than NLE_REGION_WEIGHT_ONE holds less than one pixel's mass: it takes nle_tone_curve(NULL, s, h, -1, 0) instead of
+ * being refused.  When no row has P >= 0 or A > 0 the call is nle_apply_local with the (s, h) curves, bit for bit.
+ * h_curves_out (may be NULL) receives (M + 1) x (NLE_TONE_KNOTS + 2) doubles: the curve of every row that has one, zeros for
+ * the others.  Refusals: those of the calls it composes, and nle_tone_curve's ranges per row; world > 1 as for nle_apply_local. */
+#define NLE_REGION_WEIGHT_ONE 65536
+int nle_region_histograms(nle_ctx* ctx, const float* d_y, const float* d_q, int M, long long n, long long q_stride,
+                          const double* h_scale, const int* h_row_on, double floor, long long* h_counts);
+int nle_apply_local_auto(nle_filter* f, const float* d_x, int H, int W, int L, const float* d_strokes, int M,
+                         const double* h_scale, double spread, double floor, const double* h_weights, const double* h_detail,
+                         const double* h_tone, int out_kind, void* d_out, float* d_q_out, double* h_curves_out);
+
 /* ---- several planes through one filter (new in this build) ---- */
 /* Applies f to P planes in one call, each plane with its own set of responses: the channels of a colour image, several guide
  * planes, the stroke planes of the region edits, the a / b pair of the denoiser.  nle_apply (P = 1, one response) and

@@ -188,11 +188,14 @@ struct ToneLevels {
 
 // one row of NLEFilter::enhanceLocal / enhanceSegmentsLocal (new here; see there): the whole edit of a region, or of the
 // background -- layer weights (empty: the background's), the detail options, the two slopes of a base tone curve of its own
-// (both 0: no curve) and the saturation of a and b (1: untouched)
+// (both 0: no curve) and the saturation of a and b (1: untouched); clipPercent >= 0 (auto levels) and equalise > 0 lay that
+// curve over the row's own membership-weighted histogram of the base layer (nle_region_histograms in nle.h), as
+// ToneOptions has them for the whole image
 struct LocalEdit {
     std::vector<DType> weights;
     DetailOptions detail;
     DType shadows = 0, highlights = 0, saturation = 1;
+    DType clipPercent = -1, equalise = 0;
 };
 
 // the options of NLEFilter::segment (new here; see there): the number of segments, how far a segment's indicator spreads
@@ -324,9 +327,14 @@ public:
     // With every saturation 1 the chroma planes are not touched.  Both throw std::runtime_error for an HDR image, a filter
     // trained on a device group, counts out of range, a weight count other than the background's, a saturation outside
     // [0, NLE_LOCAL_SATURATION_MAX] and whatever nle_apply_local / nle_local_combine / nle_tone_curve refuse.
+    // Per-region auto levels and equalise (new here): exactly when some row has clipPercent >= 0 or
+    // equalise > 0, the rows' curves come from nle_region_histograms -- enhanceLocal is then nle_apply_local_auto,
+    // enhanceSegmentsLocal the same stage calls on the segments' spreads; otherwise both make the calls they made.
+    // lastLocalLevels(): one entry per row of the last such call (row 0 the background), valid where the row had either.
     Image enhanceLocal(const Image& I, const std::vector<Image>& strokes, const std::vector<LocalEdit>& edits,
                        const LocalEdit& background, DType spread = 4, DType floor = 0.05) const;
     Image enhanceSegmentsLocal(const Image& I, const LocalEdit& background, const std::vector<LocalEdit>& edits) const;
+    std::vector<ToneLevels> lastLocalLevels() const { return localLevels_; }
     // include/filter.hpp:40-45: the filter is trained on the bilateral-filtered L channel; denoise shrinks the
     // eigenvalues to min(lambda, 1)^k on the a and b channels (src/filter.cpp:349-410, 521-538)
     void trainForDenoise(const Image& image, int nRowSamples, int nColSamples, DType hx, DType hy, int nSinkhornIter,
@@ -404,6 +412,7 @@ private:
     int rows_ = 0, cols_ = 0;
     bool denoiseTrained_ = false;            // the filter in hand came from trainForDenoise (what glide needs)
     mutable ToneLevels toneLevels_;          // enhance with active ToneOptions
+    mutable std::vector<ToneLevels> localLevels_;  // enhanceLocal / enhanceSegmentsLocal: one per row
     mutable DenoiseReport denoiseReport_;    // denoise with DenoiseOptions::glide
     // segment(): the plane trainForEnhancement trained on (fp32, on the device; keepTrainPlane), the spreads of the last segmentation
     // (count planes) with its floor, and what it found

@@ -52,6 +52,7 @@ KERNEL_COUNT_ALL = _abi.NLE_KERNEL_COUNT_ALL
 # the base tone curve: the knots of a curve (a curve is [lo, hi, T_0 .. T_N]: TONE_KNOTS + 2 values), the histogram's bins
 # (its counts: underflow, the bins, overflow and NaN: TONE_BINS + 2 values)
 TONE_KNOTS, TONE_BINS = _abi.NLE_TONE_KNOTS, _abi.NLE_TONE_BINS
+REGION_WEIGHT_ONE = _abi.NLE_REGION_WEIGHT_ONE  # nle_region_histograms: the count of one pixel with membership 1
 LOCAL_SATURATION_MAX = _abi.NLE_LOCAL_SATURATION_MAX  # nle_local_chroma: a row's saturation lies in [0, LOCAL_SATURATION_MAX]
 SEGMENT_ITERATIONS_MAX = _abi.NLE_SEGMENT_ITERATIONS_MAX  # nle_filter_segment: the cap on its iterations (C: 1 .. REGION_MAX)
 
@@ -1222,6 +1223,33 @@ class Context:
                                       C.c_void_p(bo.data_ptr())), self._h)
         return ao, bo
 
+    def region_histograms(self, y, q, scale, row_on=None, floor=0.05):
+        """nle_region_histograms: the membership-weighted histograms of y (n,) under the planes q (M, n), float32 device
+        tensors with contiguous rows; scale M + 1 values, row 0 the background; row_on: None (every row) or M + 1 flags.
+        Returns (M + 1, TONE_BINS + 2) int64 counts in units of 1 / REGION_WEIGHT_ONE of a pixel; rows that are off are zero."""
+        self._sync_in()
+        torch = _torch()
+        if not (isinstance(y, torch.Tensor) and isinstance(q, torch.Tensor) and q.ndim == 2):
+            raise NLEError(NLE_ERR_INVALID, "region_histograms: y (n,) and q (M, n) device tensors expected")
+        M, n = q.shape
+        if y.dtype != torch.float32 or q.dtype != torch.float32 or not self._here(y) or not self._here(q):
+            raise NLEError(NLE_ERR_INVALID, "region_histograms: float32 tensors on this ctx's device expected")
+        if y.shape != (n,) or y.stride(0) != 1 or q.stride(1) != 1:
+            raise NLEError(NLE_ERR_INVALID, "region_histograms: y (n,) and q (M, n) with contiguous rows")
+        sc = np.ascontiguousarray(scale, dtype=np.float64)
+        if sc.shape != (M + 1,):
+            raise NLEError(NLE_ERR_INVALID, f"region_histograms: scale must hold M + 1 = {M + 1} values, got {sc.shape}")
+        on = None
+        if row_on is not None:
+            on = np.ascontiguousarray([1 if r else 0 for r in row_on], dtype=np.int32)
+            if on.shape != (M + 1,):
+                raise NLEError(NLE_ERR_INVALID, f"region_histograms: row_on must hold M + 1 = {M + 1} flags, got {on.shape}")
+        counts = np.zeros((M + 1, TONE_BINS + 2), dtype=np.int64)
+        _check(lib().nle_region_histograms(self._h, C.c_void_p(y.data_ptr()), C.c_void_p(q.data_ptr()), M, n,
+                                           q.stride(0) if M > 1 else n, _np_ptr(sc), _np_ptr(on) if on is not None else None,
+                                           float(floor), _np_ptr(counts)), self._h)
+        return counts
+
     def _here(self, t):
         """t is a tensor on this ctx's device (its pointer is handed to kernels)"""
         return t.is_cuda and (t.device.index or 0) == self.device
@@ -1674,6 +1702,33 @@ class NLEFilter:
                                      _np_ptr(cv) if cv is not None else None, int(out_kind), C.c_void_p(out.data_ptr()),
                                      C.c_void_p(q.data_ptr()) if q is not None else None), self.ctx._h)
         return (out, q) if want_spreads else out
+
+    def apply_local_auto(self, x, n_layers, strokes, weights, tone, detail=None, scale=None, spread=4.0, floor=0.05,
+                         out_kind=0, out=None, want_spreads=False, want_curves=False):
+        """nle_apply_local_auto: apply_local with every row's base curve made from the row's own membership-weighted
+        histogram.  tone (M + 1, 4) = (shadows, highlights, clip_percent, equalise) per row, in tone_curve's ranges; a row of
+        (0, 0, -1, 0) has no curve.  Returns the output, then -- want_spreads -- the (M, n_local) spreads and -- want_curves --
+        the (M + 1, TONE_KNOTS + 2) curves (zeros for a row without one)."""
+        torch = _torch()
+        x = self.ctx._lum(x)
+        H, W = x.shape
+        s = self._strokes(strokes)
+        M = s.shape[0]
+        c, cp = self._scale(scale, M)
+        w, d, _, _ = _local_rows("apply_local_auto", M, int(n_layers), weights, detail, None)
+        tn = np.ascontiguousarray(tone, dtype=np.float64)
+        if tn.shape != (M + 1, 4):
+            raise NLEError(NLE_ERR_INVALID, f"apply_local_auto: tone must be {(M + 1, 4)}, got {tn.shape}")
+        n = self.info()["n_local"]
+        out = _combine_out(out, n, out_kind, x.device)
+        q = torch.empty((M, n), dtype=torch.float32, device=x.device) if want_spreads else None
+        cv = np.zeros((M + 1, TONE_KNOTS + 2)) if want_curves else None
+        _check(lib().nle_apply_local_auto(self._f, C.c_void_p(x.data_ptr()), H, W, int(n_layers), C.c_void_p(s.data_ptr()), M, cp,
+                                          float(spread), float(floor), _np_ptr(w), _np_ptr(d), _np_ptr(tn), int(out_kind),
+                                          C.c_void_p(out.data_ptr()), C.c_void_p(q.data_ptr()) if q is not None else None,
+                                          _np_ptr(cv) if cv is not None else None), self.ctx._h)
+        res = (out,) + ((q,) if want_spreads else ()) + ((cv,) if want_curves else ())
+        return res if len(res) > 1 else out
 
     def segment(self, count, spread=4.0, max_iter=40, labels=None, want_spreads=False):
         """nle_filter_segment: kernel k-means of the pixels on the trained affinity, `count` clusters.  labels: the start, n

@@ -22,7 +22,7 @@ LIBDIR = os.path.join(HERE, "lib")
 BINDIR = os.path.join(HERE, "bin")
 LIB = os.path.join(LIBDIR, "libnle_hip.so")
 
-LIB_SOURCES = ["kernels.hip", "tsgemm_bf16x3.hip", "fused.hip", "tables.hip", "sorted.hip", "sorted_planes.hip", "generic64.hip", "patch.hip", "sampler.hip", "exact.hip", "resid.hip", "tridiag.hip", "dense64.hip", "colour.hip", "colour16.hip", "tonemap.hip", "region.hip", "detail.hip", "local.hip", "tone.hip", "segment.hip", "denoise.hip", "pipeline.hip", "literal.hip", "sample_space.hip", "exact_train.hip", "samples.hip", "ortho.hip", "abi_ctx.hip", "devsolve.hip", "eigen_sym.cpp", "eigen_reduce.cpp", "eigen_tridiag.cpp", "host_dense.cpp", "lanczos.cpp", "lab8_tables.cpp", "srgb16_tables.cpp"]
+LIB_SOURCES = ["kernels.hip", "tsgemm_bf16x3.hip", "fused.hip", "tables.hip", "sorted.hip", "sorted_planes.hip", "generic64.hip", "patch.hip", "sampler.hip", "exact.hip", "resid.hip", "tridiag.hip", "dense64.hip", "colour.hip", "colour16.hip", "tonemap.hip", "region.hip", "detail.hip", "local.hip", "region_hist.hip", "tone.hip", "segment.hip", "denoise.hip", "pipeline.hip", "literal.hip", "sample_space.hip", "exact_train.hip", "samples.hip", "ortho.hip", "abi_ctx.hip", "devsolve.hip", "eigen_sym.cpp", "eigen_reduce.cpp", "eigen_tridiag.cpp", "host_dense.cpp", "lanczos.cpp", "lab8_tables.cpp", "srgb16_tables.cpp"]
 ARCH = "gfx950"
 # the C++ surface behind include/nle/filter.hpp (host/): what every tool, and a test's driver, links beside its own main
 HOST_SOURCES = ["filter.cpp", "stages.cpp", "colour.cpp", "device_group.cpp", "image_io.cpp", "jpeg.cpp"]

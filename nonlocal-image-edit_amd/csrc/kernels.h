@@ -479,6 +479,12 @@ hipError_t local_combine(hipStream_t s, const float* d_x, const float* d_layers,
                          double floor, int out_kind, void* d_out);
 hipError_t local_chroma(hipStream_t s, const float* d_a, const float* d_b, const float* d_q, long long q_stride, int M, long long n,
                         const double* saturation, double floor, float* d_a_out, float* d_b_out);
+// per-region histograms (region_hist.hip; the rule is stated in include/nle.h at nle_region_histograms): the memberships of
+// local_combine weigh every pixel's count, omega_m = the round half up of alpha_m NLE_REGION_WEIGHT_ONE, into the histogram of
+// y scale[m] of every row m = 0 .. M that is on.  slot[m]: the row's place among the nslots rows that are on, < 0 for a row
+// that is off; d_counts receives nslots x kToneCounts counters, slot-major (zeroed on the stream first).
+hipError_t region_hist(hipStream_t s, const float* d_y, const float* d_q, long long q_stride, int M, long long n, const double* scale,
+                       const int* slot, int nslots, double floor, unsigned long long* d_counts);
 // automatic regions (segment.hip; the rule is stated in include/nle.h at nle_filter_segment).  Labels are one byte per
 // pixel, planes go by base pointer and stride in floats, C is 1 .. kRegionMax.  Everything a step leaves for the host sits
 // in one SegmentResult on the device (zeroed by the launcher where the kernels add to it).

@@ -41,62 +41,6 @@ struct LocalArgs {
     LocalRows rows;
 };
 
-// the memberships' source planes of P pixels, as read, and what every row needs of them
-template <int P>
-struct Memberships {
-    Pack<P> q[kRegionMax];
-    double d[P], a0[P];
-
-    __device__ __forceinline__ void load(const float* base, long long stride, int M, long long i) {
-#pragma unroll
-        for (int m = 0; m < kRegionMax; ++m)
-            if (m < M) q[m].load(base + (long long)m * stride + i);
-    }
-    // a NaN or non-positive q counts as 0 from here on; sigma, d and alpha_0 as region.hip forms them
-    __device__ __forceinline__ void prepare(int M, double floor) {
-        double sigma[P];
-#pragma unroll
-        for (int j = 0; j < P; ++j) sigma[j] = 0.0;
-#pragma unroll
-        for (int m = 0; m < kRegionMax; ++m) {
-            if (m < M) {
-#pragma unroll
-                for (int j = 0; j < P; ++j) {
-                    q[m].v[j] = q[m].v[j] > 0.f ? q[m].v[j] : 0.f;
-                    sigma[j] = m == 0 ? (double)q[m].v[j] : sigma[j] + (double)q[m].v[j];
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < P; ++j) q[m].v[j] = 0.f;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-            d[j] = sigma[j] > floor ? sigma[j] : floor;
-            a0[j] = 1.0 - sigma[j] / d[j];
-        }
-    }
-    // alpha_m of the P pixels for m = 0, 1, .. M, one call per row in that order; false when none of them is > 0 (the row
-    // has no influence here).  Region m's plane is always read from q[0] and the planes move down one place behind it: every
-    // index is a constant, so the planes stay in registers whatever m is (a pick by the uniform m would become an indexed
-    // access to memory, that is scratch)
-    __device__ __forceinline__ bool next_alpha(int m, double (&al)[P]) {
-        bool any = false;
-        if (m == 0) {
-#pragma unroll
-            for (int j = 0; j < P; ++j) al[j] = a0[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < P; ++j) al[j] = (double)q[0].v[j] / d[j];
-#pragma unroll
-            for (int k = 0; k + 1 < kRegionMax; ++k) q[k] = q[k + 1];
-        }
-#pragma unroll
-        for (int j = 0; j < P; ++j) any = any || al[j] > 0.0;
-        return any;
-    }
-};
-
 // y_m of the P pixels: detail.hip's detail_pixels on the values already loaded, with row r's parameters.  CURVE as there;
 // the base term passes the row's tone curve when it has one (r.slot >= 0, uniform).
 template <int LMAX, bool CURVE, int P>

@@ -3,6 +3,8 @@
 // and region entry points.  The train paths themselves are literal.hip's, sample_space.hip's and exact_train.hip's (train.h).
 // Small (p x p, r x r) algebra and the three symmetric eigensolves run on the host in fp64; everything N-sized is a HIP
 // kernel.  The sample set, Ka and the fp64 affinity rows -- the patch, chroma and sampler options -- are samples.hip's.
+#include <numeric>
+
 #include "train.h"
 
 using namespace nlep;
@@ -605,6 +607,67 @@ void local_combine_impl(nle_ctx* c, const float* d_x, const float* d_layers, int
     HIP_OK(nlek::local_combine(c->stream, d_x, d_layers, layer_stride, L, d_q, q_stride, M, n, rows, d_knots.p, ncurves, floor,
                                out_kind, d_out));
     HIP_OK(hipStreamSynchronize(c->stream));
+}
+
+// what nle_apply_local does between its argument checks and its combine, for it and nle_apply_local_auto: the checks that
+// need the filter, then the L layers of x and the M spreads into one work buffer, layers first
+DevBuf<float> local_apply_planes(const char* who, nle_filter* f, const float* d_x, int H, int W, int L, const float* d_strokes, int M,
+                                 const double* h_scale, double spread, int out_kind, void* d_out, float* d_q_out) {
+    nle_ctx* c = f->ctx;
+    try {
+        region_check_spread(f, M, H, W, h_scale, spread);
+    } catch (const Fail& e) {
+        throw Fail{e.code, std::string(who) + ": " + e.msg};
+    }
+    const long long n = f->n_local;  // == H W: world == 1
+    detail_check_overlap(who, d_x, d_out, n, out_kind, "the plane");
+    for (int m = 0; m < M; ++m) detail_check_overlap(who, d_strokes + (size_t)m * n, d_out, n, out_kind, "a stroke plane");
+    if (d_q_out)
+        for (int m = 0; m < M; ++m) detail_check_overlap(who, d_q_out + (size_t)m * n, d_out, n, out_kind, "d_q_out");
+    DevBuf<float> d_work((size_t)(L + M) * n);
+    // one batch over [x; s_1 .. s_M], as nle_apply_regions makes it: the L layers of x and one spread per stroke
+    std::vector<double> resp((size_t)(L + M) * f->K);
+    layer_resp(f->eigvals.data(), f->K, L, resp.data());
+    spread_resp(f, M, h_scale, spread, resp.data() + (size_t)L * f->K);
+    const float* planes[1 + NLE_REGION_MAX];
+    int nresp[1 + NLE_REGION_MAX];
+    planes[0] = d_x, nresp[0] = L;
+    for (int m = 0; m < M; ++m) planes[1 + m] = d_strokes + (size_t)m * H * W, nresp[1 + m] = 1;
+    apply_planes_impl(f, planes, 1 + M, H, W, nresp, resp.data(), d_work.p, n, false);
+    if (d_q_out)
+        HIP_OK(hipMemcpyAsync(d_q_out, d_work.p + (size_t)L * n, (size_t)M * n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    return d_work;
+}
+
+// ---- per-region histograms (include/nle.h "per-region histograms"; the kernel is region_hist.hip) ----
+void region_hist_check(const char* who, int M, const double* h_scale, double floor) {
+    const std::string name(who);
+    if (M < 1 || M > NLE_REGION_MAX)
+        throw Fail{NLE_ERR_INVALID, name + " takes 1 to " + std::to_string(NLE_REGION_MAX) + " regions, got " + std::to_string(M)};
+    if (!h_scale) throw Fail{NLE_ERR_INVALID, name + ": NULL pointer"};
+    for (int m = 0; m <= M; ++m)
+        if (!std::isfinite(h_scale[m])) throw Fail{NLE_ERR_INVALID, name + ": the scale of row " + std::to_string(m) + " is not finite"};
+    if (!std::isfinite(floor) || !(floor > 0))
+        throw Fail{NLE_ERR_INVALID, name + ": the region floor must be finite and > 0, got " + std::to_string(floor)};
+}
+
+// only the rows that are on have counters on the device; h_counts receives every row, zeros for those that are off
+void region_histograms_impl(nle_ctx* c, const float* d_y, const float* d_q, int M, long long n, long long q_stride,
+                            const double* h_scale, const int* h_row_on, double floor, long long* h_counts) {
+    int slot[NLE_REGION_MAX + 1], nslots = 0;
+    for (int m = 0; m <= M; ++m) slot[m] = !h_row_on || h_row_on[m] ? nslots++ : -1;
+    std::fill(h_counts, h_counts + (size_t)(M + 1) * nlek::kToneCounts, 0ll);
+    if (!nslots) return;
+    HIP_OK(hipSetDevice(c->device));
+    DevBuf<unsigned long long> d_counts((size_t)nslots * nlek::kToneCounts);
+    HIP_OK(nlek::region_hist(c->stream, d_y, d_q, q_stride, M, n, h_scale, slot, nslots, floor, d_counts.p));
+    std::vector<long long> got((size_t)nslots * nlek::kToneCounts);
+    HIP_OK(hipMemcpyAsync(got.data(), d_counts.p, sizeof(long long) * got.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    for (int m = 0; m <= M; ++m)
+        if (slot[m] >= 0)
+            std::copy(got.begin() + (size_t)slot[m] * nlek::kToneCounts, got.begin() + (size_t)(slot[m] + 1) * nlek::kToneCounts,
+                      h_counts + (size_t)m * nlek::kToneCounts);
 }
 
 // ---- automatic regions (include/nle.h "automatic regions"; the kernels are segment.hip) ----
@@ -1347,32 +1410,66 @@ int nle_apply_local(nle_filter* f, const float* d_x, int H, int W, int L, const 
         nle_ctx* c = f->ctx;
         if (!d_x || !d_strokes || !d_out) throw Fail{NLE_ERR_INVALID, "nle_apply_local: NULL pointer"};
         local_check("nle_apply_local", L, M, h_weights, h_detail, h_curve_on, h_curves, floor, out_kind);
-        try {
-            region_check_spread(f, M, H, W, h_scale, spread);
-        } catch (const Fail& e) {
-            throw Fail{e.code, "nle_apply_local: " + e.msg};
-        }
+        const DevBuf<float> d_work = local_apply_planes("nle_apply_local", f, d_x, H, W, L, d_strokes, M, h_scale, spread, out_kind, d_out, d_q_out);
         const long long n = f->n_local;  // == H W: world == 1
-        detail_check_overlap("nle_apply_local", d_x, d_out, n, out_kind, "the plane");
-        for (int m = 0; m < M; ++m)
-            detail_check_overlap("nle_apply_local", d_strokes + (size_t)m * n, d_out, n, out_kind, "a stroke plane");
-        if (d_q_out)
-            for (int m = 0; m < M; ++m)
-                detail_check_overlap("nle_apply_local", d_q_out + (size_t)m * n, d_out, n, out_kind, "d_q_out");
-        DevBuf<float> d_work((size_t)(L + M) * n);
-        // one batch over [x; s_1 .. s_M], as nle_apply_regions makes it: the L layers of x and one spread per stroke
-        std::vector<double> resp((size_t)(L + M) * f->K);
-        layer_resp(f->eigvals.data(), f->K, L, resp.data());
-        spread_resp(f, M, h_scale, spread, resp.data() + (size_t)L * f->K);
-        const float* planes[1 + NLE_REGION_MAX];
-        int nresp[1 + NLE_REGION_MAX];
-        planes[0] = d_x, nresp[0] = L;
-        for (int m = 0; m < M; ++m) planes[1 + m] = d_strokes + (size_t)m * H * W, nresp[1 + m] = 1;
-        apply_planes_impl(f, planes, 1 + M, H, W, nresp, resp.data(), d_work.p, n, false);
-        if (d_q_out)
-            HIP_OK(hipMemcpyAsync(d_q_out, d_work.p + (size_t)L * n, (size_t)M * n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
         local_combine_impl(c, d_x, d_work.p, L, d_work.p + (size_t)L * n, M, n, n, n, h_weights, h_detail, h_curve_on, h_curves,
                            floor, out_kind, d_out);
+    });
+}
+
+int nle_region_histograms(nle_ctx* ctx, const float* d_y, const float* d_q, int M, long long n, long long q_stride,
+                          const double* h_scale, const int* h_row_on, double floor, long long* h_counts) {
+    if (!ctx) return NLE_ERR_INVALID;
+    return guard(ctx, [&] {
+        if (!d_y || !d_q || !h_counts) throw Fail{NLE_ERR_INVALID, "nle_region_histograms: NULL pointer"};
+        region_hist_check("nle_region_histograms", M, h_scale, floor);
+        if (n < 1) throw Fail{NLE_ERR_INVALID, "nle_region_histograms: n must be >= 1"};
+        if (q_stride < n) throw Fail{NLE_ERR_INVALID, "nle_region_histograms: the plane stride is smaller than n"};
+        region_histograms_impl(ctx, d_y, d_q, M, n, q_stride, h_scale, h_row_on, floor, h_counts);
+    });
+}
+
+int nle_apply_local_auto(nle_filter* f, const float* d_x, int H, int W, int L, const float* d_strokes, int M,
+                         const double* h_scale, double spread, double floor, const double* h_weights, const double* h_detail,
+                         const double* h_tone, int out_kind, void* d_out, float* d_q_out, double* h_curves_out) {
+    if (!f || !f->ctx) return NLE_ERR_INVALID;
+    return guard(f->ctx, [&] {
+        nle_ctx* c = f->ctx;
+        if (!d_x || !d_strokes || !d_out || !h_tone) throw Fail{NLE_ERR_INVALID, "nle_apply_local_auto: NULL pointer"};
+        local_check("nle_apply_local_auto", L, M, h_weights, h_detail, nullptr, nullptr, floor, out_kind);
+        int curve_on[NLE_REGION_MAX + 1], hist_on[NLE_REGION_MAX + 1];
+        double hist_scale[NLE_REGION_MAX + 1];
+        bool any_curve = false, any_hist = false;
+        for (int m = 0; m <= M; ++m) {
+            const double s = h_tone[4 * m], h = h_tone[4 * m + 1], P = h_tone[4 * m + 2], A = h_tone[4 * m + 3];
+            if (const char* refused = nlek::tone_check(s, h, P, A))
+                throw Fail{NLE_ERR_INVALID, "nle_apply_local_auto: row " + std::to_string(m) + ": " + refused};
+            hist_on[m] = P >= 0 || A > 0;
+            curve_on[m] = !(s == 0 && h == 0 && P < 0 && A == 0);
+            hist_scale[m] = h_weights[(size_t)m * L + (L - 1)];
+            any_curve = any_curve || curve_on[m];
+            any_hist = any_hist || hist_on[m];
+        }
+        const DevBuf<float> d_work = local_apply_planes("nle_apply_local_auto", f, d_x, H, W, L, d_strokes, M, h_scale, spread, out_kind, d_out, d_q_out);
+        const long long n = f->n_local;  // == H W: world == 1
+        const float* d_q = d_work.p + (size_t)L * n;
+        std::vector<long long> counts(any_hist ? (size_t)(M + 1) * nlek::kToneCounts : 0);
+        if (any_hist) region_histograms_impl(c, d_work.p + (size_t)(L - 1) * n, d_q, M, n, n, hist_scale, hist_on, floor, counts.data());
+        std::vector<double> curves((size_t)(M + 1) * (NLE_TONE_KNOTS + 2), 0.0);
+        for (int m = 0; m <= M; ++m) {
+            if (!curve_on[m]) continue;
+            const double s = h_tone[4 * m], h = h_tone[4 * m + 1];
+            const long long* row = hist_on[m] ? counts.data() + (size_t)m * nlek::kToneCounts : nullptr;
+            long long mass = 0;
+            if (row) mass = std::accumulate(row, row + nlek::kToneCounts, 0ll);
+            double* cv = curves.data() + (size_t)m * (NLE_TONE_KNOTS + 2);
+            // less than one pixel's mass: the levels and the equalisation have nothing to stand on, the slopes stay
+            if (row && mass >= NLE_REGION_WEIGHT_ONE) tone_curve_impl(row, s, h, h_tone[4 * m + 2], h_tone[4 * m + 3], cv);
+            else tone_curve_impl(nullptr, s, h, -1, 0, cv);
+        }
+        if (h_curves_out) std::copy(curves.begin(), curves.end(), h_curves_out);
+        local_combine_impl(c, d_x, d_work.p, L, d_q, M, n, n, n, h_weights, h_detail, any_curve ? curve_on : nullptr,
+                           any_curve ? curves.data() : nullptr, floor, out_kind, d_out);
     });
 }
 

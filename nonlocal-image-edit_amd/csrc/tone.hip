@@ -9,6 +9,7 @@
 #include <cmath>
 #include <vector>
 
+#include "detail_rule.h"
 #include "kernels.h"
 #include "nle.h"
 
@@ -20,15 +21,6 @@ namespace nlek {
 namespace {
 
 constexpr int kHistThreads = 512, kHistMaxBlocks = 1024;
-
-__device__ __forceinline__ int tone_bin(float x, double scale) {
-    const double v = (double)x * scale;
-    const double t = (v + 256.0) * 4.0;
-    if (t != t) return kToneCounts - 1;
-    if (t < 0.0) return 0;
-    if (t >= (double)NLE_TONE_BINS) return kToneCounts - 1;
-    return 1 + (int)t;  // t >= 0: the conversion truncates to the floor
-}
 
 // One pixel per lane, b < 0 for a lane without one.  Every lane of the wave calls this together.  A run of lanes with the same
 // bin is counted once, by its first lane, with the run's length: a flat region costs one LDS atomic per wave instead of 64

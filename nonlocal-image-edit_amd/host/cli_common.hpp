@@ -64,6 +64,14 @@ struct FilterArgs {
     };
     std::vector<Local> locals;
     double saturation = 1;
+    // --local-auto ROW:levels=P[,equalise=A] (enhance only, once per row): ROW 0 the background, m the m-th --local
+    struct LocalAuto {
+        std::string text;
+        int row = 0;
+        bool hasLevels = false, hasEqualise = false;
+        double levels = -1, equalise = 0;
+    };
+    std::vector<LocalAuto> localAutos;
     bool nystromReport = false;  // --nystrom-report (enhance only)
     std::string nystromMap;      // --nystrom-map FILE (with --nystrom-report)
 };
@@ -75,8 +83,10 @@ constexpr int kEnhance = (int)Tool::Enhance, kDenoise = (int)Tool::Denoise, kBot
 // that starts with its name (and refuses it).  The numbers are finite doubles: any, > 0, >= 0, in [lo, hi], in (lo, hi];
 // Integer is a whole number in [lo, hi]; Word is one of `words`; FileName is a word that does not start with `--`; Region
 // is MASK:w1,w2,... split at the last `:`, finite weights; SegmentWeights is c:w1,w2,... likewise, c a whole number in [lo, hi].
-// Local is TARGET:key=value[,key=value...] split at the last `:`, the keys those of kLocalKeys.
-enum class Takes { Flag, FlagAnySuffix, Finite, Positive, NonNegative, Closed, HalfOpen, Integer, Word, FileName, Region, SegmentWeights, Local };
+// Local is TARGET:key=value[,key=value...] split at the last `:`, the keys those of kLocalKeys.  LocalAuto is
+// ROW:levels=P[,equalise=A], ROW a whole number in [lo, hi], either key alone allowed.
+enum class Takes { Flag, FlagAnySuffix, Finite, Positive, NonNegative, Closed, HalfOpen, Integer, Word, FileName, Region, SegmentWeights, Local,
+                   LocalAuto };
 
 struct Word {
     const char* word;
@@ -87,6 +97,7 @@ struct Value {  // a parsed value: the number (or the word's constant), the text
     std::string text;
     FilterArgs::Region region;
     FilterArgs::Local local;
+    FilterArgs::LocalAuto localAuto;
 };
 
 struct Option {
@@ -196,6 +207,12 @@ inline const Option kOptions[] = {
     {"--saturation", "the background's saturation of a and b about 128 in a local adjustment (nle::LocalEdit::saturation)", kEnhance,
      Takes::Closed, 0, NLE_LOCAL_SATURATION_MAX, nullptr, [](FilterArgs& a, const Value& v) { a.saturation = v.x; },
      "--saturation takes a finite number in [0, " NLECLI_STR(NLE_LOCAL_SATURATION_MAX) "]", kLocalElsewhere},
+    {"--local-auto", "auto levels and equalisation for one row of a local adjustment, on the row's own membership-weighted histogram "
+                     "(nle::LocalEdit::clipPercent, equalise): ROW is 0 for the background and m for the m-th --local; levels=P clips "
+                     "P percent at either end, equalise=A is the share of histogram equalisation; at least one of the two; once per "
+                     "row; one more stdout line per row",
+     kEnhance, Takes::LocalAuto, 0, NLE_REGION_MAX, nullptr, [](FilterArgs& a, const Value& v) { a.localAutos.push_back(v.localAuto); },
+     "--local-auto takes ROW:levels=P[,equalise=A] (a row number, then at least one of the two keys)", kLocalElsewhere},
     {"--prefilter", "the pre-filter of the MSE-guided denoiser (nle::DenoiseOptions)", kDenoise, Takes::Word, 0, 0, kPrefilters,
      [](FilterArgs& a, const Value& v) { a.denoise.prefilter = (int)v.x; }, "--prefilter takes 'bilateral' or 'nlm'", kDenoiseElsewhere},
     {"--glide", "shrink every plane by the power the MSE estimate picks; the positional shrink factor is the upper end of the search",
@@ -329,6 +346,52 @@ inline bool local(const std::string& v, FilterArgs::Local* r, std::string* why) 
     return true;
 }
 
+// ROW:levels=P[,equalise=A] split at the first `:`; false and *why as for local()
+inline bool local_auto(const Option& o, const std::string& v, FilterArgs::LocalAuto* r, std::string* why) {
+    const size_t colon = v.find(':');
+    if (colon == std::string::npos || colon == 0 || colon + 1 >= v.size()) return false;
+    r->text = v;
+    const Option rowTakes = {"", "", 0, Takes::Integer, o.lo, o.hi, nullptr, nullptr, "", ""};
+    double row;
+    if (!number(rowTakes, v.substr(0, colon), &row)) {
+        *why = "a row is a whole number in [0, " + std::to_string((int)o.hi) + "], 0 the background and m the m-th --local";
+        return false;
+    }
+    r->row = (int)row;
+    const Option levels = {"", "", 0, Takes::Closed, 0, 25, nullptr, nullptr, "", ""}, equalise = {"", "", 0, Takes::Closed, 0, 1, nullptr, nullptr, "", ""};
+    const std::string list = v.substr(colon + 1) + ",";
+    for (size_t p = 0, q; (q = list.find(',', p)) != std::string::npos; p = q + 1) {
+        const std::string item = list.substr(p, q - p);
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos || eq == 0) return false;
+        const std::string key = item.substr(0, eq), val = item.substr(eq + 1);
+        const bool isLevels = key == "levels";
+        if (!isLevels && key != "equalise") {
+            *why = "unknown key '" + key + "' (the keys are levels, equalise)";
+            return false;
+        }
+        bool& has = isLevels ? r->hasLevels : r->hasEqualise;
+        if (has) {
+            *why = "key '" + key + "' is given twice";
+            return false;
+        }
+        has = true;
+        if (!number(isLevels ? levels : equalise, val, isLevels ? &r->levels : &r->equalise)) {
+            *why = key + " takes a finite number in " + (isLevels ? "[0, 25]" : "[0, 1]") + ", got '" + val + "'";
+            return false;
+        }
+    }
+    return true;
+}
+
+// the row of the local adjustment's combine that --local-auto's ROW names: masks are rows in the order given, a segment
+// target @c is row c + 1
+inline int local_auto_row(const FilterArgs& a, const FilterArgs::LocalAuto& u) {
+    if (u.row == 0) return 0;
+    const FilterArgs::Local& l = a.locals[(size_t)u.row - 1];
+    return l.segment >= 0 ? l.segment + 1 : u.row;
+}
+
 // row `l` of a local adjustment (null: the background's row) as the C++ surface takes it: what the spec names, and the
 // background's for every key it does not
 inline nle::LocalEdit local_edit(const FilterArgs& a, const FilterArgs::Local* l) {
@@ -344,6 +407,14 @@ inline nle::LocalEdit local_edit(const FilterArgs& a, const FilterArgs::Local* l
     if (l->given[kLocalShadows]) e.shadows = l->value[kLocalShadows];
     if (l->given[kLocalHighlights]) e.highlights = l->value[kLocalHighlights];
     if (l->given[kLocalSaturation]) e.saturation = l->value[kLocalSaturation];
+    return e;
+}
+
+// the same with the row's --local-auto, if it has one; row: 0 the background, m the m-th --local
+inline nle::LocalEdit local_edit_row(const FilterArgs& a, int row) {
+    nle::LocalEdit e = local_edit(a, row == 0 ? nullptr : &a.locals[(size_t)row - 1]);
+    for (const auto& u : a.localAutos)
+        if (u.row == row) e.clipPercent = u.hasLevels ? u.levels : -1, e.equalise = u.hasEqualise ? u.equalise : 0;
     return e;
 }
 
@@ -385,6 +456,12 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
                 std::string why;
                 ok = local(v.text, &v.local, &why);
                 if (!ok && !why.empty()) refuse(prog, "--local " + v.text + ": " + why);
+                break;
+            }
+            case Takes::LocalAuto: {
+                std::string why;
+                ok = local_auto(*o, v.text, &v.localAuto, &why);
+                if (!ok && !why.empty()) refuse(prog, "--local-auto " + v.text + ": " + why);
                 break;
             }
             default: ok = number(*o, v.text, &v.x);
@@ -457,6 +534,17 @@ inline bool parse(int argc, char* argv[], int min_argc, FilterArgs* a, Tool tool
             if (e.detail.gain != 1 && !(e.detail.sigma > 0))
                 refuse(prog, "--local " + l.target + ": a gain other than 1 needs a sigma > 0, its own or --detail-sigma's");
         }
+    }
+    if (!a->localAutos.empty() && a->locals.empty())
+        refuse(prog, "--local-auto needs at least one --local (ROW 0 is its background, ROW m the m-th --local)");
+    for (size_t k = 0; k < a->localAutos.size(); ++k) {
+        const auto& u = a->localAutos[k];
+        if (u.row > (int)a->locals.size())
+            refuse(prog, "--local-auto " + u.text + ": there are " + std::to_string(a->locals.size() + 1) +
+                             " rows, 0 the background and m the m-th --local");
+        for (size_t j = 0; j < k; ++j)
+            if (a->localAutos[j].row == u.row)
+                refuse(prog, "--local-auto can be given once per row, row " + std::to_string(u.row) + " has two");
     }
     if ((is_given("--region-spread") || is_given("--region-floor")) && a->regions.empty() && !localMasks)
         refuse(prog, "--region-spread and --region-floor need at least one --region");

@@ -17,6 +17,9 @@
 // region -- a mask, or segment @c of `--segments C` -- the whole edit of its own (NLEFilter::enhanceLocal /
 // enhanceSegmentsLocal): weights, residual, gain, sigma, shadows, highlights, saturation; what a spec does not name is the
 // background's, which is the positional weights, the detail options, `--shadows`, `--highlights` and `--saturation`.
+// `--local-auto ROW:levels=P[,equalise=A]` lays row ROW's base curve (0 the background, m the m-th `--local`) over the row's own
+// membership-weighted histogram (nle::LocalEdit::clipPercent, equalise); each such row adds one stdout line, in ascending
+// ROW: `Tone curve: row <ROW> levels <lo> <hi>`.
 #include <algorithm>
 
 #include "cli_common.hpp"
@@ -59,13 +62,15 @@ int main(int argc, char* argv[]) {
     // the rows of a local adjustment: one per mask in the order given, or one per segment that has a spec
     std::vector<nle::LocalEdit> localEdits;
     const bool localSegments = !a.locals.empty() && a.locals[0].segment >= 0;
+    // (a segment without a spec takes the background's keys, not its --local-auto: ROW 0 is the background's row alone)
     if (localSegments) localEdits.assign((size_t)a.segments, nlecli::local_edit(a, nullptr));
-    for (const auto& l : a.locals) {
+    for (size_t k = 0; k < a.locals.size(); ++k) {
+        const auto& l = a.locals[k];
         if (localSegments) {
-            localEdits[(size_t)l.segment] = nlecli::local_edit(a, &l);
+            localEdits[(size_t)l.segment] = nlecli::local_edit_row(a, (int)k + 1);
         } else {
             if (!read_stroke("--local", l.target)) return 2;
-            localEdits.push_back(nlecli::local_edit(a, &l));
+            localEdits.push_back(nlecli::local_edit_row(a, (int)k + 1));
         }
     }
     nle::NLEFilter filter;
@@ -86,8 +91,8 @@ int main(int argc, char* argv[]) {
     }
     // (inactive detail and tone options are the plain methods; segments without weights of their own leave the plain edit)
     const nle::Image result = a.tonemap                  ? filter.toneMap(image, a.extra, a.tonemapSaturation, a.detail)
-                              : localSegments             ? filter.enhanceSegmentsLocal(image, nlecli::local_edit(a, nullptr), localEdits)
-                              : !a.locals.empty()         ? filter.enhanceLocal(image, strokes, localEdits, nlecli::local_edit(a, nullptr),
+                              : localSegments             ? filter.enhanceSegmentsLocal(image, nlecli::local_edit_row(a, 0), localEdits)
+                              : !a.locals.empty()         ? filter.enhanceLocal(image, strokes, localEdits, nlecli::local_edit_row(a, 0),
                                                                                 a.regionSpread, a.regionFloor)
                               : !a.segmentWeights.empty() ? filter.enhanceSegments(image, a.extra, segmentWeights)
                               : strokes.empty()           ? filter.enhance(image, a.extra, a.detail, a.tone)  // the weights are argv[9..]
@@ -116,6 +121,15 @@ int main(int argc, char* argv[]) {
     if (a.toneLine) {
         const nle::ToneLevels t = filter.lastToneCurve();
         std::cout << "Tone curve: levels " << t.lo << " " << t.hi << std::endl;
+    }
+    if (!a.localAutos.empty()) {  // one line per row that has --local-auto, in ascending ROW
+        const std::vector<nle::ToneLevels> levels = filter.lastLocalLevels();
+        for (int row = 0; row <= (int)a.locals.size(); ++row)
+            for (const auto& u : a.localAutos)
+                if (u.row == row) {
+                    const nle::ToneLevels t = levels.at((size_t)nlecli::local_auto_row(a, u));
+                    std::cout << "Tone curve: row " << row << " levels " << t.lo << " " << t.hi << std::endl;
+                }
     }
     if (a.nystromReport) {  // after the reference's banners: one line, and the map as an 8-bit grey image
         const nle::NLEFilter::Residual res = filter.nystromResidual(image, a.rowSamples, a.colSamples, a.hx, a.hy);

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <iostream>
+#include <numeric>
 #include <string>
 
 #include "device_group.hpp"
@@ -694,9 +695,16 @@ namespace {
 // the M + 1 rows of a local edit as nle_local_combine / nle_local_chroma take them; row 0 the background
 struct LocalRowsHost {
     int L = 0;
-    std::vector<double> weights, detail, curves, saturation;
-    std::vector<int> curveOn;
-    bool anyCurve = false, chroma = false;
+    std::vector<double> weights, detail, curves, saturation, tone;  // tone: (shadows, highlights, clipPercent, equalise) per row
+    std::vector<int> curveOn, histOn;                                // histOn: the row has auto levels or equalise
+    bool anyCurve = false, chroma = false, anyHist = false;
+    // what lastLocalLevels() returns once the curves are known: `cv` (M + 1) x (NLE_TONE_KNOTS + 2)
+    std::vector<ToneLevels> levels(const double* cv) const {
+        std::vector<ToneLevels> out(histOn.size());
+        for (size_t m = 0; m < histOn.size(); ++m)
+            if (histOn[m]) out[m].lo = cv[m * (NLE_TONE_KNOTS + 2)], out[m].hi = cv[m * (NLE_TONE_KNOTS + 2) + 1], out[m].valid = true;
+        return out;
+    }
 };
 
 LocalRowsHost local_rows(const LocalEdit& background, const std::vector<const LocalEdit*>& edits) {
@@ -719,9 +727,16 @@ LocalRowsHost local_rows(const LocalEdit& background, const std::vector<const Lo
                                      std::to_string(NLE_LOCAL_SATURATION_MAX) + "].");
         r.saturation.push_back(e.saturation);
         r.chroma = r.chroma || e.saturation != 1;
-        const bool on = !(e.shadows == 0 && e.highlights == 0);
+        if (!std::isfinite(e.clipPercent) || e.clipPercent > 25 || !std::isfinite(e.equalise) || e.equalise < 0 || e.equalise > 1)
+            throw std::runtime_error("Row " + std::to_string(m) + " of the local adjustment: clipPercent must be finite and at most 25 "
+                                     "(negative: no levels), equalise finite and in [0, 1].");
+        const bool hist = e.clipPercent >= 0 || e.equalise > 0, on = hist || !(e.shadows == 0 && e.highlights == 0);
+        r.tone.insert(r.tone.end(), {e.shadows, e.highlights, e.clipPercent, e.equalise});
+        r.histOn.push_back(hist ? 1 : 0);
+        r.anyHist = r.anyHist || hist;
         r.curveOn.push_back(on ? 1 : 0);
         r.anyCurve = r.anyCurve || on;
+        // (a row with a histogram gets its curve once the counts are known; the slopes are checked here either way)
         if (on) check(nle_tone_curve(nullptr, e.shadows, e.highlights, -1, 0, r.curves.data() + m * (NLE_TONE_KNOTS + 2)), nullptr);
     }
     return r;
@@ -767,10 +782,19 @@ Image NLEFilter::enhanceLocal(const Image& image, const std::vector<Image>& stro
     if (r.chroma) d_q = Dev(ctx_, planes.size() * 4);
     check(nle_dev_upload(ctx_, d_s.p, planes.data(), planes.size() * 4), ctx_);
     const bool deep = is_deep(image);
+    localLevels_.clear();
+    std::vector<double> curves = r.curves;
     const auto op = [&](const float* d_x, float* d_y, float* d_a, float* d_b) {
-        check(nle_apply_local(f_, d_x, image.rows, image.cols, r.L, d_s.f(), M, scale.data(), spread, floor, r.weights.data(),
-                              r.detail.data(), r.anyCurve ? r.curveOn.data() : nullptr, r.anyCurve ? r.curves.data() : nullptr,
-                              deep ? NLE_REGION_OUT_F32 : NLE_REGION_OUT_ROUNDED8, d_y, r.chroma ? d_q.f() : nullptr), ctx_);
+        if (r.anyHist) {
+            check(nle_apply_local_auto(f_, d_x, image.rows, image.cols, r.L, d_s.f(), M, scale.data(), spread, floor, r.weights.data(),
+                                       r.detail.data(), r.tone.data(), deep ? NLE_REGION_OUT_F32 : NLE_REGION_OUT_ROUNDED8, d_y,
+                                       r.chroma ? d_q.f() : nullptr, curves.data()), ctx_);
+            localLevels_ = r.levels(curves.data());
+        } else {
+            check(nle_apply_local(f_, d_x, image.rows, image.cols, r.L, d_s.f(), M, scale.data(), spread, floor, r.weights.data(),
+                                  r.detail.data(), r.anyCurve ? r.curveOn.data() : nullptr, r.anyCurve ? r.curves.data() : nullptr,
+                                  deep ? NLE_REGION_OUT_F32 : NLE_REGION_OUT_ROUNDED8, d_y, r.chroma ? d_q.f() : nullptr), ctx_);
+        }
         if (r.chroma)
             check(nle_local_chroma(ctx_, d_a, d_b, d_q.f(), M, (long long)np, (long long)np, r.saturation.data(), floor, d_a, d_b), ctx_);
     };
@@ -793,10 +817,29 @@ Image NLEFilter::enhanceSegmentsLocal(const Image& image, const LocalEdit& backg
     const long long n = (long long)image.total();
     const float* d_q = static_cast<const float*>(segmentSpreads_.get());
     Dev d_layers(ctx_, (size_t)r.L * n * 4);
+    localLevels_.clear();
+    std::vector<double> curves = r.curves;
     return edit_8bit_lab(ctx_, image, r.chroma, [&](const float* d_x, float* d_y, float* d_a, float* d_b) {
         check(nle_apply_layers(f_, d_x, image.rows, image.cols, r.L, d_layers.f()), ctx_);
+        if (r.anyHist) {  // the stage calls of nle_apply_local_auto, on the segments' spreads
+            std::vector<long long> counts((size_t)(C + 1) * (NLE_TONE_BINS + 2));
+            std::vector<double> scale((size_t)C + 1);
+            for (int m = 0; m <= C; ++m) scale[m] = r.weights[(size_t)m * r.L + (r.L - 1)];
+            check(nle_region_histograms(ctx_, d_layers.f() + (size_t)(r.L - 1) * n, d_q, C, n, n, scale.data(), r.histOn.data(),
+                                        segmentFloor_, counts.data()), ctx_);
+            for (int m = 0; m <= C; ++m) {
+                if (!r.histOn[m]) continue;
+                const long long* row = counts.data() + (size_t)m * (NLE_TONE_BINS + 2);
+                const long long mass = std::accumulate(row, row + NLE_TONE_BINS + 2, 0ll);
+                const double* tn = r.tone.data() + 4 * m;
+                // (less than one pixel's mass: the curve of the two slopes alone, which local_rows has made)
+                if (mass >= NLE_REGION_WEIGHT_ONE)
+                    check(nle_tone_curve(row, tn[0], tn[1], tn[2], tn[3], curves.data() + (size_t)m * (NLE_TONE_KNOTS + 2)), nullptr);
+            }
+            localLevels_ = r.levels(curves.data());
+        }
         check(nle_local_combine(ctx_, d_x, d_layers.f(), r.L, d_q, C, n, n, n, r.weights.data(), r.detail.data(),
-                                r.anyCurve ? r.curveOn.data() : nullptr, r.anyCurve ? r.curves.data() : nullptr, segmentFloor_,
+                                r.anyCurve ? r.curveOn.data() : nullptr, r.anyCurve ? curves.data() : nullptr, segmentFloor_,
                                 NLE_REGION_OUT_ROUNDED8, d_y), ctx_);
         if (r.chroma) check(nle_local_chroma(ctx_, d_a, d_b, d_q, C, n, n, r.saturation.data(), segmentFloor_, d_a, d_b), ctx_);
     });
