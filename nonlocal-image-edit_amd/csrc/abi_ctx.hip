@@ -64,6 +64,7 @@ void nle_ctx_destroy(nle_ctx* ctx) {
     if (ctx->d_srgb16) (void)hipFree(ctx->d_srgb16);
     for (auto e : ctx->copy_ev)
         if (e) (void)hipEventDestroy(e);
+    if (ctx->hand_ev) (void)hipEventDestroy(ctx->hand_ev);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->aux_stream) {
         (void)hipStreamSynchronize(ctx->aux_stream);

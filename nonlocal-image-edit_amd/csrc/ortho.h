@@ -65,7 +65,10 @@ struct DeviceDV {
     double *D, *Vrows;
     int ldd;
 };
-// sample-space form with the p x p products (and, where use_dev_solver says so, the solvers) on the device
+// does ortho_ss_device take the root of W_A (order q) on the device, on the ctx's second stream?  (Else on the host.)
+inline bool wa_root_on_device(const nle_ctx* c, int q) { return use_dev_solver(c->sw, q) && !c->sw.host_wa; }
+// sample-space form with the p x p products (and, where use_dev_solver says so, the solvers) on the device.  On the host
+// route of W_A's root the caller may have put the Gram kernels on the stream already: enqueue_gram is then empty
 void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std::vector<double>& sA_c,
                      const std::vector<double>& sA_r, double* d_Gk, int n_eig, const std::function<void()>& enqueue_gram,
                      const std::function<void()>& reduce_gram, double* host_ms, Trace& tr,

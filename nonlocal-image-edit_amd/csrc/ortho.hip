@@ -752,7 +752,7 @@ void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std
     scalings_Kr_P(st, o, ny, p, sA_c, sA_r, dv);
     // ---- Wa and a root F of its pseudo-inverse, beside the Gram kernels: on the host below the device solvers' order (use_dev_solver), else on the
     // device on the ctx's second stream (the Gram kernels are on the first)
-    const bool dev_wa = use_dev_solver(c->sw, q) && !c->sw.host_wa;
+    const bool dev_wa = wa_root_on_device(c, q);
     const bool force_eig = c->sw.force_eig;
     // On the device route with Ka resident there (solve_Ka's device Cholesky) Wa is formed on the device; the host copy is
     // built only if the host root has to take over.
@@ -762,7 +762,7 @@ void ortho_ss_device(nle_ctx* c, OrthoSS& o, const Nystrom& ny, int p, const std
     WaDeviceWork ws;
     if (dev_wa)
         wa_root_device(c, o, ny, dv, d_Wa.p, force_eig, enqueue_gram, ws, w, tr);
-    else
+    else if (enqueue_gram)
         enqueue_gram();
     if (!w.on_device) wa_root_host(o, !dev_wa, force_eig, w, tr);
     o.r_wa = w.r_wa;

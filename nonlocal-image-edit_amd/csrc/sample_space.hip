@@ -61,6 +61,7 @@ struct SampleSinkhorn {
     // sample row sums V_A u of the scaling that defines the final c (input of the last pass) and of the output of the
     // last pass (the r scaling): complete once the stream is drained after run()
     std::vector<double> sA_c, sA_r;
+    double* h_sA = nullptr;  // run(defer): the two, staged (page-locked) until fetch_row_sums()
 
     SampleSinkhorn(nle_ctx* c_, int p_, int zld_, int T_)
         : c(c_), p(p_), T(T_), zld(zld_), d_w(zld_), d_sAh((size_t)2 * T_ * p_), d_uv((size_t)3 * p_) {
@@ -69,7 +70,11 @@ struct SampleSinkhorn {
 
     // `solve` factors Ka on the host (solve_Ka); it is called only after the first pass -- the column sum, which needs
     // nothing of it -- is on the stream, so the factorisation runs under that pass.
-    Nystrom run(const SolveKa& solve, const std::function<void(int, bool)>& pass_pixels, double* d_z, int zrows) {
+    // `defer` (single rank, W_A's root on the host: train_tables): sA_c and sA_r go to the ctx's staging block with the
+    // hand-over event behind them instead, so that the caller can queue the Gram stage before it waits -- for the event
+    // alone, in fetch_row_sums().  Without room in the staging block the copies are today's.
+    Nystrom run(const SolveKa& solve, const std::function<void(int, bool)>& pass_pixels, double* d_z, int zrows,
+                bool defer = false) {
         pass_pixels(nlek::ROWPASS_COLSUM, false);
         Nystrom ny = solve();
         build_update_operands(c, ny, p, d_X1, d_X2, d_lam);
@@ -89,11 +94,28 @@ struct SampleSinkhorn {
         // processes sharing one GPU stall for tens of milliseconds per all-reduce: one stream per ctx it stays.)
         sA_c.resize(p);
         sA_r.resize(p);
+        // (Cholesky form of Ka only: the other uploads V_A and waits for Kr ahead of the Gram kernels, ortho.hip)
+        if (defer && ny.chol && !wa_root_on_device(c, ny.r)) h_sA = static_cast<double*>(pinned_take(c, (size_t)2 * p * sizeof(double)));
+        if (h_sA) {  // the two vectors are neighbours in d_sAh: one copy
+            HIP_OK(hipMemcpyAsync(h_sA, d_sAh.p + (size_t)(2 * T - 2) * p, (size_t)2 * p * sizeof(double), hipMemcpyDeviceToHost,
+                                  c->stream));
+            HIP_OK(hipEventRecord(handover_event(c), c->stream));
+            return ny;
+        }
         HIP_OK(hipMemcpyAsync(sA_c.data(), d_sAh.p + (size_t)(2 * T - 2) * p, p * sizeof(double), hipMemcpyDeviceToHost,
                               c->stream));
         HIP_OK(hipMemcpyAsync(sA_r.data(), d_sAh.p + (size_t)(2 * T - 1) * p, p * sizeof(double), hipMemcpyDeviceToHost,
                               c->stream));
         return ny;
+    }
+
+    bool deferred() const { return h_sA != nullptr; }
+    // deferred: wait for the staged copy -- not for what the caller has queued behind it -- and take the two vectors
+    void fetch_row_sums() {
+        handover_wait(c->hand_ev);
+        std::copy(h_sA, h_sA + p, sA_c.begin());
+        std::copy(h_sA + p, h_sA + 2 * p, sA_r.begin());
+        h_sA = nullptr;
     }
 };
 
@@ -212,12 +234,18 @@ void TrainPath::train_tables(const SolveKa& solve) {
         ProfObserver obs(c, kProfTablePass);
         HIP_OK(nlek::sink_hist_tiled(c->stream, mode, view, sk.d_w.p, NLE_EPS, last ? t->c.p : nullptr, d_hws.p, d_z.p, &obs));
     };
-    const Nystrom ny = sk.run(solve, pass_pixels, d_z.p, 1);
+    // Single rank with the full eigensolve of Q: neither the Gram kernels nor the reduce half read anything the host computes
+    // after the last pass, so they are queued before the host waits for the last pass's row sums (run(defer); the host
+    // route of W_A's root only) -- every launch the host makes in front of that root is on the critical path.
+    const Nystrom ny = sk.run(solve, pass_pixels, d_z.p, 1, /*defer=*/c->world == 1 && !c->comm && c->topk_solver == 0);
+    const bool gram_first = sk.deferred();
     adopt_nystrom(f, ny, NLE_MODE_PHI_FREE);
     tm_s.stop();
     tr.mark("ss: passes enqueued");
-    HIP_OK(hipStreamSynchronize(c->stream));
-    tr.mark("ss: sinkhorn sync");
+    if (!gram_first) {
+        HIP_OK(hipStreamSynchronize(c->stream));
+        tr.mark("ss: sinkhorn sync");
+    }
 
     // Gram in sample space: histogram + fp64 GEMM over the look-up tables (k_ghist_*), enqueued; the host half that does
     // not need it runs meanwhile
@@ -256,12 +284,19 @@ void TrainPath::train_tables(const SolveKa& solve) {
         HIP_OK(hipMemsetAsync(t->Vrows.p, 0, n * sizeof(double), c->stream));
         return DeviceDV{t->D.p, t->Vrows.p, t->ldd};
     };
+    if (gram_first) {
+        enqueue_gram();
+        tr.mark("ss: gram enqueued");
+        sk.fetch_row_sums();
+        tr.mark("ss: sinkhorn sync");
+    }
     OrthoSS o;  // (outlives the last synchronisation below: o.staged)
     if (c->topk_solver == 0) {
         // the q-sized products run on the device, the eigensolves on the host; D and Vrows are written where apply reads
         // them and never visit the host
-        ortho_ss_device(c, o, ny, p, sk.sA_c, sk.sA_r, d_G.p, n_eig, enqueue_gram, [&] { all_reduce(c, d_G.p, g_elems); },
-                        host_ms, tr, place);
+        ortho_ss_device(c, o, ny, p, sk.sA_c, sk.sA_r, d_G.p, n_eig,
+                        gram_first ? std::function<void()>() : std::function<void()>(enqueue_gram),
+                        [&] { all_reduce(c, d_G.p, g_elems); }, host_ms, tr, place);
         tm_g.stop();
     } else {
         o = ortho_ss_host(c, ny, p, sk, enqueue_gram, d_G.p, g_elems, /*tile16=*/false, n_eig, tm_g, host_ms, tr);
